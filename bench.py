@@ -37,6 +37,7 @@ sys.path.insert(0, ROOT)
 
 SEED, SEED2, SEED3 = 0x5EED0001, 0x5EED0002, 0x5EED0003
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BYTES = 60_000_000  # --dump-outputs: all .npy files together stay below 64 MB
 
 
 def splitmix64(x):
@@ -273,6 +274,18 @@ def other_workloads(F, torch, dev):
     return res
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each device tensor as out_dir/<name>.npy in float64 (exact: every value is below 2^53).  An array
+    longer than its share of DUMP_BYTES is cut to a sample at sorted positions drawn with SEED3, the same in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // (8 * len(arrays)) - 16     # 16 float64 of room for each file's .npy header
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float64)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(SEED3).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def measured_traffic(m, n, kernel):
     """HBM bytes per launch of the scan kernel from the committed rocprofv3 PMC passes (profiles/, collected as
     MI355X_MICROARCH.md prescribes: separate --pmc passes, KiB units, FETCH_SIZE doubled on gfx950); None when no pass
@@ -304,7 +317,11 @@ def main():
     ap.add_argument("--replicated-index", action="store_true", help="N>1: every rank builds the whole index (column shards) instead of one key range of it")
     ap.add_argument("--backend", default="nccl", help="nccl (RCCL, default) | gloo (debug: several ranks on one GPU)")
     ap.add_argument("--serial-sweep", action="store_true", help="debug: run the sweep of a step before the next step starts (no second stream)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (f and the "
+                                                          "block boundaries, rank 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -475,6 +492,8 @@ def main():
         dt = float(tmax.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"f": d_fs[state["step"] & 1], "boundaries": d_b[:state["blocks"]]})
         ms_per_step = 1e3 * dt / args.steps
         # the extension scan is k_rank_scan (rank order, inside the index build) for gap-free MSAs,
         # k_scan_stream (text order) otherwise; one launch per step either way
