@@ -183,6 +183,7 @@ static const OptKey g_opt_keys[] = {
     {"dp_literal", &FbgOptions::dp_literal}, {"dp_wave", &FbgOptions::dp_wave}, {"dp_safe_window", &FbgOptions::dp_safe_window},
     {"dp_tile", &FbgOptions::dp_tile}, {"pure_scan", &FbgOptions::pure_scan}, {"gapped_rank", &FbgOptions::gapped_rank}, {"part_tricks_off", &FbgOptions::part_tricks_off}, {"msd_sample_bins", &FbgOptions::msd_sample_bins}, {"msd_min_force", &FbgOptions::msd_min_force}, {"msd_probe", &FbgOptions::msd_probe}, {"msd_xcd", &FbgOptions::msd_xcd}, {"rank_no_lean", &FbgOptions::rank_no_lean}, {"no_stream_upload", &FbgOptions::no_stream_upload},
     {"span_scan", &FbgOptions::span_scan}, {"span_key_flags", &FbgOptions::span_key_flags}, {"span_slow_split", &FbgOptions::span_slow_split}, {"poison", &FbgOptions::poison}, {"dpw_matrix", &FbgOptions::dpw_matrix}, {"dp_chain1", &FbgOptions::dp_chain1},
+    {"msd_ext", &FbgOptions::msd_ext},
 };
 
 // The one place the library reads the environment: FBG_DEBUG_ENV=1 lets FBG_<KEY>=<integer> preset the options of
@@ -219,6 +220,8 @@ int fbg_get_option(const fbg_ctx *ctx, const char *key, int64_t *value)
     if (strcmp(key, "dp_kind") == 0) { *value = ctx->dp_kind; return FBG_OK; }
     if (strcmp(key, "msd_decline") == 0) { *value = ctx->msd_decline; return FBG_OK; }
     if (strcmp(key, "pass1_ahead") == 0) { *value = ctx->pass1_ahead; return FBG_OK; }
+    if (strcmp(key, "ext_pairs") == 0) { *value = ctx->ext_pairs; return FBG_OK; }
+    if (strcmp(key, "text_pairs") == 0) { *value = ctx->text_pairs; return FBG_OK; }
     if (strcmp(key, "alloc_calls") == 0) { *value = (int64_t)ctx->alloc_calls; return FBG_OK; }
     if (strcmp(key, "alloc_us") == 0) { *value = (int64_t)ctx->alloc_us; return FBG_OK; }
     if (strcmp(key, "span_decline") == 0) { *value = ctx->sp_decline; return FBG_OK; }
@@ -286,7 +289,7 @@ void fbg_ctx_destroy(fbg_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     DevBuf *bufs[] = {&ctx->msa_own, &ctx->text, &ctx->pos, &ctx->tot, &ctx->segtab, &ctx->exc_scratch, &ctx->prow, &ctx->igrow, &ctx->rec,
                       &ctx->xlist, &ctx->gmax, &ctx->excol, &ctx->xslot, &ctx->xbits, &ctx->exc, &ctx->colT, &ctx->keysA, &ctx->keysB, &ctx->valsA, &ctx->valsB, &ctx->grp, &ctx->flags,
-                      &ctx->list, &ctx->tie_list, &ctx->big_groups, &ctx->kargs, &ctx->msd_w, &ctx->msd_v, &ctx->tmp, &ctx->small, &ctx->scalars, &ctx->dp_a, &ctx->dp_b, &ctx->dp_c,
+                      &ctx->msd_ext, &ctx->list, &ctx->tie_list, &ctx->big_groups, &ctx->kargs, &ctx->msd_w, &ctx->msd_v, &ctx->tmp, &ctx->small, &ctx->scalars, &ctx->dp_a, &ctx->dp_b, &ctx->dp_c,
                       &ctx->dp_d, &ctx->dp_e, &ctx->dp_f, &ctx->dp_g, &ctx->dp_h, &ctx->io_a, &ctx->io_b,
                       &ctx->io_c, &ctx->io_d, &ctx->bt_up, &ctx->bt_dep, &ctx->ps_a, &ctx->ps_b, &ctx->ps_c, &ctx->ps_d,
                       &ctx->ps_e, &ctx->ps_f, &ctx->ps_g, &ctx->ps_h, &ctx->gwin, &ctx->gbits, &ctx->gwin_rows,
@@ -355,7 +358,7 @@ int fbg_release_scratch(fbg_ctx *ctx)
     FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // valsB stays: it is the suffix array; so does whichever key buffer holds the sorted slots of a rank-order index
     const bool sorted_in_A = (ctx->ranked || ctx->granked) && ctx->rk_keys == ctx->keysA.as<uint64_t>();
-    DevBuf *bufs[] = {sorted_in_A ? &ctx->keysB : &ctx->keysA, &ctx->valsA, &ctx->grp, &ctx->flags, &ctx->list, &ctx->tie_list, &ctx->msd_w, &ctx->msd_v,
+    DevBuf *bufs[] = {sorted_in_A ? &ctx->keysB : &ctx->keysA, &ctx->valsA, &ctx->grp, &ctx->flags, &ctx->list, &ctx->tie_list, &ctx->msd_w, &ctx->msd_v, &ctx->msd_ext,
                       &ctx->tmp, &ctx->dp_a, &ctx->dp_b, &ctx->dp_c, &ctx->dp_d, &ctx->dp_e, &ctx->dp_f,
                       &ctx->dp_g, &ctx->dp_h, &ctx->ps_a, &ctx->ps_b, &ctx->ps_c, &ctx->ps_d, &ctx->ps_e, &ctx->ps_f,
                       &ctx->ps_g, &ctx->ps_h, &ctx->sp_cells, &ctx->sp_flagT, &ctx->sp_tiles};

@@ -38,7 +38,7 @@ struct FbgOptions {
     int64_t no_ranked = 0, no_packed = 0, force_wide = 0, full_keys = 0, no_msd_sort = 0, msd_min = -1, bp_min = -1,
             record_scatter = 0, lcp_text = 0, no_aux_stream = 0, rank_no_threshold = 0, dp_literal = 0, dp_wave = 0,
             dp_safe_window = 0, dp_tile = 0, pure_scan = 0, gapped_rank = 0, part_tricks_off = 0, msd_sample_bins = 0, msd_min_force = 0, msd_probe = 0, msd_xcd = -1, rank_no_lean = 0, no_stream_upload = 0,
-            span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0;
+            span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0, msd_ext = 1;
 };
 
 struct fbg_ctx {
@@ -69,6 +69,8 @@ struct fbg_ctx {
     alignas(16) unsigned char pre_state[768]; // KeyGeom + the sort's arguments between fbg_msd_pre_begin and fbg_msd_sort
     uint64_t pre_tiles = 0;                    // tiles of pass 1 launched so far
     int pass1_ahead = 0;                       // the last MSD sort found its pass 1 done (fbg_get_option "pass1_ahead")
+    bool msd_ext_valid = false;                // msd_ext holds the 4 symbols after the key of every slot the last MSD sort sorted
+    int64_t ext_pairs = -1, text_pairs = -1;   // the last rank-order scan: tied pairs settled by those symbols / by the text
 
     // index state
     bool index_valid = false;
@@ -142,6 +144,7 @@ struct fbg_ctx {
 
     // scratch
     DevBuf keysA, keysB, valsA, valsB, grp, flags, list, tie_list, big_groups, tmp, small, scalars;
+    DevBuf msd_ext;            // 1 byte per SA slot: symbols K .. K+3 of its suffix (msd_sort.hip, 2-bit symbols)
     DevBuf kargs;              // arguments a kernel reads from memory (k_rank_scan_lean) ...
     alignas(16) unsigned char kargs_host[512];   // ... and the host copy they are sent from
     DevBuf msd_w, msd_v;       // sub-bucket stretches of the MSD sort of 12-byte slots (msd_sort_pairs.hip)

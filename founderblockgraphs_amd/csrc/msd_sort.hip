@@ -18,7 +18,16 @@
 // 8 (text) + 8 + 16 + 16 = 48 bytes of traffic per suffix on paper (a little more for the gaps between buckets).
 // The fixed capacities are an optimistic bet on keys that spread evenly (dissimilar rows -- the only inputs that come
 // here, see sample_says_similar); a bucket or sub-bucket that overflows raises a flag and the caller sorts with
-// rocPRIM instead (suffix_sort.hip).  Equal keys end up in position order.
+// rocPRIM instead (suffix_sort.hip).
+//
+// Extra symbols (2-bit symbols, option msd_ext): the bucket of pass 1 implies the top 9 key bits of its slots, so pass 1
+// stores a slot without the key's first 4 symbols and with the 4 symbols after the key instead -- symbols 4 .. K+3 and the
+// position, still one word.  Passes 2 and 3 sort these words (digit shifts 8 bits lower); pass 3 knows its sub-bucket, i.e.
+// the top 18 key bits, and writes the canonical word key << pb | position back, and next to it one byte per slot: symbols
+// K .. K+3 of the suffix, in SA order (ctx->msd_ext).  The rank-order scan settles most tied pairs from those bytes instead
+// of two random text reads (rank_scan.hip, k_tie_pairs).  Slots with equal keys leave ordered by the extra symbols where
+// the finish compares words, in arrival order in its crowded bins: nothing downstream depends on the order of equal keys
+// (the tie groups are put in text order by the scan, or are pure groups of one column whose order does not matter).
 #include "fbg_internal.h"
 #include "msd_keys.h"
 #include <rocprim/rocprim.hpp>
@@ -29,6 +38,10 @@
 #define MSD_NB (1 << MSD_DIG)
 #define MSD_THREADS 1024
 #define MSD_TILE (MSD_THREADS * MSD_ITEMS)
+#define MSD_TILE_BITS 13                       // log2(MSD_TILE)
+#define MSD_XSYM 4                             // extra symbols carried by the words of the sort (2-bit symbols: 8 bits)
+#define MSD_XBITS 8
+static_assert(MSD_TILE == 1 << MSD_TILE_BITS, "tile size");
 #define MSD_FN_THREADS 512
 #define MSD_FN_CAP 4096                        // slots per sub-bucket stretch (mean at 10^9 suffixes: 3815; the few that overflow: arena)
 #define MSD_FN_ITEMS (MSD_FN_CAP / MSD_FN_THREADS)
@@ -43,6 +56,8 @@ struct MsdArgs {
     uint64_t N;
     const uint8_t *code;
     int b, K, pb, kb;                          // bits per symbol, symbols per key, position bits, key bits
+    int xb;                                    // MSD_XBITS: the words carry the extra symbols (see the head of this file); 0: canonical words
+    uint8_t *ext;                              // xb != 0: pass 3's bytes of extra symbols, in SA order
     uint64_t *buf1;                            // pass 1 output: MSD_NB stretches of cap1 slots
     uint64_t cap1;
     int xs;                                    // stretches per bucket (1, or 8: one per XCD, see k_msd_pack_split), segcap = cap1 / xs slots each
@@ -87,8 +102,10 @@ __device__ __forceinline__ void msd_scan_and_reserve(uint32_t *cnt, uint32_t *lo
     __syncthreads();
 }
 
-// FULL: every position of the tile lies inside the text (all tiles but the last one): none of the per-slot checks
-template <bool FULL>
+// FULL: every position of the tile lies inside the text (all tiles but the last one): none of the per-slot checks.
+// EXT: keys of K + MSD_XSYM symbols; LDS holds key << MSD_TILE_BITS | place in the tile (the bucket stays readable there),
+// the stored word is symbols MSD_XSYM .. K + MSD_XSYM - 1 and the position
+template <bool FULL, bool EXT>
 __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *buf, const uint8_t *cd, uint32_t *cnt, uint32_t *loff, uint32_t *gdelta,
                                                     uint32_t *wsum)
 {
@@ -100,16 +117,16 @@ __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *
     // keys of the thread's MSD_ITEMS consecutive positions
     const int t0 = threadIdx.x * MSD_ITEMS;
     uint64_t w[MSD_ITEMS];
-    msd_build_keys(tile, t0, b, K, w);
+    msd_build_keys(tile, t0, b, EXT ? K + MSD_XSYM : K, w);
     __syncthreads();                                            // the byte tile is done with: buf is free
     uint32_t rk[MSD_ITEMS];
-    const int dshift = a.kb - MSD_DIG;
+    const int dshift = a.kb + (EXT ? MSD_XBITS : 0) - MSD_DIG;
 #pragma unroll
     for (int i = 0; i < MSD_ITEMS; i++) {
         const uint64_t p = base + t0 + i;
         const bool ok = FULL || p < a.N;
         rk[i] = ok ? atomicAdd(&cnt[(uint32_t)(w[i] >> dshift)], 1u) : 0xffffffffu;
-        w[i] = (w[i] << a.pb) | p;
+        w[i] = EXT ? (w[i] << MSD_TILE_BITS) | (uint64_t)(t0 + i) : (w[i] << a.pb) | p;
     }
     __syncthreads();
     // Workgroups b and b + 8 run on the same XCD (dispatch deals them round-robin).  With one stretch per (bucket, XCD)
@@ -117,7 +134,8 @@ __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *
     // 128-byte lines before they leave for HBM; runs of different XCDs leave every line they share twice, in parts.
     const uint32_t xq = a.xs > 1 ? (blockIdx.x & (uint32_t)(a.xs - 1)) : 0u;
     msd_scan_and_reserve(cnt, loff, gdelta, wsum, a.count1 + (threadIdx.x < MSD_NB ? threadIdx.x * a.xs + xq : 0), true, nullptr);
-    const int wshift = a.pb + dshift;
+    const int wshift = (EXT ? MSD_TILE_BITS : a.pb) + dshift;
+    const uint64_t kmask = (1ull << a.kb) - 1;
     uint64_t *const obase = a.buf1 + xq * a.segcap;
 #pragma unroll
     for (int i = 0; i < MSD_ITEMS; i++)
@@ -129,8 +147,9 @@ __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *
     for (int r = 0; r < MSD_ITEMS; r++) {
         const uint32_t j = threadIdx.x + r * MSD_THREADS;
         if (FULL || j < have) {
-            const uint64_t x = buf[j];
+            uint64_t x = buf[j];
             const uint32_t d = (uint32_t)(x >> wshift);
+            if (EXT) x = (((x >> MSD_TILE_BITS) & kmask) << a.pb) | (base + (x & (MSD_TILE - 1)));
             const uint32_t at = j + gdelta[d];                  // below 2^32: the host checks cap1 + N
             if (at < a.segcap) obase[(uint64_t)d * a.cap1 + at] = x;
             else over = true;
@@ -139,6 +158,7 @@ __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *
     if (over) atomicOr(a.flag, 2ull);
 }
 
+template <bool EXT>
 __global__ __launch_bounds__(MSD_THREADS) void k_msd_pack_split(MsdArgs a)
 {
     __shared__ uint64_t buf[MSD_TILE];         // first the symbol codes of the tile (bytes), then the regrouped slots
@@ -151,7 +171,13 @@ __global__ __launch_bounds__(MSD_THREADS) void k_msd_pack_split(MsdArgs a)
     __syncthreads();
     // (a body without the end-of-text checks for the tiles inside the text is slower here: 3.35 against 3.12 ms, same box,
     // where the same specialisation takes a sixth off pass 2; not taken)
-    msd_pack_split_body<false>(a, buf, cd, cnt, loff, gdelta, wsum);
+    msd_pack_split_body<false, EXT>(a, buf, cd, cnt, loff, gdelta, wsum);
+}
+
+static void msd_launch_pass1(const MsdArgs &a, unsigned tiles, hipStream_t st)
+{
+    if (a.xb) hipLaunchKernelGGL(k_msd_pack_split<true>, dim3(tiles), dim3(MSD_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k_msd_pack_split<false>, dim3(tiles), dim3(MSD_THREADS), 0, st, a);
 }
 
 // first tile of every stretch of pass 1 (one workgroup of 1024 threads; nseg <= 4096 stretches, four per thread)
@@ -193,7 +219,7 @@ template <bool FULL>
 __device__ __forceinline__ void msd_split_body(const MsdArgs &a, uint64_t *buf, uint32_t *cnt, uint32_t *loff, uint32_t *gdelta, uint32_t *wsum,
                                                const uint64_t *__restrict__ in, uint32_t have, uint32_t seg)
 {
-    const int wshift = a.pb + a.kb - 2 * MSD_DIG;
+    const int wshift = a.pb + a.kb - 2 * MSD_DIG + a.xb;
     uint64_t w[MSD_ITEMS];
     uint32_t rk[MSD_ITEMS];
 #pragma unroll
@@ -399,10 +425,11 @@ __device__ __forceinline__ void msd_finish_sort(uint64_t *buf, uint32_t *cnt, ui
     __syncthreads();
 }
 
-// `have` slots (the first n_a from in_a, the rest from in_b) -> out, sorted
+// `have` slots (the first n_a from in_a, the rest from in_b) of sub-bucket sb -> a.out + a.off[sb], sorted; words with extra
+// symbols (a.xb) leave as canonical words, their extra symbols as bytes to a.ext + a.off[sb]
 template <int CAP, int THREADS>
-__device__ __forceinline__ void msd_finish_body(uint64_t *buf, uint32_t *cnt, uint32_t *loff, uint32_t *wsum, const uint64_t *in_a,
-                                                uint32_t n_a, const uint64_t *in_b, uint32_t have, uint64_t *out, int fshift,
+__device__ __forceinline__ void msd_finish_body(const MsdArgs &a, uint32_t sb, uint64_t *buf, uint32_t *cnt, uint32_t *loff, uint32_t *wsum,
+                                                const uint64_t *in_a, uint32_t n_a, const uint64_t *in_b, uint32_t have, int fshift,
                                                 uint32_t fmask, int lowbits, uint32_t *sub, uint16_t *biglist, uint32_t *nbig_lds)
 {
     constexpr int ITEMS = CAP / THREADS;
@@ -413,6 +440,24 @@ __device__ __forceinline__ void msd_finish_body(uint64_t *buf, uint32_t *cnt, ui
         w[r] = j < have ? (j < n_a ? in_a[j] : in_b[j - n_a]) : ~0ull;
     }
     msd_finish_sort<CAP, THREADS>(buf, cnt, loff, wsum, w, have, fshift, fmask, lowbits, sub, biglist, nbig_lds);
+    const uint64_t o = a.off[sb];
+    uint64_t *const out = a.out + o;
+    if (a.xb) {
+        // the sub-bucket is the top 2 * MSD_DIG key bits; the word holds the rest of the key, the extra symbols, the position
+        const int rest = a.kb - 2 * MSD_DIG, pb = a.pb;
+        const uint64_t top = (uint64_t)sb << (pb + rest), rmask = (1ull << rest) - 1, pmask = (1ull << pb) - 1;
+        uint8_t *const ext = a.ext + o;
+#pragma unroll
+        for (int r = 0; r < ITEMS; r++) {
+            const uint32_t j = threadIdx.x + r * THREADS;
+            if (j < have) {
+                const uint64_t y = buf[j];
+                out[j] = top | (((y >> (pb + MSD_XBITS)) & rmask) << pb) | (y & pmask);
+                ext[j] = (uint8_t)(y >> pb);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < ITEMS; r++) {
         const uint32_t j = threadIdx.x + r * THREADS;
@@ -431,8 +476,8 @@ __global__ __launch_bounds__(MSD_FN_THREADS) void k_msd_finish(MsdArgs a, int fs
     const uint32_t have = a.count2[blockIdx.x];
     if (have == 0 || have > MSD_FN_CAP) return;                // the larger ones: k_msd_finish_big
     const uint64_t *in = a.buf2 + (uint64_t)blockIdx.x * MSD_FN_CAP;
-    msd_finish_body<MSD_FN_CAP, MSD_FN_THREADS>(buf, cnt, loff, wsum, in, have, in, have, a.out + a.off[blockIdx.x], fshift, fmask,
-                                                fshift - a.pb, sub, biglist, &nbig_lds);
+    msd_finish_body<MSD_FN_CAP, MSD_FN_THREADS>(a, blockIdx.x, buf, cnt, loff, wsum, in, have, in, have, fshift, fmask,
+                                                fshift - a.pb - a.xb, sub, biglist, &nbig_lds);
 }
 
 // sub-buckets whose stretch overflowed: the arena (sorted by sub-bucket) holds the slots beyond MSD_FN_CAP.  One
@@ -453,8 +498,8 @@ __global__ __launch_bounds__(MSD_BIG_THREADS) void k_msd_finish_big(MsdArgs a, c
     if (e > 0 && sb_sorted[e - 1] == sb) return;
     const uint32_t have = a.count2[sb];
     if (have > MSD_BIG_CAP || have <= MSD_FN_CAP) { if (threadIdx.x == 0) atomicOr(a.flag, 16ull); return; }
-    msd_finish_body<MSD_BIG_CAP, MSD_BIG_THREADS>(buf, cnt, loff, wsum, a.buf2 + (uint64_t)sb * MSD_FN_CAP, MSD_FN_CAP, w_sorted + e, have,
-                                                  a.out + a.off[sb], fshift, fmask, fshift - a.pb, sub, biglist, &nbig_lds);
+    msd_finish_body<MSD_BIG_CAP, MSD_BIG_THREADS>(a, sb, buf, cnt, loff, wsum, a.buf2 + (uint64_t)sb * MSD_FN_CAP, MSD_FN_CAP, w_sorted + e,
+                                                  have, fshift, fmask, fshift - a.pb - a.xb, sub, biglist, &nbig_lds);
 }
 
 // Sorts the packed slots of the current text by their key bits.  *ok = 0: a capacity was exceeded (keys spread
@@ -501,9 +546,13 @@ static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
     FBG_TRY(fbg_reserve(ctx, ctx->dp_c, (nsub + 1) * 8));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_d, (size_t)MSD_ARENA * 4 * 2));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_e, (size_t)MSD_ARENA * 8 * 2));
+    // extra symbols: 2-bit symbols (the bucket implies 9 key bits, they stand for 8), and LDS room for key and place in pass 1
+    const bool ext = ctx->opt.msd_ext != 0 && g.b == 2 && g.key_bits + MSD_XBITS + MSD_TILE_BITS <= 64 && g.K + MSD_XSYM + MSD_ITEMS - 1 <= 64;
+    if (ext) FBG_TRY(fbg_reserve(ctx, ctx->msd_ext, (size_t)N));
     unsigned long long *flag = ctx->scalars.as<unsigned long long>() + 100;
     MsdArgs &a = p->a;
     a.T = ctx->text.as<uint8_t>(); a.N = N; a.code = g.d_code; a.b = g.b; a.K = g.K; a.pb = g.pb; a.kb = g.key_bits;
+    a.xb = ext ? MSD_XBITS : 0; a.ext = ext ? ctx->msd_ext.as<uint8_t>() : nullptr;
     a.buf1 = ctx->keysA.as<uint64_t>(); a.cap1 = cap1; a.xs = xs; a.segcap = cap1 / xs;
     a.tile0 = 0; a.tiles2 = 0; a.tiles2_x = 0;
     a.count1 = ctx->dp_a.as<unsigned long long>();
@@ -555,7 +604,7 @@ int fbg_msd_pre_pass1(fbg_ctx *ctx, uint64_t avail)
     const uint64_t upto = avail >= N ? (N + MSD_TILE - 1) / MSD_TILE : (avail >= 64 ? (avail - 64) / MSD_TILE : 0);
     if (upto <= ctx->pre_tiles) return FBG_OK;
     plan.a.tile0 = ctx->pre_tiles;
-    hipLaunchKernelGGL(k_msd_pack_split, dim3((unsigned)(upto - ctx->pre_tiles)), dim3(MSD_THREADS), 0, ctx->stream, plan.a);
+    msd_launch_pass1(plan.a, (unsigned)(upto - ctx->pre_tiles), ctx->stream);
     ctx->pre_tiles = upto;
     return FBG_OK;
 }
@@ -573,6 +622,7 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
 {
     *ok = 0;
     ctx->msd_decline = 1;                                       // the geometry does not suit this sort
+    ctx->msd_ext_valid = false;
     const uint64_t N = ctx->N;
     hipStream_t st = ctx->stream;
     MsdPlan plan;
@@ -593,7 +643,7 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
     unsigned long long *off = plan.off, *flag = plan.flag;
     if (!ahead) {
         FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_SORT_PASS1));
-        hipLaunchKernelGGL(k_msd_pack_split, dim3(fbg_blocks(N, MSD_TILE)), dim3(MSD_THREADS), 0, st, a);
+        msd_launch_pass1(a, fbg_blocks(N, MSD_TILE), st);
         FBG_TRY(fbg_stage_end(ctx, FBG_STAGE_SORT_PASS1, 1));
     }
     hipLaunchKernelGGL(k_msd_tiles, dim3(1), dim3(1024), 0, st, a.count1, a.segcap, nseg, tile_start, flag);
@@ -623,7 +673,7 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
         e = rocprim::exclusive_scan(ctx->tmp.p, have, wide, off, 0ull, (size_t)nsub, rocprim::plus<unsigned long long>(), st);
         if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim exclusive_scan: %s", hipGetErrorString(e));
     }
-    const int fshift = g.pb + rest - fbits;
+    const int fshift = g.pb + a.xb + rest - fbits;
     const uint32_t fmask = (uint32_t)((1u << fbits) - 1);
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_SORT_PASS3));
     hipLaunchKernelGGL(k_msd_finish, dim3((unsigned)nsub), dim3(MSD_FN_THREADS), 0, st, a, fshift, fmask);
@@ -656,6 +706,7 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
     }
     FBG_HIP_TRY(ctx, hipGetLastError());
     *sorted = ctx->keysA.as<uint64_t>();
+    ctx->msd_ext_valid = a.xb != 0;
     *ok = 1;
     return FBG_OK;
 }

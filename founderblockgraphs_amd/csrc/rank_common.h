@@ -40,6 +40,9 @@ struct RankArgs {
     uint32_t *tie_count;
     uint32_t tie_region;
     uint2 *pairs;              // k_rank_scan_lean: the two text positions of every simple tied pair, same per-workgroup regions (k_tie_pairs)
+    int pair_codes;            // 1: bits 30-31 of pairs[].x and bit 30 of .y hold the pair's code: 0..3 its members agree on that many
+                               // symbols after the key and differ in the next one; 4 they agree on all 4 (msd_ext, positions below 2^30)
+    unsigned long long *pair_stats;   // k_tie_pairs: [0] += pairs settled by their code, [1] += pairs settled by the text
     uint32_t *pair_count;
     uint32_t *pm;              // scratch parallel to cand: prefix minima of the forward walk
     uint32_t *big;             // tie groups too long for one thread: (head slot, size) pairs, counters[5] of them
@@ -264,7 +267,8 @@ static inline void rs_args_init(fbg_ctx *ctx, RankArgs &a, uint64_t *keys, uint3
     a.b = b; a.key_bits = key_bits; a.K = K; a.reversed = ctx->reversed;
     a.gmax = ctx->gmax.as<uint32_t>();
     a.cand = nullptr; a.pm = nullptr; a.blk_count = nullptr; a.region = 0;
-    a.ties = nullptr; a.tie_count = nullptr; a.tie_region = 0; a.pairs = nullptr; a.pair_count = nullptr;
+    a.ties = nullptr; a.tie_count = nullptr; a.tie_region = 0; a.pairs = nullptr; a.pair_count = nullptr; a.pair_codes = 0;
+    a.pair_stats = nullptr;
     a.big = ctx->big_groups.as<uint32_t>();
     a.counters = ctx->scalars.as<unsigned long long>() + 32;
     a.g_min = 0;

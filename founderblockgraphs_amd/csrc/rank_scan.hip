@@ -287,6 +287,7 @@ template <int L, bool PLAIN> __global__ __launch_bounds__(RS_THREADS) __attribut
 
 struct LeanArgs {
     const uint64_t *keys;                      // what the rows need of the scan's arguments
+    const uint8_t *ext;                        // symbols K .. K+3 of every slot (msd_sort.hip), or nullptr: the noted pairs carry a code (RankArgs::pair_codes)
     uint64_t own_lo, own_hi;
     uint32_t per_wave, pmask;
     int pb;
@@ -357,15 +358,19 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
     const unsigned long long EVM = ((1ull << (RL_EV_HI + 1)) - 1) & ~((1ull << RL_EV_LO) - 1);   // the lanes that settle their slots
     const unsigned long long RNG = ~(1ull << 63);                       // the lanes whose mask bits somebody may ask for
     const uint64_t *__restrict__ keys = f.keys;
-    auto load_row = [&](uint32_t k0) -> uint64_t {
-        // (a row that reaches beyond the array is a row the general code takes: what its lanes out there load does not matter)
-        const uint32_t k = min(max(k0 - RL_EV_LO + (uint32_t)lane, own_lo), own_hi - 1);
-        return keys[k];
-    };
-    uint64_t xnext = wlo < whi ? load_row(wlo) : 0ull;
+    const uint8_t *__restrict__ ext = f.ext;
+    // (a row that reaches beyond the array is a row the general code takes: what its lanes out there load does not matter)
+    auto row_slot = [&](uint32_t k0) -> uint32_t { return min(max(k0 - RL_EV_LO + (uint32_t)lane, own_lo), own_hi - 1); };
+    uint64_t xnext = wlo < whi ? keys[row_slot(wlo)] : 0ull;
+    uint32_t enext = ext && wlo < whi ? ext[row_slot(wlo)] : 0u;
     for (uint32_t k0 = wlo; k0 < whi; k0 += RL_EV) {
         const uint64_t x = xnext;
-        if (k0 + RL_EV < whi) xnext = load_row(k0 + RL_EV);            // in flight during this row's work
+        const uint32_t ex = enext;
+        if (k0 + RL_EV < whi) {                                         // in flight during this row's work
+            const uint32_t kn = row_slot(k0 + RL_EV);
+            xnext = keys[kn];
+            if (ext) enext = ext[kn];
+        }
         const uint32_t slot = k0 - RL_EV_LO + (uint32_t)lane;
         // rows within reach of the ends of the array (or of this wave's last slot, where a row is not full): the general
         // code knows what a missing neighbour means
@@ -406,7 +411,14 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
                 Q = QP | (QP << 1) | (EVM & (LONG | ADJL | (~TIE & (RUN | NE))));
             }
             if (SS) {
-                if ((SS >> lane) & 1ull) my_note[nn + rl_lanes_below(SS)] = make_uint2(lo & f.pmask, lo_n & f.pmask);
+                uint32_t cx = 0, cy = 0;
+                if (ext) {
+                    // the pair's code: how many of the 4 symbols after the key the two agree on (2 bits each, first on top)
+                    const uint32_t d = (ex ^ rl_from_next(ex)) & 255u;
+                    const uint32_t c = d ? (uint32_t)(__builtin_clz(d) - 24) >> 1 : 4u;
+                    cx = c << 30; cy = (c >> 2) << 30;
+                }
+                if ((SS >> lane) & 1ull) my_note[nn + rl_lanes_below(SS)] = make_uint2((lo & f.pmask) | cx, (lo_n & f.pmask) | cy);
                 nn += (uint32_t)__popcll(SS);
             }
             if (Q) {
@@ -430,7 +442,7 @@ static bool rs_lean_setup(const RankArgs &a, int pb, unsigned blocks, LeanArgs *
 {
     const uint64_t own = a.own_hi - a.own_lo, waves = (uint64_t)blocks * RL_WAVES;
     f->per_wave = (uint32_t)(((own + waves - 1) / waves + RL_EV - 1) / RL_EV * RL_EV);
-    f->keys = a.keys; f->own_lo = a.own_lo; f->own_hi = a.own_hi; f->pmask = (uint32_t)a.pmask; f->pb = pb;
+    f->keys = a.keys; f->ext = nullptr; f->own_lo = a.own_lo; f->own_hi = a.own_hi; f->pmask = (uint32_t)a.pmask; f->pb = pb;
     const double L = (double)a.row_len;
     const double delta = (ldexp(1.0, pb - 25) + ldexp(1.0, pb - 22) + 2.0) / L + 1e-6;
     f->inv_row_len = (float)(1.0 / L);
@@ -485,18 +497,41 @@ template <int L> __global__ __launch_bounds__(256) void k_tie_simple(RankArgs a)
 }
 
 // the simple tied pairs k_rank_scan_lean set aside with their text positions: the two suffixes agree on K symbols and nobody
-// else does, the extension of either is 1 + their longest common prefix (no slot is read again: two text reads per pair)
+// else does, the extension of either is 1 + their longest common prefix (no slot is read again: two text reads per pair).
+// With codes (pair_codes) the 4 symbols after the key are known: where the pair parts among them (255 in 256 pairs) no text
+// is read at all -- the pair lies more than 64 symbols before its row ends (k_rank_scan_lean's NE), so they are real symbols,
+// coded one to one; else the comparison starts behind them.
 __global__ __launch_bounds__(256) void k_tie_pairs(RankArgs a)
 {
+    __shared__ uint32_t s_stats[2];
     const uint32_t have = a.pair_count[blockIdx.x];
     if (have > a.tie_region) { if (threadIdx.x == 0) a.counters[1] = 1; return; }
+    if (threadIdx.x < 2) s_stats[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t n_code = 0, n_text = 0;
     for (uint32_t e = threadIdx.x; e < have; e += blockDim.x) {
-        const uint2 p = a.pairs[(size_t)blockIdx.x * a.tie_region + e];
-        const uint64_t x = fbg_load8(a.T, (uint64_t)p.x + a.K) ^ fbg_load8(a.T, (uint64_t)p.y + a.K);
-        const uint32_t h = x != 0 ? (uint32_t)(__ffsll((unsigned long long)x) - 1) / 8 : fbg_extend_match(a.T, (uint64_t)p.x + a.K, (uint64_t)p.y + a.K, 8);
+        uint2 p = a.pairs[(size_t)blockIdx.x * a.tie_region + e];
+        uint32_t h, from = (uint32_t)a.K;
+        const uint32_t c = a.pair_codes ? (p.x >> 30) | (((p.y >> 30) & 1u) << 2) : 4u;
+        if (a.pair_codes) { p.x &= 0x3fffffffu; p.y &= 0x3fffffffu; from += 4; }
+        if (c < 4) {
+            h = c;
+            n_code++;
+        } else {
+            const uint64_t x = fbg_load8(a.T, (uint64_t)p.x + from) ^ fbg_load8(a.T, (uint64_t)p.y + from);
+            h = (from - (uint32_t)a.K) +
+                (x != 0 ? (uint32_t)(__ffsll((unsigned long long)x) - 1) / 8 : fbg_extend_match(a.T, (uint64_t)p.x + from, (uint64_t)p.y + from, 8));
+            n_text++;
+        }
         const uint32_t g = fbg_clamp_lcp(h + (uint32_t)a.K) + 1;
         rs_update(a, rs_col_of_rem(a, rs_rem<FBG_SLOTS_PACKED>(a, p.x)), g);
         rs_update(a, rs_col_of_rem(a, rs_rem<FBG_SLOTS_PACKED>(a, p.y)), g);
+    }
+    if (a.pair_stats) {
+        if (n_code) atomicAdd(&s_stats[0], n_code);
+        if (n_text) atomicAdd(&s_stats[1], n_text);
+        __syncthreads();
+        if (threadIdx.x < 2 && s_stats[threadIdx.x]) atomicAdd(&a.pair_stats[threadIdx.x], (unsigned long long)s_stats[threadIdx.x]);
     }
 }
 
@@ -875,6 +910,14 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
                       rs_lean_setup(a, a.pb, rs_blocks, &lf);
     if (lean)
     {
+        // the symbols after the key from the MSD sort (these very slots, 2-bit symbols): the pairs carry a code in their spare
+        // position bits -- positions below 2^30
+        if (ctx->msd_ext_valid && a.keys == ctx->keysA.as<uint64_t>() && a.b == 2 && a.pb <= 30 && a.own_lo == 0 && a.own_hi == ctx->N) {
+            lf.ext = ctx->msd_ext.as<uint8_t>();
+            a.pair_codes = 1;
+        }
+        a.pair_stats = ctx->scalars.as<unsigned long long>() + 112;
+        FBG_HIP_TRY(ctx, hipMemsetAsync(a.pair_stats, 0, 2 * sizeof(unsigned long long), st));
         FBG_TRY(fbg_reserve(ctx, ctx->ps_g, (size_t)rs_blocks * tie_region * 8));
         FBG_TRY(fbg_reserve(ctx, ctx->ps_h, (size_t)rs_blocks * 4));
         a.pairs = ctx->ps_g.as<uint2>(); a.pair_count = ctx->ps_h.as<uint32_t>();
@@ -970,6 +1013,7 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     *done = 0;
     ctx->ranked = false;
     ctx->part_active = false;
+    ctx->ext_pairs = ctx->text_pairs = -1;
     const uint64_t N = ctx->N, n = ctx->n;
     const int layout = rs_layout(geom);
     hipStream_t st = ctx->stream;
@@ -992,13 +1036,16 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
         launches++;
     }
     FBG_TRY(rs_join(ctx));
-    unsigned long long h[5];
+    unsigned long long h[5], ps[2] = {0, 0};
     // a large tie group / an overflowing tie region -> record path; a column without a value lost all its rows
     // to the threshold -> redo without it
     if (a.g_min > 1)
         hipLaunchKernelGGL(k_count_unfilled, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, a.gmax, n, a.g_min, a.reversed, cnt);
     FBG_HIP_TRY(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    if (a.pair_stats) FBG_HIP_TRY(ctx, hipMemcpyAsync(ps, a.pair_stats, sizeof(ps), hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->ext_pairs = (int64_t)ps[0];
+    ctx->text_pairs = (int64_t)ps[1];
     launches++;
     if (h[1] != 0) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
     if (a.g_min > 1 && h[4] != 0) {

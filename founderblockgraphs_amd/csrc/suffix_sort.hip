@@ -838,6 +838,7 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     ctx->granked = false;
     ctx->grs_ebits = nullptr;
     ctx->grs_flagged = false;
+    ctx->msd_ext_valid = false;
     KeyGeom g;
 
     // ---- gap-free MSAs: compact keys, sort, and the whole extension scan in rank order (rank_scan.hip) -------

@@ -98,6 +98,9 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *                      runs on the rows that are there; results unchanged)
  *   rank_no_lean       1: the rank-order scan with k_rank_scan also where its lean form (k_rank_scan_lean: packed slots, threshold
  *                      above the key length) applies; results unchanged
+ *   msd_ext            0: the three-pass MSD sort carries no symbols beyond the key (default 1: with 2-bit symbols its words
+ *                      carry the 4 symbols after the key, pass 3 writes them out as one byte per slot, and the rank-order
+ *                      scan settles most tied pairs from them instead of reading the text); results unchanged
  *   msd_xcd            which passes of the MSD sort place their writes by XCD (-1 = 3): bit 0 pass 2 (the tiles of a bucket
  *                      go to the workgroups of one XCD), bit 1 pass 1 (a stretch per bucket and XCD); 0: neither (the
  *                      layout of rounds 1-3); results unchanged
@@ -133,6 +136,9 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  * geometry did not suit it (rocPRIM sorted), else the capacity that did not hold (2 / 4 a stretch of pass 1, 8 the arena
  * of pass 2, 16 a sub-bucket beyond the largest finish).  "pass1_ahead" (read-only): 1 when that sort found its pass 1 done
  * during a streamed upload (fbg_elastic_f from memory of fbg_host_alloc).
+ * "ext_pairs", "text_pairs" (read-only): the tied pairs the lean rank-order scan of the last index build settled from the
+ * MSD sort's symbols after the key (msd_ext) / by comparing the text; -1 when no rank-order scan ran, both 0 when it ran
+ * without its lean form.
  * Unknown key: FBG_ERR_INVALID.
  */
 int fbg_set_option(fbg_ctx *ctx, const char *key, int64_t value);
