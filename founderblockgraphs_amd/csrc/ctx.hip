@@ -222,6 +222,13 @@ int fbg_get_option(const fbg_ctx *ctx, const char *key, int64_t *value)
     if (strcmp(key, "pass1_ahead") == 0) { *value = ctx->pass1_ahead; return FBG_OK; }
     if (strcmp(key, "ext_pairs") == 0) { *value = ctx->ext_pairs; return FBG_OK; }
     if (strcmp(key, "text_pairs") == 0) { *value = ctx->text_pairs; return FBG_OK; }
+    if (strcmp(key, "rank_lean_used") == 0) { *value = ctx->rank_lean_used; return FBG_OK; }
+    if (strcmp(key, "rank_lean_launched") == 0) { *value = ctx->rank_lean_launched; return FBG_OK; }
+    if (strcmp(key, "pairs_rb") == 0) { *value = ctx->pairs_rb; return FBG_OK; }
+    if (strcmp(key, "key_b") == 0) { *value = ctx->key_b; return FBG_OK; }
+    if (strcmp(key, "key_K") == 0) { *value = ctx->key_K; return FBG_OK; }
+    if (strcmp(key, "key_packed") == 0) { *value = ctx->key_packed; return FBG_OK; }
+    if (strcmp(key, "key_compact") == 0) { *value = ctx->key_compact; return FBG_OK; }
     if (strcmp(key, "alloc_calls") == 0) { *value = (int64_t)ctx->alloc_calls; return FBG_OK; }
     if (strcmp(key, "alloc_us") == 0) { *value = (int64_t)ctx->alloc_us; return FBG_OK; }
     if (strcmp(key, "span_decline") == 0) { *value = ctx->sp_decline; return FBG_OK; }

@@ -71,6 +71,10 @@ struct fbg_ctx {
     int pass1_ahead = 0;                       // the last MSD sort found its pass 1 done (fbg_get_option "pass1_ahead")
     bool msd_ext_valid = false;                // msd_ext holds the 4 symbols after the key of every slot the last MSD sort sorted
     int64_t ext_pairs = -1, text_pairs = -1;   // the last rank-order scan: tied pairs settled by those symbols / by the text
+    int rank_lean_launched = 0;                // the last rank-order scan launched k_rank_scan_lean (fbg_get_option "rank_lean_launched")
+    int rank_lean_used = 0;                    // ... and finished with it: the index holds its result (fbg_get_option "rank_lean_used")
+    int pairs_rb = -1;                         // the last sample sort of pairs: rank bits of its table, -1 it did not sort ("pairs_rb")
+    int key_b = -1, key_K = -1, key_packed = -1, key_compact = -1;   // geometry of the last key setup (fbg_get_option "key_*")
 
     // index state
     bool index_valid = false;
@@ -193,6 +197,12 @@ struct KeyGeom {
     int pb = 0;
     const uint8_t *d_code = nullptr;
 };
+
+// the geometry fbg_get_option reports as key_b / key_K / key_packed / key_compact
+inline void fbg_note_key_geom(fbg_ctx *ctx, const KeyGeom &g)
+{
+    ctx->key_b = g.b; ctx->key_K = g.K; ctx->key_packed = g.packed ? 1 : 0; ctx->key_compact = g.compact ? 1 : 0;
+}
 
 // ---- stages (each in its own translation unit) ----------------------------------------------
 int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len);  // text_build.hip

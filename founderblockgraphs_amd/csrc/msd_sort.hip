@@ -615,6 +615,7 @@ bool fbg_msd_pre_geom(fbg_ctx *ctx, KeyGeom *g)
     MsdPlan plan;
     memcpy(&plan, ctx->pre_state, sizeof(plan));
     *g = plan.g;
+    fbg_note_key_geom(ctx, *g);
     return true;
 }
 

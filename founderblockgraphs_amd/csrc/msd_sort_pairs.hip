@@ -1019,6 +1019,7 @@ int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, int *ok, int *launches
 {
     *ok = 0;
     ctx->pairs_similar = false;
+    ctx->pairs_rb = -1;
     const uint64_t N = ctx->N;
     const uint64_t min_n = ctx->opt.msd_min >= 0 ? (uint64_t)ctx->opt.msd_min : (1ull << 24);
     const uint64_t nsub = (uint64_t)PP_NB * PP_NB;
@@ -1104,5 +1105,6 @@ int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, int *ok, int *launches
     const uint64_t est = N + N / 64 + 65536;
     FBG_TRY(pp_sort<1>(ctx, g, a, est, 1, 0, &count, ok, launches));
     if (*ok && count != N) { *ok = 0; }
+    ctx->pairs_rb = *ok ? a.rb : -1;
     return FBG_OK;
 }

@@ -908,6 +908,7 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
     LeanArgs lf;
     const bool lean = layout == FBG_SLOTS_PACKED && a.g_min > (uint32_t)a.K && !a.values_only && !a.part_mode && !ctx->opt.rank_no_lean &&
                       rs_lean_setup(a, a.pb, rs_blocks, &lf);
+    ctx->rank_lean_launched = lean ? 1 : 0;
     if (lean)
     {
         // the symbols after the key from the MSD sort (these very slots, 2-bit symbols): the pairs carry a code in their spare
@@ -1014,6 +1015,7 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     ctx->ranked = false;
     ctx->part_active = false;
     ctx->ext_pairs = ctx->text_pairs = -1;
+    ctx->rank_lean_used = ctx->rank_lean_launched = 0;
     const uint64_t N = ctx->N, n = ctx->n;
     const int layout = rs_layout(geom);
     hipStream_t st = ctx->stream;
@@ -1057,6 +1059,7 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     FBG_HIP_TRY(ctx, hipGetLastError());
     ctx->n_exc = 0;
     ctx->ranked = true;
+    ctx->rank_lean_used = ctx->rank_lean_launched;
     rs_remember(ctx, keys, vals, geom);
     *done = 1;
     return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);

@@ -766,6 +766,7 @@ int fbg_key_setup(fbg_ctx *ctx, bool compact, KeyGeom *g, int *launches)
         if (Kroom >= Kmin) { g->packed = true; g->pb = pb; if (K > Kroom) K = Kroom; }
     }
     g->b = b; g->K = K; g->key_bits = K * b; g->d_code = d_code;
+    fbg_note_key_geom(ctx, *g);
     FBG_HIP_TRY(ctx, hipMemcpyAsync(d_code, code, 256, hipMemcpyHostToDevice, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));  // code[] lives on this stack frame
     *launches += 1;
@@ -839,12 +840,21 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     ctx->grs_ebits = nullptr;
     ctx->grs_flagged = false;
     ctx->msd_ext_valid = false;
+    ctx->rank_lean_used = ctx->rank_lean_launched = 0;
+    ctx->pairs_rb = -1;
+    ctx->ext_pairs = ctx->text_pairs = -1;
+    ctx->pass1_ahead = 0;
+    ctx->msd_decline = -1;                      // (fbg_msd_sort says otherwise when the build reaches it)
     KeyGeom g;
 
     // ---- gap-free MSAs: compact keys, sort, and the whole extension scan in rank order (rank_scan.hip) -------
     if (ctx->gapfree && !ctx->have_ignore && !ctx->opt.no_ranked) {
         // (a streamed upload has set the keys up and run pass 1 of the sort already: same geometry)
         if (!fbg_msd_pre_geom(ctx, &g)) FBG_TRY(fbg_key_setup(ctx, true, &g, &launches));
+    }
+    // both scans read keys in the compact coding (a separator and what follows it count as code 0, rank_scan.hip); a byte
+    // below '#' or 128 distinct symbols and more leave the keys in the coding of any alphabet: the record path takes those
+    if (ctx->gapfree && !ctx->have_ignore && !ctx->opt.no_ranked && g.compact) {
         bool similar = false;
         FBG_TRY(sample_says_similar(ctx, g, &similar, &launches));
         // packed slots of a large text: three-pass MSD sort fused with the key packing (msd_sort.hip); else, or when

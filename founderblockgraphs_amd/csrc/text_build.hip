@@ -505,8 +505,9 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
     ctx->gapfree = h[0] == 0;
     ctx->N = h[2];
     if (ctx->pre_pass1) {
-        // what the first chunk promised: no gaps, and exactly the symbols the keys were set up for
-        bool same = ctx->gapfree && ctx->N == m * (n + 1) + 1;
+        // what the first chunk promised: no gaps, and exactly the symbols the keys were set up for -- byte 0 occurs either way
+        // (the sentinel), so a NUL byte in a later chunk shows only in its count (fbg_key_setup refuses it)
+        bool same = ctx->gapfree && ctx->N == m * (n + 1) + 1 && ctx->byte_hist[0] == 1;
         for (int b = 0; b < 256 && same; b++) same = (ctx->byte_hist[b] != 0) == ((ctx->pre_symbols[b >> 6] >> (b & 63)) & 1ull);
         ctx->pre_pass1 = same;
     }

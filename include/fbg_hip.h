@@ -139,6 +139,16 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  * "ext_pairs", "text_pairs" (read-only): the tied pairs the lean rank-order scan of the last index build settled from the
  * MSD sort's symbols after the key (msd_ext) / by comparing the text; -1 when no rank-order scan ran, both 0 when it ran
  * without its lean form.
+ * "rank_lean_launched" (read-only): 1 when the last rank-order scan launched its lean form (k_rank_scan_lean), whether or
+ * not the scan then finished; "rank_lean_used" (read-only): 1 when it also finished, so that the index holds that kernel's
+ * column maxima (0 when the scan handed over to the group-level scan or the record path).
+ * "pairs_rb" (read-only): the sample sort of (key, position) pairs of the last index build (msd_sort_pairs.hip): -1 it did
+ * not sort (not reached, or declined to rocPRIM), else the rank bits of its table of frequent symbols (0: no table, 1 .. 3:
+ * 2 / 4 / 8 frequent symbols, entries of 2 bits for 1 .. 2, of 4 bits for 3).
+ * "key_b", "key_K", "key_packed", "key_compact" (read-only): the key geometry of the last key setup (suffix_sort.hip
+ * fbg_key_setup): bits per symbol, symbols per key, 1 when a key and its position share one 64-bit word, 1 when the
+ * separator-free coding of the rank-order scans applies (no byte below '#' in the rows, fewer than 128 distinct symbols);
+ * -1 before the first index build.
  * Unknown key: FBG_ERR_INVALID.
  */
 int fbg_set_option(fbg_ctx *ctx, const char *key, int64_t value);
