@@ -73,6 +73,12 @@ SIGNATURES = {
     "fbg_group_scan_f": (C.c_int, [vp, u8p, C.c_uint64, C.c_int, C.POINTER(vp)]),
     "fbg_host_alloc": (vp, [C.c_uint64]),
     "fbg_host_free": (None, [vp]),
+    "fbg_pindex_build": (C.c_int, [vp, u8p, u64p, C.c_uint64, u64p, u64p, C.POINTER(vp)]),
+    "fbg_pindex_locate": (C.c_int, [vp, u8p, u64p, C.c_uint64, u64p, u64p]),
+    "fbg_pindex_text_length": (C.c_uint64, [vp]),
+    "fbg_pindex_download": (C.c_int, [vp, u8p, u32p, u32p, u32p, u64p, u64p]),
+    "fbg_pindex_stats": (C.c_int, [vp, u64p, C.POINTER(C.c_double), C.POINTER(C.c_double), u64p]),
+    "fbg_pindex_destroy": (None, [vp]),
 }
 PLANS = ("auto", "partitioned", "columns", "row_pairs")   # FBG_PLAN_*
 

@@ -6,6 +6,7 @@ Names and argument meaning follow founderblockgraph.cpp ("fbg.cpp"):
 Every call goes through the C ABI of libfbg_hip.so (include/fbg_hip.h); nothing here computes.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -64,6 +65,8 @@ class Engine:
         self.device = int(device)
 
     def close(self):
+        for pix in list(getattr(self, "_pindexes", ())):    # an index borrows the context: it goes first
+            pix.close()
         if getattr(self, "_h", None):
             if not getattr(self, "_borrowed", False):      # a group's member belongs to the group
                 self._L.fbg_ctx_destroy(self._h)
@@ -295,6 +298,148 @@ class Engine:
         arrs = [np.empty(N, dtype=np.uint32) for _ in range(4)]
         self._chk(self._L.fbg_index_download(self._h, _u8(T), *[a.ctypes.data_as(_lib.u32p) for a in arrs]))
         return (T, *arrs)
+
+    def pattern_index(self, labels, edges):
+        """Pattern index of a founder graph (fbg_pindex_build): labels in node id order (a list of str / bytes, or a
+        pair (uint8 data, uint64 offsets[nodes + 1])), edges as (u, v) pairs of 0-based indices into labels.  Borrows
+        this engine's device and stream; closing the engine closes its indexes first."""
+        pix = PatternIndex(self, labels, edges)
+        if not hasattr(self, "_pindexes"):
+            self._pindexes = weakref.WeakSet()
+        self._pindexes.add(pix)
+        return pix
+
+
+def _concat(strings):
+    """(uint8 bytes, uint64 offsets[len + 1]) of a list of str / bytes, or such a pair passed through."""
+    if isinstance(strings, tuple) and len(strings) == 2 and isinstance(strings[1], np.ndarray):
+        data = np.concatenate((np.ascontiguousarray(strings[0], dtype=np.uint8).ravel(), np.zeros(1, dtype=np.uint8)))
+        return data, np.ascontiguousarray(strings[1], dtype=np.uint64)
+    bs = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
+    off = np.zeros(len(bs) + 1, dtype=np.uint64)
+    if bs:
+        off[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+    data = np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8).copy()
+    return data, off
+
+
+class PatternIndex:
+    """fbg_pindex: the founder_block_index of the reference built on the GPU (include/fbg_hip.h, 'pattern index').
+    locate() returns what locate_patterns reports per pattern: the count of the last backward-search range (0: not
+    found) and the number of symbols matched."""
+
+    def __init__(self, engine, labels, edges):
+        self._eng = engine
+        self._L = engine._L
+        self._h = None
+        data, loff = _concat(labels)
+        n = len(loff) - 1
+        e = np.asarray(list(edges) if not isinstance(edges, np.ndarray) else edges, dtype=np.int64).reshape(-1, 2)
+        if len(e) and (e.min() < 0 or e.max() >= n):
+            raise ValueError("edge endpoints must be node indices 0 .. len(labels) - 1")
+        order = np.argsort(e[:, 0], kind="stable")
+        dst = np.ascontiguousarray(e[order, 1], dtype=np.uint64)
+        eoff = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            eoff[1:] = np.cumsum(np.bincount(e[:, 0], minlength=n)[:n], dtype=np.uint64)
+        dst = np.concatenate((dst, np.zeros(1, dtype=np.uint64)))
+        h = C.c_void_p()
+        engine._chk(self._L.fbg_pindex_build(engine._h, _u8(data), _u64(loff), n, _u64(eoff), _u64(dst), C.byref(h)))
+        self._h = h
+        self.n_nodes = n
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fbg_pindex_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def text_length(self):
+        """N + 1: the edge text including its sentinel."""
+        return int(self._L.fbg_pindex_text_length(self._h))
+
+    def locate(self, patterns):
+        """-> (count, pos), uint64 arrays with one entry per pattern (a list of str / bytes, or a pair (uint8 data,
+        uint64 offsets[k + 1]))."""
+        data, off = _concat(patterns)
+        k = len(off) - 1
+        count = np.zeros(max(k, 1), dtype=np.uint64)
+        pos = np.zeros(max(k, 1), dtype=np.uint64)
+        self._eng._chk(self._L.fbg_pindex_locate(self._h, _u8(data), _u64(off), k, _u64(count), _u64(pos)))
+        return count[:k], pos[:k]
+
+    def download(self):
+        """-> (text with the sentinel, SA, B positions, E positions)."""
+        N1 = self.text_length()
+        nb, ne = C.c_uint64(0), C.c_uint64(0)
+        self._eng._chk(self._L.fbg_pindex_download(self._h, None, None, None, None, C.byref(nb), C.byref(ne)))
+        T = np.empty(N1, dtype=np.uint8)
+        sa = np.empty(N1, dtype=np.uint32)
+        B = np.empty(max(nb.value, 1), dtype=np.uint32)
+        E = np.empty(max(ne.value, 1), dtype=np.uint32)
+        self._eng._chk(self._L.fbg_pindex_download(self._h, _u8(T), sa.ctypes.data_as(_lib.u32p), B.ctypes.data_as(_lib.u32p),
+                                                   E.ctypes.data_as(_lib.u32p), C.byref(nb), C.byref(ne)))
+        return T, sa, B[:nb.value], E[:ne.value]
+
+    def stats(self):
+        """{index_bytes, build_ms, search_ms, occ_lines}: see fbg_pindex_stats."""
+        ib, ol = C.c_uint64(0), C.c_uint64(0)
+        bm, sm = C.c_double(0), C.c_double(0)
+        self._eng._chk(self._L.fbg_pindex_stats(self._h, C.byref(ib), C.byref(bm), C.byref(sm), C.byref(ol)))
+        return {"index_bytes": ib.value, "build_ms": bm.value, "search_ms": sm.value, "occ_lines": ol.value}
+
+
+def read_xgfa(path):
+    """(labels, edges) of an xGFA (or GFA) file: S lines sorted by id (0- or 1-based alike), L lines as (u, v) pairs of
+    indices into labels.  Empty labels are kept."""
+    ids, labs, links = [], [], []
+    with open(path, "rb") as fh:
+        for line in fh:
+            f = line.rstrip(b"\r\n").split(b"\t")
+            if f[0] == b"S":
+                ids.append(int(f[1]))
+                labs.append(f[2] if len(f) > 2 else b"")
+            elif f[0] == b"L":
+                links.append((int(f[1]), int(f[3])))
+    order = sorted(range(len(ids)), key=lambda k: ids[k])
+    where = {ids[k]: i for i, k in enumerate(order)}
+    return [labs[k] for k in order], [(where[u], where[v]) for u, v in links]
+
+
+def graph_from_segmentation(engine, msa, boundaries, packed=False):
+    """(labels, edges) of the elastic founder graph of a segmentation of `msa` (the nodes and edges of
+    Engine.block_graph; the MSA becomes the engine's current one).  Labels are the gap-stripped rows of the blocks:
+    a list of bytes, or with packed=True a pair (uint8 data, uint64 offsets); edges an (E, 2) int64 array."""
+    msa = as_msa(msa)
+    m, n = msa.shape
+    engine.msa_load_host(msa)
+    b = np.ascontiguousarray(boundaries, dtype=np.uint64)
+    node_of, first, rep_row, ecount, edges = engine.block_graph(b)
+    chunks, lens = [], []
+    for j in range(len(b)):
+        x0 = int(b[j - 1]) + 1 if j else 0
+        x1 = min(int(b[j]) + 1, n)
+        sub = msa[rep_row[j, :int(first[j + 1] - first[j])], x0:x1]
+        keep = sub != ord("-")
+        chunks.append(sub[keep])
+        lens.append(keep.sum(axis=1))
+    data = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.uint8)
+    off = np.zeros(int(first[-1]) + 1, dtype=np.uint64)
+    if len(off) > 1:
+        off[1:] = np.cumsum(np.concatenate(lens), dtype=np.uint64)
+    sel = edges[np.arange(m)[None, :] < ecount[:, None].astype(np.int64)]
+    pairs = np.stack(((sel >> np.uint64(32)).astype(np.int64), (sel & np.uint64(0xffffffff)).astype(np.int64)), axis=1)
+    if packed:
+        return (data, off), pairs
+    raw = data.tobytes()
+    return [raw[int(off[k]):int(off[k + 1])] for k in range(len(off) - 1)], pairs
 
 
 class _DeviceArray:

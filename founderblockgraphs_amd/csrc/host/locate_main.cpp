@@ -1,0 +1,99 @@
+// locate_main.cpp -- fbg_locate: pattern search in an elastic founder graph through the pattern index of
+// libfbg_hip.so (include/fbg_hip.h, fbg_pindex_*).  Stands in for locate_patterns of the reference with a graph in
+// place of its .index file:
+//
+//   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found]
+//
+// Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
+// token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
+// in one fbg_pindex_locate call.  stdout is byte for byte what locate_patterns prints for an index of that graph;
+// stderr carries the messages.
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <string>
+#include <vector>
+#include "../../../include/fbg_hip.h"
+#include "xgfa_read.hpp"
+
+static int usage(const char *msg)
+{
+    std::cerr << "fbg_locate: " << msg << "\n"
+              << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found]\n";
+    return EXIT_FAILURE;
+}
+
+int main(int argc, char **argv)
+{
+    std::string graph, patterns;
+    bool have_graph = false, have_patterns = false, error_on_not_found = false;
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        auto value = [&](const char *name, std::string &out, bool &have) {
+            const std::string pre = std::string(name) + "=";
+            if (a.compare(0, pre.size(), pre) == 0) { out = a.substr(pre.size()); have = true; return true; }
+            if (a == name && i + 1 < argc) { out = argv[++i]; have = true; return true; }
+            return false;
+        };
+        if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns)) continue;
+        if (a == "--error-on-not-found") { error_on_not_found = true; continue; }
+        if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
+        return usage(("unknown argument " + a).c_str());
+    }
+    if (!have_graph || graph.empty()) return usage("--graph is required");
+
+    XgfaGraph g;
+    std::string error;
+    if (!read_xgfa_graph(graph, g, error)) { std::cerr << "fbg_locate: " << error << "\n"; return EXIT_FAILURE; }
+
+    std::ifstream pf;
+    if (have_patterns) {
+        pf.open(patterns, std::ios::binary);
+        if (!pf) { std::cerr << "fbg_locate: cannot open " << patterns << "\n"; return EXIT_FAILURE; }
+    }
+    std::istream &in = have_patterns ? static_cast<std::istream &>(pf) : std::cin;
+    std::ios_base::sync_with_stdio(false);
+    std::string data;
+    std::vector<uint64_t> off(1, 0);
+    while (true) {
+        std::string p;
+        in >> p;
+        if (in.eof()) break;           // also drops a last token that ends the input (locate_patterns.cpp:47-53)
+        if (!in) { std::cerr << "fbg_locate: cannot read the patterns\n"; return EXIT_FAILURE; }
+        data += p;
+        off.push_back(data.size());
+    }
+    const uint64_t np = off.size() - 1;
+
+    fbg_ctx *ctx = nullptr;
+    int rc = fbg_ctx_create(0, &ctx);
+    if (rc != FBG_OK) { std::cerr << "fbg_locate: " << fbg_last_error(nullptr) << "\n"; return EXIT_FAILURE; }
+    const uint64_t nodes = g.label_off.size() - 1;
+    fbg_pindex *ix = nullptr;
+    rc = fbg_pindex_build(ctx, (const uint8_t *)g.labels.data(), g.label_off.data(), nodes, g.edge_off.data(),
+                          g.edge_dst.data(), &ix);
+    std::vector<uint64_t> count(np + 1), pos(np + 1);
+    if (rc == FBG_OK) rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
+    if (rc != FBG_OK) {
+        std::cerr << "fbg_locate: " << fbg_last_error(ctx) << "\n";
+        fbg_pindex_destroy(ix);
+        fbg_ctx_destroy(ctx);
+        return EXIT_FAILURE;
+    }
+    fbg_pindex_destroy(ix);
+    fbg_ctx_destroy(ctx);
+
+    uint64_t found = 0;
+    for (uint64_t k = 0; k < np; k++) {
+        std::cout << "Pattern? " << count[k] << " occurrences found.\n";
+        if (count[k] == 0) {
+            std::cerr << "Pattern not found, pos = " << pos[k] << ".\n";
+            if (error_on_not_found) { std::cout.flush(); return EXIT_FAILURE; }
+        } else {
+            found++;
+        }
+    }
+    std::cout << "Pattern? " << found << " out of " << np << " patterns found" << std::endl;
+    return EXIT_SUCCESS;
+}

@@ -1,0 +1,744 @@
+// locate.hip -- pattern index of a founder graph and batched pattern search (the query side of the reference's
+// founder_block_index: make_index, fbg.cpp:2809-2953, and backward_search, founder_block_index.hpp:86-145).
+//
+// Text: for every node u in id order and every distinct out-neighbour v in ascending order, reverse(label(u) +
+// label(v) + '#'), then one 0 sentinel (N + 1 symbols in all).  Built here, all on the device:
+//
+//   k_px_edge_len / k_px_edge_text   |u| + |v| + 1 per edge, an exclusive scan for the offsets, one wave per edge
+//                                    writes its reversed string;
+//   suffix array                     prefix doubling: k_px_keys0 packs the first K symbol codes of every suffix,
+//                                    a radix sort orders them; every later round re-sorts only the suffixes of
+//                                    groups that still tie, by (rank of the group, rank h symbols ahead), and
+//                                    doubles h, until no group is left (exact SA, any byte alphabet);
+//   k_px_lines                       BWT and the occ structure, one wave per 128 BWT positions;
+//   k_px_walk<false>                 B / E: every label searched from [0, N], flags at lhs / rhs, compacted
+//                                    into sorted position lists;
+//   k_px_walk<true>                  the batched search of rule 4 (restarts included), one lane per pattern,
+//                                    patterns handed out in order of length.
+//
+// occ layout.  Symbols are remapped to dense codes in byte order (the sentinel is code 0, '#' code 1).  With at
+// most 16 codes a block of 128 BWT positions is one 128-byte line:
+//   bytes   0 ..  63   u32 occ of every code before the block
+//   bytes  64 ..  95   bits 0 .. 63 of the positions, bit planes 0 .. 3 (u64 each)
+//   bytes  96 .. 127   bits 64 .. 127, bit planes 0 .. 3
+// occ(c, i) = count[c] + popcount(AND over the planes of (plane or its complement) below i): one line per query,
+// about one byte per text position.  Larger alphabets take 8 bit planes per line (128 bytes) and the counts in a
+// table of their own (u32 per block and code): two lines per query.
+#include "fbg_internal.h"
+#include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#define PX_THREADS 256
+#define PX_BLK 128            // BWT positions per occ block
+#define PX_LINE 128           // bytes per occ line
+#define PX_ABSENT 0xffffu     // code of a byte that does not occur in the text
+
+struct fbg_pindex {
+    fbg_ctx *ctx = nullptr;
+    uint64_t N1 = 0;          // text length including the sentinel
+    int sigma = 0;            // distinct symbols of the text
+    bool compact = false;     // sigma <= 16: counts inside the line
+    uint64_t nblk = 0;        // occ blocks: N1 / 128 + 1 (the last one answers occ(c, N1))
+    uint64_t n_nodes = 0;
+    uint32_t nb = 0, ne = 0;
+    DevBuf text, sa, lines, cnt_tab, C, code, bpos, epos;
+    DevBuf pats, poff, okey, oval, okey2, oval2, cnt_out, pos_out, lines_ctr, tmp;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double build_ms = 0, search_ms = 0;
+    uint64_t occ_lines = 0;
+};
+
+// ---- device buffers owned by the index (the context's workspaces stay untouched) ------------------------------
+static int px_reserve(fbg_pindex *ix, DevBuf &b, size_t bytes)
+{
+    if (bytes == 0) bytes = 256;
+    if (b.cap >= bytes) return FBG_OK;
+    if (b.p) {
+        FBG_HIP_TRY(ix->ctx, hipStreamSynchronize(ix->ctx->stream));
+        FBG_HIP_TRY(ix->ctx, hipFree(b.p));
+        b.p = nullptr; b.cap = 0;
+    }
+    const size_t want = (bytes + 255) & ~(size_t)255;
+    hipError_t e = hipMalloc(&b.p, want);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return fbg_fail(ix->ctx, FBG_ERR_OOM, "pattern index: hipMalloc(%llu): %s", (unsigned long long)want, hipGetErrorString(e));
+    }
+    b.cap = want;
+    return FBG_OK;
+}
+
+static void px_free(DevBuf &b)
+{
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+}
+
+template <class F> static int px_with_tmp(fbg_pindex *ix, F &&call)
+{
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e != hipSuccess) return fbg_fail(ix->ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
+    FBG_TRY(px_reserve(ix, ix->tmp, bytes));
+    size_t have = ix->tmp.cap;
+    e = call(ix->tmp.p, have);
+    if (e != hipSuccess)
+        return fbg_fail(ix->ctx, e == hipErrorOutOfMemory ? FBG_ERR_OOM : FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
+    return FBG_OK;
+}
+
+// ---- edge text ------------------------------------------------------------------------------------------------
+__global__ void k_px_edge_len(const uint32_t *esrc, const uint32_t *edst, const uint64_t *loff, uint64_t E, uint64_t *len)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const uint32_t u = esrc[e], v = edst[e];
+    len[e] = (loff[u + 1] - loff[u]) + (loff[v + 1] - loff[v]) + 1;
+}
+
+// one wave per edge: text[eoff[e] + k] = reverse(label(u) + label(v) + '#')[k] = '#', reverse(v), reverse(u)
+__global__ __launch_bounds__(PX_THREADS) void k_px_edge_text(const uint8_t *labels, const uint64_t *loff, const uint32_t *esrc,
+                                                            const uint32_t *edst, const uint64_t *eoff, uint64_t E, uint8_t *text)
+{
+    const uint64_t e = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FBG_WAVE;
+    const unsigned lane = threadIdx.x % FBG_WAVE;
+    if (e >= E) return;
+    const uint32_t u = esrc[e], v = edst[e];
+    const uint64_t ou = loff[u], lu = loff[u + 1] - ou, ov = loff[v], lv = loff[v + 1] - ov;
+    uint8_t *out = text + eoff[e];
+    for (uint64_t k = lane; k < lu + lv + 1; k += FBG_WAVE)
+        out[k] = k == 0 ? (uint8_t)'#' : k <= lv ? labels[ov + lv - k] : labels[ou + lu - (k - lv)];
+}
+
+// ---- suffix array by prefix doubling ----------------------------------------------------------------------------
+// round 0: key = the first K symbol codes (b bits each, most significant first; 0 beyond the text, which only
+// follows the unique sentinel and so never decides an order), value = position; cidx = identity
+__global__ void k_px_keys0(const uint8_t *text, const uint8_t *code_u8, uint64_t N1, int b, int K, uint64_t *keys,
+                           uint32_t *vals, uint32_t *cidx)
+{
+    __shared__ uint8_t cs[256];
+    for (int c = threadIdx.x; c < 256; c += blockDim.x) cs[c] = code_u8[c];
+    __syncthreads();
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N1) return;
+    uint64_t key = 0;
+    for (int j = 0; j < K; j++) {
+        const uint64_t q = p + j;
+        key = (key << b) | (q < N1 ? cs[text[q]] : 0u);
+    }
+    keys[p] = key;
+    vals[p] = (uint32_t)p;
+    cidx[p] = (uint32_t)p;
+}
+
+// later rounds: the suffixes of tying groups (SA slots cidx[0 .. cnt), ascending), key = rank << pb | rank h ahead.
+// A suffix that still ties has no sentinel among its first h symbols, so p + h < N1.
+__global__ void k_px_keysh(const uint32_t *cidx, uint64_t cnt, const uint32_t *sa, const uint32_t *rank, uint64_t h,
+                           uint64_t N1, int pb, uint64_t *keys, uint32_t *vals)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= cnt) return;
+    const uint32_t p = sa[cidx[k]];
+    const uint64_t r2 = p + h < N1 ? rank[p + h] : 0u;
+    keys[k] = ((uint64_t)rank[p] << pb) | r2;
+    vals[k] = p;
+}
+
+// sorted slots back into the SA; a slot whose key differs from its predecessor's heads a new group
+__global__ void k_px_place(const uint64_t *keys, const uint32_t *vals, const uint32_t *cidx, uint64_t cnt, uint32_t *sa,
+                           uint32_t *headv, uint8_t *head)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= cnt) return;
+    const uint32_t i = cidx[k];
+    sa[i] = vals[k];
+    const bool h = k == 0 || keys[k] != keys[k - 1];
+    head[k] = h;
+    headv[k] = h ? i : 0u;
+}
+
+// rank of a suffix = SA slot of its group's head (hscan: inclusive max-scan of headv); groups of one are settled
+__global__ void k_px_rank(const uint32_t *vals, const uint32_t *hscan, const uint8_t *head, uint64_t cnt, uint32_t *rank,
+                          uint8_t *keep)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= cnt) return;
+    rank[vals[k]] = hscan[k];
+    keep[k] = !(head[k] && (k + 1 == cnt || head[k + 1]));
+}
+
+// ---- BWT and occ lines ------------------------------------------------------------------------------------------
+template <int P> __device__ __forceinline__ uint64_t px_match(uint32_t c, const uint64_t *w)
+{
+    uint64_t m = ~0ull;
+#pragma unroll
+    for (int p = 0; p < P; p++) m &= ((c >> p) & 1u) ? w[p] : ~w[p];
+    return m;
+}
+
+// one wave per block of 128 BWT positions: bit planes into the line, per-code counts into cntT[code * nblk + blk]
+template <bool COMPACT>
+__global__ __launch_bounds__(PX_THREADS) void k_px_lines(const uint32_t *sa, const uint8_t *text, const uint8_t *code_u8, uint64_t N1,
+                                                        uint64_t nblk, int S, uint8_t *lines, uint32_t *cntT)
+{
+    constexpr int P = COMPACT ? 4 : 8;
+    __shared__ uint8_t cs[256];
+    for (int c = threadIdx.x; c < 256; c += blockDim.x) cs[c] = code_u8[c];
+    __syncthreads();
+    const uint64_t blk = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FBG_WAVE;
+    const unsigned lane = threadIdx.x % FBG_WAVE;
+    if (blk >= nblk) return;
+    uint64_t w[2][P], valid[2];
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        const uint64_t i = blk * PX_BLK + half * 64 + lane;
+        uint32_t c = 0;
+        if (i < N1) {
+            const uint32_t s = sa[i];
+            c = cs[s ? text[s - 1] : 0];    // text[N] is the sentinel: the BWT of slot SA^-1[0] is code 0
+        }
+        valid[half] = __ballot(i < N1);
+#pragma unroll
+        for (int p = 0; p < P; p++) w[half][p] = __ballot((c >> p) & 1u);
+    }
+    uint8_t *ln = lines + blk * PX_LINE;
+    if (lane < 2 * P) {
+        const int half = lane / P, p = lane % P;
+        uint64_t v = 0;
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int q = 0; q < P; q++)
+                if (h == half && q == p) v = w[h][q];
+        *(uint64_t *)(ln + (COMPACT ? 64 : 0) + half * (P * 8) + p * 8) = v;
+    }
+    for (int s = lane; s < S; s += FBG_WAVE)
+        cntT[(uint64_t)s * nblk + blk] = __popcll(px_match<P>(s, w[0]) & valid[0]) + __popcll(px_match<P>(s, w[1]) & valid[1]);
+}
+
+// exclusive counts (cntX, code-major) into the lines (compact) or the block-major count table
+template <bool COMPACT>
+__global__ void k_px_counts(const uint32_t *cntX, uint64_t nblk, int S, uint8_t *lines, uint32_t *cnt_tab)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int SS = COMPACT ? 16 : S;
+    if (t >= nblk * SS) return;
+    const uint64_t blk = t / SS;
+    const int s = (int)(t % SS);
+    const uint32_t v = s < S ? cntX[(uint64_t)s * nblk + blk] : 0u;
+    if (COMPACT) ((uint32_t *)(lines + blk * PX_LINE))[s] = v;
+    else cnt_tab[blk * S + s] = v;
+}
+
+// ---- backward steps ---------------------------------------------------------------------------------------------
+struct PxDev {
+    const uint8_t *lines;
+    const uint32_t *cnt_tab;
+    const uint32_t *bpos, *epos;
+    uint32_t N, nb, ne, S;
+};
+
+__device__ __forceinline__ uint64_t px_low(uint32_t off) { return off >= 64 ? ~0ull : ((1ull << off) - 1); }
+
+// occ(c, i) of a loaded line: planes w[word][plane]
+template <int P> __device__ __forceinline__ uint32_t px_pop(uint32_t c, uint32_t off, const uint64_t (&w)[2][P])
+{
+    const uint32_t a = __popcll(px_match<P>(c, w[0]) & px_low(off));
+    return off > 64 ? a + __popcll(px_match<P>(c, w[1]) & px_low(off - 64)) : a;
+}
+
+template <bool COMPACT> __device__ __forceinline__ uint32_t px_load(const PxDev &d, uint32_t c, uint32_t blk,
+                                                                    uint64_t (&w)[2][COMPACT ? 4 : 8])
+{
+    constexpr int P = COMPACT ? 4 : 8;
+    const uint8_t *ln = d.lines + (uint64_t)blk * PX_LINE;
+    const ulonglong2 *q = (const ulonglong2 *)(ln + (COMPACT ? 64 : 0));
+#pragma unroll
+    for (int k = 0; k < P; k++) {
+        const ulonglong2 v = q[k];
+        w[(2 * k) / P][(2 * k) % P] = v.x;
+        w[(2 * k + 1) / P][(2 * k + 1) % P] = v.y;
+    }
+    return COMPACT ? ((const uint32_t *)ln)[c] : d.cnt_tab[(uint64_t)blk * d.S + c];
+}
+
+// occ(c, l) and occ(c, r1), l <= r1: both loads issued before either is used; one line when both fall in one block
+template <bool COMPACT> __device__ __forceinline__ void px_occ2(const PxDev &d, uint32_t c, uint32_t l, uint32_t r1,
+                                                                uint32_t &ol, uint32_t &or1, uint32_t &nlines)
+{
+    constexpr int P = COMPACT ? 4 : 8;
+    const uint32_t bl = l / PX_BLK, br = r1 / PX_BLK;
+    uint64_t wl[2][P], wr[2][P];
+    const uint32_t cl = px_load<COMPACT>(d, c, bl, wl);
+    uint32_t cr = cl;
+    const bool two = bl != br;
+    if (two) cr = px_load<COMPACT>(d, c, br, wr);
+    ol = cl + px_pop<P>(c, l % PX_BLK, wl);
+    or1 = two ? cr + px_pop<P>(c, r1 % PX_BLK, wr) : cl + px_pop<P>(c, r1 % PX_BLK, wl);
+    nlines += two ? 2u : 1u;
+}
+
+// bs(c, l, r) of sdsl: [C[c] + occ(c, l), C[c] + occ(c, r + 1) - 1]; the count, 0 for an absent symbol
+template <bool COMPACT> __device__ __forceinline__ uint32_t px_bs(const PxDev &d, const uint16_t *code, const uint32_t *C,
+                                                                  uint32_t ch, uint32_t l, uint32_t r, uint32_t &nl,
+                                                                  uint32_t &nr, uint32_t &nlines)
+{
+    const uint32_t c = code[ch];
+    if (c == PX_ABSENT) { nl = l; nr = r; return 0; }
+    uint32_t ol, or1;
+    px_occ2<COMPACT>(d, c, l, r + 1, ol, or1, nlines);
+    nl = C[c] + ol;
+    nr = C[c] + or1 - 1;
+    return or1 - ol;
+}
+
+// One lane per pattern.  SEARCH: rule 4 of the index (a failed step may restart at a block pair boundary), results
+// count / pos by pattern id, patterns taken in the order `order` (by length).  !SEARCH: B / E of the node labels, no
+// restart; a label whose search finds nothing sets no flag (the reference asserts there).
+template <bool SEARCH, bool COMPACT>
+__global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t *code_g, const uint32_t *C_g, const uint8_t *pats,
+                                                       const uint64_t *poff, const uint32_t *order, uint64_t n,
+                                                       unsigned long long *count_out, unsigned long long *pos_out,
+                                                       uint8_t *bflag, uint8_t *eflag, unsigned long long *lines_ctr)
+{
+    __shared__ uint16_t code[256];
+    __shared__ uint32_t C[256];
+    for (int c = threadIdx.x; c < 256; c += blockDim.x) { code[c] = code_g[c]; C[c] = C_g[c]; }
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t nlines = 0;
+    if (t < n) {
+        const uint64_t id = order ? order[t] : t;
+        const uint64_t a = poff[id], len = poff[id + 1] - a;
+        uint32_t l = 0, r = d.N, cnt = 0;
+        uint64_t pos = 0, word = 0;
+        bool ok = true;
+        for (uint64_t k = 0; k < len; k++) {
+            const uint64_t q = a + k;
+            if (k == 0 || (q & 7) == 0) word = *(const uint64_t *)(pats + (q & ~7ull));   // buffer padded to 8 bytes
+            const uint32_t ch = (uint32_t)(word >> (8 * (q & 7))) & 0xffu;
+            uint32_t nl, nr;
+            cnt = px_bs<COMPACT>(d, code, C, ch, l, r, nl, nr, nlines);
+            if (cnt) {
+                l = nl; r = nr;
+            } else {
+                if (!SEARCH) { ok = false; break; }
+                // restart: the range must be able to step over '#', and B / E must enclose it
+                uint32_t sl, sr;
+                if (!px_bs<COMPACT>(d, code, C, '#', l, r, sl, sr, nlines)) { ok = false; break; }
+                uint32_t lo = 0, hi = d.nb;       // r1 = #B positions <= l
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) / 2;
+                    if (d.bpos[mid] <= l) lo = mid + 1; else hi = mid;
+                }
+                const uint32_t r1 = lo;
+                if (r1 == 0 || r1 > d.ne) { ok = false; break; }
+                const uint32_t bl = d.bpos[r1 - 1], br = d.epos[r1 - 1];
+                if (!(bl <= l && r <= br)) { ok = false; break; }
+                cnt = px_bs<COMPACT>(d, code, C, ch, bl, br, nl, nr, nlines);
+                if (!cnt) { ok = false; break; }
+                l = nl; r = nr;
+            }
+            pos++;
+        }
+        if (SEARCH) {
+            count_out[id] = ok ? cnt : 0u;
+            pos_out[id] = pos;
+        } else if (ok) {
+            bflag[l] = 1;
+            eflag[r] = 1;
+        }
+    }
+    if (SEARCH) {
+        unsigned long long s = nlines;
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if ((threadIdx.x % FBG_WAVE) == 0 && s) atomicAdd(lines_ctr, s);
+    }
+}
+
+__global__ void k_px_lenkey(const uint64_t *poff, uint64_t n, uint32_t *key, uint32_t *id)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint64_t len = poff[t + 1] - poff[t];
+    key[t] = len > 0xffffffffull ? 0xffffffffu : (uint32_t)len;
+    id[t] = (uint32_t)t;
+}
+
+__global__ void k_px_rebase(uint64_t *off, uint64_t n, uint64_t base)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= n) off[t] -= base;
+}
+
+static PxDev px_dev(const fbg_pindex *ix)
+{
+    PxDev d;
+    d.lines = ix->lines.as<uint8_t>();
+    d.cnt_tab = ix->cnt_tab.as<uint32_t>();
+    d.bpos = ix->bpos.as<uint32_t>();
+    d.epos = ix->epos.as<uint32_t>();
+    d.N = (uint32_t)(ix->N1 - 1);
+    d.nb = ix->nb; d.ne = ix->ne;
+    d.S = (uint32_t)ix->sigma;
+    return d;
+}
+
+// ---- build ----------------------------------------------------------------------------------------------------
+struct PxScratch {
+    DevBuf labels, loff, esrc, edst, elen, eoff, keysA, keysB, valsA, valsB, cidx, cidx2, rank, headv, hscan, head, keep,
+           cntT, cntX, code_u8, count;
+    ~PxScratch()
+    {
+        for (DevBuf *b : {&labels, &loff, &esrc, &edst, &elen, &eoff, &keysA, &keysB, &valsA, &valsB, &cidx, &cidx2, &rank,
+                          &headv, &hscan, &head, &keep, &cntT, &cntX, &code_u8, &count})
+            px_free(*b);
+    }
+};
+
+struct PxMul {
+    uint64_t m;
+    __host__ __device__ uint64_t operator()(uint64_t s) const { return s * m; }
+};
+
+static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
+                    const uint64_t *edge_off, const uint64_t *edge_dst)
+{
+    fbg_ctx *ctx = ix->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t L = n_nodes ? label_off[n_nodes] - label_off[0] : 0;
+    const uint64_t lbase = n_nodes ? label_off[0] : 0;
+    // labels: no '#', no zero byte (both are separators of the text)
+    for (uint64_t u = 0; u < n_nodes; u++)
+        if (label_off[u + 1] < label_off[u]) return fbg_fail(ctx, FBG_ERR_INVALID, "label offsets decrease at node %llu", (unsigned long long)u);
+    for (uint64_t k = 0; k < L; k++) {
+        const uint8_t c = labels[lbase + k];
+        if (c == '#' || c == 0)
+            return fbg_fail(ctx, FBG_ERR_INVALID, "node labels may not contain '#' or a zero byte (byte %llu of the labels)", (unsigned long long)k);
+    }
+    if (n_nodes >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%llu nodes: at most 2^32 - 2", (unsigned long long)n_nodes);
+    // distinct out-edges in ascending order (std::set), the text length and its byte histogram
+    std::vector<uint32_t> esrc, edst, tmpv;
+    std::vector<uint64_t> use(n_nodes, 0);
+    uint64_t N1 = 1;
+    for (uint64_t u = 0; u < n_nodes; u++) {
+        if (edge_off[u + 1] < edge_off[u]) return fbg_fail(ctx, FBG_ERR_INVALID, "edge offsets decrease at node %llu", (unsigned long long)u);
+        tmpv.clear();
+        for (uint64_t e = edge_off[u]; e < edge_off[u + 1]; e++) {
+            if (edge_dst[e] >= n_nodes)
+                return fbg_fail(ctx, FBG_ERR_INVALID, "edge %llu -> %llu: no such node", (unsigned long long)u, (unsigned long long)edge_dst[e]);
+            tmpv.push_back((uint32_t)edge_dst[e]);
+        }
+        std::sort(tmpv.begin(), tmpv.end());
+        tmpv.erase(std::unique(tmpv.begin(), tmpv.end()), tmpv.end());
+        for (uint32_t v : tmpv) {
+            esrc.push_back((uint32_t)u);
+            edst.push_back(v);
+            use[u]++; use[v]++;
+            N1 += (label_off[u + 1] - label_off[u]) + (label_off[v + 1] - label_off[v]) + 1;
+            if (N1 >= (1ull << 32))
+                return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "the edge text of this graph has 2^32 symbols or more; the pattern index "
+                                "takes texts of N + 1 < 2^32 symbols");
+        }
+    }
+    const uint64_t E = esrc.size();
+    uint64_t hist[256] = {0};
+    hist[0] = 1;
+    hist['#'] = E;
+    for (uint64_t u = 0; u < n_nodes; u++)
+        if (use[u])
+            for (uint64_t k = label_off[u]; k < label_off[u + 1]; k++) hist[labels[k]] += use[u];
+    uint16_t code[256];
+    uint8_t code_u8[256];
+    uint32_t C[256];
+    int sigma = 0;
+    uint64_t acc = 0;
+    for (int c = 0; c < 256; c++) {
+        code[c] = hist[c] ? (uint16_t)sigma : (uint16_t)PX_ABSENT;
+        code_u8[c] = hist[c] ? (uint8_t)sigma : 0;
+        if (hist[c]) { C[sigma] = (uint32_t)acc; acc += hist[c]; sigma++; }
+    }
+    for (int s = sigma; s < 256; s++) C[s] = (uint32_t)acc;
+    ix->N1 = N1;
+    ix->sigma = sigma;
+    ix->compact = sigma <= 16;
+    ix->n_nodes = n_nodes;
+    ix->nblk = N1 / PX_BLK + 1;
+
+    PxScratch s;
+    auto U = [&](DevBuf &b, const void *h, size_t bytes) -> int {
+        FBG_TRY(px_reserve(ix, b, bytes + 8));
+        if (bytes) FBG_HIP_TRY(ctx, hipMemcpyAsync(b.p, h, bytes, hipMemcpyHostToDevice, st));
+        return FBG_OK;
+    };
+    // labels (padded to whole 8-byte words for the walk's reads) and offsets rebased to 0
+    FBG_TRY(px_reserve(ix, s.labels, ((L + 7) & ~7ull) + 16));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(s.labels.p, 0, s.labels.cap, st));
+    if (L) FBG_HIP_TRY(ctx, hipMemcpyAsync(s.labels.p, labels + lbase, L, hipMemcpyHostToDevice, st));
+    FBG_TRY(U(s.loff, label_off, (n_nodes + 1) * 8));
+    if (lbase) hipLaunchKernelGGL(k_px_rebase, dim3(fbg_blocks(n_nodes + 1, 256)), dim3(256), 0, st, s.loff.as<uint64_t>(), n_nodes, lbase);
+    FBG_TRY(U(s.esrc, esrc.data(), E * 4));
+    FBG_TRY(U(s.edst, edst.data(), E * 4));
+    FBG_TRY(U(s.code_u8, code_u8, 256));
+    FBG_TRY(U(ix->code, code, sizeof(code)));
+    FBG_TRY(U(ix->C, C, sizeof(C)));
+
+    // text
+    FBG_TRY(px_reserve(ix, ix->text, N1 + 64));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->text.p, 0, ix->text.cap, st));
+    if (E) {
+        FBG_TRY(px_reserve(ix, s.elen, E * 8));
+        FBG_TRY(px_reserve(ix, s.eoff, E * 8));
+        hipLaunchKernelGGL(k_px_edge_len, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, s.esrc.as<uint32_t>(), s.edst.as<uint32_t>(),
+                           s.loff.as<uint64_t>(), E, s.elen.as<uint64_t>());
+        uint64_t *elen = s.elen.as<uint64_t>(), *eoff = s.eoff.as<uint64_t>();
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, elen, eoff, (uint64_t)0, (size_t)E, rocprim::plus<uint64_t>(), st);
+        }));
+        hipLaunchKernelGGL(k_px_edge_text, dim3(fbg_blocks(E * FBG_WAVE, PX_THREADS)), dim3(PX_THREADS), 0, st, s.labels.as<uint8_t>(),
+                           s.loff.as<uint64_t>(), s.esrc.as<uint32_t>(), s.edst.as<uint32_t>(), eoff, E, ix->text.as<uint8_t>());
+    }
+
+    // suffix array
+    int b = 1;
+    while ((1 << b) < sigma) b++;
+    const int K = 64 / b;
+    int pb = 1;
+    while ((1ull << pb) < N1) pb++;
+    FBG_TRY(px_reserve(ix, ix->sa, N1 * 4));
+    for (DevBuf *d : {&s.keysA, &s.keysB}) FBG_TRY(px_reserve(ix, *d, N1 * 8));
+    for (DevBuf *d : {&s.valsA, &s.valsB, &s.cidx, &s.cidx2, &s.rank, &s.headv, &s.hscan}) FBG_TRY(px_reserve(ix, *d, N1 * 4));
+    for (DevBuf *d : {&s.head, &s.keep}) FBG_TRY(px_reserve(ix, *d, N1));
+    FBG_TRY(px_reserve(ix, s.count, 8));
+    uint64_t *kA = s.keysA.as<uint64_t>(), *kB = s.keysB.as<uint64_t>();
+    uint32_t *vA = s.valsA.as<uint32_t>(), *vB = s.valsB.as<uint32_t>();
+    uint32_t *sa = ix->sa.as<uint32_t>(), *rank = s.rank.as<uint32_t>(), *headv = s.headv.as<uint32_t>(), *hscan = s.hscan.as<uint32_t>();
+    uint8_t *head = s.head.as<uint8_t>(), *keep = s.keep.as<uint8_t>();
+    uint32_t *cidx = s.cidx.as<uint32_t>(), *cidx2 = s.cidx2.as<uint32_t>();
+    hipLaunchKernelGGL(k_px_keys0, dim3(fbg_blocks(N1, 256)), dim3(256), 0, st, ix->text.as<uint8_t>(), s.code_u8.as<uint8_t>(), N1, b, K,
+                       kA, vA, cidx);
+    uint64_t cnt = N1, h = (uint64_t)K;
+    unsigned end_bit = (unsigned)(K * b);
+    for (int round = 0; cnt > 0; round++) {
+        if (round > 0) {
+            hipLaunchKernelGGL(k_px_keysh, dim3(fbg_blocks(cnt, 256)), dim3(256), 0, st, cidx, cnt, sa, rank, h, N1, pb, kA, vA);
+            end_bit = (unsigned)(2 * pb);
+            h *= 2;
+        }
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, kA, kB, vA, vB, (size_t)cnt, 0u, end_bit, st);
+        }));
+        hipLaunchKernelGGL(k_px_place, dim3(fbg_blocks(cnt, 256)), dim3(256), 0, st, kB, vB, cidx, cnt, sa, headv, head);
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::inclusive_scan(tmp, bytes, headv, hscan, (size_t)cnt, rocprim::maximum<uint32_t>(), st);
+        }));
+        hipLaunchKernelGGL(k_px_rank, dim3(fbg_blocks(cnt, 256)), dim3(256), 0, st, vB, hscan, head, cnt, rank, keep);
+        uint64_t *d_count = s.count.as<uint64_t>();
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::select(tmp, bytes, cidx, keep, cidx2, d_count, (size_t)cnt, st);
+        }));
+        uint64_t next = 0;
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(&next, d_count, 8, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        cnt = next;
+        std::swap(cidx, cidx2);
+        if (round > 40) return fbg_fail(ctx, FBG_ERR_HIP, "pattern index: the suffix sort did not converge");
+    }
+
+    // BWT and occ lines
+    const int S = sigma;
+    const uint64_t nblk = ix->nblk;
+    FBG_TRY(px_reserve(ix, ix->lines, nblk * PX_LINE));
+    FBG_TRY(px_reserve(ix, s.cntT, nblk * S * 4));
+    FBG_TRY(px_reserve(ix, s.cntX, nblk * S * 4));
+    if (!ix->compact) FBG_TRY(px_reserve(ix, ix->cnt_tab, nblk * S * 4));
+    const dim3 gl(fbg_blocks(nblk * FBG_WAVE, PX_THREADS));
+    if (ix->compact)
+        hipLaunchKernelGGL(k_px_lines<true>, gl, dim3(PX_THREADS), 0, st, sa, ix->text.as<uint8_t>(), s.code_u8.as<uint8_t>(), N1, nblk, S,
+                           ix->lines.as<uint8_t>(), s.cntT.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_px_lines<false>, gl, dim3(PX_THREADS), 0, st, sa, ix->text.as<uint8_t>(), s.code_u8.as<uint8_t>(), N1, nblk, S,
+                           ix->lines.as<uint8_t>(), s.cntT.as<uint32_t>());
+    {
+        uint32_t *in = s.cntT.as<uint32_t>(), *out = s.cntX.as<uint32_t>();
+        auto begins = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), PxMul{nblk});
+        auto ends = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(1), PxMul{nblk});
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::segmented_exclusive_scan(tmp, bytes, in, out, (unsigned)S, begins, ends, (uint32_t)0,
+                                                     rocprim::plus<uint32_t>(), st);
+        }));
+    }
+    if (ix->compact)
+        hipLaunchKernelGGL(k_px_counts<true>, dim3(fbg_blocks(nblk * 16, 256)), dim3(256), 0, st, s.cntX.as<uint32_t>(), nblk, S,
+                           ix->lines.as<uint8_t>(), (uint32_t *)nullptr);
+    else
+        hipLaunchKernelGGL(k_px_counts<false>, dim3(fbg_blocks(nblk * S, 256)), dim3(256), 0, st, s.cntX.as<uint32_t>(), nblk, S,
+                           ix->lines.as<uint8_t>(), ix->cnt_tab.as<uint32_t>());
+
+    // B / E: flags by position, compacted in position order (sorted, each position once)
+    uint8_t *bflag = s.head.as<uint8_t>(), *eflag = s.keep.as<uint8_t>();
+    FBG_HIP_TRY(ctx, hipMemsetAsync(bflag, 0, N1, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(eflag, 0, N1, st));
+    ix->nb = ix->ne = 0;
+    PxDev d = px_dev(ix);
+    if (n_nodes) {
+        const dim3 gw(fbg_blocks(n_nodes, PX_THREADS));
+        if (ix->compact)
+            hipLaunchKernelGGL((k_px_walk<false, true>), gw, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
+                               s.labels.as<uint8_t>(), s.loff.as<uint64_t>(), (const uint32_t *)nullptr, n_nodes,
+                               (unsigned long long *)nullptr, (unsigned long long *)nullptr, bflag, eflag, (unsigned long long *)nullptr);
+        else
+            hipLaunchKernelGGL((k_px_walk<false, false>), gw, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
+                               s.labels.as<uint8_t>(), s.loff.as<uint64_t>(), (const uint32_t *)nullptr, n_nodes,
+                               (unsigned long long *)nullptr, (unsigned long long *)nullptr, bflag, eflag, (unsigned long long *)nullptr);
+    }
+    FBG_TRY(px_reserve(ix, ix->bpos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4));
+    FBG_TRY(px_reserve(ix, ix->epos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4));
+    uint64_t nbe[2] = {0, 0};
+    for (int k = 0; k < 2; k++) {
+        uint8_t *fl = k ? eflag : bflag;
+        uint32_t *out = (k ? ix->epos : ix->bpos).as<uint32_t>();
+        uint64_t *d_count = s.count.as<uint64_t>();
+        auto it = rocprim::make_counting_iterator<uint32_t>(0);
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::select(tmp, bytes, it, fl, out, d_count, (size_t)N1, st);
+        }));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(&nbe[k], d_count, 8, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    ix->nb = (uint32_t)nbe[0];
+    ix->ne = (uint32_t)nbe[1];
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    px_free(ix->tmp);
+    return FBG_OK;
+}
+
+static void px_destroy(fbg_pindex *ix)
+{
+    if (!ix) return;
+    if (ix->ctx) {
+        (void)hipSetDevice(ix->ctx->device);
+        (void)hipStreamSynchronize(ix->ctx->stream);
+    }
+    for (DevBuf *b : {&ix->text, &ix->sa, &ix->lines, &ix->cnt_tab, &ix->C, &ix->code, &ix->bpos, &ix->epos, &ix->pats, &ix->poff,
+                      &ix->okey, &ix->oval, &ix->okey2, &ix->oval2, &ix->cnt_out, &ix->pos_out, &ix->lines_ctr, &ix->tmp})
+        px_free(*b);
+    if (ix->ev0) (void)hipEventDestroy(ix->ev0);
+    if (ix->ev1) (void)hipEventDestroy(ix->ev1);
+    delete ix;
+}
+
+// ---- C ABI ------------------------------------------------------------------------------------------------------
+extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
+                                const uint64_t *edge_off, const uint64_t *edge_dst, fbg_pindex **out)
+{
+    if (!ctx) return FBG_ERR_INVALID;
+    if (!out || (n_nodes && (!label_off || !edge_off)) ||
+        (n_nodes && label_off[n_nodes] > label_off[0] && !labels) || (n_nodes && edge_off[n_nodes] > edge_off[0] && !edge_dst))
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_build: missing argument");
+    *out = nullptr;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    fbg_pindex *ix = new fbg_pindex();
+    ix->ctx = ctx;
+    int rc = px_build(ix, labels, label_off, n_nodes, edge_off, edge_dst);
+    if (rc != FBG_OK) { px_destroy(ix); return rc; }
+    ix->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = ix;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_locate(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                                 uint64_t *count, uint64_t *pos)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    if (n_patterns && (!pat_off || !count || !pos)) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_locate: missing argument");
+    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_locate: at most 2^32 - 2 patterns per call");
+    ix->search_ms = 0;
+    ix->occ_lines = 0;
+    if (n_patterns == 0) return FBG_OK;
+    for (uint64_t k = 0; k < n_patterns; k++)
+        if (pat_off[k + 1] < pat_off[k]) return fbg_fail(ctx, FBG_ERR_INVALID, "pattern offsets decrease at pattern %llu", (unsigned long long)k);
+    const uint64_t base = pat_off[0], total = pat_off[n_patterns] - base;
+    if (total && !patterns) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_locate: missing patterns");
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = n_patterns;
+    FBG_TRY(px_reserve(ix, ix->pats, ((total + 7) & ~7ull) + 16));
+    FBG_TRY(px_reserve(ix, ix->poff, (n + 1) * 8));
+    for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(px_reserve(ix, *b, n * 4));
+    FBG_TRY(px_reserve(ix, ix->cnt_out, n * 8));
+    FBG_TRY(px_reserve(ix, ix->pos_out, n * 8));
+    FBG_TRY(px_reserve(ix, ix->lines_ctr, 8));
+    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
+    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    if (total) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->pats.p, patterns + base, total, hipMemcpyHostToDevice, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->poff.p, pat_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->lines_ctr.p, 0, 8, st));
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    uint64_t *poff = ix->poff.as<uint64_t>();
+    if (base) hipLaunchKernelGGL(k_px_rebase, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, poff, n, base);
+    // lanes of a wave take patterns of similar length: pattern ids sorted by length
+    uint32_t *ka = ix->okey.as<uint32_t>(), *va = ix->oval.as<uint32_t>(), *kb = ix->okey2.as<uint32_t>(), *vb = ix->oval2.as<uint32_t>();
+    hipLaunchKernelGGL(k_px_lenkey, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, poff, n, ka, va);
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, ka, kb, va, vb, (size_t)n, 0u, 32u, st);
+    }));
+    PxDev d = px_dev(ix);
+    const dim3 g(fbg_blocks(n, PX_THREADS));
+    auto *co = ix->cnt_out.as<unsigned long long>(), *po = ix->pos_out.as<unsigned long long>();
+    auto *lc = ix->lines_ctr.as<unsigned long long>();
+    if (ix->compact)
+        hipLaunchKernelGGL((k_px_walk<true, true>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
+                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc);
+    else
+        hipLaunchKernelGGL((k_px_walk<true, false>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
+                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(count, co, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(pos, po, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&ix->occ_lines, lc, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    ix->search_ms = ms;
+    return FBG_OK;
+}
+
+extern "C" uint64_t fbg_pindex_text_length(const fbg_pindex *ix) { return ix ? ix->N1 : 0; }
+
+extern "C" int fbg_pindex_download(fbg_pindex *ix, uint8_t *text, uint32_t *sa, uint32_t *b_positions, uint32_t *e_positions,
+                                   uint64_t *nb, uint64_t *ne)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (text) FBG_HIP_TRY(ctx, hipMemcpyAsync(text, ix->text.p, ix->N1, hipMemcpyDeviceToHost, st));
+    if (sa) FBG_HIP_TRY(ctx, hipMemcpyAsync(sa, ix->sa.p, ix->N1 * 4, hipMemcpyDeviceToHost, st));
+    if (b_positions && ix->nb) FBG_HIP_TRY(ctx, hipMemcpyAsync(b_positions, ix->bpos.p, (size_t)ix->nb * 4, hipMemcpyDeviceToHost, st));
+    if (e_positions && ix->ne) FBG_HIP_TRY(ctx, hipMemcpyAsync(e_positions, ix->epos.p, (size_t)ix->ne * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (nb) *nb = ix->nb;
+    if (ne) *ne = ix->ne;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_stats(const fbg_pindex *ix, uint64_t *index_bytes, double *build_ms, double *search_ms,
+                                uint64_t *occ_lines)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    if (index_bytes)
+        *index_bytes = ix->nblk * PX_LINE + (ix->compact ? 0 : ix->nblk * ix->sigma * 4) + 4ull * (ix->nb + ix->ne) + 256 * 6;
+    if (build_ms) *build_ms = ix->build_ms;
+    if (search_ms) *search_ms = ix->search_ms;
+    if (occ_lines) *occ_lines = ix->occ_lines;
+    return FBG_OK;
+}
+
+extern "C" void fbg_pindex_destroy(fbg_pindex *ix) { px_destroy(ix); }

@@ -368,6 +368,46 @@ int fbg_group_scan_f(fbg_group *g, const uint8_t *ignore_chars, uint64_t ignore_
 void *fbg_host_alloc(uint64_t bytes);
 void fbg_host_free(void *p);
 
+/* ---- pattern index of a founder graph (locate.hip) ---------------------------------------------------------------
+ *
+ * The query side of the reference's founder_block_index (make_index, fbg.cpp:2809-2953; backward_search,
+ * founder_block_index.hpp:86-145), built and searched on the GPU.  The graph: n_nodes labels in node id order
+ * (labels + label_off[u] .. label_off[u + 1]; '#' and zero bytes are refused with FBG_ERR_INVALID, empty labels are
+ * fine) and out-edges as CSR by source (edge_dst[edge_off[u] .. edge_off[u + 1]), node indices; duplicates count
+ * once).  All arguments are host buffers.
+ *   text   for every node u in id order and every distinct v in its out-edges, ascending: reverse(label(u) +
+ *          label(v) + '#'); then one 0 sentinel.  N + 1 < 2^32 symbols (else FBG_ERR_TOO_LARGE).
+ *   SA     full suffix array of the text, unsigned byte order; bs(c, l, r) the one-symbol backward step over its BWT.
+ *   B / E  every label searched left to right from [0, N] sets B[lhs] and E[rhs] (sorted position lists, each
+ *          position once).  A label whose search finds nothing sets nothing (the reference asserts there).
+ *   locate each pattern left to right from [0, N]: a step that finds nothing may restart once per symbol at a block
+ *          pair boundary ('#' must follow the range, r1 = #B positions <= l > 0, [select_B(r1), select_E(r1)] must
+ *          enclose the range -- r1 beyond the E positions: not found -- and the symbol must occur in it); else the
+ *          search stops.  count = the size of the last range (what locate_patterns prints: occurrences in the BWT
+ *          index, not exact path matches), 0 when the search stopped; pos = symbols matched.  Empty pattern: (0, 0).
+ * An index borrows its context's device and stream (destroy it before the context) and owns all of its buffers; the context's MSA, MSA index and
+ * every other call are unaffected.  Calls on one index and its context are serialised by the caller.
+ */
+typedef struct fbg_pindex fbg_pindex;
+int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
+                     const uint64_t *edge_off, const uint64_t *edge_dst, fbg_pindex **out);
+/* patterns + pat_off[k] .. pat_off[k + 1]; count, pos: n_patterns values each */
+int fbg_pindex_locate(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                      uint64_t *count, uint64_t *pos);
+/* N + 1, the text length including the sentinel */
+uint64_t fbg_pindex_text_length(const fbg_pindex *ix);
+/* For tests; any pointer may be NULL.  text: N + 1 bytes, sa: N + 1 values, b_positions / e_positions: *nb / *ne
+ * values (at most n_nodes each; call with NULL lists first to learn the sizes). */
+int fbg_pindex_download(fbg_pindex *ix, uint8_t *text, uint32_t *sa, uint32_t *b_positions, uint32_t *e_positions,
+                        uint64_t *nb, uint64_t *ne);
+/* Measurement (any pointer may be NULL): device bytes of the search structure (occ lines, count table, B / E,
+ * symbol tables; the text and SA kept for fbg_pindex_download are not counted), host wall time of the build in ms,
+ * device time of the last fbg_pindex_locate in ms (length sort + search kernel, without the copies), and the occ
+ * lines its search read. */
+int fbg_pindex_stats(const fbg_pindex *ix, uint64_t *index_bytes, double *build_ms, double *search_ms,
+                     uint64_t *occ_lines);
+void fbg_pindex_destroy(fbg_pindex *ix);
+
 #ifdef __cplusplus
 }
 #endif
