@@ -21,8 +21,13 @@ of it is joined before the closing barrier, inside the timed region.  --serial-s
 Prints ONE JSON line on rank 0.  `roofline` prices the kernel of the step that takes longest among those
 with HIP-event brackets of their own: the extension scan (k_rank_scan_lean / k_rank_scan; k_scan_stream when
 the MSA has gaps) with (13*m + 8) bytes per column, the three passes of the MSD sort with
-the bytes a pass must move (9 / 16 / 16 per suffix); `roofline.kernels` lists all of them.  `cpu_baseline` times the CPU restatement (oracle/, kind "port") on a bounded column prefix
-of the same MSA.
+the bytes a pass must move (9 / 16 / 16 per suffix); `roofline.kernels` lists all of them.  Both come from the
+timed steps themselves.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; what takes runs of its
+own is measured only with --full (at N=1): `cpu_baseline` times the CPU restatement (oracle/, kind "port") on a
+bounded column prefix of the same MSA (--no-cpu-baseline skips it), and `boundary_ms` / `t_seg` / `latency_ms` /
+`other_workloads` are measured after the timed steps (--no-extras skips them).  Without --full `cpu_baseline` is null.
 """
 import argparse
 import json
@@ -310,9 +315,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=1000)
     ap.add_argument("--cols-per-gpu", type=int, default=1_000_000)
-    ap.add_argument("--cpu-sample-cols", type=int, default=100_000, help="column prefix the CPU port is timed on (SURVEY.md 8d: n' >= 10^5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip boundary_ms / latency_ms / other_workloads (N=1 extras outside the timed region)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need (N=1): cpu_baseline, "
+                                                        "boundary_ms / t_seg / latency_ms / other_workloads")
+    ap.add_argument("--cpu-sample-cols", type=int, default=100_000, help="--full: column prefix the CPU port is timed on (SURVEY.md 8d: n' >= 10^5)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip boundary_ms / latency_ms / other_workloads (N=1 extras outside the timed region)")
     ap.add_argument("--force-row-pairs", type=int, default=0, help="debug: use the row-group-pair plan with this many rows per pair text")
     ap.add_argument("--replicated-index", action="store_true", help="N>1: every rank builds the whole index (column shards) instead of one key range of it")
     ap.add_argument("--backend", default="nccl", help="nccl (RCCL, default) | gloo (debug: several ranks on one GPU)")
@@ -541,7 +548,7 @@ def main():
                                    f"{'' if world == 1 else f', {args.cols_per_gpu} columns per GPU, {mode_used}'}",
                        "value_is": "columns of the whole job / wall time of the timed steps, MSA resident in HBM, boundaries left on the "
                                    "device, the sweep of a step running beside the next step's index build; T_seg of SURVEY.md 8(d) "
-                                   "(host RAM to host RAM) is `t_seg`, one job alone is `latency_ms`",
+                                   "(host RAM to host RAM) is `t_seg`, one job alone is `latency_ms` (both with --full)",
                        "rows": m, "cols": n, "text_length": m * (n + 1) + 1, "blocks": state.get("blocks")},
             "roofline": {"bound": "hbm", "kernel": dominant, "achieved": dom["achieved"], "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": dom["frac"],
@@ -558,11 +565,11 @@ def main():
                        "dp_ms_last_step": sweeper.eng.stage_ms().get("dp", (0.0, 0))[0]}),
             "device_bytes": eng.device_bytes(),
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(m, n, min(args.cpu_sample_cols, n))
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             if sweeper is not None:
                 sweeper.eng.release_scratch()
             extras = boundary_and_latency(F, torch, dev, m, n, whole_msa())
