@@ -309,6 +309,11 @@ class Engine:
         self._pindexes.add(pix)
         return pix
 
+    def validate_graph(self, labels, edges, blocks, ignorechars=""):
+        """Semi-repeat-free check of a founder graph (PatternIndex.validate on a temporary index of the graph)."""
+        with self.pattern_index(labels, edges) as pix:
+            return pix.validate(blocks, ignorechars)
+
 
 def _concat(strings):
     """(uint8 bytes, uint64 offsets[len + 1]) of a list of str / bytes, or such a pair passed through."""
@@ -395,11 +400,65 @@ class PatternIndex:
         self._eng._chk(self._L.fbg_pindex_stats(self._h, C.byref(ib), C.byref(bm), C.byref(sm), C.byref(ol)))
         return {"index_bytes": ib.value, "build_ms": bm.value, "search_ms": sm.value, "occ_lines": ol.value}
 
+    def validate(self, blocks, ignorechars=""):
+        """Semi-repeat-free check of the index's graph (fbg_pindex_validate): `blocks` holds one block id per node
+        (0 .. 2^32 - 1; only equality decides a node's status, bad_cuts reads them as block indices from 0).  Nodes
+        whose label holds a byte of `ignorechars` are skipped.  -> Validation."""
+        n = self.n_nodes
+        blk = np.asarray(blocks).ravel()
+        if len(blk) != n:
+            raise ValueError(f"blocks has {len(blk)} entries for {n} nodes")
+        if n and (blk.min() < 0 or blk.max() > 0xffffffff):
+            raise ValueError("block ids must lie in 0 .. 2^32 - 1")
+        blk32 = np.ascontiguousarray(blk, dtype=np.uint32)
+        ig, il = _ignore(ignorechars)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        wn = np.zeros(max(n, 1), dtype=np.uint64)
+        wo = np.zeros(max(n, 1), dtype=np.uint64)
+        bad, ms = C.c_uint64(0), C.c_double(0)
+        self._eng._chk(self._L.fbg_pindex_validate(self._h, blk32.ctypes.data_as(_lib.u32p), _u8(ig), il, _u8(status), _u64(wn),
+                                                   _u64(wo), C.byref(bad), C.byref(ms)))
+        slots, waves, tb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._eng._chk(self._L.fbg_pindex_validate_stats(self._h, C.byref(slots), C.byref(waves), C.byref(tb)))
+        return Validation(status[:n], wn[:n], wo[:n], blk.astype(np.int64), ms.value, slots.value, waves.value)
 
-def read_xgfa(path):
+
+class Validation:
+    """Result of PatternIndex.validate / Engine.validate_graph:
+      status          uint8[n], FBG_NODE_* (0 valid, 1 invalid, 2 source / sink, 3 ignored, 4 empty label)
+      witness_node    int64[n], the node of an INVALID node's witness occurrence, -1 where there is none
+      witness_offset  int64[n], its offset in that node's label, -1 where there is none
+      valid           no node is INVALID
+      invalid_nodes   int64 indices of the INVALID nodes, ascending
+      bad_cuts        sorted distinct b - 1 over the blocks b > 0 that hold an INVALID node (the reference's to_remove)
+      device_ms       device time of the validation kernels
+      slots_scanned, wave_nodes   SA slots read and nodes scanned by the wave tier (fbg_pindex_validate_stats)"""
+
+    def __init__(self, status, wn, wo, blocks, device_ms, slots_scanned, wave_nodes):
+        none = wn == np.uint64(0xffffffffffffffff)
+        self.status = status
+        self.witness_node = np.where(none, -1, wn.astype(np.int64))
+        self.witness_offset = np.where(wo == np.uint64(0xffffffffffffffff), -1, wo.astype(np.int64))
+        self.invalid_nodes = np.nonzero(status == _lib.NODE_INVALID)[0].astype(np.int64)
+        self.valid = len(self.invalid_nodes) == 0
+        cuts = blocks[self.invalid_nodes]
+        self.bad_cuts = np.unique(cuts[cuts > 0] - 1).astype(np.int64)
+        self.device_ms = device_ms
+        self.slots_scanned = slots_scanned
+        self.wave_nodes = wave_nodes
+
+    def counts(self):
+        """{valid, invalid, source_sink, ignored, empty}: nodes per status."""
+        c = np.bincount(self.status, minlength=5)
+        return dict(zip(("valid", "invalid", "source_sink", "ignored", "empty"), (int(x) for x in c[:5])))
+
+
+def read_xgfa(path, blocks=False):
     """(labels, edges) of an xGFA (or GFA) file: S lines sorted by id (0- or 1-based alike), L lines as (u, v) pairs of
-    indices into labels.  Empty labels are kept."""
-    ids, labs, links = [], [], []
+    indices into labels.  Empty labels are kept.  blocks=True: (labels, edges, node_block), node_block int64[n] the
+    block (from 0) of every node from the B line, whose sizes cover the nodes in ascending S id (xGFAspec.md);
+    ValueError when the B line is missing or its sizes do not sum to the node count."""
+    ids, labs, links, bline = [], [], [], None
     with open(path, "rb") as fh:
         for line in fh:
             f = line.rstrip(b"\r\n").split(b"\t")
@@ -408,15 +467,28 @@ def read_xgfa(path):
                 labs.append(f[2] if len(f) > 2 else b"")
             elif f[0] == b"L":
                 links.append((int(f[1]), int(f[3])))
+            elif f[0] == b"B" and blocks:
+                if bline is not None:
+                    raise ValueError(f"{path}: a second B line")
+                bline = [int(x) for x in f[1:] if x != b""]
     order = sorted(range(len(ids)), key=lambda k: ids[k])
     where = {ids[k]: i for i, k in enumerate(order)}
-    return [labs[k] for k in order], [(where[u], where[v]) for u, v in links]
+    out = [labs[k] for k in order], [(where[u], where[v]) for u, v in links]
+    if not blocks:
+        return out
+    if bline is None:
+        raise ValueError(f"{path}: no B line (block sizes)")
+    sizes = np.array(bline, dtype=np.int64)
+    if (sizes < 0).any() or int(sizes.sum()) != len(ids):
+        raise ValueError(f"{path}: the B line's block sizes sum to {int(sizes.sum())}, not to the {len(ids)} nodes")
+    return out + (np.repeat(np.arange(len(sizes), dtype=np.int64), sizes),)
 
 
-def graph_from_segmentation(engine, msa, boundaries, packed=False):
+def graph_from_segmentation(engine, msa, boundaries, packed=False, with_blocks=False):
     """(labels, edges) of the elastic founder graph of a segmentation of `msa` (the nodes and edges of
     Engine.block_graph; the MSA becomes the engine's current one).  Labels are the gap-stripped rows of the blocks:
-    a list of bytes, or with packed=True a pair (uint8 data, uint64 offsets); edges an (E, 2) int64 array."""
+    a list of bytes, or with packed=True a pair (uint8 data, uint64 offsets); edges an (E, 2) int64 array.
+    with_blocks=True: (labels, edges, node_block), node_block int64[n] the block (from 0) of every node."""
     msa = as_msa(msa)
     m, n = msa.shape
     engine.msa_load_host(msa)
@@ -436,10 +508,11 @@ def graph_from_segmentation(engine, msa, boundaries, packed=False):
         off[1:] = np.cumsum(np.concatenate(lens), dtype=np.uint64)
     sel = edges[np.arange(m)[None, :] < ecount[:, None].astype(np.int64)]
     pairs = np.stack(((sel >> np.uint64(32)).astype(np.int64), (sel & np.uint64(0xffffffff)).astype(np.int64)), axis=1)
+    extra = (np.repeat(np.arange(len(b), dtype=np.int64), np.diff(first.astype(np.int64))),) if with_blocks else ()
     if packed:
-        return (data, off), pairs
+        return ((data, off), pairs) + extra
     raw = data.tobytes()
-    return [raw[int(off[k]):int(off[k + 1])] for k in range(len(off) - 1)], pairs
+    return ([raw[int(off[k]):int(off[k + 1])] for k in range(len(off) - 1)], pairs) + extra
 
 
 class _DeviceArray:

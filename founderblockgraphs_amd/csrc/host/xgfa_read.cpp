@@ -37,6 +37,9 @@ bool read_xgfa_graph(const std::string &path, XgfaGraph &g, std::string &error)
 {
     std::ifstream is(path, std::ios::binary);
     if (!is) { error = "cannot open " + path; return false; }
+    g.has_blocks = false;
+    g.blocks_error.clear();
+    g.block_sizes.clear();
     struct Node { uint64_t id; std::string label; };
     std::vector<Node> nodes;
     std::vector<std::pair<uint64_t, uint64_t>> links;
@@ -46,10 +49,22 @@ bool read_xgfa_graph(const std::string &path, XgfaGraph &g, std::string &error)
     while (std::getline(is, line)) {
         lineno++;
         if (!line.empty() && line.back() == '\r') line.pop_back();
-        if (line.empty() || (line[0] != 'S' && line[0] != 'L') || (line.size() > 1 && line[1] != '\t')) continue;
+        if (line.empty() || (line[0] != 'S' && line[0] != 'L' && line[0] != 'B') || (line.size() > 1 && line[1] != '\t')) continue;
         split_tabs(line, f);
         uint64_t a = 0, b = 0;
-        if (line[0] == 'S') {
+        if (line[0] == 'B') {
+            if (g.has_blocks && g.blocks_error.empty()) g.blocks_error = path + ":" + std::to_string(lineno) + ": a second B line";
+            g.has_blocks = true;
+            g.block_sizes.clear();
+            for (size_t k = 1; k < f.size(); k++) {
+                if (k + 1 == f.size() && f[k].empty()) break;         // a trailing tab
+                if (!parse_id(f[k], a)) {
+                    if (g.blocks_error.empty()) g.blocks_error = path + ":" + std::to_string(lineno) + ": malformed B line";
+                    break;
+                }
+                g.block_sizes.push_back(a);
+            }
+        } else if (line[0] == 'S') {
             if (f.size() < 2 || !parse_id(f[1], a)) { error = path + ":" + std::to_string(lineno) + ": malformed S line"; return false; }
             nodes.push_back({a, f.size() > 2 ? f[2] : std::string()});
         } else {
@@ -66,8 +81,10 @@ bool read_xgfa_graph(const std::string &path, XgfaGraph &g, std::string &error)
     where.reserve(nodes.size() * 2);
     g.labels.clear();
     g.label_off.assign(1, 0);
+    g.ids.clear();
     for (uint64_t i = 0; i < nodes.size(); i++) {
         if (!where.emplace(nodes[i].id, i).second) { error = path + ": node " + std::to_string(nodes[i].id) + " appears twice"; return false; }
+        g.ids.push_back(nodes[i].id);
         g.labels += nodes[i].label;
         g.label_off.push_back(g.labels.size());
     }
@@ -86,5 +103,25 @@ bool read_xgfa_graph(const std::string &path, XgfaGraph &g, std::string &error)
     g.edge_dst.clear();
     for (const auto &p : e) { g.edge_off[p.first + 1]++; g.edge_dst.push_back(p.second); }
     for (uint64_t i = 0; i < nodes.size(); i++) g.edge_off[i + 1] += g.edge_off[i];
+    return true;
+}
+
+bool block_of(const XgfaGraph &g, std::vector<uint32_t> &node_block, std::string &error)
+{
+    if (!g.has_blocks) { error = "the graph has no B line (block sizes)"; return false; }
+    if (!g.blocks_error.empty()) { error = g.blocks_error; return false; }
+    const uint64_t nodes = g.ids.size();
+    uint64_t sum = 0;
+    for (uint64_t s : g.block_sizes) {
+        sum += s;
+        if (sum > nodes) break;
+    }
+    if (sum != nodes || g.block_sizes.size() >= 0xffffffffull) {
+        error = "the B line's block sizes do not sum to the " + std::to_string(nodes) + " nodes";
+        return false;
+    }
+    node_block.clear();
+    node_block.reserve(nodes);
+    for (uint64_t b = 0; b < g.block_sizes.size(); b++) node_block.insert(node_block.end(), g.block_sizes[b], (uint32_t)b);
     return true;
 }

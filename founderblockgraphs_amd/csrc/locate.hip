@@ -14,7 +14,10 @@
 //   k_px_walk<false>                 B / E: every label searched from [0, N], flags at lhs / rhs, compacted
 //                                    into sorted position lists;
 //   k_px_walk<true>                  the batched search of rule 4 (restarts included), one lane per pattern,
-//                                    patterns handed out in order of length.
+//                                    patterns handed out in order of length;
+//   k_pv_node / k_pv_wave            the semi-repeat-free check (fbg_pindex_validate): the SA range of every label,
+//                                    kept from the B / E walk, scanned against the block of each occurrence's node,
+//                                    one lane per short range and one wave per long one.
 //
 // occ layout.  Symbols are remapped to dense codes in byte order (the sentinel is code 0, '#' code 1).  With at
 // most 16 codes a block of 128 BWT positions is one 128-byte line:
@@ -34,6 +37,11 @@
 #define PX_BLK 128            // BWT positions per occ block
 #define PX_LINE 128           // bytes per occ line
 #define PX_ABSENT 0xffffu     // code of a byte that does not occur in the text
+#define PV_OUT 1u             // node flags of the validation tables: has an out-edge / an in-edge
+#define PV_IN 2u
+#define PV_CSHIFT 8           // the coarse edge table holds the edge of every 2^PV_CSHIFT-th text position
+#define PV_SHORT 16           // ranges of at most this many slots are scanned by one lane, longer ones by a wave
+#define PV_NONE 0xffffffffu   // no witness
 
 struct fbg_pindex {
     fbg_ctx *ctx = nullptr;
@@ -45,9 +53,15 @@ struct fbg_pindex {
     uint32_t nb = 0, ne = 0;
     DevBuf text, sa, lines, cnt_tab, C, code, bpos, epos;
     DevBuf pats, poff, okey, oval, okey2, oval2, cnt_out, pos_out, lines_ctr, tmp;
+    // kept for fbg_pindex_validate (not in index_bytes): per node the SA range of its label, a text position of the
+    // label, its length and in / out flags; per distinct edge its text start (E + 1), source and destination; a
+    // coarse table of the edge at every 2^PV_CSHIFT-th text position
+    DevBuf vrng, vtpos, vlen, vflag, vestart, vesrc, vedst, vctab;
+    DevBuf vblock, vstatus, vwn, vwo, vlist, vctr;      // validation scratch, kept between calls
+    uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double build_ms = 0, search_ms = 0;
-    uint64_t occ_lines = 0;
+    double build_ms = 0, search_ms = 0, validate_ms = 0;
+    uint64_t occ_lines = 0, v_slots = 0, v_wave_nodes = 0;
 };
 
 // ---- device buffers owned by the index (the context's workspaces stay untouched) ------------------------------
@@ -296,12 +310,14 @@ template <bool COMPACT> __device__ __forceinline__ uint32_t px_bs(const PxDev &d
 
 // One lane per pattern.  SEARCH: rule 4 of the index (a failed step may restart at a block pair boundary), results
 // count / pos by pattern id, patterns taken in the order `order` (by length).  !SEARCH: B / E of the node labels, no
-// restart; a label whose search finds nothing sets no flag (the reference asserts there).
+// restart; a label whose search finds nothing sets no flag (the reference asserts there); every label's range goes to
+// rng[id] = (l, r), (1, 0) when nothing was found, for fbg_pindex_validate.
 template <bool SEARCH, bool COMPACT>
 __global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t *code_g, const uint32_t *C_g, const uint8_t *pats,
                                                        const uint64_t *poff, const uint32_t *order, uint64_t n,
                                                        unsigned long long *count_out, unsigned long long *pos_out,
-                                                       uint8_t *bflag, uint8_t *eflag, unsigned long long *lines_ctr)
+                                                       uint8_t *bflag, uint8_t *eflag, unsigned long long *lines_ctr,
+                                                       uint2 *rng)
 {
     __shared__ uint16_t code[256];
     __shared__ uint32_t C[256];
@@ -346,9 +362,12 @@ __global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t 
         if (SEARCH) {
             count_out[id] = ok ? cnt : 0u;
             pos_out[id] = pos;
-        } else if (ok) {
-            bflag[l] = 1;
-            eflag[r] = 1;
+        } else {
+            if (ok) {
+                bflag[l] = 1;
+                eflag[r] = 1;
+            }
+            rng[id] = ok ? make_uint2(l, r) : make_uint2(1u, 0u);
         }
     }
     if (SEARCH) {
@@ -373,6 +392,20 @@ __global__ void k_px_rebase(uint64_t *off, uint64_t n, uint64_t base)
     if (t <= n) off[t] -= base;
 }
 
+// ctab[j] = the last edge e < E with estart[e] <= j << PV_CSHIFT (estart[0] = 0)
+__global__ void k_pv_ctab(const uint32_t *estart, uint32_t E, uint64_t nctab, uint32_t *ctab)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nctab) return;
+    const uint64_t x = j << PV_CSHIFT;
+    uint32_t lo = 0, hi = E - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (estart[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    ctab[j] = lo;
+}
+
 static PxDev px_dev(const fbg_pindex *ix)
 {
     PxDev d;
@@ -388,11 +421,11 @@ static PxDev px_dev(const fbg_pindex *ix)
 
 // ---- build ----------------------------------------------------------------------------------------------------
 struct PxScratch {
-    DevBuf labels, loff, esrc, edst, elen, eoff, keysA, keysB, valsA, valsB, cidx, cidx2, rank, headv, hscan, head, keep,
+    DevBuf labels, loff, elen, eoff, keysA, keysB, valsA, valsB, cidx, cidx2, rank, headv, hscan, head, keep,
            cntT, cntX, code_u8, count;
     ~PxScratch()
     {
-        for (DevBuf *b : {&labels, &loff, &esrc, &edst, &elen, &eoff, &keysA, &keysB, &valsA, &valsB, &cidx, &cidx2, &rank,
+        for (DevBuf *b : {&labels, &loff, &elen, &eoff, &keysA, &keysB, &valsA, &valsB, &cidx, &cidx2, &rank,
                           &headv, &hscan, &head, &keep, &cntT, &cntX, &code_u8, &count})
             px_free(*b);
     }
@@ -420,7 +453,8 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     }
     if (n_nodes >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%llu nodes: at most 2^32 - 2", (unsigned long long)n_nodes);
     // distinct out-edges in ascending order (std::set), the text length and its byte histogram
-    std::vector<uint32_t> esrc, edst, tmpv;
+    std::vector<uint32_t> esrc, edst, tmpv, estart, vtpos(n_nodes, 0), vlen(n_nodes);
+    std::vector<uint8_t> vflag(n_nodes, 0);
     std::vector<uint64_t> use(n_nodes, 0);
     uint64_t N1 = 1;
     for (uint64_t u = 0; u < n_nodes; u++) {
@@ -437,6 +471,14 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
             esrc.push_back((uint32_t)u);
             edst.push_back(v);
             use[u]++; use[v]++;
+            // for validation: the edge's text start ('#'), then reverse(label(v)), then reverse(label(u)); the first
+            // edge of a node gives its label's text position
+            const uint64_t start = N1 - 1, lv = label_off[v + 1] - label_off[v];
+            estart.push_back((uint32_t)start);
+            if (!vflag[u]) vtpos[u] = (uint32_t)(start + 1 + lv);
+            vflag[u] |= PV_OUT;
+            if (!vflag[v]) vtpos[v] = (uint32_t)(start + 1);
+            vflag[v] |= PV_IN;
             N1 += (label_off[u + 1] - label_off[u]) + (label_off[v + 1] - label_off[v]) + 1;
             if (N1 >= (1ull << 32))
                 return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "the edge text of this graph has 2^32 symbols or more; the pattern index "
@@ -444,6 +486,11 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
         }
     }
     const uint64_t E = esrc.size();
+    estart.push_back((uint32_t)(N1 - 1));
+    for (uint64_t u = 0; u < n_nodes; u++) {
+        const uint64_t len = label_off[u + 1] - label_off[u];
+        vlen[u] = len > 0xffffffffull ? 0xffffffffu : (uint32_t)len;   // only nodes with edges are read (< N1)
+    }
     uint64_t hist[256] = {0};
     hist[0] = 1;
     hist['#'] = E;
@@ -479,8 +526,18 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     if (L) FBG_HIP_TRY(ctx, hipMemcpyAsync(s.labels.p, labels + lbase, L, hipMemcpyHostToDevice, st));
     FBG_TRY(U(s.loff, label_off, (n_nodes + 1) * 8));
     if (lbase) hipLaunchKernelGGL(k_px_rebase, dim3(fbg_blocks(n_nodes + 1, 256)), dim3(256), 0, st, s.loff.as<uint64_t>(), n_nodes, lbase);
-    FBG_TRY(U(s.esrc, esrc.data(), E * 4));
-    FBG_TRY(U(s.edst, edst.data(), E * 4));
+    FBG_TRY(U(ix->vesrc, esrc.data(), E * 4));
+    FBG_TRY(U(ix->vedst, edst.data(), E * 4));
+    FBG_TRY(U(ix->vestart, estart.data(), (E + 1) * 4));
+    FBG_TRY(U(ix->vtpos, vtpos.data(), n_nodes * 4));
+    FBG_TRY(U(ix->vlen, vlen.data(), n_nodes * 4));
+    FBG_TRY(U(ix->vflag, vflag.data(), n_nodes));
+    FBG_TRY(px_reserve(ix, ix->vrng, n_nodes * 8));
+    ix->n_edges = E;
+    ix->nctab = ((N1 - 1) >> PV_CSHIFT) + 2;
+    FBG_TRY(px_reserve(ix, ix->vctab, ix->nctab * 4));
+    if (E) hipLaunchKernelGGL(k_pv_ctab, dim3(fbg_blocks(ix->nctab, 256)), dim3(256), 0, st, ix->vestart.as<uint32_t>(), (uint32_t)E,
+                              ix->nctab, ix->vctab.as<uint32_t>());
     FBG_TRY(U(s.code_u8, code_u8, 256));
     FBG_TRY(U(ix->code, code, sizeof(code)));
     FBG_TRY(U(ix->C, C, sizeof(C)));
@@ -491,14 +548,14 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     if (E) {
         FBG_TRY(px_reserve(ix, s.elen, E * 8));
         FBG_TRY(px_reserve(ix, s.eoff, E * 8));
-        hipLaunchKernelGGL(k_px_edge_len, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, s.esrc.as<uint32_t>(), s.edst.as<uint32_t>(),
+        hipLaunchKernelGGL(k_px_edge_len, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, ix->vesrc.as<uint32_t>(), ix->vedst.as<uint32_t>(),
                            s.loff.as<uint64_t>(), E, s.elen.as<uint64_t>());
         uint64_t *elen = s.elen.as<uint64_t>(), *eoff = s.eoff.as<uint64_t>();
         FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
             return rocprim::exclusive_scan(tmp, bytes, elen, eoff, (uint64_t)0, (size_t)E, rocprim::plus<uint64_t>(), st);
         }));
         hipLaunchKernelGGL(k_px_edge_text, dim3(fbg_blocks(E * FBG_WAVE, PX_THREADS)), dim3(PX_THREADS), 0, st, s.labels.as<uint8_t>(),
-                           s.loff.as<uint64_t>(), s.esrc.as<uint32_t>(), s.edst.as<uint32_t>(), eoff, E, ix->text.as<uint8_t>());
+                           s.loff.as<uint64_t>(), ix->vesrc.as<uint32_t>(), ix->vedst.as<uint32_t>(), eoff, E, ix->text.as<uint8_t>());
     }
 
     // suffix array
@@ -588,11 +645,13 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
         if (ix->compact)
             hipLaunchKernelGGL((k_px_walk<false, true>), gw, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
                                s.labels.as<uint8_t>(), s.loff.as<uint64_t>(), (const uint32_t *)nullptr, n_nodes,
-                               (unsigned long long *)nullptr, (unsigned long long *)nullptr, bflag, eflag, (unsigned long long *)nullptr);
+                               (unsigned long long *)nullptr, (unsigned long long *)nullptr, bflag, eflag, (unsigned long long *)nullptr,
+                               ix->vrng.as<uint2>());
         else
             hipLaunchKernelGGL((k_px_walk<false, false>), gw, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
                                s.labels.as<uint8_t>(), s.loff.as<uint64_t>(), (const uint32_t *)nullptr, n_nodes,
-                               (unsigned long long *)nullptr, (unsigned long long *)nullptr, bflag, eflag, (unsigned long long *)nullptr);
+                               (unsigned long long *)nullptr, (unsigned long long *)nullptr, bflag, eflag, (unsigned long long *)nullptr,
+                               ix->vrng.as<uint2>());
     }
     FBG_TRY(px_reserve(ix, ix->bpos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4));
     FBG_TRY(px_reserve(ix, ix->epos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4));
@@ -624,11 +683,134 @@ static void px_destroy(fbg_pindex *ix)
         (void)hipStreamSynchronize(ix->ctx->stream);
     }
     for (DevBuf *b : {&ix->text, &ix->sa, &ix->lines, &ix->cnt_tab, &ix->C, &ix->code, &ix->bpos, &ix->epos, &ix->pats, &ix->poff,
-                      &ix->okey, &ix->oval, &ix->okey2, &ix->oval2, &ix->cnt_out, &ix->pos_out, &ix->lines_ctr, &ix->tmp})
+                      &ix->okey, &ix->oval, &ix->okey2, &ix->oval2, &ix->cnt_out, &ix->pos_out, &ix->lines_ctr, &ix->tmp,
+                      &ix->vrng, &ix->vtpos, &ix->vlen, &ix->vflag, &ix->vestart, &ix->vesrc, &ix->vedst, &ix->vctab,
+                      &ix->vblock, &ix->vstatus, &ix->vwn, &ix->vwo, &ix->vlist, &ix->vctr})
         px_free(*b);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
     delete ix;
+}
+
+// ---- semi-repeat-free validation (fbg_pindex_validate) -----------------------------------------------------------
+struct PvDev {
+    const uint32_t *sa, *tpos, *len, *estart, *esrc, *edst, *ctab, *block;
+    const uint2 *rng;
+    const uint8_t *flag, *text;
+};
+
+struct PvMask {
+    uint64_t w[4];
+};
+
+// the edge whose string holds text position p: the last e with estart[e] <= p, searched between two coarse entries
+__device__ __forceinline__ uint32_t pv_edge(const PvDev &d, uint32_t p)
+{
+    uint32_t lo = d.ctab[p >> PV_CSHIFT], hi = d.ctab[(p >> PV_CSHIFT) + 1];
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (d.estart[mid] <= p) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The occurrence of a label (m symbols, node in block bu) whose reversed copy starts at text position p: the node and
+// offset it starts at in label(a) + label(b) of its edge; true iff that is offset 0 of a node of block bu.
+__device__ __forceinline__ bool pv_allowed(const PvDev &d, uint32_t p, uint32_t m, uint32_t bu, uint32_t &node, uint32_t &off)
+{
+    const uint32_t e = pv_edge(d, p);
+    const uint32_t base = d.estart[e] + 1, ne = d.estart[e + 1] - base;   // ne = |a| + |b|
+    const uint32_t a = d.esrc[e], la = d.len[a];
+    const uint32_t s = ne - (p - base) - m;                                 // forward offset in label(a) + label(b)
+    if (s < la) { node = a; off = s; } else { node = d.edst[e]; off = s - la; }
+    return off == 0 && d.block[node] == bu;
+}
+
+__device__ __forceinline__ void pv_add_slots(unsigned long long *ctr, unsigned long long v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x % FBG_WAVE) == 0 && v) atomicAdd(ctr, v);
+}
+
+// One lane per node: rules 1-3, then a range of at most PV_SHORT slots scanned in slot order up to its first
+// disallowed occurrence; longer ranges go to `list` for k_pv_wave (status VALID until that kernel finds otherwise).
+// ctr[0]: list length, ctr[1]: SA slots scanned.
+__global__ __launch_bounds__(PX_THREADS) void k_pv_node(PvDev d, uint64_t n, PvMask ig, int has_ig, uint8_t *status, uint32_t *wn,
+                                                       uint32_t *wo, uint32_t *list, unsigned long long *ctr)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long slots = 0;
+    if (u < n) {
+        uint8_t st = FBG_NODE_VALID;
+        uint32_t wnode = PV_NONE, woff = PV_NONE;
+        const uint32_t m = d.len[u];
+        bool ignored = false;
+        if ((d.flag[u] & (PV_IN | PV_OUT)) == (PV_IN | PV_OUT) && has_ig) {
+            const uint8_t *lab = d.text + d.tpos[u];        // reverse(label(u)): the order does not matter here
+            for (uint32_t k = 0; k < m && !ignored; k++) {
+                const uint32_t c = lab[k];
+                ignored = (ig.w[c >> 6] >> (c & 63)) & 1u;
+            }
+        }
+        if ((d.flag[u] & (PV_IN | PV_OUT)) != (PV_IN | PV_OUT)) st = FBG_NODE_SKIP_SOURCE_SINK;
+        else if (ignored) st = FBG_NODE_SKIP_IGNORED;
+        else if (m == 0) st = FBG_NODE_SKIP_EMPTY;
+        else {
+            const uint2 lr = d.rng[u];
+            const uint32_t bu = d.block[u];
+            if (lr.x <= lr.y && lr.y - lr.x < PV_SHORT) {
+                for (uint32_t i = lr.x; i <= lr.y; i++) {
+                    slots++;
+                    uint32_t node, off;
+                    if (!pv_allowed(d, d.sa[i], m, bu, node, off)) {
+                        st = FBG_NODE_INVALID; wnode = node; woff = off;
+                        break;
+                    }
+                }
+            } else if (lr.x <= lr.y) {
+                list[atomicAdd(&ctr[0], 1ull)] = (uint32_t)u;
+            }
+        }
+        status[u] = st;
+        wn[u] = wnode;
+        wo[u] = woff;
+    }
+    pv_add_slots(&ctr[1], slots);
+}
+
+// One wave per listed node (a grid-stride loop over ctr[0] entries): 64 slots per step in ascending slot order; the
+// lowest lane whose occurrence is disallowed is the witness, and the node's scan ends with that step.
+__global__ __launch_bounds__(PX_THREADS) void k_pv_wave(PvDev d, const uint32_t *list, unsigned long long *ctr, uint8_t *status,
+                                                       uint32_t *wn, uint32_t *wo)
+{
+    const uint64_t nlist = ctr[0];
+    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x / FBG_WAVE);
+    const unsigned lane = threadIdx.x % FBG_WAVE;
+    unsigned long long slots = 0;
+    for (uint64_t k = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FBG_WAVE; k < nlist; k += nw) {
+        const uint32_t u = list[k];
+        const uint32_t m = d.len[u], bu = d.block[u];
+        const uint2 lr = d.rng[u];
+        for (uint64_t b = lr.x; b <= lr.y; b += FBG_WAVE) {
+            const uint64_t i = b + lane;
+            uint32_t node = 0, off = 0;
+            bool bad = false;
+            if (i <= lr.y) {
+                slots++;
+                bad = !pv_allowed(d, d.sa[i], m, bu, node, off);
+            }
+            const uint64_t bal = __ballot(bad);
+            if (bal) {
+                if (lane == (unsigned)__builtin_ctzll(bal)) {
+                    status[u] = FBG_NODE_INVALID;
+                    wn[u] = node;
+                    wo[u] = off;
+                }
+                break;
+            }
+        }
+    }
+    pv_add_slots(&ctr[1], slots);
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------
@@ -694,10 +876,10 @@ extern "C" int fbg_pindex_locate(fbg_pindex *ix, const uint8_t *patterns, const 
     auto *lc = ix->lines_ctr.as<unsigned long long>();
     if (ix->compact)
         hipLaunchKernelGGL((k_px_walk<true, true>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
-                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc);
+                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc, (uint2 *)nullptr);
     else
         hipLaunchKernelGGL((k_px_walk<true, false>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
-                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc);
+                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc, (uint2 *)nullptr);
     FBG_HIP_TRY(ctx, hipGetLastError());
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(count, co, n * 8, hipMemcpyDeviceToHost, st));
@@ -738,6 +920,88 @@ extern "C" int fbg_pindex_stats(const fbg_pindex *ix, uint64_t *index_bytes, dou
     if (build_ms) *build_ms = ix->build_ms;
     if (search_ms) *search_ms = ix->search_ms;
     if (occ_lines) *occ_lines = ix->occ_lines;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_validate(fbg_pindex *ix, const uint32_t *node_block, const uint8_t *ignore_chars, uint64_t ignore_len,
+                                   uint8_t *status, uint64_t *witness_node, uint64_t *witness_offset, uint64_t *n_invalid,
+                                   double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    const uint64_t n = ix->n_nodes;
+    if (n && (!node_block || !status)) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_validate: missing argument");
+    if (ignore_len && !ignore_chars) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_validate: missing ignore characters");
+    if (n_invalid) *n_invalid = 0;
+    if (device_ms) *device_ms = 0;
+    ix->validate_ms = 0;
+    ix->v_slots = ix->v_wave_nodes = 0;
+    if (n == 0) return FBG_OK;
+    PvMask ig = {{0, 0, 0, 0}};
+    for (uint64_t k = 0; k < ignore_len; k++) ig.w[ignore_chars[k] >> 6] |= 1ull << (ignore_chars[k] & 63);
+    const int has_ig = (ig.w[0] | ig.w[1] | ig.w[2] | ig.w[3]) != 0;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FBG_TRY(px_reserve(ix, ix->vblock, n * 4));
+    FBG_TRY(px_reserve(ix, ix->vstatus, n));
+    FBG_TRY(px_reserve(ix, ix->vwn, n * 4));
+    FBG_TRY(px_reserve(ix, ix->vwo, n * 4));
+    FBG_TRY(px_reserve(ix, ix->vlist, n * 4));
+    FBG_TRY(px_reserve(ix, ix->vctr, 16));
+    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
+    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->vblock.p, node_block, n * 4, hipMemcpyHostToDevice, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->vctr.p, 0, 16, st));
+    PvDev d;
+    d.sa = ix->sa.as<uint32_t>();
+    d.tpos = ix->vtpos.as<uint32_t>();
+    d.len = ix->vlen.as<uint32_t>();
+    d.estart = ix->vestart.as<uint32_t>();
+    d.esrc = ix->vesrc.as<uint32_t>();
+    d.edst = ix->vedst.as<uint32_t>();
+    d.ctab = ix->vctab.as<uint32_t>();
+    d.block = ix->vblock.as<uint32_t>();
+    d.rng = ix->vrng.as<uint2>();
+    d.flag = ix->vflag.as<uint8_t>();
+    d.text = ix->text.as<uint8_t>();
+    auto *ctr = ix->vctr.as<unsigned long long>();
+    uint8_t *dst = ix->vstatus.as<uint8_t>();
+    uint32_t *wn = ix->vwn.as<uint32_t>(), *wo = ix->vwo.as<uint32_t>();
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    hipLaunchKernelGGL(k_pv_node, dim3(fbg_blocks(n, PX_THREADS)), dim3(PX_THREADS), 0, st, d, n, ig, has_ig, dst, wn, wo,
+                       ix->vlist.as<uint32_t>(), ctr);
+    const uint64_t wave_blocks = std::min<uint64_t>(fbg_blocks(n * FBG_WAVE, PX_THREADS), 2048);
+    hipLaunchKernelGGL(k_pv_wave, dim3(wave_blocks), dim3(PX_THREADS), 0, st, d, (const uint32_t *)ix->vlist.as<uint32_t>(), ctr, dst,
+                       wn, wo);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    std::vector<uint32_t> hwn(witness_node ? n : 0), hwo(witness_offset ? n : 0);
+    uint64_t hctr[2] = {0, 0};
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, st));
+    if (witness_node) FBG_HIP_TRY(ctx, hipMemcpyAsync(hwn.data(), wn, n * 4, hipMemcpyDeviceToHost, st));
+    if (witness_offset) FBG_HIP_TRY(ctx, hipMemcpyAsync(hwo.data(), wo, n * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(hctr, ctr, 16, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    ix->validate_ms = ms;
+    ix->v_wave_nodes = hctr[0];
+    ix->v_slots = hctr[1];
+    uint64_t bad = 0;
+    for (uint64_t u = 0; u < n; u++) bad += status[u] == FBG_NODE_INVALID;
+    for (uint64_t u = 0; u < hwn.size(); u++) witness_node[u] = hwn[u] == PV_NONE ? UINT64_MAX : hwn[u];
+    for (uint64_t u = 0; u < hwo.size(); u++) witness_offset[u] = hwo[u] == PV_NONE ? UINT64_MAX : hwo[u];
+    if (n_invalid) *n_invalid = bad;
+    if (device_ms) *device_ms = ms;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_validate_stats(const fbg_pindex *ix, uint64_t *slots_scanned, uint64_t *wave_nodes, uint64_t *table_bytes)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    if (slots_scanned) *slots_scanned = ix->v_slots;
+    if (wave_nodes) *wave_nodes = ix->v_wave_nodes;
+    if (table_bytes) *table_bytes = 17 * ix->n_nodes + 12 * ix->n_edges + 4 + 4 * ix->nctab;
     return FBG_OK;
 }
 

@@ -408,6 +408,40 @@ int fbg_pindex_stats(const fbg_pindex *ix, uint64_t *index_bytes, double *build_
                      uint64_t *occ_lines);
 void fbg_pindex_destroy(fbg_pindex *ix);
 
+/* Semi-repeat-free check of the index's graph (the reference's efg_validate / efg_validate_node, fbg.cpp:3104-3292,
+ * without the repair).  Input: the index as built, node_block[n_nodes] (one block id per node; only equality matters)
+ * and an optional set of ignore bytes.  status[u] is given by the first rule that applies:
+ *   1. u has no in-edge or no out-edge                                  FBG_NODE_SKIP_SOURCE_SINK
+ *   2. label(u) holds a byte of the ignore set                          FBG_NODE_SKIP_IGNORED
+ *   3. label(u) is empty                                                FBG_NODE_SKIP_EMPTY (the reference is undefined)
+ *   4. every occurrence of label(u) at an offset s of label(a) + label(b), over the distinct edges (a, b) (an
+ *      occurrence never crosses the '#'), belongs to node a at offset s if s < |label(a)|, else to node b at offset
+ *      s - |label(a)|; it is allowed iff that offset is 0 and the node's block is u's.  All allowed: FBG_NODE_VALID,
+ *      else FBG_NODE_INVALID.
+ * Witness of an INVALID node: its disallowed occurrence of smallest SA slot in u's range of the index text (the
+ * suffixes that start with reverse(label(u))), as (node, offset); UINT64_MAX in both for every other status.  The
+ * per-node verdict equals the reference's, which indexes the forward text with duplicate edges in adjacency order:
+ * neither changes the set of distinct (edge, offset) occurrences.
+ * Device tables the build keeps for this (not counted in index_bytes): per node the SA range of its label (from the
+ * B / E walk), a text position, its length and in / out flags (17 bytes); per distinct edge its text start, source
+ * and destination (12 bytes, plus one text start); a coarse table of the edge at every 256th text position (4 bytes
+ * each).  A call adds 17 bytes per node of scratch, leaves later fbg_pindex_locate results and the context's
+ * segmentation results unchanged, and does not change fbg_pindex_stats' search_ms.
+ * node_block, status: n_nodes values; witness_* may be NULL; *n_invalid and *device_ms (device time of the
+ * validation kernels, without the copies) may be NULL.  A NULL index, or a NULL node_block / status with
+ * n_nodes > 0, returns FBG_ERR_INVALID. */
+#define FBG_NODE_VALID 0
+#define FBG_NODE_INVALID 1
+#define FBG_NODE_SKIP_SOURCE_SINK 2
+#define FBG_NODE_SKIP_IGNORED 3
+#define FBG_NODE_SKIP_EMPTY 4
+int fbg_pindex_validate(fbg_pindex *ix, const uint32_t *node_block, const uint8_t *ignore_chars, uint64_t ignore_len,
+                        uint8_t *status, uint64_t *witness_node, uint64_t *witness_offset, uint64_t *n_invalid,
+                        double *device_ms);
+/* Measurement of the last fbg_pindex_validate (any pointer may be NULL): SA slots scanned, nodes whose range went to
+ * the wave tier, and the device bytes of the tables the build keeps for validation. */
+int fbg_pindex_validate_stats(const fbg_pindex *ix, uint64_t *slots_scanned, uint64_t *wave_nodes, uint64_t *table_bytes);
+
 #ifdef __cplusplus
 }
 #endif
