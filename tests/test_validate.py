@@ -157,8 +157,8 @@ def test_read_xgfa_blocks(tmp_path):
 # ---- GPU ----------------------------------------------------------------------------------------------------------
 
 def check(engine, labels, edges, blocks, ignore=""):
-    """Device result == model, bit for bit; returns (result, model status)."""
-    st, wn, wo = VM.Validator(labels, edges).validate(blocks, ignore.encode())
+    """Device result == model, bit for bit; returns (result, model status).  `ignore`: str (UTF-8) or bytes as they are."""
+    st, wn, wo = VM.Validator(labels, edges).validate(blocks, LM.as_bytes(ignore))
     res = engine.validate_graph(labels, edges, blocks, ignore)
     assert res.status.dtype == np.uint8 and res.witness_node.dtype == np.int64
     assert np.array_equal(res.status, st)
