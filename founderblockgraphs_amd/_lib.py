@@ -83,6 +83,9 @@ SIGNATURES = {
     "fbg_pindex_destroy": (None, [vp]),
     "fbg_pindex_validate": (C.c_int, [vp, u32p, u8p, C.c_uint64, u8p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_validate_stats": (C.c_int, [vp, u64p, u64p, u64p]),
+    "fbg_pindex_occurrences": (C.c_int, [vp, u8p, u64p, C.c_uint64, C.c_uint64, u64p, u64p, u32p, u64p, u64p, u64p, u64p,
+                                         C.POINTER(C.c_double)]),
+    "fbg_pindex_occurrences_fetch": (C.c_int, [vp, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(C.c_double)]),
 }
 PLANS = ("auto", "partitioned", "columns", "row_pairs")   # FBG_PLAN_*
 

@@ -352,6 +352,7 @@ class PatternIndex:
         engine._chk(self._L.fbg_pindex_build(engine._h, _u8(data), _u64(loff), n, _u64(eoff), _u64(dst), C.byref(h)))
         self._h = h
         self.n_nodes = n
+        self._label_len = np.diff(loff.astype(np.int64))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -379,6 +380,28 @@ class PatternIndex:
         pos = np.zeros(max(k, 1), dtype=np.uint64)
         self._eng._chk(self._L.fbg_pindex_locate(self._h, _u8(data), _u64(off), k, _u64(count), _u64(pos)))
         return count[:k], pos[:k]
+
+    def occurrences(self, patterns, max_per_pattern=64):
+        """The search of locate() plus the places where each found pattern ends and starts, at most max_per_pattern
+        of each per pattern (fbg_pindex_occurrences and fbg_pindex_occurrences_fetch) -> Occurrences."""
+        if max_per_pattern < 0:
+            raise ValueError("max_per_pattern must be 0 or more")
+        data, off = _concat(patterns)
+        k = len(off) - 1
+        count, pos, et, st = (np.zeros(max(k, 1), dtype=np.uint64) for _ in range(4))
+        rs = np.zeros(max(k, 1), dtype=np.uint32)
+        eoff, soff = np.zeros(k + 1, dtype=np.uint64), np.zeros(k + 1, dtype=np.uint64)
+        ms1, ms2 = C.c_double(0), C.c_double(0)
+        self._eng._chk(self._L.fbg_pindex_occurrences(self._h, _u8(data), _u64(off), k, int(max_per_pattern), _u64(count), _u64(pos),
+                                                      rs.ctypes.data_as(_lib.u32p), _u64(eoff), _u64(soff), _u64(et), _u64(st),
+                                                      C.byref(ms1)))
+        ne, ns = int(eoff[k]), int(soff[k])
+        ends = [np.zeros(max(ne, 1), dtype=np.uint32) for _ in range(3)]
+        starts = [np.zeros(max(ns, 1), dtype=np.uint32) for _ in range(3)]
+        self._eng._chk(self._L.fbg_pindex_occurrences_fetch(self._h, *[a.ctypes.data_as(_lib.u32p) for a in ends + starts],
+                                                            C.byref(ms2)))
+        return Occurrences(self._label_len, count[:k], pos[:k], rs[:k], et[:k], st[:k], eoff, soff, [a[:ne] for a in ends],
+                           [a[:ns] for a in starts], ms1.value, ms2.value)
 
     def download(self):
         """-> (text with the sentinel, SA, B positions, E positions)."""
@@ -421,6 +444,61 @@ class PatternIndex:
         slots, waves, tb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._eng._chk(self._L.fbg_pindex_validate_stats(self._h, C.byref(slots), C.byref(waves), C.byref(tb)))
         return Validation(status[:n], wn[:n], wo[:n], blk.astype(np.int64), ms.value, slots.value, waves.value)
+
+
+class Occurrences:
+    """Result of PatternIndex.occurrences (include/fbg_hip.h, fbg_pindex_occurrences), one entry per pattern:
+      count, pos               what locate() returns
+      restarts                 uint32, restarts of the search that went on
+      end_total, start_total   places the search found (0 for a pattern that was not found)
+      end_off, start_off       uint64[k + 1], CSR offsets of the reported (capped) lists
+    and one entry per reported place, in ascending SA slot order within a pattern:
+      end_src, end_dst, end_offset        the edge (node indices) and the index into label(src) + label(dst) of the
+                                          match's last symbol
+      start_src, start_dst, start_offset  the same for its first symbol
+    search_ms, fetch_ms: device time of the two calls.  A (start, end) pair of a pattern with restarts is not checked to
+    lie on one path."""
+
+    def __init__(self, label_len, count, pos, restarts, end_total, start_total, end_off, start_off, ends, starts, search_ms,
+                 fetch_ms):
+        self._label_len = label_len
+        self.count, self.pos, self.restarts = count, pos, restarts
+        self.end_total, self.start_total = end_total, start_total
+        self.end_off, self.start_off = end_off, start_off
+        self.end_src, self.end_dst, self.end_offset = ends
+        self.start_src, self.start_dst, self.start_offset = starts
+        self.search_ms, self.fetch_ms = search_ms, fetch_ms
+        self.device_ms = (search_ms, fetch_ms)
+
+    def _rows(self, which, k):
+        off = self.end_off if which == "end" else self.start_off
+        a, b = int(off[k]), int(off[k + 1])
+        return np.stack([getattr(self, f"{which}_{f}")[a:b] for f in ("src", "dst", "offset")], axis=1).astype(np.int64)
+
+    def ends(self, k):
+        """int64[rows, 3]: (src, dst, offset) of pattern k's reported ends."""
+        return self._rows("end", k)
+
+    def starts(self, k):
+        """int64[rows, 3]: (src, dst, offset) of pattern k's reported starts."""
+        return self._rows("start", k)
+
+    def as_nodes(self, which="end"):
+        """Places as (node, offset in the node's label): src where offset < |label(src)|, else dst with the offset
+        less |label(src)|; duplicates within a pattern dropped.  -> a list with one sorted int64[rows, 2] array per
+        pattern.  which: "end" or "start"."""
+        if which not in ("end", "start"):
+            raise ValueError('which is "end" or "start"')
+        off = self.end_off if which == "end" else self.start_off
+        src, dst, o = (getattr(self, f"{which}_{f}").astype(np.int64) for f in ("src", "dst", "offset"))
+        la = self._label_len[src] if len(src) else src
+        in_src = o < la
+        node, noff = np.where(in_src, src, dst), np.where(in_src, o, o - la)
+        out = []
+        for k in range(len(off) - 1):
+            a, b = int(off[k]), int(off[k + 1])
+            out.append(np.unique(np.stack((node[a:b], noff[a:b]), axis=1), axis=0).reshape(-1, 2))
+        return out
 
 
 class Validation:

@@ -2,13 +2,20 @@
 // libfbg_hip.so (include/fbg_hip.h, fbg_pindex_*).  Stands in for locate_patterns of the reference with a graph in
 // place of its .index file:
 //
-//   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found]
+//   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
 // in one fbg_pindex_locate call.  stdout is byte for byte what locate_patterns prints for an index of that graph;
-// stderr carries the messages.
+// stderr carries the messages.  --occurrences[=M] (M = 64 when left out) answers through fbg_pindex_occurrences instead
+// and adds, after the line of every pattern that is found, one line per reported place:
+//   E <tab> src S id <tab> dst S id <tab> offset      where the match ends: an index into label(src) + label(dst)
+//   B <tab> src S id <tab> dst S id <tab> offset      where it begins
+// at most M of each per pattern, the ends first; a list cut by M is followed by `E <tab> ... <tab> K more` (or B) with
+// K the places left out.
+#include <cerrno>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -20,14 +27,18 @@
 static int usage(const char *msg)
 {
     std::cerr << "fbg_locate: " << msg << "\n"
-              << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found]\n";
+              << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]]\n"
+              << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
+              << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
+              << "                     at most M of each per pattern (default 64)\n";
     return EXIT_FAILURE;
 }
 
 int main(int argc, char **argv)
 {
     std::string graph, patterns;
-    bool have_graph = false, have_patterns = false, error_on_not_found = false;
+    bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false;
+    uint64_t max_places = 64;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&](const char *name, std::string &out, bool &have) {
@@ -38,6 +49,18 @@ int main(int argc, char **argv)
         };
         if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns)) continue;
         if (a == "--error-on-not-found") { error_on_not_found = true; continue; }
+        if (a == "--occurrences") { occurrences = true; continue; }
+        if (a.compare(0, 14, "--occurrences=") == 0) {
+            const std::string v = a.substr(14);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
+                return usage(("--occurrences takes a count, not '" + v + "'").c_str());
+            occurrences = true;
+            max_places = m;
+            continue;
+        }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
         return usage(("unknown argument " + a).c_str());
     }
@@ -73,8 +96,22 @@ int main(int argc, char **argv)
     fbg_pindex *ix = nullptr;
     rc = fbg_pindex_build(ctx, (const uint8_t *)g.labels.data(), g.label_off.data(), nodes, g.edge_off.data(),
                           g.edge_dst.data(), &ix);
-    std::vector<uint64_t> count(np + 1), pos(np + 1);
-    if (rc == FBG_OK) rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
+    std::vector<uint64_t> count(np + 1), pos(np + 1), end_off, start_off, end_total, start_total;
+    std::vector<uint32_t> restarts, places[6];      // end src / dst / offset, start src / dst / offset
+    if (occurrences) {
+        for (std::vector<uint64_t> *v : {&end_off, &start_off, &end_total, &start_total}) v->assign(np + 1, 0);
+        restarts.assign(np + 1, 0);
+    }
+    if (rc == FBG_OK && !occurrences)
+        rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
+    if (rc == FBG_OK && occurrences)
+        rc = fbg_pindex_occurrences(ix, (const uint8_t *)data.data(), off.data(), np, max_places, count.data(), pos.data(),
+                                    restarts.data(), end_off.data(), start_off.data(), end_total.data(), start_total.data(), nullptr);
+    if (rc == FBG_OK && occurrences) {
+        for (int k = 0; k < 6; k++) places[k].resize((k < 3 ? end_off[np] : start_off[np]) + 1);
+        rc = fbg_pindex_occurrences_fetch(ix, places[0].data(), places[1].data(), places[2].data(), places[3].data(),
+                                          places[4].data(), places[5].data(), nullptr);
+    }
     if (rc != FBG_OK) {
         std::cerr << "fbg_locate: " << fbg_last_error(ctx) << "\n";
         fbg_pindex_destroy(ix);
@@ -92,6 +129,14 @@ int main(int argc, char **argv)
             if (error_on_not_found) { std::cout.flush(); return EXIT_FAILURE; }
         } else {
             found++;
+            for (int w = 0; occurrences && w < 2; w++) {
+                const std::vector<uint64_t> &o = w ? start_off : end_off;
+                const uint64_t total = w ? start_total[k] : end_total[k];
+                const char *tag = w ? "B\t" : "E\t";
+                for (uint64_t i = o[k]; i < o[k + 1]; i++)
+                    std::cout << tag << g.ids[places[3 * w][i]] << '\t' << g.ids[places[3 * w + 1][i]] << '\t' << places[3 * w + 2][i] << '\n';
+                if (total > o[k + 1] - o[k]) std::cout << tag << "...\t" << total - (o[k + 1] - o[k]) << " more\n";
+            }
         }
     }
     std::cout << "Pattern? " << found << " out of " << np << " patterns found" << std::endl;

@@ -15,6 +15,10 @@
 //                                    into sorted position lists;
 //   k_px_walk<true>                  the batched search of rule 4 (restarts included), one lane per pattern,
 //                                    patterns handed out in order of length;
+//   k_px_walk<true, *, true>         the same search for fbg_pindex_occurrences: it also keeps the final range, the
+//                                    range after the '#' step of the first restart and the restart count;
+//   k_po_sizes / k_po_expand         capped list sizes per pattern (scanned into CSR offsets), then one lane per
+//                                    reported place: SA slot -> (edge source, edge destination, offset);
 //   k_pv_node / k_pv_wave            the semi-repeat-free check (fbg_pindex_validate): the SA range of every label,
 //                                    kept from the B / E walk, scanned against the block of each occurrence's node,
 //                                    one lane per short range and one wave per long one.
@@ -58,6 +62,11 @@ struct fbg_pindex {
     // coarse table of the edge at every 2^PV_CSHIFT-th text position
     DevBuf vrng, vtpos, vlen, vflag, vestart, vesrc, vedst, vctab;
     DevBuf vblock, vstatus, vwn, vwo, vlist, vctr;      // validation scratch, kept between calls
+    // fbg_pindex_occurrences: per pattern the walk's record (3 x uint2), totals, capped sizes and their scans, what
+    // the expansion reads (first slot of either list, k or |P|, restarts), and the places of the last fetch
+    DevBuf orec, oetot, ostot, oesz, ossz, oeoff, osoff, ors, oel, oss, osk, oplace;
+    bool occ_ready = false;
+    uint64_t occ_n = 0, occ_etotal = 0, occ_stotal = 0;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double build_ms = 0, search_ms = 0, validate_ms = 0;
@@ -311,8 +320,10 @@ template <bool COMPACT> __device__ __forceinline__ uint32_t px_bs(const PxDev &d
 // One lane per pattern.  SEARCH: rule 4 of the index (a failed step may restart at a block pair boundary), results
 // count / pos by pattern id, patterns taken in the order `order` (by length).  !SEARCH: B / E of the node labels, no
 // restart; a label whose search finds nothing sets no flag (the reference asserts there); every label's range goes to
-// rng[id] = (l, r), (1, 0) when nothing was found, for fbg_pindex_validate.
-template <bool SEARCH, bool COMPACT>
+// rng[id] = (l, r), (1, 0) when nothing was found, for fbg_pindex_validate.  OCC (with SEARCH): the search also records
+// rng[3 id] = the final (l, r), rng[3 id + 1] = (sl, sr), the range after the '#' step of the first restart that went
+// on, rng[3 id + 2] = (symbols matched at that restart, restarts that went on), for fbg_pindex_occurrences.
+template <bool SEARCH, bool COMPACT, bool OCC = false>
 __global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t *code_g, const uint32_t *C_g, const uint8_t *pats,
                                                        const uint64_t *poff, const uint32_t *order, uint64_t n,
                                                        unsigned long long *count_out, unsigned long long *pos_out,
@@ -331,6 +342,7 @@ __global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t 
         uint32_t l = 0, r = d.N, cnt = 0;
         uint64_t pos = 0, word = 0;
         bool ok = true;
+        uint32_t restarts = 0, fsl = 1, fsr = 0, fk = 0;
         for (uint64_t k = 0; k < len; k++) {
             const uint64_t q = a + k;
             if (k == 0 || (q & 7) == 0) word = *(const uint64_t *)(pats + (q & ~7ull));   // buffer padded to 8 bytes
@@ -355,6 +367,10 @@ __global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t 
                 if (!(bl <= l && r <= br)) { ok = false; break; }
                 cnt = px_bs<COMPACT>(d, code, C, ch, bl, br, nl, nr, nlines);
                 if (!cnt) { ok = false; break; }
+                if (OCC) {
+                    if (!restarts) { fsl = sl; fsr = sr; fk = (uint32_t)pos; }
+                    restarts++;
+                }
                 l = nl; r = nr;
             }
             pos++;
@@ -362,6 +378,11 @@ __global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t 
         if (SEARCH) {
             count_out[id] = ok ? cnt : 0u;
             pos_out[id] = pos;
+            if (OCC) {
+                rng[3 * id] = make_uint2(l, r);
+                rng[3 * id + 1] = make_uint2(fsl, fsr);
+                rng[3 * id + 2] = make_uint2(fk, restarts);
+            }
         } else {
             if (ok) {
                 bflag[l] = 1;
@@ -685,7 +706,8 @@ static void px_destroy(fbg_pindex *ix)
     for (DevBuf *b : {&ix->text, &ix->sa, &ix->lines, &ix->cnt_tab, &ix->C, &ix->code, &ix->bpos, &ix->epos, &ix->pats, &ix->poff,
                       &ix->okey, &ix->oval, &ix->okey2, &ix->oval2, &ix->cnt_out, &ix->pos_out, &ix->lines_ctr, &ix->tmp,
                       &ix->vrng, &ix->vtpos, &ix->vlen, &ix->vflag, &ix->vestart, &ix->vesrc, &ix->vedst, &ix->vctab,
-                      &ix->vblock, &ix->vstatus, &ix->vwn, &ix->vwo, &ix->vlist, &ix->vctr})
+                      &ix->vblock, &ix->vstatus, &ix->vwn, &ix->vwo, &ix->vlist, &ix->vctr, &ix->orec, &ix->oetot, &ix->ostot,
+                      &ix->oesz, &ix->ossz, &ix->oeoff, &ix->osoff, &ix->ors, &ix->oel, &ix->oss, &ix->osk, &ix->oplace})
         px_free(*b);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
@@ -813,6 +835,72 @@ __global__ __launch_bounds__(PX_THREADS) void k_pv_wave(PvDev d, const uint32_t 
     pv_add_slots(&ctr[1], slots);
 }
 
+// ---- occurrences (fbg_pindex_occurrences / _fetch) ---------------------------------------------------------------
+// Per pattern: the totals, the capped sizes of both lists (entry n = 0, so that their exclusive scans are the n + 1
+// CSR offsets) and what the expansion reads: the first slot of either list, and for the starts k (restarts > 0) or
+// |P| (= pos of a found pattern).  A graph without edges has no places: sizes 0, the totals stand.
+__global__ void k_po_sizes(const unsigned long long *count, const unsigned long long *pos, const uint2 *rec, uint64_t n, uint64_t cap,
+                           int has_edges, uint64_t *etot, uint64_t *stot, uint64_t *esz, uint64_t *ssz, uint32_t *restarts,
+                           uint32_t *el, uint32_t *ss, uint32_t *sk)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n) return;
+    if (t == n) { esz[n] = 0; ssz[n] = 0; return; }
+    const uint64_t cnt = count[t];
+    const uint2 lr = rec[3 * t], s = rec[3 * t + 1], kr = rec[3 * t + 2];
+    const uint64_t st = cnt == 0 ? 0 : kr.y ? (uint64_t)s.y - s.x + 1 : cnt;
+    etot[t] = cnt;
+    stot[t] = st;
+    esz[t] = has_edges ? (cnt < cap ? cnt : cap) : 0;
+    ssz[t] = has_edges ? (st < cap ? st : cap) : 0;
+    restarts[t] = kr.y;
+    el[t] = lr.x;
+    ss[t] = kr.y ? s.x : lr.x;
+    sk[t] = kr.y ? kr.x : (uint32_t)pos[t];
+}
+
+__device__ __forceinline__ uint64_t po_uniform(uint64_t v)
+{
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
+// the last q in [lo, hi] with off[q] <= x (off[lo] <= x is given)
+__device__ __forceinline__ uint64_t po_find(const uint64_t *off, uint64_t lo, uint64_t hi, uint64_t x)
+{
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// One lane per reported place, item i of a list's CSR order (off[n] = total items): the wave finds the patterns of
+// its first and last item by a search of all n offsets that is the same in every lane, each lane then searches only
+// between those two.  Item j of pattern q is SA slot first[q] + j; the place follows as in pv_allowed.  Lanes write
+// consecutive entries: a pattern's places are contiguous and in slot order.  STARTS: offsets of the match's start.
+template <bool STARTS>
+__global__ __launch_bounds__(PX_THREADS) void k_po_expand(PvDev d, const uint64_t *off, uint64_t n, uint64_t total,
+                                                         const uint32_t *first, const uint32_t *sk, const uint32_t *restarts,
+                                                         uint32_t *osrc, uint32_t *odst, uint32_t *oofs)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t w0 = po_uniform(i & ~(uint64_t)(FBG_WAVE - 1));
+    if (w0 >= total) return;
+    const uint64_t w1 = w0 + FBG_WAVE - 1 < total ? w0 + FBG_WAVE - 1 : total - 1;
+    const uint64_t q0 = po_uniform(po_find(off, 0, n - 1, w0));
+    const uint64_t q1 = po_uniform(po_find(off, q0, n - 1, w1));
+    if (i >= total) return;
+    const uint64_t q = po_find(off, q0, q1, i);
+    const uint32_t p = d.sa[first[q] + (uint32_t)(i - off[q])];
+    const uint32_t e = pv_edge(d, p);
+    const uint32_t base = d.estart[e] + 1, ne = d.estart[e + 1] - base;
+    uint32_t o = ne - 1 - (p - base);                 // of the pattern's last symbol (starts after a restart: p = base - 1)
+    if (STARTS) o = restarts[q] ? ne - sk[q] : o - sk[q] + 1;
+    osrc[i] = d.esrc[e];
+    odst[i] = d.edst[e];
+    oofs[i] = o;
+}
+
 // ---- C ABI ------------------------------------------------------------------------------------------------------
 extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
                                 const uint64_t *edge_off, const uint64_t *edge_dst, fbg_pindex **out)
@@ -833,20 +921,15 @@ extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint6
     return FBG_OK;
 }
 
-extern "C" int fbg_pindex_locate(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
-                                 uint64_t *count, uint64_t *pos)
+// The front of fbg_pindex_locate and fbg_pindex_occurrences: patterns onto the device, ev0, the length sort and the
+// walk (occ: the instantiation that records the ranges into orec).  n > 0.
+static int px_search(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns, bool occ)
 {
-    if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
-    if (n_patterns && (!pat_off || !count || !pos)) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_locate: missing argument");
-    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_locate: at most 2^32 - 2 patterns per call");
-    ix->search_ms = 0;
-    ix->occ_lines = 0;
-    if (n_patterns == 0) return FBG_OK;
     for (uint64_t k = 0; k < n_patterns; k++)
         if (pat_off[k + 1] < pat_off[k]) return fbg_fail(ctx, FBG_ERR_INVALID, "pattern offsets decrease at pattern %llu", (unsigned long long)k);
     const uint64_t base = pat_off[0], total = pat_off[n_patterns] - base;
-    if (total && !patterns) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_locate: missing patterns");
+    if (total && !patterns) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing patterns", who);
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint64_t n = n_patterns;
@@ -856,6 +939,12 @@ extern "C" int fbg_pindex_locate(fbg_pindex *ix, const uint8_t *patterns, const 
     FBG_TRY(px_reserve(ix, ix->cnt_out, n * 8));
     FBG_TRY(px_reserve(ix, ix->pos_out, n * 8));
     FBG_TRY(px_reserve(ix, ix->lines_ctr, 8));
+    if (occ) {      // everything fbg_pindex_occurrences allocates, here: after hipSetDevice
+        FBG_TRY(px_reserve(ix, ix->orec, n * 24));
+        for (DevBuf *b : {&ix->oetot, &ix->ostot}) FBG_TRY(px_reserve(ix, *b, n * 8));
+        for (DevBuf *b : {&ix->oesz, &ix->ossz, &ix->oeoff, &ix->osoff}) FBG_TRY(px_reserve(ix, *b, (n + 1) * 8));
+        for (DevBuf *b : {&ix->ors, &ix->oel, &ix->oss, &ix->osk}) FBG_TRY(px_reserve(ix, *b, n * 4));
+    }
     if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
     if (total) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->pats.p, patterns + base, total, hipMemcpyHostToDevice, st));
@@ -874,21 +963,162 @@ extern "C" int fbg_pindex_locate(fbg_pindex *ix, const uint8_t *patterns, const 
     const dim3 g(fbg_blocks(n, PX_THREADS));
     auto *co = ix->cnt_out.as<unsigned long long>(), *po = ix->pos_out.as<unsigned long long>();
     auto *lc = ix->lines_ctr.as<unsigned long long>();
-    if (ix->compact)
+    if (occ && ix->compact)
+        hipLaunchKernelGGL((k_px_walk<true, true, true>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
+                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc, ix->orec.as<uint2>());
+    else if (occ)
+        hipLaunchKernelGGL((k_px_walk<true, false, true>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
+                           ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc, ix->orec.as<uint2>());
+    else if (ix->compact)
         hipLaunchKernelGGL((k_px_walk<true, true>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
                            ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc, (uint2 *)nullptr);
     else
         hipLaunchKernelGGL((k_px_walk<true, false>), g, dim3(PX_THREADS), 0, st, d, ix->code.as<uint16_t>(), ix->C.as<uint32_t>(),
                            ix->pats.as<uint8_t>(), poff, vb, n, co, po, (uint8_t *)nullptr, (uint8_t *)nullptr, lc, (uint2 *)nullptr);
     FBG_HIP_TRY(ctx, hipGetLastError());
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_locate(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                                 uint64_t *count, uint64_t *pos)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    if (n_patterns && (!pat_off || !count || !pos)) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_locate: missing argument");
+    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_locate: at most 2^32 - 2 patterns per call");
+    ix->search_ms = 0;
+    ix->occ_lines = 0;
+    if (n_patterns == 0) return FBG_OK;
+    FBG_TRY(px_search(ix, "fbg_pindex_locate", patterns, pat_off, n_patterns, false));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = n_patterns;
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(count, co, n * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(pos, po, n * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(&ix->occ_lines, lc, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(count, ix->cnt_out.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(pos, ix->pos_out.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&ix->occ_lines, ix->lines_ctr.p, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     float ms = 0;
     FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
     ix->search_ms = ms;
+    return FBG_OK;
+}
+
+// The tables of the validation and of the occurrence expansion.  block is the scratch of fbg_pindex_validate (NULL
+// before its first call): k_po_expand reads sa, estart, esrc, edst and ctab only.
+static PvDev pv_dev(const fbg_pindex *ix)
+{
+    PvDev d;
+    d.sa = ix->sa.as<uint32_t>();
+    d.tpos = ix->vtpos.as<uint32_t>();
+    d.len = ix->vlen.as<uint32_t>();
+    d.estart = ix->vestart.as<uint32_t>();
+    d.esrc = ix->vesrc.as<uint32_t>();
+    d.edst = ix->vedst.as<uint32_t>();
+    d.ctab = ix->vctab.as<uint32_t>();
+    d.block = ix->vblock.as<uint32_t>();
+    d.rng = ix->vrng.as<uint2>();
+    d.flag = ix->vflag.as<uint8_t>();
+    d.text = ix->text.as<uint8_t>();
+    return d;
+}
+
+extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                                      uint64_t max_per_pattern, uint64_t *count, uint64_t *pos, uint32_t *restarts,
+                                      uint64_t *end_off, uint64_t *start_off, uint64_t *end_total, uint64_t *start_total,
+                                      double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    ix->occ_ready = false;
+    if (device_ms) *device_ms = 0;
+    if (!end_off || !start_off || (n_patterns && (!pat_off || !count || !pos || !restarts || !end_total || !start_total)))
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences: missing argument");
+    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_occurrences: at most 2^32 - 2 patterns per call");
+    end_off[0] = start_off[0] = 0;
+    ix->occ_n = n_patterns;
+    ix->occ_etotal = ix->occ_stotal = 0;
+    if (n_patterns == 0) { ix->occ_ready = true; return FBG_OK; }
+    const uint64_t n = n_patterns;
+    FBG_TRY(px_search(ix, "fbg_pindex_occurrences", patterns, pat_off, n, true));
+    hipStream_t st = ctx->stream;
+    uint64_t *esz = ix->oesz.as<uint64_t>(), *ssz = ix->ossz.as<uint64_t>(), *eoff = ix->oeoff.as<uint64_t>(), *soff = ix->osoff.as<uint64_t>();
+    hipLaunchKernelGGL(k_po_sizes, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, ix->cnt_out.as<unsigned long long>(),
+                       ix->pos_out.as<unsigned long long>(), (const uint2 *)ix->orec.as<uint2>(), n, max_per_pattern, ix->n_edges != 0,
+                       ix->oetot.as<uint64_t>(), ix->ostot.as<uint64_t>(), esz, ssz, ix->ors.as<uint32_t>(), ix->oel.as<uint32_t>(),
+                       ix->oss.as<uint32_t>(), ix->osk.as<uint32_t>());
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, esz, eoff, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
+    }));
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, ssz, soff, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
+    }));
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(count, ix->cnt_out.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(pos, ix->pos_out.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(restarts, ix->ors.p, n * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(end_total, ix->oetot.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(start_total, ix->ostot.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(end_off, eoff, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(start_off, soff, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    if (end_off[n] >= (1ull << 32) || start_off[n] >= (1ull << 32))
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_occurrences: %llu ends and %llu starts to report; a list takes fewer than 2^32 "
+                        "entries (lower max_per_pattern or split the batch)", (unsigned long long)end_off[n], (unsigned long long)start_off[n]);
+    ix->occ_etotal = end_off[n];
+    ix->occ_stotal = start_off[n];
+    ix->occ_ready = true;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
+                                            uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    if (device_ms) *device_ms = 0;
+    if (!ix->occ_ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences_fetch: no fbg_pindex_occurrences result to fetch");
+    const bool ends = end_src && end_dst && end_offset, starts = start_src && start_dst && start_offset;
+    if ((!ends && (end_src || end_dst || end_offset)) || (!starts && (start_src || start_dst || start_offset)))
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences_fetch: a list takes all three of its arrays or none");
+    const uint64_t ne = ends ? ix->occ_etotal : 0, ns = starts ? ix->occ_stotal : 0, n = ix->occ_n;
+    if (ne + ns == 0) return FBG_OK;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FBG_TRY(px_reserve(ix, ix->oplace, 3 * (ne + ns) * 4));
+    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
+    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    // oplace: src, dst, offset of the ends, then of the starts
+    uint32_t *pe = ix->oplace.as<uint32_t>(), *ps = pe + 3 * ne;
+    const PvDev d = pv_dev(ix);
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    if (ne)
+        hipLaunchKernelGGL(k_po_expand<false>, dim3(fbg_blocks(ne, PX_THREADS)), dim3(PX_THREADS), 0, st, d, (const uint64_t *)ix->oeoff.as<uint64_t>(),
+                           n, ne, (const uint32_t *)ix->oel.as<uint32_t>(), (const uint32_t *)ix->osk.as<uint32_t>(),
+                           (const uint32_t *)ix->ors.as<uint32_t>(), pe, pe + ne, pe + 2 * ne);
+    if (ns)
+        hipLaunchKernelGGL(k_po_expand<true>, dim3(fbg_blocks(ns, PX_THREADS)), dim3(PX_THREADS), 0, st, d, (const uint64_t *)ix->osoff.as<uint64_t>(),
+                           n, ns, (const uint32_t *)ix->oss.as<uint32_t>(), (const uint32_t *)ix->osk.as<uint32_t>(),
+                           (const uint32_t *)ix->ors.as<uint32_t>(), ps, ps + ns, ps + 2 * ns);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    if (ne) {
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(end_src, pe, ne * 4, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(end_dst, pe + ne, ne * 4, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(end_offset, pe + 2 * ne, ne * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (ns) {
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(start_src, ps, ns * 4, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(start_dst, ps + ns, ns * 4, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(start_offset, ps + 2 * ns, ns * 4, hipMemcpyDeviceToHost, st));
+    }
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
     return FBG_OK;
 }
 
@@ -952,18 +1182,7 @@ extern "C" int fbg_pindex_validate(fbg_pindex *ix, const uint32_t *node_block, c
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->vblock.p, node_block, n * 4, hipMemcpyHostToDevice, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ix->vctr.p, 0, 16, st));
-    PvDev d;
-    d.sa = ix->sa.as<uint32_t>();
-    d.tpos = ix->vtpos.as<uint32_t>();
-    d.len = ix->vlen.as<uint32_t>();
-    d.estart = ix->vestart.as<uint32_t>();
-    d.esrc = ix->vesrc.as<uint32_t>();
-    d.edst = ix->vedst.as<uint32_t>();
-    d.ctab = ix->vctab.as<uint32_t>();
-    d.block = ix->vblock.as<uint32_t>();
-    d.rng = ix->vrng.as<uint2>();
-    d.flag = ix->vflag.as<uint8_t>();
-    d.text = ix->text.as<uint8_t>();
+    const PvDev d = pv_dev(ix);
     auto *ctr = ix->vctr.as<unsigned long long>();
     uint8_t *dst = ix->vstatus.as<uint8_t>();
     uint32_t *wn = ix->vwn.as<uint32_t>(), *wo = ix->vwo.as<uint32_t>();

@@ -442,6 +442,57 @@ int fbg_pindex_validate(fbg_pindex *ix, const uint32_t *node_block, const uint8_
  * the wave tier, and the device bytes of the tables the build keeps for validation. */
 int fbg_pindex_validate_stats(const fbg_pindex *ix, uint64_t *slots_scanned, uint64_t *wave_nodes, uint64_t *table_bytes);
 
+/* Where each pattern occurs: the search of fbg_pindex_locate ("locate" above, unchanged: the same count and pos), and
+ * for every pattern that is found the places of the graph where the match ends and where it starts.
+ *
+ * Edge e = (a, b) of the build (distinct edges, by source, then destination), S_e = label(a) + label(b),
+ * n_e = |S_e|; its reversed copy with the leading '#' starts at text position estart[e], base = estart[e] + 1.  A
+ * place is (edge_src, edge_dst, offset): an index into S_e of the edge (edge_src, edge_dst), node indices as given to
+ * fbg_pindex_build.  The search of pattern P records on its way:
+ *   restarts   the steps that took the restart branch and went on;
+ *   at the first of them, before the range is replaced: k = symbols matched so far and [sl, sr] = the range after
+ *              the '#' step (every slot i there has SA[i] = estart[e] for one edge e);
+ *   at the end, if count > 0: the final range [l, r].
+ * For a found pattern (count > 0):
+ *   ends       for slot i in [l, r], p = SA[i], e = the edge whose string holds p:
+ *              (src(e), dst(e), n_e - 1 - (p - base)), the position of the pattern's last symbol.  end_total = count.
+ *   starts     restarts == 0: the same slots, offset = end offset - |P| + 1 (the match lies inside one edge string);
+ *              start_total = count.  restarts > 0: for slot i in [sl, sr], e = the edge with estart[e] == SA[i]:
+ *              (src(e), dst(e), n_e - k): the first k symbols of P are a suffix of S_e; start_total = sr - sl + 1.
+ * A pattern that is not found, the empty one included, has no ends and no starts (both totals 0), whatever was
+ * recorded; its restarts are still reported.  Places come in ascending SA slot order.  max_per_pattern = M: only the
+ * first min(total, M) slots of each range are reported, the totals say how many there are; M = 0 reports totals and
+ * restarts only.  Offsets are computed modulo 2^32: they lie inside S_e for patterns without '#' and zero bytes
+ * (others can match across a separator and get offsets outside it).  A graph without edges has no places: its lists
+ * are empty.
+ *
+ * These are the occurrences of the reference's search, with its looseness: after a restart the search goes on from
+ * all occurrences of the enclosing node label, which in a semi-repeat-free graph may be a proper prefix of a sibling
+ * node of the same block.  The starts and the ends of a pattern with restarts are therefore two independent lists; a
+ * (start, end) pair is no proof of a path through the graph.  Paths are not verified here.
+ *
+ * Two calls, because the size of the lists is known only after the search and the buffers are the caller's:
+ *   fbg_pindex_occurrences        search and sizes.  count, pos, end_total, start_total: n_patterns values; restarts:
+ *       n_patterns values; end_off, start_off: n_patterns + 1 CSR offsets of the capped lists (pattern k's places are
+ *       entries end_off[k] .. end_off[k + 1] of the fetched arrays).  The ranges stay on the device until the next
+ *       fbg_pindex_occurrences on this index; fbg_pindex_locate and fbg_pindex_validate in between do not disturb them,
+ *       and this call leaves fbg_pindex_stats' search_ms and occ_lines (the last fbg_pindex_locate) alone.
+ *       *device_ms (may be NULL): device time of length sort, walk, sizes and scans, without the copies.
+ *   fbg_pindex_occurrences_fetch  expands the ranges into end_* (end_off[n_patterns] entries each) and start_*
+ *       (start_off[n_patterns] entries each).  Either list may be left out by passing NULL for its three arrays; may be
+ *       called again.  *device_ms (may be NULL): device time of the expansion kernels.
+ * Errors: a NULL index, a NULL end_off / start_off, or with n_patterns > 0 a NULL pat_off or output array:
+ * FBG_ERR_INVALID; a fetch without a successful fbg_pindex_occurrences before it, or with one or two of a list's
+ * three arrays NULL: FBG_ERR_INVALID; a capped list of 2^32 entries or more: FBG_ERR_TOO_LARGE (nothing to fetch then).
+ * No table is added at build time; the per-call scratch (about 90 bytes per pattern, 12 per reported place) is owned by
+ * the index. */
+int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                           uint64_t max_per_pattern, uint64_t *count, uint64_t *pos, uint32_t *restarts,
+                           uint64_t *end_off, uint64_t *start_off, uint64_t *end_total, uint64_t *start_total,
+                           double *device_ms);
+int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
+                                 uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
