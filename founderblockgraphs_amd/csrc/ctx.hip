@@ -23,7 +23,7 @@ int fbg_fail(fbg_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
-int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes)
+int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes, std::vector<DevBuf *> *owner, bool accounted)
 {
     if (bytes == 0) bytes = 256;
     if (b.cap >= bytes) return FBG_OK;
@@ -31,7 +31,7 @@ int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes)
     if (b.p) {
         FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         FBG_HIP_TRY(ctx, hipFree(b.p));
-        ctx->held_bytes -= b.cap;
+        if (accounted) ctx->held_bytes -= b.cap;
         b.p = nullptr; b.cap = 0;
     }
     size_t want = (bytes + 255) & ~(size_t)255;
@@ -42,6 +42,8 @@ int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes)
                         want, hipGetErrorString(e), (unsigned long long)ctx->held_bytes);
     }
     b.cap = want;
+    if (owner && !b.listed) { owner->push_back(&b); b.listed = true; }
+    if (!accounted) return FBG_OK;
     ctx->held_bytes += want;
     ctx->alloc_calls++;
     ctx->alloc_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_begin).count();
@@ -54,9 +56,15 @@ void fbg_release(fbg_ctx *ctx, DevBuf &b)
 {
     if (b.p) {
         (void)hipFree(b.p);
-        ctx->held_bytes -= b.cap;
+        if (ctx) ctx->held_bytes -= b.cap;
         b.p = nullptr; b.cap = 0;
     }
+}
+
+void fbg_release_all(fbg_ctx *ctx, std::vector<DevBuf *> &bufs)
+{
+    for (DevBuf *b : bufs) { fbg_release(ctx, *b); b->listed = false; }
+    bufs.clear();
 }
 
 // ---- host <-> device transfers -----------------------------------------------------------------------------------
@@ -176,14 +184,69 @@ int fbg_stage_end(fbg_ctx *ctx, int stage, int launches)
 // option table: key -> member of FbgOptions
 struct OptKey { const char *name; int64_t FbgOptions::*field; };
 static const OptKey g_opt_keys[] = {
-    {"no_ranked", &FbgOptions::no_ranked}, {"no_packed", &FbgOptions::no_packed}, {"force_wide", &FbgOptions::force_wide},
-    {"full_keys", &FbgOptions::full_keys}, {"no_msd_sort", &FbgOptions::no_msd_sort}, {"msd_min", &FbgOptions::msd_min},
-    {"bp_min", &FbgOptions::bp_min}, {"record_scatter", &FbgOptions::record_scatter}, {"lcp_text", &FbgOptions::lcp_text},
-    {"no_aux_stream", &FbgOptions::no_aux_stream}, {"rank_no_threshold", &FbgOptions::rank_no_threshold},
-    {"dp_literal", &FbgOptions::dp_literal}, {"dp_wave", &FbgOptions::dp_wave}, {"dp_safe_window", &FbgOptions::dp_safe_window},
-    {"dp_tile", &FbgOptions::dp_tile}, {"pure_scan", &FbgOptions::pure_scan}, {"gapped_rank", &FbgOptions::gapped_rank}, {"part_tricks_off", &FbgOptions::part_tricks_off}, {"msd_sample_bins", &FbgOptions::msd_sample_bins}, {"msd_min_force", &FbgOptions::msd_min_force}, {"msd_probe", &FbgOptions::msd_probe}, {"msd_xcd", &FbgOptions::msd_xcd}, {"rank_no_lean", &FbgOptions::rank_no_lean}, {"no_stream_upload", &FbgOptions::no_stream_upload},
-    {"span_scan", &FbgOptions::span_scan}, {"span_key_flags", &FbgOptions::span_key_flags}, {"span_slow_split", &FbgOptions::span_slow_split}, {"poison", &FbgOptions::poison}, {"dpw_matrix", &FbgOptions::dpw_matrix}, {"dp_chain1", &FbgOptions::dp_chain1},
+    {"no_ranked", &FbgOptions::no_ranked},
+    {"no_packed", &FbgOptions::no_packed},
+    {"force_wide", &FbgOptions::force_wide},
+    {"full_keys", &FbgOptions::full_keys},
+    {"no_msd_sort", &FbgOptions::no_msd_sort},
+    {"msd_min", &FbgOptions::msd_min},
+    {"bp_min", &FbgOptions::bp_min},
+    {"record_scatter", &FbgOptions::record_scatter},
+    {"lcp_text", &FbgOptions::lcp_text},
+    {"no_aux_stream", &FbgOptions::no_aux_stream},
+    {"rank_no_threshold", &FbgOptions::rank_no_threshold},
+    {"dp_literal", &FbgOptions::dp_literal},
+    {"dp_wave", &FbgOptions::dp_wave},
+    {"dp_safe_window", &FbgOptions::dp_safe_window},
+    {"dp_tile", &FbgOptions::dp_tile},
+    {"pure_scan", &FbgOptions::pure_scan},
+    {"gapped_rank", &FbgOptions::gapped_rank},
+    {"part_tricks_off", &FbgOptions::part_tricks_off},
+    {"msd_sample_bins", &FbgOptions::msd_sample_bins},
+    {"msd_min_force", &FbgOptions::msd_min_force},
+    {"msd_probe", &FbgOptions::msd_probe},
+    {"msd_xcd", &FbgOptions::msd_xcd},
+    {"rank_no_lean", &FbgOptions::rank_no_lean},
+    {"no_stream_upload", &FbgOptions::no_stream_upload},
+    {"span_scan", &FbgOptions::span_scan},
+    {"span_key_flags", &FbgOptions::span_key_flags},
+    {"span_slow_split", &FbgOptions::span_slow_split},
+    {"poison", &FbgOptions::poison},
+    {"dpw_matrix", &FbgOptions::dpw_matrix},
+    {"dp_chain1", &FbgOptions::dp_chain1},
     {"msd_ext", &FbgOptions::msd_ext},
+};
+
+// read-only keys of fbg_get_option: what the context and its last build report
+struct InfoKey { const char *name; int64_t (*get)(const fbg_ctx &); };
+static const InfoKey g_info_keys[] = {
+    {"grs_threshold", [](const fbg_ctx &c) -> int64_t { return c.grs_t; }},
+    {"grs_redone", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.grs_redone; }},
+    {"dp_kind", [](const fbg_ctx &c) -> int64_t { return c.dp_kind; }},
+    {"msd_decline", [](const fbg_ctx &c) -> int64_t { return c.diag.msd_decline; }},
+    {"pass1_ahead", [](const fbg_ctx &c) -> int64_t { return c.diag.pass1_ahead; }},
+    {"ext_pairs", [](const fbg_ctx &c) -> int64_t { return c.diag.ext_pairs; }},
+    {"text_pairs", [](const fbg_ctx &c) -> int64_t { return c.diag.text_pairs; }},
+    {"rank_lean_used", [](const fbg_ctx &c) -> int64_t { return c.diag.rank_lean_used; }},
+    {"rank_lean_launched", [](const fbg_ctx &c) -> int64_t { return c.diag.rank_lean_launched; }},
+    {"pairs_rb", [](const fbg_ctx &c) -> int64_t { return c.diag.pairs_rb; }},
+    {"key_b", [](const fbg_ctx &c) -> int64_t { return c.key_b; }},
+    {"key_K", [](const fbg_ctx &c) -> int64_t { return c.key_K; }},
+    {"key_packed", [](const fbg_ctx &c) -> int64_t { return c.key_packed; }},
+    {"key_compact", [](const fbg_ctx &c) -> int64_t { return c.key_compact; }},
+    {"alloc_calls", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.alloc_calls; }},
+    {"alloc_us", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.alloc_us; }},
+    {"span_decline", [](const fbg_ctx &c) -> int64_t { return c.diag.sp_decline; }},
+    {"span_key_flags_used", [](const fbg_ctx &c) -> int64_t { return c.ix.index_valid && c.ix.spanned() && c.ix.sp_key_flags_sorted; }},
+    {"span_scan_used", [](const fbg_ctx &c) -> int64_t { return c.ix.index_valid && c.ix.spanned(); }},
+    {"span_scan_work", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.sp_work; }},
+    {"span_groups", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.sp_G; }},
+    {"span_odd_groups", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.sp_n_odd[0] + c.sp_n_odd[1] + c.sp_n_odd[2] + c.sp_n_odd[3]; }},
+    {"span_irregular", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.sp_n_irr; }},
+    {"span_chain", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.sp_chain_n; }},
+    {"span_slow_groups", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.sp_slow_n; }},
+    // which form the current index has
+    {"index_kind", [](const fbg_ctx &c) -> int64_t { return !c.ix.index_valid ? -1 : c.ix.part_active ? 3 : c.ix.granked() ? 2 : c.ix.ranked() ? 1 : 0; }},
 };
 
 // The one place the library reads the environment: FBG_DEBUG_ENV=1 lets FBG_<KEY>=<integer> preset the options of
@@ -198,6 +261,35 @@ static void options_from_env(FbgOptions &o)
         for (const char *c = k.name; *c; c++) name += (char)toupper((unsigned char)*c);
         if (const char *v = env(name)) o.*(k.field) = *v ? strtoll(v, nullptr, 10) : 1;
     }
+}
+
+// The one reset of what a context knows about its index and the build that made it (the top of the two build entry points)
+void fbg_index_reset(fbg_ctx *ctx)
+{
+    ctx->ix = IndexState();
+    ctx->diag = BuildDiag();
+}
+
+// the two DPs over v[] from host memory: v up, the sweep, s / prev / boundaries down
+static int host_dp_v(fbg_ctx *ctx, int (*dp)(fbg_ctx *, const uint64_t *, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *), const char *name,
+                     const uint64_t *v, uint64_t n, uint64_t *s_out, uint64_t *prev_out, uint64_t *boundaries_out, uint64_t *count_out)
+{
+    if (!ctx) return FBG_ERR_INVALID;
+    if (!v || !boundaries_out || !count_out || n == 0 || n >= (1ull << 31))
+        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: bad arguments", name);
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t w = n * sizeof(uint64_t);
+    for (DevBuf *b : {&ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d}) FBG_TRY(fbg_reserve(ctx, *b, w));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, v, w, hipMemcpyHostToDevice, ctx->stream));
+    int rc = dp(ctx, ctx->io_a.as<uint64_t>(), n, ctx->io_c.as<uint64_t>(), ctx->io_d.as<uint64_t>(), ctx->io_b.as<uint64_t>(), count_out);
+    if (rc != FBG_OK && rc != FBG_ERR_NO_SEGMENTATION) return rc;
+    if (s_out) FBG_HIP_TRY(ctx, hipMemcpyAsync(s_out, ctx->io_c.p, w, hipMemcpyDeviceToHost, ctx->stream));
+    if (prev_out) FBG_HIP_TRY(ctx, hipMemcpyAsync(prev_out, ctx->io_d.p, w, hipMemcpyDeviceToHost, ctx->stream));
+    if (rc == FBG_OK)
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(boundaries_out, ctx->io_b.p, *count_out * sizeof(uint64_t),
+                                        hipMemcpyDeviceToHost, ctx->stream));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
 }
 
 extern "C" {
@@ -215,40 +307,13 @@ int fbg_get_option(const fbg_ctx *ctx, const char *key, int64_t *value)
     if (!ctx || !key || !value) return FBG_ERR_INVALID;
     for (const OptKey &k : g_opt_keys)
         if (strcmp(k.name, key) == 0) { *value = ctx->opt.*(k.field); return FBG_OK; }
-    if (strcmp(key, "grs_threshold") == 0) { *value = ctx->grs_t; return FBG_OK; }
-    if (strcmp(key, "grs_redone") == 0) { *value = (int64_t)ctx->grs_redone; return FBG_OK; }
-    if (strcmp(key, "dp_kind") == 0) { *value = ctx->dp_kind; return FBG_OK; }
-    if (strcmp(key, "msd_decline") == 0) { *value = ctx->msd_decline; return FBG_OK; }
-    if (strcmp(key, "pass1_ahead") == 0) { *value = ctx->pass1_ahead; return FBG_OK; }
-    if (strcmp(key, "ext_pairs") == 0) { *value = ctx->ext_pairs; return FBG_OK; }
-    if (strcmp(key, "text_pairs") == 0) { *value = ctx->text_pairs; return FBG_OK; }
-    if (strcmp(key, "rank_lean_used") == 0) { *value = ctx->rank_lean_used; return FBG_OK; }
-    if (strcmp(key, "rank_lean_launched") == 0) { *value = ctx->rank_lean_launched; return FBG_OK; }
-    if (strcmp(key, "pairs_rb") == 0) { *value = ctx->pairs_rb; return FBG_OK; }
-    if (strcmp(key, "key_b") == 0) { *value = ctx->key_b; return FBG_OK; }
-    if (strcmp(key, "key_K") == 0) { *value = ctx->key_K; return FBG_OK; }
-    if (strcmp(key, "key_packed") == 0) { *value = ctx->key_packed; return FBG_OK; }
-    if (strcmp(key, "key_compact") == 0) { *value = ctx->key_compact; return FBG_OK; }
-    if (strcmp(key, "alloc_calls") == 0) { *value = (int64_t)ctx->alloc_calls; return FBG_OK; }
-    if (strcmp(key, "alloc_us") == 0) { *value = (int64_t)ctx->alloc_us; return FBG_OK; }
-    if (strcmp(key, "span_decline") == 0) { *value = ctx->sp_decline; return FBG_OK; }
-    if (strcmp(key, "span_key_flags_used") == 0) { *value = (ctx->index_valid && ctx->granked && ctx->spanned && ctx->sp_key_flags_sorted) ? 1 : 0; return FBG_OK; }
-    if (strcmp(key, "span_scan_used") == 0) { *value = (ctx->index_valid && ctx->granked && ctx->spanned) ? 1 : 0; return FBG_OK; }
-    if (strcmp(key, "span_scan_work") == 0) { *value = (int64_t)ctx->sp_work; return FBG_OK; }
-    if (strcmp(key, "span_groups") == 0) { *value = (int64_t)ctx->sp_G; return FBG_OK; }
-    if (strcmp(key, "span_odd_groups") == 0) { *value = (int64_t)ctx->sp_n_odd[0] + ctx->sp_n_odd[1] + ctx->sp_n_odd[2] + ctx->sp_n_odd[3]; return FBG_OK; }
-    if (strcmp(key, "span_irregular") == 0) { *value = (int64_t)ctx->sp_n_irr; return FBG_OK; }
-    if (strcmp(key, "span_chain") == 0) { *value = (int64_t)ctx->sp_chain_n; return FBG_OK; }
-    if (strcmp(key, "span_slow_groups") == 0) { *value = (int64_t)ctx->sp_slow_n; return FBG_OK; }
+    for (const InfoKey &k : g_info_keys)
+        if (strcmp(k.name, key) == 0) { *value = k.get(*ctx); return FBG_OK; }
     if (strncmp(key, "span_dbg", 8) == 0 && key[8] >= '0' && key[8] <= '7' && !key[9]) {   // debug builds (SP_PHASE_TIMERS): cycles per phase of k_sp_odd_pairs
         unsigned long long v = 0;
         if (hipStreamSynchronize(ctx->stream) != hipSuccess || ctx->scalars.cap < 256 * 8 ||
             hipMemcpy(&v, (const unsigned long long *)ctx->scalars.p + 208 + 24 + (key[8] - '0'), 8, hipMemcpyDeviceToHost) != hipSuccess) return FBG_ERR_HIP;
         *value = (int64_t)v;
-        return FBG_OK;
-    }
-    if (strcmp(key, "index_kind") == 0) {      // read-only: which form the current index has
-        *value = !ctx->index_valid ? -1 : ctx->part_active ? 3 : ctx->granked ? 2 : ctx->ranked ? 1 : 0;
         return FBG_OK;
     }
     return FBG_ERR_INVALID;
@@ -294,15 +359,8 @@ void fbg_ctx_destroy(fbg_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf *bufs[] = {&ctx->msa_own, &ctx->text, &ctx->pos, &ctx->tot, &ctx->segtab, &ctx->exc_scratch, &ctx->prow, &ctx->igrow, &ctx->rec,
-                      &ctx->xlist, &ctx->gmax, &ctx->excol, &ctx->xslot, &ctx->xbits, &ctx->exc, &ctx->colT, &ctx->keysA, &ctx->keysB, &ctx->valsA, &ctx->valsB, &ctx->grp, &ctx->flags,
-                      &ctx->msd_ext, &ctx->list, &ctx->tie_list, &ctx->big_groups, &ctx->kargs, &ctx->msd_w, &ctx->msd_v, &ctx->tmp, &ctx->small, &ctx->scalars, &ctx->dp_a, &ctx->dp_b, &ctx->dp_c,
-                      &ctx->dp_d, &ctx->dp_e, &ctx->dp_f, &ctx->dp_g, &ctx->dp_h, &ctx->io_a, &ctx->io_b,
-                      &ctx->io_c, &ctx->io_d, &ctx->bt_up, &ctx->bt_dep, &ctx->ps_a, &ctx->ps_b, &ctx->ps_c, &ctx->ps_d,
-                      &ctx->ps_e, &ctx->ps_f, &ctx->ps_g, &ctx->ps_h, &ctx->gwin, &ctx->gbits, &ctx->gwin_rows,
-                      &ctx->sp_cells, &ctx->sp_flagT, &ctx->sp_cwin, &ctx->sp_tiles, &ctx->sp_gstart, &ctx->sp_gcol, &ctx->sp_gflags, &ctx->sp_rstart, &ctx->sp_rid,
-                      &ctx->sp_gplo, &ctx->sp_gphi, &ctx->sp_gval, &ctx->sp_odd, &ctx->sp_irr, &ctx->sp_chain, &ctx->sp_slow, &ctx->sp_mins};
-    for (DevBuf *b : bufs) fbg_release(ctx, *b);
+    fbg_release_all(ctx, ctx->bufs);
+    fbg_msd_pre_free(ctx);
     if (ctx->up_stream) {
         (void)hipStreamSynchronize(ctx->up_stream);
         for (auto &e : ctx->up_ev) if (e) (void)hipEventDestroy(e);
@@ -363,13 +421,19 @@ int fbg_release_scratch(fbg_ctx *ctx)
     if (!ctx) return FBG_ERR_INVALID;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // valsB stays: it is the suffix array; so does whichever key buffer holds the sorted slots of a rank-order index
-    const bool sorted_in_A = (ctx->ranked || ctx->granked) && ctx->rk_keys == ctx->keysA.as<uint64_t>();
-    DevBuf *bufs[] = {sorted_in_A ? &ctx->keysB : &ctx->keysA, &ctx->valsA, &ctx->grp, &ctx->flags, &ctx->list, &ctx->tie_list, &ctx->msd_w, &ctx->msd_v, &ctx->msd_ext,
-                      &ctx->tmp, &ctx->dp_a, &ctx->dp_b, &ctx->dp_c, &ctx->dp_d, &ctx->dp_e, &ctx->dp_f,
-                      &ctx->dp_g, &ctx->dp_h, &ctx->ps_a, &ctx->ps_b, &ctx->ps_c, &ctx->ps_d, &ctx->ps_e, &ctx->ps_f,
-                      &ctx->ps_g, &ctx->ps_h, &ctx->sp_cells, &ctx->sp_flagT, &ctx->sp_tiles};
-    for (DevBuf *b : bufs) fbg_release(ctx, *b);
+    // Everything goes but what a scan, a download or the next call on this index reads:
+    const bool sorted_in_A = (ctx->ix.ranked() || ctx->ix.granked()) && ctx->ix.rk_keys == ctx->keysA.as<uint64_t>();
+    const DevBuf *keep[] = {
+        &ctx->msa_own, &ctx->text, &ctx->pos, &ctx->tot, &ctx->segtab, &ctx->colT, &ctx->gwin_rows,        // the MSA, the text and its row tables
+        &ctx->valsB, sorted_in_A ? &ctx->keysA : &ctx->keysB,     // the suffix array; the key buffer with the sorted slots of a rank-order index
+        // the index tables the scans read: record path, rank order, gapped, span
+        &ctx->prow, &ctx->igrow, &ctx->rec, &ctx->xlist, &ctx->gmax, &ctx->excol, &ctx->xslot, &ctx->xbits, &ctx->exc, &ctx->exc_scratch,
+        &ctx->big_groups, &ctx->gwin, &ctx->gbits, &ctx->sp_cwin, &ctx->sp_gstart, &ctx->sp_gcol, &ctx->sp_gflags, &ctx->sp_rstart, &ctx->sp_rid,
+        &ctx->sp_gplo, &ctx->sp_gphi, &ctx->sp_gval, &ctx->sp_odd, &ctx->sp_irr, &ctx->sp_chain, &ctx->sp_slow, &ctx->sp_mins,
+        // small tables, counters and kernel arguments; the buffers of the host entry points and of the backtrack
+        &ctx->small, &ctx->scalars, &ctx->kargs, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->bt_up, &ctx->bt_dep};
+    for (DevBuf *b : ctx->bufs)
+        if (std::find(std::begin(keep), std::end(keep), b) == std::end(keep)) fbg_release(ctx, *b);
     return FBG_OK;
 }
 
@@ -396,7 +460,7 @@ int fbg_msa_set_device(fbg_ctx *ctx, const uint8_t *d_msa, uint64_t m, uint64_t 
 {
     FBG_TRY(check_dims(ctx, m, n));
     if (!d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "null MSA pointer");
-    ctx->d_msa = d_msa; ctx->m = m; ctx->n = n; ctx->index_valid = false;
+    ctx->d_msa = d_msa; ctx->m = m; ctx->n = n; ctx->ix.index_valid = false;
     return FBG_OK;
 }
 
@@ -407,7 +471,7 @@ int fbg_msa_load_host(fbg_ctx *ctx, const uint8_t *msa, uint64_t m, uint64_t n)
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     FBG_TRY(fbg_reserve(ctx, ctx->msa_own, m * n));
     FBG_TRY(fbg_upload(ctx, ctx->msa_own.p, msa, m * n));
-    ctx->d_msa = ctx->msa_own.as<uint8_t>(); ctx->m = m; ctx->n = n; ctx->index_valid = false;
+    ctx->d_msa = ctx->msa_own.as<uint8_t>(); ctx->m = m; ctx->n = n; ctx->ix.index_valid = false;
     return FBG_OK;
 }
 
@@ -420,10 +484,7 @@ int fbg_index_build(fbg_ctx *ctx, int reversed, const uint8_t *ignore_chars, uin
         ctx->timers[st].recorded = false;
         ctx->timers[st].launches = 0;
     }
-    ctx->index_valid = false;
-    ctx->granked = false;
-    ctx->spanned = false;
-    ctx->gpart = false;
+    fbg_index_reset(ctx);
     ctx->reversed = reversed ? 1 : 0;
     FBG_TRY(fbg_build_text(ctx, reversed ? nullptr : ignore_chars, reversed ? 0 : ignore_len));
     FBG_TRY(fbg_suffix_sort(ctx));
@@ -435,7 +496,7 @@ int fbg_index_build(fbg_ctx *ctx, int reversed, const uint8_t *ignore_chars, uin
         FBG_HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         if (free_b < total_b / 2) FBG_TRY(fbg_release_scratch(ctx));
     }
-    ctx->index_valid = true;
+    ctx->ix.index_valid = true;
     return FBG_OK;
 }
 
@@ -451,12 +512,8 @@ int fbg_part_index_build_ignore(fbg_ctx *ctx, int reversed, int part, int nparts
     if (!d_blob || !ok || nparts < 1 || part < 0 || part >= nparts || (ignore_len && !ignore_chars))
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_part_index_build: bad arguments");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->index_valid = false;
-    ctx->ranked = false;
-    ctx->granked = false;
-    ctx->spanned = false;
+    fbg_index_reset(ctx);
     ctx->reversed = reversed ? 1 : 0;
-    ctx->gpart = false;
     ctx->allow_wide = true;                        // the partitions together may hold a text of 2^32 symbols and more
     const int rc = fbg_build_text(ctx, reversed ? nullptr : ignore_chars, reversed ? 0 : ignore_len);
     ctx->allow_wide = false;
@@ -467,18 +524,18 @@ int fbg_part_index_build_ignore(fbg_ctx *ctx, int reversed, int part, int nparts
 int fbg_part_scan(fbg_ctx *ctx, const void *d_blobs, uint32_t *d_gmax, int *ok)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->part_active || ctx->index_valid)
+    if (!ctx->ix.part_active || ctx->ix.index_valid)
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_part_scan needs fbg_part_index_build first");
     if (!d_blobs || !d_gmax || !ok) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_part_scan: bad arguments");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->gpart) return fbg_grs_part_scan(ctx, static_cast<const uint8_t *>(d_blobs), d_gmax, ok);
+    if (ctx->ix.gpart) return fbg_grs_part_scan(ctx, static_cast<const uint8_t *>(d_blobs), d_gmax, ok);
     return fbg_rank_part_runs(ctx, static_cast<const uint8_t *>(d_blobs), d_gmax, ok);
 }
 
 int fbg_part_finish(fbg_ctx *ctx, const uint32_t *d_gmax, int *ok)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->part_active || ctx->index_valid)
+    if (!ctx->ix.part_active || ctx->ix.index_valid)
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_part_finish needs fbg_part_scan first");
     if (!d_gmax || !ok) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_part_finish: bad arguments");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -490,11 +547,11 @@ int fbg_part_finish(fbg_ctx *ctx, const uint32_t *d_gmax, int *ok)
     if (*ok) {
         // a column whose maximum is below the threshold some partition scanned with may have lost a larger value
         uint64_t unfilled = 0;
-        if (ctx->gpart) FBG_TRY(fbg_grs_part_unfilled(ctx, &unfilled));
+        if (ctx->ix.gpart) FBG_TRY(fbg_grs_part_unfilled(ctx, &unfilled));
         else FBG_TRY(fbg_rank_part_unfilled(ctx, &unfilled));
         if (unfilled) { *ok = 2; return FBG_OK; }
-        ctx->n_exc = 0; ctx->index_valid = true;
-        if (ctx->gpart) ctx->granked = true; else ctx->ranked = true;
+        ctx->ix.n_exc = 0; ctx->ix.index_valid = true;
+        ctx->ix.kind = ctx->ix.gpart ? IndexKind::gapped : IndexKind::ranked;
     }
     return FBG_OK;
 }
@@ -502,12 +559,12 @@ int fbg_part_finish(fbg_ctx *ctx, const uint32_t *d_gmax, int *ok)
 int fbg_part_rescan(fbg_ctx *ctx, uint32_t *d_gmax)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->part_active || ctx->index_valid)
+    if (!ctx->ix.part_active || ctx->ix.index_valid)
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_part_rescan follows a fbg_part_finish that returned *ok = 2");
     if (!d_gmax) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_part_rescan: bad arguments");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t verdict = 0;
-    if (ctx->gpart) { FBG_TRY(fbg_grs_part_rescan(ctx)); verdict = ctx->grs_part_failed ? 1u : 0u; }
+    if (ctx->ix.gpart) { FBG_TRY(fbg_grs_part_rescan(ctx)); verdict = ctx->grs_part_failed ? 1u : 0u; }
     else FBG_TRY(fbg_rank_part_rescan(ctx));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(d_gmax, ctx->gmax.p, (ctx->n + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(d_gmax + ctx->n, &verdict, 4, hipMemcpyHostToDevice, ctx->stream));
@@ -518,7 +575,7 @@ int fbg_part_rescan(fbg_ctx *ctx, uint32_t *d_gmax)
 int fbg_scan_f(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int disable_tricks, uint64_t *d_f)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->index_valid || ctx->reversed)
+    if (!ctx->ix.index_valid || ctx->reversed)
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_scan_f needs fbg_index_build(reversed=0) first");
     if (x0 > x1 || x1 > ctx->n || !d_f) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_scan_f: bad column range");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -528,7 +585,7 @@ int fbg_scan_f(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int disable_tricks, uint6
 int fbg_scan_v(fbg_ctx *ctx, uint64_t x0, uint64_t x1, uint64_t *d_v)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->index_valid || !ctx->reversed)
+    if (!ctx->ix.index_valid || !ctx->reversed)
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_scan_v needs fbg_index_build(reversed=1) first");
     if (x0 > x1 || x1 > ctx->n || !d_v) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_scan_v: bad column range");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -558,7 +615,7 @@ int fbg_repeatfree_dp_device(fbg_ctx *ctx, const uint64_t *d_v, uint64_t n, uint
 int fbg_scan_gapped_v(fbg_ctx *ctx, uint64_t *d_v)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->index_valid || ctx->reversed)
+    if (!ctx->ix.index_valid || ctx->reversed)
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_scan_gapped_v needs fbg_index_build(reversed=0) first");
     if (!d_v) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_scan_gapped_v: null d_v");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -592,7 +649,7 @@ int fbg_elastic_f(fbg_ctx *ctx, const uint8_t *msa, uint64_t m, uint64_t n, cons
         FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
         FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         FBG_TRY(fbg_reserve(ctx, ctx->msa_own, m * n));
-        ctx->d_msa = ctx->msa_own.as<uint8_t>(); ctx->m = m; ctx->n = n; ctx->index_valid = false;
+        ctx->d_msa = ctx->msa_own.as<uint8_t>(); ctx->m = m; ctx->n = n; ctx->ix.index_valid = false;
         ctx->up_host = msa;
         const int rc = fbg_index_build(ctx, 0, ignore_chars, ignore_len);
         ctx->up_host = nullptr;
@@ -620,10 +677,7 @@ int fbg_minmax_dp(fbg_ctx *ctx, const uint64_t *f, uint64_t n, uint64_t *boundar
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_minmax_dp: bad arguments");
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     size_t w = (n + 1) * sizeof(uint64_t);
-    FBG_TRY(fbg_reserve(ctx, ctx->io_a, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_b, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_c, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_d, w));
+    for (DevBuf *b : {&ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d}) FBG_TRY(fbg_reserve(ctx, *b, w));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, f, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     int rc = fbg_dp_minmax(ctx, ctx->io_a.as<uint64_t>(), n, ctx->io_b.as<uint64_t>(), count_out,
                            ctx->io_c.as<uint64_t>(), ctx->io_d.as<uint64_t>());
@@ -655,26 +709,7 @@ int fbg_repeatfree_v(fbg_ctx *ctx, const uint8_t *msa, uint64_t m, uint64_t n, u
 int fbg_repeatfree_dp(fbg_ctx *ctx, const uint64_t *v, uint64_t n, uint64_t *s_out, uint64_t *prev_out,
                       uint64_t *boundaries_out, uint64_t *count_out)
 {
-    if (!ctx) return FBG_ERR_INVALID;
-    if (!v || !boundaries_out || !count_out || n == 0 || n >= (1ull << 31))
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_repeatfree_dp: bad arguments");
-    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t w = n * sizeof(uint64_t);
-    FBG_TRY(fbg_reserve(ctx, ctx->io_a, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_b, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_c, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_d, w));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, v, w, hipMemcpyHostToDevice, ctx->stream));
-    int rc = fbg_dp_repeatfree(ctx, ctx->io_a.as<uint64_t>(), n, ctx->io_c.as<uint64_t>(),
-                               ctx->io_d.as<uint64_t>(), ctx->io_b.as<uint64_t>(), count_out);
-    if (rc != FBG_OK && rc != FBG_ERR_NO_SEGMENTATION) return rc;
-    if (s_out) FBG_HIP_TRY(ctx, hipMemcpyAsync(s_out, ctx->io_c.p, w, hipMemcpyDeviceToHost, ctx->stream));
-    if (prev_out) FBG_HIP_TRY(ctx, hipMemcpyAsync(prev_out, ctx->io_d.p, w, hipMemcpyDeviceToHost, ctx->stream));
-    if (rc == FBG_OK)
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(boundaries_out, ctx->io_b.p, *count_out * sizeof(uint64_t),
-                                        hipMemcpyDeviceToHost, ctx->stream));
-    FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return rc;
+    return host_dp_v(ctx, fbg_dp_repeatfree, "fbg_repeatfree_dp", v, n, s_out, prev_out, boundaries_out, count_out);
 }
 
 int fbg_gapped_v(fbg_ctx *ctx, const uint8_t *msa, uint64_t m, uint64_t n, uint64_t *v)
@@ -693,52 +728,30 @@ int fbg_gapped_v(fbg_ctx *ctx, const uint8_t *msa, uint64_t m, uint64_t n, uint6
 int fbg_gapped_dp(fbg_ctx *ctx, const uint64_t *v, uint64_t n, uint64_t *s_out, uint64_t *prev_out,
                   uint64_t *boundaries_out, uint64_t *count_out)
 {
-    if (!ctx) return FBG_ERR_INVALID;
-    if (!v || !boundaries_out || !count_out || n == 0 || n >= (1ull << 31))
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_gapped_dp: bad arguments");
-    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t w = n * sizeof(uint64_t);
-    FBG_TRY(fbg_reserve(ctx, ctx->io_a, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_b, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_c, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->io_d, w));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, v, w, hipMemcpyHostToDevice, ctx->stream));
-    int rc = fbg_dp_gapped(ctx, ctx->io_a.as<uint64_t>(), n, ctx->io_c.as<uint64_t>(),
-                           ctx->io_d.as<uint64_t>(), ctx->io_b.as<uint64_t>(), count_out);
-    if (rc != FBG_OK && rc != FBG_ERR_NO_SEGMENTATION) return rc;
-    if (s_out) FBG_HIP_TRY(ctx, hipMemcpyAsync(s_out, ctx->io_c.p, w, hipMemcpyDeviceToHost, ctx->stream));
-    if (prev_out) FBG_HIP_TRY(ctx, hipMemcpyAsync(prev_out, ctx->io_d.p, w, hipMemcpyDeviceToHost, ctx->stream));
-    if (rc == FBG_OK)
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(boundaries_out, ctx->io_b.p, *count_out * sizeof(uint64_t),
-                                        hipMemcpyDeviceToHost, ctx->stream));
-    FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return rc;
+    return host_dp_v(ctx, fbg_dp_gapped, "fbg_gapped_dp", v, n, s_out, prev_out, boundaries_out, count_out);
 }
 
-uint64_t fbg_text_length(const fbg_ctx *ctx) { return ctx && ctx->index_valid ? ctx->N : 0; }
+uint64_t fbg_text_length(const fbg_ctx *ctx) { return ctx && ctx->ix.index_valid ? ctx->N : 0; }
 
 int fbg_index_download(fbg_ctx *ctx, uint8_t *text, uint32_t *sa, uint32_t *isa, uint32_t *lcp_prev,
                        uint32_t *lcp_next)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->index_valid) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_index_download: no index");
-    if (ctx->part_active) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_index_download: the index is partitioned over several GPUs");
+    if (!ctx->ix.index_valid) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_index_download: no index");
+    if (ctx->ix.part_active) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_index_download: the index is partitioned over several GPUs");
     if (ctx->N >= (1ull << 32)) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_index_download: 32-bit arrays");
-    if (ctx->granked && ctx->spanned && (sa || isa || lcp_prev || lcp_next))
+    if (ctx->ix.spanned() && (sa || isa || lcp_prev || lcp_next))
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_index_download: the group-level scan (span_scan.hip) leaves the suffixes with equal keys unordered; "
                                               "set option span_scan = -1 for an index with a suffix array");
     size_t N = ctx->N;
     // test / debugging API: plain blocking copies
     FBG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (text) FBG_HIP_TRY(ctx, hipMemcpy(text, ctx->text.p, N, hipMemcpyDeviceToHost));
-    if (sa && !ctx->ranked && !ctx->granked) FBG_HIP_TRY(ctx, hipMemcpy(sa, ctx->sa_ptr, N * 4, hipMemcpyDeviceToHost));
-    if ((sa || isa || lcp_prev || lcp_next) && (ctx->ranked || ctx->granked)) {
+    if (sa && !ctx->ix.ranked() && !ctx->ix.granked()) FBG_HIP_TRY(ctx, hipMemcpy(sa, ctx->ix.sa_ptr, N * 4, hipMemcpyDeviceToHost));
+    if ((sa || isa || lcp_prev || lcp_next) && (ctx->ix.ranked() || ctx->ix.granked())) {
         // rank-order index: no per-position records exist; derive the arrays from the sorted keys once
-        FBG_TRY(fbg_reserve(ctx, ctx->io_a, N * 4));
-        FBG_TRY(fbg_reserve(ctx, ctx->io_b, N * 4));
-        FBG_TRY(fbg_reserve(ctx, ctx->io_c, N * 4));
-        FBG_TRY(fbg_reserve(ctx, ctx->io_d, N * 4));
-        if (ctx->granked)
+        for (DevBuf *b : {&ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d}) FBG_TRY(fbg_reserve(ctx, *b, N * 4));
+        if (ctx->ix.granked())
             FBG_TRY(fbg_grs_materialize(ctx, ctx->io_d.as<uint32_t>(), ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>()));
         else
             FBG_TRY(fbg_rank_materialize(ctx, ctx->io_d.as<uint32_t>(), ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),

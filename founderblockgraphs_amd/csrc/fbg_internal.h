@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 #include "../../include/fbg_hip.h"
 
 #define FBG_WAVE 64
@@ -13,6 +14,7 @@
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    bool listed = false;     // in its owner's list (fbg_reserve)
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
@@ -41,46 +43,78 @@ struct FbgOptions {
             span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0, msd_ext = 1;
 };
 
+// The index at hand: per-position records, or the sorted slots plus per-column maxima of rank_scan.hip / pure_scan.hip
+// (ranked), gapped_rank.hip (gapped) or span_scan.hip (span)
+enum class IndexKind { none, record, ranked, gapped, span };
+
+// What describes the index a context holds.  fbg_index_reset (ctx.hip) puts a default-constructed value here at the
+// top of every build; the stage that finishes an index sets `kind`, once.
+struct IndexState {
+    bool index_valid = false;
+    IndexKind kind = IndexKind::none;
+    bool ranked() const { return kind == IndexKind::ranked; }
+    bool granked() const { return kind == IndexKind::gapped || kind == IndexKind::span; }
+    bool spanned() const { return kind == IndexKind::span; }
+    uint32_t *sa_ptr = nullptr;     // u32[N] suffix array (lives in the sort's value buffer)
+    uint64_t *rk_keys = nullptr;    // keys (pairs layout, positions in sa_ptr) or key << rk_pb | position (packed)
+    int rk_b = 0, rk_key_bits = 0, rk_K = 0;
+    int rk_layout = 0, rk_pb = 0;   // FBG_SLOTS_*
+    bool grs_flagged = false;       // bit 31 of the sorted values: an irregular position among the K from there on (gapped_rank.hip)
+    bool sp_key_flags_sorted = false;   // span scan: the flags W / I are the two lowest bits of the sorted key words
+    bool msd_ext_valid = false;     // msd_ext holds the 4 symbols after the key of every slot the MSD sort sorted
+    bool lcp_from_keys = false;     // neighbour LCPs came from the sorted keys (few ties) or from text compares
+    bool grs_ties_done = false;     // the tie groups of the kept slots are in text order
+    uint32_t n_exc = 0;             // exception columns of a ranked index (rows in `exc`)
+    // partitioned index (fbg_part_*): this GPU holds the SA slots of key range `part` of `nparts`
+    bool part_active = false;
+    bool gpart = false;             // ... of an MSA with gaps / ignore characters (gapped_rank.hip)
+    int part = 0, nparts = 1;
+    uint64_t part_count = 0;        // owned slots (keys / vals arrays: FBG_PART_HALO + part_count + FBG_PART_HALO)
+    uint64_t part_T = 0;            // candidates found by phase 1
+    uint32_t part_gmin = 0;         // largest threshold any partition scanned with (0: none, nothing to verify)
+};
+
+// What the last build did on its way, as fbg_get_option reports it; reset together with IndexState.
+struct BuildDiag {
+    int64_t msd_decline = -1;    // fbg_msd_sort: -1 not reached, 0 sorted; 1 not tried (geometry), 2 / 4 a stretch of pass 1, 8 the arena of pass 2, 16 a sub-bucket too large
+    int pass1_ahead = 0;         // the MSD sort found its pass 1 done (streamed upload)
+    int64_t ext_pairs = -1, text_pairs = -1;   // the rank-order scan: tied pairs settled by the msd_ext symbols / by the text
+    int rank_lean_launched = 0;  // the rank-order scan launched k_rank_scan_lean ...
+    int rank_lean_used = 0;      // ... and finished with it: the index holds its result
+    int pairs_rb = -1;           // the sample sort of pairs: rank bits of its table, -1 it did not sort
+    int sp_decline = 0;          // why the group-level scan handed the slots back (0: it did not; include/fbg_hip.h "span_decline")
+};
+
+// What the round-0 sort of (key, value) pairs carries besides keys and text positions (built in suffix_sort.hip)
+struct SortExtras {
+    const uint64_t *ebits = nullptr;    // bitmap the pack kernels fold into bit 31 of the values (gapped_rank.hip)
+    const uint32_t *payload = nullptr;  // the value of position p is payload[p] (span_scan.hip: cell | flags)
+    bool key_flags = false;             // span scan, 2^30 cells and more: sp_flagT[p] goes below the key, in its two lowest bits
+};
+
+struct MsdPlan;                         // msd_sort.hip
 struct fbg_ctx {
     int device = 0;
     FbgOptions opt;
+    std::string err;
+    // ---- streams ----
     hipStream_t stream = nullptr;
     bool own_stream = false;
     // second stream for work that only raises column maxima (k_tie_simple) beside the candidate kernels
     hipStream_t aux = nullptr;
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
     bool aux_pending = false;
-    std::string err;
-    uint64_t held_bytes = 0;
     Stager stager;
+    StageTimer timers[FBG_STAGE_COUNT];
 
-    // current MSA (row-major m x n bytes, device)
+    // ---- current MSA (row-major m x n bytes, device) and its text ----
     const uint8_t *d_msa = nullptr;
     DevBuf msa_own;
     uint64_t m = 0, n = 0;
-
-    // a streamed upload (fbg_elastic_f from pinned host memory; text_build.hip): the MSA still on the host while the index build
-    // starts, pass 1 of the MSD sort done ahead on the alphabet the first chunk of rows promised (msd_sort.hip fbg_msd_pre_*)
-    const uint8_t *up_host = nullptr;
-    hipStream_t up_stream = nullptr;
-    hipEvent_t up_ev[9] = {};
-    bool pre_pass1 = false;
-    uint64_t pre_symbols[4] = {0, 0, 0, 0};   // the symbols (bytes of the text) the speculative keys were set up for
-    alignas(16) unsigned char pre_state[768]; // KeyGeom + the sort's arguments between fbg_msd_pre_begin and fbg_msd_sort
-    uint64_t pre_tiles = 0;                    // tiles of pass 1 launched so far
-    int pass1_ahead = 0;                       // the last MSD sort found its pass 1 done (fbg_get_option "pass1_ahead")
-    bool msd_ext_valid = false;                // msd_ext holds the 4 symbols after the key of every slot the last MSD sort sorted
-    int64_t ext_pairs = -1, text_pairs = -1;   // the last rank-order scan: tied pairs settled by those symbols / by the text
-    int rank_lean_launched = 0;                // the last rank-order scan launched k_rank_scan_lean (fbg_get_option "rank_lean_launched")
-    int rank_lean_used = 0;                    // ... and finished with it: the index holds its result (fbg_get_option "rank_lean_used")
-    int pairs_rb = -1;                         // the last sample sort of pairs: rank bits of its table, -1 it did not sort ("pairs_rb")
-    int key_b = -1, key_K = -1, key_packed = -1, key_compact = -1;   // geometry of the last key setup (fbg_get_option "key_*")
-
-    // index state
-    bool index_valid = false;
     int reversed = 0;
     bool gapfree = true;
     bool have_ignore = false;
+    uint8_t ignore_tab[256] = {0};
     uint64_t N = 0;            // text length incl. sentinel
     uint64_t byte_hist[256] = {0}; // symbol histogram of the current text (fbg_build_text; read by fbg_key_setup)
     bool allow_wide = false;       // the caller can work with text positions beyond 32 bits (partitioned index only)
@@ -88,65 +122,60 @@ struct fbg_ctx {
     DevBuf text;               // N + 64 bytes, zero padded
     DevBuf pos, tot;           // u32[m]
     DevBuf segtab;             // u32[3][m][segments]: per 65536-column segment of a row: non-gap cells, prefix, first ignore column
+    DevBuf colT;               // u32[N]: MSA column of each text position (gapped MSAs only)
+    DevBuf gwin_rows;          // u16 per window of 128 positions: the row of its first position (written with the text)
+
+    // ---- a streamed upload (fbg_elastic_f from pinned host memory; text_build.hip): the MSA still on the host while the index
+    // build starts, pass 1 of the MSD sort done ahead on the alphabet the first chunk of rows promised (msd_sort.hip fbg_msd_pre_*)
+    const uint8_t *up_host = nullptr;
+    hipStream_t up_stream = nullptr;
+    hipEvent_t up_ev[9] = {};
+    bool pre_pass1 = false;
+    uint64_t pre_symbols[4] = {0, 0, 0, 0};   // the symbols (bytes of the text) the speculative keys were set up for
+    MsdPlan *pre_plan = nullptr;               // KeyGeom + the sort's arguments between fbg_msd_pre_begin and fbg_msd_sort (owned: fbg_msd_pre_free)
+    uint64_t pre_tiles = 0;                    // tiles of pass 1 launched so far
+
+    // ---- index state and the diagnostics of the last build: reset by fbg_index_reset at the top of a build ----
+    IndexState ix;
+    BuildDiag diag;
+    // ---- what outlives a build ----
+    int key_b = -1, key_K = -1, key_packed = -1, key_compact = -1;   // geometry of the last key setup (fbg_get_option "key_*")
+    int dp_kind = -1;              // which sweep produced the last fbg_dp_minmax result (fbg_get_option "dp_kind")
+    bool grs_skip = false;         // the next build takes the record path: the gapped scan ran out of room (scan.hip)
+    bool cells_built = false;      // prow / igrow hold the current MSA (built on demand: only the record path reads them)
+    uint64_t held_bytes = 0;
+    uint64_t alloc_calls = 0, alloc_us = 0;   // device allocations of the context so far and the host time they took (free + malloc)
+    std::vector<DevBuf *> bufs;    // every buffer reserved for this context (fbg_reserve); fbg_ctx_destroy walks it
+
+    // ---- per-stage tables: record path (suffix_sort.hip, lcp.hip, scan.hip) ----
     DevBuf prow;               // u32[m*n]: text pointer of cell (i,x), row-major (gapped MSAs only)
     DevBuf igrow;              // u32[m*n]: first ignore-char column >= x, row-major (ignore chars only)
     DevBuf rec;                // uint4[N] by text position: {rank, lcp-prev | hint<<31, lcp-next | hint<<31, 0}
-    uint32_t *sa_ptr = nullptr; // u32[N] suffix array (lives in the sort's value buffer)
-    bool lcp_from_keys = false; // neighbour LCPs came from the sorted keys (few ties) or from text compares
-    DevBuf colT;               // u32[N]: MSA column of each text position (gapped MSAs only)
     DevBuf xlist;              // u32[n+1]: columns whose coloured ranks may contain consecutive integers
-    // rank-order scan (rank_scan.hip): valid when `ranked`
-    bool ranked = false;
+    // rank-order scan (rank_scan.hip): kind ranked
     DevBuf gmax, excol, xslot; // u32[n+1]: column maxima of g, exception flags, exception slots
     DevBuf xbits;              // bitmap of the exception columns
     DevBuf exc_scratch;        // per-workgroup column state of k_scan_exceptions_big (MSAs of more than 4096 rows)
     DevBuf exc;                // uint4[n_exc * m]: (rank, lcp_prev, lcp_next) of the rows of the exception columns
-    uint32_t n_exc = 0;
-    // rank-order scan of MSAs with gaps / ignore characters (gapped_rank.hip): valid when `granked`
-    bool granked = false;
+    // rank-order scan of MSAs with gaps / ignore characters (gapped_rank.hip): kind gapped
     int grs_tricks_off = 0;        // the setting of the elastic tricks gmax was computed for
-    bool grs_skip = false;         // rebuilding the record way after the scan ran out of room
     uint32_t grs_ign_lo = 0, grs_ign_hi = 0;
     DevBuf gwin;                   // 16 bytes per 128 text positions: column, row, gap runs
     DevBuf gbits;                  // 1 bit per text position: not the column after its predecessor's
-    DevBuf gwin_rows;              // u16 per window of 128 positions: the row of its first position (written with the text)
-    const uint64_t *grs_ebits = nullptr;   // gbits while the pack kernels are to fold it into bit 31 of the sort's values
-    bool grs_flagged = false;      // the sorted values carry that bit
     bool pairs_similar = false;    // the sample of the (key, position) sort says: rows that resemble each other (ties everywhere)
-    bool grs_ties_done = false;    // the tie groups of the kept slots are in text order
-    bool gpart = false;            // one key-range partition of such an index (fbg_part_*)
-    bool grs_part_failed = false;  // its exact redo of a few columns ran out of room
+    bool grs_part_failed = false;  // a partition's exact redo of a few columns ran out of room
     uint32_t grs_t = 1;            // the threshold of the last scan (1: none), the columns it redid exactly
     uint64_t grs_redone = 0;
-    // group-level scan on column spans for similar rows with gaps / ignore characters (span_scan.hip): `granked` and `spanned`
-    bool spanned = false;
+    // group-level scan on column spans for similar rows with gaps / ignore characters (span_scan.hip): kind span
     DevBuf sp_cells;               // u32[N]: cell | flags of every text position, the payload of the sort
-    DevBuf sp_flagT;               // u8[N]: the flags alone where the cells take all 32 bits (sp_key_flags)
-    bool sp_key_flags = false;     // span scan: the flags W / I are the key words' two lowest bits (2^30 cells and more): the sort ahead
-    uint64_t alloc_calls = 0, alloc_us = 0;   // device allocations of the context so far and the host time they took (free + malloc)
-    int sp_decline = 0;            // why the group-level scan handed the slots back (0: it did not; include/fbg_hip.h "span_decline")
-    bool sp_key_flags_sorted = false;   // ... the sorted slots at hand
+    DevBuf sp_flagT;               // u8[N]: the flags alone where the cells take all 32 bits (SortExtras::key_flags)
     DevBuf sp_cwin;                // 20 bytes per 128 cells of a row: text position of a cell
     DevBuf sp_tiles, sp_gstart, sp_gcol, sp_gflags, sp_rstart, sp_rid, sp_gplo, sp_gphi, sp_gval, sp_odd, sp_irr, sp_chain, sp_slow, sp_mins;
     uint32_t sp_chain_n = 0, sp_slow_n = 0;
     uint64_t sp_G = 0, sp_R = 0, sp_n_irr = 0, sp_work = 0;
     uint32_t sp_n_odd[4] = {0, 0, 0, 0}, sp_odd_cap = 0;
-    const uint32_t *sort_payload = nullptr;   // while set: the pack kernels of the (key, value) sorts write payload[p] instead of p | flag
-    int64_t msd_decline = -1;    // the last fbg_msd_sort: 0 sorted; 1 not tried (geometry), 2 / 4 a stretch of pass 1, 8 the arena of pass 2, 16 a sub-bucket too large
-    int dp_kind = -1;            // which sweep produced the last fbg_dp_minmax result (fbg_get_option "dp_kind")
-    bool cells_built = false;      // prow / igrow hold the current MSA (built on demand: only the record path reads them)
-    uint8_t ignore_tab[256] = {0};
-    uint64_t *rk_keys = nullptr; // sorted slots: keys (pairs layout, positions in sa_ptr) or key << rk_pb | position (packed)
-    int rk_b = 0, rk_key_bits = 0, rk_K = 0;
-    int rk_layout = 0, rk_pb = 0;   // FBG_SLOTS_*
-    // partitioned index (partition.hip): this GPU holds the SA slots of key range `part` of `nparts`
-    bool part_active = false;
-    int part = 0, nparts = 1;
-    uint64_t part_count = 0;   // owned slots (keys / vals arrays: FBG_PART_HALO + part_count + FBG_PART_HALO)
-    uint64_t part_T = 0;       // candidates found by phase 1
-    uint32_t part_gmin = 0;    // largest threshold any partition scanned with (0: none, nothing to verify)
 
-    // scratch
+    // ---- scratch ----
     DevBuf keysA, keysB, valsA, valsB, grp, flags, list, tie_list, big_groups, tmp, small, scalars;
     DevBuf msd_ext;            // 1 byte per SA slot: symbols K .. K+3 of its suffix (msd_sort.hip, 2-bit symbols)
     DevBuf kargs;              // arguments a kernel reads from memory (k_rank_scan_lean) ...
@@ -155,8 +184,6 @@ struct fbg_ctx {
     DevBuf dp_a, dp_b, dp_c, dp_d, dp_e, dp_f, dp_g, dp_h, io_a, io_b, io_c, io_d;
     DevBuf bt_up, bt_dep;      // binary-lifting tables of the parallel backtrack
     DevBuf ps_a, ps_b, ps_c, ps_d, ps_e, ps_f, ps_g, ps_h;   // group / run tables of the scan for similar rows (pure_scan.hip)
-
-    StageTimer timers[FBG_STAGE_COUNT];
 };
 
 // ---- error plumbing ----------------------------------------------------------------------
@@ -175,12 +202,19 @@ int fbg_fail(fbg_ctx *ctx, int code, const char *fmt, ...);
         if (rc_ != FBG_OK) return rc_; \
     } while (0)
 
-int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes);   // grow-only device allocation
+// Grow-only device allocation.  The buffer joins its owner's list on its first successful reserve; the owner frees
+// the list (fbg_release_all).  owner = nullptr: no list, the caller releases the buffer by name (group.hip).  accounted:
+// in fbg_device_bytes and alloc_calls / alloc_us, with the poison fill -- the context's buffers and a group member's,
+// not those of a pattern index or of its build's scratch.
+int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes, std::vector<DevBuf *> *owner, bool accounted);
+inline int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes) { return fbg_reserve(ctx, b, bytes, &ctx->bufs, true); }
+void fbg_release(fbg_ctx *ctx, DevBuf &b);                         // ctx = nullptr: a buffer outside the context's accounting
+void fbg_release_all(fbg_ctx *ctx, std::vector<DevBuf *> &bufs);   // ... every buffer of a list
+void fbg_index_reset(fbg_ctx *ctx);                                // ctx.hip: the top of a build, nowhere else
 // blocking host <-> device copies; pageable memory of 32 MB and more goes through pinned bounce buffers filled by
 // several host threads (the runtime's own staging of pageable memory is a single-threaded memcpy)
 int fbg_upload(fbg_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int fbg_download(fbg_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
-void fbg_release(fbg_ctx *ctx, DevBuf &b);
 int fbg_stage_begin(fbg_ctx *ctx, int stage);
 int fbg_stage_end(fbg_ctx *ctx, int stage, int launches);
 
@@ -198,6 +232,13 @@ struct KeyGeom {
     const uint8_t *d_code = nullptr;
 };
 
+// the sorted slots a rank-order index keeps (layout: FBG_SLOTS_*; pb = 0 in the pairs layout)
+inline void fbg_remember_slots(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, int layout, const KeyGeom &g)
+{
+    ctx->ix.rk_keys = keys; ctx->ix.sa_ptr = vals; ctx->ix.rk_layout = layout; ctx->ix.rk_pb = g.pb;
+    ctx->ix.rk_b = g.b; ctx->ix.rk_key_bits = g.key_bits; ctx->ix.rk_K = g.K;
+}
+
 // the geometry fbg_get_option reports as key_b / key_K / key_packed / key_compact
 inline void fbg_note_key_geom(fbg_ctx *ctx, const KeyGeom &g)
 {
@@ -213,7 +254,7 @@ int fbg_pure_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
 int fbg_rank_finish(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disable_tricks, uint64_t *d_out);
 int fbg_rank_materialize(fbg_ctx *ctx, uint32_t *d_sa, uint32_t *d_isa, uint32_t *d_pl, uint32_t *d_pr);
 #define FBG_STAGE_RANKSCAN FBG_STAGE_TILE
-int fbg_grs_prepare(fbg_ctx *ctx, int *launches);
+int fbg_grs_prepare(fbg_ctx *ctx, const uint64_t **ebits, int *launches);   // *ebits = nullptr: no flag bit in the values
 int fbg_grs_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t count, const KeyGeom &g, int eligible, uint8_t *d_blob, int *ok);
 int fbg_grs_part_scan(fbg_ctx *ctx, const uint8_t *d_blobs, uint32_t *d_gmax, int *ok);
 int fbg_grs_part_unfilled(fbg_ctx *ctx, uint64_t *unfilled);
@@ -224,7 +265,7 @@ int fbg_grs_finish(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int disable_tricks, u
 int fbg_grs_materialize(fbg_ctx *ctx, uint32_t *d_sa, uint32_t *d_isa, uint32_t *d_pl, uint32_t *d_pr);
 bool fbg_span_eligible(fbg_ctx *ctx, const KeyGeom &g);
 bool fbg_span_key_flags(fbg_ctx *ctx, KeyGeom &g);                                                 // span_scan.hip
-int fbg_span_prepare(fbg_ctx *ctx, const KeyGeom &g, int *launches);
+int fbg_span_prepare(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, int *launches);
 int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g, int *done);
 int fbg_span_rescan(fbg_ctx *ctx, int disable_tricks, int *ok);
 int fbg_build_cell_tables(fbg_ctx *ctx);                                                                // text_build.hip
@@ -239,9 +280,10 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
 int fbg_msd_pre_begin(fbg_ctx *ctx, int *ok);                     // pass 1 ahead of the rest, on a text that is still arriving
 int fbg_msd_pre_pass1(fbg_ctx *ctx, uint64_t avail);              // ... over the tiles whose positions (and 64 beyond) are below avail
 bool fbg_msd_pre_geom(fbg_ctx *ctx, KeyGeom *g);                  // the key geometry it used, if pass 1 was done ahead
+void fbg_msd_pre_free(fbg_ctx *ctx);                              // the plan kept between those calls (fbg_ctx_destroy)
 int fbg_msd_sort_part(fbg_ctx *ctx, const KeyGeom &g, uint64_t lo, uint64_t hi, int nohi, int nparts, uint64_t out_offset,
-                      uint64_t *count, int *ok, int *launches);                                       // msd_sort_pairs.hip                        // suffix_sort.hip
-int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, int *ok, int *launches);                      // msd_sort_pairs.hip
+                      uint64_t *count, int *ok, int *launches);                                       // msd_sort_pairs.hip
+int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, int *ok, int *launches);                      // msd_sort_pairs.hip
 int fbg_scan_columns(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disable_tricks,
                      uint64_t *d_out);                                        // scan.hip
 int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_boundaries,

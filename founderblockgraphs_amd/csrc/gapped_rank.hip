@@ -904,22 +904,22 @@ __global__ void k_grs_strip(uint32_t *__restrict__ vals, uint64_t N)
 
 static void grs_args(fbg_ctx *ctx, GrsArgs &a, int disable_tricks)
 {
-    a.keys = ctx->rk_keys; a.vals = ctx->sa_ptr; a.T = ctx->text.as<uint8_t>();
-    a.vmask = ctx->grs_flagged ? 0x7fffffffu : 0xffffffffu;
+    a.keys = ctx->ix.rk_keys; a.vals = ctx->ix.sa_ptr; a.T = ctx->text.as<uint8_t>();
+    a.vmask = ctx->ix.grs_flagged ? 0x7fffffffu : 0xffffffffu;
     a.win = ctx->gapfree ? nullptr : ctx->gwin.as<GWin>();
     a.colT = ctx->gapfree ? nullptr : ctx->colT.as<uint32_t>();
     a.pos = ctx->pos.as<uint32_t>(); a.tot = ctx->tot.as<uint32_t>();
     a.is_ignore = ctx->have_ignore ? ctx->small.as<uint8_t>() : nullptr;
     a.N = ctx->N; a.n = ctx->n; a.m = ctx->m;
-    if (ctx->part_active) {
-        a.own_lo = FBG_PART_HALO; a.own_hi = FBG_PART_HALO + ctx->part_count;
-        a.open_lo = ctx->part > 0; a.open_hi = ctx->part + 1 < ctx->nparts;
+    if (ctx->ix.part_active) {
+        a.own_lo = FBG_PART_HALO; a.own_hi = FBG_PART_HALO + ctx->ix.part_count;
+        a.open_lo = ctx->ix.part > 0; a.open_hi = ctx->ix.part + 1 < ctx->ix.nparts;
         a.lim_lo = a.open_lo ? 0 : a.own_lo; a.lim_hi = a.open_hi ? a.own_hi + FBG_PART_HALO : a.own_hi;
     } else {
         a.own_lo = a.lim_lo = 0; a.own_hi = a.lim_hi = ctx->N;
         a.open_lo = a.open_hi = 0;
     }
-    a.b = ctx->rk_b; a.K = ctx->rk_K; a.key_bits = ctx->rk_key_bits; a.disable_tricks = disable_tricks;
+    a.b = ctx->ix.rk_b; a.K = ctx->ix.rk_K; a.key_bits = ctx->ix.rk_key_bits; a.disable_tricks = disable_tricks;
     a.ign_lo = ctx->grs_ign_lo; a.ign_hi = ctx->grs_ign_hi;
     a.t = 1;
     a.fmax = ctx->gmax.as<uint32_t>();
@@ -928,11 +928,11 @@ static void grs_args(fbg_ctx *ctx, GrsArgs &a, int disable_tricks)
 }
 
 // Before the sort: the window table and the bitmap of irregular positions the pack kernels turn into the flag bit of
-// the sort's payload (ctx->grs_ebits; nullptr: no flags -- texts of 2^31 symbols and more have no spare bit).
-int fbg_grs_prepare(fbg_ctx *ctx, int *launches)
+// the sort's payload (*ebits; nullptr: no flags -- texts of 2^31 symbols and more have no spare bit).
+int fbg_grs_prepare(fbg_ctx *ctx, const uint64_t **ebits, int *launches)
 {
-    ctx->grs_ebits = nullptr;
-    ctx->grs_flagged = false;
+    *ebits = nullptr;
+    ctx->ix.grs_flagged = false;
     const uint64_t N = ctx->N, n = ctx->n, m = ctx->m;
     if (N >= (1ull << 32) || m >= GW_IRREGULAR) return FBG_OK;
     hipStream_t st = ctx->stream;
@@ -946,16 +946,16 @@ int fbg_grs_prepare(fbg_ctx *ctx, int *launches)
         hipLaunchKernelGGL(k_grs_ebits_gapfree, dim3(fbg_blocks(nwin * 2, 256)), dim3(256), 0, st, N, n, nwin * 2, ctx->gbits.as<unsigned long long>());
     }
     *launches += 1;
-    if (N < (1ull << 31) && ctx->opt.gapped_rank != 2) { ctx->grs_ebits = ctx->gbits.as<uint64_t>(); ctx->grs_flagged = true; }
+    if (N < (1ull << 31) && ctx->opt.gapped_rank != 2) { *ebits = ctx->gbits.as<uint64_t>(); ctx->ix.grs_flagged = true; }
     return FBG_OK;
 }
 
 // positions without the flag bit (the record path reads the values as the suffix array)
 int fbg_grs_strip(fbg_ctx *ctx, uint32_t *vals)
 {
-    if (!ctx->grs_flagged) return FBG_OK;
+    if (!ctx->ix.grs_flagged) return FBG_OK;
     hipLaunchKernelGGL(k_grs_strip, dim3(fbg_blocks(ctx->N, 256)), dim3(256), 0, ctx->stream, vals, ctx->N);
-    ctx->grs_flagged = false;
+    ctx->ix.grs_flagged = false;
     return FBG_OK;
 }
 
@@ -1045,7 +1045,7 @@ static int grs_pick_threshold(fbg_ctx *ctx, GrsArgs &a, uint32_t *t, int *launch
     *t = 1;
     hipStream_t st = ctx->stream;
     const uint64_t own = a.own_hi - a.own_lo, N = ctx->N, n = ctx->n;
-    if (!ctx->grs_flagged || ctx->opt.gapped_rank == 3 || !(own > 4 * (uint64_t)GR_SAMPLE || ctx->opt.gapped_rank == 4) || own < 4) return FBG_OK;
+    if (!ctx->ix.grs_flagged || ctx->opt.gapped_rank == 3 || !(own > 4 * (uint64_t)GR_SAMPLE || ctx->opt.gapped_rank == 4) || own < 4) return FBG_OK;
     unsigned long long *hist = a.counters + 8;
     FBG_HIP_TRY(ctx, hipMemsetAsync(hist, 0, 66 * sizeof(unsigned long long), st));
     const uint64_t stride = std::max<uint64_t>(1, own / GR_SAMPLE);
@@ -1170,9 +1170,9 @@ static int grs_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
     FBG_TRY(grs_pick_threshold(ctx, a, &a.t, launches));
     ctx->grs_t = a.t;
     ctx->grs_redone = 0;
-    FBG_TRY(grs_main_pass(ctx, a, !ctx->grs_ties_done, ok, launches));
+    FBG_TRY(grs_main_pass(ctx, a, !ctx->ix.grs_ties_done, ok, launches));
     if (!*ok) return FBG_OK;
-    ctx->grs_ties_done = true;
+    ctx->ix.grs_ties_done = true;
     uint64_t nc = 0;
     FBG_TRY(grs_unfilled(ctx, a, a.t, &nc));
     ctx->grs_redone = nc;
@@ -1202,18 +1202,16 @@ static bool grs_ignore_mask(fbg_ctx *ctx, uint64_t *by_code)
 
 static void grs_remember(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g, uint64_t by_code)
 {
-    ctx->rk_keys = keys; ctx->sa_ptr = vals;
-    ctx->rk_layout = FBG_SLOTS_PAIRS; ctx->rk_pb = 0; ctx->rk_b = g.b; ctx->rk_key_bits = g.key_bits; ctx->rk_K = g.K;
+    fbg_remember_slots(ctx, keys, vals, FBG_SLOTS_PAIRS, g);
     ctx->grs_ign_lo = (uint32_t)by_code; ctx->grs_ign_hi = (uint32_t)(by_code >> 32);
 }
 
 // Called by fbg_suffix_sort after the round-0 sort of the (key, position) pairs of an MSA with gaps / ignore characters
 // (fbg_grs_prepare ran before it).  *done = 1: the index is the sorted slots plus the per-column maxima
-// (ctx->granked); 0: continue with the record path.
+// (kind gapped); 0: continue with the record path.
 int fbg_grs_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g, int *done)
 {
     *done = 0;
-    ctx->granked = false;
     const uint64_t N = ctx->N, n = ctx->n, m = ctx->m;
     if (N >= (1ull << 32) || m >= GW_IRREGULAR || g.compact || g.packed || g.wide || ctx->reversed) return FBG_OK;
     hipStream_t st = ctx->stream;
@@ -1226,13 +1224,11 @@ int fbg_grs_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g, 
     GrsArgs a;
     grs_args(ctx, a, 0);
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.counters, 0, 6 * sizeof(unsigned long long), st));
-    ctx->grs_ties_done = false;                    // (the tie groups are put in text order by the first scan)
+    ctx->ix.grs_ties_done = false;                    // (the tie groups are put in text order by the first scan)
     int ok = 0;
     FBG_TRY(grs_scan(ctx, 0, &ok, &launches));
     if (ok) {
-        ctx->granked = true;
-        ctx->ranked = false;
-        ctx->part_active = false;
+        ctx->ix.kind = IndexKind::gapped;
         *done = 1;
     }
     return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
@@ -1279,8 +1275,8 @@ int fbg_grs_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_RANKSCAN));
     int launches = 0;
-    ctx->granked = false; ctx->ranked = false; ctx->gpart = true;
-    ctx->part_count = count;
+    ctx->ix.gpart = true;
+    ctx->ix.part_count = count;
     uint64_t by_code = 0;
     int good = eligible && count >= 2 * FBG_PART_HALO && ctx->N < (1ull << 32) && ctx->m < GW_IRREGULAR && grs_ignore_mask(ctx, &by_code);
     FBG_TRY(fbg_reserve(ctx, ctx->gmax, (ctx->n + 1) * 4));
@@ -1314,12 +1310,12 @@ int fbg_grs_part_scan(fbg_ctx *ctx, const uint8_t *d_blobs, uint32_t *d_gmax, in
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_RANKSCAN));
     int launches = 0;
-    std::vector<uint8_t> hb((size_t)ctx->nparts * FBG_PART_HALO_BYTES);
+    std::vector<uint8_t> hb((size_t)ctx->ix.nparts * FBG_PART_HALO_BYTES);
     FBG_HIP_TRY(ctx, hipMemcpyAsync(hb.data(), d_blobs, hb.size(), hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     int good = 1;
     uint32_t t_all = 1;
-    for (int p = 0; p < ctx->nparts; p++) {
+    for (int p = 0; p < ctx->ix.nparts; p++) {
         uint64_t tail[2];
         memcpy(tail, hb.data() + (size_t)p * FBG_PART_HALO_BYTES + 2 * FBG_PART_HALO * 12, sizeof(tail));
         if (!(tail[0] & 1)) good = 0;
@@ -1329,14 +1325,14 @@ int fbg_grs_part_scan(fbg_ctx *ctx, const uint8_t *d_blobs, uint32_t *d_gmax, in
     if (good) {
         GrsArgs a;
         grs_args(ctx, a, ctx->opt.part_tricks_off ? 1 : 0);
-        hipLaunchKernelGGL(k_grs_halo_import, dim3(1), dim3(FBG_PART_HALO), 0, st, d_blobs, ctx->part, ctx->nparts, a.own_hi, ctx->rk_keys, a.vals);
+        hipLaunchKernelGGL(k_grs_halo_import, dim3(1), dim3(FBG_PART_HALO), 0, st, d_blobs, ctx->ix.part, ctx->ix.nparts, a.own_hi, ctx->ix.rk_keys, a.vals);
         launches++;
         FBG_TRY(grs_buffers(ctx, a));
         a.t = ctx->grs_t;
         FBG_TRY(grs_main_pass(ctx, a, false, &good, &launches));
         ctx->grs_tricks_off = a.disable_tricks;
     }
-    ctx->part_gmin = t_all;         // the unfilled test of fbg_part_finish goes by the largest threshold any partition used
+    ctx->ix.part_gmin = t_all;         // the unfilled test of fbg_part_finish goes by the largest threshold any partition used
     FBG_HIP_TRY(ctx, hipMemcpyAsync(d_gmax, ctx->gmax.p, (n + 1) * 4, hipMemcpyDeviceToDevice, st));
     const uint32_t verdict = good ? 0u : 1u;
     FBG_HIP_TRY(ctx, hipMemcpyAsync(d_gmax + n, &verdict, 4, hipMemcpyHostToDevice, st));
@@ -1350,7 +1346,7 @@ int fbg_grs_part_unfilled(fbg_ctx *ctx, uint64_t *unfilled)
 {
     GrsArgs a;
     grs_args(ctx, a, ctx->grs_tricks_off);
-    FBG_TRY(grs_unfilled(ctx, a, ctx->part_gmin, unfilled));
+    FBG_TRY(grs_unfilled(ctx, a, ctx->ix.part_gmin, unfilled));
     ctx->grs_redone = *unfilled;
     return FBG_OK;
 }
@@ -1365,7 +1361,7 @@ int fbg_grs_part_rescan(fbg_ctx *ctx)
     FBG_TRY(grs_buffers(ctx, a));
     a.t = ctx->grs_t;
     FBG_TRY(grs_redo(ctx, a, ctx->grs_redone, &ok, &launches));
-    ctx->part_gmin = 0;
+    ctx->ix.part_gmin = 0;
     ctx->grs_part_failed = !ok;
     return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
 }
@@ -1376,11 +1372,11 @@ int fbg_grs_finish(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int disable_tricks, u
 {
     *ok = 1;
     if ((disable_tricks != 0) != (ctx->grs_tricks_off != 0)) {
-        if (ctx->gpart)
+        if (ctx->ix.gpart)
             return fbg_fail(ctx, FBG_ERR_INVALID, "the partitioned index of this MSA (gaps / ignore characters) was scanned %s the elastic tricks; "
                             "set option part_tricks_off before fbg_part_index_build for the other setting", ctx->grs_tricks_off ? "without" : "with");
         int launches = 0;
-        if (ctx->spanned) FBG_TRY(fbg_span_rescan(ctx, disable_tricks ? 1 : 0, ok));    // (similar rows: the group-level scan, span_scan.hip)
+        if (ctx->ix.spanned()) FBG_TRY(fbg_span_rescan(ctx, disable_tricks ? 1 : 0, ok));    // (similar rows: the group-level scan, span_scan.hip)
         else FBG_TRY(grs_scan(ctx, disable_tricks ? 1 : 0, ok, &launches));
         if (!*ok) return FBG_OK;
     }

@@ -151,7 +151,7 @@ int parallel(fbg_group *g, const std::function<int(int)> &fn)
 int mem_reserve(fbg_group *g, Member &mb, DevBuf &b, size_t bytes)
 {
     GRP_HIP_TRY(g, hipSetDevice(mb.dev));
-    const int rc = fbg_reserve(mb.ctx, b, bytes);
+    const int rc = fbg_reserve(mb.ctx, b, bytes, nullptr, true);     // (released by name: fbg_group_destroy)
     if (rc != FBG_OK) set_err(g, fbg_last_error(mb.ctx));
     return rc;
 }

@@ -79,13 +79,13 @@ int fbg_neighbour_lcp(fbg_ctx *ctx)
     const uint64_t N = ctx->N;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_LCP));
     int launches = 0;
-    if (!ctx->lcp_from_keys && !ctx->ranked && !ctx->granked) {
+    if (!ctx->ix.lcp_from_keys && !ctx->ix.ranked() && !ctx->ix.granked()) {
         HintArgs ha;
         ha.colT = ctx->gapfree ? nullptr : ctx->colT.as<uint32_t>();
         ha.n = ctx->n; ha.N = N; ha.row_len = (uint32_t)(ctx->n + 1);
         const uint64_t threads = (N + LCP_CHUNK - 1) / LCP_CHUNK;
         hipLaunchKernelGGL(k_neighbour_lcp, dim3(fbg_blocks(threads, LCP_THREADS)), dim3(LCP_THREADS), 0, ctx->stream,
-                           ctx->text.as<uint8_t>(), N, ctx->sa_ptr, ctx->rec.as<uint4>(), ha);
+                           ctx->text.as<uint8_t>(), N, ctx->ix.sa_ptr, ctx->rec.as<uint4>(), ha);
         FBG_HIP_TRY(ctx, hipGetLastError());
         launches = 1;
     }

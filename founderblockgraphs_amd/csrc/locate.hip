@@ -69,42 +69,17 @@ struct fbg_pindex {
     uint64_t occ_n = 0, occ_etotal = 0, occ_stotal = 0;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
     double build_ms = 0, search_ms = 0, validate_ms = 0;
     uint64_t occ_lines = 0, v_slots = 0, v_wave_nodes = 0;
 };
-
-// ---- device buffers owned by the index (the context's workspaces stay untouched) ------------------------------
-static int px_reserve(fbg_pindex *ix, DevBuf &b, size_t bytes)
-{
-    if (bytes == 0) bytes = 256;
-    if (b.cap >= bytes) return FBG_OK;
-    if (b.p) {
-        FBG_HIP_TRY(ix->ctx, hipStreamSynchronize(ix->ctx->stream));
-        FBG_HIP_TRY(ix->ctx, hipFree(b.p));
-        b.p = nullptr; b.cap = 0;
-    }
-    const size_t want = (bytes + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return fbg_fail(ix->ctx, FBG_ERR_OOM, "pattern index: hipMalloc(%llu): %s", (unsigned long long)want, hipGetErrorString(e));
-    }
-    b.cap = want;
-    return FBG_OK;
-}
-
-static void px_free(DevBuf &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
-}
 
 template <class F> static int px_with_tmp(fbg_pindex *ix, F &&call)
 {
     size_t bytes = 0;
     hipError_t e = call(nullptr, bytes);
     if (e != hipSuccess) return fbg_fail(ix->ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
-    FBG_TRY(px_reserve(ix, ix->tmp, bytes));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->tmp, bytes, &ix->bufs, false));
     size_t have = ix->tmp.cap;
     e = call(ix->tmp.p, have);
     if (e != hipSuccess)
@@ -444,12 +419,8 @@ static PxDev px_dev(const fbg_pindex *ix)
 struct PxScratch {
     DevBuf labels, loff, elen, eoff, keysA, keysB, valsA, valsB, cidx, cidx2, rank, headv, hscan, head, keep,
            cntT, cntX, code_u8, count;
-    ~PxScratch()
-    {
-        for (DevBuf *b : {&labels, &loff, &elen, &eoff, &keysA, &keysB, &valsA, &valsB, &cidx, &cidx2, &rank,
-                          &headv, &hscan, &head, &keep, &cntT, &cntX, &code_u8, &count})
-            px_free(*b);
-    }
+    std::vector<DevBuf *> bufs;
+    ~PxScratch() { fbg_release_all(nullptr, bufs); }
 };
 
 struct PxMul {
@@ -536,39 +507,39 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     ix->nblk = N1 / PX_BLK + 1;
 
     PxScratch s;
-    auto U = [&](DevBuf &b, const void *h, size_t bytes) -> int {
-        FBG_TRY(px_reserve(ix, b, bytes + 8));
+    auto U = [&](std::vector<DevBuf *> &owner, DevBuf &b, const void *h, size_t bytes) -> int {
+        FBG_TRY(fbg_reserve(ctx, b, bytes + 8, &owner, false));
         if (bytes) FBG_HIP_TRY(ctx, hipMemcpyAsync(b.p, h, bytes, hipMemcpyHostToDevice, st));
         return FBG_OK;
     };
     // labels (padded to whole 8-byte words for the walk's reads) and offsets rebased to 0
-    FBG_TRY(px_reserve(ix, s.labels, ((L + 7) & ~7ull) + 16));
+    FBG_TRY(fbg_reserve(ix->ctx, s.labels, ((L + 7) & ~7ull) + 16, &s.bufs, false));
     FBG_HIP_TRY(ctx, hipMemsetAsync(s.labels.p, 0, s.labels.cap, st));
     if (L) FBG_HIP_TRY(ctx, hipMemcpyAsync(s.labels.p, labels + lbase, L, hipMemcpyHostToDevice, st));
-    FBG_TRY(U(s.loff, label_off, (n_nodes + 1) * 8));
+    FBG_TRY(U(s.bufs, s.loff, label_off, (n_nodes + 1) * 8));
     if (lbase) hipLaunchKernelGGL(k_px_rebase, dim3(fbg_blocks(n_nodes + 1, 256)), dim3(256), 0, st, s.loff.as<uint64_t>(), n_nodes, lbase);
-    FBG_TRY(U(ix->vesrc, esrc.data(), E * 4));
-    FBG_TRY(U(ix->vedst, edst.data(), E * 4));
-    FBG_TRY(U(ix->vestart, estart.data(), (E + 1) * 4));
-    FBG_TRY(U(ix->vtpos, vtpos.data(), n_nodes * 4));
-    FBG_TRY(U(ix->vlen, vlen.data(), n_nodes * 4));
-    FBG_TRY(U(ix->vflag, vflag.data(), n_nodes));
-    FBG_TRY(px_reserve(ix, ix->vrng, n_nodes * 8));
+    FBG_TRY(U(ix->bufs, ix->vesrc, esrc.data(), E * 4));
+    FBG_TRY(U(ix->bufs, ix->vedst, edst.data(), E * 4));
+    FBG_TRY(U(ix->bufs, ix->vestart, estart.data(), (E + 1) * 4));
+    FBG_TRY(U(ix->bufs, ix->vtpos, vtpos.data(), n_nodes * 4));
+    FBG_TRY(U(ix->bufs, ix->vlen, vlen.data(), n_nodes * 4));
+    FBG_TRY(U(ix->bufs, ix->vflag, vflag.data(), n_nodes));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vrng, n_nodes * 8, &ix->bufs, false));
     ix->n_edges = E;
     ix->nctab = ((N1 - 1) >> PV_CSHIFT) + 2;
-    FBG_TRY(px_reserve(ix, ix->vctab, ix->nctab * 4));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vctab, ix->nctab * 4, &ix->bufs, false));
     if (E) hipLaunchKernelGGL(k_pv_ctab, dim3(fbg_blocks(ix->nctab, 256)), dim3(256), 0, st, ix->vestart.as<uint32_t>(), (uint32_t)E,
                               ix->nctab, ix->vctab.as<uint32_t>());
-    FBG_TRY(U(s.code_u8, code_u8, 256));
-    FBG_TRY(U(ix->code, code, sizeof(code)));
-    FBG_TRY(U(ix->C, C, sizeof(C)));
+    FBG_TRY(U(s.bufs, s.code_u8, code_u8, 256));
+    FBG_TRY(U(ix->bufs, ix->code, code, sizeof(code)));
+    FBG_TRY(U(ix->bufs, ix->C, C, sizeof(C)));
 
     // text
-    FBG_TRY(px_reserve(ix, ix->text, N1 + 64));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->text, N1 + 64, &ix->bufs, false));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ix->text.p, 0, ix->text.cap, st));
     if (E) {
-        FBG_TRY(px_reserve(ix, s.elen, E * 8));
-        FBG_TRY(px_reserve(ix, s.eoff, E * 8));
+        FBG_TRY(fbg_reserve(ix->ctx, s.elen, E * 8, &s.bufs, false));
+        FBG_TRY(fbg_reserve(ix->ctx, s.eoff, E * 8, &s.bufs, false));
         hipLaunchKernelGGL(k_px_edge_len, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, ix->vesrc.as<uint32_t>(), ix->vedst.as<uint32_t>(),
                            s.loff.as<uint64_t>(), E, s.elen.as<uint64_t>());
         uint64_t *elen = s.elen.as<uint64_t>(), *eoff = s.eoff.as<uint64_t>();
@@ -585,11 +556,11 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     const int K = 64 / b;
     int pb = 1;
     while ((1ull << pb) < N1) pb++;
-    FBG_TRY(px_reserve(ix, ix->sa, N1 * 4));
-    for (DevBuf *d : {&s.keysA, &s.keysB}) FBG_TRY(px_reserve(ix, *d, N1 * 8));
-    for (DevBuf *d : {&s.valsA, &s.valsB, &s.cidx, &s.cidx2, &s.rank, &s.headv, &s.hscan}) FBG_TRY(px_reserve(ix, *d, N1 * 4));
-    for (DevBuf *d : {&s.head, &s.keep}) FBG_TRY(px_reserve(ix, *d, N1));
-    FBG_TRY(px_reserve(ix, s.count, 8));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->sa, N1 * 4, &ix->bufs, false));
+    for (DevBuf *d : {&s.keysA, &s.keysB}) FBG_TRY(fbg_reserve(ix->ctx, *d, N1 * 8, &s.bufs, false));
+    for (DevBuf *d : {&s.valsA, &s.valsB, &s.cidx, &s.cidx2, &s.rank, &s.headv, &s.hscan}) FBG_TRY(fbg_reserve(ix->ctx, *d, N1 * 4, &s.bufs, false));
+    for (DevBuf *d : {&s.head, &s.keep}) FBG_TRY(fbg_reserve(ix->ctx, *d, N1, &s.bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, s.count, 8, &s.bufs, false));
     uint64_t *kA = s.keysA.as<uint64_t>(), *kB = s.keysB.as<uint64_t>();
     uint32_t *vA = s.valsA.as<uint32_t>(), *vB = s.valsB.as<uint32_t>();
     uint32_t *sa = ix->sa.as<uint32_t>(), *rank = s.rank.as<uint32_t>(), *headv = s.headv.as<uint32_t>(), *hscan = s.hscan.as<uint32_t>();
@@ -628,10 +599,10 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     // BWT and occ lines
     const int S = sigma;
     const uint64_t nblk = ix->nblk;
-    FBG_TRY(px_reserve(ix, ix->lines, nblk * PX_LINE));
-    FBG_TRY(px_reserve(ix, s.cntT, nblk * S * 4));
-    FBG_TRY(px_reserve(ix, s.cntX, nblk * S * 4));
-    if (!ix->compact) FBG_TRY(px_reserve(ix, ix->cnt_tab, nblk * S * 4));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->lines, nblk * PX_LINE, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, s.cntT, nblk * S * 4, &s.bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, s.cntX, nblk * S * 4, &s.bufs, false));
+    if (!ix->compact) FBG_TRY(fbg_reserve(ix->ctx, ix->cnt_tab, nblk * S * 4, &ix->bufs, false));
     const dim3 gl(fbg_blocks(nblk * FBG_WAVE, PX_THREADS));
     if (ix->compact)
         hipLaunchKernelGGL(k_px_lines<true>, gl, dim3(PX_THREADS), 0, st, sa, ix->text.as<uint8_t>(), s.code_u8.as<uint8_t>(), N1, nblk, S,
@@ -674,8 +645,8 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
                                (unsigned long long *)nullptr, (unsigned long long *)nullptr, bflag, eflag, (unsigned long long *)nullptr,
                                ix->vrng.as<uint2>());
     }
-    FBG_TRY(px_reserve(ix, ix->bpos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4));
-    FBG_TRY(px_reserve(ix, ix->epos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->bpos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->epos, N1 * 4 < n_nodes * 4 ? N1 * 4 : n_nodes * 4, &ix->bufs, false));
     uint64_t nbe[2] = {0, 0};
     for (int k = 0; k < 2; k++) {
         uint8_t *fl = k ? eflag : bflag;
@@ -692,7 +663,7 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     ix->ne = (uint32_t)nbe[1];
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     FBG_HIP_TRY(ctx, hipGetLastError());
-    px_free(ix->tmp);
+    fbg_release(nullptr, ix->tmp);
     return FBG_OK;
 }
 
@@ -703,12 +674,7 @@ static void px_destroy(fbg_pindex *ix)
         (void)hipSetDevice(ix->ctx->device);
         (void)hipStreamSynchronize(ix->ctx->stream);
     }
-    for (DevBuf *b : {&ix->text, &ix->sa, &ix->lines, &ix->cnt_tab, &ix->C, &ix->code, &ix->bpos, &ix->epos, &ix->pats, &ix->poff,
-                      &ix->okey, &ix->oval, &ix->okey2, &ix->oval2, &ix->cnt_out, &ix->pos_out, &ix->lines_ctr, &ix->tmp,
-                      &ix->vrng, &ix->vtpos, &ix->vlen, &ix->vflag, &ix->vestart, &ix->vesrc, &ix->vedst, &ix->vctab,
-                      &ix->vblock, &ix->vstatus, &ix->vwn, &ix->vwo, &ix->vlist, &ix->vctr, &ix->orec, &ix->oetot, &ix->ostot,
-                      &ix->oesz, &ix->ossz, &ix->oeoff, &ix->osoff, &ix->ors, &ix->oel, &ix->oss, &ix->osk, &ix->oplace})
-        px_free(*b);
+    fbg_release_all(nullptr, ix->bufs);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
     delete ix;
@@ -933,17 +899,17 @@ static int px_search(fbg_pindex *ix, const char *who, const uint8_t *patterns, c
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint64_t n = n_patterns;
-    FBG_TRY(px_reserve(ix, ix->pats, ((total + 7) & ~7ull) + 16));
-    FBG_TRY(px_reserve(ix, ix->poff, (n + 1) * 8));
-    for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(px_reserve(ix, *b, n * 4));
-    FBG_TRY(px_reserve(ix, ix->cnt_out, n * 8));
-    FBG_TRY(px_reserve(ix, ix->pos_out, n * 8));
-    FBG_TRY(px_reserve(ix, ix->lines_ctr, 8));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->pats, ((total + 7) & ~7ull) + 16, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->poff, (n + 1) * 8, &ix->bufs, false));
+    for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->cnt_out, n * 8, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->pos_out, n * 8, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->lines_ctr, 8, &ix->bufs, false));
     if (occ) {      // everything fbg_pindex_occurrences allocates, here: after hipSetDevice
-        FBG_TRY(px_reserve(ix, ix->orec, n * 24));
-        for (DevBuf *b : {&ix->oetot, &ix->ostot}) FBG_TRY(px_reserve(ix, *b, n * 8));
-        for (DevBuf *b : {&ix->oesz, &ix->ossz, &ix->oeoff, &ix->osoff}) FBG_TRY(px_reserve(ix, *b, (n + 1) * 8));
-        for (DevBuf *b : {&ix->ors, &ix->oel, &ix->oss, &ix->osk}) FBG_TRY(px_reserve(ix, *b, n * 4));
+        FBG_TRY(fbg_reserve(ix->ctx, ix->orec, n * 24, &ix->bufs, false));
+        for (DevBuf *b : {&ix->oetot, &ix->ostot}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 8, &ix->bufs, false));
+        for (DevBuf *b : {&ix->oesz, &ix->ossz, &ix->oeoff, &ix->osoff}) FBG_TRY(fbg_reserve(ix->ctx, *b, (n + 1) * 8, &ix->bufs, false));
+        for (DevBuf *b : {&ix->ors, &ix->oel, &ix->oss, &ix->osk}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
     }
     if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
@@ -1088,7 +1054,7 @@ extern "C" int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, u
     if (ne + ns == 0) return FBG_OK;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    FBG_TRY(px_reserve(ix, ix->oplace, 3 * (ne + ns) * 4));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->oplace, 3 * (ne + ns) * 4, &ix->bufs, false));
     if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
     // oplace: src, dst, offset of the ends, then of the starts
@@ -1172,12 +1138,12 @@ extern "C" int fbg_pindex_validate(fbg_pindex *ix, const uint32_t *node_block, c
     const int has_ig = (ig.w[0] | ig.w[1] | ig.w[2] | ig.w[3]) != 0;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    FBG_TRY(px_reserve(ix, ix->vblock, n * 4));
-    FBG_TRY(px_reserve(ix, ix->vstatus, n));
-    FBG_TRY(px_reserve(ix, ix->vwn, n * 4));
-    FBG_TRY(px_reserve(ix, ix->vwo, n * 4));
-    FBG_TRY(px_reserve(ix, ix->vlist, n * 4));
-    FBG_TRY(px_reserve(ix, ix->vctr, 16));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vblock, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vstatus, n, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vwn, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vwo, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vlist, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vctr, 16, &ix->bufs, false));
     if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->vblock.p, node_block, n * 4, hipMemcpyHostToDevice, st));

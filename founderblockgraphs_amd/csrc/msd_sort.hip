@@ -515,7 +515,6 @@ struct MsdPlan {
     uint32_t *tile_start;
     unsigned long long *off, *flag;
 };
-static_assert(sizeof(MsdPlan) <= sizeof(((fbg_ctx *)nullptr)->pre_state), "room for the plan of a sort begun ahead");
 
 // *ok = 0: the geometry does not suit this sort
 static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
@@ -575,7 +574,7 @@ static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
 
 // Pass 1 ahead of the rest of the index build, while the MSA is still arriving (text_build.hip, streamed upload): the keys are set
 // up for the alphabet ctx->byte_hist promises (the first chunk of rows, scaled); fbg_build_text checks the promise at the end
-// (ctx->pre_pass1) and fbg_msd_sort picks the plan up from ctx->pre_state.
+// (ctx->pre_pass1) and fbg_msd_sort picks the plan up from ctx->pre_plan.
 int fbg_msd_pre_begin(fbg_ctx *ctx, int *ok)
 {
     *ok = 0;
@@ -583,13 +582,12 @@ int fbg_msd_pre_begin(fbg_ctx *ctx, int *ok)
     int launches = 0;
     KeyGeom g;
     FBG_TRY(fbg_key_setup(ctx, true, &g, &launches));
-    MsdPlan plan;
+    if (!ctx->pre_plan) ctx->pre_plan = new MsdPlan();
     int good = 0;
-    FBG_TRY(msd_plan(ctx, g, &plan, &good));
+    FBG_TRY(msd_plan(ctx, g, ctx->pre_plan, &good));
     if (!good) return FBG_OK;
     for (int w = 0; w < 4; w++) ctx->pre_symbols[w] = 0;
     for (int b = 0; b < 256; b++) if (ctx->byte_hist[b]) ctx->pre_symbols[b >> 6] |= 1ull << (b & 63);
-    memcpy(ctx->pre_state, &plan, sizeof(plan));
     ctx->pre_tiles = 0;
     *ok = 1;
     return FBG_OK;
@@ -597,24 +595,39 @@ int fbg_msd_pre_begin(fbg_ctx *ctx, int *ok)
 
 int fbg_msd_pre_pass1(fbg_ctx *ctx, uint64_t avail)
 {
-    MsdPlan plan;
-    memcpy(&plan, ctx->pre_state, sizeof(plan));
-    const uint64_t N = plan.a.N;
+    MsdArgs a = ctx->pre_plan->a;
+    const uint64_t N = a.N;
     // a tile reads MSD_TILE + 64 text positions
     const uint64_t upto = avail >= N ? (N + MSD_TILE - 1) / MSD_TILE : (avail >= 64 ? (avail - 64) / MSD_TILE : 0);
     if (upto <= ctx->pre_tiles) return FBG_OK;
-    plan.a.tile0 = ctx->pre_tiles;
-    msd_launch_pass1(plan.a, (unsigned)(upto - ctx->pre_tiles), ctx->stream);
+    a.tile0 = ctx->pre_tiles;
+    msd_launch_pass1(a, (unsigned)(upto - ctx->pre_tiles), ctx->stream);
     ctx->pre_tiles = upto;
     return FBG_OK;
+}
+
+void fbg_msd_pre_free(fbg_ctx *ctx)
+{
+    delete ctx->pre_plan;
+    ctx->pre_plan = nullptr;
+}
+
+// The plan holds device pointers: are they still the context's buffers?  (Nothing between fbg_msd_pre_begin and
+// fbg_msd_sort grows them today; a reserve that did would have freed what pass 1 wrote.)
+static bool msd_plan_current(const fbg_ctx *ctx, const MsdPlan &p)
+{
+    const MsdArgs &a = p.a;
+    return a.T == ctx->text.p && a.code == ctx->small.as<uint8_t>() + 2048 && a.buf1 == ctx->keysA.p && a.out == ctx->keysA.p &&
+           a.buf2 == ctx->keysB.p && a.count1 == ctx->dp_a.p && (const void *)p.tile_start == ctx->dp_a.as<uint8_t>() + (size_t)p.nseg * 8 &&
+           a.count2 == ctx->dp_b.p && p.off == ctx->dp_c.p && a.arena_sb == ctx->dp_d.p && a.arena_w == ctx->dp_e.p &&
+           p.flag == ctx->scalars.as<unsigned long long>() + 100 && (!a.xb || a.ext == ctx->msd_ext.p);
 }
 
 bool fbg_msd_pre_geom(fbg_ctx *ctx, KeyGeom *g)
 {
     if (!ctx->pre_pass1) return false;
-    MsdPlan plan;
-    memcpy(&plan, ctx->pre_state, sizeof(plan));
-    *g = plan.g;
+    if (!msd_plan_current(ctx, *ctx->pre_plan)) { ctx->pre_pass1 = false; return false; }   // (the caller sets the keys up afresh)
+    *g = ctx->pre_plan->g;
     fbg_note_key_geom(ctx, *g);
     return true;
 }
@@ -622,15 +635,16 @@ bool fbg_msd_pre_geom(fbg_ctx *ctx, KeyGeom *g)
 int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int *launches)
 {
     *ok = 0;
-    ctx->msd_decline = 1;                                       // the geometry does not suit this sort
-    ctx->msd_ext_valid = false;
+    ctx->diag.msd_decline = 1;                                       // the geometry does not suit this sort
+    ctx->ix.msd_ext_valid = false;
     const uint64_t N = ctx->N;
     hipStream_t st = ctx->stream;
     MsdPlan plan;
-    const bool ahead = ctx->pre_pass1;                          // pass 1 ran while the MSA was uploaded (same g: fbg_msd_pre_geom)
+    // pass 1 ran while the MSA was uploaded (same g: fbg_msd_pre_geom) -- unless a buffer of its plan has moved since: all again
+    const bool ahead = ctx->pre_pass1 && msd_plan_current(ctx, *ctx->pre_plan);
     ctx->pre_pass1 = false;
-    ctx->pass1_ahead = ahead ? 1 : 0;
-    if (ahead) memcpy(&plan, ctx->pre_state, sizeof(plan));
+    ctx->diag.pass1_ahead = ahead ? 1 : 0;
+    if (ahead) plan = *ctx->pre_plan;
     else {
         int good = 0;
         FBG_TRY(msd_plan(ctx, g, &plan, &good));
@@ -654,7 +668,7 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_flag, flag, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     *launches += 2;
-    ctx->msd_decline = (int64_t)h_flag;                         // (fbg_get_option "msd_decline": which capacity did not hold)
+    ctx->diag.msd_decline = (int64_t)h_flag;                         // (fbg_get_option "msd_decline": which capacity did not hold)
     if (h_flag != 0 || tiles2 == 0) return FBG_OK;
     a.tiles2 = tiles2;
     a.tiles2_x = (xcd & 1) ? (tiles2 + 7) / 8 : 0;
@@ -683,7 +697,7 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
     FBG_HIP_TRY(ctx, hipMemcpyAsync(h2, flag, 16, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     *launches += 4;
-    ctx->msd_decline = (int64_t)h2[0];
+    ctx->diag.msd_decline = (int64_t)h2[0];
     if (h2[0] != 0) return FBG_OK;
     if (h2[1] > 0) {
         // a few sub-buckets were larger than their stretch (row ends pile up on keys that end in zeros): their
@@ -702,12 +716,12 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
         FBG_HIP_TRY(ctx, hipMemcpyAsync(h2, flag, 16, hipMemcpyDeviceToHost, st));
         FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
         *launches += 2;
-        ctx->msd_decline = (int64_t)h2[0];
+        ctx->diag.msd_decline = (int64_t)h2[0];
         if (h2[0] != 0) return FBG_OK;
     }
     FBG_HIP_TRY(ctx, hipGetLastError());
     *sorted = ctx->keysA.as<uint64_t>();
-    ctx->msd_ext_valid = a.xb != 0;
+    ctx->ix.msd_ext_valid = a.xb != 0;
     *ok = 1;
     return FBG_OK;
 }

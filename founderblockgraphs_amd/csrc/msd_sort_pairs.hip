@@ -801,7 +801,7 @@ __global__ void k_pp_iota(uint32_t *__restrict__ idx, uint32_t n)
 // The three passes.  a: key range / bucket function filled in by the caller; est: slots expected.  *ok = 0: not done
 // (a capacity was exceeded): nothing usable.
 template <int MODE>
-static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, PpArgs &a, uint64_t est, int nparts, uint64_t out_offset, uint64_t *count, int *ok,
+static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, PpArgs &a, uint64_t est, int nparts, uint64_t out_offset, uint64_t *count, int *ok,
                    int *launches)
 {
     const uint64_t N = ctx->N;
@@ -823,8 +823,8 @@ static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, PpArgs &a, uint64_t est, int 
     unsigned long long *flag = ctx->scalars.as<unsigned long long>() + 100;      // [0] flag, [1] arena count, [2] total
     a.T = ctx->text.as<uint8_t>(); a.N = N; a.code = g.d_code; a.b = g.b; a.K = g.K; a.pb = (g.wide || g.packed) ? g.pb : 0; a.nparts = nparts;
     a.wide = g.wide ? 1 : 0; a.packed = g.packed ? 1 : 0;
-    a.ebits = (MODE == 1 && !g.wide && !g.packed && g.K <= 32) ? ctx->grs_ebits : nullptr;
-    a.payload = (MODE == 1 && !g.wide && !g.packed) ? ctx->sort_payload : nullptr;
+    a.ebits = (MODE == 1 && !g.wide && !g.packed && g.K <= 32) ? x.ebits : nullptr;
+    a.payload = (MODE == 1 && !g.wide && !g.packed) ? x.payload : nullptr;
     a.any_order = a.payload ? 1 : 0;
     a.probe = 0;
     const bool any = MODE == 1 && a.any_order;
@@ -964,7 +964,7 @@ int fbg_msd_sort_part(fbg_ctx *ctx, const KeyGeom &g, uint64_t lo, uint64_t hi, 
     a.lo = lo; a.hi = hi; a.mul = (uint64_t)((one << 92) / span); a.nohi = nohi;      // mul < 2^64 since span > 2^28
     a.grid = nullptr; a.top = top; a.sigma = 1 << g.b;
     a.rb = 0; a.ew = 2; a.nd = 0; a.rtab = a.mtab = 0; a.key_bits = g.key_bits;
-    return pp_sort<0>(ctx, g, a, est, nparts, out_offset, count, ok, launches);
+    return pp_sort<0>(ctx, g, SortExtras(), a, est, nparts, out_offset, count, ok, launches);
 }
 
 // keys of every stride-th text position, as k_pack builds them without the compact coding (general alphabet)
@@ -1015,17 +1015,16 @@ __global__ void k_ss_grid(const uint64_t *__restrict__ sorted, uint64_t S, uint6
 
 // The record path's round-0 sort (suffix_sort.hip): all N (key, position) pairs of the current text, keys in the
 // order-preserving code of any alphabet, into keysB / valsB.  Sample sort: see the head of this file.
-int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, int *ok, int *launches)
+int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, int *ok, int *launches)
 {
     *ok = 0;
     ctx->pairs_similar = false;
-    ctx->pairs_rb = -1;
     const uint64_t N = ctx->N;
     const uint64_t min_n = ctx->opt.msd_min >= 0 ? (uint64_t)ctx->opt.msd_min : (1ull << 24);
     const uint64_t nsub = (uint64_t)PP_NB * PP_NB;
     // sub-bucket sizes follow the sample (2^22 keys, 16 per sub-bucket: +-25 %): they must fit their stretches twice over
     if (g.compact || g.packed || g.wide || N < min_n || N >= (1ull << 32) || ctx->opt.no_msd_sort || g.key_bits >= 64) return FBG_OK;
-    if (ctx->sp_key_flags) return FBG_OK;                  // (span_scan.hip beyond 2^30 cells: flag bits below the key; such texts are beyond the next line anyway)
+    if (x.key_flags) return FBG_OK;                  // (span_scan.hip beyond 2^30 cells: flag bits below the key; such texts are beyond the next line anyway)
     if (2 * (N / nsub) + 64 > PP_FN_CAP) return FBG_OK;
     hipStream_t st = ctx->stream;
     uint64_t S = 1ull << 22;
@@ -1058,7 +1057,7 @@ int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, int *ok, int *launches
         FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
         *launches += 1;
         ctx->pairs_similar = (double)twins * (double)N / ((double)S * (double)S) > 0.5 && !ctx->opt.msd_min_force;
-        if (ctx->pairs_similar && !ctx->sort_payload) return FBG_OK;    // (with a payload the consumer is the group-level scan: equal keys in any order)
+        if (ctx->pairs_similar && !x.payload) return FBG_OK;    // (with a payload the consumer is the group-level scan: equal keys in any order)
     }
     hipLaunchKernelGGL(k_ss_grid, dim3(fbg_blocks(nsub, 256)), dim3(256), 0, st, srt, S, grid);
     *launches += 3;
@@ -1103,8 +1102,8 @@ int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, int *ok, int *launches
     }
     uint64_t count = 0;
     const uint64_t est = N + N / 64 + 65536;
-    FBG_TRY(pp_sort<1>(ctx, g, a, est, 1, 0, &count, ok, launches));
+    FBG_TRY(pp_sort<1>(ctx, g, x, a, est, 1, 0, &count, ok, launches));
     if (*ok && count != N) { *ok = 0; }
-    ctx->pairs_rb = *ok ? a.rb : -1;
+    ctx->diag.pairs_rb = *ok ? a.rb : -1;
     return FBG_OK;
 }

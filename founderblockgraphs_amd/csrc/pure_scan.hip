@@ -306,7 +306,7 @@ template <class F> static int ps_with_tmp(fbg_ctx *ctx, F &&call)
     } while (0)
 
 // Called by fbg_suffix_sort after the round-0 sort of the compact keys, when the slot-level scan (rank_scan.hip) is
-// not the way (similar rows).  *done = 1: the column maxima are complete (ctx->ranked); 0: continue with the record path.
+// not the way (similar rows).  *done = 1: the column maxima are complete (kind ranked); 0: continue with the record path.
 int fbg_pure_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &geom, int *done)
 {
     *done = 0;
@@ -387,10 +387,9 @@ int fbg_pure_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
         launches++;
     }
     FBG_HIP_TRY(ctx, hipGetLastError());
-    ctx->n_exc = 0;
-    ctx->ranked = true;
-    ctx->part_active = false;
-    rs_remember(ctx, keys, vals, geom);
+    ctx->ix.n_exc = 0;
+    ctx->ix.kind = IndexKind::ranked;
+    fbg_remember_slots(ctx, keys, vals, rs_layout(geom), geom);
     *done = 1;
     return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
 }

@@ -274,10 +274,3 @@ static inline void rs_args_init(fbg_ctx *ctx, RankArgs &a, uint64_t *keys, uint3
     a.g_min = 0;
 }
 
-static inline void rs_remember(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g)
-{
-    ctx->rk_keys = keys; ctx->sa_ptr = vals;
-    ctx->rk_layout = rs_layout(g); ctx->rk_pb = g.pb;
-    ctx->rk_b = g.b; ctx->rk_key_bits = g.key_bits; ctx->rk_K = g.K;
-}
-

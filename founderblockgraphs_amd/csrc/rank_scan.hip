@@ -908,12 +908,12 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
     LeanArgs lf;
     const bool lean = layout == FBG_SLOTS_PACKED && a.g_min > (uint32_t)a.K && !a.values_only && !a.part_mode && !ctx->opt.rank_no_lean &&
                       rs_lean_setup(a, a.pb, rs_blocks, &lf);
-    ctx->rank_lean_launched = lean ? 1 : 0;
+    ctx->diag.rank_lean_launched = lean ? 1 : 0;
     if (lean)
     {
         // the symbols after the key from the MSD sort (these very slots, 2-bit symbols): the pairs carry a code in their spare
         // position bits -- positions below 2^30
-        if (ctx->msd_ext_valid && a.keys == ctx->keysA.as<uint64_t>() && a.b == 2 && a.pb <= 30 && a.own_lo == 0 && a.own_hi == ctx->N) {
+        if (ctx->ix.msd_ext_valid && a.keys == ctx->keysA.as<uint64_t>() && a.b == 2 && a.pb <= 30 && a.own_lo == 0 && a.own_hi == ctx->N) {
             lf.ext = ctx->msd_ext.as<uint8_t>();
             a.pair_codes = 1;
         }
@@ -1008,14 +1008,10 @@ static int rs_pick_threshold(fbg_ctx *ctx, RankArgs &a, const uint64_t *keys, ui
 }
 
 // Called by fbg_suffix_sort right after the round-0 sort of the compact keys.  *done = 1 when the rank-order scan
-// covered the whole input (ctx->ranked set); 0 = continue with the record path.
+// covered the whole input (kind ranked); 0 = continue with the record path.
 int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &geom, int *done)
 {
     *done = 0;
-    ctx->ranked = false;
-    ctx->part_active = false;
-    ctx->ext_pairs = ctx->text_pairs = -1;
-    ctx->rank_lean_used = ctx->rank_lean_launched = 0;
     const uint64_t N = ctx->N, n = ctx->n;
     const int layout = rs_layout(geom);
     hipStream_t st = ctx->stream;
@@ -1046,8 +1042,8 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     FBG_HIP_TRY(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     if (a.pair_stats) FBG_HIP_TRY(ctx, hipMemcpyAsync(ps, a.pair_stats, sizeof(ps), hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->ext_pairs = (int64_t)ps[0];
-    ctx->text_pairs = (int64_t)ps[1];
+    ctx->diag.ext_pairs = (int64_t)ps[0];
+    ctx->diag.text_pairs = (int64_t)ps[1];
     launches++;
     if (h[1] != 0) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
     if (a.g_min > 1 && h[4] != 0) {
@@ -1057,10 +1053,10 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
         launches++;
     }
     FBG_HIP_TRY(ctx, hipGetLastError());
-    ctx->n_exc = 0;
-    ctx->ranked = true;
-    ctx->rank_lean_used = ctx->rank_lean_launched;
-    rs_remember(ctx, keys, vals, geom);
+    ctx->ix.n_exc = 0;
+    ctx->ix.kind = IndexKind::ranked;
+    ctx->diag.rank_lean_used = ctx->diag.rank_lean_launched;
+    fbg_remember_slots(ctx, keys, vals, rs_layout(geom), geom);
     *done = 1;
     return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
 }
@@ -1100,11 +1096,11 @@ __global__ void k_halo_import(const uint8_t *__restrict__ blobs, int part, int n
 
 static void rs_part_args(fbg_ctx *ctx, RankArgs &a)
 {
-    rs_args_init(ctx, a, ctx->rk_keys, ctx->sa_ptr, ctx->part_count + 2 * FBG_PART_HALO, ctx->rk_layout, ctx->rk_pb, ctx->rk_b,
-                 ctx->rk_key_bits, ctx->rk_K);
-    a.own_lo = FBG_PART_HALO; a.own_hi = FBG_PART_HALO + ctx->part_count;
-    a.first_part = ctx->part == 0; a.last_part = ctx->part + 1 == ctx->nparts;
-    a.part_mode = ctx->nparts > 1;
+    rs_args_init(ctx, a, ctx->ix.rk_keys, ctx->ix.sa_ptr, ctx->ix.part_count + 2 * FBG_PART_HALO, ctx->ix.rk_layout, ctx->ix.rk_pb, ctx->ix.rk_b,
+                 ctx->ix.rk_key_bits, ctx->ix.rk_K);
+    a.own_lo = FBG_PART_HALO; a.own_hi = FBG_PART_HALO + ctx->ix.part_count;
+    a.first_part = ctx->ix.part == 0; a.last_part = ctx->ix.part + 1 == ctx->ix.nparts;
+    a.part_mode = ctx->ix.nparts > 1;
 }
 
 // Phase 1: classify the owned slots, order the tie groups, publish the edge slots (d_blob, FBG_PART_HALO_BYTES).
@@ -1116,10 +1112,9 @@ int fbg_rank_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_RANKSCAN));
     int launches = 0;
-    ctx->ranked = false;
-    ctx->part_count = count;
-    ctx->part_T = 0;
-    rs_remember(ctx, keys, vals, geom);
+    ctx->ix.part_count = count;
+    ctx->ix.part_T = 0;
+    fbg_remember_slots(ctx, keys, vals, rs_layout(geom), geom);
     const int layout = rs_layout(geom);
     FBG_TRY(fbg_reserve(ctx, ctx->gmax, (n + 1) * 4));
     unsigned long long *cnt = ctx->scalars.as<unsigned long long>() + 32;
@@ -1133,14 +1128,14 @@ int fbg_rank_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_
         FBG_TRY(rs_pick_threshold(ctx, a, keys + a.own_lo, count, geom, &reject, &launches));
         if (reject) good = 0;
     }
-    ctx->part_gmin = a.g_min;
+    ctx->ix.part_gmin = a.g_min;
     if (good) {
         uint64_t T = 0;
         FBG_TRY(rs_classify(ctx, a, layout, &T, &launches));
         FBG_TRY(rs_join(ctx));
         if (T == ~0ull) good = 0;
         else {
-            ctx->part_T = T;
+            ctx->ix.part_T = T;
             unsigned long long h[2];                   // tie groups longer than 64 / tie regions too small raise [1]
             FBG_HIP_TRY(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
             FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1164,27 +1159,27 @@ int fbg_rank_part_runs(fbg_ctx *ctx, const uint8_t *d_blobs, uint32_t *d_gmax, i
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_RANKSCAN));
     int launches = 0;
-    std::vector<uint8_t> hb((size_t)ctx->nparts * FBG_PART_HALO_BYTES);
+    std::vector<uint8_t> hb((size_t)ctx->ix.nparts * FBG_PART_HALO_BYTES);
     FBG_HIP_TRY(ctx, hipMemcpyAsync(hb.data(), d_blobs, hb.size(), hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     int good = 1;
     uint32_t gmin_all = 0;
-    for (int p = 0; p < ctx->nparts; p++) {
+    for (int p = 0; p < ctx->ix.nparts; p++) {
         uint64_t tail[2];
         memcpy(tail, hb.data() + (size_t)p * FBG_PART_HALO_BYTES + 2 * FBG_PART_HALO * 12, sizeof(tail));
         if (!(tail[0] & 1)) good = 0;
         gmin_all = std::max(gmin_all, (uint32_t)(tail[0] >> 8));
     }
-    ctx->part_gmin = gmin_all;      // a column maximum of at least this cannot be beaten by anything any partition skipped
+    ctx->ix.part_gmin = gmin_all;      // a column maximum of at least this cannot be beaten by anything any partition skipped
     if (good) {
         RankArgs a;
         rs_part_args(ctx, a);
         a.cand = ctx->dp_a.as<uint32_t>(); a.pm = ctx->dp_b.as<uint32_t>();
-        hipLaunchKernelGGL(k_halo_import, dim3(1), dim3(FBG_PART_HALO), 0, st, d_blobs, ctx->part, ctx->nparts, a.own_lo,
+        hipLaunchKernelGGL(k_halo_import, dim3(1), dim3(FBG_PART_HALO), 0, st, d_blobs, ctx->ix.part, ctx->ix.nparts, a.own_lo,
                            a.own_hi, a.keys, a.vals);
         launches++;
-        if (ctx->part_T > 0) {
-            RS_LAUNCH(k_runs, ctx->rk_layout, dim3(fbg_blocks(ctx->part_T, 64)), dim3(64), st, a, ctx->part_T);
+        if (ctx->ix.part_T > 0) {
+            RS_LAUNCH(k_runs, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->ix.part_T, 64)), dim3(64), st, a, ctx->ix.part_T);
             launches++;
             unsigned long long h[2];
             FBG_HIP_TRY(ctx, hipMemcpyAsync(h, a.counters, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -1205,11 +1200,11 @@ int fbg_rank_part_runs(fbg_ctx *ctx, const uint8_t *d_blobs, uint32_t *d_gmax, i
 int fbg_rank_part_unfilled(fbg_ctx *ctx, uint64_t *unfilled)
 {
     *unfilled = 0;
-    if (ctx->part_gmin <= 1) return FBG_OK;
+    if (ctx->ix.part_gmin <= 1) return FBG_OK;
     hipStream_t st = ctx->stream;
     unsigned long long *cnt = ctx->scalars.as<unsigned long long>() + 32;
     FBG_HIP_TRY(ctx, hipMemsetAsync(cnt + 4, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_count_unfilled, dim3(fbg_blocks(ctx->n, 256)), dim3(256), 0, st, ctx->gmax.as<uint32_t>(), ctx->n, ctx->part_gmin,
+    hipLaunchKernelGGL(k_count_unfilled, dim3(fbg_blocks(ctx->n, 256)), dim3(256), 0, st, ctx->gmax.as<uint32_t>(), ctx->n, ctx->ix.part_gmin,
                        ctx->reversed, cnt);
     unsigned long long h = 0;
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&h, cnt + 4, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -1226,9 +1221,9 @@ int fbg_rank_part_rescan(fbg_ctx *ctx)
     rs_part_args(ctx, a);
     a.g_min = 0;
     a.values_only = 1;
-    RS_LAUNCH_SCAN(ctx->rk_layout, true, dim3(fbg_blocks(ctx->part_count, RS_CHUNK, 256 * 16)), ctx->stream, a);
+    RS_LAUNCH_SCAN(ctx->ix.rk_layout, true, dim3(fbg_blocks(ctx->ix.part_count, RS_CHUNK, 256 * 16)), ctx->stream, a);
     FBG_HIP_TRY(ctx, hipGetLastError());
-    ctx->part_gmin = 0;
+    ctx->ix.part_gmin = 0;
     return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, 1);
 }
 
@@ -1247,13 +1242,13 @@ int fbg_rank_finish(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disabl
 int fbg_rank_materialize(fbg_ctx *ctx, uint32_t *d_sa, uint32_t *d_isa, uint32_t *d_pl, uint32_t *d_pr)
 {
     RankArgs a;
-    rs_args_init(ctx, a, ctx->rk_keys, ctx->sa_ptr, ctx->N, ctx->rk_layout, ctx->rk_pb, ctx->rk_b, ctx->rk_key_bits, ctx->rk_K);
+    rs_args_init(ctx, a, ctx->ix.rk_keys, ctx->ix.sa_ptr, ctx->N, ctx->ix.rk_layout, ctx->ix.rk_pb, ctx->ix.rk_b, ctx->ix.rk_key_bits, ctx->ix.rk_K);
     FBG_TRY(fbg_reserve(ctx, ctx->big_groups, RS_BIG_GROUPS * 8));
     a.big = ctx->big_groups.as<uint32_t>();
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.counters + 5, 0, sizeof(unsigned long long), ctx->stream));
-    RS_LAUNCH(k_tie_groups, ctx->rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, ctx->N, 0);
-    RS_LAUNCH(k_tie_big, ctx->rk_layout, dim3(RS_BIG_GROUPS), dim3(256), ctx->stream, a, 1);
-    RS_LAUNCH(k_rank_materialize, ctx->rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, d_sa, d_isa, d_pl, d_pr);
+    RS_LAUNCH(k_tie_groups, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, ctx->N, 0);
+    RS_LAUNCH(k_tie_big, ctx->ix.rk_layout, dim3(RS_BIG_GROUPS), dim3(256), ctx->stream, a, 1);
+    RS_LAUNCH(k_rank_materialize, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, d_sa, d_isa, d_pl, d_pr);
     FBG_HIP_TRY(ctx, hipGetLastError());
     return FBG_OK;
 }

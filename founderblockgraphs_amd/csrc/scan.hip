@@ -358,25 +358,27 @@ int fbg_scan_columns(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disab
 {
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_SCAN));
     int launches = 0;
-    if (x1 > x0 && ctx->granked) {
+    if (x1 > x0 && ctx->ix.granked()) {
         int ok = 0;
         FBG_TRY(fbg_grs_finish(ctx, x0, x1, disable_tricks, d_out, &ok));
         launches++;
         if (!ok) {
             // the scan for this setting of the tricks ran out of room: the index again, the record way
+            uint8_t ign[256];
+            uint64_t n_ign = 0;
+            for (int c = 0; c < 256; c++) if (ctx->ignore_tab[c]) ign[n_ign++] = (uint8_t)c;
             ctx->grs_skip = true;
-            int rc = fbg_suffix_sort(ctx);
+            int rc = fbg_index_build(ctx, 0, ign, n_ign);
             ctx->grs_skip = false;
             FBG_TRY(rc);
-            FBG_TRY(fbg_neighbour_lcp(ctx));
         }
     }
-    if (x1 > x0 && ctx->granked) {
-    } else if (x1 > x0 && ctx->ranked) {
+    if (x1 > x0 && ctx->ix.granked()) {
+    } else if (x1 > x0 && ctx->ix.ranked()) {
         // rank-order index: column maxima are ready, only the exception columns need the per-column kernel
         FBG_TRY(fbg_rank_finish(ctx, x0, x1, mode, disable_tricks, d_out));
         launches++;
-        if (ctx->n_exc > 0) {
+        if (ctx->ix.n_exc > 0) {
             ScanArgs a;
             a.rec = nullptr; a.exc = ctx->exc.as<uint4>();
             a.prow = nullptr; a.igrow = nullptr;
@@ -388,7 +390,7 @@ int fbg_scan_columns(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disab
             uint32_t logH = 7;
             while ((1u << logH) < 2 * ctx->m) logH++;
             a.H = 1u << logH; a.logH = logH;
-            FBG_TRY(launch_exceptions(ctx, a, (uint64_t)ctx->n_exc));
+            FBG_TRY(launch_exceptions(ctx, a, (uint64_t)ctx->ix.n_exc));
             launches++;
         }
         FBG_HIP_TRY(ctx, hipGetLastError());

@@ -1321,11 +1321,11 @@ template <class F> static int sp_with_tmp(fbg_ctx *ctx, F &&call)
 
 static void sp_args(fbg_ctx *ctx, SpArgs &a, int disable_tricks)
 {
-    a.keys = ctx->rk_keys; a.vals = ctx->sa_ptr; a.N = ctx->N;
+    a.keys = ctx->ix.rk_keys; a.vals = ctx->ix.sa_ptr; a.N = ctx->N;
     a.n = (uint32_t)ctx->n; a.m = (uint32_t)ctx->m; a.row_len = (uint32_t)(ctx->n + 1);
     a.magic = (uint32_t)((1ull << 32) / (ctx->n + 1));
-    a.b = ctx->rk_b; a.K = ctx->rk_K; a.key_bits = ctx->rk_key_bits; a.disable_tricks = disable_tricks;
-    a.ksh = ctx->sp_key_flags_sorted ? 2 : 0;
+    a.b = ctx->ix.rk_b; a.K = ctx->ix.rk_K; a.key_bits = ctx->ix.rk_key_bits; a.disable_tricks = disable_tricks;
+    a.ksh = ctx->ix.sp_key_flags_sorted ? 2 : 0;
     a.T = ctx->text.as<uint8_t>();
     a.colT = ctx->gapfree ? nullptr : ctx->colT.as<uint32_t>();
     a.pos = ctx->pos.as<uint32_t>(); a.tot = ctx->tot.as<uint32_t>();
@@ -1372,12 +1372,12 @@ bool fbg_span_key_flags(fbg_ctx *ctx, KeyGeom &g)
 
 // Before the sort (fbg_grs_prepare has made the bitmap of irregular positions): the payload of every text position ->
 // ctx->sp_cells (and ctx->sp_flagT), the window table of the cells.
-int fbg_span_prepare(fbg_ctx *ctx, const KeyGeom &g, int *launches)
+int fbg_span_prepare(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, int *launches)
 {
     const uint64_t N = ctx->N, n = ctx->n, m = ctx->m;
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_reserve(ctx, ctx->sp_cells, N * 4));
-    if (ctx->sp_key_flags) FBG_TRY(fbg_reserve(ctx, ctx->sp_flagT, N));
+    if (x.key_flags) FBG_TRY(fbg_reserve(ctx, ctx->sp_flagT, N));
     if (!ctx->gapfree) {
         const uint32_t wpr = (uint32_t)((n + 127) / 128);
         FBG_TRY(fbg_reserve(ctx, ctx->sp_cwin, (size_t)m * wpr * sizeof(CWin)));
@@ -1389,7 +1389,7 @@ int fbg_span_prepare(fbg_ctx *ctx, const KeyGeom &g, int *launches)
     }
     hipLaunchKernelGGL(k_sp_cells, dim3(fbg_blocks(N, 256 * SPC_CHUNKS)), dim3(256), 0, st, ctx->gapfree ? (const uint32_t *)nullptr : ctx->colT.as<uint32_t>(),
                        ctx->pos.as<uint32_t>(), N, (uint32_t)n, (uint32_t)m, g.K, ctx->gbits.as<unsigned long long>(), ctx->sp_cells.as<uint32_t>(),
-                       ctx->sp_key_flags ? ctx->sp_flagT.as<uint8_t>() : (uint8_t *)nullptr);
+                       x.key_flags ? ctx->sp_flagT.as<uint8_t>() : (uint8_t *)nullptr);
     *launches += 1;
     FBG_HIP_TRY(ctx, hipGetLastError());
     return FBG_OK;
@@ -1399,7 +1399,7 @@ int fbg_span_prepare(fbg_ctx *ctx, const KeyGeom &g, int *launches)
 static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
 {
     *ok = 0;
-    ctx->sp_decline = 0;
+    ctx->diag.sp_decline = 0;
     hipStream_t st = ctx->stream;
     const uint64_t n = ctx->n, G = ctx->sp_G;
     SpArgs a;
@@ -1422,8 +1422,8 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
     // the star phylogeny 1000 x 200 000 with deletions that 30 % / 90 % of the rows share at 1000 and at 4000 columns
     // (scripts/gpu_stargaps.py, FBG_STAR_SHARED; profiles/r04_shared_deletions.txt): 4.2 / 5.9 / 7.1 comparisons per suffix took
     // 87 / 131 / 118 ms here against 150 / 149 / 140 on the record path, 12.7 took 326 against 128 (the bound was 32 until round 4)
-    if (h[1] != 0) { ctx->sp_decline = 1; return FBG_OK; }
-    if (h[0] > std::max<unsigned long long>(10 * ctx->N, 1ull << 26)) { ctx->sp_decline = 2; return FBG_OK; }
+    if (h[1] != 0) { ctx->diag.sp_decline = 1; return FBG_OK; }
+    if (h[0] > std::max<unsigned long long>(10 * ctx->N, 1ull << 26)) { ctx->diag.sp_decline = 2; return FBG_OK; }
     // the larger groups' odd members: a list for those that are coloured alone, a list of the groups that need every pair compared
     const uint64_t members = h[3];
     FBG_TRY(fbg_reserve(ctx, ctx->sp_chain, (members + 1) * sizeof(SpChain)));
@@ -1458,7 +1458,7 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
         // the groups with more odd members than that kernel takes: every pair the slow way
         FBG_HIP_TRY(ctx, hipMemcpyAsync(h, a.counters + 2, sizeof(h), hipMemcpyDeviceToHost, st));
         FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (h[1] != 0) { ctx->sp_decline = 3; return FBG_OK; }
+        if (h[1] != 0) { ctx->diag.sp_decline = 3; return FBG_OK; }
         const uint32_t n_slow = (uint32_t)h[5];
         ctx->sp_slow_n = n_slow;
         // (a large group on the slow list has more odd members than the kernel above takes -- a deletion in dozens of a few
@@ -1473,7 +1473,7 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
             // (ahead[1]: the large groups with more than 256 odd members.  A long MSA has some by chance -- two columns whose K
             // symbols agree make one group of twice the rows, half of them "odd"; their number grows with the square of the
             // columns -- and they run side by side, a workgroup each: up to one per 2^22 suffixes is accepted)
-            if (ahead[1] > (ctx->N >> 22) || ahead[0] > 64 * ctx->N) { ctx->sp_decline = 4; return FBG_OK; }
+            if (ahead[1] > (ctx->N >> 22) || ahead[0] > 64 * ctx->N) { ctx->diag.sp_decline = 4; return FBG_OK; }
         }
         if (n_slow) {
             hipLaunchKernelGGL((k_sp_odd_slow<1024>), dim3(std::min<uint32_t>(n_slow, 1u << 20)), dim3(SP_THREADS), 0, st, a, (const uint32_t *)a.slow, n_slow, 0u, 1u);
@@ -1490,7 +1490,7 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
         hipLaunchKernelGGL((k_sp_odd<8192>), dim3(std::min<uint32_t>(n_big, 1u << 16)), dim3(SP_THREADS), 0, st, a, lists[3], n_big);
         FBG_HIP_TRY(ctx, hipMemcpyAsync(h, a.counters + 2, sizeof(h), hipMemcpyDeviceToHost, st));
         FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (h[1] != 0) { ctx->sp_decline = 5; return FBG_OK; }
+        if (h[1] != 0) { ctx->diag.sp_decline = 5; return FBG_OK; }
         const uint32_t n_chain = (uint32_t)h[4];
         if (n_chain) {
             hipLaunchKernelGGL(k_sp_chain, dim3(fbg_blocks(n_chain, 64)), dim3(64), 0, st, a, n_chain, 0);
@@ -1498,7 +1498,7 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
         }
         FBG_HIP_TRY(ctx, hipMemcpyAsync(h, a.counters + 2, sizeof(h), hipMemcpyDeviceToHost, st));
         FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (h[1] != 0) { ctx->sp_decline = 6; return FBG_OK; }
+        if (h[1] != 0) { ctx->diag.sp_decline = 6; return FBG_OK; }
         const uint32_t n_slow = (uint32_t)h[5];
         ctx->sp_chain_n = n_chain; ctx->sp_slow_n = n_slow;
         if (n_slow) {
@@ -1516,7 +1516,7 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
             FBG_HIP_TRY(ctx, hipMemcpyAsync(&uniq, a.counters + 15, 8, hipMemcpyDeviceToHost, st));
             FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
             ctx->sp_slow_n = (uint32_t)uniq;
-            if (ctx->opt.span_scan != 1 && ctx->opt.span_scan != 3 && uniq > ctx->N / (1ull << 20) + 4) { ctx->sp_decline = 7; return FBG_OK; }
+            if (ctx->opt.span_scan != 1 && ctx->opt.span_scan != 3 && uniq > ctx->N / (1ull << 20) + 4) { ctx->diag.sp_decline = 7; return FBG_OK; }
             hipLaunchKernelGGL((k_sp_odd_slow<8192>), dim3(std::min<uint32_t>(n_slow, 1u << 16)), dim3(SP_THREADS), 0, st, a, (const uint32_t *)sorted, n_slow, 0u, 1u);
             *launches += 3;
         }
@@ -1533,7 +1533,7 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&flag, a.counters + 3, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     FBG_HIP_TRY(ctx, hipGetLastError());
-    if (flag != 0) { ctx->sp_decline = 8; return FBG_OK; }
+    if (flag != 0) { ctx->diag.sp_decline = 8; return FBG_OK; }
     ctx->grs_tricks_off = disable_tricks;
     *ok = 1;
     return FBG_OK;
@@ -1554,21 +1554,19 @@ static bool sp_ignore_mask(fbg_ctx *ctx, uint64_t *by_code)
 }
 
 // After the sort of the (key, cell) pairs.  *done = 1: the index is the sorted slots, the group tables and the
-// per-column maxima (ctx->granked, ctx->spanned); 0: vals hold text positions again, continue with the record path.
+// per-column maxima (kind span); 0: vals hold text positions again, continue with the record path.
 int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g, int *done)
 {
     *done = 0;
-    ctx->granked = false; ctx->spanned = false;
     const uint64_t N = ctx->N, n = ctx->n;
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_RANKSCAN));
     int launches = 0;
     uint64_t by_code = 0;
     bool good = sp_ignore_mask(ctx, &by_code);
-    ctx->sp_decline = good ? 0 : 10;
+    ctx->diag.sp_decline = good ? 0 : 10;
     FBG_TRY(fbg_reserve(ctx, ctx->gmax, (n + 1) * 4));
-    ctx->rk_keys = keys; ctx->sa_ptr = vals;
-    ctx->rk_layout = FBG_SLOTS_PAIRS; ctx->rk_pb = 0; ctx->rk_b = g.b; ctx->rk_key_bits = g.key_bits; ctx->rk_K = g.K;
+    fbg_remember_slots(ctx, keys, vals, FBG_SLOTS_PAIRS, g);
     ctx->grs_ign_lo = (uint32_t)by_code; ctx->grs_ign_hi = (uint32_t)(by_code >> 32);
     ctx->sp_G = 0; ctx->sp_R = 0; ctx->sp_n_irr = 0; ctx->sp_n_odd[0] = ctx->sp_n_odd[1] = ctx->sp_n_odd[2] = ctx->sp_n_odd[3] = 0; ctx->sp_odd_cap = 0;
     SpArgs a;
@@ -1637,7 +1635,7 @@ int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g,
         FBG_HIP_TRY(ctx, hipMemcpyAsync(h, a.counters, sizeof(h), hipMemcpyDeviceToHost, st));
         FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
         launches += 2;
-        if (h[3] != 0) { good = false; ctx->sp_decline = 9; }
+        if (h[3] != 0) { good = false; ctx->diag.sp_decline = 9; }
         for (int c = 0; c < 4; c++) ctx->sp_n_odd[c] = (uint32_t)std::min<unsigned long long>(h[8 + c], cap);
         // The lists in COLUMN order: the workgroups of an odd group read the texts of all its members -- hundreds of rows at
         // one column, two memory lines each -- and so do the groups of the columns next to it.  In key order those meet at
@@ -1662,8 +1660,7 @@ int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g,
     int ok = 0;
     if (good) FBG_TRY(sp_scan(ctx, 0, &ok, &launches));
     if (ok) {
-        ctx->granked = true; ctx->spanned = true;
-        ctx->ranked = false; ctx->part_active = false;
+        ctx->ix.kind = IndexKind::span;
         *done = 1;
     } else {
         sp_args(ctx, a, 0);

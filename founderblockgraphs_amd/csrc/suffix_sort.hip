@@ -164,8 +164,10 @@ __global__ __launch_bounds__(SS_THREADS) void k_pack(PackArgs a)
     }
 }
 
-static void launch_pack(fbg_ctx *ctx, const KeyGeom &g, bool filter, PackArgs &a)
+static void launch_pack(fbg_ctx *ctx, const KeyGeom &g, bool filter, PackArgs &a, const SortExtras &x)
 {
+    a.ebits = x.ebits; a.payload = x.payload;
+    a.key_flags = x.key_flags ? ctx->sp_flagT.as<uint8_t>() : nullptr;
     const dim3 grid(fbg_blocks(a.N, SS_THREADS * PK_ITEMS)), block(SS_THREADS);
     hipStream_t st = ctx->stream;
 #define FBG_PACK(C, L, F) hipLaunchKernelGGL((k_pack<C, L, F>), grid, block, 0, st, a)
@@ -773,8 +775,9 @@ int fbg_key_setup(fbg_ctx *ctx, bool compact, KeyGeom *g, int *launches)
     return FBG_OK;
 }
 
-// sorted (by key) slots of the first `count` entries of the A buffers -> B buffers (+ offset)
-static int sort_slots(fbg_ctx *ctx, const KeyGeom &g, uint64_t count, uint64_t out_offset)
+// sorted (by key) slots of the first `count` entries of the A buffers -> B buffers (+ offset); key_flags: two flag bits
+// below the key of a pair (span_scan.hip)
+static int sort_slots(fbg_ctx *ctx, const KeyGeom &g, bool key_flags, uint64_t count, uint64_t out_offset)
 {
     hipStream_t st = ctx->stream;
     uint64_t *ka = ctx->keysA.as<uint64_t>(), *kb = ctx->keysB.as<uint64_t>() + out_offset;
@@ -789,7 +792,7 @@ static int sort_slots(fbg_ctx *ctx, const KeyGeom &g, uint64_t count, uint64_t o
         });
     }
     uint32_t *va = ctx->valsA.as<uint32_t>(), *vb = ctx->valsB.as<uint32_t>() + out_offset;
-    unsigned lo = g.wide ? (unsigned)g.pb : ctx->sp_key_flags ? 2u : 0u;     // (span_scan.hip: two flag bits below the key)
+    unsigned lo = g.wide ? (unsigned)g.pb : key_flags ? 2u : 0u;
     const unsigned hi = lo + (unsigned)g.key_bits;
     if (hi == 64 && count < (1u << 23)) lo = 0;        // same caution as above
     return with_tmp(ctx, [&](void *tmp, size_t &bytes) {
@@ -834,18 +837,8 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_SUFFIX_SORT));
     int launches = 0;
     const uint8_t *T = ctx->text.as<uint8_t>();
-    ctx->part_active = false;
-    ctx->ranked = false;
-    ctx->granked = false;
-    ctx->grs_ebits = nullptr;
-    ctx->grs_flagged = false;
-    ctx->msd_ext_valid = false;
-    ctx->rank_lean_used = ctx->rank_lean_launched = 0;
-    ctx->pairs_rb = -1;
-    ctx->ext_pairs = ctx->text_pairs = -1;
-    ctx->pass1_ahead = 0;
-    ctx->msd_decline = -1;                      // (fbg_msd_sort says otherwise when the build reaches it)
     KeyGeom g;
+    SortExtras x;                               // (what the sort of a gap-free MSA carries: nothing)
 
     // ---- gap-free MSAs: compact keys, sort, and the whole extension scan in rank order (rank_scan.hip) -------
     if (ctx->gapfree && !ctx->have_ignore && !ctx->opt.no_ranked) {
@@ -873,9 +866,9 @@ int fbg_suffix_sort(fbg_ctx *ctx)
             pa.T = T; pa.N = N; pa.code = g.d_code; pa.b = g.b; pa.K = g.K; pa.pb = g.pb;
             pa.keys = ctx->keysA.as<uint64_t>(); pa.vals = ctx->valsA.as<uint32_t>();
             pa.lo = pa.hi = pa.cap = 0; pa.nohi = 1; pa.counter = nullptr;
-            launch_pack(ctx, g, false, pa);
+            launch_pack(ctx, g, false, pa, x);
             launches++;
-            FBG_TRY(sort_slots(ctx, g, N, 0));
+            FBG_TRY(sort_slots(ctx, g, false, N, 0));
             sorted = ctx->keysB.as<uint64_t>();
         }
         uint32_t *svals = g.packed ? nullptr : ctx->valsB.as<uint32_t>();
@@ -903,7 +896,7 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     uint4 *rec = nullptr;
     uint8_t *flags = nullptr;
     uint32_t *sa = valsB;                     // the sorted positions ARE the suffix array
-    ctx->sa_ptr = sa;
+    ctx->ix.sa_ptr = sa;
     ColTest ct;
     ct.colT = ctx->gapfree ? nullptr : ctx->colT.as<uint32_t>();
     ct.row_len = (uint32_t)(ctx->n + 1);
@@ -912,9 +905,6 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     // MSAs with gaps / ignore characters: the scan in rank order follows the sort (gapped_rank.hip); its table of the
     // text's irregular positions is made now, the pack kernels fold it into the values' top bit
     ctx->pairs_similar = false;
-    ctx->spanned = false;
-    ctx->sort_payload = nullptr;
-    ctx->sp_key_flags = false;
     // rows that resemble each other (twins among the keys of a sample; option span_scan = 1: whatever the rows): the
     // group-level scan on column spans (span_scan.hip), whose sort carries cells instead of positions
     bool try_span = fbg_span_eligible(ctx, g);
@@ -924,43 +914,37 @@ int fbg_suffix_sort(fbg_ctx *ctx)
         try_span = similar;
     }
     const bool try_grs = !try_span && (!ctx->gapfree || ctx->have_ignore) && !ctx->reversed && !ctx->grs_skip && ctx->opt.gapped_rank != -1 && K <= 32;
-    if (try_grs || try_span) FBG_TRY(fbg_grs_prepare(ctx, &launches));
+    if (try_grs || try_span) FBG_TRY(fbg_grs_prepare(ctx, &x.ebits, &launches));
     if (try_span) {
-        ctx->grs_ebits = nullptr; ctx->grs_flagged = false;           // (the bitmap goes into the cells' flags instead)
-        ctx->sp_key_flags = fbg_span_key_flags(ctx, g);               // (2^30 cells and more: may shorten the key by a symbol)
+        x.ebits = nullptr; ctx->ix.grs_flagged = false;               // (the bitmap goes into the cells' flags instead)
+        x.key_flags = fbg_span_key_flags(ctx, g);                     // (2^30 cells and more: may shorten the key by a symbol)
         K = g.K; key_bits = g.key_bits;
-        FBG_TRY(fbg_span_prepare(ctx, g, &launches));
-        ctx->sort_payload = ctx->sp_cells.as<uint32_t>();
+        FBG_TRY(fbg_span_prepare(ctx, g, x, &launches));
+        x.payload = ctx->sp_cells.as<uint32_t>();
     }
     {
         // three passes of a sample sort fused with the key packing (msd_sort_pairs.hip) where the sizes suit it; else,
         // or when a capacity does not hold, pack and sort with rocPRIM's onesweep
         int ss_ok = 0;
-        FBG_TRY(fbg_sample_sort_pairs(ctx, g, &ss_ok, &launches));
+        FBG_TRY(fbg_sample_sort_pairs(ctx, g, x, &ss_ok, &launches));
         if (!ss_ok) {
             PackArgs pa;
             pa.T = T; pa.N = N; pa.code = g.d_code; pa.b = b; pa.K = K; pa.pb = 0;
             // the sample sort reserves larger buffers before it can decline: the pointers taken above may be stale
             pa.keys = ctx->keysA.as<uint64_t>(); pa.vals = ctx->valsA.as<uint32_t>();
             pa.lo = pa.hi = pa.cap = 0; pa.nohi = 1; pa.counter = nullptr;
-            pa.ebits = ctx->grs_ebits;
-            pa.payload = ctx->sort_payload;
-            pa.key_flags = ctx->sp_key_flags ? ctx->sp_flagT.as<uint8_t>() : nullptr;
-            launch_pack(ctx, g, false, pa);
+            launch_pack(ctx, g, false, pa, x);
             launches++;
-            FBG_TRY(sort_slots(ctx, g, N, 0));
+            FBG_TRY(sort_slots(ctx, g, x.key_flags, N, 0));
         }
-        ctx->sort_payload = nullptr;
-        ctx->sp_key_flags_sorted = ctx->sp_key_flags;
-        ctx->sp_key_flags = false;                                    // (sort_slots serves the later rounds too)
+        ctx->ix.sp_key_flags_sorted = x.key_flags;
         // the sample sort sizes its buffers itself: take the pointers again
         keysA = ctx->keysA.as<uint64_t>(); keysB = ctx->keysB.as<uint64_t>();
         valsA = ctx->valsA.as<uint32_t>(); valsB = ctx->valsB.as<uint32_t>();
         sa = valsB;
-        ctx->sa_ptr = sa;
+        ctx->ix.sa_ptr = sa;
     }
     // ---- MSAs with gaps / ignore characters: the extension scan in rank order on these slots (gapped_rank.hip) ----
-    ctx->grs_ebits = nullptr;
     if (try_span) {
         int done = 0;
         FBG_TRY(fbg_span_try(ctx, keysB, valsB, g, &done));
@@ -1048,7 +1032,7 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     int pp = 0;
     uint64_t h = (uint64_t)K;
     uint64_t dirty_cnt = 0;
-    ctx->lcp_from_keys = false;
+    ctx->ix.lcp_from_keys = false;
     uint64_t *dkeys_in = keysA, *dkeys_out = nullptr;
     for (int round = 1;; round++) {
         // select unresolved members of the current list
@@ -1072,8 +1056,8 @@ int fbg_suffix_sort(fbg_ctx *ctx)
         if (round == 1) {
             // few ties: the key-derived LCPs stand, only the tie groups are patched afterwards;
             // the round-0 keys (keysB) must then survive the doubling rounds
-            ctx->lcp_from_keys = hc <= N / 32 && !ctx->opt.lcp_text;
-            if (ctx->lcp_from_keys && hc > 0) {
+            ctx->ix.lcp_from_keys = hc <= N / 32 && !ctx->opt.lcp_text;
+            if (ctx->ix.lcp_from_keys && hc > 0) {
                 dirty_cnt = hc;
                 FBG_TRY(fbg_reserve(ctx, ctx->io_d, hc * 4));
                 FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->io_d.p, sel, hc * 4, hipMemcpyDeviceToDevice, st));
@@ -1119,12 +1103,13 @@ int fbg_suffix_sort(fbg_ctx *ctx)
         pp ^= 1;
         h *= 2;
     }
-    if (ctx->lcp_from_keys && dirty_cnt > 0) {
+    if (ctx->ix.lcp_from_keys && dirty_cnt > 0) {
         hipLaunchKernelGGL(k_fix_dirty, dim3(fbg_blocks(dirty_cnt, 256)), dim3(256), 0, st, ctx->io_d.as<uint32_t>(),
                            dirty_cnt, sa, keysB, T, N, b, key_bits, K, ct, rec);
         launches += 1;
     }
     FBG_HIP_TRY(ctx, hipGetLastError());
+    ctx->ix.kind = IndexKind::record;          // the index is the records by text position
     return fbg_stage_end(ctx, FBG_STAGE_SUFFIX_SORT, launches);
 }
 
@@ -1141,8 +1126,7 @@ int fbg_part_sort(fbg_ctx *ctx, int part, int nparts, uint8_t *d_blob, int *ok)
     int launches = 0;
     const uint8_t *T = ctx->text.as<uint8_t>();
     KeyGeom g;
-    ctx->granked = false; ctx->gpart = false;
-    ctx->grs_ebits = nullptr; ctx->grs_flagged = false;
+    SortExtras x;
     int pre_ok = ctx->gapfree && !ctx->have_ignore && !ctx->opt.no_ranked;
     FBG_TRY(fbg_key_setup(ctx, pre_ok != 0, &g, &launches));
     pre_ok = pre_ok && g.compact;
@@ -1150,7 +1134,7 @@ int fbg_part_sort(fbg_ctx *ctx, int part, int nparts, uint8_t *d_blob, int *ok)
     // scanned by gapped_rank.hip
     const bool gapped = (!ctx->gapfree || ctx->have_ignore) && !ctx->reversed && ctx->opt.gapped_rank != -1 && !g.compact && g.K <= 32 &&
                         N < (1ull << 32);
-    if (gapped) FBG_TRY(fbg_grs_prepare(ctx, &launches));
+    if (gapped) FBG_TRY(fbg_grs_prepare(ctx, &x.ebits, &launches));
     if (pre_ok) {
         // similar rows tie almost everywhere: not for the slot-level scan of the partitions (every rank draws the same
         // sample and declines alike); the caller builds the whole index, whose group-level scan is made for them
@@ -1158,7 +1142,7 @@ int fbg_part_sort(fbg_ctx *ctx, int part, int nparts, uint8_t *d_blob, int *ok)
         FBG_TRY(sample_says_similar(ctx, g, &similar, &launches));
         if (similar) pre_ok = 0;
     }
-    ctx->part = part; ctx->nparts = nparts; ctx->part_active = true;
+    ctx->ix.part = part; ctx->ix.nparts = nparts; ctx->ix.part_active = true;
     uint64_t count = 0;
     // splitters: quantiles of a sorted key sample -- the same on every rank, ties never straddle a boundary
     uint64_t S = N / 64;
@@ -1196,8 +1180,7 @@ int fbg_part_sort(fbg_ctx *ctx, int part, int nparts, uint8_t *d_blob, int *ok)
             pa.T = T; pa.N = N; pa.code = g.d_code; pa.b = g.b; pa.K = g.K; pa.pb = g.pb;
             pa.keys = ctx->keysA.as<uint64_t>(); pa.vals = ctx->valsA.as<uint32_t>();
             pa.lo = lo; pa.hi = hi; pa.cap = cap; pa.nohi = part + 1 >= nparts; pa.counter = d_count;
-            pa.ebits = gapped ? ctx->grs_ebits : nullptr;
-            launch_pack(ctx, g, true, pa);
+            launch_pack(ctx, g, true, pa, x);
             launches++;
             unsigned long long hc = 0;
             FBG_HIP_TRY(ctx, hipMemcpyAsync(&hc, d_count, 8, hipMemcpyDeviceToHost, st));
@@ -1210,8 +1193,7 @@ int fbg_part_sort(fbg_ctx *ctx, int part, int nparts, uint8_t *d_blob, int *ok)
     const uint64_t slots = count + 2 * FBG_PART_HALO;
     FBG_TRY(fbg_reserve(ctx, ctx->keysB, slots * 8));
     if (!g.packed) FBG_TRY(fbg_reserve(ctx, ctx->valsB, slots * 4));
-    if ((pre_ok || gapped) && !msd_ok && count > 0) FBG_TRY(sort_slots(ctx, g, count, FBG_PART_HALO));
-    ctx->grs_ebits = nullptr;
+    if ((pre_ok || gapped) && !msd_ok && count > 0) FBG_TRY(sort_slots(ctx, g, false, count, FBG_PART_HALO));
     FBG_HIP_TRY(ctx, hipGetLastError());
     FBG_TRY(fbg_stage_end(ctx, FBG_STAGE_SUFFIX_SORT, launches));
     if (gapped)

@@ -1391,6 +1391,38 @@ def test_span_scan_matches_oracle(engine, case, key_flags):
                 assert bad.size == 0, (case, ignore, tricks_off, bad[:8].tolist(), got[bad[:8]].tolist(), ref[bad[:8]].tolist())
 
 
+def test_one_engine_builds_every_index_kind_in_sequence():
+    """One Engine builds, one after the other, a span-scan index with the flags in the key words, a gapped index, a
+    gap-free rank-order index and a record-path index: what a build leaves in the context (which index it holds, how
+    its sort laid the slots out) must not reach the next one.  Every f against the oracle (fbg.cpp:1579-1695), every
+    index_kind against the kind the options ask for."""
+    import torch
+    import founderblockgraphs_amd as F
+    star = star_msa(np.random.default_rng(9100), 16, 1200, gap_cells=0.03, gap_run=7)
+    gapped = random_msa(np.random.default_rng(9101), 12, 900, gap_p=0.02, gap_run=5, n_p=0.01)
+    gapfree = random_msa(np.random.default_rng(9102), 24, 700)
+    steps = [("span", star, "", {"span_scan": 1, "span_key_flags": 1}, 2, 1),
+             ("gapped", gapped, "N", {"span_scan": -1}, 2, 0),
+             ("ranked", gapfree, "", {}, 1, 0),
+             ("record", gapfree, "", {"no_ranked": 1}, 0, 0)]
+    with F.Engine(0) as eng:
+        for name, msa, ignore, opts, kind, span in steps:
+            n = msa.shape[1]
+            want = O.compute_f(msa, ignore=ignore)
+            with fbg_options(eng, opts):
+                eng.msa_load_host(msa)
+                eng.index_build(ignorechars=ignore)
+                assert eng.get_option("index_kind") == kind, name
+                assert eng.get_option("span_scan_used") == span and eng.get_option("span_key_flags_used") == span, name
+                d = torch.zeros(n, dtype=torch.int64, device="cuda")
+                torch.cuda.synchronize()
+                eng.scan_f(0, n, d.data_ptr(), False)
+                eng.sync()
+            got = d.cpu().numpy().astype(np.uint64)
+            bad = np.flatnonzero(got != want)
+            assert bad.size == 0, (name, bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())
+
+
 def test_span_scan_large_groups_by_chains(engine):
     """Groups of more than 1024 members through the chains along the later keys' groups (option span_scan = 3: the path
     the large instances of k_sp_odd_pairs replaced as the default) -- same f (fbg.cpp:1579-1695)."""
