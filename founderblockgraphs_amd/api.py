@@ -309,6 +309,46 @@ class Engine:
         self._pindexes.add(pix)
         return pix
 
+    def pattern_index_of_segmentation(self, boundaries):
+        """Pattern index of the graph that `boundaries` cuts out of the current MSA, built on the device
+        (fbg_pindex_build_segmentation): the index pattern_index(*graph_from_segmentation(...)) gives, without the trip
+        of nodes, edges and labels through the host.  node_block / first_node: the block of every node, the first
+        node of every block."""
+        b = np.ascontiguousarray(boundaries, dtype=np.uint64)
+        h = C.c_void_p()
+        self._chk(self._L.fbg_pindex_build_segmentation(self._h, _u64(b), len(b), C.byref(h)))
+        pix = PatternIndex._adopt(self, h, len(b))
+        if not hasattr(self, "_pindexes"):
+            self._pindexes = weakref.WeakSet()
+        self._pindexes.add(pix)
+        return pix
+
+    def validate_segmentation(self, boundaries, ignorechars=""):
+        """Semi-repeat-free check of the graph of a segmentation of the current MSA (fbg_segmentation_validate)
+        -> SegmentationCheck: cut_bad uint8[nb] (1: the block after this boundary holds an INVALID node), bad_cuts
+        (their indices, the reference's to_remove), n_nodes, n_invalid, valid, device_ms."""
+        b = np.ascontiguousarray(boundaries, dtype=np.uint64)
+        ig, il = _ignore(ignorechars)
+        cut = np.zeros(max(len(b), 1), dtype=np.uint8)
+        nn, bad, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        self._chk(self._L.fbg_segmentation_validate(self._h, _u64(b), len(b), _u8(ig), il, _u8(cut), C.byref(nn), C.byref(bad),
+                                                    C.byref(ms)))
+        return SegmentationCheck(cut[:len(b)], nn.value, bad.value, ms.value)
+
+    def repair_segmentation(self, boundaries, ignorechars="", timing=None):
+        """The repair loop of the row-chunk mode (fbg_segmentation_repair; fbg.cpp:3471-3497): validate, drop the
+        boundaries before blocks that hold an INVALID node, repeat -> (boundaries, rounds, removed), removed the
+        count of dropped boundaries per round.  timing: a dict that receives device_ms."""
+        b = np.ascontiguousarray(boundaries, dtype=np.uint64).copy()
+        ig, il = _ignore(ignorechars)
+        nb, rounds, ms = C.c_uint64(len(b)), C.c_uint64(0), C.c_double(0)
+        removed = np.zeros(max(len(b), 1), dtype=np.uint64)
+        self._chk(self._L.fbg_segmentation_repair(self._h, _u64(b), C.byref(nb), _u8(ig), il, C.byref(rounds), _u64(removed),
+                                                  C.byref(ms)))
+        if timing is not None:
+            timing["device_ms"] = ms.value
+        return b[:nb.value].copy(), int(rounds.value), [int(x) for x in removed[:rounds.value]]
+
     def validate_graph(self, labels, edges, blocks, ignorechars=""):
         """Semi-repeat-free check of a founder graph (PatternIndex.validate on a temporary index of the graph)."""
         with self.pattern_index(labels, edges) as pix:
@@ -353,6 +393,22 @@ class PatternIndex:
         self._h = h
         self.n_nodes = n
         self._label_len = np.diff(loff.astype(np.int64))
+
+    @classmethod
+    def _adopt(cls, engine, handle, nb):
+        """An index the library built from a segmentation: label lengths and blocks come from the device."""
+        self = cls.__new__(cls)
+        self._eng, self._L, self._h = engine, engine._L, handle
+        n = int(self._L.fbg_pindex_node_count(handle))
+        self.n_nodes = n
+        ll = np.zeros(max(n, 1), dtype=np.uint32)
+        blk = np.zeros(max(n, 1), dtype=np.uint32)
+        first = np.zeros(nb + 1, dtype=np.uint64)
+        engine._chk(self._L.fbg_pindex_node_info(handle, ll.ctypes.data_as(_lib.u32p), blk.ctypes.data_as(_lib.u32p), _u64(first)))
+        self._label_len = ll[:n].astype(np.int64)
+        self.node_block = blk[:n].astype(np.int64)
+        self.first_node = first
+        return self
 
     def close(self):
         if getattr(self, "_h", None):
@@ -529,6 +585,18 @@ class Validation:
         """{valid, invalid, source_sink, ignored, empty}: nodes per status."""
         c = np.bincount(self.status, minlength=5)
         return dict(zip(("valid", "invalid", "source_sink", "ignored", "empty"), (int(x) for x in c[:5])))
+
+
+class SegmentationCheck:
+    """Result of Engine.validate_segmentation: cut_bad uint8[nb], bad_cuts int64 (indices of the flagged boundaries,
+    ascending), n_nodes, n_invalid, valid (nothing flagged), device_ms."""
+
+    def __init__(self, cut_bad, n_nodes, n_invalid, device_ms):
+        self.cut_bad = cut_bad
+        self.bad_cuts = np.nonzero(cut_bad)[0].astype(np.int64)
+        self.n_nodes, self.n_invalid = int(n_nodes), int(n_invalid)
+        self.valid = len(self.bad_cuts) == 0
+        self.device_ms = device_ms
 
 
 def read_xgfa(path, blocks=False):
@@ -718,6 +786,28 @@ def segment_elastic_minmaxlength(MSA, ignorechars="", disable_efg_tricks=False, 
         if not segment:
             return None, f
         return eng.minmax_dp(f), f
+    finally:
+        if engine is None:
+            eng.close()
+
+
+def segment_elastic_heuristic(MSA, rows, ignorechars="", disable_efg_tricks=False, engine=None):
+    """The row-chunk mode, --heuristic-subset=ROWNUM (fbg.cpp:3400-3433, 3467-3500): f of every chunk of `rows`
+    consecutive rows max-merged, the min-max-length DP on the merged f, then the repair loop on the graph of the whole
+    MSA.  Returns (boundaries, f, rounds, removed).  NoSegmentation as a chunk raises it (disable_efg_tricks only)."""
+    MSA = as_msa(MSA)
+    rows = int(rows)
+    if rows <= 0:
+        raise ValueError("rows must be positive")
+    eng = engine or Engine()
+    try:
+        f = None
+        for r in range(0, MSA.shape[0], rows):
+            f = eng.elastic_f(MSA[r:r + rows], ignorechars, disable_efg_tricks, f)
+        b = eng.minmax_dp(f)
+        eng.msa_load_host(MSA)
+        b, rounds, removed = eng.repair_segmentation(b, ignorechars)
+        return b, f, rounds, removed
     finally:
         if engine is None:
             eng.close()

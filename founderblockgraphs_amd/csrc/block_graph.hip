@@ -210,13 +210,11 @@ __global__ void k_bg_widen(const uint32_t *__restrict__ c, unsigned long long *_
     if (i < cnt) w[i] = c[i];
 }
 
-int fbg_block_graph(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, uint32_t *node_of, uint64_t *first_node,
-                    uint32_t *rep_row, uint64_t *edge_count, uint64_t *edges)
+// The device stage of fbg_block_graph: everything up to the copy-out.  The arrays stay in the context's dp_* / io_a
+// workspaces (valid until the next call that uses them); *g says where.  A hash collision is reported in g->collision,
+// not as an error: the caller decides (fbg_block_graph copies out first, as it always did).
+int fbg_block_graph_device(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, BlockGraphDev *g)
 {
-    if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_block_graph: no MSA set");
-    if (!boundaries || nb == 0 || !node_of || !first_node || !rep_row || !edge_count || !edges)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_block_graph: bad arguments");
     const uint64_t m = ctx->m, n = ctx->n;
     if (m * nb >= (1ull << 32)) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_block_graph: more than 2^32 (row, block) cells");
     if (m > FBG_MAX_ROWS) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_block_graph: more than %d rows", FBG_MAX_ROWS);
@@ -285,17 +283,37 @@ int fbg_block_graph(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, uint3
     }
     hipLaunchKernelGGL(k_block_edges, dim3(wgs), dim3(BG_THREADS), in_lds ? (size_t)cap * 8 : 0, st, a, cap, scratch2);
     hipLaunchKernelGGL(k_block_globalize, dim3(fbg_blocks(cells, 256)), dim3(256), 0, st, a);
-    unsigned long long h_flag = 0;
+    unsigned long long h_flag = 0, h_nodes = 0;
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_flag, a.flag, 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(first_node, first, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(edge_count, a.edge_count, nb * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_nodes, first + nb, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    g->bounds = a.bounds; g->node_of = a.node_of; g->rep_row = a.rep_row; g->count = a.count;
+    g->first = first; g->edge_count = a.edge_count; g->edges = a.edges;
+    g->n_nodes = h_nodes;
+    g->collision = h_flag != 0;
+    return FBG_OK;
+}
+
+int fbg_block_graph(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, uint32_t *node_of, uint64_t *first_node,
+                    uint32_t *rep_row, uint64_t *edge_count, uint64_t *edges)
+{
+    if (!ctx) return FBG_ERR_INVALID;
+    if (!ctx->d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_block_graph: no MSA set");
+    if (!boundaries || nb == 0 || !node_of || !first_node || !rep_row || !edge_count || !edges)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_block_graph: bad arguments");
+    BlockGraphDev g;
+    FBG_TRY(fbg_block_graph_device(ctx, boundaries, nb, &g));
+    hipStream_t st = ctx->stream;
+    const uint64_t cells = ctx->m * nb;
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(first_node, g.first, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(edge_count, g.edge_count, nb * 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     // the three per-(row, block) arrays are hundreds of MB at a million columns: pinned bounce buffers, several threads
-    FBG_TRY(fbg_download(ctx, node_of, a.node_of, cells * 4));
-    FBG_TRY(fbg_download(ctx, rep_row, a.rep_row, cells * 4));
-    FBG_TRY(fbg_download(ctx, edges, a.edges, cells * 8));
+    FBG_TRY(fbg_download(ctx, node_of, g.node_of, cells * 4));
+    FBG_TRY(fbg_download(ctx, rep_row, g.rep_row, cells * 4));
+    FBG_TRY(fbg_download(ctx, edges, g.edges, cells * 8));
     FBG_HIP_TRY(ctx, hipGetLastError());
-    if (h_flag != 0)
+    if (g.collision)
         return fbg_fail(ctx, FBG_ERR_HASH_COLLISION, "two different block labels share a 128-bit hash; use the host-side numbering");
     return FBG_OK;
 }

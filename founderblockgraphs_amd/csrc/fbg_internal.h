@@ -288,6 +288,16 @@ int fbg_scan_columns(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disab
                      uint64_t *d_out);                                        // scan.hip
 int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_boundaries,
                   uint64_t *count_out, uint64_t *d_mml, uint64_t *d_bt);      // dp.hip
+// block_graph.hip: where the device stage of fbg_block_graph left the graph of a segmentation (the context's dp_* / io_a
+// workspaces).  edges: edge_count[j] sorted distinct (source << 32 | destination) at edges[j * m ..], global node numbers.
+struct BlockGraphDev {
+    const uint64_t *bounds = nullptr;              // [nb]
+    const uint32_t *node_of = nullptr, *rep_row = nullptr, *count = nullptr;   // [nb * m], [nb * m], [nb]
+    const unsigned long long *first = nullptr, *edge_count = nullptr, *edges = nullptr;   // [nb + 1], [nb], [nb * m]
+    uint64_t n_nodes = 0;
+    bool collision = false;                        // two different labels share a hash: the numbering is not to be used
+};
+int fbg_block_graph_device(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, BlockGraphDev *g);
 int fbg_dp_repeatfree(fbg_ctx *ctx, const uint64_t *d_v, uint64_t n, uint64_t *d_s,
                       uint64_t *d_prev, uint64_t *d_boundaries, uint64_t *count_out);
 int fbg_gapped_v_from_f(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_v);

@@ -1,6 +1,7 @@
 #include "fasta.hpp"
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <iostream>
 #include <string_view>
@@ -109,5 +110,39 @@ bool read_msa(const std::string &path, long gap_limit, bool elastic, bool output
     finish_record();
     msa.m = rows;
     msa.n = rows == 0 ? 0 : expected;
+    return true;
+}
+
+bool read_msa_strict(const std::string &path, bool output_paths, Msa &msa)
+{
+    std::ifstream fs(path, std::ios::binary);
+    if (!fs) return false;
+    msa.cells.clear();
+    msa.m = msa.n = 0;
+    std::string line, entry;
+    if (!std::getline(fs, line)) return false;                 // the first line is taken as a header (fbg.cpp:214)
+    if (output_paths) msa.identifiers.push_back(line.empty() ? line : line.substr(1));
+    bool first = true;
+    std::size_t expected = 0;
+    auto finish_record = [&]() {
+        if (first) { expected = entry.size(); first = false; }
+        if (entry.size() != expected) {                                                                      // 231-235, 253-257
+            std::cerr << "MSA rows have mismatching size!" << std::endl;
+            std::exit(1);
+        }
+        msa.cells.insert(msa.cells.end(), entry.begin(), entry.end());
+        msa.m++;
+        entry.clear();
+    };
+    while (std::getline(fs, line)) {
+        if (!line.empty() && line[0] == '>') {
+            if (output_paths) msa.identifiers.push_back(line.substr(1));
+            finish_record();
+        } else {
+            entry += line;
+        }
+    }
+    finish_record();
+    msa.n = expected;
     return true;
 }

@@ -12,7 +12,9 @@
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <set>
 #include <string>
+#include <unordered_map>
 #include <vector>
 #include "../../../include/fbg_hip.h"
 #include "fasta.hpp"
@@ -32,6 +34,72 @@ void write_empty_graphviz(const std::string &path)
     // output_graphviz (fbg.cpp:3043-3092) receives empty node/edge vectors in elastic mode
     std::ofstream os(path);
     os << "digraph founder_block_graph {\n" << "rankdir=\"LR\"\n" << "}\n";
+}
+
+// The repair loop (fbg.cpp:3471-3497) for inputs fbg_segmentation_repair declines: labels are cut out of the MSA and
+// numbered here as output_efg does (per block a map label -> id by first row, a set of edges), the check itself is
+// fbg_pindex_build + fbg_pindex_validate, once per round.
+int repair_on_host(fbg_ctx *ctx, const Msa &msa, std::vector<uint64_t> &boundaries, const std::string &ignore_chars,
+                   uint64_t &rounds, std::vector<uint64_t> &removed)
+{
+    rounds = 0;
+    removed.assign(boundaries.size(), 0);
+    for (;;) {
+        const uint64_t nb = boundaries.size();
+        std::string labels;
+        std::vector<uint64_t> label_off{0}, edge_off{0}, edge_dst;
+        std::vector<uint32_t> node_block;
+        std::vector<std::set<uint64_t>> out;                  // distinct out-neighbours per node
+        std::vector<int64_t> prev(msa.m, -1), cur(msa.m, -1);
+        for (uint64_t j = 0; j < nb; j++) {
+            const uint64_t x0 = j ? boundaries[j - 1] + 1 : 0, x1 = std::min(boundaries[j] + 1, msa.n);
+            std::unordered_map<std::string, uint64_t> ids;
+            for (uint64_t i = 0; i < msa.m; i++) {
+                std::string lab;
+                for (uint64_t x = x0; x < x1; x++)
+                    if (msa.cells[i * msa.n + x] != '-') lab.push_back((char)msa.cells[i * msa.n + x]);
+                cur[i] = -1;
+                if (lab.empty()) continue;                    // a row of gaps has no node in this block
+                auto it = ids.find(lab);
+                if (it == ids.end()) {
+                    it = ids.emplace(lab, node_block.size()).first;
+                    labels += lab;
+                    label_off.push_back(labels.size());
+                    node_block.push_back((uint32_t)j);
+                    out.emplace_back();
+                }
+                cur[i] = (int64_t)it->second;
+                if (j && prev[i] >= 0) out[(size_t)prev[i]].insert(it->second);
+            }
+            std::swap(prev, cur);
+        }
+        const uint64_t n_nodes = node_block.size();
+        for (uint64_t u = 0; u < n_nodes; u++) {
+            edge_dst.insert(edge_dst.end(), out[u].begin(), out[u].end());
+            edge_off.push_back(edge_dst.size());
+        }
+        edge_dst.push_back(0);
+        labels.push_back('\0');
+        fbg_pindex *ix = nullptr;
+        int rc = fbg_pindex_build(ctx, reinterpret_cast<const uint8_t *>(labels.data()), label_off.data(), n_nodes, edge_off.data(),
+                                  edge_dst.data(), &ix);
+        if (rc != FBG_OK) return rc;
+        std::vector<uint8_t> status(n_nodes + 1);
+        rc = fbg_pindex_validate(ix, node_block.data(), reinterpret_cast<const uint8_t *>(ignore_chars.data()), ignore_chars.size(),
+                                 status.data(), nullptr, nullptr, nullptr, nullptr);
+        fbg_pindex_destroy(ix);
+        if (rc != FBG_OK) return rc;
+        std::vector<bool> cut(nb, false);
+        for (uint64_t u = 0; u < n_nodes; u++)
+            if (status[u] == FBG_NODE_INVALID && node_block[u] > 0) cut[node_block[u] - 1] = true;
+        const uint64_t flagged = (uint64_t)std::count(cut.begin(), cut.end(), true);
+        if (!flagged) return FBG_OK;
+        removed[rounds++] = flagged;
+        std::vector<uint64_t> kept;
+        for (uint64_t k = 0; k < nb; k++)
+            if (!cut[k]) kept.push_back(boundaries[k]);
+        boundaries.swap(kept);
+    }
 }
 
 } // namespace
@@ -55,8 +123,10 @@ int main(int argc, char **argv)
         std::cerr << "wrong value for --heuristic-subset!\n";
         return EXIT_FAILURE;
     }
-    if (opt.heuristic_subset != -1) {
-        std::cerr << "--heuristic-subset (hidden, non-optimal row-chunk mode) is not provided by this build.\n";
+    const bool heuristic = opt.heuristic_subset != -1;
+    if (heuristic && !(opt.elastic && opt.gfa)) {
+        // the reference goes on to segment() with an MSA it never read (fbg.cpp:3347-3366, 3437): undefined
+        std::cerr << "--heuristic-subset needs --elastic and --gfa: the row-chunk mode is defined for the elastic xGFA output only.\n";
         return EXIT_FAILURE;
     }
 
@@ -72,7 +142,9 @@ int main(int argc, char **argv)
     };
 
     Msa msa;
-    if (!read_msa(opt.input, opt.gap_limit, opt.elastic, opt.output_paths, msa) || msa.m == 0 || msa.n == 0) {
+    const bool have_input = heuristic ? read_msa_strict(opt.input, opt.output_paths, msa)                     // 3363
+                                      : read_msa(opt.input, opt.gap_limit, opt.elastic, opt.output_paths, msa);
+    if (!have_input || msa.m == 0 || msa.n == 0) {
         std::cerr << "Unable to read sequences from the input\n.";                                          // 3353
         return EXIT_FAILURE;
     }
@@ -120,7 +192,50 @@ int main(int argc, char **argv)
 
     lap("open the GPU engine");
     std::vector<uint64_t> boundaries;
-    if (opt.elastic) {
+    const uint8_t *ignore = reinterpret_cast<const uint8_t *>(opt.ignore_chars.data());
+    if (heuristic) {
+        // fbg.cpp:3400-3433: f of every chunk of ROWNUM consecutive rows, max-merged (1681); the sweep on the merged f.
+        // Chunks are small: they run on member 0.  --threads only spreads the reference's chunks over workers; the
+        // merge is a max, so the result does not depend on it.
+        std::vector<uint64_t> f(msa.n, 0);                                                                   // 3388
+        const uint64_t R = (uint64_t)opt.heuristic_subset;
+        for (uint64_t r0 = 0; r0 < msa.m; r0 += R) {
+            const uint64_t rows = std::min<uint64_t>(R, msa.m - r0);
+            std::cerr << "Reading MSA[" << r0 << ".." << r0 + R - 1 << "]..." << std::endl;                  // 271
+            rc = fbg_elastic_f(ctx, msa.cells.data() + r0 * msa.n, rows, msa.n, ignore, opt.ignore_chars.size(),
+                               opt.disable_elastic_tricks ? 1 : 0, f.data());
+            std::cerr << "MSA index construction complete, index requires "
+                      << (double)fbg_device_bytes(ctx) / (1024.0 * 1024.0) << " MiB." << std::endl;          // 3410
+            if (rc == FBG_ERR_NO_SEGMENTATION) { std::cerr << "No valid segmentation found!\n"; close_engine(); std::exit(1); }
+            if (rc != FBG_OK) return engine_failure(ctx, "fbg_elastic_f", rc);
+        }
+        std::cerr << "Computing optimal segmentation..." << std::flush;                                     // 1958
+        boundaries.resize(msa.n + 1);
+        uint64_t count = 0;
+        std::vector<uint64_t> mml(msa.n + 1);
+        rc = fbg_minmax_dp(ctx, f.data(), msa.n, boundaries.data(), &count, mml.data(), nullptr);
+        if (rc != FBG_OK) return engine_failure(ctx, "fbg_minmax_dp", rc);
+        boundaries.resize(count);
+        std::cerr << "done (optimal segment length = " << mml[msa.n] << ")." << std::endl;                   // 2023
+        lap("chunked scan and sweep");
+        // fbg.cpp:3467-3498: the graph of this segmentation is in general not semi-repeat-free; repair it
+        rc = fbg_msa_load_host(ctx, msa.cells.data(), msa.m, msa.n);
+        if (rc != FBG_OK) return engine_failure(ctx, "fbg_msa_load_host", rc);
+        uint64_t nb = boundaries.size(), rounds = 0;
+        std::vector<uint64_t> removed(nb);
+        rc = fbg_segmentation_repair(ctx, boundaries.data(), &nb, ignore, opt.ignore_chars.size(), &rounds, removed.data(), nullptr);
+        if (rc == FBG_ERR_HASH_COLLISION || rc == FBG_ERR_TOO_LARGE) {
+            // block grouping declined (a hash collision, more rows than it takes): labels cut and numbered here
+            rc = repair_on_host(ctx, msa, boundaries, opt.ignore_chars, rounds, removed);
+            if (rc != FBG_OK) return engine_failure(ctx, "the repair of the segmentation", rc);
+        } else {
+            if (rc != FBG_OK) return engine_failure(ctx, "fbg_segmentation_repair", rc);
+            boundaries.resize(nb);
+        }
+        for (uint64_t r = 0; r < rounds; r++) std::cerr << "There are " << removed[r] << " blocks to remove" << std::endl;   // 3476-3480
+        std::cerr << "There are 0 blocks to remove" << std::endl;
+        std::cerr << "Graph fixed in " << rounds << "iterations\xe2\x80\xa6\n";                             // 3498
+    } else if (opt.elastic) {
         std::vector<uint64_t> f(msa.n, 0);                                                                   // 3388
         rc = fbg_group_elastic_f(grp, msa.cells.data(), msa.m, msa.n,
                                  reinterpret_cast<const uint8_t *>(opt.ignore_chars.data()), opt.ignore_chars.size(),

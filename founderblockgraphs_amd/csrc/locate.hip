@@ -21,7 +21,11 @@
 //                                    reported place: SA slot -> (edge source, edge destination, offset);
 //   k_pv_node / k_pv_wave            the semi-repeat-free check (fbg_pindex_validate): the SA range of every label,
 //                                    kept from the B / E walk, scanned against the block of each occurrence's node,
-//                                    one lane per short range and one wave per long one.
+//                                    one lane per short range and one wave per long one;
+//   k_ps_*                           the index of a segmentation's graph without the host (fbg_pindex_build_segmentation):
+//                                    labels gathered from the resident MSA, edges, validation tables and the byte
+//                                    histogram from the device stage of fbg_block_graph ("prepare from a segmentation");
+//   k_sv_cuts                        the cuts before blocks that hold an INVALID node (fbg_segmentation_validate / _repair).
 //
 // occ layout.  Symbols are remapped to dense codes in byte order (the sentinel is code 0, '#' code 1).  With at
 // most 16 codes a block of 128 BWT positions is one 128-byte line:
@@ -62,6 +66,12 @@ struct fbg_pindex {
     // coarse table of the edge at every 2^PV_CSHIFT-th text position
     DevBuf vrng, vtpos, vlen, vflag, vestart, vesrc, vedst, vctab;
     DevBuf vblock, vstatus, vwn, vwo, vlist, vctr;      // validation scratch, kept between calls
+    // an index built from a segmentation (fbg_pindex_build_segmentation) keeps the block of every node and the first
+    // node of every block; scut / sctr: the flagged cuts and the INVALID count of fbg_segmentation_validate
+    DevBuf snode_block, sfirst, scut, sctr;
+    bool from_segmentation = false;
+    uint64_t seg_nb = 0;
+    hipEvent_t sv0 = nullptr, sv1 = nullptr;
     // fbg_pindex_occurrences: per pattern the walk's record (3 x uint2), totals, capped sizes and their scans, what
     // the expansion reads (first slot of either list, k or |P|, restarts), and the places of the last fetch
     DevBuf orec, oetot, ostot, oesz, ossz, oeoff, osoff, ors, oel, oss, osk, oplace;
@@ -419,8 +429,17 @@ static PxDev px_dev(const fbg_pindex *ix)
 struct PxScratch {
     DevBuf labels, loff, elen, eoff, keysA, keysB, valsA, valsB, cidx, cidx2, rank, headv, hscan, head, keep,
            cntT, cntX, code_u8, count;
+    DevBuf nrow, len64, ebase, firstE, nout, nin, hist;     // px_prepare_segmentation
     std::vector<DevBuf *> bufs;
     ~PxScratch() { fbg_release_all(nullptr, bufs); }
+};
+
+// What a prepare step hands to px_build_prepared, besides the device arrays it filled: labels (padded) and loff in the
+// scratch; vesrc, vedst, vestart, vtpos, vlen, vflag in the index.
+struct PxPrep {
+    uint64_t n_nodes = 0, E = 0, N1 = 1;
+    uint64_t hist[256] = {0};      // bytes of the text: the sentinel, E times '#', every label byte once per edge of its node
+    bool eoff_ready = false;       // scratch.eoff already holds the text offset of every edge
 };
 
 struct PxMul {
@@ -428,8 +447,10 @@ struct PxMul {
     __host__ __device__ uint64_t operator()(uint64_t s) const { return s * m; }
 };
 
-static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
-                    const uint64_t *edge_off, const uint64_t *edge_dst)
+// Prepare from host arrays (fbg_pindex_build): checks, distinct sorted edges, the validation tables and the byte
+// histogram in serial host loops, then the upload.
+static int px_prepare_host(fbg_pindex *ix, PxScratch &s, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
+                           const uint64_t *edge_off, const uint64_t *edge_dst, PxPrep &pp)
 {
     fbg_ctx *ctx = ix->ctx;
     hipStream_t st = ctx->stream;
@@ -483,30 +504,13 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
         const uint64_t len = label_off[u + 1] - label_off[u];
         vlen[u] = len > 0xffffffffull ? 0xffffffffu : (uint32_t)len;   // only nodes with edges are read (< N1)
     }
-    uint64_t hist[256] = {0};
+    uint64_t *hist = pp.hist;
     hist[0] = 1;
     hist['#'] = E;
     for (uint64_t u = 0; u < n_nodes; u++)
         if (use[u])
             for (uint64_t k = label_off[u]; k < label_off[u + 1]; k++) hist[labels[k]] += use[u];
-    uint16_t code[256];
-    uint8_t code_u8[256];
-    uint32_t C[256];
-    int sigma = 0;
-    uint64_t acc = 0;
-    for (int c = 0; c < 256; c++) {
-        code[c] = hist[c] ? (uint16_t)sigma : (uint16_t)PX_ABSENT;
-        code_u8[c] = hist[c] ? (uint8_t)sigma : 0;
-        if (hist[c]) { C[sigma] = (uint32_t)acc; acc += hist[c]; sigma++; }
-    }
-    for (int s = sigma; s < 256; s++) C[s] = (uint32_t)acc;
-    ix->N1 = N1;
-    ix->sigma = sigma;
-    ix->compact = sigma <= 16;
-    ix->n_nodes = n_nodes;
-    ix->nblk = N1 / PX_BLK + 1;
-
-    PxScratch s;
+    pp.n_nodes = n_nodes; pp.E = E; pp.N1 = N1;
     auto U = [&](std::vector<DevBuf *> &owner, DevBuf &b, const void *h, size_t bytes) -> int {
         FBG_TRY(fbg_reserve(ctx, b, bytes + 8, &owner, false));
         if (bytes) FBG_HIP_TRY(ctx, hipMemcpyAsync(b.p, h, bytes, hipMemcpyHostToDevice, st));
@@ -524,6 +528,41 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     FBG_TRY(U(ix->bufs, ix->vtpos, vtpos.data(), n_nodes * 4));
     FBG_TRY(U(ix->bufs, ix->vlen, vlen.data(), n_nodes * 4));
     FBG_TRY(U(ix->bufs, ix->vflag, vflag.data(), n_nodes));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));        // the vectors above end with this function
+    return FBG_OK;
+}
+
+// Build from prepared device arrays, shared by both entry points: symbol tables from the histogram, the text, the
+// suffix array, the occ lines, B / E and the label ranges.
+static int px_build_prepared(fbg_pindex *ix, PxScratch &s, const PxPrep &pp)
+{
+    fbg_ctx *ctx = ix->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t n_nodes = pp.n_nodes, E = pp.E, N1 = pp.N1;
+    const uint64_t *hist = pp.hist;
+    uint16_t code[256];
+    uint8_t code_u8[256];
+    uint32_t C[256];
+    int sigma = 0;
+    uint64_t acc = 0;
+    for (int c = 0; c < 256; c++) {
+        code[c] = hist[c] ? (uint16_t)sigma : (uint16_t)PX_ABSENT;
+        code_u8[c] = hist[c] ? (uint8_t)sigma : 0;
+        if (hist[c]) { C[sigma] = (uint32_t)acc; acc += hist[c]; sigma++; }
+    }
+    for (int s = sigma; s < 256; s++) C[s] = (uint32_t)acc;
+    ix->N1 = N1;
+    ix->sigma = sigma;
+    ix->compact = sigma <= 16;
+    ix->n_nodes = n_nodes;
+    ix->nblk = N1 / PX_BLK + 1;
+    ix->occ_ready = false;
+
+    auto U = [&](std::vector<DevBuf *> &owner, DevBuf &b, const void *h, size_t bytes) -> int {
+        FBG_TRY(fbg_reserve(ctx, b, bytes + 8, &owner, false));
+        if (bytes) FBG_HIP_TRY(ctx, hipMemcpyAsync(b.p, h, bytes, hipMemcpyHostToDevice, st));
+        return FBG_OK;
+    };
     FBG_TRY(fbg_reserve(ix->ctx, ix->vrng, n_nodes * 8, &ix->bufs, false));
     ix->n_edges = E;
     ix->nctab = ((N1 - 1) >> PV_CSHIFT) + 2;
@@ -538,14 +577,18 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     FBG_TRY(fbg_reserve(ix->ctx, ix->text, N1 + 64, &ix->bufs, false));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ix->text.p, 0, ix->text.cap, st));
     if (E) {
-        FBG_TRY(fbg_reserve(ix->ctx, s.elen, E * 8, &s.bufs, false));
-        FBG_TRY(fbg_reserve(ix->ctx, s.eoff, E * 8, &s.bufs, false));
-        hipLaunchKernelGGL(k_px_edge_len, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, ix->vesrc.as<uint32_t>(), ix->vedst.as<uint32_t>(),
-                           s.loff.as<uint64_t>(), E, s.elen.as<uint64_t>());
-        uint64_t *elen = s.elen.as<uint64_t>(), *eoff = s.eoff.as<uint64_t>();
-        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
-            return rocprim::exclusive_scan(tmp, bytes, elen, eoff, (uint64_t)0, (size_t)E, rocprim::plus<uint64_t>(), st);
-        }));
+        uint64_t *eoff = s.eoff.as<uint64_t>();
+        if (!pp.eoff_ready) {
+            FBG_TRY(fbg_reserve(ix->ctx, s.elen, E * 8, &s.bufs, false));
+            FBG_TRY(fbg_reserve(ix->ctx, s.eoff, E * 8, &s.bufs, false));
+            hipLaunchKernelGGL(k_px_edge_len, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, ix->vesrc.as<uint32_t>(), ix->vedst.as<uint32_t>(),
+                               s.loff.as<uint64_t>(), E, s.elen.as<uint64_t>());
+            uint64_t *elen = s.elen.as<uint64_t>();
+            eoff = s.eoff.as<uint64_t>();
+            FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+                return rocprim::exclusive_scan(tmp, bytes, elen, eoff, (uint64_t)0, (size_t)E, rocprim::plus<uint64_t>(), st);
+            }));
+        }
         hipLaunchKernelGGL(k_px_edge_text, dim3(fbg_blocks(E * FBG_WAVE, PX_THREADS)), dim3(PX_THREADS), 0, st, s.labels.as<uint8_t>(),
                            s.loff.as<uint64_t>(), ix->vesrc.as<uint32_t>(), ix->vedst.as<uint32_t>(), eoff, E, ix->text.as<uint8_t>());
     }
@@ -667,6 +710,264 @@ static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label
     return FBG_OK;
 }
 
+static int px_build(fbg_pindex *ix, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
+                    const uint64_t *edge_off, const uint64_t *edge_dst)
+{
+    PxScratch s;
+    PxPrep pp;
+    FBG_TRY(px_prepare_host(ix, s, labels, label_off, n_nodes, edge_off, edge_dst, pp));
+    return px_build_prepared(ix, s, pp);
+}
+
+// ---- prepare from a segmentation (fbg_pindex_build_segmentation) ------------------------------------------------
+// The graph of a segmentation as the device stage of fbg_block_graph leaves it, turned into what px_build_prepared
+// reads without a trip through the host:
+//   k_ps_nodes        block and representative row of every node (blocks in order, representatives by row: the
+//                     reference's numbering);
+//   k_ps_labels<0>    one wave per node along its row's bytes: the gap-stripped length, and a flag for '#' / 0;
+//   k_ps_labels<1>    the same walk again after the scan of the lengths: the label bytes into the padded buffer;
+//   k_ps_edges        the per-block edge lists (distinct, ascending, blocks ascending) compacted with the scan of
+//                     edge_count: the (source, destination) order of px_prepare_host;
+//   k_ps_touch        per node the first edge that touches it (a min over the edge index: px_prepare_host's rule for
+//                     vtpos) and its out- / in-degree over distinct edges;
+//   k_ps_estart, k_ps_node_tables   estart from the scanned edge string lengths; vtpos and vflag per node;
+//   k_ps_hist         bytes of the labels times the degree of their node, per workgroup in LDS, then global.
+#define PS_NONE 0xffffffffu
+
+// the columns [x0, x1) of block j: bg_block_range's clamp (block_graph.hip)
+__device__ __forceinline__ void ps_block_range(const uint64_t *bounds, uint64_t n, uint64_t j, uint64_t &x0, uint64_t &x1)
+{
+    x0 = j ? bounds[j - 1] + 1 : 0;
+    x1 = min(bounds[j] + 1, n);
+    if (x0 > x1) x0 = x1;
+}
+
+__global__ void k_ps_nodes(const uint32_t *rep_row, const uint32_t *count, const unsigned long long *first, uint64_t m, uint64_t nb,
+                           uint32_t *node_block, uint32_t *node_row)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m * nb) return;
+    const uint64_t j = t / m, k = t % m;
+    if (k >= count[j]) return;
+    const uint64_t u = first[j] + k;
+    node_block[u] = (uint32_t)j;
+    node_row[u] = rep_row[t];
+}
+
+// One wave per node (grid-stride), 64 columns of its row per step; the rank of a kept byte among the kept bytes of
+// the step comes from the ballot.  !GATHER: len64[u], vlen[u] and *bad (a '#' or a zero byte in a label).
+template <bool GATHER>
+__global__ __launch_bounds__(PX_THREADS) void k_ps_labels(const uint8_t *msa, uint64_t n, const uint64_t *bounds, const uint32_t *node_block,
+                                                         const uint32_t *node_row, uint64_t n_nodes, uint64_t *len64, uint32_t *vlen,
+                                                         unsigned long long *bad, const uint64_t *loff, uint8_t *labels)
+{
+    const unsigned lane = threadIdx.x % FBG_WAVE;
+    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x / FBG_WAVE);
+    for (uint64_t u = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FBG_WAVE; u < n_nodes; u += nw) {
+        uint64_t x0, x1;
+        ps_block_range(bounds, n, node_block[u], x0, x1);
+        const uint8_t *row = msa + (uint64_t)node_row[u] * n;
+        uint8_t *out = GATHER ? labels + loff[u] : nullptr;
+        uint64_t base = 0;
+        bool sep = false;
+        for (uint64_t xb = x0; xb < x1; xb += FBG_WAVE) {
+            const uint64_t x = xb + lane;
+            const uint8_t c = x < x1 ? row[x] : (uint8_t)'-';
+            const bool keep = c != '-';
+            const uint64_t bal = __ballot(keep);
+            if (GATHER) { if (keep) out[base + __popcll(bal & px_low(lane))] = c; }
+            else sep |= keep && (c == '#' || c == 0);
+            base += __popcll(bal);
+        }
+        if (!GATHER) {
+            if (lane == 0) {
+                len64[u] = base;
+                vlen[u] = base > 0xffffffffull ? 0xffffffffu : (uint32_t)base;
+            }
+            if (sep) *bad = 1;
+        }
+    }
+}
+
+__global__ void k_ps_edges(const unsigned long long *edges, const unsigned long long *edge_count, const uint64_t *ebase, uint64_t m,
+                           uint64_t nb, uint32_t *esrc, uint32_t *edst)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m * nb) return;
+    const uint64_t j = t / m, k = t % m;
+    if (k >= edge_count[j]) return;
+    const unsigned long long pr = edges[t];
+    const uint64_t e = ebase[j] + k;
+    esrc[e] = (uint32_t)(pr >> 32);
+    edst[e] = (uint32_t)pr;
+}
+
+__global__ void k_ps_touch(const uint32_t *esrc, const uint32_t *edst, uint64_t E, uint32_t *firstE, uint32_t *nout, uint32_t *nin)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const uint32_t u = esrc[e], v = edst[e];
+    atomicMin(&firstE[u], (uint32_t)e);
+    atomicMin(&firstE[v], (uint32_t)e);
+    atomicAdd(&nout[u], 1u);
+    atomicAdd(&nin[v], 1u);
+}
+
+__global__ void k_ps_estart(const uint64_t *eoff, uint64_t E, uint32_t *estart)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e <= E) estart[e] = (uint32_t)eoff[e];
+}
+
+// the first edge of a node gives its label's text position: after '#' and reverse(label(dst)) when the node is the
+// edge's source, right after '#' when it is its destination
+__global__ void k_ps_node_tables(const uint32_t *firstE, const uint32_t *nout, const uint32_t *nin, const uint32_t *esrc,
+                                 const uint32_t *edst, const uint32_t *estart, const uint32_t *vlen, uint64_t n_nodes,
+                                 uint32_t *vtpos, uint8_t *vflag)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_nodes) return;
+    const uint32_t e = firstE[u];
+    uint32_t tp = 0;
+    if (e != PS_NONE) tp = esrc[e] == u ? estart[e] + 1 + vlen[edst[e]] : estart[e] + 1;
+    vtpos[u] = tp;
+    vflag[u] = (uint8_t)((nout[u] ? PV_OUT : 0u) | (nin[u] ? PV_IN : 0u));
+}
+
+// hist[c] += degree(u) for every byte c of label(u): one wave per node, a workgroup's sums in LDS (they stay below the
+// text length, which the caller has checked against 2^32), one global add per workgroup and symbol
+__global__ __launch_bounds__(PX_THREADS) void k_ps_hist(const uint8_t *labels, const uint64_t *loff, const uint32_t *nout, const uint32_t *nin,
+                                                       uint64_t n_nodes, unsigned long long *hist)
+{
+    __shared__ uint32_t h[256];
+    for (int c = threadIdx.x; c < 256; c += blockDim.x) h[c] = 0;
+    __syncthreads();
+    const unsigned lane = threadIdx.x % FBG_WAVE;
+    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x / FBG_WAVE);
+    for (uint64_t u = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FBG_WAVE; u < n_nodes; u += nw) {
+        const uint32_t use = nout[u] + nin[u];
+        if (!use) continue;
+        const uint64_t a = loff[u], b = loff[u + 1];
+        for (uint64_t k = a + lane; k < b; k += FBG_WAVE) atomicAdd(&h[labels[k]], use);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < 256; c += blockDim.x)
+        if (h[c]) atomicAdd(&hist[c], (unsigned long long)h[c]);
+}
+
+static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, PxPrep &pp)
+{
+    fbg_ctx *ctx = ix->ctx;
+    BlockGraphDev g;
+    FBG_TRY(fbg_block_graph_device(ctx, boundaries, nb, &g));
+    if (g.collision)
+        return fbg_fail(ctx, FBG_ERR_HASH_COLLISION, "two different block labels share a 128-bit hash; use the host-side numbering");
+    hipStream_t st = ctx->stream;
+    const uint64_t m = ctx->m, n = ctx->n, cells = m * nb, n_nodes = g.n_nodes;
+    if (n_nodes >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%llu nodes: at most 2^32 - 2", (unsigned long long)n_nodes);
+    auto R = [&](std::vector<DevBuf *> &owner, DevBuf &b, size_t bytes) { return fbg_reserve(ctx, b, bytes + 8, &owner, false); };
+    FBG_TRY(R(ix->bufs, ix->snode_block, n_nodes * 4));
+    FBG_TRY(R(ix->bufs, ix->sfirst, (nb + 1) * 8));
+    FBG_TRY(R(ix->bufs, ix->vlen, n_nodes * 4));
+    FBG_TRY(R(ix->bufs, ix->vtpos, n_nodes * 4));
+    FBG_TRY(R(ix->bufs, ix->vflag, n_nodes));
+    FBG_TRY(R(s.bufs, s.nrow, n_nodes * 4));
+    FBG_TRY(R(s.bufs, s.len64, (n_nodes + 1) * 8));
+    FBG_TRY(R(s.bufs, s.loff, (n_nodes + 1) * 8));
+    FBG_TRY(R(s.bufs, s.ebase, (nb + 1) * 8));
+    FBG_TRY(R(s.bufs, s.firstE, n_nodes * 4));
+    FBG_TRY(R(s.bufs, s.nout, n_nodes * 4));
+    FBG_TRY(R(s.bufs, s.nin, n_nodes * 4));
+    FBG_TRY(R(s.bufs, s.hist, 257 * 8));                 // 256 counts and the separator flag
+    uint32_t *node_block = ix->snode_block.as<uint32_t>(), *node_row = s.nrow.as<uint32_t>(), *vlen = ix->vlen.as<uint32_t>();
+    uint64_t *len64 = s.len64.as<uint64_t>(), *loff = s.loff.as<uint64_t>(), *ebase = s.ebase.as<uint64_t>();
+    auto *hist = s.hist.as<unsigned long long>(), *bad = hist + 256;
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->sfirst.p, g.first, (nb + 1) * 8, hipMemcpyDeviceToDevice, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(hist, 0, 257 * 8, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(len64 + n_nodes, 0, 8, st));
+    hipLaunchKernelGGL(k_ps_nodes, dim3(fbg_blocks(cells, 256)), dim3(256), 0, st, g.rep_row, g.count, g.first, m, nb, node_block, node_row);
+    const dim3 gw(fbg_blocks(n_nodes * FBG_WAVE, PX_THREADS, 4096));
+    hipLaunchKernelGGL(k_ps_labels<false>, gw, dim3(PX_THREADS), 0, st, ctx->d_msa, n, g.bounds, (const uint32_t *)node_block,
+                       (const uint32_t *)node_row, n_nodes, len64, vlen, bad, (const uint64_t *)nullptr, (uint8_t *)nullptr);
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, len64, loff, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
+    }));
+    // edges: the scan of edge_count places every block's list (entry nb of edge_count does not exist: scan nb, add the last)
+    const unsigned long long *ecount = g.edge_count;
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::inclusive_scan(tmp, bytes, ecount, ebase + 1, (size_t)nb, rocprim::plus<uint64_t>(), st);
+    }));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ebase, 0, 8, st));
+    uint64_t h_L = 0, h_E = 0;
+    unsigned long long h_bad = 0;
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_L, loff + n_nodes, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_E, ebase + nb, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (h_bad) return fbg_fail(ctx, FBG_ERR_INVALID, "the MSA may not contain '#' or a zero byte (both are separators of the index text)");
+    const uint64_t L = h_L, E = h_E;
+    FBG_TRY(fbg_reserve(ctx, s.labels, ((L + 7) & ~7ull) + 16, &s.bufs, false));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(s.labels.p, 0, s.labels.cap, st));
+    hipLaunchKernelGGL(k_ps_labels<true>, gw, dim3(PX_THREADS), 0, st, ctx->d_msa, n, g.bounds, (const uint32_t *)node_block,
+                       (const uint32_t *)node_row, n_nodes, (uint64_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr,
+                       (const uint64_t *)loff, s.labels.as<uint8_t>());
+    FBG_TRY(R(ix->bufs, ix->vesrc, E * 4));
+    FBG_TRY(R(ix->bufs, ix->vedst, E * 4));
+    FBG_TRY(R(ix->bufs, ix->vestart, (E + 1) * 4));
+    FBG_TRY(R(s.bufs, s.elen, (E + 1) * 8));
+    FBG_TRY(R(s.bufs, s.eoff, (E + 1) * 8));
+    uint32_t *esrc = ix->vesrc.as<uint32_t>(), *edst = ix->vedst.as<uint32_t>(), *estart = ix->vestart.as<uint32_t>();
+    uint32_t *firstE = s.firstE.as<uint32_t>(), *nout = s.nout.as<uint32_t>(), *nin = s.nin.as<uint32_t>();
+    uint64_t *elen = s.elen.as<uint64_t>(), *eoff = s.eoff.as<uint64_t>();
+    FBG_HIP_TRY(ctx, hipMemsetAsync(firstE, 0xff, n_nodes * 4 + 8, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(nout, 0, n_nodes * 4 + 8, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(nin, 0, n_nodes * 4 + 8, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(elen + E, 0, 8, st));
+    if (E) {
+        hipLaunchKernelGGL(k_ps_edges, dim3(fbg_blocks(cells, 256)), dim3(256), 0, st, g.edges, g.edge_count, (const uint64_t *)ebase, m, nb,
+                           esrc, edst);
+        hipLaunchKernelGGL(k_ps_touch, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, (const uint32_t *)esrc, (const uint32_t *)edst, E, firstE,
+                           nout, nin);
+        hipLaunchKernelGGL(k_px_edge_len, dim3(fbg_blocks(E, 256)), dim3(256), 0, st, (const uint32_t *)esrc, (const uint32_t *)edst,
+                           (const uint64_t *)loff, E, elen);
+    }
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, elen, eoff, (uint64_t)0, (size_t)(E + 1), rocprim::plus<uint64_t>(), st);
+    }));
+    uint64_t h_N = 0;
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_N, eoff + E, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (h_N + 1 >= (1ull << 32))
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "the edge text of this graph has 2^32 symbols or more; the pattern index "
+                        "takes texts of N + 1 < 2^32 symbols");
+    hipLaunchKernelGGL(k_ps_estart, dim3(fbg_blocks(E + 1, 256)), dim3(256), 0, st, (const uint64_t *)eoff, E, estart);
+    hipLaunchKernelGGL(k_ps_node_tables, dim3(fbg_blocks(n_nodes, 256)), dim3(256), 0, st, (const uint32_t *)firstE, (const uint32_t *)nout,
+                       (const uint32_t *)nin, (const uint32_t *)esrc, (const uint32_t *)edst, (const uint32_t *)estart,
+                       (const uint32_t *)vlen, n_nodes, ix->vtpos.as<uint32_t>(), ix->vflag.as<uint8_t>());
+    if (E)
+        hipLaunchKernelGGL(k_ps_hist, dim3(fbg_blocks(n_nodes * FBG_WAVE, PX_THREADS, 1024)), dim3(PX_THREADS), 0, st,
+                           (const uint8_t *)s.labels.as<uint8_t>(), (const uint64_t *)loff, (const uint32_t *)nout, (const uint32_t *)nin,
+                           n_nodes, hist);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    // the 256-entry table is finished on the host
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(pp.hist, hist, 256 * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    pp.hist[0] = 1;
+    pp.hist['#'] = E;
+    pp.n_nodes = n_nodes; pp.E = E; pp.N1 = h_N + 1;
+    pp.eoff_ready = true;
+    ix->from_segmentation = true;
+    ix->seg_nb = nb;
+    return FBG_OK;
+}
+
+static int px_build_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb)
+{
+    PxPrep pp;
+    FBG_TRY(px_prepare_segmentation(ix, s, boundaries, nb, pp));
+    return px_build_prepared(ix, s, pp);
+}
+
 static void px_destroy(fbg_pindex *ix)
 {
     if (!ix) return;
@@ -677,6 +978,8 @@ static void px_destroy(fbg_pindex *ix)
     fbg_release_all(nullptr, ix->bufs);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
+    if (ix->sv0) (void)hipEventDestroy(ix->sv0);
+    if (ix->sv1) (void)hipEventDestroy(ix->sv1);
     delete ix;
 }
 
@@ -1119,6 +1422,45 @@ extern "C" int fbg_pindex_stats(const fbg_pindex *ix, uint64_t *index_bytes, dou
     return FBG_OK;
 }
 
+// The validation kernels over the index's n_nodes > 0 nodes, blocks from d_block (device), between ev0 and ev1; status,
+// witnesses and counters stay in vstatus / vwn / vwo / vctr.
+static int pv_launch(fbg_pindex *ix, const uint32_t *d_block, const PvMask &ig, int has_ig)
+{
+    fbg_ctx *ctx = ix->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = ix->n_nodes;
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vstatus, n, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vwn, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vwo, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vlist, n * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, ix->vctr, 16, &ix->bufs, false));
+    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
+    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->vctr.p, 0, 16, st));
+    PvDev d = pv_dev(ix);
+    d.block = d_block;
+    auto *ctr = ix->vctr.as<unsigned long long>();
+    uint8_t *dst = ix->vstatus.as<uint8_t>();
+    uint32_t *wn = ix->vwn.as<uint32_t>(), *wo = ix->vwo.as<uint32_t>();
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    hipLaunchKernelGGL(k_pv_node, dim3(fbg_blocks(n, PX_THREADS)), dim3(PX_THREADS), 0, st, d, n, ig, has_ig, dst, wn, wo,
+                       ix->vlist.as<uint32_t>(), ctr);
+    const uint64_t wave_blocks = std::min<uint64_t>(fbg_blocks(n * FBG_WAVE, PX_THREADS), 2048);
+    hipLaunchKernelGGL(k_pv_wave, dim3(wave_blocks), dim3(PX_THREADS), 0, st, d, (const uint32_t *)ix->vlist.as<uint32_t>(), ctr, dst,
+                       wn, wo);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    return FBG_OK;
+}
+
+static PvMask pv_mask(const uint8_t *ignore_chars, uint64_t ignore_len, int *has_ig)
+{
+    PvMask ig = {{0, 0, 0, 0}};
+    for (uint64_t k = 0; k < ignore_len; k++) ig.w[ignore_chars[k] >> 6] |= 1ull << (ignore_chars[k] & 63);
+    *has_ig = (ig.w[0] | ig.w[1] | ig.w[2] | ig.w[3]) != 0;
+    return ig;
+}
+
 extern "C" int fbg_pindex_validate(fbg_pindex *ix, const uint32_t *node_block, const uint8_t *ignore_chars, uint64_t ignore_len,
                                    uint8_t *status, uint64_t *witness_node, uint64_t *witness_offset, uint64_t *n_invalid,
                                    double *device_ms)
@@ -1133,33 +1475,16 @@ extern "C" int fbg_pindex_validate(fbg_pindex *ix, const uint32_t *node_block, c
     ix->validate_ms = 0;
     ix->v_slots = ix->v_wave_nodes = 0;
     if (n == 0) return FBG_OK;
-    PvMask ig = {{0, 0, 0, 0}};
-    for (uint64_t k = 0; k < ignore_len; k++) ig.w[ignore_chars[k] >> 6] |= 1ull << (ignore_chars[k] & 63);
-    const int has_ig = (ig.w[0] | ig.w[1] | ig.w[2] | ig.w[3]) != 0;
+    int has_ig = 0;
+    const PvMask ig = pv_mask(ignore_chars, ignore_len, &has_ig);
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_reserve(ix->ctx, ix->vblock, n * 4, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->vstatus, n, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->vwn, n * 4, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->vwo, n * 4, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->vlist, n * 4, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->vctr, 16, &ix->bufs, false));
-    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
-    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->vblock.p, node_block, n * 4, hipMemcpyHostToDevice, st));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->vctr.p, 0, 16, st));
-    const PvDev d = pv_dev(ix);
+    FBG_TRY(pv_launch(ix, ix->vblock.as<uint32_t>(), ig, has_ig));
     auto *ctr = ix->vctr.as<unsigned long long>();
     uint8_t *dst = ix->vstatus.as<uint8_t>();
     uint32_t *wn = ix->vwn.as<uint32_t>(), *wo = ix->vwo.as<uint32_t>();
-    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
-    hipLaunchKernelGGL(k_pv_node, dim3(fbg_blocks(n, PX_THREADS)), dim3(PX_THREADS), 0, st, d, n, ig, has_ig, dst, wn, wo,
-                       ix->vlist.as<uint32_t>(), ctr);
-    const uint64_t wave_blocks = std::min<uint64_t>(fbg_blocks(n * FBG_WAVE, PX_THREADS), 2048);
-    hipLaunchKernelGGL(k_pv_wave, dim3(wave_blocks), dim3(PX_THREADS), 0, st, d, (const uint32_t *)ix->vlist.as<uint32_t>(), ctr, dst,
-                       wn, wo);
-    FBG_HIP_TRY(ctx, hipGetLastError());
-    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
     std::vector<uint32_t> hwn(witness_node ? n : 0), hwo(witness_offset ? n : 0);
     uint64_t hctr[2] = {0, 0};
     FBG_HIP_TRY(ctx, hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, st));
@@ -1191,3 +1516,158 @@ extern "C" int fbg_pindex_validate_stats(const fbg_pindex *ix, uint64_t *slots_s
 }
 
 extern "C" void fbg_pindex_destroy(fbg_pindex *ix) { px_destroy(ix); }
+
+// ---- an index straight from a segmentation; validation and repair of a segmentation ----------------------------------
+extern "C" int fbg_pindex_build_segmentation(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, fbg_pindex **out)
+{
+    if (!ctx) return FBG_ERR_INVALID;
+    if (!ctx->d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_build_segmentation: no MSA set");
+    if (!out || !boundaries || nb == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_build_segmentation: missing argument");
+    *out = nullptr;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    fbg_pindex *ix = new fbg_pindex();
+    ix->ctx = ctx;
+    int rc;
+    {
+        PxScratch s;
+        rc = px_build_segmentation(ix, s, boundaries, nb);
+    }
+    if (rc != FBG_OK) { px_destroy(ix); return rc; }
+    ix->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = ix;
+    return FBG_OK;
+}
+
+extern "C" uint64_t fbg_pindex_node_count(const fbg_pindex *ix) { return ix ? ix->n_nodes : 0; }
+
+extern "C" int fbg_pindex_node_info(fbg_pindex *ix, uint32_t *label_len, uint32_t *node_block, uint64_t *first_node)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    if ((node_block || first_node) && !ix->from_segmentation)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_node_info: only an index built from a segmentation knows its blocks");
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = ix->n_nodes;
+    if (label_len && n) FBG_HIP_TRY(ctx, hipMemcpyAsync(label_len, ix->vlen.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (node_block && n) FBG_HIP_TRY(ctx, hipMemcpyAsync(node_block, ix->snode_block.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (first_node) FBG_HIP_TRY(ctx, hipMemcpyAsync(first_node, ix->sfirst.p, (ix->seg_nb + 1) * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return FBG_OK;
+}
+
+// cut[b - 1] = 1 for every block b > 0 that holds an INVALID node (the reference's to_remove); *count: INVALID nodes
+__global__ void k_sv_cuts(const uint8_t *status, const uint32_t *node_block, uint64_t n, uint8_t *cut, unsigned long long *count)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool bad = u < n && status[u] == FBG_NODE_INVALID;
+    if (bad && node_block[u] > 0) cut[node_block[u] - 1] = 1;
+    const uint64_t bal = __ballot(bad);
+    if ((threadIdx.x % FBG_WAVE) == 0 && bal) atomicAdd(count, (unsigned long long)__popcll(bal));
+}
+
+// One round: the index of the segmentation into ix (its buffers and the scratch are reused from round to round), the
+// validation kernels on the device's own node_block, the flagged cuts.  The events sv0 / sv1 enclose all of it.
+static int sv_round(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, const PvMask &ig, int has_ig,
+                    uint8_t *cut_bad, uint64_t *n_invalid, double *ms)
+{
+    fbg_ctx *ctx = ix->ctx;
+    hipStream_t st = ctx->stream;
+    if (!ix->sv0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->sv0));
+    if (!ix->sv1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->sv1));
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->sv0, st));
+    FBG_TRY(px_build_segmentation(ix, s, boundaries, nb));
+    const uint64_t n = ix->n_nodes;
+    FBG_TRY(fbg_reserve(ctx, ix->scut, nb + 8, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ctx, ix->sctr, 8, &ix->bufs, false));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->scut.p, 0, nb + 8, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->sctr.p, 0, 8, st));
+    if (n) {
+        FBG_TRY(pv_launch(ix, ix->snode_block.as<uint32_t>(), ig, has_ig));
+        hipLaunchKernelGGL(k_sv_cuts, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, (const uint8_t *)ix->vstatus.as<uint8_t>(),
+                           (const uint32_t *)ix->snode_block.as<uint32_t>(), n, ix->scut.as<uint8_t>(), ix->sctr.as<unsigned long long>());
+        FBG_HIP_TRY(ctx, hipGetLastError());
+    }
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->sv1, st));
+    unsigned long long bad = 0;
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(cut_bad, ix->scut.p, nb, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&bad, ix->sctr.p, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float f = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&f, ix->sv0, ix->sv1));
+    *ms += f;
+    *n_invalid = bad;
+    return FBG_OK;
+}
+
+extern "C" int fbg_segmentation_validate(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, const uint8_t *ignore_chars,
+                                         uint64_t ignore_len, uint8_t *cut_bad, uint64_t *n_nodes, uint64_t *n_invalid,
+                                         double *device_ms)
+{
+    if (!ctx) return FBG_ERR_INVALID;
+    if (!ctx->d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_segmentation_validate: no MSA set");
+    if (!boundaries || nb == 0 || !cut_bad) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_segmentation_validate: missing argument");
+    if (ignore_len && !ignore_chars) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_segmentation_validate: missing ignore characters");
+    if (n_nodes) *n_nodes = 0;
+    if (n_invalid) *n_invalid = 0;
+    if (device_ms) *device_ms = 0;
+    int has_ig = 0;
+    const PvMask ig = pv_mask(ignore_chars, ignore_len, &has_ig);
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    fbg_pindex *ix = new fbg_pindex();
+    ix->ctx = ctx;
+    uint64_t bad = 0;
+    double ms = 0;
+    int rc;
+    {
+        PxScratch s;
+        rc = sv_round(ix, s, boundaries, nb, ig, has_ig, cut_bad, &bad, &ms);
+    }
+    if (rc == FBG_OK) {
+        if (n_nodes) *n_nodes = ix->n_nodes;
+        if (n_invalid) *n_invalid = bad;
+        if (device_ms) *device_ms = ms;
+    }
+    px_destroy(ix);
+    return rc;
+}
+
+extern "C" int fbg_segmentation_repair(fbg_ctx *ctx, uint64_t *boundaries, uint64_t *nb, const uint8_t *ignore_chars,
+                                       uint64_t ignore_len, uint64_t *rounds, uint64_t *removed, double *device_ms)
+{
+    if (!ctx) return FBG_ERR_INVALID;
+    if (!ctx->d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_segmentation_repair: no MSA set");
+    if (!boundaries || !nb || *nb == 0 || !rounds || !removed) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_segmentation_repair: missing argument");
+    if (ignore_len && !ignore_chars) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_segmentation_repair: missing ignore characters");
+    *rounds = 0;
+    if (device_ms) *device_ms = 0;
+    int has_ig = 0;
+    const PvMask ig = pv_mask(ignore_chars, ignore_len, &has_ig);
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    fbg_pindex *ix = new fbg_pindex();
+    ix->ctx = ctx;
+    std::vector<uint8_t> cut(*nb);
+    double ms = 0;
+    int rc = FBG_OK;
+    {
+        PxScratch s;
+        // fbg.cpp:3471-3497: validate, drop the flagged boundaries, again until none is flagged.  Every round with a
+        // flagged cut shortens the list, and a single block has no node with both an in- and an out-edge.
+        for (;;) {
+            uint64_t bad = 0;
+            rc = sv_round(ix, s, boundaries, *nb, ig, has_ig, cut.data(), &bad, &ms);
+            if (rc != FBG_OK) break;
+            uint64_t flagged = 0, keep = 0;
+            for (uint64_t k = 0; k < *nb; k++) flagged += cut[k] != 0;
+            if (!flagged) break;
+            removed[(*rounds)++] = flagged;
+            for (uint64_t k = 0; k < *nb; k++)
+                if (!cut[k]) boundaries[keep++] = boundaries[k];
+            *nb = keep;
+        }
+    }
+    if (rc == FBG_OK && device_ms) *device_ms = ms;
+    px_destroy(ix);
+    return rc;
+}

@@ -493,6 +493,51 @@ int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, const uint64
 int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
                                  uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms);
 
+/* ---- the pattern index of a segmentation, built on the device; validation and repair of a segmentation ------------
+ *
+ * fbg_pindex_build_segmentation: the pattern index of the elastic founder graph that `boundaries` (the fbg_minmax_dp
+ * convention: inclusive block ends, the last one is n) cuts out of the context's current MSA.  The result is an
+ * ordinary fbg_pindex, indistinguishable from fbg_pindex_build given the labels and edges of fbg_block_graph: the same
+ * node numbering (blocks in order, within a block by first appearance by row), text, SA, B and E; locate,
+ * occurrences, validate, download and stats work on it unchanged.  Nothing but a few sizes and a 256-entry byte
+ * histogram goes through the host: the device stage of fbg_block_graph leaves nodes and distinct sorted edges in
+ * device memory, the labels are gathered from the resident MSA, and the tables of fbg_pindex_validate are derived
+ * there (the label position of a node from the FIRST edge that touches it, as fbg_pindex_build does).  The index
+ * also keeps node_block[n_nodes] and first_node[nb + 1] on the device (fbg_pindex_node_info).
+ * Errors: FBG_ERR_INVALID for a missing argument, no MSA, boundaries that do not increase or pass n, or a '#' or a
+ * zero byte in the MSA (checked on the device); FBG_ERR_TOO_LARGE for more than FBG_MAX_ROWS rows, 2^32 (row, block)
+ * cells, or an edge text of 2^32 symbols or more; FBG_ERR_HASH_COLLISION as fbg_block_graph reports it.
+ * The call uses the workspaces of fbg_block_graph; the context's MSA, its MSA index and every other fbg_pindex are
+ * left as they were. */
+int fbg_pindex_build_segmentation(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, fbg_pindex **out);
+/* nodes of an index's graph */
+uint64_t fbg_pindex_node_count(const fbg_pindex *ix);
+/* For tests and the Python layer; any pointer may be NULL.  label_len: n_nodes values (the label lengths, capped at
+ * 2^32 - 1; any index).  node_block: n_nodes values, first_node: nb + 1 values (an index built from a segmentation
+ * only, else FBG_ERR_INVALID). */
+int fbg_pindex_node_info(fbg_pindex *ix, uint32_t *label_len, uint32_t *node_block, uint64_t *first_node);
+
+/* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
+ * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
+ * to_remove[node_blocks[i] - 1] (fbg.cpp:3269-3270, 3194); cut_bad[nb - 1] is always 0.  The index is built by
+ * fbg_pindex_build_segmentation, validated against its own device-resident node_block, and the cuts are flagged by a
+ * kernel over status and node_block: no per-node array goes to the host.  *n_nodes, *n_invalid (INVALID nodes) and
+ * *device_ms may be NULL.  *device_ms: time on the stream from the first to the last device operation of the build and
+ * the validation, the waits for the sizes the host reads in between included.
+ *
+ * fbg_segmentation_repair: the loop of fbg.cpp:3471-3497 -- validate, drop the flagged boundaries, repeat until none is
+ * flagged.  boundaries / *nb: in and out (the result is a subsequence of the input and keeps its last entry).
+ * *rounds = the rounds that removed something (the reference's iterations - 1); removed[r] = boundaries dropped in
+ * round r ("There are K blocks to remove"), room for the incoming *nb values; the final round's 0 is not stored.  The
+ * loop ends: a round that flags a cut shortens the list, and the nodes of a single block are sources and sinks.  Every
+ * round rebuilds the index into the same buffers.  *device_ms (may be NULL): the sum over the rounds.
+ * Errors as fbg_pindex_build_segmentation; on an error boundaries / *nb hold the state before the failing round.
+ * Both calls leave the context's MSA, its MSA index and every fbg_pindex untouched. */
+int fbg_segmentation_validate(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, const uint8_t *ignore_chars,
+                              uint64_t ignore_len, uint8_t *cut_bad, uint64_t *n_nodes, uint64_t *n_invalid, double *device_ms);
+int fbg_segmentation_repair(fbg_ctx *ctx, uint64_t *boundaries, uint64_t *nb, const uint8_t *ignore_chars, uint64_t ignore_len,
+                            uint64_t *rounds, uint64_t *removed, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
