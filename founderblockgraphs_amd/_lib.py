@@ -86,6 +86,9 @@ SIGNATURES = {
     "fbg_pindex_occurrences": (C.c_int, [vp, u8p, u64p, C.c_uint64, C.c_uint64, u64p, u64p, u32p, u64p, u64p, u64p, u64p,
                                          C.POINTER(C.c_double)]),
     "fbg_pindex_occurrences_fetch": (C.c_int, [vp, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(C.c_double)]),
+    "fbg_pindex_seeds": (C.c_int, [vp, u8p, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_double)]),
+    "fbg_pindex_seeds_fetch": (C.c_int, [vp, u32p, u32p, u64p, u32p, u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
+    "fbg_pindex_seeds_places": (C.c_int, [vp, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(C.c_double)]),
     "fbg_pindex_build_segmentation": (C.c_int, [vp, u64p, C.c_uint64, C.POINTER(vp)]),
     "fbg_pindex_node_count": (C.c_uint64, [vp]),
     "fbg_pindex_node_info": (C.c_int, [vp, u32p, u32p, u64p]),

@@ -459,6 +459,35 @@ class PatternIndex:
         return Occurrences(self._label_len, count[:k], pos[:k], rs[:k], et[:k], st[:k], eoff, soff, [a[:ne] for a in ends],
                            [a[:ns] for a in starts], ms1.value, ms2.value)
 
+    def seeds(self, patterns, min_length=1, max_per_seed=0):
+        """Every read cut greedily into the maximal pieces the search accepts (fbg_pindex_seeds, _fetch and _places):
+        seeds of at least min_length symbols, each with what occurrences() reports for that substring, at most
+        max_per_seed places per seed and list -> Seeds."""
+        if min_length < 1:
+            raise ValueError("min_length must be 1 or more")
+        if max_per_seed < 0:
+            raise ValueError("max_per_seed must be 0 or more")
+        data, off = _concat(patterns)
+        k = len(off) - 1
+        seed_off = np.zeros(k + 1, dtype=np.uint64)
+        ms1, ms2, ms3 = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._eng._chk(self._L.fbg_pindex_seeds(self._h, _u8(data), _u64(off), k, int(min_length), int(max_per_seed),
+                                                _u64(seed_off), C.byref(ms1)))
+        n = int(seed_off[k])
+        q, ln, rs = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        count, et, st = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(3))
+        eoff, soff = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+        u32 = lambda a: a.ctypes.data_as(_lib.u32p)      # noqa: E731
+        self._eng._chk(self._L.fbg_pindex_seeds_fetch(self._h, u32(q), u32(ln), _u64(count), u32(rs), _u64(et), _u64(st),
+                                                      _u64(eoff), _u64(soff), C.byref(ms2)))
+        ne, ns = int(eoff[n]), int(soff[n])
+        ends = [np.zeros(max(ne, 1), dtype=np.uint32) for _ in range(3)]
+        starts = [np.zeros(max(ns, 1), dtype=np.uint32) for _ in range(3)]
+        self._eng._chk(self._L.fbg_pindex_seeds_places(self._h, *[u32(a) for a in ends + starts], C.byref(ms3)))
+        occ = Occurrences(self._label_len, count[:n], ln[:n].astype(np.uint64), rs[:n], et[:n], st[:n], eoff, soff,
+                          [a[:ne] for a in ends], [a[:ns] for a in starts], ms1.value, ms2.value + ms3.value)
+        return Seeds(seed_off, q[:n], ln[:n], occ)
+
     def download(self):
         """-> (text with the sentinel, SA, B positions, E positions)."""
         N1 = self.text_length()
@@ -555,6 +584,29 @@ class Occurrences:
             a, b = int(off[k]), int(off[k + 1])
             out.append(np.unique(np.stack((node[a:b], noff[a:b]), axis=1), axis=0).reshape(-1, 2))
         return out
+
+
+class Seeds:
+    """Result of PatternIndex.seeds (include/fbg_hip.h, fbg_pindex_seeds):
+      seed_off            uint64[k + 1], CSR offsets of the reported seeds of the k reads (a read's seeds by q_start)
+      q_start, length     uint32 per seed: the seed is read[q_start : q_start + length]
+      pattern_of          int64 per seed: its read
+      occ                 an Occurrences object over the seeds in order, as if every seed had been searched as a pattern
+                          of its own (occ.pos equals length; occ.ends(j), occ.starts(j), occ.as_nodes() work per seed)
+    search_ms: device time of fbg_pindex_seeds; fetch_ms: of the per-seed copies and the expansion of the places."""
+
+    def __init__(self, seed_off, q_start, length, occ):
+        self.seed_off, self.q_start, self.length, self.occ = seed_off, q_start, length, occ
+        self.pattern_of = np.repeat(np.arange(len(seed_off) - 1, dtype=np.int64), np.diff(seed_off.astype(np.int64)))
+        self.search_ms, self.fetch_ms = occ.search_ms, occ.fetch_ms
+
+    def __len__(self):
+        return len(self.q_start)
+
+    def of(self, k):
+        """int64[rows, 3]: (q_start, length, count) of the seeds of read k."""
+        a, b = int(self.seed_off[k]), int(self.seed_off[k + 1])
+        return np.stack((self.q_start[a:b], self.length[a:b], self.occ.count[a:b]), axis=1).astype(np.int64)
 
 
 class Validation:

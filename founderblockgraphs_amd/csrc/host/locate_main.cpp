@@ -2,7 +2,7 @@
 // libfbg_hip.so (include/fbg_hip.h, fbg_pindex_*).  Stands in for locate_patterns of the reference with a graph in
 // place of its .index file:
 //
-//   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]]
+//   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -13,6 +13,11 @@
 //   B <tab> src S id <tab> dst S id <tab> offset      where it begins
 // at most M of each per pattern, the ends first; a list cut by M is followed by `E <tab> ... <tab> K more` (or B) with
 // K the places left out.
+// --seeds[=L] (L = 1 when left out) answers through fbg_pindex_seeds instead: every pattern cut greedily into the maximal
+// pieces the search accepts, pieces of fewer than L symbols left out.  Per pattern `Pattern? K seeds found.`, then per seed
+//   S <tab> q_start <tab> length <tab> count <tab> restarts
+// followed, with --occurrences, by that seed's E / B lines as above; the last line is `Pattern? X out of Y patterns
+// seeded`, X the patterns with a seed.  --error-on-not-found then fails at the first pattern without one.
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -27,18 +32,35 @@
 static int usage(const char *msg)
 {
     std::cerr << "fbg_locate: " << msg << "\n"
-              << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]]\n"
+              << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
-              << "                     at most M of each per pattern (default 64)\n";
+              << "                     at most M of each per pattern (default 64)\n"
+              << "  --seeds[=L]        cut every pattern greedily into the maximal pieces the search accepts and print, per\n"
+              << "                     piece of L symbols or more (default 1), an S line: q_start, length, count, restarts;\n"
+              << "                     with --occurrences the E / B lines of every piece follow its S line\n";
     return EXIT_FAILURE;
+}
+
+// the E / B lines of item k of a place state: offsets o[2], totals t[2], places p[6] (end src / dst / offset, start ...)
+static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint64_t> *const o[2], const std::vector<uint64_t> *const t[2],
+                         const std::vector<uint32_t> *p)
+{
+    for (int w = 0; w < 2; w++) {
+        const std::vector<uint64_t> &off = *o[w];
+        const uint64_t total = (*t[w])[k];
+        const char *tag = w ? "B\t" : "E\t";
+        for (uint64_t i = off[k]; i < off[k + 1]; i++)
+            std::cout << tag << g.ids[p[3 * w][i]] << '\t' << g.ids[p[3 * w + 1][i]] << '\t' << p[3 * w + 2][i] << '\n';
+        if (total > off[k + 1] - off[k]) std::cout << tag << "...\t" << total - (off[k + 1] - off[k]) << " more\n";
+    }
 }
 
 int main(int argc, char **argv)
 {
     std::string graph, patterns;
-    bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false;
-    uint64_t max_places = 64;
+    bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false;
+    uint64_t max_places = 64, min_seed = 1;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&](const char *name, std::string &out, bool &have) {
@@ -59,6 +81,18 @@ int main(int argc, char **argv)
                 return usage(("--occurrences takes a count, not '" + v + "'").c_str());
             occurrences = true;
             max_places = m;
+            continue;
+        }
+        if (a == "--seeds") { seeds = true; continue; }
+        if (a.compare(0, 8, "--seeds=") == 0) {
+            const std::string v = a.substr(8);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end || m == 0)
+                return usage(("--seeds takes a positive count, not '" + v + "'").c_str());
+            seeds = true;
+            min_seed = m;
             continue;
         }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
@@ -102,12 +136,29 @@ int main(int argc, char **argv)
         for (std::vector<uint64_t> *v : {&end_off, &start_off, &end_total, &start_total}) v->assign(np + 1, 0);
         restarts.assign(np + 1, 0);
     }
-    if (rc == FBG_OK && !occurrences)
+    std::vector<uint64_t> seed_off(np + 1, 0), seed_count;
+    std::vector<uint32_t> q_start, length;
+    if (rc == FBG_OK && seeds) {
+        rc = fbg_pindex_seeds(ix, (const uint8_t *)data.data(), off.data(), np, min_seed, occurrences ? max_places : 0,
+                              seed_off.data(), nullptr);
+        const uint64_t ns = rc == FBG_OK ? seed_off[np] : 0;
+        for (std::vector<uint64_t> *v : {&seed_count, &end_off, &start_off, &end_total, &start_total}) v->assign(ns + 1, 0);
+        for (std::vector<uint32_t> *v : {&q_start, &length, &restarts}) v->assign(ns + 1, 0);
+        if (rc == FBG_OK)
+            rc = fbg_pindex_seeds_fetch(ix, q_start.data(), length.data(), seed_count.data(), restarts.data(), end_total.data(),
+                                        start_total.data(), end_off.data(), start_off.data(), nullptr);
+        if (rc == FBG_OK) {
+            for (int k = 0; k < 6; k++) places[k].resize((k < 3 ? end_off[ns] : start_off[ns]) + 1);
+            rc = fbg_pindex_seeds_places(ix, places[0].data(), places[1].data(), places[2].data(), places[3].data(),
+                                         places[4].data(), places[5].data(), nullptr);
+        }
+    }
+    if (rc == FBG_OK && !occurrences && !seeds)
         rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
-    if (rc == FBG_OK && occurrences)
+    if (rc == FBG_OK && occurrences && !seeds)
         rc = fbg_pindex_occurrences(ix, (const uint8_t *)data.data(), off.data(), np, max_places, count.data(), pos.data(),
                                     restarts.data(), end_off.data(), start_off.data(), end_total.data(), start_total.data(), nullptr);
-    if (rc == FBG_OK && occurrences) {
+    if (rc == FBG_OK && occurrences && !seeds) {
         for (int k = 0; k < 6; k++) places[k].resize((k < 3 ? end_off[np] : start_off[np]) + 1);
         rc = fbg_pindex_occurrences_fetch(ix, places[0].data(), places[1].data(), places[2].data(), places[3].data(),
                                           places[4].data(), places[5].data(), nullptr);
@@ -121,7 +172,26 @@ int main(int argc, char **argv)
     fbg_pindex_destroy(ix);
     fbg_ctx_destroy(ctx);
 
+    const std::vector<uint64_t> *const o[2] = {&end_off, &start_off}, *const t[2] = {&end_total, &start_total};
     uint64_t found = 0;
+    if (seeds) {
+        for (uint64_t k = 0; k < np; k++) {
+            const uint64_t ns = seed_off[k + 1] - seed_off[k];
+            std::cout << "Pattern? " << ns << " seeds found.\n";
+            if (ns == 0 && error_on_not_found) {
+                std::cerr << "Pattern has no seed.\n";
+                std::cout.flush();
+                return EXIT_FAILURE;
+            }
+            found += ns != 0;
+            for (uint64_t j = seed_off[k]; j < seed_off[k + 1]; j++) {
+                std::cout << "S\t" << q_start[j] << '\t' << length[j] << '\t' << seed_count[j] << '\t' << restarts[j] << '\n';
+                if (occurrences) print_places(g, j, o, t, places);
+            }
+        }
+        std::cout << "Pattern? " << found << " out of " << np << " patterns seeded" << std::endl;
+        return EXIT_SUCCESS;
+    }
     for (uint64_t k = 0; k < np; k++) {
         std::cout << "Pattern? " << count[k] << " occurrences found.\n";
         if (count[k] == 0) {
@@ -129,14 +199,7 @@ int main(int argc, char **argv)
             if (error_on_not_found) { std::cout.flush(); return EXIT_FAILURE; }
         } else {
             found++;
-            for (int w = 0; occurrences && w < 2; w++) {
-                const std::vector<uint64_t> &o = w ? start_off : end_off;
-                const uint64_t total = w ? start_total[k] : end_total[k];
-                const char *tag = w ? "B\t" : "E\t";
-                for (uint64_t i = o[k]; i < o[k + 1]; i++)
-                    std::cout << tag << g.ids[places[3 * w][i]] << '\t' << g.ids[places[3 * w + 1][i]] << '\t' << places[3 * w + 2][i] << '\n';
-                if (total > o[k + 1] - o[k]) std::cout << tag << "...\t" << total - (o[k + 1] - o[k]) << " more\n";
-            }
+            if (occurrences) print_places(g, k, o, t, places);
         }
     }
     std::cout << "Pattern? " << found << " out of " << np << " patterns found" << std::endl;

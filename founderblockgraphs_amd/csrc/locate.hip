@@ -17,6 +17,9 @@
 //                                    patterns handed out in order of length;
 //   k_px_walk<true, *, true>         the same search for fbg_pindex_occurrences: it also keeps the final range, the
 //                                    range after the '#' step of the first restart and the restart count;
+//   k_px_seeds                       fbg_pindex_seeds: that search run to the end of every read, restarted from [0, N]
+//                                    wherever it stops; a counting instantiation and a writing one (one record per
+//                                    maximal piece, which k_po_sizes / k_po_expand then treat as a pattern);
 //   k_po_sizes / k_po_expand         capped list sizes per pattern (scanned into CSR offsets), then one lane per
 //                                    reported place: SA slot -> (edge source, edge destination, offset);
 //   k_pv_node / k_pv_wave            the semi-repeat-free check (fbg_pindex_validate): the SA range of every label,
@@ -51,6 +54,15 @@
 #define PV_SHORT 16           // ranges of at most this many slots are scanned by one lane, longer ones by a wave
 #define PV_NONE 0xffffffffu   // no witness
 
+// What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
+// fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
+// and the places of the last fetch.  Grow-only, on the index's buffer list.
+struct PoState {
+    DevBuf etot, stot, esz, ssz, eoff, soff, rs, el, ss, sk, place;
+    bool ready = false;
+    uint64_t n = 0, etotal = 0, stotal = 0;
+};
+
 struct fbg_pindex {
     fbg_ctx *ctx = nullptr;
     uint64_t N1 = 0;          // text length including the sentinel
@@ -72,11 +84,14 @@ struct fbg_pindex {
     bool from_segmentation = false;
     uint64_t seg_nb = 0;
     hipEvent_t sv0 = nullptr, sv1 = nullptr;
-    // fbg_pindex_occurrences: per pattern the walk's record (3 x uint2), totals, capped sizes and their scans, what
-    // the expansion reads (first slot of either list, k or |P|, restarts), and the places of the last fetch
-    DevBuf orec, oetot, ostot, oesz, ossz, oeoff, osoff, ors, oel, oss, osk, oplace;
-    bool occ_ready = false;
-    uint64_t occ_n = 0, occ_etotal = 0, occ_stotal = 0;
+    // fbg_pindex_occurrences: the walk's record per pattern (3 x uint2) and the place state of its patterns;
+    // fbg_pindex_seeds: per pattern the number of reported seeds and its scan, per seed what the walk wrote (the same
+    // record, count, length as u64 for k_po_sizes, q_start, length) and the place state of the seeds.  The two place
+    // states never share a buffer: a fetch of one is not disturbed by a search of the other.
+    DevBuf orec;
+    PoState occ;
+    DevBuf snum, soff, srec, scnt, spos, sq, slen;
+    PoState sd;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -383,6 +398,87 @@ __global__ __launch_bounds__(PX_THREADS) void k_px_walk(PxDev d, const uint16_t 
     }
 }
 
+// fbg_pindex_seeds: the search of k_px_walk<true, *, true>, run to the end of every read.  One lane per read, reads
+// taken in the order `order` (by length).  When a step finally fails, or the read ends, after pos > 0 symbols, those
+// symbols are a seed: the state is the one the search of exactly those symbols ends in, so (l, r), the record of the
+// first restart and the restart count are what fbg_pindex_occurrences keeps for that substring.  The search then starts
+// again from [0, N] at the failing symbol, or at the next one when it failed at once (pos == 0).  k moves by at most one
+// symbol per step, so the pattern word held is always the one of symbol k, wherever in a word a seed starts.
+// !WRITE: num[id] = seeds of at least min_len symbols.  WRITE: seed j of read id goes to entry num[id] + j (num: the
+// exclusive scan of the counts) of cnt / len64 (u64, as k_po_sizes reads count and pos), rec (3 x uint2), qs and ln.
+template <bool COMPACT, bool WRITE>
+__global__ __launch_bounds__(PX_THREADS) void k_px_seeds(PxDev d, const uint16_t *code_g, const uint32_t *C_g, const uint8_t *pats,
+                                                        const uint64_t *poff, const uint32_t *order, uint64_t n, uint32_t min_len,
+                                                        uint64_t *num, unsigned long long *cnt_out, unsigned long long *len64,
+                                                        uint2 *rec, uint32_t *qs, uint32_t *ln)
+{
+    __shared__ uint16_t code[256];
+    __shared__ uint32_t C[256];
+    for (int c = threadIdx.x; c < 256; c += blockDim.x) { code[c] = code_g[c]; C[c] = C_g[c]; }
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint64_t id = order[t];
+    const uint64_t a = poff[id];
+    const uint32_t len = (uint32_t)(poff[id + 1] - a);       // < 2^32: checked by the host
+    uint64_t at = WRITE ? num[id] : 0;                        // next entry (WRITE) or seeds counted so far
+    uint32_t l = 0, r = d.N, pos = 0, nlines = 0;
+    uint32_t restarts = 0, fsl = 1, fsr = 0, fk = 0;
+    uint64_t word = 0;
+    uint32_t k = 0;
+    while (true) {
+        bool ok = false;
+        if (k < len) {
+            const uint64_t q = a + k;
+            if (k == 0 || (q & 7) == 0) word = *(const uint64_t *)(pats + (q & ~7ull));   // buffer padded to 8 bytes
+            const uint32_t ch = (uint32_t)(word >> (8 * (q & 7))) & 0xffu;
+            uint32_t nl, nr;
+            ok = px_bs<COMPACT>(d, code, C, ch, l, r, nl, nr, nlines) != 0;
+            if (!ok) {
+                // restart: the branch of k_px_walk
+                uint32_t sl, sr;
+                if (px_bs<COMPACT>(d, code, C, '#', l, r, sl, sr, nlines)) {
+                    uint32_t lo = 0, hi = d.nb;       // r1 = #B positions <= l
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi) / 2;
+                        if (d.bpos[mid] <= l) lo = mid + 1; else hi = mid;
+                    }
+                    const uint32_t r1 = lo;
+                    if (r1 != 0 && r1 <= d.ne) {
+                        const uint32_t bl = d.bpos[r1 - 1], br = d.epos[r1 - 1];
+                        if (bl <= l && r <= br && px_bs<COMPACT>(d, code, C, ch, bl, br, nl, nr, nlines)) {
+                            if (!restarts) { fsl = sl; fsr = sr; fk = pos; }
+                            restarts++;
+                            ok = true;
+                        }
+                    }
+                }
+            }
+            if (ok) { l = nl; r = nr; pos++; k++; continue; }
+        }
+        // the search stopped at symbol k (k == len: the read ended)
+        if (pos) {
+            if (pos >= min_len) {
+                if (WRITE) {
+                    cnt_out[at] = (unsigned long long)r - l + 1;
+                    len64[at] = pos;
+                    rec[3 * at] = make_uint2(l, r);
+                    rec[3 * at + 1] = make_uint2(fsl, fsr);
+                    rec[3 * at + 2] = make_uint2(fk, restarts);
+                    qs[at] = k - pos;
+                    ln[at] = pos;
+                }
+                at++;
+            }
+            l = 0; r = d.N; pos = 0; restarts = 0; fsl = 1; fsr = 0; fk = 0;
+        } else {
+            if (k < len) k++;                                 // symbol k starts no match: skipped
+        }
+        if (k >= len) break;
+    }
+    if (!WRITE) num[id] = at;
+}
+
 __global__ void k_px_lenkey(const uint64_t *poff, uint64_t n, uint32_t *key, uint32_t *id)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -556,7 +652,7 @@ static int px_build_prepared(fbg_pindex *ix, PxScratch &s, const PxPrep &pp)
     ix->compact = sigma <= 16;
     ix->n_nodes = n_nodes;
     ix->nblk = N1 / PX_BLK + 1;
-    ix->occ_ready = false;
+    ix->occ.ready = ix->sd.ready = false;
 
     auto U = [&](std::vector<DevBuf *> &owner, DevBuf &b, const void *h, size_t bytes) -> int {
         FBG_TRY(fbg_reserve(ctx, b, bytes + 8, &owner, false));
@@ -1190,13 +1286,29 @@ extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint6
     return FBG_OK;
 }
 
-// The front of fbg_pindex_locate and fbg_pindex_occurrences: patterns onto the device, ev0, the length sort and the
-// walk (occ: the instantiation that records the ranges into orec).  n > 0.
-static int px_search(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns, bool occ)
+enum PxMode { PX_LOCATE, PX_OCC, PX_SEEDS };
+
+// The per-pattern (or per-seed) buffers of a place state, for n of them.
+static int po_reserve(fbg_pindex *ix, PoState &s, uint64_t n)
+{
+    for (DevBuf *b : {&s.etot, &s.stot}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 8, &ix->bufs, false));
+    for (DevBuf *b : {&s.esz, &s.ssz, &s.eoff, &s.soff}) FBG_TRY(fbg_reserve(ix->ctx, *b, (n + 1) * 8, &ix->bufs, false));
+    for (DevBuf *b : {&s.rs, &s.el, &s.ss, &s.sk}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
+    return FBG_OK;
+}
+
+// The front of fbg_pindex_locate, fbg_pindex_occurrences and fbg_pindex_seeds: checks, every allocation of the call
+// that depends on n only (after hipSetDevice), patterns onto the device, ev0, and the pattern ids sorted by length into
+// oval2.  n > 0.
+static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns, PxMode mode)
 {
     fbg_ctx *ctx = ix->ctx;
     for (uint64_t k = 0; k < n_patterns; k++)
         if (pat_off[k + 1] < pat_off[k]) return fbg_fail(ctx, FBG_ERR_INVALID, "pattern offsets decrease at pattern %llu", (unsigned long long)k);
+    if (mode == PX_SEEDS)
+        for (uint64_t k = 0; k < n_patterns; k++)
+            if (pat_off[k + 1] - pat_off[k] >= (1ull << 32))
+                return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: pattern %llu has 2^32 symbols or more", who, (unsigned long long)k);
     const uint64_t base = pat_off[0], total = pat_off[n_patterns] - base;
     if (total && !patterns) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing patterns", who);
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1205,20 +1317,22 @@ static int px_search(fbg_pindex *ix, const char *who, const uint8_t *patterns, c
     FBG_TRY(fbg_reserve(ix->ctx, ix->pats, ((total + 7) & ~7ull) + 16, &ix->bufs, false));
     FBG_TRY(fbg_reserve(ix->ctx, ix->poff, (n + 1) * 8, &ix->bufs, false));
     for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->cnt_out, n * 8, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->pos_out, n * 8, &ix->bufs, false));
-    FBG_TRY(fbg_reserve(ix->ctx, ix->lines_ctr, 8, &ix->bufs, false));
-    if (occ) {      // everything fbg_pindex_occurrences allocates, here: after hipSetDevice
+    if (mode == PX_SEEDS) {
+        for (DevBuf *b : {&ix->snum, &ix->soff}) FBG_TRY(fbg_reserve(ix->ctx, *b, (n + 1) * 8, &ix->bufs, false));
+    } else {
+        FBG_TRY(fbg_reserve(ix->ctx, ix->cnt_out, n * 8, &ix->bufs, false));
+        FBG_TRY(fbg_reserve(ix->ctx, ix->pos_out, n * 8, &ix->bufs, false));
+        FBG_TRY(fbg_reserve(ix->ctx, ix->lines_ctr, 8, &ix->bufs, false));
+    }
+    if (mode == PX_OCC) {
         FBG_TRY(fbg_reserve(ix->ctx, ix->orec, n * 24, &ix->bufs, false));
-        for (DevBuf *b : {&ix->oetot, &ix->ostot}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 8, &ix->bufs, false));
-        for (DevBuf *b : {&ix->oesz, &ix->ossz, &ix->oeoff, &ix->osoff}) FBG_TRY(fbg_reserve(ix->ctx, *b, (n + 1) * 8, &ix->bufs, false));
-        for (DevBuf *b : {&ix->ors, &ix->oel, &ix->oss, &ix->osk}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
+        FBG_TRY(po_reserve(ix, ix->occ, n));
     }
     if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
     if (total) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->pats.p, patterns + base, total, hipMemcpyHostToDevice, st));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->poff.p, pat_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(ix->lines_ctr.p, 0, 8, st));
+    if (mode != PX_SEEDS) FBG_HIP_TRY(ctx, hipMemsetAsync(ix->lines_ctr.p, 0, 8, st));
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
     uint64_t *poff = ix->poff.as<uint64_t>();
     if (base) hipLaunchKernelGGL(k_px_rebase, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, poff, n, base);
@@ -1228,6 +1342,18 @@ static int px_search(fbg_pindex *ix, const char *who, const uint8_t *patterns, c
     FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
         return rocprim::radix_sort_pairs(tmp, bytes, ka, kb, va, vb, (size_t)n, 0u, 32u, st);
     }));
+    return FBG_OK;
+}
+
+// px_front and the walk (occ: the instantiation that records the ranges into orec).  n > 0.
+static int px_search(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns, bool occ)
+{
+    fbg_ctx *ctx = ix->ctx;
+    FBG_TRY(px_front(ix, who, patterns, pat_off, n_patterns, occ ? PX_OCC : PX_LOCATE));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = n_patterns;
+    uint64_t *poff = ix->poff.as<uint64_t>();
+    uint32_t *vb = ix->oval2.as<uint32_t>();
     PxDev d = px_dev(ix);
     const dim3 g(fbg_blocks(n, PX_THREADS));
     auto *co = ix->cnt_out.as<unsigned long long>(), *po = ix->pos_out.as<unsigned long long>();
@@ -1291,30 +1417,17 @@ static PvDev pv_dev(const fbg_pindex *ix)
     return d;
 }
 
-extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
-                                      uint64_t max_per_pattern, uint64_t *count, uint64_t *pos, uint32_t *restarts,
-                                      uint64_t *end_off, uint64_t *start_off, uint64_t *end_total, uint64_t *start_total,
-                                      double *device_ms)
+// k_po_sizes over n > 0 items (count, pos and rec on the device; s reserved for n) and the scans of the capped sizes
+// into the CSR offsets s.eoff / s.soff.  Shared by the occurrence and the seed calls.
+static int po_sizes(fbg_pindex *ix, PoState &s, const DevBuf &count, const DevBuf &pos, const DevBuf &rec, uint64_t n, uint64_t cap)
 {
-    if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
-    ix->occ_ready = false;
-    if (device_ms) *device_ms = 0;
-    if (!end_off || !start_off || (n_patterns && (!pat_off || !count || !pos || !restarts || !end_total || !start_total)))
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences: missing argument");
-    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_occurrences: at most 2^32 - 2 patterns per call");
-    end_off[0] = start_off[0] = 0;
-    ix->occ_n = n_patterns;
-    ix->occ_etotal = ix->occ_stotal = 0;
-    if (n_patterns == 0) { ix->occ_ready = true; return FBG_OK; }
-    const uint64_t n = n_patterns;
-    FBG_TRY(px_search(ix, "fbg_pindex_occurrences", patterns, pat_off, n, true));
     hipStream_t st = ctx->stream;
-    uint64_t *esz = ix->oesz.as<uint64_t>(), *ssz = ix->ossz.as<uint64_t>(), *eoff = ix->oeoff.as<uint64_t>(), *soff = ix->osoff.as<uint64_t>();
-    hipLaunchKernelGGL(k_po_sizes, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, ix->cnt_out.as<unsigned long long>(),
-                       ix->pos_out.as<unsigned long long>(), (const uint2 *)ix->orec.as<uint2>(), n, max_per_pattern, ix->n_edges != 0,
-                       ix->oetot.as<uint64_t>(), ix->ostot.as<uint64_t>(), esz, ssz, ix->ors.as<uint32_t>(), ix->oel.as<uint32_t>(),
-                       ix->oss.as<uint32_t>(), ix->osk.as<uint32_t>());
+    uint64_t *esz = s.esz.as<uint64_t>(), *ssz = s.ssz.as<uint64_t>(), *eoff = s.eoff.as<uint64_t>(), *soff = s.soff.as<uint64_t>();
+    hipLaunchKernelGGL(k_po_sizes, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, count.as<unsigned long long>(),
+                       pos.as<unsigned long long>(), (const uint2 *)rec.as<uint2>(), n, cap, ix->n_edges != 0,
+                       s.etot.as<uint64_t>(), s.stot.as<uint64_t>(), esz, ssz, s.rs.as<uint32_t>(), s.el.as<uint32_t>(),
+                       s.ss.as<uint32_t>(), s.sk.as<uint32_t>());
     FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
         return rocprim::exclusive_scan(tmp, bytes, esz, eoff, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
     }));
@@ -1322,56 +1435,38 @@ extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, c
         return rocprim::exclusive_scan(tmp, bytes, ssz, soff, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
     }));
     FBG_HIP_TRY(ctx, hipGetLastError());
-    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(count, ix->cnt_out.p, n * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(pos, ix->pos_out.p, n * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(restarts, ix->ors.p, n * 4, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(end_total, ix->oetot.p, n * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(start_total, ix->ostot.p, n * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(end_off, eoff, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(start_off, soff, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    float ms = 0;
-    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-    if (device_ms) *device_ms = ms;
-    if (end_off[n] >= (1ull << 32) || start_off[n] >= (1ull << 32))
-        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_occurrences: %llu ends and %llu starts to report; a list takes fewer than 2^32 "
-                        "entries (lower max_per_pattern or split the batch)", (unsigned long long)end_off[n], (unsigned long long)start_off[n]);
-    ix->occ_etotal = end_off[n];
-    ix->occ_stotal = start_off[n];
-    ix->occ_ready = true;
     return FBG_OK;
 }
 
-extern "C" int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
-                                            uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms)
+// The places of a place state into the caller's arrays (fbg_pindex_occurrences_fetch, fbg_pindex_seeds_places).
+static int po_fetch(fbg_pindex *ix, const char *who, const char *search, PoState &s, uint32_t *end_src, uint32_t *end_dst,
+                    uint32_t *end_offset, uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms)
 {
-    if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
     if (device_ms) *device_ms = 0;
-    if (!ix->occ_ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences_fetch: no fbg_pindex_occurrences result to fetch");
+    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no %s result to fetch", who, search);
     const bool ends = end_src && end_dst && end_offset, starts = start_src && start_dst && start_offset;
     if ((!ends && (end_src || end_dst || end_offset)) || (!starts && (start_src || start_dst || start_offset)))
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences_fetch: a list takes all three of its arrays or none");
-    const uint64_t ne = ends ? ix->occ_etotal : 0, ns = starts ? ix->occ_stotal : 0, n = ix->occ_n;
+        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: a list takes all three of its arrays or none", who);
+    const uint64_t ne = ends ? s.etotal : 0, ns = starts ? s.stotal : 0, n = s.n;
     if (ne + ns == 0) return FBG_OK;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    FBG_TRY(fbg_reserve(ix->ctx, ix->oplace, 3 * (ne + ns) * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, s.place, 3 * (ne + ns) * 4, &ix->bufs, false));
     if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
-    // oplace: src, dst, offset of the ends, then of the starts
-    uint32_t *pe = ix->oplace.as<uint32_t>(), *ps = pe + 3 * ne;
+    // place: src, dst, offset of the ends, then of the starts
+    uint32_t *pe = s.place.as<uint32_t>(), *ps = pe + 3 * ne;
     const PvDev d = pv_dev(ix);
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
     if (ne)
-        hipLaunchKernelGGL(k_po_expand<false>, dim3(fbg_blocks(ne, PX_THREADS)), dim3(PX_THREADS), 0, st, d, (const uint64_t *)ix->oeoff.as<uint64_t>(),
-                           n, ne, (const uint32_t *)ix->oel.as<uint32_t>(), (const uint32_t *)ix->osk.as<uint32_t>(),
-                           (const uint32_t *)ix->ors.as<uint32_t>(), pe, pe + ne, pe + 2 * ne);
+        hipLaunchKernelGGL(k_po_expand<false>, dim3(fbg_blocks(ne, PX_THREADS)), dim3(PX_THREADS), 0, st, d, (const uint64_t *)s.eoff.as<uint64_t>(),
+                           n, ne, (const uint32_t *)s.el.as<uint32_t>(), (const uint32_t *)s.sk.as<uint32_t>(),
+                           (const uint32_t *)s.rs.as<uint32_t>(), pe, pe + ne, pe + 2 * ne);
     if (ns)
-        hipLaunchKernelGGL(k_po_expand<true>, dim3(fbg_blocks(ns, PX_THREADS)), dim3(PX_THREADS), 0, st, d, (const uint64_t *)ix->osoff.as<uint64_t>(),
-                           n, ns, (const uint32_t *)ix->oss.as<uint32_t>(), (const uint32_t *)ix->osk.as<uint32_t>(),
-                           (const uint32_t *)ix->ors.as<uint32_t>(), ps, ps + ns, ps + 2 * ns);
+        hipLaunchKernelGGL(k_po_expand<true>, dim3(fbg_blocks(ns, PX_THREADS)), dim3(PX_THREADS), 0, st, d, (const uint64_t *)s.soff.as<uint64_t>(),
+                           n, ns, (const uint32_t *)s.ss.as<uint32_t>(), (const uint32_t *)s.sk.as<uint32_t>(),
+                           (const uint32_t *)s.rs.as<uint32_t>(), ps, ps + ns, ps + 2 * ns);
     FBG_HIP_TRY(ctx, hipGetLastError());
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
     if (ne) {
@@ -1389,6 +1484,184 @@ extern "C" int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, u
     FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
     if (device_ms) *device_ms = ms;
     return FBG_OK;
+}
+
+extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                                      uint64_t max_per_pattern, uint64_t *count, uint64_t *pos, uint32_t *restarts,
+                                      uint64_t *end_off, uint64_t *start_off, uint64_t *end_total, uint64_t *start_total,
+                                      double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PoState &s = ix->occ;
+    s.ready = false;
+    if (device_ms) *device_ms = 0;
+    if (!end_off || !start_off || (n_patterns && (!pat_off || !count || !pos || !restarts || !end_total || !start_total)))
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences: missing argument");
+    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_occurrences: at most 2^32 - 2 patterns per call");
+    end_off[0] = start_off[0] = 0;
+    s.n = n_patterns;
+    s.etotal = s.stotal = 0;
+    if (n_patterns == 0) { s.ready = true; return FBG_OK; }
+    const uint64_t n = n_patterns;
+    FBG_TRY(px_search(ix, "fbg_pindex_occurrences", patterns, pat_off, n, true));
+    hipStream_t st = ctx->stream;
+    FBG_TRY(po_sizes(ix, s, ix->cnt_out, ix->pos_out, ix->orec, n, max_per_pattern));
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(count, ix->cnt_out.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(pos, ix->pos_out.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(restarts, s.rs.p, n * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(end_total, s.etot.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(start_total, s.stot.p, n * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(end_off, s.eoff.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(start_off, s.soff.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    if (end_off[n] >= (1ull << 32) || start_off[n] >= (1ull << 32))
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_occurrences: %llu ends and %llu starts to report; a list takes fewer than 2^32 "
+                        "entries (lower max_per_pattern or split the batch)", (unsigned long long)end_off[n], (unsigned long long)start_off[n]);
+    s.etotal = end_off[n];
+    s.stotal = start_off[n];
+    s.ready = true;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
+                                            uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    return po_fetch(ix, "fbg_pindex_occurrences_fetch", "fbg_pindex_occurrences", ix->occ, end_src, end_dst, end_offset, start_src,
+                    start_dst, start_offset, device_ms);
+}
+
+// ---- seeds (fbg_pindex_seeds / _fetch / _places) -------------------------------------------------------------------
+// Count, then write: k_px_seeds<*, false> counts the reported seeds of every read, an exclusive scan places them (reads
+// in input order, a read's seeds contiguous and by q_start), the host learns the total and sizes the per-seed buffers,
+// k_px_seeds<*, true> walks again and writes.  From there the seeds are the patterns of po_sizes / po_fetch.
+template <bool COMPACT, bool WRITE> static void px_seeds_launch(fbg_pindex *ix, const PxDev &d, uint64_t n, uint32_t min_len)
+{
+    hipLaunchKernelGGL((k_px_seeds<COMPACT, WRITE>), dim3(fbg_blocks(n, PX_THREADS)), dim3(PX_THREADS), 0, ix->ctx->stream, d,
+                       ix->code.as<uint16_t>(), ix->C.as<uint32_t>(), ix->pats.as<uint8_t>(), ix->poff.as<uint64_t>(),
+                       ix->oval2.as<uint32_t>(), n, min_len, (WRITE ? ix->soff : ix->snum).as<uint64_t>(),
+                       ix->scnt.as<unsigned long long>(), ix->spos.as<unsigned long long>(), ix->srec.as<uint2>(),
+                       ix->sq.as<uint32_t>(), ix->slen.as<uint32_t>());
+}
+
+extern "C" int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                                uint64_t min_length, uint64_t max_per_seed, uint64_t *seed_off, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PoState &s = ix->sd;
+    s.ready = false;
+    if (device_ms) *device_ms = 0;
+    if (!seed_off || (n_patterns && !pat_off)) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds: missing argument");
+    if (min_length == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds: min_length is 1 or more");
+    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_seeds: at most 2^32 - 2 patterns per call");
+    seed_off[0] = 0;
+    s.n = 0;
+    s.etotal = s.stotal = 0;
+    if (n_patterns == 0) { s.ready = true; return FBG_OK; }
+    const uint64_t n = n_patterns;
+    FBG_TRY(px_front(ix, "fbg_pindex_seeds", patterns, pat_off, n, PX_SEEDS));
+    hipStream_t st = ctx->stream;
+    const bool none = min_length >= (1ull << 32);   // no pattern has 2^32 symbols: nothing can be reported
+    const uint32_t L = none ? 0xffffffffu : (uint32_t)min_length;
+    const PxDev d = px_dev(ix);
+    uint64_t *num = ix->snum.as<uint64_t>(), *soff = ix->soff.as<uint64_t>();
+    auto walk = [&](bool write) {
+        if (ix->compact) { if (write) px_seeds_launch<true, true>(ix, d, n, L); else px_seeds_launch<true, false>(ix, d, n, L); }
+        else { if (write) px_seeds_launch<false, true>(ix, d, n, L); else px_seeds_launch<false, false>(ix, d, n, L); }
+    };
+    if (none) {
+        std::fill(seed_off, seed_off + n + 1, (uint64_t)0);
+    } else {
+        FBG_HIP_TRY(ctx, hipMemsetAsync(num + n, 0, 8, st));
+        walk(false);
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, num, soff, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
+        }));
+        FBG_HIP_TRY(ctx, hipGetLastError());
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(seed_off, soff, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    const uint64_t S = seed_off[n];
+    if (S >= (1ull << 32))
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_seeds: %llu seeds to report; a call takes fewer than 2^32 (raise min_length or "
+                        "split the batch)", (unsigned long long)S);
+    uint64_t tot[2] = {0, 0};
+    if (S) {
+        FBG_TRY(fbg_reserve(ix->ctx, ix->srec, S * 24, &ix->bufs, false));
+        for (DevBuf *b : {&ix->scnt, &ix->spos}) FBG_TRY(fbg_reserve(ix->ctx, *b, S * 8, &ix->bufs, false));
+        for (DevBuf *b : {&ix->sq, &ix->slen}) FBG_TRY(fbg_reserve(ix->ctx, *b, S * 4, &ix->bufs, false));
+        FBG_TRY(po_reserve(ix, s, S));
+        walk(true);
+        FBG_TRY(po_sizes(ix, s, ix->scnt, ix->spos, ix->srec, S, max_per_seed));
+    }
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    if (S) {
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(&tot[0], s.eoff.as<uint64_t>() + S, 8, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(&tot[1], s.soff.as<uint64_t>() + S, 8, hipMemcpyDeviceToHost, st));
+    }
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    if (tot[0] >= (1ull << 32) || tot[1] >= (1ull << 32))
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_seeds: %llu ends and %llu starts to report; a list takes fewer than 2^32 "
+                        "entries (lower max_per_seed or split the batch)", (unsigned long long)tot[0], (unsigned long long)tot[1]);
+    s.n = S;
+    s.etotal = tot[0];
+    s.stotal = tot[1];
+    s.ready = true;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_seeds_fetch(fbg_pindex *ix, uint32_t *q_start, uint32_t *length, uint64_t *count, uint32_t *restarts,
+                                      uint64_t *end_total, uint64_t *start_total, uint64_t *end_off, uint64_t *start_off,
+                                      double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PoState &s = ix->sd;
+    if (device_ms) *device_ms = 0;
+    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds_fetch: no fbg_pindex_seeds result to fetch");
+    const uint64_t S = s.n;
+    if (S == 0) {
+        if (end_off) end_off[0] = 0;
+        if (start_off) start_off[0] = 0;
+        return FBG_OK;
+    }
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    auto get = [&](void *dst, const DevBuf &src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+    };
+    FBG_HIP_TRY(ctx, get(q_start, ix->sq, S * 4));
+    FBG_HIP_TRY(ctx, get(length, ix->slen, S * 4));
+    FBG_HIP_TRY(ctx, get(count, ix->scnt, S * 8));
+    FBG_HIP_TRY(ctx, get(restarts, s.rs, S * 4));
+    FBG_HIP_TRY(ctx, get(end_total, s.etot, S * 8));
+    FBG_HIP_TRY(ctx, get(start_total, s.stot, S * 8));
+    FBG_HIP_TRY(ctx, get(end_off, s.eoff, (S + 1) * 8));
+    FBG_HIP_TRY(ctx, get(start_off, s.soff, (S + 1) * 8));
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_seeds_places(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
+                                       uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    return po_fetch(ix, "fbg_pindex_seeds_places", "fbg_pindex_seeds", ix->sd, end_src, end_dst, end_offset, start_src, start_dst,
+                    start_offset, device_ms);
 }
 
 extern "C" uint64_t fbg_pindex_text_length(const fbg_pindex *ix) { return ix ? ix->N1 : 0; }

@@ -493,6 +493,56 @@ int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, const uint64
 int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
                                  uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms);
 
+/* Maximal exact-match seeds: every read cut greedily into the pieces the search of the index accepts.
+ *
+ * search(Q) is "locate" above: it reads Q left to right and returns (count, pos); its state after j symbols depends
+ * only on Q[:j].  For a pattern P and a minimum length L >= 1:
+ *     i = 0
+ *     while i < |P|:
+ *         k = search(P[i:]).pos             the longest prefix of P[i:] the search accepts
+ *         if k == 0:  i += 1                P[i] cannot be matched from the full range: skipped
+ *         else:       seed (i, k); i += k   the failing symbol, if any, starts the next search
+ * Seeds with k < L are consumed like the others but not reported.  The empty pattern has no seeds.  For a reported
+ * seed (q_start, length) = (i, k), count (> 0 always), restarts, end_total, start_total and the capped end and start
+ * place lists, in ascending SA slot order, are what fbg_pindex_occurrences and fbg_pindex_occurrences_fetch report for
+ * the pattern P[i : i + k] with max_per_pattern = max_per_seed: a seed adds no notion of a match to the occurrence
+ * calls, and it shares their looseness (no path is verified, seeds are not chained).  Patterns holding '#' or zero
+ * bytes get no special treatment: whatever the search does with them is what a seed is.
+ *
+ * Three calls, because the number of seeds is known only after the search and the buffers are the caller's:
+ *   fbg_pindex_seeds         search and sizes.  seed_off: n_patterns + 1 CSR offsets of the reported seeds (pattern k's
+ *       seeds are entries seed_off[k] .. seed_off[k + 1] of the fetched arrays, in ascending q_start; patterns in input
+ *       order).  The device walks every read twice: a pass that counts the reported seeds, a scan, and a pass that
+ *       writes one record per seed (56 bytes; nothing is reserved for seeds that are not there); the sizes and scans of
+ *       fbg_pindex_occurrences then run over the seeds.  *device_ms (may be NULL): device time from the length sort to
+ *       the scans, the host's look at the seed total between the two passes included, without the other copies.
+ *   fbg_pindex_seeds_fetch   per seed (seed_off[n_patterns] entries; end_off / start_off one more, the CSR offsets of
+ *       the capped place lists): any pointer may be NULL.  *device_ms (may be NULL): device time of the copies.
+ *   fbg_pindex_seeds_places  the places of the seeds, as fbg_pindex_occurrences_fetch: end_* take end_off[seeds]
+ *       entries each, start_* start_off[seeds]; either list may be left out by passing NULL for its three arrays; may
+ *       be called again.  *device_ms (may be NULL): device time of the expansion kernels.
+ * The seeds stay on the device until the next fbg_pindex_seeds on this index.  They are kept apart from the ranges of
+ * fbg_pindex_occurrences: fbg_pindex_occurrences_fetch after a seeds call still returns the places of the last
+ * fbg_pindex_occurrences, and the other way round.  The calls leave fbg_pindex_stats' search_ms and occ_lines,
+ * fbg_pindex_validate's results and the context's segmentation results alone.
+ * Errors: a NULL index, a NULL seed_off, min_length == 0, a NULL pat_off with n_patterns > 0, missing pattern bytes,
+ * decreasing offsets, a fetch or places call without a successful fbg_pindex_seeds before it, one or two of a place
+ * list's three arrays NULL: FBG_ERR_INVALID.  A pattern of 2^32 symbols or more, 2^32 - 1 patterns or more, 2^32
+ * reported seeds or more, a capped place list of 2^32 entries or more: FBG_ERR_TOO_LARGE (nothing to fetch then).
+ * n_patterns == 0: seed_off[0] = 0, FBG_OK.  A min_length of 2^32 or more, which no pattern reaches: no seeds, FBG_OK
+ * (the patterns are checked as always).  The per-call scratch (16 bytes per pattern, about 130 per reported seed,
+ * 12 per reported place) is owned by the index. */
+/* search and sizes: seed_off[n_patterns + 1] = CSR of the reported seeds per pattern */
+int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                     uint64_t min_length, uint64_t max_per_seed, uint64_t *seed_off, double *device_ms);
+/* per seed (seed_off[n_patterns] entries; end_off / start_off one more): any pointer may be NULL */
+int fbg_pindex_seeds_fetch(fbg_pindex *ix, uint32_t *q_start, uint32_t *length, uint64_t *count, uint32_t *restarts,
+                           uint64_t *end_total, uint64_t *start_total, uint64_t *end_off, uint64_t *start_off,
+                           double *device_ms);
+/* places of the seeds, as fbg_pindex_occurrences_fetch: either list may be left out, may be called again */
+int fbg_pindex_seeds_places(fbg_pindex *ix, uint32_t *end_src, uint32_t *end_dst, uint32_t *end_offset,
+                            uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms);
+
 /* ---- the pattern index of a segmentation, built on the device; validation and repair of a segmentation ------------
  *
  * fbg_pindex_build_segmentation: the pattern index of the elastic founder graph that `boundaries` (the fbg_minmax_dp
