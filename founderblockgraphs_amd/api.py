@@ -437,9 +437,25 @@ class PatternIndex:
         self._eng._chk(self._L.fbg_pindex_locate(self._h, _u8(data), _u64(off), k, _u64(count), _u64(pos)))
         return count[:k], pos[:k]
 
-    def occurrences(self, patterns, max_per_pattern=64):
+    def _msa_coords(self, call, ne, ns):
+        """The four arrays of fbg_pindex_occurrences_msa / fbg_pindex_seeds_msa for ne ends and ns starts, and device ms."""
+        out = [np.zeros(max(k, 1), dtype=np.uint32) for k in (ne, ne, ns, ns)]
+        ms = C.c_double(0)
+        self._eng._chk(call(self._h, *[a.ctypes.data_as(_lib.u32p) for a in out], C.byref(ms)))
+        return [a[:k] for a, k in zip(out, (ne, ne, ns, ns))], ms.value
+
+    def msa_stats(self):
+        """{map_bytes, gapped_nodes, sample_columns} of the MSA coordinate table (fbg_pindex_msa_stats; an index built
+        by Engine.pattern_index_of_segmentation only)."""
+        mb, gn, sc = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._eng._chk(self._L.fbg_pindex_msa_stats(self._h, C.byref(mb), C.byref(gn), C.byref(sc)))
+        return {"map_bytes": mb.value, "gapped_nodes": gn.value, "sample_columns": sc.value}
+
+    def occurrences(self, patterns, max_per_pattern=64, msa=False):
         """The search of locate() plus the places where each found pattern ends and starts, at most max_per_pattern
-        of each per pattern (fbg_pindex_occurrences and fbg_pindex_occurrences_fetch) -> Occurrences."""
+        of each per pattern (fbg_pindex_occurrences and fbg_pindex_occurrences_fetch) -> Occurrences.  msa=True (an
+        index built by Engine.pattern_index_of_segmentation only): also the MSA row and column of every place
+        (fbg_pindex_occurrences_msa)."""
         if max_per_pattern < 0:
             raise ValueError("max_per_pattern must be 0 or more")
         data, off = _concat(patterns)
@@ -456,13 +472,14 @@ class PatternIndex:
         starts = [np.zeros(max(ns, 1), dtype=np.uint32) for _ in range(3)]
         self._eng._chk(self._L.fbg_pindex_occurrences_fetch(self._h, *[a.ctypes.data_as(_lib.u32p) for a in ends + starts],
                                                             C.byref(ms2)))
+        coords, ms3 = self._msa_coords(self._L.fbg_pindex_occurrences_msa, ne, ns) if msa else (None, 0.0)
         return Occurrences(self._label_len, count[:k], pos[:k], rs[:k], et[:k], st[:k], eoff, soff, [a[:ne] for a in ends],
-                           [a[:ns] for a in starts], ms1.value, ms2.value)
+                           [a[:ns] for a in starts], ms1.value, ms2.value, coords, ms3)
 
-    def seeds(self, patterns, min_length=1, max_per_seed=0):
+    def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False):
         """Every read cut greedily into the maximal pieces the search accepts (fbg_pindex_seeds, _fetch and _places):
         seeds of at least min_length symbols, each with what occurrences() reports for that substring, at most
-        max_per_seed places per seed and list -> Seeds."""
+        max_per_seed places per seed and list -> Seeds.  msa=True: as for occurrences() (fbg_pindex_seeds_msa)."""
         if min_length < 1:
             raise ValueError("min_length must be 1 or more")
         if max_per_seed < 0:
@@ -484,8 +501,9 @@ class PatternIndex:
         ends = [np.zeros(max(ne, 1), dtype=np.uint32) for _ in range(3)]
         starts = [np.zeros(max(ns, 1), dtype=np.uint32) for _ in range(3)]
         self._eng._chk(self._L.fbg_pindex_seeds_places(self._h, *[u32(a) for a in ends + starts], C.byref(ms3)))
+        coords, ms4 = self._msa_coords(self._L.fbg_pindex_seeds_msa, ne, ns) if msa else (None, 0.0)
         occ = Occurrences(self._label_len, count[:n], ln[:n].astype(np.uint64), rs[:n], et[:n], st[:n], eoff, soff,
-                          [a[:ne] for a in ends], [a[:ns] for a in starts], ms1.value, ms2.value + ms3.value)
+                          [a[:ne] for a in ends], [a[:ns] for a in starts], ms1.value, ms2.value + ms3.value, coords, ms4)
         return Seeds(seed_off, q[:n], ln[:n], occ)
 
     def download(self):
@@ -541,11 +559,14 @@ class Occurrences:
       end_src, end_dst, end_offset        the edge (node indices) and the index into label(src) + label(dst) of the
                                           match's last symbol
       start_src, start_dst, start_offset  the same for its first symbol
-    search_ms, fetch_ms: device time of the two calls.  A (start, end) pair of a pattern with restarts is not checked to
-    lie on one path."""
+    and, asked for with msa=True (None otherwise), aligned with them:
+      end_row, end_col, start_row, start_col   uint32: the MSA cell of that symbol in the representative row of its node
+                                          (one witness row per place; 0xffffffff in both for an offset outside the edge)
+    search_ms, fetch_ms: device time of the two calls; msa_ms: of the MSA coordinates.  A (start, end) pair of a pattern
+    with restarts is not checked to lie on one path."""
 
     def __init__(self, label_len, count, pos, restarts, end_total, start_total, end_off, start_off, ends, starts, search_ms,
-                 fetch_ms):
+                 fetch_ms, msa=None, msa_ms=0.0):
         self._label_len = label_len
         self.count, self.pos, self.restarts = count, pos, restarts
         self.end_total, self.start_total = end_total, start_total
@@ -554,6 +575,8 @@ class Occurrences:
         self.start_src, self.start_dst, self.start_offset = starts
         self.search_ms, self.fetch_ms = search_ms, fetch_ms
         self.device_ms = (search_ms, fetch_ms)
+        self.end_row, self.end_col, self.start_row, self.start_col = msa if msa is not None else (None,) * 4
+        self.msa_ms = msa_ms
 
     def _rows(self, which, k):
         off = self.end_off if which == "end" else self.start_off
@@ -567,6 +590,21 @@ class Occurrences:
     def starts(self, k):
         """int64[rows, 3]: (src, dst, offset) of pattern k's reported starts."""
         return self._rows("start", k)
+
+    def _msa_rows(self, which, k):
+        if getattr(self, f"{which}_row") is None:
+            raise ValueError("no MSA coordinates: ask for them with msa=True")
+        off = self.end_off if which == "end" else self.start_off
+        a, b = int(off[k]), int(off[k + 1])
+        return np.stack([getattr(self, f"{which}_{f}")[a:b] for f in ("row", "col")], axis=1).astype(np.int64)
+
+    def msa_ends(self, k):
+        """int64[rows, 2]: (MSA row, MSA column) of pattern k's reported ends, aligned with ends(k)."""
+        return self._msa_rows("end", k)
+
+    def msa_starts(self, k):
+        """int64[rows, 2]: (MSA row, MSA column) of pattern k's reported starts, aligned with starts(k)."""
+        return self._msa_rows("start", k)
 
     def as_nodes(self, which="end"):
         """Places as (node, offset in the node's label): src where offset < |label(src)|, else dst with the offset

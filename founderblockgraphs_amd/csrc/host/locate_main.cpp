@@ -2,7 +2,7 @@
 // libfbg_hip.so (include/fbg_hip.h, fbg_pindex_*).  Stands in for locate_patterns of the reference with a graph in
 // place of its .index file:
 //
-//   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]
+//   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -18,6 +18,13 @@
 //   S <tab> q_start <tab> length <tab> count <tab> restarts
 // followed, with --occurrences, by that seed's E / B lines as above; the last line is `Pattern? X out of Y patterns
 // seeded`, X the patterns with a seed.  --error-on-not-found then fails at the first pattern without one.
+// --msa=msa.fasta names the MSA the graph was cut from (read with the elastic rules: no gap filter).  The index is then
+// built from that MSA and the segmentation of the graph's M and X lines (fbg_pindex_build_segmentation; block i ends at
+// column X[i + 1] - 2, the last one at n), checked against the S lines (node count and label lengths), and every E / B
+// line gets `<tab> row <tab> column` appended: the MSA cell, from 0, of that symbol in the representative row of its node
+// (fbg_pindex_occurrences_msa / _seeds_msa; `*` in both for an offset outside the edge).  Without --occurrences the
+// option only changes how the index is built.  A FASTA that does not fit the graph fails with a message.
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -28,37 +35,87 @@
 #include <vector>
 #include "../../../include/fbg_hip.h"
 #include "xgfa_read.hpp"
+#include "fasta.hpp"
 
 static int usage(const char *msg)
 {
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
+              << "                  [--msa=msa.fasta]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
               << "  --seeds[=L]        cut every pattern greedily into the maximal pieces the search accepts and print, per\n"
               << "                     piece of L symbols or more (default 1), an S line: q_start, length, count, restarts;\n"
-              << "                     with --occurrences the E / B lines of every piece follow its S line\n";
+              << "                     with --occurrences the E / B lines of every piece follow its S line\n"
+              << "  --msa=msa.fasta    the MSA the graph was cut from: the index is built from it and the graph's M and X\n"
+              << "                     lines, and every E / B line ends with the MSA row and column (from 0) of that symbol\n"
+              << "                     in the representative row of its node (* for an offset outside the edge)\n";
     return EXIT_FAILURE;
 }
 
-// the E / B lines of item k of a place state: offsets o[2], totals t[2], places p[6] (end src / dst / offset, start ...)
+// The M line (rows, columns) and the X line (the first column of every block, from 1) of an xGFA file.
+static bool read_segmentation(const std::string &path, uint64_t &m, uint64_t &n, std::vector<uint64_t> &starts, std::string &error)
+{
+    std::ifstream is(path, std::ios::binary);
+    if (!is) { error = "cannot open " + path; return false; }
+    bool have_m = false, have_x = false;
+    std::string line;
+    while (std::getline(is, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.size() < 2 || (line[0] != 'M' && line[0] != 'X') || line[1] != '\t') continue;
+        std::vector<uint64_t> v;
+        size_t a = 2;
+        while (a <= line.size()) {
+            size_t b = line.find('\t', a);
+            if (b == std::string::npos) b = line.size();
+            const std::string f = line.substr(a, b - a);
+            if (f.empty() && b == line.size()) break;                         // a trailing tab
+            if (f.empty() || f.size() > 19 || f.find_first_not_of("0123456789") != std::string::npos) {
+                error = path + ": malformed " + line[0] + " line";
+                return false;
+            }
+            v.push_back(std::strtoull(f.c_str(), nullptr, 10));
+            a = b + 1;
+        }
+        if (line[0] == 'M') {
+            if (have_m || v.size() != 2) { error = path + ": malformed or repeated M line"; return false; }
+            have_m = true; m = v[0]; n = v[1];
+        } else {
+            if (have_x) { error = path + ": a second X line"; return false; }
+            have_x = true; starts = v;
+        }
+    }
+    if (!have_m || !have_x || starts.empty()) { error = path + ": --msa needs the graph's M and X lines"; return false; }
+    return true;
+}
+
+// the E / B lines of item k of a place state: offsets o[2], totals t[2], places p[6] (end src / dst / offset, start ...);
+// rc (NULL without --msa): end row / column, start row / column
 static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint64_t> *const o[2], const std::vector<uint64_t> *const t[2],
-                         const std::vector<uint32_t> *p)
+                         const std::vector<uint32_t> *p, const std::vector<uint32_t> *rc = nullptr)
 {
     for (int w = 0; w < 2; w++) {
         const std::vector<uint64_t> &off = *o[w];
         const uint64_t total = (*t[w])[k];
         const char *tag = w ? "B\t" : "E\t";
-        for (uint64_t i = off[k]; i < off[k + 1]; i++)
-            std::cout << tag << g.ids[p[3 * w][i]] << '\t' << g.ids[p[3 * w + 1][i]] << '\t' << p[3 * w + 2][i] << '\n';
+        for (uint64_t i = off[k]; i < off[k + 1]; i++) {
+            std::cout << tag << g.ids[p[3 * w][i]] << '\t' << g.ids[p[3 * w + 1][i]] << '\t' << p[3 * w + 2][i];
+            if (rc) {
+                const uint32_t r = rc[2 * w][i], c = rc[2 * w + 1][i];
+                if (r == 0xffffffffu && c == 0xffffffffu) std::cout << "\t*\t*";
+                else std::cout << '\t' << r << '\t' << c;
+            }
+            std::cout << '\n';
+        }
         if (total > off[k + 1] - off[k]) std::cout << tag << "...\t" << total - (off[k + 1] - off[k]) << " more\n";
     }
 }
 
 int main(int argc, char **argv)
 {
-    std::string graph, patterns;
+    std::string graph, patterns, msa_path;
+    bool have_msa = false;
     bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false;
     uint64_t max_places = 64, min_seed = 1;
     for (int i = 1; i < argc; i++) {
@@ -69,7 +126,8 @@ int main(int argc, char **argv)
             if (a == name && i + 1 < argc) { out = argv[++i]; have = true; return true; }
             return false;
         };
-        if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns)) continue;
+        if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns) ||
+            value("--msa", msa_path, have_msa)) continue;
         if (a == "--error-on-not-found") { error_on_not_found = true; continue; }
         if (a == "--occurrences") { occurrences = true; continue; }
         if (a.compare(0, 14, "--occurrences=") == 0) {
@@ -99,10 +157,30 @@ int main(int argc, char **argv)
         return usage(("unknown argument " + a).c_str());
     }
     if (!have_graph || graph.empty()) return usage("--graph is required");
+    if (have_msa && msa_path.empty()) return usage("--msa takes a FASTA file");
 
     XgfaGraph g;
     std::string error;
     if (!read_xgfa_graph(graph, g, error)) { std::cerr << "fbg_locate: " << error << "\n"; return EXIT_FAILURE; }
+
+    Msa msa;
+    std::vector<uint64_t> bounds;                   // inclusive block ends, the last one n (fbg_minmax_dp's convention)
+    if (have_msa) {
+        uint64_t gm = 0, gn = 0;
+        std::vector<uint64_t> xs;
+        if (!read_segmentation(graph, gm, gn, xs, error)) { std::cerr << "fbg_locate: " << error << "\n"; return EXIT_FAILURE; }
+        if (!read_msa(msa_path, 1, true, false, msa)) { std::cerr << "fbg_locate: cannot open " << msa_path << "\n"; return EXIT_FAILURE; }
+        if (msa.m != gm || msa.n != gn) {
+            std::cerr << "fbg_locate: " << msa_path << " does not fit " << graph << ": the MSA has " << msa.m << " rows and " << msa.n
+                      << " columns, the M line says " << gm << " and " << gn << "\n";
+            return EXIT_FAILURE;
+        }
+        for (size_t i = 1; i < xs.size(); i++) {
+            if (xs[i] < 2) { std::cerr << "fbg_locate: " << graph << ": malformed X line\n"; return EXIT_FAILURE; }
+            bounds.push_back(xs[i] - 2);
+        }
+        bounds.push_back(gn);
+    }
 
     std::ifstream pf;
     if (have_patterns) {
@@ -128,8 +206,34 @@ int main(int argc, char **argv)
     if (rc != FBG_OK) { std::cerr << "fbg_locate: " << fbg_last_error(nullptr) << "\n"; return EXIT_FAILURE; }
     const uint64_t nodes = g.label_off.size() - 1;
     fbg_pindex *ix = nullptr;
-    rc = fbg_pindex_build(ctx, (const uint8_t *)g.labels.data(), g.label_off.data(), nodes, g.edge_off.data(),
-                          g.edge_dst.data(), &ix);
+    if (have_msa) {
+        // the index of the MSA's segmentation, which must be the graph that was read
+        std::string why;
+        if (bounds.size() > 1 && !std::is_sorted(bounds.begin(), bounds.end() - 1)) why = "the X line does not increase";
+        rc = fbg_msa_load_host(ctx, msa.cells.data(), msa.m, msa.n);
+        if (rc == FBG_OK && why.empty()) rc = fbg_pindex_build_segmentation(ctx, bounds.data(), bounds.size(), &ix);
+        if (rc == FBG_OK && why.empty()) {
+            std::vector<uint32_t> len(nodes + 1);
+            if (fbg_pindex_node_count(ix) != nodes)
+                why = "its segmentation has " + std::to_string(fbg_pindex_node_count(ix)) + " nodes, the graph " + std::to_string(nodes);
+            else if ((rc = fbg_pindex_node_info(ix, len.data(), nullptr, nullptr)) == FBG_OK)
+                for (uint64_t u = 0; u < nodes && why.empty(); u++)
+                    if (len[u] != g.label_off[u + 1] - g.label_off[u])
+                        why = "node " + std::to_string(g.ids[u]) + " has " + std::to_string(g.label_off[u + 1] - g.label_off[u]) +
+                              " symbols in the graph and " + std::to_string(len[u]) + " in the MSA";
+        }
+        if (!why.empty()) {
+            std::cerr << "fbg_locate: " << msa_path << " does not fit " << graph << ": " << why << "\n";
+            fbg_pindex_destroy(ix);
+            fbg_ctx_destroy(ctx);
+            return EXIT_FAILURE;
+        }
+    } else {
+        rc = fbg_pindex_build(ctx, (const uint8_t *)g.labels.data(), g.label_off.data(), nodes, g.edge_off.data(),
+                              g.edge_dst.data(), &ix);
+    }
+    std::vector<uint32_t> coords[4];                // end row / column, start row / column (--msa with --occurrences)
+    const bool want_coords = have_msa && occurrences;
     std::vector<uint64_t> count(np + 1), pos(np + 1), end_off, start_off, end_total, start_total;
     std::vector<uint32_t> restarts, places[6];      // end src / dst / offset, start src / dst / offset
     if (occurrences) {
@@ -152,6 +256,10 @@ int main(int argc, char **argv)
             rc = fbg_pindex_seeds_places(ix, places[0].data(), places[1].data(), places[2].data(), places[3].data(),
                                          places[4].data(), places[5].data(), nullptr);
         }
+        if (rc == FBG_OK && want_coords) {
+            for (int k = 0; k < 4; k++) coords[k].resize((k < 2 ? end_off[ns] : start_off[ns]) + 1);
+            rc = fbg_pindex_seeds_msa(ix, coords[0].data(), coords[1].data(), coords[2].data(), coords[3].data(), nullptr);
+        }
     }
     if (rc == FBG_OK && !occurrences && !seeds)
         rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
@@ -162,6 +270,10 @@ int main(int argc, char **argv)
         for (int k = 0; k < 6; k++) places[k].resize((k < 3 ? end_off[np] : start_off[np]) + 1);
         rc = fbg_pindex_occurrences_fetch(ix, places[0].data(), places[1].data(), places[2].data(), places[3].data(),
                                           places[4].data(), places[5].data(), nullptr);
+    }
+    if (rc == FBG_OK && want_coords && !seeds) {
+        for (int k = 0; k < 4; k++) coords[k].resize((k < 2 ? end_off[np] : start_off[np]) + 1);
+        rc = fbg_pindex_occurrences_msa(ix, coords[0].data(), coords[1].data(), coords[2].data(), coords[3].data(), nullptr);
     }
     if (rc != FBG_OK) {
         std::cerr << "fbg_locate: " << fbg_last_error(ctx) << "\n";
@@ -186,7 +298,7 @@ int main(int argc, char **argv)
             found += ns != 0;
             for (uint64_t j = seed_off[k]; j < seed_off[k + 1]; j++) {
                 std::cout << "S\t" << q_start[j] << '\t' << length[j] << '\t' << seed_count[j] << '\t' << restarts[j] << '\n';
-                if (occurrences) print_places(g, j, o, t, places);
+                if (occurrences) print_places(g, j, o, t, places, want_coords ? coords : nullptr);
             }
         }
         std::cout << "Pattern? " << found << " out of " << np << " patterns seeded" << std::endl;
@@ -199,7 +311,7 @@ int main(int argc, char **argv)
             if (error_on_not_found) { std::cout.flush(); return EXIT_FAILURE; }
         } else {
             found++;
-            if (occurrences) print_places(g, k, o, t, places);
+            if (occurrences) print_places(g, k, o, t, places, want_coords ? coords : nullptr);
         }
     }
     std::cout << "Pattern? " << found << " out of " << np << " patterns found" << std::endl;

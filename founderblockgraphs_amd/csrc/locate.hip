@@ -28,6 +28,11 @@
 //   k_ps_*                           the index of a segmentation's graph without the host (fbg_pindex_build_segmentation):
 //                                    labels gathered from the resident MSA, edges, validation tables and the byte
 //                                    histogram from the device stage of fbg_block_graph ("prepare from a segmentation");
+//   k_pm_units / k_pm_fill           the MSA coordinate table of such an index: per node its representative row, first
+//                                    column and, for a row with gaps in the block, a bitmap of its non-gap cells with a
+//                                    running count every PM_W words;
+//   k_po_expand_msa                  k_po_expand's walk from a reported place to its edge and offset, then through that
+//                                    table to the MSA row and column of the place (fbg_pindex_occurrences_msa / _seeds_msa);
 //   k_sv_cuts                        the cuts before blocks that hold an INVALID node (fbg_segmentation_validate / _repair).
 //
 // occ layout.  Symbols are remapped to dense codes in byte order (the sentinel is code 0, '#' code 1).  With at
@@ -53,12 +58,15 @@
 #define PV_CSHIFT 8           // the coarse edge table holds the edge of every 2^PV_CSHIFT-th text position
 #define PV_SHORT 16           // ranges of at most this many slots are scanned by one lane, longer ones by a wave
 #define PV_NONE 0xffffffffu   // no witness
+#define PM_W 8                // the MSA coordinate table keeps a running non-gap count every PM_W bitmap words (512 columns)
+#define PM_NONE 0xffffffffu   // a node without a bitmap (no gap in its row's stretch); the coordinate of no cell
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
 // and the places of the last fetch.  Grow-only, on the index's buffer list.
 struct PoState {
     DevBuf etot, stot, esz, ssz, eoff, soff, rs, el, ss, sk, place;
+    DevBuf msa;               // the rows and columns of the last fbg_pindex_occurrences_msa / _seeds_msa, apart from place
     bool ready = false;
     uint64_t n = 0, etotal = 0, stotal = 0;
 };
@@ -83,6 +91,13 @@ struct fbg_pindex {
     DevBuf snode_block, sfirst, scut, sctr;
     bool from_segmentation = false;
     uint64_t seg_nb = 0;
+    // the MSA coordinate table of fbg_pindex_build_segmentation (not in index_bytes, not in table_bytes): mnode, one
+    // uint4 per node (representative row, first column of the block, first unit of the node's bitmap or PM_NONE, width
+    // of the block); mbits, u64 units: per gapped node, for every PM_W bitmap words, the non-gap cells before them and
+    // then those words
+    DevBuf mnode, mbits;
+    bool has_map = false;
+    uint64_t map_units = 0, map_gapped = 0;
     hipEvent_t sv0 = nullptr, sv1 = nullptr;
     // fbg_pindex_occurrences: the walk's record per pattern (3 x uint2) and the place state of its patterns;
     // fbg_pindex_seeds: per pattern the number of reported seeds and its scan, per seed what the walk wrote (the same
@@ -526,6 +541,7 @@ struct PxScratch {
     DevBuf labels, loff, elen, eoff, keysA, keysB, valsA, valsB, cidx, cidx2, rank, headv, hscan, head, keep,
            cntT, cntX, code_u8, count;
     DevBuf nrow, len64, ebase, firstE, nout, nin, hist;     // px_prepare_segmentation
+    DevBuf munit, muoff, mctr;                              // ... its MSA coordinate table
     std::vector<DevBuf *> bufs;
     ~PxScratch() { fbg_release_all(nullptr, bufs); }
 };
@@ -885,6 +901,67 @@ __global__ __launch_bounds__(PX_THREADS) void k_ps_labels(const uint8_t *msa, ui
     }
 }
 
+// ---- the MSA coordinate table --------------------------------------------------------------------------------------
+// Node u of block [x0, x1) with representative row r: col(u, o) = the column of the o-th non-gap cell of row r in the
+// block.  A row without a gap there (|label(u)| == x1 - x0) needs no table: col = x0 + o.  Any other node gets
+// nw = ceil((x1 - x0) / 64) bitmap words (bit k of word w: cell x0 + 64 w + k is not '-'), laid out in groups of PM_W
+// words, each group headed by one unit that holds the non-gap cells before it: nw + ceil(nw / PM_W) u64 units.
+__host__ __device__ __forceinline__ uint64_t pm_units(uint64_t width)
+{
+    const uint64_t nw = (width + 63) / 64;
+    return nw + (nw + PM_W - 1) / PM_W;
+}
+
+// units[u] of every node (0 without gaps; units[n_nodes] = 0 for the scan); *gapped: nodes with a bitmap
+__global__ void k_pm_units(const uint64_t *bounds, uint64_t n, const uint32_t *node_block, const uint64_t *len64, uint64_t n_nodes,
+                           uint64_t *units, unsigned long long *gapped)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool gap = false;
+    if (u < n_nodes) {
+        uint64_t x0, x1;
+        ps_block_range(bounds, n, node_block[u], x0, x1);
+        gap = len64[u] != x1 - x0;
+        units[u] = gap ? pm_units(x1 - x0) : 0;
+    } else if (u == n_nodes) {
+        units[u] = 0;
+    }
+    const uint64_t bal = __ballot(gap);
+    if ((threadIdx.x % FBG_WAVE) == 0 && bal) atomicAdd(gapped, (unsigned long long)__popcll(bal));
+}
+
+// One wave per node (grid-stride), the walk of k_ps_labels: every step's ballot is one bitmap word.  uoff: the exclusive
+// scan of units (uoff[u + 1] - uoff[u] != 0: the node has a bitmap; its last unit is uoff[u] + units - 1 < uoff[u + 1]).
+// n < 2^32 and uoff[n_nodes] < 2^32 - 1 are the caller's checks.
+__global__ __launch_bounds__(PX_THREADS) void k_pm_fill(const uint8_t *msa, uint64_t n, const uint64_t *bounds, const uint32_t *node_block,
+                                                       const uint32_t *node_row, uint64_t n_nodes, const uint64_t *uoff, uint4 *mnode,
+                                                       uint64_t *mbits)
+{
+    const unsigned lane = threadIdx.x % FBG_WAVE;
+    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x / FBG_WAVE);
+    for (uint64_t u = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FBG_WAVE; u < n_nodes; u += nw) {
+        uint64_t x0, x1;
+        ps_block_range(bounds, n, node_block[u], x0, x1);
+        const uint32_t r = node_row[u];
+        const uint64_t base = uoff[u];
+        const bool gap = uoff[u + 1] != base;
+        if (lane == 0) mnode[u] = make_uint4(r, (uint32_t)x0, gap ? (uint32_t)base : PM_NONE, (uint32_t)(x1 - x0));
+        if (!gap) continue;
+        const uint8_t *row = msa + (uint64_t)r * n;
+        uint64_t before = 0, w = 0;
+        for (uint64_t xb = x0; xb < x1; xb += FBG_WAVE, w++) {
+            const uint64_t x = xb + lane;
+            const uint64_t bal = __ballot(x < x1 && row[x] != '-');
+            if (lane == 0) {
+                uint64_t *grp = mbits + base + (w / PM_W) * (PM_W + 1);
+                if (w % PM_W == 0) grp[0] = before;
+                grp[1 + w % PM_W] = bal;
+            }
+            before += __popcll(bal);
+        }
+    }
+}
+
 __global__ void k_ps_edges(const unsigned long long *edges, const unsigned long long *edge_count, const uint64_t *ebase, uint64_t m,
                            uint64_t nb, uint32_t *esrc, uint32_t *edst)
 {
@@ -951,7 +1028,9 @@ __global__ __launch_bounds__(PX_THREADS) void k_ps_hist(const uint8_t *labels, c
         if (h[c]) atomicAdd(&hist[c], (unsigned long long)h[c]);
 }
 
-static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, PxPrep &pp)
+// with_map: also the MSA coordinate table (fbg_pindex_build_segmentation; the rounds of fbg_segmentation_validate /
+// _repair report no places and leave it out)
+static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, PxPrep &pp, bool with_map)
 {
     fbg_ctx *ctx = ix->ctx;
     BlockGraphDev g;
@@ -994,8 +1073,27 @@ static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t 
         return rocprim::inclusive_scan(tmp, bytes, ecount, ebase + 1, (size_t)nb, rocprim::plus<uint64_t>(), st);
     }));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ebase, 0, 8, st));
-    uint64_t h_L = 0, h_E = 0;
-    unsigned long long h_bad = 0;
+    uint64_t h_L = 0, h_E = 0, h_units = 0;
+    unsigned long long h_bad = 0, h_gapped = 0;
+    ix->has_map = false;
+    if (with_map) {
+        // the units of every node's bitmap and their scan; the host reads the total with the other sizes below
+        if (n >= (1ull << 32))
+            return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "the MSA has 2^32 columns or more; the MSA coordinates of a pattern index are 32-bit");
+        FBG_TRY(R(s.bufs, s.munit, (n_nodes + 1) * 8));
+        FBG_TRY(R(s.bufs, s.muoff, (n_nodes + 1) * 8));
+        FBG_TRY(R(s.bufs, s.mctr, 8));
+        FBG_TRY(R(ix->bufs, ix->mnode, n_nodes * 16));
+        uint64_t *munit = s.munit.as<uint64_t>(), *muoff = s.muoff.as<uint64_t>();
+        FBG_HIP_TRY(ctx, hipMemsetAsync(s.mctr.p, 0, 8, st));
+        hipLaunchKernelGGL(k_pm_units, dim3(fbg_blocks(n_nodes + 1, 256)), dim3(256), 0, st, g.bounds, n, (const uint32_t *)node_block,
+                           (const uint64_t *)len64, n_nodes, munit, s.mctr.as<unsigned long long>());
+        FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, munit, muoff, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
+        }));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_units, muoff + n_nodes, 8, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_gapped, s.mctr.p, 8, hipMemcpyDeviceToHost, st));
+    }
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_L, loff + n_nodes, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_E, ebase + nb, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st));
@@ -1007,6 +1105,18 @@ static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t 
     hipLaunchKernelGGL(k_ps_labels<true>, gw, dim3(PX_THREADS), 0, st, ctx->d_msa, n, g.bounds, (const uint32_t *)node_block,
                        (const uint32_t *)node_row, n_nodes, (uint64_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr,
                        (const uint64_t *)loff, s.labels.as<uint8_t>());
+    if (with_map) {
+        // unit offsets are kept in 32 bits with PM_NONE set aside; the sums above are 64-bit, so nothing wraps
+        if (h_units >= PM_NONE)
+            return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "the MSA coordinate table of this segmentation takes %llu 64-bit words; it holds "
+                            "fewer than 2^32 - 1", (unsigned long long)h_units);
+        FBG_TRY(R(ix->bufs, ix->mbits, h_units * 8));
+        hipLaunchKernelGGL(k_pm_fill, gw, dim3(PX_THREADS), 0, st, ctx->d_msa, n, g.bounds, (const uint32_t *)node_block,
+                           (const uint32_t *)node_row, n_nodes, (const uint64_t *)s.muoff.as<uint64_t>(), ix->mnode.as<uint4>(),
+                           ix->mbits.as<uint64_t>());
+        ix->map_units = h_units;
+        ix->map_gapped = h_gapped;
+    }
     FBG_TRY(R(ix->bufs, ix->vesrc, E * 4));
     FBG_TRY(R(ix->bufs, ix->vedst, E * 4));
     FBG_TRY(R(ix->bufs, ix->vestart, (E + 1) * 4));
@@ -1053,14 +1163,15 @@ static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t 
     pp.n_nodes = n_nodes; pp.E = E; pp.N1 = h_N + 1;
     pp.eoff_ready = true;
     ix->from_segmentation = true;
+    ix->has_map = with_map;
     ix->seg_nb = nb;
     return FBG_OK;
 }
 
-static int px_build_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb)
+static int px_build_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, bool with_map)
 {
     PxPrep pp;
-    FBG_TRY(px_prepare_segmentation(ix, s, boundaries, nb, pp));
+    FBG_TRY(px_prepare_segmentation(ix, s, boundaries, nb, pp, with_map));
     return px_build_prepared(ix, s, pp);
 }
 
@@ -1264,6 +1375,83 @@ __global__ __launch_bounds__(PX_THREADS) void k_po_expand(PvDev d, const uint64_
     osrc[i] = d.esrc[e];
     odst[i] = d.edst[e];
     oofs[i] = o;
+}
+
+struct PmDev {
+    const uint4 *node;
+    const uint64_t *bits;
+};
+
+// the position of the k-th (from 0) set bit of w, k < popcount(w): halves narrowed by their popcounts, six steps
+__device__ __forceinline__ uint32_t pm_select(uint64_t w, uint32_t k)
+{
+    uint32_t pos = 0;
+#pragma unroll
+    for (int h = 32; h > 0; h >>= 1) {
+        const uint32_t c = __popcll(w & ((1ull << h) - 1));
+        if (k >= c) { k -= c; w >>= h; pos += h; }
+    }
+    return pos;
+}
+
+// col(u, o) of a node with entry nd = (row, x0, first unit, width), o < |label(u)|: the last group whose count is at
+// most o (a search over the node's ceil(nw / PM_W) group heads), then at most PM_W words of that group.  A table that
+// disagreed with |label(u)| would end the word loop without a hit: PM_NONE then, never a read past the node's units.
+__device__ __forceinline__ uint32_t pm_col(const PmDev &m, const uint4 nd, uint32_t o)
+{
+    if (nd.z == PM_NONE) return nd.y + o;
+    const uint64_t *b = m.bits + nd.z;
+    const uint32_t nw = (nd.w + 63) / 64;
+    uint32_t lo = 0, hi = (nw + PM_W - 1) / PM_W - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (b[(uint64_t)mid * (PM_W + 1)] <= o) lo = mid; else hi = mid - 1;
+    }
+    const uint64_t *grp = b + (uint64_t)lo * (PM_W + 1);
+    uint32_t k = o - (uint32_t)grp[0];
+    const uint32_t w0 = lo * PM_W, wn = nw - w0 < PM_W ? nw - w0 : PM_W;
+    for (uint32_t j = 0; j < wn; j++) {
+        const uint64_t w = grp[1 + j];
+        const uint32_t c = __popcll(w);
+        if (k < c) return nd.y + (w0 + j) * 64 + pm_select(w, k);
+        k -= c;
+    }
+    return PM_NONE;
+}
+
+// k_po_expand for the MSA coordinate of every place: the same lane per place, the same search of the offsets and the
+// same SA slot -> edge -> offset; then the node and offset of Occurrences.as_nodes (the source below |label(src)|, else
+// the destination), and through the table the row and column of that cell of the node's representative row.  An offset
+// outside S_e (a pattern with '#' or a zero byte) gets PM_NONE in both.  Lanes write consecutive entries of orow / ocol.
+template <bool STARTS>
+__global__ __launch_bounds__(PX_THREADS) void k_po_expand_msa(PvDev d, PmDev m, const uint64_t *off, uint64_t n, uint64_t total,
+                                                             const uint32_t *first, const uint32_t *sk, const uint32_t *restarts,
+                                                             uint32_t *orow, uint32_t *ocol)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t w0 = po_uniform(i & ~(uint64_t)(FBG_WAVE - 1));
+    if (w0 >= total) return;
+    const uint64_t w1 = w0 + FBG_WAVE - 1 < total ? w0 + FBG_WAVE - 1 : total - 1;
+    const uint64_t q0 = po_uniform(po_find(off, 0, n - 1, w0));
+    const uint64_t q1 = po_uniform(po_find(off, q0, n - 1, w1));
+    if (i >= total) return;
+    const uint64_t q = po_find(off, q0, q1, i);
+    const uint32_t p = d.sa[first[q] + (uint32_t)(i - off[q])];
+    const uint32_t e = pv_edge(d, p);
+    const uint32_t base = d.estart[e] + 1, ne = d.estart[e + 1] - base;
+    uint32_t o = ne - 1 - (p - base);
+    if (STARTS) o = restarts[q] ? ne - sk[q] : o - sk[q] + 1;
+    uint32_t u = d.esrc[e];
+    const uint32_t la = d.len[u];
+    if (o >= la) { u = d.edst[e]; o -= la; }
+    uint32_t row = PM_NONE, col = PM_NONE;
+    if (o < d.len[u]) {
+        const uint4 nd = m.node[u];
+        col = pm_col(m, nd, o);
+        row = col == PM_NONE ? PM_NONE : nd.x;
+    }
+    orow[i] = row;
+    ocol[i] = col;
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------
@@ -1486,6 +1674,56 @@ static int po_fetch(fbg_pindex *ix, const char *who, const char *search, PoState
     return FBG_OK;
 }
 
+// The MSA coordinates of a place state's places into the caller's arrays (fbg_pindex_occurrences_msa, fbg_pindex_seeds_msa):
+// po_fetch with k_po_expand_msa and a buffer of its own, so that neither s.place nor a later fetch sees it.
+static int po_fetch_msa(fbg_pindex *ix, const char *who, const char *search, PoState &s, uint32_t *end_row, uint32_t *end_col,
+                        uint32_t *start_row, uint32_t *start_col, double *device_ms)
+{
+    fbg_ctx *ctx = ix->ctx;
+    if (device_ms) *device_ms = 0;
+    if (!ix->from_segmentation || !ix->has_map)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation knows MSA coordinates", who);
+    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no %s result to expand", who, search);
+    const bool ends = end_row && end_col, starts = start_row && start_col;
+    if ((!ends && (end_row || end_col)) || (!starts && (start_row || start_col)))
+        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: a list takes both of its arrays or none", who);
+    const uint64_t ne = ends ? s.etotal : 0, ns = starts ? s.stotal : 0, n = s.n;
+    if (ne + ns == 0) return FBG_OK;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FBG_TRY(fbg_reserve(ix->ctx, s.msa, 2 * (ne + ns) * 4, &ix->bufs, false));
+    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
+    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    // msa: row, column of the ends, then of the starts
+    uint32_t *pe = s.msa.as<uint32_t>(), *ps = pe + 2 * ne;
+    const PvDev d = pv_dev(ix);
+    const PmDev m = {ix->mnode.as<uint4>(), ix->mbits.as<uint64_t>()};
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    if (ne)
+        hipLaunchKernelGGL(k_po_expand_msa<false>, dim3(fbg_blocks(ne, PX_THREADS)), dim3(PX_THREADS), 0, st, d, m,
+                           (const uint64_t *)s.eoff.as<uint64_t>(), n, ne, (const uint32_t *)s.el.as<uint32_t>(),
+                           (const uint32_t *)s.sk.as<uint32_t>(), (const uint32_t *)s.rs.as<uint32_t>(), pe, pe + ne);
+    if (ns)
+        hipLaunchKernelGGL(k_po_expand_msa<true>, dim3(fbg_blocks(ns, PX_THREADS)), dim3(PX_THREADS), 0, st, d, m,
+                           (const uint64_t *)s.soff.as<uint64_t>(), n, ns, (const uint32_t *)s.ss.as<uint32_t>(),
+                           (const uint32_t *)s.sk.as<uint32_t>(), (const uint32_t *)s.rs.as<uint32_t>(), ps, ps + ns);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    if (ne) {
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(end_row, pe, ne * 4, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(end_col, pe + ne, ne * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (ns) {
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(start_row, ps, ns * 4, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(start_col, ps + ns, ns * 4, hipMemcpyDeviceToHost, st));
+    }
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    return FBG_OK;
+}
+
 extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
                                       uint64_t max_per_pattern, uint64_t *count, uint64_t *pos, uint32_t *restarts,
                                       uint64_t *end_off, uint64_t *start_off, uint64_t *end_total, uint64_t *start_total,
@@ -1534,6 +1772,14 @@ extern "C" int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, u
     if (!ix) return FBG_ERR_INVALID;
     return po_fetch(ix, "fbg_pindex_occurrences_fetch", "fbg_pindex_occurrences", ix->occ, end_src, end_dst, end_offset, start_src,
                     start_dst, start_offset, device_ms);
+}
+
+extern "C" int fbg_pindex_occurrences_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t *end_col, uint32_t *start_row,
+                                          uint32_t *start_col, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    return po_fetch_msa(ix, "fbg_pindex_occurrences_msa", "fbg_pindex_occurrences", ix->occ, end_row, end_col, start_row, start_col,
+                        device_ms);
 }
 
 // ---- seeds (fbg_pindex_seeds / _fetch / _places) -------------------------------------------------------------------
@@ -1662,6 +1908,24 @@ extern "C" int fbg_pindex_seeds_places(fbg_pindex *ix, uint32_t *end_src, uint32
     if (!ix) return FBG_ERR_INVALID;
     return po_fetch(ix, "fbg_pindex_seeds_places", "fbg_pindex_seeds", ix->sd, end_src, end_dst, end_offset, start_src, start_dst,
                     start_offset, device_ms);
+}
+
+extern "C" int fbg_pindex_seeds_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t *end_col, uint32_t *start_row, uint32_t *start_col,
+                                    double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    return po_fetch_msa(ix, "fbg_pindex_seeds_msa", "fbg_pindex_seeds", ix->sd, end_row, end_col, start_row, start_col, device_ms);
+}
+
+extern "C" int fbg_pindex_msa_stats(const fbg_pindex *ix, uint64_t *map_bytes, uint64_t *gapped_nodes, uint64_t *sample_columns)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    if (!ix->from_segmentation || !ix->has_map)
+        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "fbg_pindex_msa_stats: only an index built by fbg_pindex_build_segmentation has the table");
+    if (map_bytes) *map_bytes = 16 * ix->n_nodes + 8 * ix->map_units;
+    if (gapped_nodes) *gapped_nodes = ix->map_gapped;
+    if (sample_columns) *sample_columns = 64 * PM_W;
+    return FBG_OK;
 }
 
 extern "C" uint64_t fbg_pindex_text_length(const fbg_pindex *ix) { return ix ? ix->N1 : 0; }
@@ -1804,7 +2068,7 @@ extern "C" int fbg_pindex_build_segmentation(fbg_ctx *ctx, const uint64_t *bound
     int rc;
     {
         PxScratch s;
-        rc = px_build_segmentation(ix, s, boundaries, nb);
+        rc = px_build_segmentation(ix, s, boundaries, nb, true);
     }
     if (rc != FBG_OK) { px_destroy(ix); return rc; }
     ix->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1850,7 +2114,7 @@ static int sv_round(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, ui
     if (!ix->sv0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->sv0));
     if (!ix->sv1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->sv1));
     FBG_HIP_TRY(ctx, hipEventRecord(ix->sv0, st));
-    FBG_TRY(px_build_segmentation(ix, s, boundaries, nb));
+    FBG_TRY(px_build_segmentation(ix, s, boundaries, nb, false));
     const uint64_t n = ix->n_nodes;
     FBG_TRY(fbg_reserve(ctx, ix->scut, nb + 8, &ix->bufs, false));
     FBG_TRY(fbg_reserve(ctx, ix->sctr, 8, &ix->bufs, false));

@@ -567,6 +567,49 @@ uint64_t fbg_pindex_node_count(const fbg_pindex *ix);
  * only, else FBG_ERR_INVALID). */
 int fbg_pindex_node_info(fbg_pindex *ix, uint32_t *label_len, uint32_t *node_block, uint64_t *first_node);
 
+/* MSA row and column of every reported place (an index built by fbg_pindex_build_segmentation only).
+ *
+ * A place (edge_src, edge_dst, offset) is private to one segmentation; the MSA column is the one coordinate all rows
+ * and all blocks share.  For the MSA A[m][n] and the boundaries the index was built from:
+ *   block j    covers the columns [x0, x1), x0 = j ? boundaries[j - 1] + 1 : 0, x1 = min(boundaries[j] + 1, n);
+ *   r(u)       the representative row of node u of block j: rep_row of fbg_block_graph, the first row, by row index,
+ *              whose gap-stripped label in the block is label(u);
+ *   col(u, o)  for 0 <= o < |label(u)|: the column of the o-th (from 0) non-gap cell of row r(u) in [x0, x1).
+ * A place (a, b, offset) belongs to node a at o = offset if offset < |label(a)|, else to node b at
+ * o = offset - |label(a)| (what Occurrences.as_nodes does); its coordinate is (row, col) = (r(u), col(u, o)), so that
+ * A[row][col] == S_e[offset]: the pattern's last symbol for an end, its first symbol for a start.  If o >= |label(u)|,
+ * row = col = 0xffffffff; only patterns holding '#' or a zero byte get there (their offsets may lie outside S_e).
+ * ONE witness row per place, not the set of rows: other rows that carry the same node may have their gaps elsewhere
+ * in the block and so other columns for the same offset.  The rows through a node or edge are not reported.
+ *
+ * The build keeps a table for this on the device, derived from the resident MSA (the index keeps no pointer to the
+ * MSA: replacing the context's MSA later changes no answer): 16 bytes per node (row, x0, bitmap position, x1 - x0),
+ * and for every node whose row has a gap in its block a bitmap of the non-gap cells of [x0, x1) in 64-bit words with
+ * a running count in front of every 8 words (9/8 bits per column).  A lookup is a search over a node's counts, at
+ * most 8 popcounts and one select inside a word, whatever the block's width; a node without gaps is x0 + o.  The
+ * table is counted neither in index_bytes nor in table_bytes; fbg_pindex_msa_stats reports it.  With it
+ * fbg_pindex_build_segmentation also returns FBG_ERR_TOO_LARGE for an MSA of 2^32 columns or more and for a table of
+ * 2^32 - 1 words or more (sizes are summed in 64 bits; nothing wraps).  The rounds of fbg_segmentation_validate and
+ * fbg_segmentation_repair report no places and build no table.
+ *
+ *   fbg_pindex_occurrences_msa   entry i of end_row / end_col is the coordinate of entry i of what
+ *       fbg_pindex_occurrences_fetch returns in end_*, and the same for start_*: the same CSR offsets (end_off,
+ *       start_off of fbg_pindex_occurrences), order and cap.
+ *   fbg_pindex_seeds_msa         the same for fbg_pindex_seeds_places and the offsets of fbg_pindex_seeds_fetch.
+ * Either list may be left out by passing NULL for both of its arrays.  A call may come before, after or without the
+ * fetch / places call and may be repeated; it expands into a buffer of its own and leaves the other place state, later
+ * fetches, fbg_pindex_stats' search_ms and occ_lines, validation results and the context alone.  *device_ms (may be
+ * NULL): device time of the expansion kernels.
+ * Errors, all FBG_ERR_INVALID: a NULL index; an index not built from a segmentation; no successful search of that
+ * kind before the call; one of a list's two arrays NULL.  Nothing to report returns FBG_OK.
+ *   fbg_pindex_msa_stats         any pointer may be NULL: device bytes of the table, nodes with a bitmap, and the columns
+ *       between two running counts (64 * 8).  FBG_ERR_INVALID for a NULL index or one not built from a segmentation. */
+int fbg_pindex_occurrences_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t *end_col, uint32_t *start_row,
+                               uint32_t *start_col, double *device_ms);
+int fbg_pindex_seeds_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t *end_col, uint32_t *start_row, uint32_t *start_col,
+                         double *device_ms);
+int fbg_pindex_msa_stats(const fbg_pindex *ix, uint64_t *map_bytes, uint64_t *gapped_nodes, uint64_t *sample_columns);
+
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
  * to_remove[node_blocks[i] - 1] (fbg.cpp:3269-3270, 3194); cut_bad[nb - 1] is always 0.  The index is built by
