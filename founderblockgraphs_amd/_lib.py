@@ -95,6 +95,9 @@ SIGNATURES = {
     "fbg_pindex_occurrences_msa": (C.c_int, [vp, u32p, u32p, u32p, u32p, C.POINTER(C.c_double)]),
     "fbg_pindex_seeds_msa": (C.c_int, [vp, u32p, u32p, u32p, u32p, C.POINTER(C.c_double)]),
     "fbg_pindex_msa_stats": (C.c_int, [vp, u64p, u64p, u64p]),
+    "fbg_pindex_chains": (C.c_int, [vp, C.c_uint64, C.c_uint64, u64p, u32p, C.POINTER(C.c_double)]),
+    "fbg_pindex_chains_fetch": (C.c_int, [vp, u32p, u32p, C.POINTER(C.c_double)]),
+    "fbg_pindex_chain_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, u64p]),
     "fbg_segmentation_validate": (C.c_int, [vp, u64p, C.c_uint64, u8p, C.c_uint64, u8p, u64p, u64p, C.POINTER(C.c_double)]),
     "fbg_segmentation_repair": (C.c_int, [vp, u64p, u64p, u8p, C.c_uint64, u64p, u64p, C.POINTER(C.c_double)]),
 }

@@ -476,10 +476,11 @@ class PatternIndex:
         return Occurrences(self._label_len, count[:k], pos[:k], rs[:k], et[:k], st[:k], eoff, soff, [a[:ne] for a in ends],
                            [a[:ns] for a in starts], ms1.value, ms2.value, coords, ms3)
 
-    def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False):
+    def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False, chain=False, band=None, min_score=0):
         """Every read cut greedily into the maximal pieces the search accepts (fbg_pindex_seeds, _fetch and _places):
         seeds of at least min_length symbols, each with what occurrences() reports for that substring, at most
-        max_per_seed places per seed and list -> Seeds.  msa=True: as for occurrences() (fbg_pindex_seeds_msa)."""
+        max_per_seed places per seed and list -> Seeds.  msa=True: as for occurrences() (fbg_pindex_seeds_msa).
+        chain=True: also chains(band, min_score) of these seeds, as Seeds.chains."""
         if min_length < 1:
             raise ValueError("min_length must be 1 or more")
         if max_per_seed < 0:
@@ -504,7 +505,39 @@ class PatternIndex:
         coords, ms4 = self._msa_coords(self._L.fbg_pindex_seeds_msa, ne, ns) if msa else (None, 0.0)
         occ = Occurrences(self._label_len, count[:n], ln[:n].astype(np.uint64), rs[:n], et[:n], st[:n], eoff, soff,
                           [a[:ne] for a in ends], [a[:ns] for a in starts], ms1.value, ms2.value + ms3.value, coords, ms4)
-        return Seeds(seed_off, q[:n], ln[:n], occ)
+        self._seed_reads = k
+        out = Seeds(seed_off, q[:n], ln[:n], occ)
+        if chain:
+            out.chains = self.chains(band=band, min_score=min_score)
+        return out
+
+    def chains(self, band=None, min_score=0):
+        """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
+        Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
+        that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
+        neighbours at most band (None: unbounded); chains scoring below min_score come out empty -> Chains."""
+        if band is not None and band < 0:
+            raise ValueError("band must be 0 or more, or None")
+        if min_score < 0:
+            raise ValueError("min_score must be 0 or more")
+        k = getattr(self, "_seed_reads", 0)
+        chain_off = np.zeros(k + 1, dtype=np.uint64)
+        score = np.zeros(max(k, 1), dtype=np.uint32)
+        ms1, ms2 = C.c_double(0), C.c_double(0)
+        b = 0xffffffffffffffff if band is None else min(int(band), 0xffffffffffffffff)
+        self._eng._chk(self._L.fbg_pindex_chains(self._h, b, min(int(min_score), 0xffffffffffffffff), _u64(chain_off),
+                                                 score.ctypes.data_as(_lib.u32p), C.byref(ms1)))
+        t = int(chain_off[k])
+        place, seed = np.zeros(max(t, 1), dtype=np.uint32), np.zeros(max(t, 1), dtype=np.uint32)
+        self._eng._chk(self._L.fbg_pindex_chains_fetch(self._h, place.ctypes.data_as(_lib.u32p), seed.ctypes.data_as(_lib.u32p),
+                                                       C.byref(ms2)))
+        return Chains(chain_off, score[:k], place[:t], seed[:t], ms1.value, ms2.value)
+
+    def chain_stats(self):
+        """{anchors, reads_small, reads_wave, reads_spill, small_max, lds_max}: see fbg_pindex_chain_stats."""
+        v = [C.c_uint64(0) for _ in range(6)]
+        self._eng._chk(self._L.fbg_pindex_chain_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("anchors", "reads_small", "reads_wave", "reads_spill", "small_max", "lds_max"), (x.value for x in v)))
 
     def download(self):
         """-> (text with the sentinel, SA, B positions, E positions)."""
@@ -631,10 +664,12 @@ class Seeds:
       pattern_of          int64 per seed: its read
       occ                 an Occurrences object over the seeds in order, as if every seed had been searched as a pattern
                           of its own (occ.pos equals length; occ.ends(j), occ.starts(j), occ.as_nodes() work per seed)
+      chains              the Chains of these seeds when asked for with chain=True, else None
     search_ms: device time of fbg_pindex_seeds; fetch_ms: of the per-seed copies and the expansion of the places."""
 
     def __init__(self, seed_off, q_start, length, occ):
         self.seed_off, self.q_start, self.length, self.occ = seed_off, q_start, length, occ
+        self.chains = None
         self.pattern_of = np.repeat(np.arange(len(seed_off) - 1, dtype=np.int64), np.diff(seed_off.astype(np.int64)))
         self.search_ms, self.fetch_ms = occ.search_ms, occ.fetch_ms
 
@@ -645,6 +680,26 @@ class Seeds:
         """int64[rows, 3]: (q_start, length, count) of the seeds of read k."""
         a, b = int(self.seed_off[k]), int(self.seed_off[k + 1])
         return np.stack((self.q_start[a:b], self.length[a:b], self.occ.count[a:b]), axis=1).astype(np.int64)
+
+
+class Chains:
+    """Result of PatternIndex.chains (include/fbg_hip.h, fbg_pindex_chains), for the k reads of the last seeds() call:
+      chain_off       uint64[k + 1], CSR offsets of the chains (a read's anchors in ascending q_start)
+      score           uint32 per read: read symbols covered by the chain's seeds (0: no anchor); reported also where
+                      it is below min_score and the chain therefore empty
+      anchor_place    uint32 per chain entry: index into the start arrays of Seeds.occ (start_src .. start_col)
+      anchor_seed     uint32 per chain entry: index of its seed (Seeds.q_start, Seeds.length)
+    device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
+
+    def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
+        self.chain_off, self.score = chain_off, score
+        self.anchor_place, self.anchor_seed = anchor_place, anchor_seed
+        self.device_ms, self.fetch_ms = device_ms, fetch_ms
+
+    def of(self, k):
+        """int64[rows, 2]: (anchor_place, anchor_seed) of the chain of read k."""
+        a, b = int(self.chain_off[k]), int(self.chain_off[k + 1])
+        return np.stack((self.anchor_place[a:b], self.anchor_seed[a:b]), axis=1).astype(np.int64)
 
 
 class Validation:

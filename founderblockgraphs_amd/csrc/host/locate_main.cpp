@@ -3,6 +3,7 @@
 // place of its .index file:
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
+//              [--chain[=BAND]]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -24,6 +25,12 @@
 // line gets `<tab> row <tab> column` appended: the MSA cell, from 0, of that symbol in the representative row of its node
 // (fbg_pindex_occurrences_msa / _seeds_msa; `*` in both for an offset outside the edge).  Without --occurrences the
 // option only changes how the index is built.  A FASTA that does not fit the graph fails with a message.
+// --chain[=BAND] (with --seeds, --msa and --occurrences[=M], M > 0) chains every pattern's seeds by the MSA columns of
+// their start places (fbg_pindex_chains; BAND bounds the surplus of columns over pattern symbols between two neighbours of
+// a chain, unbounded when left out) and prints, after the S / E / B lines of a pattern,
+//   C <tab> score <tab> anchors                       symbols covered by the chain, places in it
+//   A <tab> q_start <tab> length <tab> row <tab> column    per place of the chain, in pattern order: its seed and the MSA cell
+//                                                     of the seed's first symbol
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -41,7 +48,7 @@ static int usage(const char *msg)
 {
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
-              << "                  [--msa=msa.fasta]\n"
+              << "                  [--msa=msa.fasta] [--chain[=BAND]]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -50,7 +57,11 @@ static int usage(const char *msg)
               << "                     with --occurrences the E / B lines of every piece follow its S line\n"
               << "  --msa=msa.fasta    the MSA the graph was cut from: the index is built from it and the graph's M and X\n"
               << "                     lines, and every E / B line ends with the MSA row and column (from 0) of that symbol\n"
-              << "                     in the representative row of its node (* for an offset outside the edge)\n";
+              << "                     in the representative row of its node (* for an offset outside the edge)\n"
+              << "  --chain[=BAND]     needs --seeds, --msa and --occurrences[=M] with M > 0: after a pattern's S / E / B lines a\n"
+              << "                     C line (score, anchors) and per anchor of its best co-linear chain of start places an A\n"
+              << "                     line: q_start, length, MSA row, MSA column; BAND bounds the surplus of columns over\n"
+              << "                     pattern symbols between neighbours (default: unbounded)\n";
     return EXIT_FAILURE;
 }
 
@@ -116,8 +127,8 @@ int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path;
     bool have_msa = false;
-    bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false;
-    uint64_t max_places = 64, min_seed = 1;
+    bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
+    uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&](const char *name, std::string &out, bool &have) {
@@ -153,11 +164,25 @@ int main(int argc, char **argv)
             min_seed = m;
             continue;
         }
+        if (a == "--chain") { chain = true; continue; }
+        if (a.compare(0, 8, "--chain=") == 0) {
+            const std::string v = a.substr(8);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
+                return usage(("--chain takes a band, not '" + v + "'").c_str());
+            chain = true;
+            band = m;
+            continue;
+        }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
         return usage(("unknown argument " + a).c_str());
     }
     if (!have_graph || graph.empty()) return usage("--graph is required");
     if (have_msa && msa_path.empty()) return usage("--msa takes a FASTA file");
+    if (chain && !(seeds && have_msa && occurrences && max_places > 0))
+        return usage("--chain needs --seeds, --msa and --occurrences[=M] with M > 0");
 
     XgfaGraph g;
     std::string error;
@@ -242,6 +267,8 @@ int main(int argc, char **argv)
     }
     std::vector<uint64_t> seed_off(np + 1, 0), seed_count;
     std::vector<uint32_t> q_start, length;
+    std::vector<uint64_t> chain_off(np + 1, 0);
+    std::vector<uint32_t> chain_score(np + 1, 0), anchor_place, anchor_seed;
     if (rc == FBG_OK && seeds) {
         rc = fbg_pindex_seeds(ix, (const uint8_t *)data.data(), off.data(), np, min_seed, occurrences ? max_places : 0,
                               seed_off.data(), nullptr);
@@ -259,6 +286,12 @@ int main(int argc, char **argv)
         if (rc == FBG_OK && want_coords) {
             for (int k = 0; k < 4; k++) coords[k].resize((k < 2 ? end_off[ns] : start_off[ns]) + 1);
             rc = fbg_pindex_seeds_msa(ix, coords[0].data(), coords[1].data(), coords[2].data(), coords[3].data(), nullptr);
+        }
+        if (rc == FBG_OK && chain) rc = fbg_pindex_chains(ix, band, 0, chain_off.data(), chain_score.data(), nullptr);
+        if (rc == FBG_OK && chain) {
+            anchor_place.resize(chain_off[np] + 1);
+            anchor_seed.resize(chain_off[np] + 1);
+            rc = fbg_pindex_chains_fetch(ix, anchor_place.data(), anchor_seed.data(), nullptr);
         }
     }
     if (rc == FBG_OK && !occurrences && !seeds)
@@ -299,6 +332,12 @@ int main(int argc, char **argv)
             for (uint64_t j = seed_off[k]; j < seed_off[k + 1]; j++) {
                 std::cout << "S\t" << q_start[j] << '\t' << length[j] << '\t' << seed_count[j] << '\t' << restarts[j] << '\n';
                 if (occurrences) print_places(g, j, o, t, places, want_coords ? coords : nullptr);
+            }
+            if (chain) {
+                std::cout << "C\t" << chain_score[k] << '\t' << chain_off[k + 1] - chain_off[k] << '\n';
+                for (uint64_t i = chain_off[k]; i < chain_off[k + 1]; i++)
+                    std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]
+                              << '\t' << coords[3][anchor_place[i]] << '\n';
             }
         }
         std::cout << "Pattern? " << found << " out of " << np << " patterns seeded" << std::endl;

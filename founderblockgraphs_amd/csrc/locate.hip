@@ -33,6 +33,9 @@
 //                                    running count every PM_W words;
 //   k_po_expand_msa                  k_po_expand's walk from a reported place to its edge and offset, then through that
 //                                    table to the MSA row and column of the place (fbg_pindex_occurrences_msa / _seeds_msa);
+//   k_pc_key / k_pc_chain / k_pc_trace   fbg_pindex_chains: the reads binned by their number of start places, the
+//                                    co-linear chaining DP over a read's start places in three tiers, and the walk back
+//                                    from the chain's end (a pass that counts, a scan, a pass that writes);
 //   k_sv_cuts                        the cuts before blocks that hold an INVALID node (fbg_segmentation_validate / _repair).
 //
 // occ layout.  Symbols are remapped to dense codes in byte order (the sentinel is code 0, '#' code 1).  With at
@@ -60,6 +63,10 @@
 #define PV_NONE 0xffffffffu   // no witness
 #define PM_W 8                // the MSA coordinate table keeps a running non-gap count every PM_W bitmap words (512 columns)
 #define PM_NONE 0xffffffffu   // a node without a bitmap (no gap in its row's stretch); the coordinate of no cell
+#define PC_SUB 16             // chaining: lanes that share a read of the small tier
+#define PC_SMALL 32           // start places of a read up to which PC_SUB lanes chain it (small_max)
+#define PC_LDS 1024           // start places of a read up to which a wave chains it with its state in LDS (lds_max)
+#define PC_NONE 0xffffffffu   // no predecessor / no chain end
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
@@ -69,6 +76,16 @@ struct PoState {
     DevBuf msa;               // the rows and columns of the last fbg_pindex_occurrences_msa / _seeds_msa, apart from place
     bool ready = false;
     uint64_t n = 0, etotal = 0, stotal = 0;
+};
+
+// fbg_pindex_chains: per start place of the last fbg_pindex_seeds its MSA row and column (col: rows first, a copy apart
+// from sd.msa) and its predecessor; per read the binning keys and ids (before and after the sort), the chain's end
+// place, score and length, the scan of the lengths; the chains (places, then seeds); the spill tier's slab (a uint4 per
+// start place, reserved when a read needs it); the counters of k_pc_key and k_pc_chain.
+struct PcState {
+    DevBuf col, pred, key, id, key2, id2, end, score, len, off, out, slab, ctr;
+    bool ready = false;
+    uint64_t n = 0, total = 0, anchors = 0, tier[3] = {0, 0, 0};
 };
 
 struct fbg_pindex {
@@ -107,6 +124,8 @@ struct fbg_pindex {
     PoState occ;
     DevBuf snum, soff, srec, scnt, spos, sq, slen;
     PoState sd;
+    uint64_t sd_reads = 0;        // n_patterns of the last successful fbg_pindex_seeds
+    PcState ch;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -1454,6 +1473,149 @@ __global__ __launch_bounds__(PX_THREADS) void k_po_expand_msa(PvDev d, PmDev m, 
     ocol[i] = col;
 }
 
+// ---- chains (fbg_pindex_chains) ------------------------------------------------------------------------------------
+// Read R has the seeds seed_off[R] .. seed_off[R + 1] and, as its candidate anchors, their capped start places
+// g0 = start_off[seed_off[R]] .. start_off[seed_off[R + 1]]: the places of earlier seeds first, a seed's places in slot
+// order.  A place whose column is PC_NONE is no anchor; it keeps its slot with best = 0, which no comparison picks.
+struct PcDev {
+    const uint64_t *seed_off, *start_off;
+    const uint32_t *q, *k, *col;
+    uint32_t *pred, *end, *score;
+    uint4 *slab;
+    unsigned long long *ctr;      // 0 .. 3: reads without a start place, of the small, wave and spill tier; 4: anchors
+    uint64_t band;
+};
+
+// key = start places of the read (what picks its tier), id = the read; reads without one are done here
+__global__ void k_pc_key(PcDev d, uint64_t n, uint32_t *key, uint32_t *id)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int tier = -1;
+    if (t < n) {
+        const uint64_t cnt = d.start_off[d.seed_off[t + 1]] - d.start_off[d.seed_off[t]];
+        key[t] = (uint32_t)cnt;
+        id[t] = (uint32_t)t;
+        tier = cnt == 0 ? 0 : cnt <= PC_SMALL ? 1 : cnt <= PC_LDS ? 2 : 3;
+        if (cnt == 0) { d.end[t] = PC_NONE; d.score[t] = 0; }
+    }
+    for (int b = 0; b < 4; b++) {
+        const unsigned long long m = __ballot(tier == b);
+        if (m && (threadIdx.x & (FBG_WAVE - 1)) == 0) atomicAdd(&d.ctr[b], (unsigned long long)__popcll(m));
+    }
+}
+
+// what a seed's lanes wrote becomes visible to the lanes of the same wave that scan it for the next seed
+__device__ __forceinline__ void pc_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// The DP of one read on G lanes (lane = 0 .. G - 1), state st[0 .. places of the read) = (best, column, q_start, length).
+// Seed by seed: the lanes take the seed's places G at a time, each scans the state of all earlier seeds' places in
+// ascending order -- every lane reads the same entry, a broadcast -- and keeps the first of the best predecessors; the
+// seed's own entries are written meanwhile (nobody reads them before the next seed) and published by pc_sync.  A lane
+// meets its own places in ascending order, so the first maximum it keeps is its smallest; the G lanes' maxima are
+// merged by (best descending, place ascending).  live = false: a group without a read, which only takes part in the
+// shuffles.
+template <int G, class ST>
+__device__ __forceinline__ void pc_read(const PcDev &d, bool live, uint32_t R, uint32_t lane, ST st)
+{
+    const uint64_t s0 = live ? d.seed_off[R] : 0, s1 = live ? d.seed_off[R + 1] : 0;
+    const uint64_t g0 = live ? d.start_off[s0] : 0;
+    uint32_t bestv = 0, bestj = PC_NONE, valid = 0;
+    for (uint64_t t = s0; t < s1; t++) {
+        const uint32_t a0 = (uint32_t)(d.start_off[t] - g0), a1 = (uint32_t)(d.start_off[t + 1] - g0);
+        const uint32_t q = d.q[t], k = d.k[t];
+        for (uint32_t j = a0 + lane; j < a1; j += G) {
+            const uint32_t c = d.col[g0 + j];
+            uint32_t b = 0, p = PC_NONE;
+            if (c != PC_NONE) {
+                uint32_t m = 0;
+                for (uint32_t i = 0; i < a0; i++) {
+                    const uint4 e = st[i];
+                    const int64_t dc = (int64_t)c - (int64_t)e.y;
+                    const int64_t sur = dc - ((int64_t)q - (int64_t)e.z);
+                    const uint64_t mag = sur < 0 ? (uint64_t)-sur : (uint64_t)sur;
+                    if (e.x > m && dc >= (int64_t)e.w && mag <= d.band) { m = e.x; p = i; }
+                }
+                b = k + m;
+                valid++;
+                if (b > bestv) { bestv = b; bestj = j; }
+            }
+            d.pred[g0 + j] = p == PC_NONE ? PC_NONE : (uint32_t)(g0 + p);
+            st[j] = make_uint4(b, c, q, k);
+        }
+        pc_sync();
+    }
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) {
+        const uint32_t ov = __shfl_xor(bestv, o, G), oj = __shfl_xor(bestj, o, G);
+        valid += __shfl_xor(valid, o, G);
+        if (ov > bestv || (ov == bestv && oj < bestj)) { bestv = ov; bestj = oj; }
+    }
+    if (live && lane == 0) {
+        d.end[R] = bestj == PC_NONE ? PC_NONE : (uint32_t)(g0 + bestj);
+        d.score[R] = bestv;
+        if (valid) atomicAdd(&d.ctr[4], (unsigned long long)valid);
+    }
+}
+
+// The reads ids[0 .. cnt) of one tier.  TIER 0 (small): PC_SUB lanes per read, PX_THREADS / PC_SUB reads per workgroup,
+// PC_SMALL entries of LDS each.  TIER 1 (wave): one wave per workgroup and read, PC_LDS entries of LDS.  TIER 2 (spill):
+// the same with the read's stretch of the slab in device memory.  The binning guarantees the capacities; a read beyond
+// its tier's would be left without a chain, never written past the array.
+template <int TIER>
+__global__ __launch_bounds__(TIER == 0 ? PX_THREADS : FBG_WAVE) void k_pc_chain(PcDev d, const uint32_t *ids, uint64_t cnt)
+{
+    __shared__ uint4 lds[TIER == 0 ? PX_THREADS / PC_SUB * PC_SMALL : TIER == 1 ? PC_LDS : 1];
+    if constexpr (TIER == 0) {
+        const uint64_t i = (uint64_t)blockIdx.x * (PX_THREADS / PC_SUB) + threadIdx.x / PC_SUB;
+        bool live = i < cnt;
+        const uint32_t R = live ? ids[i] : 0;
+        if (live && d.start_off[d.seed_off[R + 1]] - d.start_off[d.seed_off[R]] > PC_SMALL) live = false;
+        pc_read<PC_SUB>(d, live, R, threadIdx.x % PC_SUB, lds + threadIdx.x / PC_SUB * PC_SMALL);
+    } else {
+        const uint64_t i = blockIdx.x;
+        if (i >= cnt) return;
+        const uint32_t R = ids[i];
+        if constexpr (TIER == 1) {
+            if (d.start_off[d.seed_off[R + 1]] - d.start_off[d.seed_off[R]] > PC_LDS) return;
+            pc_read<FBG_WAVE>(d, true, R, threadIdx.x, lds);
+        } else {
+            pc_read<FBG_WAVE>(d, true, R, threadIdx.x, d.slab + d.start_off[d.seed_off[R]]);
+        }
+    }
+}
+
+// One lane per read follows pred back from the chain's end.  The counting pass stores the chain's length (0 below
+// min_score or without an anchor; entry n = 0 for the scan); the writing pass fills the read's stretch off[R] ..
+// off[R + 1] from its last entry backwards, so that it ascends in q_start: the place, and its seed by a search of the
+// read's stretch of start_off.  Either walk ends after as many steps as the read has seeds, whatever pred holds.
+template <bool WRITE>
+__global__ void k_pc_trace(PcDev d, uint64_t n, uint64_t min_score, uint64_t *len, const uint64_t *off, uint32_t *oplace, uint32_t *oseed)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n) return;
+    if (t == n) { if (!WRITE) len[n] = 0; return; }
+    const uint64_t s0 = d.seed_off[t], s1 = d.seed_off[t + 1];
+    uint32_t g = d.end[t];
+    if (d.score[t] < min_score) g = PC_NONE;
+    if (!WRITE) {
+        uint64_t c = 0;
+        while (g != PC_NONE && c < s1 - s0) { c++; g = d.pred[g]; }
+        len[t] = c;
+    } else {
+        const uint64_t o0 = off[t];
+        for (uint64_t i = off[t + 1] - o0; i-- > 0 && g != PC_NONE;) {
+            oplace[o0 + i] = g;
+            oseed[o0 + i] = (uint32_t)po_find(d.start_off, s0, s1 - 1, g);
+            g = d.pred[g];
+        }
+    }
+}
+
 // ---- C ABI ------------------------------------------------------------------------------------------------------
 extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
                                 const uint64_t *edge_off, const uint64_t *edge_dst, fbg_pindex **out)
@@ -1674,6 +1836,19 @@ static int po_fetch(fbg_pindex *ix, const char *who, const char *search, PoState
     return FBG_OK;
 }
 
+// k_po_expand_msa over one list of a place state (STARTS: its starts, else its ends; the list is not empty) into orow /
+// ocol on the device, on the context's stream.
+template <bool STARTS> static void po_expand_msa(fbg_pindex *ix, const PoState &s, uint32_t *orow, uint32_t *ocol)
+{
+    const PvDev d = pv_dev(ix);
+    const PmDev m = {ix->mnode.as<uint4>(), ix->mbits.as<uint64_t>()};
+    const uint64_t total = STARTS ? s.stotal : s.etotal;
+    hipLaunchKernelGGL(k_po_expand_msa<STARTS>, dim3(fbg_blocks(total, PX_THREADS)), dim3(PX_THREADS), 0, ix->ctx->stream, d, m,
+                       (const uint64_t *)(STARTS ? s.soff : s.eoff).as<uint64_t>(), s.n, total,
+                       (const uint32_t *)(STARTS ? s.ss : s.el).as<uint32_t>(), (const uint32_t *)s.sk.as<uint32_t>(),
+                       (const uint32_t *)s.rs.as<uint32_t>(), orow, ocol);
+}
+
 // The MSA coordinates of a place state's places into the caller's arrays (fbg_pindex_occurrences_msa, fbg_pindex_seeds_msa):
 // po_fetch with k_po_expand_msa and a buffer of its own, so that neither s.place nor a later fetch sees it.
 static int po_fetch_msa(fbg_pindex *ix, const char *who, const char *search, PoState &s, uint32_t *end_row, uint32_t *end_col,
@@ -1687,7 +1862,7 @@ static int po_fetch_msa(fbg_pindex *ix, const char *who, const char *search, PoS
     const bool ends = end_row && end_col, starts = start_row && start_col;
     if ((!ends && (end_row || end_col)) || (!starts && (start_row || start_col)))
         return fbg_fail(ctx, FBG_ERR_INVALID, "%s: a list takes both of its arrays or none", who);
-    const uint64_t ne = ends ? s.etotal : 0, ns = starts ? s.stotal : 0, n = s.n;
+    const uint64_t ne = ends ? s.etotal : 0, ns = starts ? s.stotal : 0;
     if (ne + ns == 0) return FBG_OK;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -1696,17 +1871,9 @@ static int po_fetch_msa(fbg_pindex *ix, const char *who, const char *search, PoS
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
     // msa: row, column of the ends, then of the starts
     uint32_t *pe = s.msa.as<uint32_t>(), *ps = pe + 2 * ne;
-    const PvDev d = pv_dev(ix);
-    const PmDev m = {ix->mnode.as<uint4>(), ix->mbits.as<uint64_t>()};
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
-    if (ne)
-        hipLaunchKernelGGL(k_po_expand_msa<false>, dim3(fbg_blocks(ne, PX_THREADS)), dim3(PX_THREADS), 0, st, d, m,
-                           (const uint64_t *)s.eoff.as<uint64_t>(), n, ne, (const uint32_t *)s.el.as<uint32_t>(),
-                           (const uint32_t *)s.sk.as<uint32_t>(), (const uint32_t *)s.rs.as<uint32_t>(), pe, pe + ne);
-    if (ns)
-        hipLaunchKernelGGL(k_po_expand_msa<true>, dim3(fbg_blocks(ns, PX_THREADS)), dim3(PX_THREADS), 0, st, d, m,
-                           (const uint64_t *)s.soff.as<uint64_t>(), n, ns, (const uint32_t *)s.ss.as<uint32_t>(),
-                           (const uint32_t *)s.sk.as<uint32_t>(), (const uint32_t *)s.rs.as<uint32_t>(), ps, ps + ns);
+    if (ne) po_expand_msa<false>(ix, s, pe, pe + ne);
+    if (ns) po_expand_msa<true>(ix, s, ps, ps + ns);
     FBG_HIP_TRY(ctx, hipGetLastError());
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
     if (ne) {
@@ -1802,6 +1969,7 @@ extern "C" int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const u
     fbg_ctx *ctx = ix->ctx;
     PoState &s = ix->sd;
     s.ready = false;
+    ix->ch.ready = false;         // chains belong to the seeds they were made from
     if (device_ms) *device_ms = 0;
     if (!seed_off || (n_patterns && !pat_off)) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds: missing argument");
     if (min_length == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds: min_length is 1 or more");
@@ -1809,6 +1977,7 @@ extern "C" int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const u
     seed_off[0] = 0;
     s.n = 0;
     s.etotal = s.stotal = 0;
+    ix->sd_reads = n_patterns;
     if (n_patterns == 0) { s.ready = true; return FBG_OK; }
     const uint64_t n = n_patterns;
     FBG_TRY(px_front(ix, "fbg_pindex_seeds", patterns, pat_off, n, PX_SEEDS));
@@ -1915,6 +2084,139 @@ extern "C" int fbg_pindex_seeds_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t 
 {
     if (!ix) return FBG_ERR_INVALID;
     return po_fetch_msa(ix, "fbg_pindex_seeds_msa", "fbg_pindex_seeds", ix->sd, end_row, end_col, start_row, start_col, device_ms);
+}
+
+// ---- chains (fbg_pindex_chains / _fetch / _stats) -----------------------------------------------------------------
+// The start columns of the seeds' places (k_po_expand_msa<true> into the chain state's own buffer), the reads sorted by
+// their number of start places, the host's look at the four bin sizes, one k_pc_chain launch per tier that has reads,
+// then count, scan and write as the seeds do.  A chain has at most one anchor per seed: S entries hold every chain.
+extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_score, uint64_t *chain_off, uint32_t *score,
+                                 double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PcState &c = ix->ch;
+    const PoState &s = ix->sd;
+    c.ready = false;
+    if (device_ms) *device_ms = 0;
+    if (!chain_off) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains: missing chain_off");
+    if (!ix->from_segmentation || !ix->has_map)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains: only an index built by fbg_pindex_build_segmentation knows MSA columns");
+    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains: no fbg_pindex_seeds result to chain");
+    const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
+    c.n = n;
+    c.total = c.anchors = 0;
+    c.tier[0] = c.tier[1] = c.tier[2] = 0;
+    std::fill(chain_off, chain_off + n + 1, (uint64_t)0);
+    if (score) std::fill(score, score + n, (uint32_t)0);
+    if (n == 0 || S == 0 || A == 0) { c.ready = true; return FBG_OK; }   // no start place: every score 0, every chain empty
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FBG_TRY(fbg_reserve(ix->ctx, c.col, 2 * A * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, c.pred, A * 4, &ix->bufs, false));
+    for (DevBuf *b : {&c.key, &c.id, &c.key2, &c.id2, &c.end, &c.score}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
+    for (DevBuf *b : {&c.len, &c.off}) FBG_TRY(fbg_reserve(ix->ctx, *b, (n + 1) * 8, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, c.out, 2 * S * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ix->ctx, c.ctr, 5 * 8, &ix->bufs, false));
+    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
+    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    PcDev d;
+    d.seed_off = ix->soff.as<uint64_t>();
+    d.start_off = s.soff.as<uint64_t>();
+    d.q = ix->sq.as<uint32_t>();
+    d.k = ix->slen.as<uint32_t>();
+    d.col = c.col.as<uint32_t>() + A;
+    d.pred = c.pred.as<uint32_t>();
+    d.end = c.end.as<uint32_t>();
+    d.score = c.score.as<uint32_t>();
+    d.slab = nullptr;
+    d.ctr = c.ctr.as<unsigned long long>();
+    d.band = band;
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(c.ctr.p, 0, 5 * 8, st));
+    po_expand_msa<true>(ix, s, c.col.as<uint32_t>(), c.col.as<uint32_t>() + A);
+    uint32_t *ka = c.key.as<uint32_t>(), *va = c.id.as<uint32_t>(), *kb = c.key2.as<uint32_t>(), *vb = c.id2.as<uint32_t>();
+    hipLaunchKernelGGL(k_pc_key, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, d, n, ka, va);
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, ka, kb, va, vb, (size_t)n, 0u, 32u, st);
+    }));
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    uint64_t bin[5] = {0, 0, 0, 0, 0};
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(bin, c.ctr.p, 4 * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (bin[0] + bin[1] + bin[2] + bin[3] != n) return fbg_fail(ctx, FBG_ERR_HIP, "fbg_pindex_chains: the tiers hold %llu of %llu reads",
+                                                                (unsigned long long)(bin[0] + bin[1] + bin[2] + bin[3]), (unsigned long long)n);
+    if (bin[3]) {
+        FBG_TRY(fbg_reserve(ix->ctx, c.slab, A * 16, &ix->bufs, false));
+        d.slab = c.slab.as<uint4>();
+    }
+    const uint32_t *ids = vb + bin[0];
+    if (bin[1])
+        hipLaunchKernelGGL(k_pc_chain<0>, dim3(fbg_blocks(bin[1], PX_THREADS / PC_SUB)), dim3(PX_THREADS), 0, st, d, ids, bin[1]);
+    if (bin[2]) hipLaunchKernelGGL(k_pc_chain<1>, dim3((unsigned)bin[2]), dim3(FBG_WAVE), 0, st, d, ids + bin[1], bin[2]);
+    if (bin[3]) hipLaunchKernelGGL(k_pc_chain<2>, dim3((unsigned)bin[3]), dim3(FBG_WAVE), 0, st, d, ids + bin[1] + bin[2], bin[3]);
+    uint64_t *len = c.len.as<uint64_t>(), *off = c.off.as<uint64_t>();
+    uint32_t *out = c.out.as<uint32_t>();
+    hipLaunchKernelGGL(k_pc_trace<false>, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, d, n, min_score, len, (const uint64_t *)off, out, out + S);
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, len, off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
+    }));
+    hipLaunchKernelGGL(k_pc_trace<true>, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, d, n, min_score, len, (const uint64_t *)off, out, out + S);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(chain_off, off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (score) FBG_HIP_TRY(ctx, hipMemcpyAsync(score, c.score.p, n * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&bin[4], d.ctr + 4, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    // a chain takes one place per seed at most, and a call has fewer than 2^32 seeds
+    if (chain_off[n] >= (1ull << 32))
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_chains: %llu chain entries; a call takes fewer than 2^32", (unsigned long long)chain_off[n]);
+    c.total = chain_off[n];
+    c.anchors = bin[4];
+    c.tier[0] = bin[1];
+    c.tier[1] = bin[2];
+    c.tier[2] = bin[3];
+    c.ready = true;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, uint32_t *anchor_seed, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    const PcState &c = ix->ch;
+    if (device_ms) *device_ms = 0;
+    if (!c.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_fetch: no fbg_pindex_chains result to fetch");
+    if (c.total == 0 || (!anchor_place && !anchor_seed)) return FBG_OK;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t *out = c.out.as<uint32_t>();
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    if (anchor_place) FBG_HIP_TRY(ctx, hipMemcpyAsync(anchor_place, out, c.total * 4, hipMemcpyDeviceToHost, st));
+    if (anchor_seed) FBG_HIP_TRY(ctx, hipMemcpyAsync(anchor_seed, out + ix->sd.n, c.total * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_chain_stats(const fbg_pindex *ix, uint64_t *anchors, uint64_t *reads_small, uint64_t *reads_wave,
+                                      uint64_t *reads_spill, uint64_t *small_max, uint64_t *lds_max)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    const PcState &c = ix->ch;
+    if (anchors) *anchors = c.ready ? c.anchors : 0;
+    if (reads_small) *reads_small = c.ready ? c.tier[0] : 0;
+    if (reads_wave) *reads_wave = c.ready ? c.tier[1] : 0;
+    if (reads_spill) *reads_spill = c.ready ? c.tier[2] : 0;
+    if (small_max) *small_max = PC_SMALL;
+    if (lds_max) *lds_max = PC_LDS;
+    return FBG_OK;
 }
 
 extern "C" int fbg_pindex_msa_stats(const fbg_pindex *ix, uint64_t *map_bytes, uint64_t *gapped_nodes, uint64_t *sample_columns)

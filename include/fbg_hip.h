@@ -506,7 +506,7 @@ int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, uint32_t *en
  * seed (q_start, length) = (i, k), count (> 0 always), restarts, end_total, start_total and the capped end and start
  * place lists, in ascending SA slot order, are what fbg_pindex_occurrences and fbg_pindex_occurrences_fetch report for
  * the pattern P[i : i + k] with max_per_pattern = max_per_seed: a seed adds no notion of a match to the occurrence
- * calls, and it shares their looseness (no path is verified, seeds are not chained).  Patterns holding '#' or zero
+ * calls, and it shares their looseness (no path is verified; fbg_pindex_chains below chains a read's seeds).  Patterns holding '#' or zero
  * bytes get no special treatment: whatever the search does with them is what a seed is.
  *
  * Three calls, because the number of seeds is known only after the search and the buffers are the caller's:
@@ -609,6 +609,56 @@ int fbg_pindex_occurrences_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t *end_
 int fbg_pindex_seeds_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t *end_col, uint32_t *start_row, uint32_t *start_col,
                          double *device_ms);
 int fbg_pindex_msa_stats(const fbg_pindex *ix, uint64_t *map_bytes, uint64_t *gapped_nodes, uint64_t *sample_columns);
+
+/* Co-linear chaining of a read's seeds (an index built by fbg_pindex_build_segmentation only).
+ *
+ * The reads are those of the last successful fbg_pindex_seeds on the index: n = its n_patterns, read R has the seeds
+ * seed_off[R] .. seed_off[R + 1], seed t has q_start[t], length[t] and the capped start places start_off[t] ..
+ * start_off[t + 1], and place g has the column start_col[g] that fbg_pindex_seeds_msa reports.  An anchor of read R is
+ * a start place g of one of its seeds t with start_col[g] != 0xffffffff; write q = q_start[t], k = length[t],
+ * c = start_col[g].  Anchors are identified and ordered by g: those of earlier seeds first, a seed's in slot order.
+ * The witness row and the end places play no part.
+ *   i precedes j   iff t_i < t_j, c_j >= c_i + k_i (along any path every symbol sits in a later column than the one
+ *                  before, so a seed takes at least k columns from c on) and |(c_j - c_i) - (q_j - q_i)| <= band (the
+ *                  surplus of columns over read symbols: gap columns if positive, read insertions if negative), all in
+ *                  signed 64-bit; band = UINT64_MAX: unbounded;
+ *   best[j]        k_j + max(0, max over the i that precede j of best[i]); pred[j] = the i of that inner maximum, the
+ *                  smallest g among equals, none if nothing precedes j;
+ *   the chain      of read R ends at its anchor of largest best, the smallest g among equals, and follows pred back;
+ *                  score[R] = that best, 0 for a read without an anchor; if score[R] < min_score the score is
+ *                  reported and the chain is empty.
+ * A chain is a best-scoring co-linear selection among the places the seed calls already report: it adds no notion of
+ * a match and inherits their looseness (one witness row per place, the cap, no path is verified).  Scores count covered
+ * read symbols only, are at most the read's length and fit uint32_t.
+ *
+ *   fbg_pindex_chains        the DP and the sizes.  chain_off: n + 1 CSR offsets (read R's chain is entries chain_off[R]
+ *       .. chain_off[R + 1] of the fetched arrays, in ascending q_start); score: n values, may be NULL.  On the device:
+ *       the start columns are expanded into a buffer of the chain state, the reads are sorted by their number of start
+ *       places (known from start_off; at least their number of anchors) and chained in three tiers -- up to small_max
+ *       places by a quarter of a wave per read, up to lds_max by a wave with the state of the earlier places in LDS,
+ *       beyond by a wave with that state in device memory -- which run the same code and give the same chains; one lane
+ *       per read then walks back from the chain's end, a pass that counts, a scan, a pass that writes.  *device_ms (may
+ *       be NULL): device time of all of it, the host's look at the tier sizes included, without the copies out.
+ *   fbg_pindex_chains_fetch  anchor_place: the g of every chain entry, an index into the start arrays of
+ *       fbg_pindex_seeds_places and fbg_pindex_seeds_msa; anchor_seed: its seed t, an index into the arrays of
+ *       fbg_pindex_seeds_fetch.  chain_off[n] entries each; either may be NULL; may be called again.
+ *   fbg_pindex_chain_stats   any pointer may be NULL: of the last successful fbg_pindex_chains (0 without one) the anchors
+ *       of all reads and the reads each tier chained (reads without a start place are in none); small_max and lds_max,
+ *       the tiers' limits, at any time.
+ * The chains stay on the device until the next fbg_pindex_chains or fbg_pindex_seeds on this index; a new
+ * fbg_pindex_seeds invalidates them.  A chains call leaves the seeds (fbg_pindex_seeds_fetch, _places and _msa return
+ * what they returned before), the occurrences, fbg_pindex_stats, validation results and the context alone.
+ * Errors, all FBG_ERR_INVALID: a NULL index or chain_off; an index not built from a segmentation; no successful
+ * fbg_pindex_seeds before the call; a fetch without a successful fbg_pindex_chains since the last fbg_pindex_seeds.
+ * n == 0: chain_off[0] = 0, FBG_OK.  Seeds without places (max_per_seed == 0): every score 0, every chain empty, FBG_OK.
+ * 2^32 chain entries or more would be FBG_ERR_TOO_LARGE; a chain holds one place per seed at most and a seeds call
+ * fewer than 2^32 seeds, so the limit is not reached.  Scratch owned by the index: 12 bytes per start place (16 more
+ * when a read takes the third tier), 40 per read, 8 per seed. */
+int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_score, uint64_t *chain_off, uint32_t *score,
+                      double *device_ms);
+int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, uint32_t *anchor_seed, double *device_ms);
+int fbg_pindex_chain_stats(const fbg_pindex *ix, uint64_t *anchors, uint64_t *reads_small, uint64_t *reads_wave,
+                           uint64_t *reads_spill, uint64_t *small_max, uint64_t *lds_max);
 
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
