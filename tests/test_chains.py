@@ -65,7 +65,7 @@ def test_library_exports_the_chain_calls_and_the_header_declares_them():
 
 def random_anchors(rng):
     """Up to 10 anchors of one read in g order, [(g, t, q, k, c)]: seeds in read order without overlap, a few places
-    each, columns from a range small enough for equal scores and for both signs of the surplus."""
+    each (some seeds none), columns from a range small enough for equal scores and for both signs of the surplus."""
     out, q, g = [], 0, int(rng.integers(0, 50))
     for t in range(int(rng.integers(1, 6))):
         q += int(rng.integers(0, 3))
@@ -80,13 +80,36 @@ def random_anchors(rng):
 
 def test_model_agrees_with_brute_force():
     rng = np.random.default_rng(11)
-    ties = longest = 0
+    ties = longest = holes = 0
+    at_band = {(sign, over): 0 for sign in (1, -1) for over in (0, 1)}      # pairs with surplus sign * (band + over)
     for trial in range(400):
         an = random_anchors(rng)
+        # the same read as the arrays of a Seeds object: the holes in g are places without a column
+        if an:
+            g0, t0 = an[0][0], an[0][1]
+            col = np.full(an[-1][0] - g0 + 2, NONE, dtype=np.uint32)
+            q, k = np.zeros(an[-1][1] - t0 + 1, dtype=np.uint32), np.ones(an[-1][1] - t0 + 1, dtype=np.uint32)
+            start_off = np.zeros(len(q) + 1, dtype=np.uint64)
+            for g, t, qq, kk, c in an:
+                col[g - g0], q[t - t0], k[t - t0] = c, qq, kk
+                start_off[t - t0 + 1:] = g - g0 + 1
+            start_off[-1] = len(col)
+            seed_off = np.array([0, len(q)], dtype=np.uint64)
+            assert CM.read_anchors(seed_off, q, k, start_off, col, 0) == [(g - g0, t - t0, qq, kk, c) for g, t, qq, kk, c in an]
+            holes += bool((col[:-1] == NONE).any())
         for band in (0, 1, 3, None):
             top, at = CM.brute_force(an, band)
             score, idx = CM.chain_of(an, band)
             assert score == top, (trial, band)
+            if an:
+                _, score2, place, _ = CM.chains(seed_off, q, k, start_off, col, band, 0)
+                assert score2.tolist() == [top] and place.tolist() == [an[j][0] - g0 for j in idx], (trial, band)
+            for i, a in enumerate(an if band is not None else []):
+                for b in an[i + 1:]:
+                    if a[1] < b[1] and b[4] >= a[4] + a[3]:
+                        sur = (b[4] - a[4]) - (b[2] - a[2])
+                        for sign, over in at_band:
+                            at_band[(sign, over)] += sur == sign * (band + over)
             if an:
                 assert sum(an[j][3] for j in idx) == score
                 # among the best chains: the smallest end, then the smallest predecessor of it, and so on
@@ -96,6 +119,8 @@ def test_model_agrees_with_brute_force():
             else:
                 assert (score, idx, at) == (0, [], [])
     assert ties > 50 and longest >= 4
+    # both signs of the surplus at the band and one beyond it, and places without a column between anchors
+    assert holes > 50 and all(v > 20 for v in at_band.values()), (holes, at_band)
     # chains(): CSR assembly, min_score, a read without anchors, a place that is none
     seed_off = np.array([0, 2, 2, 3], dtype=np.uint64)
     q, k = np.array([0, 5, 1], dtype=np.uint32), np.array([4, 3, 2], dtype=np.uint32)
