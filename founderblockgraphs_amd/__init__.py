@@ -5,5 +5,5 @@ host program built from csrc/host/.  This package is the thin ctypes mirror used
 bench.py; it contains no compute and no fallback.
 """
 from .api import (Engine, FbgError, Group, NoSegmentation, Occurrences, PatternIndex, Seeds, SegmentationCheck, Validation,  # noqa: F401
-                  as_msa, graph_from_segmentation, read_xgfa, segment, segment2elasticValid, segment_elastic_heuristic,
+                  as_msa, complement_table, graph_from_segmentation, read_xgfa, segment, segment2elasticValid, segment_elastic_heuristic,
                   segment_elastic_minmaxlength)

@@ -368,6 +368,38 @@ def _concat(strings):
     return data, off
 
 
+def complement_table(spec=None):
+    """The 256-byte complement table of seeds(strands=True) as a uint8 array.  spec: None for the default (A <-> T,
+    C <-> G, a <-> t, c <-> g, every other byte itself); a mapping such as {"A": "T", "T": "A"} of single symbols (str,
+    bytes or byte values), every byte not named mapping to itself; or the 256 bytes themselves.  The table is applied
+    once per symbol and need not be an involution."""
+    if spec is None:
+        spec = {"A": "T", "T": "A", "C": "G", "G": "C", "a": "t", "t": "a", "c": "g", "g": "c"}
+    if hasattr(spec, "items"):
+        def sym(x):
+            if isinstance(x, str):
+                x = x.encode("latin-1")
+            if isinstance(x, (bytes, bytearray)):
+                if len(x) != 1:
+                    raise ValueError(f"a complement maps single symbols, not {x!r}")
+                return x[0]
+            if not 0 <= int(x) <= 255:
+                raise ValueError(f"a complement maps bytes, not {x!r}")
+            return int(x)
+        table = np.arange(256, dtype=np.uint8)
+        for a, b in spec.items():
+            table[sym(a)] = sym(b)
+        return table
+    if isinstance(spec, str):
+        spec = spec.encode("latin-1")
+    table = np.array(np.frombuffer(spec, dtype=np.uint8) if isinstance(spec, (bytes, bytearray)) else spec)
+    if table.shape != (256,):
+        raise ValueError(f"a complement table has 256 entries, not {table.size}")
+    if table.dtype != np.uint8 and len(table) and (table.min() < 0 or table.max() > 255):
+        raise ValueError("a complement table holds bytes")
+    return np.ascontiguousarray(table, dtype=np.uint8)
+
+
 class PatternIndex:
     """fbg_pindex: the founder_block_index of the reference built on the GPU (include/fbg_hip.h, 'pattern index').
     locate() returns what locate_patterns reports per pattern: the count of the last backward-search range (0: not
@@ -476,21 +508,33 @@ class PatternIndex:
         return Occurrences(self._label_len, count[:k], pos[:k], rs[:k], et[:k], st[:k], eoff, soff, [a[:ne] for a in ends],
                            [a[:ns] for a in starts], ms1.value, ms2.value, coords, ms3)
 
-    def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False, chain=False, band=None, min_score=0):
+    def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False, chain=False, band=None, min_score=0, strands=False,
+              complement=None):
         """Every read cut greedily into the maximal pieces the search accepts (fbg_pindex_seeds, _fetch and _places):
         seeds of at least min_length symbols, each with what occurrences() reports for that substring, at most
         max_per_seed places per seed and list -> Seeds.  msa=True: as for occurrences() (fbg_pindex_seeds_msa).
-        chain=True: also chains(band, min_score) of these seeds, as Seeds.chains."""
+        chain=True: also chains(band, min_score) of these seeds, as Seeds.chains.  strands=True: every read is searched
+        as given and as its reverse complement under complement_table(complement), made on the device
+        (fbg_pindex_seeds_strands): the Seeds then cover 2k virtual reads, the k given ones and then their k reverse
+        complements, and chains() also picks a strand per read."""
         if min_length < 1:
             raise ValueError("min_length must be 1 or more")
         if max_per_seed < 0:
             raise ValueError("max_per_seed must be 0 or more")
         data, off = _concat(patterns)
-        k = len(off) - 1
+        given = len(off) - 1
+        k = 2 * given if strands else given
         seed_off = np.zeros(k + 1, dtype=np.uint64)
         ms1, ms2, ms3 = C.c_double(0), C.c_double(0), C.c_double(0)
-        self._eng._chk(self._L.fbg_pindex_seeds(self._h, _u8(data), _u64(off), k, int(min_length), int(max_per_seed),
-                                                _u64(seed_off), C.byref(ms1)))
+        if strands:
+            table = complement_table(complement)
+            self._eng._chk(self._L.fbg_pindex_seeds_strands(self._h, _u8(data), _u64(off), given, _u8(table), int(min_length),
+                                                            int(max_per_seed), _u64(seed_off), C.byref(ms1)))
+        else:
+            if complement is not None:
+                raise ValueError("complement needs strands=True")
+            self._eng._chk(self._L.fbg_pindex_seeds(self._h, _u8(data), _u64(off), k, int(min_length), int(max_per_seed),
+                                                    _u64(seed_off), C.byref(ms1)))
         n = int(seed_off[k])
         q, ln, rs = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
         count, et, st = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(3))
@@ -506,7 +550,8 @@ class PatternIndex:
         occ = Occurrences(self._label_len, count[:n], ln[:n].astype(np.uint64), rs[:n], et[:n], st[:n], eoff, soff,
                           [a[:ne] for a in ends], [a[:ns] for a in starts], ms1.value, ms2.value + ms3.value, coords, ms4)
         self._seed_reads = k
-        out = Seeds(seed_off, q[:n], ln[:n], occ)
+        self._seed_given = given if strands else None
+        out = Seeds(seed_off, q[:n], ln[:n], occ, np.diff(off.astype(np.int64)), strands)
         if chain:
             out.chains = self.chains(band=band, min_score=min_score)
         return out
@@ -515,7 +560,9 @@ class PatternIndex:
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
-        neighbours at most band (None: unbounded); chains scoring below min_score come out empty -> Chains."""
+        neighbours at most band (None: unbounded); chains scoring below min_score come out empty -> Chains.  After
+        seeds(strands=True) the chains cover the 2k virtual reads and the strand of every given read is picked from
+        their scores on the device (fbg_pindex_chain_strands)."""
         if band is not None and band < 0:
             raise ValueError("band must be 0 or more, or None")
         if min_score < 0:
@@ -531,7 +578,18 @@ class PatternIndex:
         place, seed = np.zeros(max(t, 1), dtype=np.uint32), np.zeros(max(t, 1), dtype=np.uint32)
         self._eng._chk(self._L.fbg_pindex_chains_fetch(self._h, place.ctypes.data_as(_lib.u32p), seed.ctypes.data_as(_lib.u32p),
                                                        C.byref(ms2)))
-        return Chains(chain_off, score[:k], place[:t], seed[:t], ms1.value, ms2.value)
+        out = Chains(chain_off, score[:k], place[:t], seed[:t], ms1.value, ms2.value)
+        given = getattr(self, "_seed_given", None)
+        if given is not None:
+            strand, best = np.zeros(max(given, 1), dtype=np.uint8), np.zeros(max(given, 1), dtype=np.uint32)
+            cnt = [C.c_uint64(0) for _ in range(3)]
+            ms3 = C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chain_strands(self._h, _u8(strand), best.ctypes.data_as(_lib.u32p),
+                                                            *[C.byref(x) for x in cnt], C.byref(ms3)))
+            out.strand, out.best_score = strand[:given], best[:given]
+            out.strand_counts = dict(zip(("forward", "reverse", "none"), (x.value for x in cnt)))
+            out.strand_ms = ms3.value
+        return out
 
     def chain_stats(self):
         """{anchors, reads_small, reads_wave, reads_spill, small_max, lds_max}: see fbg_pindex_chain_stats."""
@@ -665,19 +723,35 @@ class Seeds:
       occ                 an Occurrences object over the seeds in order, as if every seed had been searched as a pattern
                           of its own (occ.pos equals length; occ.ends(j), occ.starts(j), occ.as_nodes() work per seed)
       chains              the Chains of these seeds when asked for with chain=True, else None
+      strands, reads      asked for with strands=True: True and the number k of given reads; seed_off then covers 2k virtual
+                          reads, read R as given and read k + R its reverse complement, whose seeds are in the
+                          coordinates of the reverse complement.  Otherwise False and the number of reads
+      q_forward           int64 per seed: its start in the given read, q_start for a forward seed and
+                          L - q_start - length for one of the reverse complement of a read of L symbols
     search_ms: device time of fbg_pindex_seeds; fetch_ms: of the per-seed copies and the expansion of the places."""
 
-    def __init__(self, seed_off, q_start, length, occ):
+    def __init__(self, seed_off, q_start, length, occ, read_len=None, strands=False):
         self.seed_off, self.q_start, self.length, self.occ = seed_off, q_start, length, occ
         self.chains = None
         self.pattern_of = np.repeat(np.arange(len(seed_off) - 1, dtype=np.int64), np.diff(seed_off.astype(np.int64)))
         self.search_ms, self.fetch_ms = occ.search_ms, occ.fetch_ms
+        self.strands = bool(strands)
+        self.reads = (len(seed_off) - 1) // 2 if strands else len(seed_off) - 1
+        self.q_forward = q_start.astype(np.int64)
+        if strands:
+            rev = self.pattern_of >= self.reads
+            L = np.asarray(read_len, dtype=np.int64)[self.pattern_of[rev] - self.reads]
+            self.q_forward[rev] = L - self.q_forward[rev] - length[rev].astype(np.int64)
 
     def __len__(self):
         return len(self.q_start)
 
-    def of(self, k):
-        """int64[rows, 3]: (q_start, length, count) of the seeds of read k."""
+    def of(self, k, strand=0):
+        """int64[rows, 3]: (q_start, length, count) of the seeds of read k; strand=1 (strands=True only): of its reverse
+        complement."""
+        if strand not in (0, 1) or (strand and not self.strands):
+            raise ValueError("strand is 0, or 1 after seeds(strands=True)")
+        k += strand * self.reads
         a, b = int(self.seed_off[k]), int(self.seed_off[k + 1])
         return np.stack((self.q_start[a:b], self.length[a:b], self.occ.count[a:b]), axis=1).astype(np.int64)
 
@@ -689,17 +763,32 @@ class Chains:
                       it is below min_score and the chain therefore empty
       anchor_place    uint32 per chain entry: index into the start arrays of Seeds.occ (start_src .. start_col)
       anchor_seed     uint32 per chain entry: index of its seed (Seeds.q_start, Seeds.length)
+    and, after seeds(strands=True) (None otherwise), for the k given reads, whose virtual reads R and k + R these chains cover:
+      strand          uint8 per read: 1 if the reverse complement's chain scores higher, else 0; 0xff (_lib.STRAND_NONE) if
+                      the chain of that strand is empty
+      best_score      uint32 per read: the larger of the two scores
+      strand_counts   {forward, reverse, none}: the reads by outcome
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
         self.chain_off, self.score = chain_off, score
         self.anchor_place, self.anchor_seed = anchor_place, anchor_seed
         self.device_ms, self.fetch_ms = device_ms, fetch_ms
+        self.strand = self.best_score = self.strand_counts = None
 
     def of(self, k):
         """int64[rows, 2]: (anchor_place, anchor_seed) of the chain of read k."""
         a, b = int(self.chain_off[k]), int(self.chain_off[k + 1])
         return np.stack((self.anchor_place[a:b], self.anchor_seed[a:b]), axis=1).astype(np.int64)
+
+    def best(self, k):
+        """int64[rows, 2]: the chain of given read k on its chosen strand, as of(); empty where strand[k] is 0xff."""
+        if self.strand is None:
+            raise ValueError("no strands: ask for them with seeds(strands=True)")
+        t = int(self.strand[k])
+        if t == _lib.STRAND_NONE:
+            return np.zeros((0, 2), dtype=np.int64)
+        return self.of(t * len(self.strand) + k)
 
 
 class Validation:

@@ -3,7 +3,7 @@
 // place of its .index file:
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
-//              [--chain[=BAND]]
+//              [--chain[=BAND]] [--strands] [--complement=FROMTO]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -31,6 +31,15 @@
 //   C <tab> score <tab> anchors                       symbols covered by the chain, places in it
 //   A <tab> q_start <tab> length <tab> row <tab> column    per place of the chain, in pattern order: its seed and the MSA cell
 //                                                     of the seed's first symbol
+// --strands (with --seeds) searches every pattern also as its reverse complement (fbg_pindex_seeds_strands; A <-> T,
+// C <-> G in either case, or the pairs of --complement=FROMTO, e.g. ATTACGGC: every first character maps to the second,
+// every byte not named to itself).  A pattern's block as above is then followed by
+//   - <tab> K                                         K the reported seeds of the reverse complement
+// and that strand's S / E / B (/ C / A) lines in the same format, q_start counted in the reverse complement; with --chain
+// a pattern closes with
+//   T <tab> + | - | * <tab> score                     the strand whose chain scores higher (a tie: +; * if that chain is
+//                                                     empty) and the higher score (fbg_pindex_chain_strands)
+// A pattern counts as seeded with a seed on either strand, and --error-on-not-found fails at the first with none on both.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -48,7 +57,7 @@ static int usage(const char *msg)
 {
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
-              << "                  [--msa=msa.fasta] [--chain[=BAND]]\n"
+              << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -61,7 +70,12 @@ static int usage(const char *msg)
               << "  --chain[=BAND]     needs --seeds, --msa and --occurrences[=M] with M > 0: after a pattern's S / E / B lines a\n"
               << "                     C line (score, anchors) and per anchor of its best co-linear chain of start places an A\n"
               << "                     line: q_start, length, MSA row, MSA column; BAND bounds the surplus of columns over\n"
-              << "                     pattern symbols between neighbours (default: unbounded)\n";
+              << "                     pattern symbols between neighbours (default: unbounded)\n"
+              << "  --strands          needs --seeds: every pattern also as its reverse complement; after a pattern's block a\n"
+              << "                     line `- K` and the K seeds of the reverse complement in the same format; with --chain a\n"
+              << "                     closing T line: + or - for the strand of the better chain (* if it is empty), its score\n"
+              << "  --complement=FROMTO  pairs of characters for --strands, e.g. ATTACGGC (the default, and the same in lower\n"
+              << "                     case); every byte not named maps to itself\n";
     return EXIT_FAILURE;
 }
 
@@ -125,8 +139,8 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
 
 int main(int argc, char **argv)
 {
-    std::string graph, patterns, msa_path;
-    bool have_msa = false;
+    std::string graph, patterns, msa_path, complement;
+    bool have_msa = false, have_complement = false, strands = false;
     bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
     uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
     for (int i = 1; i < argc; i++) {
@@ -138,7 +152,8 @@ int main(int argc, char **argv)
             return false;
         };
         if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns) ||
-            value("--msa", msa_path, have_msa)) continue;
+            value("--msa", msa_path, have_msa) || value("--complement", complement, have_complement)) continue;
+        if (a == "--strands") { strands = true; continue; }
         if (a == "--error-on-not-found") { error_on_not_found = true; continue; }
         if (a == "--occurrences") { occurrences = true; continue; }
         if (a.compare(0, 14, "--occurrences=") == 0) {
@@ -183,6 +198,9 @@ int main(int argc, char **argv)
     if (have_msa && msa_path.empty()) return usage("--msa takes a FASTA file");
     if (chain && !(seeds && have_msa && occurrences && max_places > 0))
         return usage("--chain needs --seeds, --msa and --occurrences[=M] with M > 0");
+    if (strands && !seeds) return usage("--strands needs --seeds");
+    if (have_complement && !strands) return usage("--complement needs --strands");
+    if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
 
     XgfaGraph g;
     std::string error;
@@ -225,6 +243,7 @@ int main(int argc, char **argv)
         off.push_back(data.size());
     }
     const uint64_t np = off.size() - 1;
+    const uint64_t nv = strands ? 2 * np : np;      // virtual reads: the patterns, then their reverse complements
 
     fbg_ctx *ctx = nullptr;
     int rc = fbg_ctx_create(0, &ctx);
@@ -265,14 +284,23 @@ int main(int argc, char **argv)
         for (std::vector<uint64_t> *v : {&end_off, &start_off, &end_total, &start_total}) v->assign(np + 1, 0);
         restarts.assign(np + 1, 0);
     }
-    std::vector<uint64_t> seed_off(np + 1, 0), seed_count;
+    std::vector<uint64_t> seed_off(nv + 1, 0), seed_count;
     std::vector<uint32_t> q_start, length;
-    std::vector<uint64_t> chain_off(np + 1, 0);
-    std::vector<uint32_t> chain_score(np + 1, 0), anchor_place, anchor_seed;
+    std::vector<uint64_t> chain_off(nv + 1, 0);
+    std::vector<uint32_t> chain_score(nv + 1, 0), anchor_place, anchor_seed, best_score(np + 1, 0);
+    std::vector<uint8_t> strand(np + 1, 0);
     if (rc == FBG_OK && seeds) {
-        rc = fbg_pindex_seeds(ix, (const uint8_t *)data.data(), off.data(), np, min_seed, occurrences ? max_places : 0,
-                              seed_off.data(), nullptr);
-        const uint64_t ns = rc == FBG_OK ? seed_off[np] : 0;
+        if (strands) {
+            uint8_t table[256];
+            for (int c = 0; c < 256; c++) table[c] = (uint8_t)c;
+            for (size_t i = 0; i + 1 < complement.size(); i += 2) table[(uint8_t)complement[i]] = (uint8_t)complement[i + 1];
+            rc = fbg_pindex_seeds_strands(ix, (const uint8_t *)data.data(), off.data(), np, have_complement ? table : nullptr,
+                                          min_seed, occurrences ? max_places : 0, seed_off.data(), nullptr);
+        } else {
+            rc = fbg_pindex_seeds(ix, (const uint8_t *)data.data(), off.data(), np, min_seed, occurrences ? max_places : 0,
+                                  seed_off.data(), nullptr);
+        }
+        const uint64_t ns = rc == FBG_OK ? seed_off[nv] : 0;
         for (std::vector<uint64_t> *v : {&seed_count, &end_off, &start_off, &end_total, &start_total}) v->assign(ns + 1, 0);
         for (std::vector<uint32_t> *v : {&q_start, &length, &restarts}) v->assign(ns + 1, 0);
         if (rc == FBG_OK)
@@ -289,10 +317,12 @@ int main(int argc, char **argv)
         }
         if (rc == FBG_OK && chain) rc = fbg_pindex_chains(ix, band, 0, chain_off.data(), chain_score.data(), nullptr);
         if (rc == FBG_OK && chain) {
-            anchor_place.resize(chain_off[np] + 1);
-            anchor_seed.resize(chain_off[np] + 1);
+            anchor_place.resize(chain_off[nv] + 1);
+            anchor_seed.resize(chain_off[nv] + 1);
             rc = fbg_pindex_chains_fetch(ix, anchor_place.data(), anchor_seed.data(), nullptr);
         }
+        if (rc == FBG_OK && chain && strands)
+            rc = fbg_pindex_chain_strands(ix, strand.data(), best_score.data(), nullptr, nullptr, nullptr, nullptr);
     }
     if (rc == FBG_OK && !occurrences && !seeds)
         rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
@@ -320,24 +350,35 @@ int main(int argc, char **argv)
     const std::vector<uint64_t> *const o[2] = {&end_off, &start_off}, *const t[2] = {&end_total, &start_total};
     uint64_t found = 0;
     if (seeds) {
-        for (uint64_t k = 0; k < np; k++) {
-            const uint64_t ns = seed_off[k + 1] - seed_off[k];
-            std::cout << "Pattern? " << ns << " seeds found.\n";
-            if (ns == 0 && error_on_not_found) {
-                std::cerr << "Pattern has no seed.\n";
-                std::cout.flush();
-                return EXIT_FAILURE;
-            }
-            found += ns != 0;
-            for (uint64_t j = seed_off[k]; j < seed_off[k + 1]; j++) {
+        // the S / E / B (/ C / A) lines of virtual read v
+        auto block = [&](uint64_t v) {
+            for (uint64_t j = seed_off[v]; j < seed_off[v + 1]; j++) {
                 std::cout << "S\t" << q_start[j] << '\t' << length[j] << '\t' << seed_count[j] << '\t' << restarts[j] << '\n';
                 if (occurrences) print_places(g, j, o, t, places, want_coords ? coords : nullptr);
             }
             if (chain) {
-                std::cout << "C\t" << chain_score[k] << '\t' << chain_off[k + 1] - chain_off[k] << '\n';
-                for (uint64_t i = chain_off[k]; i < chain_off[k + 1]; i++)
+                std::cout << "C\t" << chain_score[v] << '\t' << chain_off[v + 1] - chain_off[v] << '\n';
+                for (uint64_t i = chain_off[v]; i < chain_off[v + 1]; i++)
                     std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]
                               << '\t' << coords[3][anchor_place[i]] << '\n';
+            }
+        };
+        for (uint64_t k = 0; k < np; k++) {
+            const uint64_t ns = seed_off[k + 1] - seed_off[k];
+            const uint64_t nr = strands ? seed_off[np + k + 1] - seed_off[np + k] : 0;
+            std::cout << "Pattern? " << ns << " seeds found.\n";
+            if (ns + nr == 0 && error_on_not_found) {
+                std::cerr << "Pattern has no seed.\n";
+                std::cout.flush();
+                return EXIT_FAILURE;
+            }
+            found += ns + nr != 0;
+            block(k);
+            if (strands) {
+                std::cout << "-\t" << nr << '\n';
+                block(np + k);
+                if (chain)
+                    std::cout << "T\t" << (strand[k] == FBG_STRAND_NONE ? '*' : strand[k] ? '-' : '+') << '\t' << best_score[k] << '\n';
             }
         }
         std::cout << "Pattern? " << found << " out of " << np << " patterns seeded" << std::endl;

@@ -81,9 +81,11 @@ struct PoState {
 // fbg_pindex_chains: per start place of the last fbg_pindex_seeds its MSA row and column (col: rows first, a copy apart
 // from sd.msa) and its predecessor; per read the binning keys and ids (before and after the sort), the chain's end
 // place, score and length, the scan of the lengths; the chains (places, then seeds); the spill tier's slab (a uint4 per
-// start place, reserved when a read needs it); the counters of k_pc_key and k_pc_chain.
+// start place, reserved when a read needs it); the counters of k_pc_key and k_pc_chain.  fbg_pindex_chain_strands: per
+// given read its strand and best score, and the three counters of k_pc_strand.
 struct PcState {
     DevBuf col, pred, key, id, key2, id2, end, score, len, off, out, slab, ctr;
+    DevBuf strand, best, sctr;
     bool ready = false;
     uint64_t n = 0, total = 0, anchors = 0, tier[3] = {0, 0, 0};
 };
@@ -124,7 +126,9 @@ struct fbg_pindex {
     PoState occ;
     DevBuf snum, soff, srec, scnt, spos, sq, slen;
     PoState sd;
-    uint64_t sd_reads = 0;        // n_patterns of the last successful fbg_pindex_seeds
+    uint64_t sd_reads = 0;        // reads of the last successful fbg_pindex_seeds (_strands: the 2n virtual reads)
+    bool sd_stranded = false;     // the last seeds call was fbg_pindex_seeds_strands, with sd_reads / 2 given reads
+    DevBuf comp;                  // its complement table (256 bytes)
     PcState ch;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -526,6 +530,45 @@ __global__ void k_px_rebase(uint64_t *off, uint64_t n, uint64_t base)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t <= n) off[t] -= base;
+}
+
+// fbg_pindex_seeds_strands: the reverse virtual reads.  pats[0 .. total) and poff[0 .. n] (rebased: poff[0] = 0,
+// poff[n] = total) are the given reads; the kernel writes pats[total + j] = comp[pats[poff[R] + poff[R + 1] - 1 - j]]
+// for every j in [poff[R], poff[R + 1]) and poff[n + R] = total + poff[R] for R = 1 .. n (R = 0 is poff[n] itself and
+// already holds total).  One lane per aligned 8-byte word of the destination: it finds the read of its first byte by
+// a search of poff, walks on through poff where reads end inside the word (empty reads are stepped over) and stores
+// the word whole; the two words that the range [total, 2 * total) covers only in part are stored byte by byte, so the
+// forward bytes that share the first one are left alone.  The table sits in LDS.  The first n lanes of the grid also
+// write the offsets.  n > 0.
+__global__ __launch_bounds__(PX_THREADS) void k_px_revcomp(const uint8_t *comp_g, uint8_t *pats, uint64_t *poff, uint64_t n,
+                                                          uint64_t total)
+{
+    __shared__ uint8_t comp[256];
+    for (int c = threadIdx.x; c < 256; c += blockDim.x) comp[c] = comp_g[c];
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t b0 = (total / 8 + t) * 8;                  // the word's first byte in pats
+    const uint64_t lo = b0 > total ? b0 : total, hi = b0 + 8 < 2 * total ? b0 + 8 : 2 * total;
+    if (lo < hi) {
+        uint64_t j = lo - total;
+        uint64_t R = 0, top = n;                              // poff[R] <= j < poff[top]
+        while (top - R > 1) {
+            const uint64_t mid = R + (top - R) / 2;
+            if (poff[mid] <= j) R = mid; else top = mid;
+        }
+        uint64_t a = poff[R], e = poff[R + 1];
+        uint64_t word = 0;
+        for (uint64_t b = lo; b < hi; b++, j++) {
+            while (j >= e) { R++; a = e; e = poff[R + 1]; }   // j < total = poff[n]: R stays below n
+            word |= (uint64_t)comp[pats[a + (e - 1 - j)]] << (8 * (b - b0));
+        }
+        if (hi - lo == 8) {
+            *(uint64_t *)(pats + b0) = word;
+        } else {
+            for (uint64_t b = lo; b < hi; b++) pats[b] = (uint8_t)(word >> (8 * (b - b0)));
+        }
+    }
+    if (t < n) poff[n + 1 + t] = total + poff[1 + t];
 }
 
 // ctab[j] = the last edge e < E with estart[e] <= j << PV_CSHIFT (estart[0] = 0)
@@ -1616,6 +1659,27 @@ __global__ void k_pc_trace(PcDev d, uint64_t n, uint64_t min_score, uint64_t *le
     }
 }
 
+// fbg_pindex_chain_strands: one lane per given read R < n picks between the chains of the virtual reads R and n + R.
+// len is what the counting trace left (0 below min_score).  ctr: reads that went forward, reverse, to neither; summed
+// per wave before the atomic.
+__global__ void k_pc_strand(const uint32_t *score, const uint64_t *len, uint64_t n, uint8_t *strand, uint32_t *best,
+                            unsigned long long *ctr)
+{
+    const uint64_t R = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int out = -1;
+    if (R < n) {
+        const uint32_t s0 = score[R], s1 = score[n + R];
+        const int t = s1 > s0;
+        out = len[t ? n + R : R] ? t : 2;
+        strand[R] = out == 2 ? (uint8_t)FBG_STRAND_NONE : (uint8_t)out;
+        best[R] = t ? s1 : s0;
+    }
+    for (int b = 0; b < 3; b++) {
+        const unsigned long long m = __ballot(out == b);
+        if (m && (threadIdx.x & (FBG_WAVE - 1)) == 0) atomicAdd(&ctr[b], (unsigned long long)__popcll(m));
+    }
+}
+
 // ---- C ABI ------------------------------------------------------------------------------------------------------
 extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
                                 const uint64_t *edge_off, const uint64_t *edge_dst, fbg_pindex **out)
@@ -1649,8 +1713,11 @@ static int po_reserve(fbg_pindex *ix, PoState &s, uint64_t n)
 
 // The front of fbg_pindex_locate, fbg_pindex_occurrences and fbg_pindex_seeds: checks, every allocation of the call
 // that depends on n only (after hipSetDevice), patterns onto the device, ev0, and the pattern ids sorted by length into
-// oval2.  n > 0.
-static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns, PxMode mode)
+// oval2.  n > 0.  comp (PX_SEEDS only; NULL: the reads as given): the complement table of fbg_pindex_seeds_strands.
+// Everything is then reserved for 2n reads and twice the bytes, k_px_revcomp appends the reverse virtual reads after
+// ev0, and the sort runs over the 2n.
+static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns, PxMode mode,
+                    const uint8_t *comp = nullptr)
 {
     fbg_ctx *ctx = ix->ctx;
     for (uint64_t k = 0; k < n_patterns; k++)
@@ -1661,10 +1728,13 @@ static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
                 return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: pattern %llu has 2^32 symbols or more", who, (unsigned long long)k);
     const uint64_t base = pat_off[0], total = pat_off[n_patterns] - base;
     if (total && !patterns) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing patterns", who);
+    if (comp && total > (0xffffffffffffffffull - 64) / 2)
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: the patterns and their reverse complements hold 2^64 bytes or more", who);
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const uint64_t n = n_patterns;
-    FBG_TRY(fbg_reserve(ix->ctx, ix->pats, ((total + 7) & ~7ull) + 16, &ix->bufs, false));
+    const uint64_t n = comp ? 2 * n_patterns : n_patterns;     // reads on the device
+    const uint64_t pbytes = comp ? 2 * total : total;
+    FBG_TRY(fbg_reserve(ix->ctx, ix->pats, ((pbytes + 7) & ~7ull) + 16, &ix->bufs, false));
     FBG_TRY(fbg_reserve(ix->ctx, ix->poff, (n + 1) * 8, &ix->bufs, false));
     for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
     if (mode == PX_SEEDS) {
@@ -1680,12 +1750,19 @@ static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     }
     if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
     if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    if (comp) FBG_TRY(fbg_reserve(ix->ctx, ix->comp, 256, &ix->bufs, false));
     if (total) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->pats.p, patterns + base, total, hipMemcpyHostToDevice, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->poff.p, pat_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->poff.p, pat_off, (n_patterns + 1) * 8, hipMemcpyHostToDevice, st));
+    if (comp) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->comp.p, comp, 256, hipMemcpyHostToDevice, st));
     if (mode != PX_SEEDS) FBG_HIP_TRY(ctx, hipMemsetAsync(ix->lines_ctr.p, 0, 8, st));
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
     uint64_t *poff = ix->poff.as<uint64_t>();
-    if (base) hipLaunchKernelGGL(k_px_rebase, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, poff, n, base);
+    if (base) hipLaunchKernelGGL(k_px_rebase, dim3(fbg_blocks(n_patterns + 1, 256)), dim3(256), 0, st, poff, n_patterns, base);
+    if (comp) {
+        const uint64_t words = (2 * total + 7) / 8 - total / 8;
+        hipLaunchKernelGGL(k_px_revcomp, dim3(fbg_blocks(std::max(words, n_patterns), PX_THREADS)), dim3(PX_THREADS), 0, st,
+                           ix->comp.as<uint8_t>(), ix->pats.as<uint8_t>(), poff, n_patterns, total);
+    }
     // lanes of a wave take patterns of similar length: pattern ids sorted by length
     uint32_t *ka = ix->okey.as<uint32_t>(), *va = ix->oval.as<uint32_t>(), *kb = ix->okey2.as<uint32_t>(), *vb = ix->oval2.as<uint32_t>();
     hipLaunchKernelGGL(k_px_lenkey, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, poff, n, ka, va);
@@ -1962,25 +2039,29 @@ template <bool COMPACT, bool WRITE> static void px_seeds_launch(fbg_pindex *ix, 
                        ix->sq.as<uint32_t>(), ix->slen.as<uint32_t>());
 }
 
-extern "C" int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
-                                uint64_t min_length, uint64_t max_per_seed, uint64_t *seed_off, double *device_ms)
+// The body of fbg_pindex_seeds (comp == NULL) and fbg_pindex_seeds_strands (comp: the 256-byte table; the device then
+// searches the 2 * n_patterns virtual reads and seed_off has that many entries and one).
+static int px_seeds(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                    const uint8_t *comp, uint64_t min_length, uint64_t max_per_seed, uint64_t *seed_off, double *device_ms)
 {
-    if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
     PoState &s = ix->sd;
     s.ready = false;
     ix->ch.ready = false;         // chains belong to the seeds they were made from
     if (device_ms) *device_ms = 0;
-    if (!seed_off || (n_patterns && !pat_off)) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds: missing argument");
-    if (min_length == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds: min_length is 1 or more");
-    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_seeds: at most 2^32 - 2 patterns per call");
+    if (!seed_off || (n_patterns && !pat_off)) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing argument", who);
+    if (min_length == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: min_length is 1 or more", who);
+    if (n_patterns >= 0xffffffffull) return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: at most 2^32 - 2 patterns per call", who);
+    if (comp && 2 * n_patterns >= 0xffffffffull)
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: at most 2^31 - 1 patterns per call (both strands: 2^32 - 2 reads)", who);
     seed_off[0] = 0;
     s.n = 0;
     s.etotal = s.stotal = 0;
-    ix->sd_reads = n_patterns;
-    if (n_patterns == 0) { s.ready = true; return FBG_OK; }
-    const uint64_t n = n_patterns;
-    FBG_TRY(px_front(ix, "fbg_pindex_seeds", patterns, pat_off, n, PX_SEEDS));
+    const uint64_t n = comp ? 2 * n_patterns : n_patterns;
+    ix->sd_reads = n;
+    ix->sd_stranded = comp != nullptr;
+    if (n == 0) { s.ready = true; return FBG_OK; }
+    FBG_TRY(px_front(ix, who, patterns, pat_off, n_patterns, PX_SEEDS, comp));
     hipStream_t st = ctx->stream;
     const bool none = min_length >= (1ull << 32);   // no pattern has 2^32 symbols: nothing can be reported
     const uint32_t L = none ? 0xffffffffu : (uint32_t)min_length;
@@ -2004,8 +2085,8 @@ extern "C" int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const u
     }
     const uint64_t S = seed_off[n];
     if (S >= (1ull << 32))
-        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_seeds: %llu seeds to report; a call takes fewer than 2^32 (raise min_length or "
-                        "split the batch)", (unsigned long long)S);
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: %llu seeds to report; a call takes fewer than 2^32 (raise min_length or "
+                        "split the batch)", who, (unsigned long long)S);
     uint64_t tot[2] = {0, 0};
     if (S) {
         FBG_TRY(fbg_reserve(ix->ctx, ix->srec, S * 24, &ix->bufs, false));
@@ -2025,13 +2106,36 @@ extern "C" int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const u
     FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
     if (device_ms) *device_ms = ms;
     if (tot[0] >= (1ull << 32) || tot[1] >= (1ull << 32))
-        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_seeds: %llu ends and %llu starts to report; a list takes fewer than 2^32 "
-                        "entries (lower max_per_seed or split the batch)", (unsigned long long)tot[0], (unsigned long long)tot[1]);
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: %llu ends and %llu starts to report; a list takes fewer than 2^32 "
+                        "entries (lower max_per_seed or split the batch)", who, (unsigned long long)tot[0], (unsigned long long)tot[1]);
     s.n = S;
     s.etotal = tot[0];
     s.stotal = tot[1];
     s.ready = true;
     return FBG_OK;
+}
+
+extern "C" int fbg_pindex_seeds(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                                uint64_t min_length, uint64_t max_per_seed, uint64_t *seed_off, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    return px_seeds(ix, "fbg_pindex_seeds", patterns, pat_off, n_patterns, nullptr, min_length, max_per_seed, seed_off, device_ms);
+}
+
+extern "C" int fbg_pindex_seeds_strands(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                                        const uint8_t *complement, uint64_t min_length, uint64_t max_per_seed, uint64_t *seed_off,
+                                        double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    uint8_t table[256];
+    if (!complement) {
+        for (int c = 0; c < 256; c++) table[c] = (uint8_t)c;
+        const char *pairs = "ATCGatcg";
+        for (int k = 0; k < 8; k += 2) { table[(uint8_t)pairs[k]] = pairs[k + 1]; table[(uint8_t)pairs[k + 1]] = pairs[k]; }
+        complement = table;
+    }
+    return px_seeds(ix, "fbg_pindex_seeds_strands", patterns, pat_off, n_patterns, complement, min_length, max_per_seed, seed_off,
+                    device_ms);
 }
 
 extern "C" int fbg_pindex_seeds_fetch(fbg_pindex *ix, uint32_t *q_start, uint32_t *length, uint64_t *count, uint32_t *restarts,
@@ -2202,6 +2306,50 @@ extern "C" int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, u
     float ms = 0;
     FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
     if (device_ms) *device_ms = ms;
+    return FBG_OK;
+}
+
+// The strand of every given read from the scores and lengths fbg_pindex_chains left on the device (k_pc_strand).  Where
+// that call found no start place at all it returned before touching the device: every read is then without a chain.
+extern "C" int fbg_pindex_chain_strands(fbg_pindex *ix, uint8_t *strand, uint32_t *score, uint64_t *n_forward, uint64_t *n_reverse,
+                                        uint64_t *n_none, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PcState &c = ix->ch;
+    if (device_ms) *device_ms = 0;
+    if (!ix->sd.ready || !ix->sd_stranded)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chain_strands: the last seeds call was no successful fbg_pindex_seeds_strands");
+    if (!c.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chain_strands: no fbg_pindex_chains result since that seeds call");
+    const uint64_t n = ix->sd_reads / 2;
+    if (n == 0) return FBG_OK;
+    uint64_t cnt[3] = {0, 0, n};
+    if (ix->sd.n == 0 || ix->sd.stotal == 0) {
+        if (strand) std::fill(strand, strand + n, (uint8_t)FBG_STRAND_NONE);
+        if (score) std::fill(score, score + n, (uint32_t)0);
+    } else {
+        FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        FBG_TRY(fbg_reserve(ix->ctx, c.strand, n, &ix->bufs, false));
+        FBG_TRY(fbg_reserve(ix->ctx, c.best, n * 4, &ix->bufs, false));
+        FBG_TRY(fbg_reserve(ix->ctx, c.sctr, 3 * 8, &ix->bufs, false));
+        FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+        FBG_HIP_TRY(ctx, hipMemsetAsync(c.sctr.p, 0, 3 * 8, st));
+        hipLaunchKernelGGL(k_pc_strand, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, c.score.as<uint32_t>(), c.len.as<uint64_t>(), n,
+                           c.strand.as<uint8_t>(), c.best.as<uint32_t>(), c.sctr.as<unsigned long long>());
+        FBG_HIP_TRY(ctx, hipGetLastError());
+        FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+        if (strand) FBG_HIP_TRY(ctx, hipMemcpyAsync(strand, c.strand.p, n, hipMemcpyDeviceToHost, st));
+        if (score) FBG_HIP_TRY(ctx, hipMemcpyAsync(score, c.best.p, n * 4, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(cnt, c.sctr.p, 3 * 8, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        float ms = 0;
+        FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+        if (device_ms) *device_ms = ms;
+    }
+    if (n_forward) *n_forward = cnt[0];
+    if (n_reverse) *n_reverse = cnt[1];
+    if (n_none) *n_none = cnt[2];
     return FBG_OK;
 }
 

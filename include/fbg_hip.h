@@ -660,6 +660,43 @@ int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, uint32_t *an
 int fbg_pindex_chain_stats(const fbg_pindex *ix, uint64_t *anchors, uint64_t *reads_small, uint64_t *reads_wave,
                            uint64_t *reads_spill, uint64_t *small_max, uint64_t *lds_max);
 
+/* Both strands: seeds and chains of every read and of its reverse complement, from one upload.
+ *
+ *   complement table   comp: 256 bytes.  NULL stands for the default: A <-> T, C <-> G, a <-> t, c <-> g, every other
+ *                      byte maps to itself.
+ *   reverse complement for a read P of length L: rc(P)[i] = comp[P[L - 1 - i]].  The table is applied once per symbol; it
+ *                      need not be an involution.  Bytes that map to '#' or to zero get no special treatment: whatever
+ *                      the search does with them is the answer, as for fbg_pindex_seeds.
+ *   virtual reads      the n reads P_0 .. P_{n-1} make 2n virtual reads: read R is the forward read P_R, read n + R is
+ *                      rc(P_R).  The layout is blocked, not interleaved.
+ *   seed coordinates   the seeds of a reverse virtual read are reported in the coordinates of rc(P_R): a seed (q, k)
+ *                      there covers P_R[L - q - k : L - q].
+ *
+ *   fbg_pindex_seeds_strands   by definition fbg_pindex_seeds on those 2n patterns; seed_off has 2n + 1 entries.
+ *       Afterwards fbg_pindex_seeds_fetch, _places, _msa, fbg_pindex_chains, _chains_fetch and fbg_pindex_chain_stats
+ *       behave exactly as after that fbg_pindex_seeds call, with 2n reads.  The chains of reverse virtual reads ascend in
+ *       the MSA columns like any other: the read is complemented, not the graph.  On the device the given reads are
+ *       uploaded once, a kernel appends their reverse complements and the second half of the offsets, and the length
+ *       sort, the two walks and the sizes of fbg_pindex_seeds run over the 2n reads.  *device_ms covers that kernel too.
+ *       State rules and errors are those of fbg_pindex_seeds, and: FBG_ERR_TOO_LARGE if 2n >= 2^32 - 1 or if twice the
+ *       pattern bytes do not fit the 64-bit size sums.  The index remembers that its seeds are stranded and with which
+ *       n; a later fbg_pindex_seeds clears that.
+ *   fbg_pindex_chain_strands   the strand of every given read.  It needs a successful fbg_pindex_seeds_strands as the
+ *       last seeds call and a successful fbg_pindex_chains since it, else FBG_ERR_INVALID.  With s0, s1 the scores that
+ *       fbg_pindex_chains reported for the virtual reads R and n + R, and c0, c1 whether their chains are non-empty:
+ *       t = 1 if s1 > s0, else 0 (a tie goes to the forward strand); strand[R] = t if chain t is non-empty, else
+ *       FBG_STRAND_NONE; score[R] = max(s0, s1) always; *n_forward, *n_reverse and *n_none count the reads by outcome.
+ *       Any output pointer may be NULL; with n == 0 the call writes nothing and returns FBG_OK.  The chain of read R is
+ *       then entries chain_off[t * n + R] .. chain_off[t * n + R + 1] of what fbg_pindex_chains_fetch returned: nothing
+ *       is copied or reordered.  The call leaves every other state alone and may be repeated.  *device_ms (may be NULL):
+ *       device time of the kernel. */
+#define FBG_STRAND_NONE 0xff
+int fbg_pindex_seeds_strands(fbg_pindex *ix, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns,
+                             const uint8_t *complement, uint64_t min_length, uint64_t max_per_seed, uint64_t *seed_off,
+                             double *device_ms);
+int fbg_pindex_chain_strands(fbg_pindex *ix, uint8_t *strand, uint32_t *score, uint64_t *n_forward, uint64_t *n_reverse,
+                             uint64_t *n_none, double *device_ms);
+
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
  * to_remove[node_blocks[i] - 1] (fbg.cpp:3269-3270, 3194); cut_bad[nb - 1] is always 0.  The index is built by
