@@ -309,14 +309,16 @@ class Engine:
         self._pindexes.add(pix)
         return pix
 
-    def pattern_index_of_segmentation(self, boundaries):
+    def pattern_index_of_segmentation(self, boundaries, rows=False):
         """Pattern index of the graph that `boundaries` cuts out of the current MSA, built on the device
         (fbg_pindex_build_segmentation): the index pattern_index(*graph_from_segmentation(...)) gives, without the trip
         of nodes, edges and labels through the host.  node_block / first_node: the block of every node, the first
-        node of every block."""
+        node of every block.  rows=True (fbg_pindex_build_segmentation_rows): the same index plus the row table that
+        seeds(rows=True), chains(rows=True) and rows_stats() need."""
         b = np.ascontiguousarray(boundaries, dtype=np.uint64)
         h = C.c_void_p()
-        self._chk(self._L.fbg_pindex_build_segmentation(self._h, _u64(b), len(b), C.byref(h)))
+        build = self._L.fbg_pindex_build_segmentation_rows if rows else self._L.fbg_pindex_build_segmentation
+        self._chk(build(self._h, _u64(b), len(b), C.byref(h)))
         pix = PatternIndex._adopt(self, h, len(b))
         if not hasattr(self, "_pindexes"):
             self._pindexes = weakref.WeakSet()
@@ -508,15 +510,24 @@ class PatternIndex:
         return Occurrences(self._label_len, count[:k], pos[:k], rs[:k], et[:k], st[:k], eoff, soff, [a[:ne] for a in ends],
                            [a[:ns] for a in starts], ms1.value, ms2.value, coords, ms3)
 
+    def rows_stats(self):
+        """{rows, table_bytes, words_per_set, places_unsupported, chains_unsupported} of the row table and of the last
+        seeds(rows=True) / chains(rows=True) (fbg_pindex_rows_stats; an index built with rows=True only)."""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._eng._chk(self._L.fbg_pindex_rows_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("rows", "table_bytes", "words_per_set", "places_unsupported", "chains_unsupported"), (x.value for x in v)))
+
     def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False, chain=False, band=None, min_score=0, strands=False,
-              complement=None):
+              complement=None, rows=False):
         """Every read cut greedily into the maximal pieces the search accepts (fbg_pindex_seeds, _fetch and _places):
         seeds of at least min_length symbols, each with what occurrences() reports for that substring, at most
         max_per_seed places per seed and list -> Seeds.  msa=True: as for occurrences() (fbg_pindex_seeds_msa).
         chain=True: also chains(band, min_score) of these seeds, as Seeds.chains.  strands=True: every read is searched
         as given and as its reverse complement under complement_table(complement), made on the device
         (fbg_pindex_seeds_strands): the Seeds then cover 2k virtual reads, the k given ones and then their k reverse
-        complements, and chains() also picks a strand per read."""
+        complements, and chains() also picks a strand per read.  rows=True (an index built with rows=True only): also,
+        per start place, the number of MSA rows that carry it and the smallest of them (fbg_pindex_seeds_rows), as
+        Seeds.start_n_rows / Seeds.start_first_row; with chain=True the chains get their row sets too."""
         if min_length < 1:
             raise ValueError("min_length must be 1 or more")
         if max_per_seed < 0:
@@ -552,17 +563,24 @@ class PatternIndex:
         self._seed_reads = k
         self._seed_given = given if strands else None
         out = Seeds(seed_off, q[:n], ln[:n], occ, np.diff(off.astype(np.int64)), strands)
+        if rows:
+            nr, fr = np.zeros(max(ns, 1), dtype=np.uint32), np.zeros(max(ns, 1), dtype=np.uint32)
+            ms5 = C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_seeds_rows(self._h, u32(nr), u32(fr), C.byref(ms5)))
+            out.start_n_rows, out.start_first_row, out.rows_ms = nr[:ns], fr[:ns], ms5.value
         if chain:
-            out.chains = self.chains(band=band, min_score=min_score)
+            out.chains = self.chains(band=band, min_score=min_score, rows=rows)
         return out
 
-    def chains(self, band=None, min_score=0):
+    def chains(self, band=None, min_score=0, rows=False):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
         neighbours at most band (None: unbounded); chains scoring below min_score come out empty -> Chains.  After
         seeds(strands=True) the chains cover the 2k virtual reads and the strand of every given read is picked from
-        their scores on the device (fbg_pindex_chain_strands)."""
+        their scores on the device (fbg_pindex_chain_strands).  rows=True (an index built with rows=True only): also
+        the MSA rows that carry every anchor of a read's chain (fbg_pindex_chains_rows), as Chains.n_rows, .first_row
+        and .row_set(k)."""
         if band is not None and band < 0:
             raise ValueError("band must be 0 or more, or None")
         if min_score < 0:
@@ -589,6 +607,15 @@ class PatternIndex:
             out.strand, out.best_score = strand[:given], best[:given]
             out.strand_counts = dict(zip(("forward", "reverse", "none"), (x.value for x in cnt)))
             out.strand_ms = ms3.value
+        if rows:
+            words = self.rows_stats()["words_per_set"]
+            nr, fr = np.zeros(max(k, 1), dtype=np.uint32), np.zeros(max(k, 1), dtype=np.uint32)
+            bits = np.zeros(max(k * words, 1), dtype=np.uint64)
+            ms4 = C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chains_rows(self._h, nr.ctypes.data_as(_lib.u32p), fr.ctypes.data_as(_lib.u32p),
+                                                          _u64(bits), C.byref(ms4)))
+            out.n_rows, out.first_row, out.rows_ms = nr[:k], fr[:k], ms4.value
+            out.row_bits = bits[:k * words].reshape(k, words)
         return out
 
     def chain_stats(self):
@@ -728,11 +755,15 @@ class Seeds:
                           coordinates of the reverse complement.  Otherwise False and the number of reads
       q_forward           int64 per seed: its start in the given read, q_start for a forward seed and
                           L - q_start - length for one of the reverse complement of a read of L symbols
+      start_n_rows, start_first_row   asked for with rows=True (None otherwise), uint32 per start place of occ: the number
+                          of MSA rows that carry the seed from that place on, and the smallest of them (0xffffffff: none,
+                          a place only a recombinant path of the graph spells)
     search_ms: device time of fbg_pindex_seeds; fetch_ms: of the per-seed copies and the expansion of the places."""
 
     def __init__(self, seed_off, q_start, length, occ, read_len=None, strands=False):
         self.seed_off, self.q_start, self.length, self.occ = seed_off, q_start, length, occ
         self.chains = None
+        self.start_n_rows = self.start_first_row = None
         self.pattern_of = np.repeat(np.arange(len(seed_off) - 1, dtype=np.int64), np.diff(seed_off.astype(np.int64)))
         self.search_ms, self.fetch_ms = occ.search_ms, occ.fetch_ms
         self.strands = bool(strands)
@@ -768,6 +799,10 @@ class Chains:
                       the chain of that strand is empty
       best_score      uint32 per read: the larger of the two scores
       strand_counts   {forward, reverse, none}: the reads by outcome
+    and, asked for with rows=True (None otherwise):
+      n_rows, first_row   uint32 per read: how many MSA rows carry every anchor of its chain, and the smallest of them
+                      (0 and 0xffffffff for an empty chain, and for one whose anchors no single row carries)
+      row_bits        uint64[k, words_per_set]: bit r % 64 of word r // 64 is set for each such row r; row_set(k) lists them
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -775,6 +810,14 @@ class Chains:
         self.anchor_place, self.anchor_seed = anchor_place, anchor_seed
         self.device_ms, self.fetch_ms = device_ms, fetch_ms
         self.strand = self.best_score = self.strand_counts = None
+        self.n_rows = self.first_row = self.row_bits = None
+
+    def row_set(self, k):
+        """int64[n_rows[k]]: the rows that carry the whole chain of read k, ascending."""
+        if self.row_bits is None:
+            raise ValueError("no row sets: ask for them with rows=True")
+        w = self.row_bits[k]
+        return np.flatnonzero(np.unpackbits(w.view(np.uint8), bitorder="little")).astype(np.int64)
 
     def of(self, k):
         """int64[rows, 2]: (anchor_place, anchor_seed) of the chain of read k."""

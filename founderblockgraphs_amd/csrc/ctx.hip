@@ -215,6 +215,7 @@ static const OptKey g_opt_keys[] = {
     {"dpw_matrix", &FbgOptions::dpw_matrix},
     {"dp_chain1", &FbgOptions::dp_chain1},
     {"msd_ext", &FbgOptions::msd_ext},
+    {"rows_wave", &FbgOptions::rows_wave},
 };
 
 // read-only keys of fbg_get_option: what the context and its last build report

@@ -3,7 +3,7 @@
 // place of its .index file:
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
-//              [--chain[=BAND]] [--strands] [--complement=FROMTO]
+//              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -40,6 +40,10 @@
 //   T <tab> + | - | * <tab> score                     the strand whose chain scores higher (a tie: +; * if that chain is
 //                                                     empty) and the higher score (fbg_pindex_chain_strands)
 // A pattern counts as seeded with a seed on either strand, and --error-on-not-found fails at the first with none on both.
+// --rows (with --seeds and --msa) builds the index with its row table (fbg_pindex_build_segmentation_rows) and appends
+// `<tab> rows <tab> first` to every B line of a seed and to every C line: how many MSA rows carry the seed from that place
+// on, or every anchor of the chain, and the smallest of them, from 0 (fbg_pindex_seeds_rows / _chains_rows; `*` for first
+// when there is none: a place or chain that only a recombinant path of the graph spells).  Without --rows no line changes.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -57,7 +61,7 @@ static int usage(const char *msg)
 {
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
-              << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO]\n"
+              << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -75,7 +79,11 @@ static int usage(const char *msg)
               << "                     line `- K` and the K seeds of the reverse complement in the same format; with --chain a\n"
               << "                     closing T line: + or - for the strand of the better chain (* if it is empty), its score\n"
               << "  --complement=FROMTO  pairs of characters for --strands, e.g. ATTACGGC (the default, and the same in lower\n"
-              << "                     case); every byte not named maps to itself\n";
+              << "                     case); every byte not named maps to itself\n"
+              << "  --rows             needs --seeds and --msa: every B line of a seed and every C line ends with the number\n"
+              << "                     of MSA rows that carry the seed from that place on (the C line: every anchor of the\n"
+              << "                     chain) and the smallest such row, from 0 (* if no row does: only a recombinant path\n"
+              << "                     of the graph spells it); no other line changes\n";
     return EXIT_FAILURE;
 }
 
@@ -116,9 +124,18 @@ static bool read_segmentation(const std::string &path, uint64_t &m, uint64_t &n,
 }
 
 // the E / B lines of item k of a place state: offsets o[2], totals t[2], places p[6] (end src / dst / offset, start ...);
-// rc (NULL without --msa): end row / column, start row / column
+// rc (NULL without --msa): end row / column, start row / column; rows (NULL without --rows): per start its supporting
+// rows and the first of them
+static void print_row_set(uint32_t n_rows, uint32_t first)
+{
+    std::cout << '\t' << n_rows << '\t';
+    if (first == 0xffffffffu) std::cout << '*';
+    else std::cout << first;
+}
+
 static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint64_t> *const o[2], const std::vector<uint64_t> *const t[2],
-                         const std::vector<uint32_t> *p, const std::vector<uint32_t> *rc = nullptr)
+                         const std::vector<uint32_t> *p, const std::vector<uint32_t> *rc = nullptr,
+                         const std::vector<uint32_t> *rows = nullptr)
 {
     for (int w = 0; w < 2; w++) {
         const std::vector<uint64_t> &off = *o[w];
@@ -131,6 +148,7 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
                 if (r == 0xffffffffu && c == 0xffffffffu) std::cout << "\t*\t*";
                 else std::cout << '\t' << r << '\t' << c;
             }
+            if (w && rows) print_row_set(rows[0][i], rows[1][i]);
             std::cout << '\n';
         }
         if (total > off[k + 1] - off[k]) std::cout << tag << "...\t" << total - (off[k + 1] - off[k]) << " more\n";
@@ -140,7 +158,7 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement;
-    bool have_msa = false, have_complement = false, strands = false;
+    bool have_msa = false, have_complement = false, strands = false, rows = false;
     bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
     uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
     for (int i = 1; i < argc; i++) {
@@ -154,6 +172,7 @@ int main(int argc, char **argv)
         if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns) ||
             value("--msa", msa_path, have_msa) || value("--complement", complement, have_complement)) continue;
         if (a == "--strands") { strands = true; continue; }
+        if (a == "--rows") { rows = true; continue; }
         if (a == "--error-on-not-found") { error_on_not_found = true; continue; }
         if (a == "--occurrences") { occurrences = true; continue; }
         if (a.compare(0, 14, "--occurrences=") == 0) {
@@ -199,6 +218,7 @@ int main(int argc, char **argv)
     if (chain && !(seeds && have_msa && occurrences && max_places > 0))
         return usage("--chain needs --seeds, --msa and --occurrences[=M] with M > 0");
     if (strands && !seeds) return usage("--strands needs --seeds");
+    if (rows && !(seeds && have_msa)) return usage("--rows needs --seeds and --msa");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
 
@@ -255,7 +275,9 @@ int main(int argc, char **argv)
         std::string why;
         if (bounds.size() > 1 && !std::is_sorted(bounds.begin(), bounds.end() - 1)) why = "the X line does not increase";
         rc = fbg_msa_load_host(ctx, msa.cells.data(), msa.m, msa.n);
-        if (rc == FBG_OK && why.empty()) rc = fbg_pindex_build_segmentation(ctx, bounds.data(), bounds.size(), &ix);
+        if (rc == FBG_OK && why.empty())
+            rc = rows ? fbg_pindex_build_segmentation_rows(ctx, bounds.data(), bounds.size(), &ix)
+                      : fbg_pindex_build_segmentation(ctx, bounds.data(), bounds.size(), &ix);
         if (rc == FBG_OK && why.empty()) {
             std::vector<uint32_t> len(nodes + 1);
             if (fbg_pindex_node_count(ix) != nodes)
@@ -289,6 +311,7 @@ int main(int argc, char **argv)
     std::vector<uint64_t> chain_off(nv + 1, 0);
     std::vector<uint32_t> chain_score(nv + 1, 0), anchor_place, anchor_seed, best_score(np + 1, 0);
     std::vector<uint8_t> strand(np + 1, 0);
+    std::vector<uint32_t> place_rows[2], chain_rows[2];     // --rows: supporting rows and the first of them
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -323,6 +346,14 @@ int main(int argc, char **argv)
         }
         if (rc == FBG_OK && chain && strands)
             rc = fbg_pindex_chain_strands(ix, strand.data(), best_score.data(), nullptr, nullptr, nullptr, nullptr);
+        if (rc == FBG_OK && rows && occurrences) {
+            for (int k = 0; k < 2; k++) place_rows[k].resize(start_off[ns] + 1);
+            rc = fbg_pindex_seeds_rows(ix, place_rows[0].data(), place_rows[1].data(), nullptr);
+        }
+        if (rc == FBG_OK && rows && chain) {
+            for (int k = 0; k < 2; k++) chain_rows[k].resize(nv + 1);
+            rc = fbg_pindex_chains_rows(ix, chain_rows[0].data(), chain_rows[1].data(), nullptr, nullptr);
+        }
     }
     if (rc == FBG_OK && !occurrences && !seeds)
         rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
@@ -354,10 +385,12 @@ int main(int argc, char **argv)
         auto block = [&](uint64_t v) {
             for (uint64_t j = seed_off[v]; j < seed_off[v + 1]; j++) {
                 std::cout << "S\t" << q_start[j] << '\t' << length[j] << '\t' << seed_count[j] << '\t' << restarts[j] << '\n';
-                if (occurrences) print_places(g, j, o, t, places, want_coords ? coords : nullptr);
+                if (occurrences) print_places(g, j, o, t, places, want_coords ? coords : nullptr, rows ? place_rows : nullptr);
             }
             if (chain) {
-                std::cout << "C\t" << chain_score[v] << '\t' << chain_off[v + 1] - chain_off[v] << '\n';
+                std::cout << "C\t" << chain_score[v] << '\t' << chain_off[v + 1] - chain_off[v];
+                if (rows) print_row_set(chain_rows[0][v], chain_rows[1][v]);
+                std::cout << '\n';
                 for (uint64_t i = chain_off[v]; i < chain_off[v + 1]; i++)
                     std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]
                               << '\t' << coords[3][anchor_place[i]] << '\n';

@@ -36,6 +36,10 @@
 //   k_pc_key / k_pc_chain / k_pc_trace   fbg_pindex_chains: the reads binned by their number of start places, the
 //                                    co-linear chaining DP over a read's start places in three tiers, and the walk back
 //                                    from the chain's end (a pass that counts, a scan, a pass that writes);
+//   k_pr_seed / k_pr_place / k_pr_rows / k_pr_chain   the MSA rows that carry a start place or a whole chain
+//                                    (fbg_pindex_seeds_rows / _chains_rows): per seed the byte its substring starts at,
+//                                    per start place its node, offset, seed and block, then lanes as rows: one read of
+//                                    the row table, a walk along the row's labels, a ballot per 64 rows;
 //   k_sv_cuts                        the cuts before blocks that hold an INVALID node (fbg_segmentation_validate / _repair).
 //
 // occ layout.  Symbols are remapped to dense codes in byte order (the sentinel is code 0, '#' code 1).  With at
@@ -67,6 +71,8 @@
 #define PC_SMALL 32           // start places of a read up to which PC_SUB lanes chain it (small_max)
 #define PC_LDS 1024           // start places of a read up to which a wave chains it with its state in LDS (lds_max)
 #define PC_NONE 0xffffffffu   // no predecessor / no chain end
+#define PR_SUB 16             // rows: lanes that share a place (or a chain) when the MSA has at most this many rows
+#define PR_NONE 0xffffffffu   // no node in a (row, block) cell (BG_NONE of block_graph.hip); no supporting row
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
@@ -88,6 +94,17 @@ struct PcState {
     DevBuf strand, best, sctr;
     bool ready = false;
     uint64_t n = 0, total = 0, anchors = 0, tier[3] = {0, 0, 0};
+};
+
+// The row table of fbg_pindex_build_segmentation_rows: node_of[nb * m], block-major, and the gathered labels with their
+// offsets (a node without an edge has no copy of its label in the index text).  reads / roff: the reads of the last seeds
+// call, moved aside when a locate or occurrences call is about to overwrite pats / poff (saved).  sbase: per seed the
+// byte of the reads its substring starts at; rec: per start place (node, offset in the node, seed, block) or PR_NONE
+// first; out / cout: what the last fbg_pindex_seeds_rows / _chains_rows copied out; ctr: its count of empty sets.
+struct PrState {
+    DevBuf node_of, labels, loff, reads, roff, sbase, rec, out, cout, ctr;
+    bool saved = false;
+    uint64_t m = 0, label_bytes = 0, read_bytes = 0, places_unsupported = 0, chains_unsupported = 0;
 };
 
 struct fbg_pindex {
@@ -130,6 +147,8 @@ struct fbg_pindex {
     bool sd_stranded = false;     // the last seeds call was fbg_pindex_seeds_strands, with sd_reads / 2 given reads
     DevBuf comp;                  // its complement table (256 bytes)
     PcState ch;
+    bool has_rows = false;        // built by fbg_pindex_build_segmentation_rows
+    PrState rw;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -1091,8 +1110,10 @@ __global__ __launch_bounds__(PX_THREADS) void k_ps_hist(const uint8_t *labels, c
 }
 
 // with_map: also the MSA coordinate table (fbg_pindex_build_segmentation; the rounds of fbg_segmentation_validate /
-// _repair report no places and leave it out)
-static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, PxPrep &pp, bool with_map)
+// _repair report no places and leave it out).  with_rows: also the row table (fbg_pindex_build_segmentation_rows only):
+// copies of node_of and of the gathered labels and their offsets, owned by the index.
+static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, PxPrep &pp, bool with_map,
+                                   bool with_rows)
 {
     fbg_ctx *ctx = ix->ctx;
     BlockGraphDev g;
@@ -1120,6 +1141,11 @@ static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t 
     uint64_t *len64 = s.len64.as<uint64_t>(), *loff = s.loff.as<uint64_t>(), *ebase = s.ebase.as<uint64_t>();
     auto *hist = s.hist.as<unsigned long long>(), *bad = hist + 256;
     FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->sfirst.p, g.first, (nb + 1) * 8, hipMemcpyDeviceToDevice, st));
+    ix->has_rows = false;
+    if (with_rows) {
+        FBG_TRY(R(ix->bufs, ix->rw.node_of, cells * 4));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->rw.node_of.p, g.node_of, cells * 4, hipMemcpyDeviceToDevice, st));
+    }
     FBG_HIP_TRY(ctx, hipMemsetAsync(hist, 0, 257 * 8, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(len64 + n_nodes, 0, 8, st));
     hipLaunchKernelGGL(k_ps_nodes, dim3(fbg_blocks(cells, 256)), dim3(256), 0, st, g.rep_row, g.count, g.first, m, nb, node_block, node_row);
@@ -1167,6 +1193,14 @@ static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t 
     hipLaunchKernelGGL(k_ps_labels<true>, gw, dim3(PX_THREADS), 0, st, ctx->d_msa, n, g.bounds, (const uint32_t *)node_block,
                        (const uint32_t *)node_row, n_nodes, (uint64_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr,
                        (const uint64_t *)loff, s.labels.as<uint8_t>());
+    if (with_rows) {
+        FBG_TRY(R(ix->bufs, ix->rw.labels, L));
+        FBG_TRY(R(ix->bufs, ix->rw.loff, (n_nodes + 1) * 8));
+        if (L) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->rw.labels.p, s.labels.p, L, hipMemcpyDeviceToDevice, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->rw.loff.p, loff, (n_nodes + 1) * 8, hipMemcpyDeviceToDevice, st));
+        ix->rw.m = m;
+        ix->rw.label_bytes = L;
+    }
     if (with_map) {
         // unit offsets are kept in 32 bits with PM_NONE set aside; the sums above are 64-bit, so nothing wraps
         if (h_units >= PM_NONE)
@@ -1226,14 +1260,16 @@ static int px_prepare_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t 
     pp.eoff_ready = true;
     ix->from_segmentation = true;
     ix->has_map = with_map;
+    ix->has_rows = with_rows;
     ix->seg_nb = nb;
     return FBG_OK;
 }
 
-static int px_build_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, bool with_map)
+static int px_build_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, bool with_map,
+                                 bool with_rows = false)
 {
     PxPrep pp;
-    FBG_TRY(px_prepare_segmentation(ix, s, boundaries, nb, pp, with_map));
+    FBG_TRY(px_prepare_segmentation(ix, s, boundaries, nb, pp, with_map, with_rows));
     return px_build_prepared(ix, s, pp);
 }
 
@@ -1680,6 +1716,149 @@ __global__ void k_pc_strand(const uint32_t *score, const uint64_t *len, uint64_t
     }
 }
 
+// ---- rows (fbg_pindex_seeds_rows / fbg_pindex_chains_rows) ----------------------------------------------------------
+// Row r supports the start place g of seed t iff g belongs to node u at o < |label(u)|, node_of[r][block(u)] == u, and
+// the read substring S of t equals the row's gap-stripped text from o inside label(u) on.  That text is label(u)[o:]
+// followed by the labels of the row's nodes in the blocks after block(u): cells without a node (the row is all gaps
+// there) are passed over, and the text ends with block nb - 1.
+struct PrDev {
+    const uint32_t *node_of;      // [nb * m], block-major: 64 lanes read 64 consecutive rows of one block
+    const uint8_t *labels;
+    const uint64_t *loff;         // [n_nodes + 1]
+    const uint8_t *reads;
+    const uint64_t *sbase;        // [S] byte of reads at which the seed's substring starts
+    const uint32_t *slen;         // [S]
+    uint64_t m, nb;
+};
+
+// sbase[t] = poff[R] + q_start[t] for seed t of read R (a search of the n + 1 seed offsets, as k_pc_trace's)
+__global__ void k_pr_seed(const uint64_t *seed_off, const uint64_t *poff, const uint32_t *q, uint64_t n, uint64_t S, uint64_t *sbase)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= S) return;
+    sbase[t] = poff[po_find(seed_off, 0, n - 1, t)] + q[t];
+}
+
+// k_po_expand_msa<true> up to the node and offset of the place, then rec[i] = (u, o, seed, block(u)); u = PR_NONE where
+// o is not below |label(u)| (no row supports such a place).
+__global__ __launch_bounds__(PX_THREADS) void k_pr_place(PvDev d, const uint32_t *node_block, const uint64_t *off, uint64_t n, uint64_t total,
+                                                        const uint32_t *first, const uint32_t *sk, const uint32_t *restarts, uint4 *rec)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t w0 = po_uniform(i & ~(uint64_t)(FBG_WAVE - 1));
+    if (w0 >= total) return;
+    const uint64_t w1 = w0 + FBG_WAVE - 1 < total ? w0 + FBG_WAVE - 1 : total - 1;
+    const uint64_t q0 = po_uniform(po_find(off, 0, n - 1, w0));
+    const uint64_t q1 = po_uniform(po_find(off, q0, n - 1, w1));
+    if (i >= total) return;
+    const uint64_t q = po_find(off, q0, q1, i);
+    const uint32_t p = d.sa[first[q] + (uint32_t)(i - off[q])];
+    const uint32_t e = pv_edge(d, p);
+    const uint32_t base = d.estart[e] + 1, ne = d.estart[e + 1] - base;
+    uint32_t o = restarts[q] ? ne - sk[q] : ne - 1 - (p - base) - sk[q] + 1;
+    uint32_t u = d.esrc[e];
+    const uint32_t la = d.len[u];
+    if (o >= la) { u = d.edst[e]; o -= la; }
+    const bool in = o < d.len[u];
+    rec[i] = make_uint4(in ? u : PR_NONE, o, (uint32_t)q, in ? node_block[u] : 0u);
+}
+
+// Does the text of row r from offset o of its node u in block j on start with S[0 .. k)?  k >= 1, o < |label(u)|.
+// Every read is bounded: a label by its length, the row's cells by block nb, S by k.
+__device__ __forceinline__ bool pr_walk(const PrDev &d, uint64_t r, uint32_t u, uint32_t o, uint64_t j, const uint8_t *S, uint32_t k)
+{
+    uint32_t pos = 0;
+    uint64_t a = d.loff[u] + o, b = d.loff[u + 1];
+    for (;;) {
+        const uint64_t take = b - a < (uint64_t)(k - pos) ? b - a : (uint64_t)(k - pos);
+        for (uint64_t x = 0; x < take; x++)
+            if (d.labels[a + x] != S[pos + x]) return false;
+        pos += (uint32_t)take;
+        if (pos == k) return true;
+        uint32_t v;
+        do {
+            if (++j >= d.nb) return false;        // the row ends before the seed does
+            v = d.node_of[j * d.m + r];
+        } while (v == PR_NONE);
+        a = d.loff[v];
+        b = d.loff[v + 1];
+    }
+}
+
+// rec of one place and row r: is r in rows(place)?
+__device__ __forceinline__ bool pr_supports(const PrDev &d, const uint4 rc, uint64_t r)
+{
+    if (rc.x == PR_NONE || d.node_of[(uint64_t)rc.w * d.m + r] != rc.x) return false;
+    return pr_walk(d, r, rc.x, rc.y, rc.w, d.reads + d.sbase[rc.z], d.slen[rc.z]);
+}
+
+// the G bits of a wave-wide ballot that belong to the group whose first lane is sh
+template <int G> __device__ __forceinline__ uint64_t pr_group_bits(bool ok, unsigned sh)
+{
+    const uint64_t bal = __ballot(ok);
+    return G == FBG_WAVE ? bal : (bal >> sh) & ((1ull << (G % 64)) - 1);
+}
+
+// G lanes per start place, the lanes are rows, G at a time: one coalesced read of the block's stretch of node_of, the
+// lanes that hold the place's node walk, the ballot is the chunk of the set.  Every lane of the wave runs the row loop
+// (m is the same for all), so the ballots meet; places past the end and rows past m only vote no.
+template <int G>
+__global__ __launch_bounds__(PX_THREADS) void k_pr_rows(PrDev d, const uint4 *rec, uint64_t total, uint32_t *n_rows, uint32_t *first_row,
+                                                       unsigned long long *unsupported)
+{
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const unsigned lane = threadIdx.x % FBG_WAVE, gl = lane % G, sh = lane - gl;
+    const bool live = i < total;
+    const uint4 rc = live ? rec[i] : make_uint4(PR_NONE, 0, 0, 0);
+    uint32_t cnt = 0, first = PR_NONE;
+    for (uint64_t r0 = 0; r0 < d.m; r0 += G) {
+        const uint64_t r = r0 + gl;
+        const uint64_t bits = pr_group_bits<G>(r < d.m && pr_supports(d, rc, r), sh);
+        if (bits && first == PR_NONE) first = (uint32_t)r0 + (uint32_t)__ffsll((unsigned long long)bits) - 1;
+        cnt += __popcll(bits);
+    }
+    if (live && gl == 0) { n_rows[i] = cnt; first_row[i] = first; }
+    const uint64_t none = __ballot(live && gl == 0 && cnt == 0);
+    if (lane == 0 && none) atomicAdd(unsupported, (unsigned long long)__popcll(none));
+}
+
+// G lanes per read: a lane stays with its row while the row supports anchor after anchor of the read's chain (place:
+// the g of every chain entry, off: the n + 1 chain offsets) and drops out at the first that it does not; with a wave
+// per read the loop over the anchors ends as soon as no lane is left, that is, when the word of the set is zero.  What
+// is left after the last anchor is the chunk of the intersection.  bits (may be NULL): words 64-bit words per read; a
+// chunk is shifted into its word, which is stored when it is complete or the rows end, so rows past m stay zero.
+template <int G>
+__global__ __launch_bounds__(PX_THREADS) void k_pr_chain(PrDev d, const uint4 *rec, const uint32_t *place, const uint64_t *off, uint64_t n,
+                                                        uint64_t words, uint32_t *n_rows, uint32_t *first_row, uint64_t *bits_out,
+                                                        unsigned long long *unsupported)
+{
+    const uint64_t R = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const unsigned lane = threadIdx.x % FBG_WAVE, gl = lane % G, sh = lane - gl;
+    const bool live = R < n;
+    const uint64_t o0 = live ? off[R] : 0, len = live ? off[R + 1] - o0 : 0;
+    uint32_t cnt = 0, first = PR_NONE;
+    uint64_t word = 0;
+    for (uint64_t r0 = 0; r0 < d.m; r0 += G) {
+        const uint64_t r = r0 + gl;
+        bool ok = len != 0 && r < d.m;
+        for (uint64_t a = 0; a < len; a++) {
+            if (G == FBG_WAVE && !__any(ok)) break;      // one read per wave: len and this test are the same in every lane
+            if (ok) ok = pr_supports(d, rec[place[o0 + a]], r);
+        }
+        const uint64_t bits = pr_group_bits<G>(ok, sh);
+        if (bits && first == PR_NONE) first = (uint32_t)r0 + (uint32_t)__ffsll((unsigned long long)bits) - 1;
+        cnt += __popcll(bits);
+        word |= bits << (r0 % 64);
+        if ((r0 + G) % 64 == 0 || r0 + G >= d.m) {
+            if (bits_out && live && gl == 0) bits_out[R * words + r0 / 64] = word;
+            word = 0;
+        }
+    }
+    if (live && gl == 0) { n_rows[R] = cnt; first_row[R] = first; }
+    const uint64_t none = __ballot(live && gl == 0 && len != 0 && cnt == 0);
+    if (lane == 0 && none) atomicAdd(unsupported, (unsigned long long)__popcll(none));
+}
+
 // ---- C ABI ------------------------------------------------------------------------------------------------------
 extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
                                 const uint64_t *edge_off, const uint64_t *edge_dst, fbg_pindex **out)
@@ -1701,6 +1880,19 @@ extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint6
 }
 
 enum PxMode { PX_LOCATE, PX_OCC, PX_SEEDS };
+
+// pats / poff of the last seeds call into buffers of the row state, in stream order before whatever overwrites them
+static int pr_save_reads(fbg_pindex *ix)
+{
+    fbg_ctx *ctx = ix->ctx;
+    PrState &w = ix->rw;
+    FBG_TRY(fbg_reserve(ctx, w.reads, w.read_bytes + 8, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ctx, w.roff, (ix->sd_reads + 1) * 8, &ix->bufs, false));
+    if (w.read_bytes) FBG_HIP_TRY(ctx, hipMemcpyAsync(w.reads.p, ix->pats.p, w.read_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(w.roff.p, ix->poff.p, (ix->sd_reads + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    w.saved = true;
+    return FBG_OK;
+}
 
 // The per-pattern (or per-seed) buffers of a place state, for n of them.
 static int po_reserve(fbg_pindex *ix, PoState &s, uint64_t n)
@@ -1734,6 +1926,10 @@ static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     hipStream_t st = ctx->stream;
     const uint64_t n = comp ? 2 * n_patterns : n_patterns;     // reads on the device
     const uint64_t pbytes = comp ? 2 * total : total;
+    // an index with the row table: fbg_pindex_seeds_rows / _chains_rows read the reads of the last seeds call, which a
+    // locate or occurrences call is about to overwrite
+    if (mode == PX_SEEDS) { ix->rw.saved = false; ix->rw.read_bytes = pbytes; }
+    else if (ix->has_rows && ix->sd.ready && ix->sd_reads && !ix->rw.saved) FBG_TRY(pr_save_reads(ix));
     FBG_TRY(fbg_reserve(ix->ctx, ix->pats, ((pbytes + 7) & ~7ull) + 16, &ix->bufs, false));
     FBG_TRY(fbg_reserve(ix->ctx, ix->poff, (n + 1) * 8, &ix->bufs, false));
     for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(fbg_reserve(ix->ctx, *b, n * 4, &ix->bufs, false));
@@ -2378,6 +2574,148 @@ extern "C" int fbg_pindex_msa_stats(const fbg_pindex *ix, uint64_t *map_bytes, u
     return FBG_OK;
 }
 
+// ---- rows (fbg_pindex_seeds_rows / _chains_rows / _rows_stats) -------------------------------------------------------
+// What both calls start with, for S > 0 seeds and A > 0 start places of the last seeds call: sbase per seed and rec per
+// start place (k_pr_seed, k_pr_place), into buffers of the row state; d: what the row kernels read.
+static int pr_prepare(fbg_pindex *ix, PrDev &d)
+{
+    fbg_ctx *ctx = ix->ctx;
+    hipStream_t st = ctx->stream;
+    PrState &w = ix->rw;
+    const PoState &s = ix->sd;
+    const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
+    FBG_TRY(fbg_reserve(ctx, w.sbase, S * 8, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ctx, w.rec, A * 16, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ctx, w.ctr, 8, &ix->bufs, false));
+    if (!ix->ev0) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev0));
+    if (!ix->ev1) FBG_HIP_TRY(ctx, hipEventCreate(&ix->ev1));
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(w.ctr.p, 0, 8, st));
+    hipLaunchKernelGGL(k_pr_seed, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, (const uint64_t *)ix->soff.as<uint64_t>(),
+                       (const uint64_t *)(w.saved ? w.roff : ix->poff).as<uint64_t>(), (const uint32_t *)ix->sq.as<uint32_t>(), n, S,
+                       w.sbase.as<uint64_t>());
+    hipLaunchKernelGGL(k_pr_place, dim3(fbg_blocks(A, PX_THREADS)), dim3(PX_THREADS), 0, st, pv_dev(ix),
+                       (const uint32_t *)ix->snode_block.as<uint32_t>(), (const uint64_t *)s.soff.as<uint64_t>(), S, A,
+                       (const uint32_t *)s.ss.as<uint32_t>(), (const uint32_t *)s.sk.as<uint32_t>(), (const uint32_t *)s.rs.as<uint32_t>(),
+                       w.rec.as<uint4>());
+    d.node_of = w.node_of.as<uint32_t>();
+    d.labels = w.labels.as<uint8_t>();
+    d.loff = w.loff.as<uint64_t>();
+    d.reads = (w.saved ? w.reads : ix->pats).as<uint8_t>();
+    d.sbase = w.sbase.as<uint64_t>();
+    d.slen = ix->slen.as<uint32_t>();
+    d.m = w.m;
+    d.nb = ix->seg_nb;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_seeds_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PrState &w = ix->rw;
+    const PoState &s = ix->sd;
+    if (device_ms) *device_ms = 0;
+    if (!ix->has_rows)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds_rows: only an index built by fbg_pindex_build_segmentation_rows has the row table");
+    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds_rows: no fbg_pindex_seeds result to expand");
+    w.places_unsupported = 0;
+    const uint64_t A = s.stotal;
+    if (A == 0) return FBG_OK;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FBG_TRY(fbg_reserve(ctx, w.out, 2 * A * 4, &ix->bufs, false));
+    PrDev d;
+    FBG_TRY(pr_prepare(ix, d));
+    uint32_t *out = w.out.as<uint32_t>();
+    auto *ctr = w.ctr.as<unsigned long long>();
+    if (w.m <= PR_SUB && !ctx->opt.rows_wave)
+        hipLaunchKernelGGL(k_pr_rows<PR_SUB>, dim3(fbg_blocks(A * PR_SUB, PX_THREADS)), dim3(PX_THREADS), 0, st, d,
+                           (const uint4 *)w.rec.as<uint4>(), A, out, out + A, ctr);
+    else
+        hipLaunchKernelGGL(k_pr_rows<FBG_WAVE>, dim3(fbg_blocks(A * FBG_WAVE, PX_THREADS)), dim3(PX_THREADS), 0, st, d,
+                           (const uint4 *)w.rec.as<uint4>(), A, out, out + A, ctr);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    unsigned long long none = 0;
+    if (n_rows) FBG_HIP_TRY(ctx, hipMemcpyAsync(n_rows, out, A * 4, hipMemcpyDeviceToHost, st));
+    if (first_row) FBG_HIP_TRY(ctx, hipMemcpyAsync(first_row, out + A, A * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&none, ctr, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    w.places_unsupported = none;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_chains_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, uint64_t *row_bits, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PrState &w = ix->rw;
+    const PcState &c = ix->ch;
+    if (device_ms) *device_ms = 0;
+    if (!ix->has_rows)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_rows: only an index built by fbg_pindex_build_segmentation_rows has the row table");
+    if (!ix->sd.ready || !c.ready)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_rows: no fbg_pindex_chains result since the last seeds call");
+    w.chains_unsupported = 0;
+    const uint64_t n = c.n, words = (w.m + 63) / 64;
+    if (n == 0) return FBG_OK;
+    if (c.total == 0) {          // every chain is empty, and fbg_pindex_chains may have left nothing on the device
+        if (n_rows) std::fill(n_rows, n_rows + n, (uint32_t)0);
+        if (first_row) std::fill(first_row, first_row + n, (uint32_t)PR_NONE);
+        if (row_bits) std::fill(row_bits, row_bits + n * words, (uint64_t)0);
+        return FBG_OK;
+    }
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    FBG_TRY(fbg_reserve(ctx, w.cout, n * words * 8 + 2 * n * 4, &ix->bufs, false));
+    PrDev d;
+    FBG_TRY(pr_prepare(ix, d));
+    uint64_t *bits = w.cout.as<uint64_t>();
+    uint32_t *out = (uint32_t *)(bits + n * words);
+    auto *ctr = w.ctr.as<unsigned long long>();
+    const uint4 *rec = w.rec.as<uint4>();
+    const uint32_t *place = c.out.as<uint32_t>();
+    const uint64_t *off = c.off.as<uint64_t>();
+    if (w.m <= PR_SUB && !ctx->opt.rows_wave)
+        hipLaunchKernelGGL(k_pr_chain<PR_SUB>, dim3(fbg_blocks(n * PR_SUB, PX_THREADS)), dim3(PX_THREADS), 0, st, d, rec, place, off, n, words,
+                           out, out + n, row_bits ? bits : (uint64_t *)nullptr, ctr);
+    else
+        hipLaunchKernelGGL(k_pr_chain<FBG_WAVE>, dim3(fbg_blocks(n * FBG_WAVE, PX_THREADS)), dim3(PX_THREADS), 0, st, d, rec, place, off, n,
+                           words, out, out + n, row_bits ? bits : (uint64_t *)nullptr, ctr);
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    unsigned long long none = 0;
+    if (n_rows) FBG_HIP_TRY(ctx, hipMemcpyAsync(n_rows, out, n * 4, hipMemcpyDeviceToHost, st));
+    if (first_row) FBG_HIP_TRY(ctx, hipMemcpyAsync(first_row, out + n, n * 4, hipMemcpyDeviceToHost, st));
+    if (row_bits) FBG_HIP_TRY(ctx, hipMemcpyAsync(row_bits, bits, n * words * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&none, ctr, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    w.chains_unsupported = none;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_rows_stats(const fbg_pindex *ix, uint64_t *rows, uint64_t *table_bytes, uint64_t *words_per_set,
+                                     uint64_t *places_unsupported, uint64_t *chains_unsupported)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    if (!ix->has_rows)
+        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "fbg_pindex_rows_stats: only an index built by fbg_pindex_build_segmentation_rows has the row table");
+    const PrState &w = ix->rw;
+    if (rows) *rows = w.m;
+    if (table_bytes) *table_bytes = 4 * w.m * ix->seg_nb + w.label_bytes + 8 * (ix->n_nodes + 1);
+    if (words_per_set) *words_per_set = (w.m + 63) / 64;
+    if (places_unsupported) *places_unsupported = w.places_unsupported;
+    if (chains_unsupported) *chains_unsupported = w.chains_unsupported;
+    return FBG_OK;
+}
+
 extern "C" uint64_t fbg_pindex_text_length(const fbg_pindex *ix) { return ix ? ix->N1 : 0; }
 
 extern "C" int fbg_pindex_download(fbg_pindex *ix, uint8_t *text, uint32_t *sa, uint32_t *b_positions, uint32_t *e_positions,
@@ -2505,11 +2843,11 @@ extern "C" int fbg_pindex_validate_stats(const fbg_pindex *ix, uint64_t *slots_s
 extern "C" void fbg_pindex_destroy(fbg_pindex *ix) { px_destroy(ix); }
 
 // ---- an index straight from a segmentation; validation and repair of a segmentation ----------------------------------
-extern "C" int fbg_pindex_build_segmentation(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, fbg_pindex **out)
+static int px_new_from_segmentation(fbg_ctx *ctx, const char *who, const uint64_t *boundaries, uint64_t nb, bool with_rows, fbg_pindex **out)
 {
     if (!ctx) return FBG_ERR_INVALID;
-    if (!ctx->d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_build_segmentation: no MSA set");
-    if (!out || !boundaries || nb == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_build_segmentation: missing argument");
+    if (!ctx->d_msa) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no MSA set", who);
+    if (!out || !boundaries || nb == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing argument", who);
     *out = nullptr;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const auto t0 = std::chrono::steady_clock::now();
@@ -2518,12 +2856,23 @@ extern "C" int fbg_pindex_build_segmentation(fbg_ctx *ctx, const uint64_t *bound
     int rc;
     {
         PxScratch s;
-        rc = px_build_segmentation(ix, s, boundaries, nb, true);
+        rc = px_build_segmentation(ix, s, boundaries, nb, true, with_rows);
     }
     if (rc != FBG_OK) { px_destroy(ix); return rc; }
     ix->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = ix;
     return FBG_OK;
+}
+
+extern "C" int fbg_pindex_build_segmentation(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, fbg_pindex **out)
+{
+    return px_new_from_segmentation(ctx, "fbg_pindex_build_segmentation", boundaries, nb, false, out);
+}
+
+// ... with the row table of fbg_pindex_seeds_rows / _chains_rows
+extern "C" int fbg_pindex_build_segmentation_rows(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, fbg_pindex **out)
+{
+    return px_new_from_segmentation(ctx, "fbg_pindex_build_segmentation_rows", boundaries, nb, true, out);
 }
 
 extern "C" uint64_t fbg_pindex_node_count(const fbg_pindex *ix) { return ix ? ix->n_nodes : 0; }

@@ -96,6 +96,8 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *   no_stream_upload   1: fbg_elastic_f copies the whole MSA to the device before the index build starts, also from memory of
  *                      fbg_host_alloc (default: the rows go up in eight chunks while the text is written and pass 1 of the MSD sort
  *                      runs on the rows that are there; results unchanged)
+ *   rows_wave          1: fbg_pindex_seeds_rows / _chains_rows give every start place / chain a whole wave also when the MSA
+ *                      has at most 16 rows (default: 16 lanes each then); results unchanged (tests, measurements)
  *   rank_no_lean       1: the rank-order scan with k_rank_scan also where its lean form (k_rank_scan_lean: packed slots, threshold
  *                      above the key length) applies; results unchanged
  *   msd_ext            0: the three-pass MSD sort carries no symbols beyond the key (default 1: with 2-bit symbols its words
@@ -696,6 +698,65 @@ int fbg_pindex_seeds_strands(fbg_pindex *ix, const uint8_t *patterns, const uint
                              double *device_ms);
 int fbg_pindex_chain_strands(fbg_pindex *ix, uint8_t *strand, uint32_t *score, uint64_t *n_forward, uint64_t *n_reverse,
                              uint64_t *n_none, double *device_ms);
+
+/* Which MSA rows carry a start place, and which carry a whole chain (an index built by
+ * fbg_pindex_build_segmentation_rows only).
+ *
+ * A founder graph accepts recombinant paths: the search restarts at block-pair boundaries, so a seed that runs
+ * X1 -> Y1 -> Z2 is reported even when no input sequence ever read X1 Y1 Z2.  For an index built from a segmentation
+ * the rows of the MSA themselves say which places some input sequence carries.  Take the MSA A[m][n] and the
+ * boundaries the index was built from:
+ *   G_r            row r with its gap cells removed;
+ *   p(r, j)        the number of non-gap cells of row r before the first column of block j;
+ *   node_of[r][j]  the node of row r in block j, "none" for a row that is all gaps there (the node numbering of
+ *                  fbg_pindex_build_segmentation).
+ * A start place g = (a, b, offset) of seed t of (virtual) read R belongs to node u at o exactly as fbg_pindex_seeds_msa
+ * decides it (u = a, o = offset if offset < |label(a)|, else u = b, o = offset - |label(a)|) and has the read substring
+ * S = P_R[q_start[t] : q_start[t] + length[t]), for a reverse virtual read taken from rc(P_R).
+ *   row r supports g   iff o < |label(u)|, node_of[r][block(u)] == u, and G_r[x : x + |S|) == S with
+ *                      x = p(r, block(u)) + o; a row whose text ends before x + |S| does not support the place;
+ *   rows(g)            the set of supporting rows;
+ *   rows(chain of R)   the intersection of rows(g) over the chain's anchors, the empty set for an empty chain.
+ * A place with rows(g) empty is a match only the graph has: a recombinant.  This is a statement about rows and so about
+ * one path; it replaces neither the witness cell of fbg_pindex_seeds_msa (whose row need not support the place) nor the
+ * chain score, and no existing call changes its results.  Sets are reported per chain only, not per place.
+ *
+ *   fbg_pindex_build_segmentation_rows   fbg_pindex_build_segmentation plus the row table: text, SA, B, E, node tables,
+ *       MSA map, fbg_pindex_stats and fbg_pindex_msa_stats are those of the plain build, and so are the errors and limits
+ *       (at most FBG_MAX_ROWS rows, fewer than 2^32 (row, block) cells).  The table is a device copy of node_of (4 bytes
+ *       per (row, block) cell, block-major, so that 64 lanes read 64 consecutive rows) and of the gathered node labels
+ *       with their 64-bit offsets: a node whose rows are all gaps in both neighbouring blocks has no edge and hence no
+ *       copy of its label in the index text, yet a row's text runs through it.  The index keeps no pointer to the MSA and
+ *       no copy of it.  The plain build and the rounds of fbg_segmentation_validate / _repair build no such table.
+ *   fbg_pindex_rows_stats    any pointer may be NULL: m; the device bytes of the table; ceil(m / 64), the 64-bit words of
+ *       a set; the places with an empty set in the last fbg_pindex_seeds_rows; the non-empty chains with an empty set in
+ *       the last fbg_pindex_chains_rows (0 before the first such call; a call that fails its checks leaves them).
+ *   fbg_pindex_seeds_rows    entry g is for start place g of fbg_pindex_seeds_places: the same offsets (start_off of
+ *       fbg_pindex_seeds_fetch), order and cap.  n_rows[g] = |rows(g)|, first_row[g] = the smallest supporting row or
+ *       0xffffffff.  End places get nothing.  Either array may be NULL.
+ *   fbg_pindex_chains_rows   per read of the last seeds call (2n after fbg_pindex_seeds_strands): n_rows[R] = |rows(chain
+ *       of R)|, first_row[R] its smallest row or 0xffffffff, and, if row_bits is not NULL, words_per_set 64-bit words per
+ *       read: bit r % 64 of word r / 64 is set for each supporting row, bits at m and above are zero.  Any array may be
+ *       NULL.
+ * On the device: one lane per seed finds the byte its substring starts at, one lane per start place its node, offset,
+ * seed and block; then lanes are rows, 64 at a time (16 when the MSA has at most 16 rows): one read of the block's
+ * stretch of node_of, the lanes that hold the node compare S with label(u)[o:] and then with the labels of the row's
+ * nodes in the following blocks (cells without a node are passed over, block nb ends the row), and a ballot is the word
+ * of the set.  For a chain a lane stays with its row from anchor to anchor and the loop ends when the word is zero; no
+ * per-place set is kept in device memory.  Scratch owned by the index: 16 bytes per start place, 8 per seed, and what a
+ * call copies out.  *device_ms (may be NULL): device time of these kernels.
+ * A call may be repeated and leaves the seeds, their places and MSA coordinates, the chains, the occurrences,
+ * fbg_pindex_stats, validation results and the context alone.  The reads of the last seeds call stay readable: when
+ * fbg_pindex_locate or fbg_pindex_occurrences is about to overwrite them, an index with the row table first moves them
+ * into a buffer of its own.
+ * Errors, all FBG_ERR_INVALID: a NULL index; an index without the row table (the plain builder's included); no
+ * successful seeds call before fbg_pindex_seeds_rows; no successful fbg_pindex_chains since the last seeds call before
+ * fbg_pindex_chains_rows.  Nothing to report returns FBG_OK. */
+int fbg_pindex_build_segmentation_rows(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb, fbg_pindex **out);
+int fbg_pindex_rows_stats(const fbg_pindex *ix, uint64_t *rows, uint64_t *table_bytes, uint64_t *words_per_set,
+                          uint64_t *places_unsupported, uint64_t *chains_unsupported);
+int fbg_pindex_seeds_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, double *device_ms);
+int fbg_pindex_chains_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, uint64_t *row_bits, double *device_ms);
 
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
