@@ -216,6 +216,12 @@ static const OptKey g_opt_keys[] = {
     {"dp_chain1", &FbgOptions::dp_chain1},
     {"msd_ext", &FbgOptions::msd_ext},
     {"rows_wave", &FbgOptions::rows_wave},
+    {"pairs_in_scan", &FbgOptions::pairs_in_scan},
+    {"runs_wave_min", &FbgOptions::runs_wave_min},
+    {"wave_list_cap", &FbgOptions::wave_list_cap},
+    {"cand_local_sort", &FbgOptions::cand_local_sort},
+    {"cand_lds_cap", &FbgOptions::cand_lds_cap},
+    {"cand_sort_check", &FbgOptions::cand_sort_check},
 };
 
 // read-only keys of fbg_get_option: what the context and its last build report
@@ -228,6 +234,9 @@ static const InfoKey g_info_keys[] = {
     {"pass1_ahead", [](const fbg_ctx &c) -> int64_t { return c.diag.pass1_ahead; }},
     {"ext_pairs", [](const fbg_ctx &c) -> int64_t { return c.diag.ext_pairs; }},
     {"text_pairs", [](const fbg_ctx &c) -> int64_t { return c.diag.text_pairs; }},
+    {"cand_inversions", [](const fbg_ctx &c) -> int64_t { return c.diag.cand_inversions; }},
+    {"cand_local_sorted", [](const fbg_ctx &c) -> int64_t { return c.diag.cand_local_sorted; }},
+    {"wave_runs", [](const fbg_ctx &c) -> int64_t { return c.diag.wave_runs; }},
     {"rank_lean_used", [](const fbg_ctx &c) -> int64_t { return c.diag.rank_lean_used; }},
     {"rank_lean_launched", [](const fbg_ctx &c) -> int64_t { return c.diag.rank_lean_launched; }},
     {"pairs_rb", [](const fbg_ctx &c) -> int64_t { return c.diag.pairs_rb; }},

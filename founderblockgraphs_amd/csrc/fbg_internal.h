@@ -40,7 +40,9 @@ struct FbgOptions {
     int64_t no_ranked = 0, no_packed = 0, force_wide = 0, full_keys = 0, no_msd_sort = 0, msd_min = -1, bp_min = -1,
             record_scatter = 0, lcp_text = 0, no_aux_stream = 0, rank_no_threshold = 0, dp_literal = 0, dp_wave = 0,
             dp_safe_window = 0, dp_tile = 0, pure_scan = 0, gapped_rank = 0, part_tricks_off = 0, msd_sample_bins = 0, msd_min_force = 0, msd_probe = 0, msd_xcd = -1, rank_no_lean = 0, no_stream_upload = 0,
-            span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0, msd_ext = 1, rows_wave = 0;
+            span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0, msd_ext = 1, rows_wave = 0,
+            pairs_in_scan = 1, runs_wave_min = 16, wave_list_cap = 0,
+            cand_local_sort = 1, cand_lds_cap = 0, cand_sort_check = 0;
 };
 
 // The index at hand: per-position records, or the sorted slots plus per-column maxima of rank_scan.hip / pure_scan.hip
@@ -79,6 +81,9 @@ struct BuildDiag {
     int64_t msd_decline = -1;    // fbg_msd_sort: -1 not reached, 0 sorted; 1 not tried (geometry), 2 / 4 a stretch of pass 1, 8 the arena of pass 2, 16 a sub-bucket too large
     int pass1_ahead = 0;         // the MSD sort found its pass 1 done (streamed upload)
     int64_t ext_pairs = -1, text_pairs = -1;   // the rank-order scan: tied pairs settled by the msd_ext symbols / by the text
+    int64_t wave_runs = -1;      // the rank-order scan: runs that a wave each walked (k_runs_long)
+    int64_t cand_inversions = -1;  // option cand_sort_check: places of the sorted candidate list that do not ascend
+    int cand_local_sorted = -1;  // the candidates were sorted region by region in k_cand_sort_compact (1) / by the radix sort (0)
     int rank_lean_launched = 0;  // the rank-order scan launched k_rank_scan_lean ...
     int rank_lean_used = 0;      // ... and finished with it: the index holds its result
     int pairs_rb = -1;           // the sample sort of pairs: rank bits of its table, -1 it did not sort
@@ -178,6 +183,7 @@ struct fbg_ctx {
     // ---- scratch ----
     DevBuf keysA, keysB, valsA, valsB, grp, flags, list, tie_list, big_groups, tmp, small, scalars;
     DevBuf msd_ext;            // 1 byte per SA slot: symbols K .. K+3 of its suffix (msd_sort.hip, 2-bit symbols)
+    DevBuf wave_list;          // the runs that get a wave each (RankArgs::wl)
     DevBuf kargs;              // arguments a kernel reads from memory (k_rank_scan_lean) ...
     alignas(16) unsigned char kargs_host[512];   // ... and the host copy they are sent from
     DevBuf msd_w, msd_v;       // sub-bucket stretches of the MSD sort of 12-byte slots (msd_sort_pairs.hip)

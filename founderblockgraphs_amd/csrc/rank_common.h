@@ -46,8 +46,15 @@ struct RankArgs {
     uint32_t *pair_count;
     uint32_t *pm;              // scratch parallel to cand: prefix minima of the forward walk
     uint32_t *big;             // tie groups too long for one thread: (head slot, size) pairs, counters[5] of them
-    unsigned long long *counters;   // [1] fallback flag
+    unsigned long long *counters;   // [1] fallback flag, [7] runs noted in wl
+    // runs that get a wave instead of a thread (rank_scan.hip: k_runs_long; never with partitions).  wl: pairs (candidate index,
+    // head slot), counters[7] of them noted; a full list (wl_cap entries, RS_WAVE_LIST at most) sends the thread back to its own walk
+    uint32_t *wl;
+    uint32_t wl_cap;
+    uint32_t runs_wave_min;    // k_runs: a run of this many members and more goes to the list (0: none does)
+    int pairs_in_scan;         // k_rank_scan_lean settles the pairs whose code says where they part itself (pair_codes only)
 };
+#define RS_WAVE_LIST 1024
 
 struct Slot {
     uint64_t key;
@@ -269,6 +276,7 @@ static inline void rs_args_init(fbg_ctx *ctx, RankArgs &a, uint64_t *keys, uint3
     a.cand = nullptr; a.pm = nullptr; a.blk_count = nullptr; a.region = 0;
     a.ties = nullptr; a.tie_count = nullptr; a.tie_region = 0; a.pairs = nullptr; a.pair_count = nullptr; a.pair_codes = 0;
     a.pair_stats = nullptr;
+    a.wl = nullptr; a.wl_cap = 0; a.runs_wave_min = 0; a.pairs_in_scan = 0;
     a.big = ctx->big_groups.as<uint32_t>();
     a.counters = ctx->scalars.as<unsigned long long>() + 32;
     a.g_min = 0;

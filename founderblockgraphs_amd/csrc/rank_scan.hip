@@ -19,6 +19,8 @@
 //   k_runs          candidates, in final order: every maximal run of same-column neighbouring slots gets
 //                   g = 1 + max(min LCP towards the run head, min LCP towards the run tail) per member
 //                   (fbg.cpp:1644-1678) by one forward and one backward walk.
+//   k_runs_long     without partitions: runs of 16 members and more, noted by k_runs, get a wave each -- the row ends make
+//                   such runs, and a thread's walk through one is what the whole step would wait for.
 //   k_rank_finish   f[x] / v[j] from the column maxima (fbg.cpp:1656-1672 with rank_i(x) = x, tot_i = n).
 //
 // Keys use the compact coding of suffix_sort.hip: a separator ('#', sentinel) and everything behind it inside a
@@ -301,14 +303,33 @@ __device__ __forceinline__ uint32_t rl_lanes_below(unsigned long long m)      //
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// the noted pairs [0, n) of a wave's list (n <= 64): simple tied pairs, their two text positions, to the workgroup's region of a.pairs
-__device__ __attribute__((noinline)) void rl_noted(const RankArgs &a, const uint2 *list, uint32_t n, uint32_t *s_pair_n)
+// the noted pairs [0, n) of a wave's list (n <= 64): simple tied pairs, their two text positions.  A pair whose code says where
+// it parts (pairs_in_scan; 255 in 256) is settled here, as k_tie_pairs would: extension K + code + 1 into the maxima of its two
+// columns, no text read; the others go to the workgroup's region of a.pairs.
+__device__ __attribute__((noinline)) void rl_noted(const RankArgs &a, const uint2 *list, uint32_t n, uint32_t *s_pair_n, uint32_t *s_code_n)
 {
     const int lane = threadIdx.x & 63;
+    bool keep = (uint32_t)lane < n;
+    const uint2 p = keep ? list[lane] : make_uint2(0u, 0u);
+    if (a.pairs_in_scan) {
+        const uint32_t c = (p.x >> 30) | (((p.y >> 30) & 1u) << 2);
+        const bool coded = keep && c < 4;
+        if (coded) {
+            const uint32_t g = fbg_clamp_lcp((uint32_t)a.K + c) + 1;
+            rs_update(a, rs_col_of_rem(a, rs_rem<FBG_SLOTS_PACKED>(a, p.x & 0x3fffffffu)), g);
+            rs_update(a, rs_col_of_rem(a, rs_rem<FBG_SLOTS_PACKED>(a, p.y & 0x3fffffffu)), g);
+        }
+        keep = keep && !coded;
+        const unsigned long long cm = __ballot(coded);
+        if (lane == 0 && cm) atomicAdd(s_code_n, (uint32_t)__popcll(cm));
+    }
+    const unsigned long long mask = __ballot(keep);
+    if (!mask) return;
     uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(s_pair_n, n);
-    base = __shfl(base, 0, 64);
-    if ((uint32_t)lane < n && base + (uint32_t)lane < a.tie_region) a.pairs[(size_t)blockIdx.x * a.tie_region + base + lane] = list[lane];
+    const int leader = __ffsll((long long)mask) - 1;
+    if (lane == leader) base = atomicAdd(s_pair_n, (uint32_t)__popcll(mask));
+    base = __shfl(base, leader, 64) + rl_lanes_below(mask);
+    if (keep && base < a.tie_region) a.pairs[(size_t)blockIdx.x * a.tie_region + base] = p;
 }
 
 // the queued slots [0, n) of a wave's list (n <= 64): rank_scan_slow on the RS_HALO slots either side, from global memory
@@ -344,10 +365,10 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
     // together crowd out the masks)
     __shared__ uint2 s_note[RL_WAVES][RL_LIST];
     __shared__ uint32_t s_queue[RL_WAVES][RL_LIST];
-    __shared__ uint32_t s_cand_n, s_tie_n, s_pair_n;
+    __shared__ uint32_t s_cand_n, s_tie_n, s_pair_n, s_code_n;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // (told to be uniform: the loop below runs on scalar registers)
-    if (threadIdx.x == 0) { s_cand_n = 0; s_tie_n = 0; s_pair_n = 0; }
+    if (threadIdx.x == 0) { s_cand_n = 0; s_tie_n = 0; s_pair_n = 0; s_code_n = 0; }
     __syncthreads();
     uint2 *my_note = s_note[wv];
     uint32_t *my_queue = s_queue[wv];
@@ -427,12 +448,13 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
             }
         }
         while (nq >= 64) { rl_queued(*ap, my_queue, 64, &s_cand_n, &s_tie_n); rl_shift(my_queue, nq); }
-        if (nn >= 64) { rl_noted(*ap, my_note, 64, &s_pair_n); rl_shift(my_note, nn); }
+        if (nn >= 64) { rl_noted(*ap, my_note, 64, &s_pair_n, &s_code_n); rl_shift(my_note, nn); }
     }
-    if (nn) rl_noted(*ap, my_note, nn, &s_pair_n);
+    if (nn) rl_noted(*ap, my_note, nn, &s_pair_n, &s_code_n);
     if (nq) rl_queued(*ap, my_queue, nq, &s_cand_n, &s_tie_n);
     __syncthreads();
     if (threadIdx.x == 0) { ap->blk_count[blockIdx.x] = s_cand_n; ap->tie_count[blockIdx.x] = s_tie_n; ap->pair_count[blockIdx.x] = s_pair_n; }
+    if (threadIdx.x == 0 && s_code_n) atomicAdd(&ap->pair_stats[0], (unsigned long long)s_code_n);     // (k_tie_pairs counts the rest)
 }
 
 // Can fractions of the row length in single precision tell the columns apart?  x = fract((float)position * (float)(1 / row length)):
@@ -598,6 +620,45 @@ __global__ void k_cand_compact(const uint32_t *__restrict__ regions, const uint3
 {
     const uint32_t c = counts[blockIdx.x] < region ? counts[blockIdx.x] : region, o = offsets[blockIdx.x];
     for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) out[o + i] = regions[(size_t)blockIdx.x * region + i];
+}
+
+// The same after k_rank_scan_lean, where a workgroup owns one contiguous stretch of the slots and the stretches ascend with the
+// workgroups: what a region holds lies in its workgroup's stretch -- but for the tail of a pair whose head is the stretch's last
+// slot, the first slot of the next stretch, which its owner never lists (a row's lane 3 that ties with lane 2 and not with lane 4
+// is neither head of a pair, nor member of a longer group, nor "not tied": none of the masks Q is made of) -- so regions sorted
+// one by one and written out at their offsets are the sorted list: no device-wide sort.  Bitonic sort in LDS, counts up to
+// RS_CAND_LDS (the host knows the largest).
+#define RS_CAND_LDS 4096
+__global__ __launch_bounds__(256) void k_cand_sort_compact(const uint32_t *__restrict__ regions, const uint32_t *__restrict__ counts,
+                                                           const uint32_t *__restrict__ offsets, uint32_t region, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t buf[RS_CAND_LDS];
+    const uint32_t c = min(min(counts[blockIdx.x], region), (uint32_t)RS_CAND_LDS), o = offsets[blockIdx.x];
+    if (c == 0) return;
+    uint32_t P = 2;
+    while (P < c) P <<= 1;
+    for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) buf[i] = i < c ? regions[(size_t)blockIdx.x * region + i] : 0xffffffffu;
+    __syncthreads();
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint32_t x = buf[i], y = buf[l];
+                    if ((x > y) == ((i & k) == 0)) { buf[i] = y; buf[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) out[o + i] = buf[i];
+}
+
+// debugging aid (option cand_sort_check): places of the sorted candidate list that do not ascend
+__global__ void k_cand_inversions(const uint32_t *__restrict__ cand, uint64_t T, unsigned long long *__restrict__ count)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long mask = __ballot(t + 1 < T && cand[t] >= cand[t + 1]);
+    if ((threadIdx.x & 63) == 0 && mask) atomicAdd(count, (unsigned long long)__popcll(mask));
 }
 
 // a slot whose key equals its successor's but not its predecessor's heads a tie group: put the group in text
@@ -769,6 +830,10 @@ template <int L> __global__ void k_runs(RankArgs a, uint64_t T)
         if (s >= k0 && s < a.own_hi) a.pm[t + (s - k0)] = run;
         if (s + 1 >= hi_slot || rs_col<L>(a, s + 1) != col) break;
         s++;
+        if (a.runs_wave_min && s - ks + 1 == a.runs_wave_min) {        // a long run: a wave walks it (k_runs_long), unless the list is full
+            const unsigned long long e = atomicAdd(&a.counters[7], 1ull);
+            if (e < a.wl_cap) { a.wl[2 * e] = (uint32_t)t; a.wl[2 * e + 1] = (uint32_t)ks; return; }
+        }
         run = min(run, rs_slot_lcp<L>(a, s));
     }
     if (s + 1 == a.N && !a.last_part) { a.counters[1] = 1; return; }   // ran through the next halo
@@ -779,6 +844,52 @@ template <int L> __global__ void k_runs(RankArgs a, uint64_t T)
         if (s >= k0 && s < a.own_hi) rs_update(a, col, max(a.pm[t + (s - k0)], rmin) + 1);
         if (s == ks || s <= k0) break;                                 // members before k0 belong to the neighbour
     }
+}
+
+// The runs k_runs noted (runs_wave_min members and more; no partitions: the head is the candidate itself and every slot is
+// owned).  The last column of 1000 rows holds 250 suffixes "X#" per symbol, one run: 500 text comparisons one after the other
+// for a thread.  One wave per run, 64 members at a time, a lane each: the members' LCPs side by side, an inclusive minimum
+// scan across the wave with a carry from chunk to chunk -- forward into a.pm, then backward from the tail; the arithmetic is
+// k_runs' (fbg.cpp:1644-1678).  The members share their column: one update of its maximum.
+template <int L> __global__ __launch_bounds__(64) void k_runs_long(RankArgs a)
+{
+    if (blockIdx.x >= a.counters[7]) return;                            // (the grid is wl_cap blocks)
+    const uint64_t t = a.wl[2 * blockIdx.x], ks = a.wl[2 * blockIdx.x + 1];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t col = rs_col<L>(a, ks);
+    uint64_t len = 0;
+    uint32_t carry = 0xffffffffu;
+    for (uint64_t c0 = 0;; c0 += 64) {                                 // forward: minimum of LCP[head .. member]
+        const uint64_t s = ks + c0 + lane;
+        const unsigned long long out = ~__ballot(s < a.own_hi && rs_col<L>(a, s) == col);
+        const uint32_t cnt = out ? (uint32_t)__ffsll((long long)out) - 1 : 64u;       // members among these 64 slots
+        uint32_t v = lane < cnt ? rs_slot_lcp<L>(a, s) : 0xffffffffu;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(v, d, 64);
+            if (lane >= (uint32_t)d) v = min(v, o);
+        }
+        v = min(v, carry);
+        if (lane < cnt) a.pm[t + c0 + lane] = v;
+        carry = __shfl(v, 63, 64);
+        len += cnt;
+        if (cnt < 64) break;
+    }
+    uint32_t best = 0;
+    carry = 0xffffffffu;
+    for (uint64_t c0 = (len - 1) / 64 * 64;; c0 -= 64) {               // backward: minimum of LCP[member + 1 .. tail + 1], extension
+        const uint64_t i = c0 + lane;
+        uint32_t v = i < len ? rs_slot_lcp<L>(a, ks + i + 1) : 0xffffffffu;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_down(v, d, 64);
+            if (lane + (uint32_t)d < 64) v = min(v, o);
+        }
+        v = min(v, carry);
+        if (i < len) best = max(best, max(a.pm[t + i], v) + 1);        // (a.pm[t + i]: this lane's own store)
+        carry = __shfl(v, 0, 64);
+        if (c0 == 0) break;
+    }
+    for (int d = 32; d > 0; d >>= 1) best = max(best, (uint32_t)__shfl_xor(best, d, 64));
+    if (lane == 0) rs_update(a, col, best);
 }
 
 struct FinishArgs {
@@ -861,18 +972,38 @@ static int rs_join(fbg_ctx *ctx)
     return FBG_OK;
 }
 
-// The candidates, flat and unsorted in dp_e: sorted (SA order), tie groups put in final order.  On return a.cand / a.pm name
-// the sorted list and its scratch.
-static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T, int *launches)
+// the list of the runs that get a wave each (its count is counters[7], zeroed with the other counters); which runs go there
+static int rs_wave_list(fbg_ctx *ctx, RankArgs &a)
+{
+    FBG_TRY(fbg_reserve(ctx, ctx->wave_list, (size_t)2 * RS_WAVE_LIST * 4));
+    a.wl = ctx->wave_list.as<uint32_t>();
+    const int64_t cap = ctx->opt.wave_list_cap;
+    a.wl_cap = cap > 0 && cap < RS_WAVE_LIST ? (uint32_t)cap : RS_WAVE_LIST;
+    a.runs_wave_min = ctx->opt.runs_wave_min > 0 ? (uint32_t)ctx->opt.runs_wave_min : 0u;
+    return FBG_OK;
+}
+
+// The candidates, flat and unsorted in dp_e (or sorted in dp_a already: `sorted_already`): sorted (SA order), tie groups put in
+// final order.  On return a.cand / a.pm name the sorted list and its scratch.
+static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T, bool sorted_already, int *launches)
 {
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_b, T * 4));
     uint32_t *sorted = ctx->dp_a.as<uint32_t>();
     uint32_t *flat = ctx->dp_e.as<uint32_t>();
-    FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
-        return rocprim::radix_sort_keys(tmp, bytes, flat, sorted, (size_t)T, 0u, 32u, st);
-    }));
+    if (!sorted_already)
+        FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, flat, sorted, (size_t)T, 0u, 32u, st);
+        }));
+    if (ctx->opt.cand_sort_check) {
+        unsigned long long *d_inv = ctx->scalars.as<unsigned long long>() + 114, inv = 0;
+        FBG_HIP_TRY(ctx, hipMemsetAsync(d_inv, 0, sizeof(inv), st));
+        hipLaunchKernelGGL(k_cand_inversions, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, sorted, T, d_inv);
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(&inv, d_inv, sizeof(inv), hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        ctx->diag.cand_inversions = (int64_t)inv;
+    }
     a.cand = sorted;
     a.pm = ctx->dp_b.as<uint32_t>();
     RS_LAUNCH(k_tie_groups, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T, 1);
@@ -895,6 +1026,7 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
     FBG_TRY(fbg_reserve(ctx, ctx->tie_list, (size_t)rs_blocks * tie_region * 4));
     FBG_TRY(fbg_reserve(ctx, ctx->big_groups, RS_BIG_GROUPS * 8));
     a.big = ctx->big_groups.as<uint32_t>();
+    if (!a.part_mode) FBG_TRY(rs_wave_list(ctx, a));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_c, (size_t)(rs_blocks + 1) * 4));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_d, (size_t)(rs_blocks + 1) * 4));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_f, (size_t)(rs_blocks + 1) * 4));
@@ -909,6 +1041,7 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
     const bool lean = layout == FBG_SLOTS_PACKED && a.g_min > (uint32_t)a.K && !a.values_only && !a.part_mode && !ctx->opt.rank_no_lean &&
                       rs_lean_setup(a, a.pb, rs_blocks, &lf);
     ctx->diag.rank_lean_launched = lean ? 1 : 0;
+    if (ctx->opt.cand_sort_check) ctx->diag.cand_inversions = 0;
     if (lean)
     {
         // the symbols after the key from the MSD sort (these very slots, 2-bit symbols): the pairs carry a code in their spare
@@ -916,6 +1049,7 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
         if (ctx->ix.msd_ext_valid && a.keys == ctx->keysA.as<uint64_t>() && a.b == 2 && a.pb <= 30 && a.own_lo == 0 && a.own_hi == ctx->N) {
             lf.ext = ctx->msd_ext.as<uint8_t>();
             a.pair_codes = 1;
+            a.pairs_in_scan = ctx->opt.pairs_in_scan != 0;
         }
         a.pair_stats = ctx->scalars.as<unsigned long long>() + 112;
         FBG_HIP_TRY(ctx, hipMemsetAsync(a.pair_stats, 0, 2 * sizeof(unsigned long long), st));
@@ -959,11 +1093,20 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
         *T_out = T;
         if (mx > region) { *T_out = ~0ull; return rs_join(ctx); }
         if (T > 0) {
-            // regions are in SA order already (workgroup b owns chunks b, b+G, ...: not contiguous) -> compact, then sort
-            FBG_TRY(fbg_reserve(ctx, ctx->dp_e, T * 4));
-            uint32_t *flat = ctx->dp_e.as<uint32_t>();
-            hipLaunchKernelGGL(k_cand_compact, dim3(rs_blocks), dim3(256), 0, st, a.cand, d_counts, d_offs, region, flat);
-            FBG_TRY(rs_order_candidates(ctx, a, layout, T, launches));
+            // k_rank_scan: workgroup b owns chunks b, b+G, ...: not contiguous -> compact, then sort.  k_rank_scan_lean: one
+            // stretch per workgroup -> every region sorted in LDS on its way out, where the largest fits
+            const int64_t cap_opt = ctx->opt.cand_lds_cap;
+            const uint32_t lds_cap = cap_opt > 0 && cap_opt < RS_CAND_LDS ? (uint32_t)cap_opt : RS_CAND_LDS;
+            const bool local = lean && ctx->opt.cand_local_sort && mx <= lds_cap;
+            ctx->diag.cand_local_sorted = local ? 1 : 0;
+            if (local) {
+                FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
+                hipLaunchKernelGGL(k_cand_sort_compact, dim3(rs_blocks), dim3(256), 0, st, a.cand, d_counts, d_offs, region, ctx->dp_a.as<uint32_t>());
+            } else {
+                FBG_TRY(fbg_reserve(ctx, ctx->dp_e, T * 4));
+                hipLaunchKernelGGL(k_cand_compact, dim3(rs_blocks), dim3(256), 0, st, a.cand, d_counts, d_offs, region, ctx->dp_e.as<uint32_t>());
+            }
+            FBG_TRY(rs_order_candidates(ctx, a, layout, T, local, launches));
         }
         return FBG_OK;
     }();
@@ -1032,9 +1175,10 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     if (T > 0) {
         RS_LAUNCH(k_runs, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T);
         launches++;
+        if (a.runs_wave_min) { RS_LAUNCH(k_runs_long, layout, dim3(a.wl_cap), dim3(64), st, a); launches++; }
     }
     FBG_TRY(rs_join(ctx));
-    unsigned long long h[5], ps[2] = {0, 0};
+    unsigned long long h[8], ps[2] = {0, 0};                           // h[7]: the runs k_runs noted for k_runs_long
     // a large tie group / an overflowing tie region -> record path; a column without a value lost all its rows
     // to the threshold -> redo without it
     if (a.g_min > 1)
@@ -1044,6 +1188,7 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     ctx->diag.ext_pairs = (int64_t)ps[0];
     ctx->diag.text_pairs = (int64_t)ps[1];
+    ctx->diag.wave_runs = (int64_t)std::min(h[7], (unsigned long long)a.wl_cap);
     launches++;
     if (h[1] != 0) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
     if (a.g_min > 1 && h[4] != 0) {

@@ -119,6 +119,18 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *                      closed form for the older ones (k_dpw_blockY / k_dpw_chain2); results unchanged
  *   dp_chain1          1: the walk over the groups of byte matrices on one wave (k_dp_chain, rounds 1-3) instead of six
  *                      (k_dp_chain6); results unchanged
+ *   pairs_in_scan      0: the lean rank-order scan hands every simple tied pair to k_tie_pairs (default 1: a pair whose msd_ext
+ *                      code says where it parts, 255 in 256, is settled inside the scan kernel; k_tie_pairs takes the rest);
+ *                      results, "ext_pairs" and "text_pairs" unchanged
+ *   runs_wave_min      the rank-order scan without partitions: a run of same-column slots with this many members and more is
+ *                      walked by a wave (k_runs_long) instead of its head's thread (default 16; 0: none is); results unchanged
+ *   wave_list_cap      entries the list of such runs holds (0 = 1024, the most); a run that finds the list full stays with
+ *                      its thread (tests)
+ *   cand_local_sort    0: the candidate list of the rank-order scan always goes through the device-wide radix sort (default 1:
+ *                      after the lean scan every workgroup's region is sorted in LDS on its way into the list, where the
+ *                      largest region fits); results unchanged
+ *   cand_lds_cap       the largest region count that sort takes (0 = 4096, the most; tests)
+ *   cand_sort_check    1: the sorted candidate list is checked to ascend ("cand_inversions"; debugging, one more wait)
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
  * fbg_get_option also answers "index_kind" (read-only): -1 no index, 0 per-position records, 1 rank-order scan of a
@@ -141,6 +153,11 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  * "ext_pairs", "text_pairs" (read-only): the tied pairs the lean rank-order scan of the last index build settled from the
  * MSD sort's symbols after the key (msd_ext) / by comparing the text; -1 when no rank-order scan ran, both 0 when it ran
  * without its lean form.
+ * "cand_inversions" (read-only): with cand_sort_check, the places of the last scan's sorted candidate list whose successor
+ * is not larger (0 also when the scan had no list to sort); -1 without the option.  "cand_local_sorted" (read-only): 1 when
+ * that list was sorted region by region, 0 by the radix sort, -1 when no list was sorted.
+ * "wave_runs" (read-only): the runs of the last rank-order scan that a wave each walked; -1 when no rank-order scan
+ * finished.
  * "rank_lean_launched" (read-only): 1 when the last rank-order scan launched its lean form (k_rank_scan_lean), whether or
  * not the scan then finished; "rank_lean_used" (read-only): 1 when it also finished, so that the index holds that kernel's
  * column maxima (0 when the scan handed over to the group-level scan or the record path).
