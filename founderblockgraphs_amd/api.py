@@ -572,7 +572,15 @@ class PatternIndex:
             out.chains = self.chains(band=band, min_score=min_score, rows=rows)
         return out
 
-    def chains(self, band=None, min_score=0, rows=False):
+    def align_stats(self):
+        """{aligned, unsupported, too_long, too_wide, cells, max_read, table_bytes} of the last chains(align=True)
+        (fbg_pindex_align_stats; an index built with rows=True only): cells is the sum of read length times window length
+        over the aligned reads, max_read the longest read that is aligned, table_bytes the prefix table's."""
+        v = [C.c_uint64(0) for _ in range(7)]
+        self._eng._chk(self._L.fbg_pindex_align_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("aligned", "unsupported", "too_long", "too_wide", "cells", "max_read", "table_bytes"), (x.value for x in v)))
+
+    def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -580,11 +588,16 @@ class PatternIndex:
         seeds(strands=True) the chains cover the 2k virtual reads and the strand of every given read is picked from
         their scores on the device (fbg_pindex_chain_strands).  rows=True (an index built with rows=True only): also
         the MSA rows that carry every anchor of a read's chain (fbg_pindex_chains_rows), as Chains.n_rows, .first_row
-        and .row_set(k)."""
+        and .row_set(k).  align=True (an index built with rows=True only): also the edit distance of every read to the
+        smallest row that carries its chain, in a window of that row's text pad symbols around the chain's diagonals
+        (fbg_pindex_chains_align), as Chains.align_row, .edits, .t_start and .t_end; a read whose window is longer than
+        max_window (0: no limit) is skipped.  After seeds(strands=True) also Chains.best_edits."""
         if band is not None and band < 0:
             raise ValueError("band must be 0 or more, or None")
         if min_score < 0:
             raise ValueError("min_score must be 0 or more")
+        if pad < 0 or max_window < 0:
+            raise ValueError("pad and max_window must be 0 or more")
         k = getattr(self, "_seed_reads", 0)
         chain_off = np.zeros(k + 1, dtype=np.uint64)
         score = np.zeros(max(k, 1), dtype=np.uint32)
@@ -616,6 +629,17 @@ class PatternIndex:
                                                           _u64(bits), C.byref(ms4)))
             out.n_rows, out.first_row, out.rows_ms = nr[:k], fr[:k], ms4.value
             out.row_bits = bits[:k * words].reshape(k, words)
+        if align:
+            arr = [np.zeros(max(k, 1), dtype=np.uint32) for _ in range(4)]
+            ms5 = C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chains_align(self._h, min(int(pad), 0xffffffffffffffff), min(int(max_window), 0xffffffffffffffff),
+                                                           *[a.ctypes.data_as(_lib.u32p) for a in arr], C.byref(ms5)))
+            out.align_row, out.edits, out.t_start, out.t_end = (a[:k] for a in arr)
+            out.align_ms = ms5.value
+            if given is not None:
+                pick = np.where(out.strand[:given] == 1, given, 0) + np.arange(given)
+                out.best_edits = np.where(out.strand[:given] == _lib.STRAND_NONE, np.uint32(_lib.ALIGN_NONE),
+                                          out.edits[pick] if given else out.edits[:0]).astype(np.uint32)
         return out
 
     def chain_stats(self):
@@ -803,6 +827,15 @@ class Chains:
       n_rows, first_row   uint32 per read: how many MSA rows carry every anchor of its chain, and the smallest of them
                       (0 and 0xffffffff for an empty chain, and for one whose anchors no single row carries)
       row_bits        uint64[k, words_per_set]: bit r % 64 of word r // 64 is set for each such row r; row_set(k) lists them
+    and, asked for with align=True (None otherwise; include/fbg_hip.h, fbg_pindex_chains_align):
+      align_row       uint32 per read: the smallest row that carries its chain, 0xffffffff (_lib.ALIGN_NONE) if none does
+      edits           uint32 per read: the fewest edits that turn the read into a stretch of that row's gap-stripped text
+                      around the chain; 0xffffffff without a row, and for a read skipped as too long or too wide
+      t_start, t_end  uint32 per read: that stretch [t_start, t_end) of the row's text (the smallest end, then the largest
+                      start); 0xffffffff where edits is
+      best_edits      after seeds(strands=True): uint32 per given read, the edits of the strand that strand picked,
+                      0xffffffff where strand is 0xff
+      align_ms        device time of fbg_pindex_chains_align: the row choice, the windows and the two passes
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -811,6 +844,7 @@ class Chains:
         self.device_ms, self.fetch_ms = device_ms, fetch_ms
         self.strand = self.best_score = self.strand_counts = None
         self.n_rows = self.first_row = self.row_bits = None
+        self.align_row = self.edits = self.t_start = self.t_end = self.best_edits = self.align_ms = None
 
     def row_set(self, k):
         """int64[n_rows[k]]: the rows that carry the whole chain of read k, ascending."""

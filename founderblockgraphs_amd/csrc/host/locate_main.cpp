@@ -3,7 +3,7 @@
 // place of its .index file:
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
-//              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]
+//              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--align[=PAD]]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -44,6 +44,12 @@
 // `<tab> rows <tab> first` to every B line of a seed and to every C line: how many MSA rows carry the seed from that place
 // on, or every anchor of the chain, and the smallest of them, from 0 (fbg_pindex_seeds_rows / _chains_rows; `*` for first
 // when there is none: a place or chain that only a recombinant path of the graph spells).  Without --rows no line changes.
+// --align[=PAD] (with --chain and --rows) aligns every pattern against the smallest row that carries its chain, in a window
+// of that row's gap-stripped text PAD symbols (default 16) around the chain's diagonals (fbg_pindex_chains_align), and
+// prints after the A lines of a chain
+//   G <tab> row <tab> edits <tab> t_start <tab> t_end   the fewest edits, and the stretch [t_start, t_end) of the row's text
+// or `G <tab> *` when there is no alignment (no chain, no row that carries it, a pattern longer than the engine aligns).
+// Without --align no line changes.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -62,6 +68,7 @@ static int usage(const char *msg)
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
+              << "                  [--align[=PAD]]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -83,7 +90,11 @@ static int usage(const char *msg)
               << "  --rows             needs --seeds and --msa: every B line of a seed and every C line ends with the number\n"
               << "                     of MSA rows that carry the seed from that place on (the C line: every anchor of the\n"
               << "                     chain) and the smallest such row, from 0 (* if no row does: only a recombinant path\n"
-              << "                     of the graph spells it); no other line changes\n";
+              << "                     of the graph spells it); no other line changes\n"
+              << "  --align[=PAD]      needs --chain and --rows: after the A lines of a chain a G line: the smallest row that\n"
+              << "                     carries the chain, the fewest edits between the pattern and a stretch of that row's\n"
+              << "                     gap-stripped text within PAD symbols (default 16) of the chain, and that stretch's start\n"
+              << "                     and end in the row's text, from 0 (G and * if there is no alignment)\n";
     return EXIT_FAILURE;
 }
 
@@ -158,7 +169,8 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement;
-    bool have_msa = false, have_complement = false, strands = false, rows = false;
+    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false;
+    uint64_t pad = 16;
     bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
     uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
     for (int i = 1; i < argc; i++) {
@@ -210,6 +222,18 @@ int main(int argc, char **argv)
             band = m;
             continue;
         }
+        if (a == "--align") { align = true; continue; }
+        if (a.compare(0, 8, "--align=") == 0) {
+            const std::string v = a.substr(8);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
+                return usage(("--align takes a pad, not '" + v + "'").c_str());
+            align = true;
+            pad = m;
+            continue;
+        }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
         return usage(("unknown argument " + a).c_str());
     }
@@ -219,6 +243,7 @@ int main(int argc, char **argv)
         return usage("--chain needs --seeds, --msa and --occurrences[=M] with M > 0");
     if (strands && !seeds) return usage("--strands needs --seeds");
     if (rows && !(seeds && have_msa)) return usage("--rows needs --seeds and --msa");
+    if (align && !(chain && rows)) return usage("--align needs --chain and --rows");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
 
@@ -312,6 +337,7 @@ int main(int argc, char **argv)
     std::vector<uint32_t> chain_score(nv + 1, 0), anchor_place, anchor_seed, best_score(np + 1, 0);
     std::vector<uint8_t> strand(np + 1, 0);
     std::vector<uint32_t> place_rows[2], chain_rows[2];     // --rows: supporting rows and the first of them
+    std::vector<uint32_t> aligned[4];                       // --align: row, edits, t_start, t_end
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -354,6 +380,10 @@ int main(int argc, char **argv)
             for (int k = 0; k < 2; k++) chain_rows[k].resize(nv + 1);
             rc = fbg_pindex_chains_rows(ix, chain_rows[0].data(), chain_rows[1].data(), nullptr, nullptr);
         }
+        if (rc == FBG_OK && align) {
+            for (int k = 0; k < 4; k++) aligned[k].resize(nv + 1);
+            rc = fbg_pindex_chains_align(ix, pad, 0, aligned[0].data(), aligned[1].data(), aligned[2].data(), aligned[3].data(), nullptr);
+        }
     }
     if (rc == FBG_OK && !occurrences && !seeds)
         rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
@@ -394,6 +424,9 @@ int main(int argc, char **argv)
                 for (uint64_t i = chain_off[v]; i < chain_off[v + 1]; i++)
                     std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]
                               << '\t' << coords[3][anchor_place[i]] << '\n';
+                if (align && aligned[1][v] == FBG_ALIGN_NONE) std::cout << "G\t*\n";
+                else if (align)
+                    std::cout << "G\t" << aligned[0][v] << '\t' << aligned[1][v] << '\t' << aligned[2][v] << '\t' << aligned[3][v] << '\n';
             }
         };
         for (uint64_t k = 0; k < np; k++) {

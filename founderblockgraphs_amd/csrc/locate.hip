@@ -73,6 +73,9 @@
 #define PC_NONE 0xffffffffu   // no predecessor / no chain end
 #define PR_SUB 16             // rows: lanes that share a place (or a chain) when the MSA has at most this many rows
 #define PR_NONE 0xffffffffu   // no node in a (row, block) cell (BG_NONE of block_graph.hip); no supporting row
+#define PA_MAX_READ 1024      // alignment: the longest read fbg_pindex_chains_align takes (max_read), a multiple of 64
+#define PA_REG_WORDS 4        // reads of up to this many 64-symbol words keep the bit-vector state in registers
+#define PA_NONE 0xffffffffu   // FBG_ALIGN_NONE
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
@@ -105,6 +108,17 @@ struct PrState {
     DevBuf node_of, labels, loff, reads, roff, sbase, rec, out, cout, ctr;
     bool saved = false;
     uint64_t m = 0, label_bytes = 0, read_bytes = 0, places_unsupported = 0, chains_unsupported = 0;
+};
+
+// fbg_pindex_chains_align.  pref: p(r, j) as uint32[nb * m], block-major like node_of, built by the first call.  Per read
+// of the last seeds call: nrows / first (what k_pr_chain leaves: the row choice), info = (row, w0, |W| or 0 where nothing
+// is aligned, L), start = (block, node, offset in the node) at which w0 falls, wlen and its scan woff (n + 1 each), out
+// (row, edits, t_start, t_end: 4 n); win: the windows, back to back; ctr: non-empty chains without a row, reads aligned,
+// too long, too wide, and the cells.
+struct PaState {
+    DevBuf pref, nrows, info, start, wlen, woff, win, out, ctr;
+    bool has_pref = false;
+    uint64_t stat[5] = {0, 0, 0, 0, 0};
 };
 
 struct fbg_pindex {
@@ -149,6 +163,7 @@ struct fbg_pindex {
     PcState ch;
     bool has_rows = false;        // built by fbg_pindex_build_segmentation_rows
     PrState rw;
+    PaState al;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -1859,6 +1874,252 @@ __global__ __launch_bounds__(PX_THREADS) void k_pr_chain(PrDev d, const uint4 *r
     if (lane == 0 && none) atomicAdd(unsupported, (unsigned long long)__popcll(none));
 }
 
+// ---- alignment (fbg_pindex_chains_align) ----------------------------------------------------------------------------
+// The text of row r is the labels of its nodes in block order, so a position x of G_r lies in the last block j with
+// p(r, j) <= x (a block without a node of the row has p(r, j) == p(r, j + 1) and is never that last one while x < |G_r|).
+struct PaDev {
+    const uint32_t *node_of, *pref;   // [nb * m] each, block-major
+    const uint8_t *labels;
+    const uint64_t *loff;
+    const uint8_t *reads;
+    const uint64_t *roff;             // [n + 1] byte offsets of the (virtual) reads
+    uint64_t m, nb;
+};
+
+// pref[j * m + r] = p(r, j): one lane per row steps over the blocks, so a wave reads and writes 64 consecutive rows
+__global__ void k_pa_prefix(const uint32_t *node_of, const uint64_t *loff, uint64_t m, uint64_t nb, uint32_t *pref)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= m) return;
+    uint32_t run = 0;
+    for (uint64_t j = 0; j < nb; j++) {
+        pref[j * m + r] = run;
+        const uint32_t v = node_of[j * m + r];
+        if (v != PR_NONE) run += (uint32_t)(loff[v + 1] - loff[v]);
+    }
+}
+
+// One lane per read, after k_pr_chain chose the row (first_row; rec, place, off as there; q: q_start per seed): the
+// diagonals of the chain's anchors on that row, the window, the skip status and the block, node and offset at which
+// the window starts (a search of the row's column of pref).  Writes row and, where nothing is aligned, PA_NONE into
+// the three other outputs (out: 4 n); wlen[R] = |W| of an aligned read, else 0, wlen[n] = 0.  ctr[1 .. 4]: reads
+// aligned, too long, too wide, and the cells, summed per wave before the atomic.
+__global__ void k_pa_prepare(PaDev d, const uint4 *rec, const uint32_t *place, const uint64_t *off, const uint32_t *q,
+                             const uint32_t *first_row, uint64_t n, uint64_t pad, uint64_t max_window, uint4 *info, uint4 *start,
+                             uint64_t *wlen, uint32_t *out, unsigned long long *ctr)
+{
+    const uint64_t R = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int kind = -1;                // 0 aligned, 1 too long, 2 too wide
+    unsigned long long cells = 0;
+    if (R == n) wlen[n] = 0;
+    if (R < n) {
+        const uint64_t o0 = off[R], len = off[R + 1] - o0, L = d.roff[R + 1] - d.roff[R];
+        const uint32_t r = len ? first_row[R] : PR_NONE;
+        uint4 in = make_uint4(r, 0, 0, (uint32_t)L), at = make_uint4(0, 0, 0, 0);
+        if (r != PR_NONE) {
+            long long dmin = 0, dmax = 0;
+            for (uint64_t a = 0; a < len; a++) {
+                const uint4 rc = rec[place[o0 + a]];
+                const long long dg = (long long)d.pref[(uint64_t)rc.w * d.m + r] + rc.y - (long long)q[rc.z];
+                if (a == 0 || dg < dmin) dmin = dg;
+                if (a == 0 || dg > dmax) dmax = dg;
+            }
+            const uint64_t jl = (d.nb - 1) * d.m + r;
+            const uint32_t vl = d.node_of[jl];
+            const long long glen = (long long)d.pref[jl] + (vl != PR_NONE ? (long long)(d.loff[vl + 1] - d.loff[vl]) : 0);
+            const long long lo = dmin - (long long)pad, hi = dmax + (long long)L + (long long)pad;
+            const uint64_t w0 = lo > 0 ? (uint64_t)lo : 0, w1 = hi < glen ? (uint64_t)hi : (uint64_t)glen;
+            kind = L > PA_MAX_READ ? 1 : max_window && w1 - w0 > max_window ? 2 : 0;
+            if (kind == 0) {
+                uint64_t a = 0, b = d.nb - 1;
+                while (a < b) {
+                    const uint64_t mid = a + (b - a + 1) / 2;
+                    if (d.pref[mid * d.m + r] <= w0) a = mid; else b = mid - 1;
+                }
+                in.y = (uint32_t)w0;
+                in.z = (uint32_t)(w1 - w0);
+                at = make_uint4((uint32_t)a, d.node_of[a * d.m + r], (uint32_t)w0 - d.pref[a * d.m + r], 0);
+                cells = (unsigned long long)L * (w1 - w0);
+            }
+        }
+        info[R] = in;
+        start[R] = at;
+        wlen[R] = in.z;
+        out[R] = r;
+        if (kind != 0) out[n + R] = out[2 * n + R] = out[3 * n + R] = PA_NONE;
+    }
+    for (int off2 = FBG_WAVE / 2; off2 > 0; off2 >>= 1) cells += __shfl_xor(cells, off2);
+    const bool first = (threadIdx.x & (FBG_WAVE - 1)) == 0;
+    for (int b = 0; b < 3; b++) {
+        const unsigned long long mk = __ballot(kind == b);
+        if (mk && first) atomicAdd(&ctr[1 + b], (unsigned long long)__popcll(mk));
+    }
+    if (cells && first) atomicAdd(&ctr[4], cells);
+}
+
+// A wave per read writes its window W = G_r[w0 : w1) to win + woff[R]: label after label of the row's nodes from the
+// start node on, the lanes taking consecutive bytes of a label; cells without a node are passed over.  Every loop is
+// bounded: a label by its length, the window by |W|, the row's cells by block nb.
+__global__ __launch_bounds__(FBG_WAVE) void k_pa_gather(PaDev d, const uint4 *info, const uint4 *start, const uint64_t *woff, uint8_t *win)
+{
+    const uint64_t R = blockIdx.x;
+    const unsigned lane = threadIdx.x;
+    const uint4 in = info[R];
+    const uint32_t wl = in.z;
+    if (wl == 0) return;
+    const uint4 at = start[R];
+    if (at.y == PR_NONE) return;
+    uint8_t *dst = win + woff[R];
+    uint64_t j = at.x, a = d.loff[at.y] + at.z, b = d.loff[at.y + 1];
+    uint32_t done = 0;
+    for (;;) {
+        const uint32_t take = b - a < (uint64_t)(wl - done) ? (uint32_t)(b - a) : wl - done;
+        for (uint32_t x = lane; x < take; x += FBG_WAVE) dst[done + x] = d.labels[a + x];
+        done += take;
+        if (done == wl) return;
+        uint32_t v;
+        do {
+            if (++j >= d.nb) return;
+            v = d.node_of[j * d.m + in.x];
+        } while (v == PR_NONE);
+        a = d.loff[v];
+        b = d.loff[v + 1];
+    }
+}
+
+// One column of Myers' bit-vector recurrence for a word of 64 read symbols (Hyyro's block form).  eq: the rows of the
+// word whose read symbol equals the column's text symbol; pv / mv: the rows whose vertical difference D(i, j) -
+// D(i - 1, j) is +1 / -1; hin: the horizontal difference D(i0, j) - D(i0, j - 1) of the row below the word's first;
+// -> the horizontal difference of the row whose bit is top.  Bits above top never reach the bits below it.
+__device__ __forceinline__ int pa_step(uint64_t eq, uint64_t &pv, uint64_t &mv, int hin, uint64_t top)
+{
+    const uint64_t neg = hin < 0 ? 1 : 0;
+    const uint64_t xv = eq | mv;
+    eq |= neg;
+    const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
+    uint64_t ph = mv | ~(xh | pv), mh = pv & xh;
+    const int hout = (ph & top) ? 1 : (mh & top) ? -1 : 0;
+    ph = (ph << 1) | (hin > 0 ? 1 : 0);
+    mh = (mh << 1) | neg;
+    pv = mh | ~(xv | ph);
+    mv = ph & xv;
+    return hout;
+}
+
+// 64 text symbols of a pass per load, lane t takes column j0 + t; REV: the text backwards
+template <bool REV> __device__ __forceinline__ int pa_chunk(const uint8_t *W, uint32_t wl, uint32_t j0, unsigned lane)
+{
+    const uint32_t j = j0 + lane;
+    return j < wl ? (int)W[REV ? wl - 1 - j : j] : 0;
+}
+
+// One pass of a wave over the text W[0 .. wl) with a read of exactly NW words, the state in registers: lane i holds
+// read symbols i, 64 + i, ...  (256: no symbol, equal to no byte, which masks the last word to L % 64 bits), a text byte
+// is made wave-uniform by readlane and its match word is one ballot per read word.  D(L, j) is followed at bit L - 1 of
+// the last word; -> best = min_j D(L, j) and bestj, the smallest j that attains it (D(L, 0) = L).  REV: the read and the
+// text backwards and D(0, j) = j, which is the carry-in 1 of the first word.
+template <int NW, bool REV>
+__device__ __forceinline__ void pa_pass_reg(const uint8_t *P, uint32_t L, const uint8_t *W, uint32_t wl, unsigned lane, uint32_t &best,
+                                            uint32_t &bestj)
+{
+    int p[NW];
+    uint64_t pv[NW], mv[NW];
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+        const uint32_t i = w * 64 + lane;
+        p[w] = i < L ? (int)P[REV ? L - 1 - i : i] : 256;
+        pv[w] = ~0ull;
+        mv[w] = 0;
+    }
+    const uint64_t top = 1ull << ((L - 1) & 63);
+    uint32_t score = L;
+    best = L;
+    bestj = 0;
+    for (uint32_t j0 = 0; j0 < wl; j0 += 64) {
+        const int chunk = pa_chunk<REV>(W, wl, j0, lane);
+        const uint32_t cnt = wl - j0 < 64 ? wl - j0 : 64;
+        for (uint32_t t = 0; t < cnt; t++) {
+            const int c = __builtin_amdgcn_readlane(chunk, t);
+            int h = REV ? 1 : 0;
+#pragma unroll
+            for (int w = 0; w < NW; w++) h = pa_step(__ballot(p[w] == c), pv[w], mv[w], h, w == NW - 1 ? top : 1ull << 63);
+            score += h;
+            if (score < best) { best = score; bestj = j0 + t + 1; }
+        }
+    }
+}
+
+// The same pass for a read of nw > PA_REG_WORDS words: the read (rd) and the state (st: pv, then mv) in LDS and a loop
+// over the words.  Every lane computes and stores the same state and reads back what it stored itself, and a lane reads
+// the read symbols it staged itself: no lane waits for another, so there is no barrier.
+template <bool REV>
+__device__ __forceinline__ void pa_pass_lds(const uint8_t *P, uint32_t L, uint32_t nw, const uint8_t *W, uint32_t wl, unsigned lane,
+                                            uint8_t *rd, uint64_t *st, uint32_t &best, uint32_t &bestj)
+{
+    for (uint32_t w = 0; w < nw; w++) {
+        const uint32_t i = w * 64 + lane;
+        rd[i] = i < L ? P[REV ? L - 1 - i : i] : 0;
+        st[w] = ~0ull;
+        st[PA_MAX_READ / 64 + w] = 0;
+    }
+    const uint64_t top = 1ull << ((L - 1) & 63);
+    uint32_t score = L;
+    best = L;
+    bestj = 0;
+    for (uint32_t j0 = 0; j0 < wl; j0 += 64) {
+        const int chunk = pa_chunk<REV>(W, wl, j0, lane);
+        const uint32_t cnt = wl - j0 < 64 ? wl - j0 : 64;
+        for (uint32_t t = 0; t < cnt; t++) {
+            const int c = __builtin_amdgcn_readlane(chunk, t);
+            int h = REV ? 1 : 0;
+            for (uint32_t w = 0; w < nw; w++) {
+                const uint32_t i = w * 64 + lane;
+                uint64_t pv = st[w], mv = st[PA_MAX_READ / 64 + w];
+                h = pa_step(__ballot(i < L && rd[i] == c), pv, mv, h, w == nw - 1 ? top : 1ull << 63);
+                st[w] = pv;
+                st[PA_MAX_READ / 64 + w] = mv;
+            }
+            score += h;
+            if (score < best) { best = score; bestj = j0 + t + 1; }
+        }
+    }
+}
+
+template <bool REV>
+__device__ __forceinline__ void pa_pass(const uint8_t *P, uint32_t L, const uint8_t *W, uint32_t wl, unsigned lane, uint8_t *rd, uint64_t *st,
+                                        uint32_t &best, uint32_t &bestj)
+{
+    const uint32_t nw = (L + 63) / 64;         // the tier: the same in every lane
+    if (nw == 1) pa_pass_reg<1, REV>(P, L, W, wl, lane, best, bestj);
+    else if (nw == 2) pa_pass_reg<2, REV>(P, L, W, wl, lane, best, bestj);
+    else if (nw == 3) pa_pass_reg<3, REV>(P, L, W, wl, lane, best, bestj);
+    else if (nw == 4) pa_pass_reg<4, REV>(P, L, W, wl, lane, best, bestj);
+    else pa_pass_lds<REV>(P, L, nw, W, wl, lane, rd, st, best, bestj);
+}
+
+// A wave per aligned read, 1 <= L <= PA_MAX_READ: the forward pass over the window gives edits and the smallest end e,
+// the backward pass over W[0 : e) the largest start.  out as in k_pa_prepare.
+__global__ __launch_bounds__(FBG_WAVE) void k_pa_edit(PaDev d, const uint4 *info, const uint64_t *woff, const uint8_t *win, uint64_t n,
+                                                     uint32_t *out)
+{
+    __shared__ uint8_t rd[PA_MAX_READ];
+    __shared__ uint64_t st[2 * (PA_MAX_READ / 64)];
+    const uint64_t R = blockIdx.x;
+    const unsigned lane = threadIdx.x;
+    const uint4 in = info[R];
+    const uint32_t L = in.w;
+    if (in.z == 0 || L == 0 || L > PA_MAX_READ) return;
+    const uint8_t *P = d.reads + d.roff[R], *W = win + woff[R];
+    uint32_t edits, e, back, j;
+    pa_pass<false>(P, L, W, in.z, lane, rd, st, edits, e);
+    pa_pass<true>(P, L, W, e, lane, rd, st, back, j);
+    if (lane == 0) {
+        out[n + R] = edits;
+        out[2 * n + R] = in.y + e - j;
+        out[3 * n + R] = in.y + e;
+    }
+}
+
 // ---- C ABI ------------------------------------------------------------------------------------------------------
 extern "C" int fbg_pindex_build(fbg_ctx *ctx, const uint8_t *labels, const uint64_t *label_off, uint64_t n_nodes,
                                 const uint64_t *edge_off, const uint64_t *edge_dst, fbg_pindex **out)
@@ -2713,6 +2974,117 @@ extern "C" int fbg_pindex_rows_stats(const fbg_pindex *ix, uint64_t *rows, uint6
     if (words_per_set) *words_per_set = (w.m + 63) / 64;
     if (places_unsupported) *places_unsupported = w.places_unsupported;
     if (chains_unsupported) *chains_unsupported = w.chains_unsupported;
+    return FBG_OK;
+}
+
+// ---- alignment (fbg_pindex_chains_align / _align_stats) ------------------------------------------------------------------
+// pr_prepare and k_pr_chain as in fbg_pindex_chains_rows (into buffers of the alignment state, so that call's results
+// stay), the prefix table on the first call, k_pa_prepare, a scan of the window lengths, the host's look at their sum,
+// the windows gathered into scratch of that size, and a wave per read for the two passes.
+extern "C" int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t max_window, uint32_t *row, uint32_t *edits,
+                                       uint32_t *t_start, uint32_t *t_end, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PrState &w = ix->rw;
+    PaState &al = ix->al;
+    const PcState &c = ix->ch;
+    if (device_ms) *device_ms = 0;
+    if (!ix->has_rows)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_align: only an index built by fbg_pindex_build_segmentation_rows has the row table");
+    if (!ix->sd.ready || !c.ready)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_align: no fbg_pindex_chains result since the last seeds call");
+    std::fill(al.stat, al.stat + 5, (uint64_t)0);
+    const uint64_t n = c.n;
+    if (n == 0) return FBG_OK;
+    if (n > 0x7fffffffull)        // a wave, and so a workgroup, per read
+        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_chains_align: %llu reads; a call takes fewer than 2^31", (unsigned long long)n);
+    uint32_t *host[4] = {row, edits, t_start, t_end};
+    if (c.total == 0) {          // every chain is empty, and fbg_pindex_chains may have left nothing on the device
+        for (uint32_t *h : host)
+            if (h) std::fill(h, h + n, (uint32_t)PA_NONE);
+        return FBG_OK;
+    }
+    if (pad > (1ull << 33)) pad = 1ull << 33;         // positions and read offsets are below 2^32: beyond this nothing changes
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t nb = ix->seg_nb;
+    FBG_TRY(fbg_reserve(ctx, al.pref, nb * w.m * 4, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ctx, al.nrows, 2 * n * 4, &ix->bufs, false));
+    for (DevBuf *b : {&al.info, &al.start, &al.out}) FBG_TRY(fbg_reserve(ctx, *b, n * 16, &ix->bufs, false));
+    for (DevBuf *b : {&al.wlen, &al.woff}) FBG_TRY(fbg_reserve(ctx, *b, (n + 1) * 8, &ix->bufs, false));
+    FBG_TRY(fbg_reserve(ctx, al.ctr, 5 * 8, &ix->bufs, false));
+    PrDev d;
+    FBG_TRY(pr_prepare(ix, d));                       // records ev0
+    PaDev a;
+    a.node_of = d.node_of;
+    a.pref = al.pref.as<uint32_t>();
+    a.labels = d.labels;
+    a.loff = d.loff;
+    a.reads = d.reads;
+    a.roff = (w.saved ? w.roff : ix->poff).as<uint64_t>();
+    a.m = w.m;
+    a.nb = nb;
+    if (!al.has_pref)             // the flag is set at the end of the call, once the table is known to be written
+        hipLaunchKernelGGL(k_pa_prefix, dim3(fbg_blocks(w.m, 64)), dim3(64), 0, st, a.node_of, a.loff, a.m, a.nb, al.pref.as<uint32_t>());
+    auto *ctr = al.ctr.as<unsigned long long>();
+    FBG_HIP_TRY(ctx, hipMemsetAsync(ctr, 0, 5 * 8, st));
+    const uint4 *rec = w.rec.as<uint4>();
+    const uint32_t *place = c.out.as<uint32_t>();
+    const uint64_t *off = c.off.as<uint64_t>();
+    uint32_t *nr = al.nrows.as<uint32_t>(), *out = al.out.as<uint32_t>();
+    if (w.m <= PR_SUB && !ctx->opt.rows_wave)
+        hipLaunchKernelGGL(k_pr_chain<PR_SUB>, dim3(fbg_blocks(n * PR_SUB, PX_THREADS)), dim3(PX_THREADS), 0, st, d, rec, place, off, n,
+                           (uint64_t)0, nr, nr + n, (uint64_t *)nullptr, ctr);
+    else
+        hipLaunchKernelGGL(k_pr_chain<FBG_WAVE>, dim3(fbg_blocks(n * FBG_WAVE, PX_THREADS)), dim3(PX_THREADS), 0, st, d, rec, place, off, n,
+                           (uint64_t)0, nr, nr + n, (uint64_t *)nullptr, ctr);
+    uint64_t *wlen = al.wlen.as<uint64_t>(), *woff = al.woff.as<uint64_t>();
+    hipLaunchKernelGGL(k_pa_prepare, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, a, rec, place, off, (const uint32_t *)ix->sq.as<uint32_t>(),
+                       (const uint32_t *)(nr + n), n, pad, max_window, al.info.as<uint4>(), al.start.as<uint4>(), wlen, out, ctr);
+    FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, wlen, woff, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
+    }));
+    FBG_HIP_TRY(ctx, hipGetLastError());
+    uint64_t total = 0;
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&total, woff + n, 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (total) {
+        FBG_TRY(fbg_reserve(ctx, al.win, total, &ix->bufs, false));
+        hipLaunchKernelGGL(k_pa_gather, dim3((unsigned)n), dim3(FBG_WAVE), 0, st, a, (const uint4 *)al.info.as<uint4>(),
+                           (const uint4 *)al.start.as<uint4>(), (const uint64_t *)woff, al.win.as<uint8_t>());
+        hipLaunchKernelGGL(k_pa_edit, dim3((unsigned)n), dim3(FBG_WAVE), 0, st, a, (const uint4 *)al.info.as<uint4>(), (const uint64_t *)woff,
+                           (const uint8_t *)al.win.as<uint8_t>(), n, out);
+        FBG_HIP_TRY(ctx, hipGetLastError());
+    }
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev1, st));
+    uint64_t stat[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < 4; k++)
+        if (host[k]) FBG_HIP_TRY(ctx, hipMemcpyAsync(host[k], out + k * n, n * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(stat, ctr, 5 * 8, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    float ms = 0;
+    FBG_HIP_TRY(ctx, hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    if (device_ms) *device_ms = ms;
+    std::copy(stat, stat + 5, al.stat);
+    al.has_pref = true;
+    return FBG_OK;
+}
+
+extern "C" int fbg_pindex_align_stats(const fbg_pindex *ix, uint64_t *aligned, uint64_t *unsupported, uint64_t *too_long,
+                                      uint64_t *too_wide, uint64_t *cells, uint64_t *max_read, uint64_t *table_bytes)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    if (!ix->has_rows)
+        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "fbg_pindex_align_stats: only an index built by fbg_pindex_build_segmentation_rows has the row table");
+    const PaState &al = ix->al;
+    if (aligned) *aligned = al.stat[1];
+    if (unsupported) *unsupported = al.stat[0];
+    if (too_long) *too_long = al.stat[2];
+    if (too_wide) *too_wide = al.stat[3];
+    if (cells) *cells = al.stat[4];
+    if (max_read) *max_read = PA_MAX_READ;
+    if (table_bytes) *table_bytes = al.has_pref ? 4 * ix->rw.m * ix->seg_nb : 0;
     return FBG_OK;
 }
 

@@ -775,6 +775,67 @@ int fbg_pindex_rows_stats(const fbg_pindex *ix, uint64_t *rows, uint64_t *table_
 int fbg_pindex_seeds_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, double *device_ms);
 int fbg_pindex_chains_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, uint64_t *row_bits, double *device_ms);
 
+/* The edit distance of each read to a row that carries its chain (an index built by
+ * fbg_pindex_build_segmentation_rows only; after a successful seeds call, plain or stranded, and a successful
+ * fbg_pindex_chains since it).
+ *
+ * A chain says which pieces of a read match exactly and where; it says nothing about the symbols between and around
+ * the anchors.  fbg_pindex_chains_rows names the rows that spell every anchor of a chain, and the row table holds the
+ * gap-stripped text G_r of every row, so the whole read can be aligned against one real input sequence around its
+ * chain: "this read lies on input sequence r from t_start to t_end with d edits".  For a (virtual) read R let P be its
+ * text, for a reverse virtual read rc(P_R), exactly as fbg_pindex_chains_rows reads it, and L = |P|.
+ *   r          the smallest row of rows(chain of R).  If the chain is empty or no row carries it,
+ *              row[R] = edits[R] = t_start[R] = t_end[R] = FBG_ALIGN_NONE.
+ *   x_i, d_i   for anchor i of the chain, a place in node u_i at o_i of a seed (q_i, k_i): x_i = p(r, block(u_i)) + o_i,
+ *              its position in G_r (the x of the rows section), and the diagonal d_i = x_i - q_i, signed 64-bit.
+ *   W          the window G_r[w0 : w1) with w0 = max(0, min_i d_i - pad) and w1 = min(|G_r|, max_i d_i + L + pad).  It
+ *              holds every anchor's stretch of G_r and so is never empty.
+ *   D          unit costs, the ends of the row free, the read global: D(0, j) = 0, D(i, 0) = i,
+ *              D(i, j) = min(D(i-1, j-1) + [P[i-1] != W[j-1]], D(i-1, j) + 1, D(i, j-1) + 1).  Symbols are compared as
+ *              bytes: no case folding, no ignore characters.
+ *   edits[R]   min_j D(L, j).  It follows that edits[R] <= L - max_i k_i.
+ *   t_end[R]   w0 + e, e the smallest j that attains edits[R].
+ *   t_start[R] the largest s in [w0, t_end] with lev(P, G_r[s : t_end)) == edits[R]; one always exists.  It is t_end - j'
+ *              for the smallest end j' of a second pass over the reversed read against W[0 : e) reversed, with
+ *              D'(0, j) = j.
+ * The result is exact: the full recurrence over the window, no band inside it and no early cut-off.  Two per-read skips
+ * keep row[R] and set the three other arrays to FBG_ALIGN_NONE; a skipped read is no error:
+ *   too long   L > max_read, a constant of the implementation (1024, reported by fbg_pindex_align_stats);
+ *   too wide   w1 - w0 > max_window (0: no limit), tested after too long.
+ *
+ *   fbg_pindex_chains_align   one entry per read of the last seeds call (2n after fbg_pindex_seeds_strands) in each of
+ *       the four arrays; any of them may be NULL.  pad is clamped to 2^33, beyond which no window changes, so the sums
+ *       stay in 64 bits.
+ *   fbg_pindex_align_stats    any pointer may be NULL.  Of the last fbg_pindex_chains_align (0 before the first; a call
+ *       that fails its checks leaves them): the reads aligned; the non-empty chains that no row carries; the reads
+ *       skipped as too long and as too wide; cells, the sum of L * |W| over the aligned reads, which is the work.  Then
+ *       max_read, and the device bytes of the prefix table (0 until the first call builds it).
+ * On the device.  The prefix table p(r, j) is uint32[nb * m], block-major like node_of, built by the first call (one
+ * lane per row steps over the blocks, so a wave reads 64 consecutive rows at every step) and owned by the index;
+ * |G_r| < 2^32 holds because the build takes fewer than 2^32 columns.  A call chooses the rows with the kernel of
+ * fbg_pindex_chains_rows; one lane per read then finds the diagonals, the window, the skip status and, by a search of
+ * the row's column of the prefix table, the block, node and offset at which the window starts; the window lengths are
+ * scanned and their sum sizes the scratch; a wave per read gathers its window label by label (lanes take consecutive
+ * bytes, cells without a node are passed over); a wave per read runs Myers' bit-vector recurrence twice.  There lane i
+ * holds read symbols i, 64 + i, ..., the window is loaded 64 bytes at a time, each byte is made wave-uniform by a
+ * readlane, and the match word of a text byte is one ballot per 64 read symbols: no per-symbol table, any byte
+ * alphabet.  The vertical difference words are wave-uniform 64-bit values; the last word is masked to L % 64 bits and
+ * the score is followed at bit L - 1.  Reads of 1, 2, 3 and 4 words keep the state in registers (a template on the word
+ * count), longer ones up to max_read in LDS with a loop over the words; every tier runs the same recurrence.  Scratch
+ * owned by the index: 72 bytes per read, the windows, and what fbg_pindex_chains_rows keeps per seed and start place.
+ * *device_ms (may be NULL): device time of these kernels.
+ * A call may be repeated and leaves the seeds, their places and MSA coordinates, the chains, what the row calls
+ * returned, the occurrences, fbg_pindex_stats, validation results and the context alone; like the row calls it still
+ * sees the reads of the last seeds call after a later fbg_pindex_locate or fbg_pindex_occurrences.
+ * Errors, all FBG_ERR_INVALID: a NULL index; an index without the row table; no successful fbg_pindex_chains since the
+ * last seeds call.  FBG_ERR_TOO_LARGE for 2^31 reads or more (a workgroup per read); the allocator's error if the
+ * windows do not fit device memory.  No reads returns FBG_OK. */
+#define FBG_ALIGN_NONE 0xffffffffu
+int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t max_window, uint32_t *row, uint32_t *edits,
+                            uint32_t *t_start, uint32_t *t_end, double *device_ms);
+int fbg_pindex_align_stats(const fbg_pindex *ix, uint64_t *aligned, uint64_t *unsupported, uint64_t *too_long,
+                           uint64_t *too_wide, uint64_t *cells, uint64_t *max_read, uint64_t *table_bytes);
+
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
  * to_remove[node_blocks[i] - 1] (fbg.cpp:3269-3270, 3194); cut_bad[nb - 1] is always 0.  The index is built by
