@@ -222,6 +222,9 @@ static const OptKey g_opt_keys[] = {
     {"cand_local_sort", &FbgOptions::cand_local_sort},
     {"cand_lds_cap", &FbgOptions::cand_lds_cap},
     {"cand_sort_check", &FbgOptions::cand_sort_check},
+    {"tie_gallop", &FbgOptions::tie_gallop},
+    {"cand_counts_fused", &FbgOptions::cand_counts_fused},
+    {"tie_sample_loop", &FbgOptions::tie_sample_loop},
 };
 
 // read-only keys of fbg_get_option: what the context and its last build report
@@ -386,6 +389,7 @@ void fbg_ctx_destroy(fbg_ctx *ctx)
         (void)hipStreamDestroy(ctx->stager.stream);
         (void)hipHostFree(ctx->stager.base);
     }
+    if (ctx->pin_pair) (void)hipHostFree(ctx->pin_pair);
     if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
     if (ctx->aux_join) (void)hipEventDestroy(ctx->aux_join);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);

@@ -42,7 +42,8 @@ struct FbgOptions {
             dp_safe_window = 0, dp_tile = 0, pure_scan = 0, gapped_rank = 0, part_tricks_off = 0, msd_sample_bins = 0, msd_min_force = 0, msd_probe = 0, msd_xcd = -1, rank_no_lean = 0, no_stream_upload = 0,
             span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0, msd_ext = 1, rows_wave = 0,
             pairs_in_scan = 1, runs_wave_min = 16, wave_list_cap = 0,
-            cand_local_sort = 1, cand_lds_cap = 0, cand_sort_check = 0;
+            cand_local_sort = 1, cand_lds_cap = 0, cand_sort_check = 0,
+            tie_gallop = 1, cand_counts_fused = 1, tie_sample_loop = 1;
 };
 
 // The index at hand: per-position records, or the sorted slots plus per-column maxima of rank_scan.hip / pure_scan.hip
@@ -109,6 +110,7 @@ struct fbg_ctx {
     hipStream_t aux = nullptr;
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
     bool aux_pending = false;
+    uint32_t *pin_pair = nullptr;  // two pinned words the candidates' total and largest count come back into (rank_scan.hip)
     Stager stager;
     StageTimer timers[FBG_STAGE_COUNT];
 
@@ -186,6 +188,7 @@ struct fbg_ctx {
     DevBuf wave_list;          // the runs that get a wave each (RankArgs::wl)
     DevBuf kargs;              // arguments a kernel reads from memory (k_rank_scan_lean) ...
     alignas(16) unsigned char kargs_host[512];   // ... and the host copy they are sent from
+    uint8_t code_host[256];    // fbg_key_setup's code table on its way to the device (kept here: nothing to wait for)
     DevBuf msd_w, msd_v;       // sub-bucket stretches of the MSD sort of 12-byte slots (msd_sort_pairs.hip)
     DevBuf dp_a, dp_b, dp_c, dp_d, dp_e, dp_f, dp_g, dp_h, io_a, io_b, io_c, io_d;
     DevBuf bt_up, bt_dep;      // binary-lifting tables of the parallel backtrack

@@ -7,15 +7,65 @@
 // as the program does with the GPU's arrays, instead of from labels hashed on the host (write_xgfa).
 // prints "m n" of the MSA as read, then (with boundaries given: inclusive block ends, the last one == n, fbg.cpp:2027-2039)
 // writes the xGFA and prints "nodes total_label_length founders edges".
+//     fbg_host_selftest tie-extent
+// checks fbg_tie_extent (tie_extent.h, the size of a tie group as rank_scan.hip's k_tie_groups finds it) against the plain count
+// it replaces: groups of 1 .. 70 and 8191 .. 8194 slots at the start of a sorted array, in its middle and ending exactly at
+// `hi`, each also with `hi` cutting the group short; prints "tie_extent ok CASES" or the first case that differs.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 #include "fasta.hpp"
 #include "xgfa.hpp"
+#include "../tie_extent.h"
+
+static int tie_extent_selftest()
+{
+    const uint32_t cap = 8192;                          // rank_scan.hip: RS_BIG_MEMBERS
+    std::vector<uint32_t> sizes;
+    for (uint32_t s = 1; s <= 70; s++) sizes.push_back(s);
+    for (uint32_t s = 8191; s <= 8194; s++) sizes.push_back(s);
+    unsigned long long cases = 0;
+    for (const uint32_t s : sizes)
+        for (int where = 0; where < 3; where++) {       // the group at the array's start, in the middle, ending exactly at hi
+            const uint64_t before = where == 0 ? 0 : 37, after = where == 2 ? 0 : 29;
+            std::vector<uint64_t> keys;
+            for (uint64_t i = 0; i < before; i++) keys.push_back(10 + i / 3);          // (small groups before and after)
+            const uint64_t key = 1000;
+            for (uint32_t i = 0; i < s; i++) keys.push_back(key);
+            for (uint64_t i = 0; i < after; i++) keys.push_back(2000 + i / 2);
+            const uint64_t k0 = before;
+            uint64_t reads = 0;
+            auto key_at = [&](uint64_t k) -> uint64_t {
+                reads++;
+                if (k >= keys.size()) { std::fprintf(stderr, "tie_extent: read of slot %llu beyond the array\n", (unsigned long long)k); std::exit(1); }
+                return keys[k];
+            };
+            // hi: the array's end, and every place that cuts the group short by 0 .. 3 slots
+            std::vector<uint64_t> his = {keys.size()};
+            for (uint64_t cut = 0; cut <= 3 && cut < s; cut++) his.push_back(k0 + s - cut);
+            for (const uint64_t hi : his) {
+                uint32_t want = 1;
+                while (k0 + want < hi && want <= cap && keys[k0 + want] == key) want++;
+                reads = 0;
+                const uint32_t got = fbg_tie_extent(k0, hi, cap, key, key_at);
+                // FBG_TIE_PROBE slots one by one, then two reads per doubling: far below one read per member
+                const uint64_t most = FBG_TIE_PROBE + 2 * 14;
+                if (got != want || reads > most) {
+                    std::printf("tie_extent differs: size %u position %d hi %llu: got %u, want %u, %llu reads\n", s, where,
+                                (unsigned long long)hi, got, want, (unsigned long long)reads);
+                    return 1;
+                }
+                cases++;
+            }
+        }
+    std::printf("tie_extent ok %llu\n", cases);
+    return 0;
+}
 
 int main(int argc, char **argv)
 {
+    if (argc == 2 && std::string(argv[1]) == "tie-extent") return tie_extent_selftest();
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s FASTA GAP_LIMIT ELASTIC PATHS OUT.gfa [BOUNDARY ...]\n", argv[0]);
         return 2;

@@ -40,6 +40,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rank_common.h"
+#include "tie_extent.h"
 
 // k_rank_scan stages a chunk of 256 slots (+ RS_HALO either side) in LDS as (key, column): all the looking around
 // that tie groups need happens there.
@@ -601,6 +602,64 @@ __global__ __launch_bounds__(256) void k_tie_sample(const uint64_t *__restrict__
     }
 }
 
+// The same sample by a fixed grid: a workgroup walks clusters blockIdx.x, blockIdx.x + gridDim.x, ... (the next cluster's keys
+// in flight), counts in LDS and adds its counts to global memory once -- k_tie_sample's 3815 workgroups at 10^9 slots each end in
+// up to 20 atomics on the same 65 words, which the L2 takes one after the other.  Same slots, same sums.
+#define RS_SAMPLE_BLOCKS 512
+__global__ __launch_bounds__(256) void k_tie_sample_loop(const uint64_t *__restrict__ keys, int shift, uint64_t N, int b, int key_bits,
+                                                         uint64_t clusters, unsigned long long *__restrict__ counters,
+                                                         unsigned int *__restrict__ hist)
+{
+    __shared__ unsigned int sh[64];
+    __shared__ unsigned int sties;
+    if (threadIdx.x < 64) sh[threadIdx.x] = 0;
+    if (threadIdx.x == 0) sties = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    unsigned long long looked = 0;                                    // (thread 0's)
+    uint64_t w[3] = {0, 0, 0};                                        // the slot's word and its two neighbours'
+    auto fetch = [&](uint64_t c) {
+        const uint64_t k = c * 1024 * 256 + threadIdx.x;
+        if (k < N) {
+            w[1] = keys[k];
+            w[0] = k > 0 ? keys[k - 1] : 0ull;
+            w[2] = k + 1 < N ? keys[k + 1] : 0ull;
+        }
+    };
+    if (blockIdx.x < clusters) fetch(blockIdx.x);
+    for (uint64_t c = blockIdx.x; c < clusters; c += gridDim.x) {
+        const uint64_t k = c * 1024 * 256 + threadIdx.x;
+        const uint64_t key = w[1] >> shift;
+        const uint64_t kp = k > 0 ? w[0] >> shift : ~key, kn = k + 1 < N ? w[2] >> shift : ~key;
+        if (c + gridDim.x < clusters) fetch(c + gridDim.x);
+        uint32_t bin = 0xffffffffu;                                   // 64 = ties on the whole key
+        if (k < N) {
+            if (kp == key || kn == key) {
+                bin = 64;
+            } else {
+                const uint32_t lp = k > 0 ? rs_key_lcp(kp, key, b, key_bits) : 0u;
+                const uint32_t ln = k + 1 < N ? rs_key_lcp(key, kn, b, key_bits) : 0u;
+                bin = min(max(lp, ln) + 1, 63u);
+            }
+        }
+        unsigned long long rest = __ballot(bin != 0xffffffffu);
+        while (rest) {
+            const int l = __ffsll((long long)rest) - 1;
+            const uint32_t v = __shfl(bin, l, 64);
+            const unsigned long long same = __ballot(bin == v);
+            if (lane == l) { if (v == 64) atomicAdd(&sties, (uint32_t)__popcll(same)); else atomicAdd(&sh[v], (uint32_t)__popcll(same)); }
+            rest &= ~same;
+        }
+        looked += min((uint64_t)256, N - c * 1024 * 256);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64 && sh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], sh[threadIdx.x]);
+    if (threadIdx.x == 0 && looked) {
+        if (sties) atomicAdd(&counters[2], (unsigned long long)sties);
+        atomicAdd(&counters[3], looked);
+    }
+}
+
 // columns whose maximum stayed below the threshold: extensions that were skipped for being smaller than g_min may
 // exceed it -- the threshold was too optimistic for them (a maximum of g_min or more cannot be beaten by a skipped one)
 __global__ void k_count_unfilled(const uint32_t *__restrict__ gmax, uint64_t n, uint32_t g_min, int reversed,
@@ -653,6 +712,38 @@ __global__ __launch_bounds__(256) void k_cand_sort_compact(const uint32_t *__res
     for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) out[o + i] = buf[i];
 }
 
+// The candidate counts of the workgroups (nb of them, 4096 at most) -> their exclusive offsets offs[0 .. nb] (offs[nb]: the total),
+// and the total and the largest count side by side in tot_max[0 .. 1], for one copy to the host.  One workgroup: a thread
+// takes a stretch of counts, the stretches' sums are scanned across the wave and then across the 16 waves.
+#define RS_COUNTS_THREADS 1024
+__global__ __launch_bounds__(RS_COUNTS_THREADS) void k_cand_counts(const uint32_t *__restrict__ counts, uint32_t nb, uint32_t *__restrict__ offs,
+                                                                   uint32_t *__restrict__ tot_max)
+{
+    __shared__ uint32_t wsum[RS_COUNTS_THREADS / 64], wmax[RS_COUNTS_THREADS / 64];
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t per = (nb + RS_COUNTS_THREADS - 1) / RS_COUNTS_THREADS;
+    const uint32_t i0 = min(threadIdx.x * per, nb), i1 = min(i0 + per, nb);
+    uint32_t sum = 0, mx = 0;
+    for (uint32_t i = i0; i < i1; i++) { const uint32_t c = counts[i]; sum += c; mx = max(mx, c); }
+    uint32_t inc = sum;                                                // inclusive scan of the stretches' sums in the wave
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if (lane >= (uint32_t)d) inc += o;
+    }
+    for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, d, 64));
+    if (lane == 63) wsum[wv] = inc;
+    if (lane == 0) wmax[wv] = mx;
+    __syncthreads();
+    uint32_t before = inc - sum, total = 0, largest = 0;
+    for (uint32_t v = 0; v < RS_COUNTS_THREADS / 64; v++) {
+        if (v < wv) before += wsum[v];
+        total += wsum[v];
+        largest = max(largest, wmax[v]);
+    }
+    for (uint32_t i = i0; i < i1; i++) { offs[i] = before; before += counts[i]; }
+    if (threadIdx.x == 0) { offs[nb] = total; tot_max[0] = total; tot_max[1] = largest; }
+}
+
 // debugging aid (option cand_sort_check): places of the sorted candidate list that do not ascend
 __global__ void k_cand_inversions(const uint32_t *__restrict__ cand, uint64_t T, unsigned long long *__restrict__ count)
 {
@@ -666,7 +757,7 @@ __global__ void k_cand_inversions(const uint32_t *__restrict__ cand, uint64_t T,
 // Groups of more than 64 go to k_tie_big.
 #define RS_BIG_GROUPS 1024
 #define RS_BIG_MEMBERS 8192
-template <int L> __global__ void k_tie_groups(RankArgs a, uint64_t T, int by_list)
+template <int L> __global__ void k_tie_groups(RankArgs a, uint64_t T, int by_list, int gallop)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
@@ -674,8 +765,11 @@ template <int L> __global__ void k_tie_groups(RankArgs a, uint64_t T, int by_lis
     const uint64_t key = rs_key<L>(a, k0);
     if (k0 > a.own_lo && rs_key<L>(a, k0 - 1) == key) return;                      // inside a group
     if (k0 + 1 >= a.own_hi || rs_key<L>(a, k0 + 1) != key) return;                 // not a tie (ties never cross partitions)
+    // the group's size, RS_BIG_MEMBERS + 1 for anything larger.  Counting member by member is one dependent load each: the
+    // row ends make groups of a thousand and more, and the whole kernel is as long as that one thread (gallop: tie_extent.h)
     uint32_t s = 1;
-    while (k0 + s < a.own_hi && s <= RS_BIG_MEMBERS && rs_key<L>(a, k0 + s) == key) s++;
+    if (gallop) s = fbg_tie_extent(k0, a.own_hi, RS_BIG_MEMBERS, key, [&](uint64_t k) { return rs_key<L>(a, k); });
+    else while (k0 + s < a.own_hi && s <= RS_BIG_MEMBERS && rs_key<L>(a, k0 + s) == key) s++;
     if (s > 64) {
         if (s > RS_BIG_MEMBERS) { a.counters[1] = 1; return; }
         const unsigned long long e = atomicAdd(&a.counters[5], 1ull);
@@ -1006,7 +1100,7 @@ static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T
     }
     a.cand = sorted;
     a.pm = ctx->dp_b.as<uint32_t>();
-    RS_LAUNCH(k_tie_groups, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T, 1);
+    RS_LAUNCH(k_tie_groups, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T, 1, ctx->opt.tie_gallop != 0 ? 1 : 0);
     RS_LAUNCH(k_tie_big, layout, dim3(RS_BIG_GROUPS), dim3(256), st, a, 0);
     *launches += 3;
     return FBG_OK;
@@ -1078,17 +1172,26 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
     const int rc_rest = [&]() -> int {
         // candidate counts per workgroup -> offsets; total and the largest count come back to the host
         uint32_t *d_counts = a.blk_count, *d_offs = ctx->dp_d.as<uint32_t>();
-        FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
-            return rocprim::exclusive_scan(tmp, bytes, d_counts, d_offs, 0u, (size_t)(rs_blocks + 1), rocprim::plus<uint32_t>(), st);
-        }));
-        uint32_t *d_max = reinterpret_cast<uint32_t *>(a.counters + 6);
-        FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
-            return rocprim::reduce(tmp, bytes, d_counts, d_max, 0u, (size_t)rs_blocks, rocprim::maximum<uint32_t>(), st);
-        }));
+        uint32_t *d_max = reinterpret_cast<uint32_t *>(a.counters + 6);           // (the fused kernel: total, largest)
         uint32_t tot = 0, mx = 0;
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(&tot, d_offs + rs_blocks, 4, hipMemcpyDeviceToHost, st));
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, st));
-        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (ctx->opt.cand_counts_fused) {
+            // one small kernel and one copy into pinned memory instead of a scan (two launches), a reduce and two copies
+            if (!ctx->pin_pair) FBG_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->pin_pair), 2 * sizeof(uint32_t), hipHostMallocDefault));
+            hipLaunchKernelGGL(k_cand_counts, dim3(1), dim3(RS_COUNTS_THREADS), 0, st, d_counts, (uint32_t)rs_blocks, d_offs, d_max);
+            FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->pin_pair, d_max, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+            tot = ctx->pin_pair[0]; mx = ctx->pin_pair[1];
+        } else {
+            FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+                return rocprim::exclusive_scan(tmp, bytes, d_counts, d_offs, 0u, (size_t)(rs_blocks + 1), rocprim::plus<uint32_t>(), st);
+            }));
+            FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+                return rocprim::reduce(tmp, bytes, d_counts, d_max, 0u, (size_t)rs_blocks, rocprim::maximum<uint32_t>(), st);
+            }));
+            FBG_HIP_TRY(ctx, hipMemcpyAsync(&tot, d_offs + rs_blocks, 4, hipMemcpyDeviceToHost, st));
+            FBG_HIP_TRY(ctx, hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, st));
+            FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        }
         const uint64_t T = tot;
         *T_out = T;
         if (mx > region) { *T_out = ~0ull; return rs_join(ctx); }
@@ -1114,6 +1217,15 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
     return FBG_OK;
 }
 
+// The scan's eight counters and, where rs_pick_threshold will sample (count > 2^22), the 64 words of its histogram right
+// behind them: one fill
+static int rs_zero_counters(fbg_ctx *ctx, unsigned long long *cnt, uint64_t count)
+{
+    const size_t bytes = 8 * sizeof(unsigned long long) + (count > (1u << 22) ? 64 * sizeof(unsigned int) : 0);
+    FBG_HIP_TRY(ctx, hipMemsetAsync(cnt, 0, bytes, ctx->stream));
+    return FBG_OK;
+}
+
 // Sample of the sorted keys (count > 2^22 only): (a) similar rows tie almost everywhere -> *reject, the rank-order scan
 // is not for them; (b) a.g_min: extensions so small that >= 32 rows of every column are expected to exceed them cannot
 // be a column maximum -- skipping them removes almost all table reads.  The threshold is verified afterwards
@@ -1126,9 +1238,15 @@ static int rs_pick_threshold(fbg_ctx *ctx, RankArgs &a, const uint64_t *keys, ui
     hipStream_t st = ctx->stream;
     unsigned long long *cnt = a.counters;
     unsigned int *d_hist = reinterpret_cast<unsigned int *>(cnt + 8);
-    FBG_HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, 64 * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(k_tie_sample, dim3(fbg_blocks(count, 1024 * 256)), dim3(256), 0, st, keys, a.pb, count, geom.b, geom.key_bits,
-                       cnt, d_hist);
+    // (the histogram was zeroed with the counters: rs_zero_counters)
+    const unsigned clusters = fbg_blocks(count, 1024 * 256);
+    if (ctx->opt.tie_sample_loop > 0) {
+        const unsigned grid = ctx->opt.tie_sample_loop == 1 ? RS_SAMPLE_BLOCKS : (unsigned)std::min<int64_t>(ctx->opt.tie_sample_loop, 4096);
+        hipLaunchKernelGGL(k_tie_sample_loop, dim3(std::min(clusters, grid)), dim3(256), 0, st, keys, a.pb, count, geom.b, geom.key_bits,
+                           (uint64_t)clusters, cnt, d_hist);
+    }
+    else
+        hipLaunchKernelGGL(k_tie_sample, dim3(clusters), dim3(256), 0, st, keys, a.pb, count, geom.b, geom.key_bits, cnt, d_hist);
     (*launches)++;
     unsigned long long hs[4];
     unsigned int hh[64];
@@ -1165,7 +1283,7 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     RankArgs a;
     rs_args_init(ctx, a, keys, vals, N, layout, geom.pb, geom.b, geom.key_bits, geom.K);
     uint64_t T = 0;
-    FBG_HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 8 * sizeof(unsigned long long), st));
+    FBG_TRY(rs_zero_counters(ctx, cnt, N));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->gmax.p, 0, (n + 1) * 4, st));
     int reject = 0;
     FBG_TRY(rs_pick_threshold(ctx, a, keys, N, geom, &reject, &launches));
@@ -1263,7 +1381,7 @@ int fbg_rank_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_
     const int layout = rs_layout(geom);
     FBG_TRY(fbg_reserve(ctx, ctx->gmax, (n + 1) * 4));
     unsigned long long *cnt = ctx->scalars.as<unsigned long long>() + 32;
-    FBG_HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 8 * sizeof(unsigned long long), st));
+    FBG_TRY(rs_zero_counters(ctx, cnt, count));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->gmax.p, 0, (n + 1) * 4, st));
     int good = pre_ok && count >= 2 * FBG_PART_HALO;
     RankArgs a;
@@ -1391,7 +1509,7 @@ int fbg_rank_materialize(fbg_ctx *ctx, uint32_t *d_sa, uint32_t *d_isa, uint32_t
     FBG_TRY(fbg_reserve(ctx, ctx->big_groups, RS_BIG_GROUPS * 8));
     a.big = ctx->big_groups.as<uint32_t>();
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.counters + 5, 0, sizeof(unsigned long long), ctx->stream));
-    RS_LAUNCH(k_tie_groups, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, ctx->N, 0);
+    RS_LAUNCH(k_tie_groups, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, ctx->N, 0, ctx->opt.tie_gallop != 0 ? 1 : 0);
     RS_LAUNCH(k_tie_big, ctx->ix.rk_layout, dim3(RS_BIG_GROUPS), dim3(256), ctx->stream, a, 1);
     RS_LAUNCH(k_rank_materialize, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, d_sa, d_isa, d_pl, d_pr);
     FBG_HIP_TRY(ctx, hipGetLastError());

@@ -723,7 +723,7 @@ int fbg_key_setup(fbg_ctx *ctx, bool compact, KeyGeom *g, int *launches)
     for (int c = 1; c < 256; c++)
         if (hist[c] && c != '#') { real++; if (c < '#') below++; }
     compact = compact && below == 0 && real >= 1 && real < FBG_SEP;
-    uint8_t code[256];
+    uint8_t *code = ctx->code_host;                       // (in the context: the copy below needs no wait)
     int sigma = 0;
     if (compact) {
         for (int c = 0; c < 256; c++) {
@@ -770,7 +770,6 @@ int fbg_key_setup(fbg_ctx *ctx, bool compact, KeyGeom *g, int *launches)
     g->b = b; g->K = K; g->key_bits = K * b; g->d_code = d_code;
     fbg_note_key_geom(ctx, *g);
     FBG_HIP_TRY(ctx, hipMemcpyAsync(d_code, code, 256, hipMemcpyHostToDevice, st));
-    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));  // code[] lives on this stack frame
     *launches += 1;
     return FBG_OK;
 }

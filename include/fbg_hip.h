@@ -131,6 +131,14 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *                      largest region fits); results unchanged
  *   cand_lds_cap       the largest region count that sort takes (0 = 4096, the most; tests)
  *   cand_sort_check    1: the sorted candidate list is checked to ascend ("cand_inversions"; debugging, one more wait)
+ *   tie_gallop         0: k_tie_groups counts the members of a tie group one by one (default 1: 8 slots one by one, then
+ *                      doubling steps and bisection on the sorted keys, tie_extent.h); results unchanged
+ *   cand_counts_fused  0: the candidate counts of the rank-order scan's workgroups go through rocPRIM's scan and reduce and two
+ *                      copies (default 1: one kernel of one workgroup writes their offsets, their total and the largest, one
+ *                      copy brings the two to the host); results unchanged
+ *   tie_sample_loop    0: the sample of the sorted keys before the rank-order scan (k_tie_sample) takes one workgroup per
+ *                      cluster of 256 slots (default 1: 512 workgroups walk the clusters and add their counts to global memory
+ *                      once each; n > 1: n workgroups, tests); same slots, same sums, same threshold and verdict
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
  * fbg_get_option also answers "index_kind" (read-only): -1 no index, 0 per-position records, 1 rank-order scan of a
