@@ -225,6 +225,9 @@ static const OptKey g_opt_keys[] = {
     {"tie_gallop", &FbgOptions::tie_gallop},
     {"cand_counts_fused", &FbgOptions::cand_counts_fused},
     {"tie_sample_loop", &FbgOptions::tie_sample_loop},
+    {"row_count_fast", &FbgOptions::row_count_fast},
+    {"twin_hash", &FbgOptions::twin_hash},
+    {"front_one_fill", &FbgOptions::front_one_fill},
 };
 
 // read-only keys of fbg_get_option: what the context and its last build report
@@ -237,6 +240,7 @@ static const InfoKey g_info_keys[] = {
     {"pass1_ahead", [](const fbg_ctx &c) -> int64_t { return c.diag.pass1_ahead; }},
     {"ext_pairs", [](const fbg_ctx &c) -> int64_t { return c.diag.ext_pairs; }},
     {"text_pairs", [](const fbg_ctx &c) -> int64_t { return c.diag.text_pairs; }},
+    {"sample_twins", [](const fbg_ctx &c) -> int64_t { return c.diag.sample_twins; }},
     {"cand_inversions", [](const fbg_ctx &c) -> int64_t { return c.diag.cand_inversions; }},
     {"cand_local_sorted", [](const fbg_ctx &c) -> int64_t { return c.diag.cand_local_sorted; }},
     {"wave_runs", [](const fbg_ctx &c) -> int64_t { return c.diag.wave_runs; }},
@@ -390,6 +394,9 @@ void fbg_ctx_destroy(fbg_ctx *ctx)
         (void)hipHostFree(ctx->stager.base);
     }
     if (ctx->pin_pair) (void)hipHostFree(ctx->pin_pair);
+    if (ctx->pin_twins) (void)hipHostFree(ctx->pin_twins);
+    if (ctx->twin_ev) (void)hipEventDestroy(ctx->twin_ev);
+    if (ctx->pin_front) (void)hipHostFree(ctx->pin_front);
     if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
     if (ctx->aux_join) (void)hipEventDestroy(ctx->aux_join);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);

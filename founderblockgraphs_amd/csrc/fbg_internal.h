@@ -43,7 +43,8 @@ struct FbgOptions {
             span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0, msd_ext = 1, rows_wave = 0,
             pairs_in_scan = 1, runs_wave_min = 16, wave_list_cap = 0,
             cand_local_sort = 1, cand_lds_cap = 0, cand_sort_check = 0,
-            tie_gallop = 1, cand_counts_fused = 1, tie_sample_loop = 1;
+            tie_gallop = 1, cand_counts_fused = 1, tie_sample_loop = 1,
+            row_count_fast = 1, twin_hash = 1, front_one_fill = 1;
 };
 
 // The index at hand: per-position records, or the sorted slots plus per-column maxima of rank_scan.hip / pure_scan.hip
@@ -82,6 +83,7 @@ struct BuildDiag {
     int64_t msd_decline = -1;    // fbg_msd_sort: -1 not reached, 0 sorted; 1 not tried (geometry), 2 / 4 a stretch of pass 1, 8 the arena of pass 2, 16 a sub-bucket too large
     int pass1_ahead = 0;         // the MSD sort found its pass 1 done (streamed upload)
     int64_t ext_pairs = -1, text_pairs = -1;   // the rank-order scan: tied pairs settled by the msd_ext symbols / by the text
+    int64_t sample_twins = -1;   // twins among the keys of the sample before the sort (suffix_sort.hip); -1: no sample was drawn
     int64_t wave_runs = -1;      // the rank-order scan: runs that a wave each walked (k_runs_long)
     int64_t cand_inversions = -1;  // option cand_sort_check: places of the sorted candidate list that do not ascend
     int cand_local_sorted = -1;  // the candidates were sorted region by region in k_cand_sort_compact (1) / by the radix sort (0)
@@ -111,6 +113,11 @@ struct fbg_ctx {
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
     bool aux_pending = false;
     uint32_t *pin_pair = nullptr;  // two pinned words the candidates' total and largest count come back into (rank_scan.hip)
+    // the twins among the sampled keys come back into two pinned words; twin_ev follows the copy (suffix_sort.hip sample_launch)
+    unsigned long long *pin_twins = nullptr;
+    hipEvent_t twin_ev = nullptr;
+    bool twin_pending = false;
+    unsigned long long *pin_front = nullptr;   // the symbol histogram and the three counts of the counting pass, pinned (text_build.hip)
     Stager stager;
     StageTimer timers[FBG_STAGE_COUNT];
 
@@ -127,7 +134,8 @@ struct fbg_ctx {
     bool allow_wide = false;       // the caller can work with text positions beyond 32 bits (partitioned index only)
     uint32_t mp = 0;           // rows padded to a multiple of 64 (column-tile pitch)
     DevBuf text;               // N + 64 bytes, zero padded
-    DevBuf pos, tot;           // u32[m]
+    DevBuf pos, tot;           // u32[m]; behind tot (at the next multiple of 8 bytes): the byte histogram of the counting pass, u64[256],
+                               // and its counts, u64[8] -- gaps, ignore cells, N (text_build.hip: one fill clears all three)
     DevBuf segtab;             // u32[3][m][segments]: per 65536-column segment of a row: non-gap cells, prefix, first ignore column
     DevBuf colT;               // u32[N]: MSA column of each text position (gapped MSAs only)
     DevBuf gwin_rows;          // u16 per window of 128 positions: the row of its first position (written with the text)

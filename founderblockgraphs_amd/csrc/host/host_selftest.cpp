@@ -11,6 +11,12 @@
 // checks fbg_tie_extent (tie_extent.h, the size of a tie group as rank_scan.hip's k_tie_groups finds it) against the plain count
 // it replaces: groups of 1 .. 70 and 8191 .. 8194 slots at the start of a sorted array, in its middle and ending exactly at
 // `hi`, each also with `hi` cutting the group short; prints "tie_extent ok CASES" or the first case that differs.
+//     fbg_host_selftest twin-hash KEYS.bin BITS
+// counts the twins among the 64-bit keys of a file the way suffix_sort.hip's k_sample_twins does (twin_hash.h: a table of 2^BITS
+// words and two counters, all filled with all-ones; one insertion per key) and prints "twin_hash TWINS PROBES", PROBES being
+// the longest probe sequence of an insertion.
+//     fbg_host_selftest twin-slots KEYS.bin BITS
+// prints the first slot of every key, one per line.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -18,6 +24,7 @@
 #include "fasta.hpp"
 #include "xgfa.hpp"
 #include "../tie_extent.h"
+#include "../twin_hash.h"
 
 static int tie_extent_selftest()
 {
@@ -63,8 +70,41 @@ static int tie_extent_selftest()
     return 0;
 }
 
+static int twin_hash_selftest(const char *path, int bits, bool slots_only)
+{
+    FILE *fh = std::fopen(path, "rb");
+    if (!fh || bits < 1 || bits > 30) { std::fprintf(stderr, "twin-hash: cannot read %s, or BITS not in 1 .. 30\n", path); return 2; }
+    std::vector<uint64_t> keys;
+    uint64_t k;
+    while (std::fread(&k, 8, 1, fh) == 1) keys.push_back(k);
+    std::fclose(fh);
+    if (slots_only) {
+        for (const uint64_t key : keys) std::printf("%llu\n", (unsigned long long)fbg_twin_slot(key, bits));
+        return 0;
+    }
+    std::vector<uint64_t> table((1ull << bits) + 2, FBG_TWIN_EMPTY);
+    uint64_t *counters = table.data() + (1ull << bits);
+    uint64_t longest = 0;
+    for (const uint64_t key : keys) {
+        if (key == FBG_TWIN_EMPTY) { counters[1]++; continue; }
+        uint64_t probes = 0;
+        counters[0] += fbg_twin_insert(key, bits, [&](uint64_t slot, uint64_t kk) -> uint64_t {
+            if (slot >= (1ull << bits)) { std::fprintf(stderr, "twin-hash: slot %llu beyond the table\n", (unsigned long long)slot); std::exit(1); }
+            probes++;
+            const uint64_t seen = table[slot];
+            if (seen == FBG_TWIN_EMPTY) table[slot] = kk;
+            return seen;
+        });
+        if (probes > longest) longest = probes;
+    }
+    std::printf("twin_hash %llu %llu\n", (unsigned long long)fbg_twin_total(counters[0], counters[1]), (unsigned long long)longest);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 4 && (std::string(argv[1]) == "twin-hash" || std::string(argv[1]) == "twin-slots"))
+        return twin_hash_selftest(argv[2], std::atoi(argv[3]), std::string(argv[1]) == "twin-slots");
     if (argc == 2 && std::string(argv[1]) == "tie-extent") return tie_extent_selftest();
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s FASTA GAP_LIMIT ELASTIC PATHS OUT.gfa [BOUNDARY ...]\n", argv[0]);

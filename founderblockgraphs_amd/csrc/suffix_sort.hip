@@ -22,6 +22,7 @@
 // gaps, lcp.hip recomputes both LCP words for every position instead.
 #include "fbg_internal.h"
 #include "text_cmp.h"
+#include "twin_hash.h"
 #include <rocprim/rocprim.hpp>
 #include <utility>
 #include <cmath>
@@ -182,17 +183,10 @@ static void launch_pack(fbg_ctx *ctx, const KeyGeom &g, bool filter, PackArgs &a
 }
 
 // keys of every stride-th position (same definition as k_pack): splitters and the regime pre-test
-__global__ void k_sample_keys(const uint8_t *__restrict__ T, uint64_t N, const uint8_t *__restrict__ code, int b, int K,
-                              int compact, uint64_t stride, uint64_t S, uint64_t *__restrict__ out)
+__device__ __forceinline__ uint64_t sample_key(const uint8_t *__restrict__ T, uint64_t N, const uint8_t *cd, int b, int K, int compact, uint64_t p)
 {
-    // the code table in LDS, the text 8 bytes at a time (T is zero padded beyond N): K dependent byte loads through
+    // the code table in LDS (cd), the text 8 bytes at a time (T is zero padded beyond N): K dependent byte loads through
     // a table in global memory made this small kernel take 0.3 ms
-    __shared__ uint8_t cd[256];
-    if (threadIdx.x < 256) cd[threadIdx.x] = code[threadIdx.x];
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S) return;
-    const uint64_t p = i * stride;
     uint64_t key = 0;
     bool dead = false;
     for (int k0 = 0; k0 < K; k0 += 8) {
@@ -203,7 +197,44 @@ __global__ void k_sample_keys(const uint8_t *__restrict__ T, uint64_t N, const u
             key = (key << b) | (dead ? 0u : c);
         }
     }
-    out[i] = key;
+    return key;
+}
+
+__global__ void k_sample_keys(const uint8_t *__restrict__ T, uint64_t N, const uint8_t *__restrict__ code, int b, int K,
+                              int compact, uint64_t stride, uint64_t S, uint64_t *__restrict__ out)
+{
+    __shared__ uint8_t cd[256];
+    if (threadIdx.x < 256) cd[threadIdx.x] = code[threadIdx.x];
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S) return;
+    out[i] = sample_key(T, N, cd, b, K, compact, i * stride);
+}
+
+// The same keys, not written out: every thread puts its key into an open-addressing table of 2^bits words (twin_hash.h;
+// filled with all-ones, as are the two counter words behind it) and counts a twin when the key is there already.
+// counters[0] += twins, counters[1] += keys that are all-ones themselves and cannot be stored: one atomic per wave each.
+__global__ __launch_bounds__(256) void k_sample_twins(const uint8_t *__restrict__ T, uint64_t N, const uint8_t *__restrict__ code, int b, int K,
+                                                      int compact, uint64_t stride, uint64_t S, unsigned long long *__restrict__ table, int bits)
+{
+    __shared__ uint8_t cd[256];
+    cd[threadIdx.x] = code[threadIdx.x];
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t twin = 0, ones = 0;
+    if (i < S) {
+        const uint64_t key = sample_key(T, N, cd, b, K, compact, i * stride);
+        if (key == FBG_TWIN_EMPTY) ones = 1;
+        else twin = fbg_twin_insert(key, bits, [&](uint64_t slot, uint64_t k) -> uint64_t {
+            return atomicCAS(&table[slot], (unsigned long long)FBG_TWIN_EMPTY, (unsigned long long)k);
+        });
+    }
+    unsigned long long *counters = table + (1ull << bits);
+    const unsigned long long mt = __ballot(twin), mo = __ballot(ones);
+    if ((threadIdx.x & 63) == 0) {
+        if (mt) atomicAdd(&counters[0], (unsigned long long)__popcll(mt));
+        if (mo) atomicAdd(&counters[1], (unsigned long long)__popcll(mo));
+    }
 }
 
 __global__ void k_count_equal_neighbours(const uint64_t *__restrict__ keys, uint64_t S, unsigned long long *__restrict__ out)
@@ -801,11 +832,64 @@ static int sort_slots(fbg_ctx *ctx, const KeyGeom &g, bool key_flags, uint64_t c
 
 // Rows that resemble each other tie on almost every key: the rank-order scan is not for them.  Cheap look before
 // the sort: twins among the keys of a sample (the exact test follows after the sort, rank_scan.hip).
+//
+// Option twin_hash (default 1): one kernel counts the twins with an open-addressing table (k_sample_twins, twin_hash.h) and
+// the count travels to pinned words of the context; nobody waits.  sample_verdict reads it where the answer is first needed.
+// twin_hash = 0: the sample is written out, sorted by rocPRIM (22 launches) and equal neighbours are counted; the host waits.
+static int sample_launch(fbg_ctx *ctx, const KeyGeom &g, int *launches)
+{
+    const uint64_t N = ctx->N;
+    hipStream_t st = ctx->stream;
+    ctx->twin_pending = false;
+    if (N < (1u << 22)) return FBG_OK;
+    constexpr int LOG_S = 20, BITS = LOG_S + FBG_TWIN_SPARE;
+    const uint64_t S = 1u << LOG_S, stride = N / S;
+    if (!ctx->pin_twins) {
+        FBG_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->pin_twins), 2 * sizeof(unsigned long long), hipHostMallocDefault));
+        FBG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->twin_ev, hipEventDisableTiming));
+    }
+    FBG_TRY(fbg_reserve(ctx, ctx->dp_g, ((1ull << BITS) + 2) * 8));
+    unsigned long long *table = ctx->dp_g.as<unsigned long long>();
+    FBG_HIP_TRY(ctx, hipMemsetAsync(table, 0xff, ((1ull << BITS) + 2) * 8, st));       // the table and its two counters: one fill
+    hipLaunchKernelGGL(k_sample_twins, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, ctx->text.as<uint8_t>(), N, g.d_code, g.b, g.K,
+                       g.compact ? 1 : 0, stride, S, table, BITS);
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->pin_twins, table + (1ull << BITS), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipEventRecord(ctx->twin_ev, st));
+    ctx->twin_pending = true;
+    *launches += 1;
+    return FBG_OK;
+}
+
+static bool twins_say_similar(fbg_ctx *ctx, uint64_t twins)
+{
+    const uint64_t N = ctx->N, S = 1u << 20;
+    ctx->diag.sample_twins = (int64_t)twins;
+    // a suffix with one twin somewhere shows up as a sample twin with probability S/N: estimated tie fraction
+    const double est = (double)twins * (double)N / ((double)S * (double)S);
+    return est > 0.5;
+}
+
+// the answer of the sample sample_launch started (false when the text was too short for one); waits for the count only
+// when the stream has not got that far yet
+static int sample_verdict(fbg_ctx *ctx, bool *similar)
+{
+    *similar = false;
+    if (!ctx->twin_pending) return FBG_OK;
+    ctx->twin_pending = false;
+    FBG_HIP_TRY(ctx, hipEventSynchronize(ctx->twin_ev));
+    *similar = twins_say_similar(ctx, fbg_twin_total(ctx->pin_twins[0], ctx->pin_twins[1]));
+    return FBG_OK;
+}
+
 static int sample_says_similar(fbg_ctx *ctx, const KeyGeom &g, bool *similar, int *launches)
 {
     const uint64_t N = ctx->N;
     hipStream_t st = ctx->stream;
     *similar = false;
+    if (ctx->opt.twin_hash) {
+        FBG_TRY(sample_launch(ctx, g, launches));
+        return sample_verdict(ctx, similar);
+    }
     if (N < (1u << 22)) return FBG_OK;
     const uint64_t S = 1u << 20, stride = N / S;
     FBG_TRY(fbg_reserve(ctx, ctx->dp_g, S * 8));
@@ -823,9 +907,7 @@ static int sample_says_similar(fbg_ctx *ctx, const KeyGeom &g, bool *similar, in
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&twins, d_count, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     *launches += 3;
-    // a suffix with one twin somewhere shows up as a sample twin with probability S/N: estimated tie fraction
-    const double est = (double)twins * (double)N / ((double)S * (double)S);
-    *similar = est > 0.5;
+    *similar = twins_say_similar(ctx, twins);
     return FBG_OK;
 }
 
@@ -847,8 +929,11 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     // both scans read keys in the compact coding (a separator and what follows it count as code 0, rank_scan.hip); a byte
     // below '#' or 128 distinct symbols and more leave the keys in the coding of any alphabet: the record path takes those
     if (ctx->gapfree && !ctx->have_ignore && !ctx->opt.no_ranked && g.compact) {
+        // (nothing before the sort reads the sample's answer: with twin_hash it is fetched behind the sort, which has waited
+        // on the stream by then)
         bool similar = false;
-        FBG_TRY(sample_says_similar(ctx, g, &similar, &launches));
+        if (ctx->opt.twin_hash) FBG_TRY(sample_launch(ctx, g, &launches));
+        else FBG_TRY(sample_says_similar(ctx, g, &similar, &launches));
         // packed slots of a large text: three-pass MSD sort fused with the key packing (msd_sort.hip); else, or when
         // its optimistic bucket capacities do not hold, pack and sort with rocPRIM's onesweep
         uint64_t *sorted = nullptr;
@@ -871,6 +956,7 @@ int fbg_suffix_sort(fbg_ctx *ctx)
             sorted = ctx->keysB.as<uint64_t>();
         }
         uint32_t *svals = g.packed ? nullptr : ctx->valsB.as<uint32_t>();
+        if (ctx->opt.twin_hash) FBG_TRY(sample_verdict(ctx, &similar));
         int done = 0;
         // rows that differ: the scan slot by slot (rank_scan.hip).  Rows that resemble each other (judged from key twins in a
         // sample, or by the slot-level scan itself, which gives up where a quarter of the slots tie): group by group

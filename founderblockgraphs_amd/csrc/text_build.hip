@@ -11,6 +11,7 @@
 // One workgroup sweeps one row in chunks with a running carry, so every load and store is a
 // contiguous stream along the row.
 #include "fbg_internal.h"
+#include <type_traits>
 
 #define TB_THREADS 256
 #define TB_ITEMS 8
@@ -201,6 +202,177 @@ __global__ __launch_bounds__(TB_THREADS) void k_row_count(const uint8_t *__restr
         segcnt[i * gridDim.x + blockIdx.x] = a;                         // non-gap cells of this segment: k_seg_offsets
         atomicAdd(&scalars[0], (unsigned long long)((x_hi > x_lo ? x_hi - x_lo : 0) - a));
         if (b) atomicAdd(&scalars[1], (unsigned long long)b);
+    }
+}
+
+// k_row_count for the MSAs that take its word-wide path in every row and get their optimistic text written along the way
+// (no ignore table, n and the MSA's address multiples of 8; option row_count_fast): same tot, segcnt, scalars[0], hist and
+// text bytes, at a third of the instructions per byte and with 16-byte loads and stores.
+//   * Only the candidates the segment's first 64 bytes showed are tested (DNA: '-' and four symbols), the loop is compiled
+//     for every count of them.
+//   * While every byte of a trip is below 128 (and so is every candidate) a byte of w ^ candidate is below 128 too, so
+//     adding 0x7f to each byte carries nowhere and sets its top bit exactly where the byte differs: xor, add, and, popcount-
+//     and-add per 32-bit word and candidate.  The candidates are distinct, so the bytes of a word that differ sum to
+//     (candidates - 1) * 4 over the candidates exactly when every byte equals one of them: one comparison per trip and wave
+//     instead of a hit mask per word.
+//   * A trip that fails either test (a byte outside the guess, a byte of 128 and more) is counted again word by word with the
+//     exact zero-byte test; its bytes outside the guess go through count(), as in k_row_count.
+// Units past the segment's end read as sixteen '-' (the first candidate) and are taken off its count at the end.
+#define RCF_UNROLL 4
+__global__ __launch_bounds__(TB_THREADS) void k_row_count_fast(const uint8_t *__restrict__ msa, uint64_t n, uint32_t *__restrict__ tot,
+                                                               unsigned long long *__restrict__ scalars,
+                                                               unsigned long long *__restrict__ hist, uint32_t *__restrict__ segcnt,
+                                                               uint8_t *__restrict__ T_copy, uint32_t row0)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef u32x4 u32x4_a8 __attribute__((aligned(8)));                // a row starts at a multiple of 8 bytes, not always of 16
+    typedef u32x4 u32x4_a1 __attribute__((aligned(1)));                // the text's row is shifted by i bytes
+    constexpr int RC_CAND = 6;
+    __shared__ uint32_t red[TB_THREADS / 64];
+    __shared__ uint32_t sh[256];
+    const uint64_t i = (uint64_t)blockIdx.y + row0;
+    const uint8_t *row = msa + i * n;
+    const uint64_t x_lo = (uint64_t)blockIdx.x * RC_SEG, x_hi = min(n, x_lo + RC_SEG);
+    const int lane = threadIdx.x & 63;
+    sh[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t nongap = 0;
+    auto count = [&](uint32_t c, bool valid) {                         // one byte per lane
+        nongap += valid && c != '-';
+        unsigned long long rest = __ballot(valid);
+        while (rest) {
+            const int l = __ffsll((long long)rest) - 1;
+            const uint32_t v = __shfl(c, l, 64);
+            const unsigned long long same = __ballot(valid && c == v);
+            if (lane == l) atomicAdd(&sh[v], (uint32_t)__popcll(same));
+            rest &= ~same;
+        }
+    };
+    uint32_t cand[RC_CAND], pat[RC_CAND], pc[RC_CAND];
+    int nc = 1;                                                         // candidates found ('-' always is one): the same in every wave
+    bool ascii = true;
+    {
+        const uint64_t x = x_lo + lane;
+        uint32_t c = x < x_hi ? (uint32_t)row[x] : 0x100u;
+        cand[0] = '-';
+        unsigned long long rest = __ballot(c < 0x100u && c != '-');
+#pragma unroll
+        for (int k = 1; k < RC_CAND; k++) {
+            cand[k] = 0x100u;                                           // no byte equals 0x100: an unused candidate
+            if (rest) {
+                const int l = __ffsll((long long)rest) - 1;
+                cand[k] = __shfl(c, l, 64);
+                rest &= ~__ballot(c == cand[k]);
+                nc = k + 1;
+                ascii = ascii && cand[k] < 0x80u;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < RC_CAND; k++) { pat[k] = 0x01010101u * (cand[k] & 0xffu); pc[k] = 0; }
+    }
+    const uint8_t *seg = row + x_lo;
+    uint8_t *tseg = T_copy + i * (n + 1) + x_lo;
+    const uint32_t nbytes = x_hi > x_lo ? (uint32_t)(x_hi - x_lo) : 0u, nunits = nbytes / 16;
+    uint32_t inv = 0;                                                   // bytes of units past the end, counted as '-'
+    auto body = [&](auto tag) {
+        constexpr int NC = decltype(tag)::value;
+        for (uint32_t q0 = 0; q0 < nunits; q0 += TB_THREADS * RCF_UNROLL) {     // uniform trip count
+            const uint32_t q = q0 + threadIdx.x;
+            u32x4 wv[RCF_UNROLL];
+#pragma unroll
+            for (int u = 0; u < RCF_UNROLL; u++) {
+                const uint32_t qq = q + (uint32_t)u * TB_THREADS;
+                wv[u] = (u32x4)(0x2d2d2d2du);
+                if (qq < nunits) wv[u] = *reinterpret_cast<const u32x4_a8 *>(seg + 16 * qq);
+            }
+#pragma unroll
+            for (int u = 0; u < RCF_UNROLL; u++) {
+                const uint32_t qq = q + (uint32_t)u * TB_THREADS;
+                if (qq < nunits) *reinterpret_cast<u32x4_a1 *>(tseg + 16 * qq) = wv[u];
+            }
+            uint32_t tm[NC], any = 0, sum = 0;                          // tm[k]: bytes of the trip that differ from candidate k
+#pragma unroll
+            for (int k = 0; k < NC; k++) tm[k] = 0;
+#pragma unroll
+            for (int u = 0; u < RCF_UNROLL; u++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t w = wv[u][j];
+                    any |= w;
+#pragma unroll
+                    for (int k = 0; k < NC; k++) tm[k] += (uint32_t)__popc(((w ^ pat[k]) + 0x7f7f7f7fu) & 0x80808080u);
+                }
+#pragma unroll
+            for (int k = 0; k < NC; k++) sum += tm[k];
+            const bool bad = !ascii || (any & 0x80808080u) != 0 || sum != (uint32_t)(NC - 1) * 16u * RCF_UNROLL;
+            if (!__ballot(bad)) {
+#pragma unroll
+                for (int k = 0; k < NC; k++) pc[k] += 16u * RCF_UNROLL - tm[k];
+#pragma unroll
+                for (int u = 0; u < RCF_UNROLL; u++) inv += q + (uint32_t)u * TB_THREADS < nunits ? 0u : 16u;
+            } else {
+                // (rare: the words are read again, one by one, in loops that stay rolled -- this path is compiled six times)
+#pragma clang loop unroll(disable)
+                for (int u = 0; u < RCF_UNROLL; u++) {
+                    const uint32_t qq = q + (uint32_t)u * TB_THREADS;
+                    const bool valid = qq < nunits;
+#pragma clang loop unroll(disable)
+                    for (int j = 0; j < 4; j++) {
+                        const uint32_t w = valid ? *reinterpret_cast<const uint32_t *>(seg + 16 * qq + 4 * j) : 0u;
+                        uint32_t hit = 0;                               // 0x80 in every byte that equals some candidate
+#pragma unroll
+                        for (int k = 0; k < NC; k++) {
+                            const uint32_t d = w ^ pat[k];
+                            uint32_t z = ~(((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u;      // bytes of d that are 0
+                            if (!valid) z = 0;
+                            pc[k] += (uint32_t)__popc(z);
+                            hit |= z;
+                        }
+                        const bool odd = valid && hit != 0x80808080u;    // a byte outside the guess
+                        if (__ballot(odd)) {
+#pragma clang loop unroll(disable)
+                            for (int bb = 0; bb < 4; bb++) count((w >> (8 * bb)) & 0xffu, odd && !((hit >> (8 * bb + 7)) & 1u));
+                        }
+                    }
+                }
+            }
+        }
+    };
+    switch (nc) {
+    case 1: body(std::integral_constant<int, 1>()); break;
+    case 2: body(std::integral_constant<int, 2>()); break;
+    case 3: body(std::integral_constant<int, 3>()); break;
+    case 4: body(std::integral_constant<int, 4>()); break;
+    case 5: body(std::integral_constant<int, 5>()); break;
+    default: body(std::integral_constant<int, 6>()); break;
+    }
+    pc[0] -= inv;
+#pragma unroll
+    for (int k = 0; k < RC_CAND; k++) {
+        if (k >= nc) break;
+        uint32_t v = pc[k];
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+        if (lane == 0 && v) atomicAdd(&sh[cand[k]], v);
+        if (k > 0) nongap += lane == 0 ? v : 0u;                        // cand[0] is the gap symbol
+    }
+    const uint64_t tail = x_lo + (uint64_t)nunits * 16 + threadIdx.x;  // eight bytes left where the segment is no multiple of 16 (first wave only)
+    if (threadIdx.x < 64) {
+        const bool valid = tail < x_hi;
+        const uint32_t c = valid ? (uint32_t)row[tail] : 0u;
+        if (valid) T_copy[i * (n + 1) + tail] = (uint8_t)c;
+        count(c, valid);
+    }
+    for (int d = 32; d >= 1; d >>= 1) nongap += __shfl_down(nongap, d, 64);
+    if (lane == 0) red[threadIdx.x >> 6] = nongap;
+    __syncthreads();
+    if (sh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)sh[threadIdx.x]);
+    if (threadIdx.x == 1 && x_hi == n) T_copy[i * (n + 1) + n] = '#';
+    if (threadIdx.x == 0) {
+        uint32_t a = 0;
+        for (int k = 0; k < TB_THREADS / 64; k++) a += red[k];
+        atomicAdd(&tot[i], a);
+        segcnt[i * gridDim.x + blockIdx.x] = a;                         // non-gap cells of this segment: k_seg_offsets
+        atomicAdd(&scalars[0], (unsigned long long)(nbytes - a));
     }
 }
 
@@ -414,10 +586,19 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_TEXT));
     int launches = 0;
     FBG_TRY(fbg_reserve(ctx, ctx->pos, m * 4));
-    FBG_TRY(fbg_reserve(ctx, ctx->tot, m * 4));
+    // Option front_one_fill (default 1): the byte histogram and the pass's counts live behind the row totals, so that one fill
+    // clears what the counting pass adds to and one copy brings histogram and counts into pinned words.  0: the histogram in
+    // `small`, the counts in scalars[0..2], a fill each, and two copies -- the counts into a stack array, a staged copy.
+    const bool one_fill = ctx->opt.front_one_fill != 0;
+    const size_t tot_bytes = (m * 4 + 7) & ~(size_t)7, hist_bytes = 256 * sizeof(unsigned long long), cnt_bytes = 8 * sizeof(unsigned long long);
+    FBG_TRY(fbg_reserve(ctx, ctx->tot, tot_bytes + hist_bytes + cnt_bytes));
     FBG_TRY(fbg_reserve(ctx, ctx->scalars, 256 * sizeof(unsigned long long)));
-    FBG_TRY(fbg_reserve(ctx, ctx->small, 8192));   // [0,256) ignore table, [2048,2304) code table, [4096,6144) symbol histogram
-    FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->scalars.p, 0, 64 * sizeof(unsigned long long), st));
+    FBG_TRY(fbg_reserve(ctx, ctx->small, 8192));   // [0,256) ignore table, [2048,2304) code table, [4096,6144) symbol histogram (front_one_fill = 0)
+    if (one_fill) {
+        if (!ctx->pin_front) FBG_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->pin_front), hist_bytes + cnt_bytes, hipHostMallocDefault));
+        FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->tot.p, 0, tot_bytes + hist_bytes + cnt_bytes, st));
+    } else
+        FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->scalars.p, 0, 64 * sizeof(unsigned long long), st));
 
     ctx->have_ignore = ignore_len > 0;
     ctx->cells_built = false;
@@ -426,10 +607,12 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
         for (uint64_t k = 0; k < ignore_len; k++) ctx->ignore_tab[ignore[k]] = 1;   // fbg.cpp:1853,1868
         FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->small.as<uint8_t>(), ctx->ignore_tab, 256, hipMemcpyHostToDevice, st));
     }
-    unsigned long long *sc = ctx->scalars.as<unsigned long long>();
-    unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(ctx->small.as<uint8_t>() + 4096);
-    FBG_HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, 2048, st));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->tot.p, 0, m * 4, st));
+    unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(one_fill ? ctx->tot.as<uint8_t>() + tot_bytes : ctx->small.as<uint8_t>() + 4096);
+    unsigned long long *sc = one_fill ? d_hist + 256 : ctx->scalars.as<unsigned long long>();
+    if (!one_fill) {
+        FBG_HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, 2048, st));
+        FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->tot.p, 0, m * 4, st));
+    }
     const unsigned nseg = (unsigned)((n + RC_SEG - 1) / RC_SEG);
     FBG_TRY(fbg_reserve(ctx, ctx->segtab, (size_t)m * nseg * 4 * 3));   // per (row, segment): non-gap cells, their prefix, first ignore column
     uint32_t *segcnt = ctx->segtab.as<uint32_t>(), *segoff = segcnt + (size_t)m * nseg;
@@ -438,6 +621,19 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
     // written by the counting pass itself from the words it loads (one read of the MSA instead of two)
     const bool fused = !ctx->reversed && n % 8 == 0 && ((uintptr_t)ctx->d_msa & 7) == 0 && m * (n + 1) + 1 < (1ull << 40);
     if (fused) FBG_TRY(fbg_reserve(ctx, ctx->text, m * (n + 1) + 1 + 64));
+    // (the sentinel and the padding behind the optimistic text go with the fill above: the rows end one byte before them)
+    const bool early_sentinel = one_fill && fused;
+    if (early_sentinel) FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->text.as<uint8_t>() + m * (n + 1), 0, 65, st));
+    // the word-wide counting pass that writes the optimistic text: at 16 bytes per lane (k_row_count_fast) or as before
+    const bool fast = fused && ctx->opt.row_count_fast != 0;
+    auto launch_count = [&](unsigned rows, uint32_t r0) {
+        if (fast)
+            hipLaunchKernelGGL(k_row_count_fast, dim3(nseg, rows), dim3(TB_THREADS), 0, st, ctx->d_msa, n, ctx->tot.as<uint32_t>(), sc, d_hist,
+                               segcnt, ctx->text.as<uint8_t>(), r0);
+        else
+            hipLaunchKernelGGL(k_row_count, dim3(nseg, rows), dim3(TB_THREADS), 0, st, ctx->d_msa, n, (const uint8_t *)nullptr,
+                               ctx->tot.as<uint32_t>(), sc, d_hist, segcnt, fused ? ctx->text.as<uint8_t>() : (uint8_t *)nullptr, r0);
+    };
     const uint8_t *up = ctx->up_host;                           // fbg_elastic_f: the MSA is still in (pinned) host memory
     ctx->up_host = nullptr;
     ctx->pre_pass1 = false;
@@ -463,8 +659,7 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
         bool pre = false;
         for (int c = 0; c < CHUNKS; c++) {
             FBG_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->up_ev[c], 0));
-            hipLaunchKernelGGL(k_row_count, dim3(nseg, (unsigned)(r0s[c + 1] - r0s[c])), dim3(TB_THREADS), 0, st, ctx->d_msa,
-                               n, (const uint8_t *)nullptr, ctx->tot.as<uint32_t>(), sc, d_hist, segcnt, ctx->text.as<uint8_t>(), (uint32_t)r0s[c]);
+            launch_count((unsigned)(r0s[c + 1] - r0s[c]), (uint32_t)r0s[c]);
             if (c == 0) {
                 unsigned long long h0[1];
                 FBG_HIP_TRY(ctx, hipMemcpyAsync(h0, sc, sizeof(h0), hipMemcpyDeviceToHost, st));
@@ -476,7 +671,7 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
                     ctx->byte_hist['-'] = 0; ctx->byte_hist['#'] += m; ctx->byte_hist[0] += 1;
                     ctx->N = m * (n + 1) + 1;
                     ctx->gapfree = true;
-                    FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->text.as<uint8_t>() + ctx->N - 1, 0, 65, st));
+                    if (!early_sentinel) FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->text.as<uint8_t>() + ctx->N - 1, 0, 65, st));
                     int ok = 0;
                     FBG_TRY(fbg_msd_pre_begin(ctx, &ok));
                     pre = ok != 0;
@@ -488,16 +683,22 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
         launches += CHUNKS - 1;
     } else {
         if (up) FBG_TRY(fbg_upload(ctx, ctx->msa_own.p, up, m * n));
-        hipLaunchKernelGGL(k_row_count, dim3(nseg, (unsigned)m), dim3(TB_THREADS), 0, st, ctx->d_msa,
-                           n, (const uint8_t *)nullptr, ctx->tot.as<uint32_t>(), sc, d_hist, segcnt, fused ? ctx->text.as<uint8_t>() : (uint8_t *)nullptr);
+        launch_count((unsigned)m, 0);
     }
     hipLaunchKernelGGL(k_row_offsets, dim3(1), dim3(64), 0, st, ctx->tot.as<uint32_t>(), m,
                        ctx->pos.as<uint32_t>(), sc);
     launches += 2;
     unsigned long long h[3];
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(h, sc, sizeof(h), hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->byte_hist, d_hist, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (one_fill) {
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->pin_front, d_hist, hist_bytes + cnt_bytes, hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        memcpy(ctx->byte_hist, ctx->pin_front, hist_bytes);
+        memcpy(h, ctx->pin_front + 256, sizeof(h));
+    } else {
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(h, sc, sizeof(h), hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->byte_hist, d_hist, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
     // symbol histogram of the text: the cells without the gaps, a '#' per row, the sentinel
     ctx->byte_hist['-'] = 0;
     ctx->byte_hist['#'] += m;
@@ -522,8 +723,10 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
 
     const size_t tbytes = ctx->N + 64;
     FBG_TRY(fbg_reserve(ctx, ctx->text, tbytes));
-    // sentinel (the 0 byte sdsl::construct appends) + zero padding for 8-byte compares
-    FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->text.as<uint8_t>() + ctx->N - 1, 0, 65, st));
+    // sentinel (the 0 byte sdsl::construct appends) + zero padding for 8-byte compares (a gap-free MSA that got its optimistic
+    // text has them already)
+    if (!(early_sentinel && ctx->gapfree && ctx->N == m * (n + 1) + 1))
+        FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->text.as<uint8_t>() + ctx->N - 1, 0, 65, st));
     uint8_t *T = ctx->text.as<uint8_t>();
     const uint32_t *pos = ctx->pos.as<uint32_t>(), *tot = ctx->tot.as<uint32_t>();
     if (!ctx->gapfree) {

@@ -139,6 +139,17 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *   tie_sample_loop    0: the sample of the sorted keys before the rank-order scan (k_tie_sample) takes one workgroup per
  *                      cluster of 256 slots (default 1: 512 workgroups walk the clusters and add their counts to global memory
  *                      once each; n > 1: n workgroups, tests); same slots, same sums, same threshold and verdict
+ *   row_count_fast     0: the counting pass over a gap-free candidate MSA whose rows start at multiples of 8 bytes (k_row_count,
+ *                      which also writes the optimistic text) takes 8 bytes per lane and load and tests every word against
+ *                      six candidate symbols with 64-bit arithmetic (default 1: k_row_count_fast -- 16 bytes per lane, load and
+ *                      store, only the candidates the segment's first 64 bytes showed, three instructions per 32-bit word and
+ *                      candidate while all bytes are below 128 and in the guess); same counts, same text
+ *   twin_hash          0: the twins among the 2^20 sampled keys before the sort are counted by sorting the sample (rocPRIM,
+ *                      22 launches) and the host waits for the count (default 1: one kernel puts the keys into an
+ *                      open-addressing table, twin_hash.h, and the count is read behind the sort); same count ("sample_twins")
+ *   front_one_fill     0: the counting pass's row totals, byte histogram and counts are cleared by three fills, come back by two
+ *                      copies, one of them staged, and the text's sentinel is written after the wait (default 1: one fill, one
+ *                      copy into pinned words, the sentinel of a gap-free candidate in front of the counting pass); results unchanged
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
  * fbg_get_option also answers "index_kind" (read-only): -1 no index, 0 per-position records, 1 rank-order scan of a
@@ -161,6 +172,8 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  * "ext_pairs", "text_pairs" (read-only): the tied pairs the lean rank-order scan of the last index build settled from the
  * MSD sort's symbols after the key (msd_ext) / by comparing the text; -1 when no rank-order scan ran, both 0 when it ran
  * without its lean form.
+ * "sample_twins" (read-only): the twins among the keys of the sample drawn before the sort of the last index build (texts
+ * of 2^22 symbols and more: 2^20 keys minus the distinct ones among them); -1 when no sample was drawn.
  * "cand_inversions" (read-only): with cand_sort_check, the places of the last scan's sorted candidate list whose successor
  * is not larger (0 also when the scan had no list to sort); -1 without the option.  "cand_local_sorted" (read-only): 1 when
  * that list was sorted region by region, 0 by the radix sort, -1 when no list was sorted.
