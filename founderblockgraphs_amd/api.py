@@ -580,7 +580,16 @@ class PatternIndex:
         self._eng._chk(self._L.fbg_pindex_align_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("aligned", "unsupported", "too_long", "too_wide", "cells", "max_read", "table_bytes"), (x.value for x in v)))
 
-    def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0):
+    def cigar_stats(self):
+        """{paths, ops, columns, history_bytes, batches} of the last chains(align=True, cigar=True)
+        (fbg_pindex_cigar_stats; an index built with rows=True only): the reads traced, their runs, the sum of
+        t_end - t_start, the bytes of column history that went to device memory (reads of more than 256 symbols) and
+        the batches those reads were worked off in."""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._eng._chk(self._L.fbg_pindex_cigar_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("paths", "ops", "columns", "history_bytes", "batches"), (x.value for x in v)))
+
+    def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -591,7 +600,11 @@ class PatternIndex:
         and .row_set(k).  align=True (an index built with rows=True only): also the edit distance of every read to the
         smallest row that carries its chain, in a window of that row's text pad symbols around the chain's diagonals
         (fbg_pindex_chains_align), as Chains.align_row, .edits, .t_start and .t_end; a read whose window is longer than
-        max_window (0: no limit) is skipped.  After seeds(strands=True) also Chains.best_edits."""
+        max_window (0: no limit) is skipped.  After seeds(strands=True) also Chains.best_edits.  cigar=True (with
+        align=True): also the alignment path of every aligned read (fbg_pindex_chains_cigar and _fetch), as
+        Chains.cigar_off and .cigar_ops, read with .cigar(k) and .cigar_runs(k)."""
+        if cigar and not align:
+            raise ValueError("cigar=True needs align=True")
         if band is not None and band < 0:
             raise ValueError("band must be 0 or more, or None")
         if min_score < 0:
@@ -640,6 +653,13 @@ class PatternIndex:
                 pick = np.where(out.strand[:given] == 1, given, 0) + np.arange(given)
                 out.best_edits = np.where(out.strand[:given] == _lib.STRAND_NONE, np.uint32(_lib.ALIGN_NONE),
                                           out.edits[pick] if given else out.edits[:0]).astype(np.uint32)
+        if cigar:
+            coff = np.zeros(k + 1, dtype=np.uint64)
+            total, ms6 = C.c_uint64(0), C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chains_cigar(self._h, None, C.byref(total), C.byref(ms6)))
+            ops = np.zeros(max(total.value, 1), dtype=np.uint32)
+            self._eng._chk(self._L.fbg_pindex_chains_cigar_fetch(self._h, _u64(coff), ops.ctypes.data_as(_lib.u32p)))
+            out.cigar_off, out.cigar_ops, out.cigar_ms = coff, ops[:total.value], ms6.value
         return out
 
     def chain_stats(self):
@@ -836,6 +856,11 @@ class Chains:
       best_edits      after seeds(strands=True): uint32 per given read, the edits of the strand that strand picked,
                       0xffffffff where strand is 0xff
       align_ms        device time of fbg_pindex_chains_align: the row choice, the windows and the two passes
+    and, asked for with cigar=True beside align=True (None otherwise; include/fbg_hip.h, fbg_pindex_chains_cigar):
+      cigar_off       uint64[k + 1], CSR offsets of the reads' runs; a read without an alignment has none
+      cigar_ops       uint32 per run: length << 4 | code with BAM's codes I = 1, D = 2, = is 7, X = 8, in read order;
+                      cigar(k) gives the string, cigar_runs(k) the (code, length) pairs
+      cigar_ms        device time of fbg_pindex_chains_cigar
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -845,6 +870,18 @@ class Chains:
         self.strand = self.best_score = self.strand_counts = None
         self.n_rows = self.first_row = self.row_bits = None
         self.align_row = self.edits = self.t_start = self.t_end = self.best_edits = self.align_ms = None
+        self.cigar_off = self.cigar_ops = self.cigar_ms = None
+
+    def cigar_runs(self, k):
+        """int64[runs, 2]: (code, length) of the runs of read k's alignment path; no rows without an alignment."""
+        if self.cigar_off is None:
+            raise ValueError("no paths: ask for them with align=True, cigar=True")
+        v = self.cigar_ops[int(self.cigar_off[k]):int(self.cigar_off[k + 1])].astype(np.int64)
+        return np.stack((v & 15, v >> 4), axis=1)
+
+    def cigar(self, k):
+        """The alignment path of read k as a CIGAR string with = and X, such as 25=1X24=; "" without an alignment."""
+        return "".join(f"{n}{_lib.CIGAR_OPS[c]}" for c, n in self.cigar_runs(k).tolist())
 
     def row_set(self, k):
         """int64[n_rows[k]]: the rows that carry the whole chain of read k, ascending."""

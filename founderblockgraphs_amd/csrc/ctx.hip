@@ -228,6 +228,7 @@ static const OptKey g_opt_keys[] = {
     {"row_count_fast", &FbgOptions::row_count_fast},
     {"twin_hash", &FbgOptions::twin_hash},
     {"front_one_fill", &FbgOptions::front_one_fill},
+    {"path_batch_kib", &FbgOptions::path_batch_kib},
 };
 
 // read-only keys of fbg_get_option: what the context and its last build report

@@ -3,7 +3,7 @@
 // place of its .index file:
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
-//              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--align[=PAD]]
+//              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--align[=PAD]] [--cigar]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -50,6 +50,10 @@
 //   G <tab> row <tab> edits <tab> t_start <tab> t_end   the fewest edits, and the stretch [t_start, t_end) of the row's text
 // or `G <tab> *` when there is no alignment (no chain, no row that carries it, a pattern longer than the engine aligns).
 // Without --align no line changes.
+// --cigar (with --align) appends to the G line of every aligned pattern a sixth field, its alignment path against that
+// stretch (fbg_pindex_chains_cigar): runs of = (equal symbols), X (a substitution), I (a pattern symbol with no symbol of
+// the row) and D (a symbol of the row with no pattern symbol) in pattern order, such as 25=1X24=.  `G <tab> *` stays as it
+// is, and without --cigar no line changes.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -68,7 +72,7 @@ static int usage(const char *msg)
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
-              << "                  [--align[=PAD]]\n"
+              << "                  [--align[=PAD]] [--cigar]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -94,7 +98,9 @@ static int usage(const char *msg)
               << "  --align[=PAD]      needs --chain and --rows: after the A lines of a chain a G line: the smallest row that\n"
               << "                     carries the chain, the fewest edits between the pattern and a stretch of that row's\n"
               << "                     gap-stripped text within PAD symbols (default 16) of the chain, and that stretch's start\n"
-              << "                     and end in the row's text, from 0 (G and * if there is no alignment)\n";
+              << "                     and end in the row's text, from 0 (G and * if there is no alignment)\n"
+              << "  --cigar            needs --align: a G line with numbers ends with the alignment path of the pattern against\n"
+              << "                     that stretch, runs of = X I D in pattern order (25=1X24=); no other line changes\n";
     return EXIT_FAILURE;
 }
 
@@ -169,7 +175,7 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement;
-    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false;
+    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false;
     uint64_t pad = 16;
     bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
     uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
@@ -222,6 +228,7 @@ int main(int argc, char **argv)
             band = m;
             continue;
         }
+        if (a == "--cigar") { cigar = true; continue; }
         if (a == "--align") { align = true; continue; }
         if (a.compare(0, 8, "--align=") == 0) {
             const std::string v = a.substr(8);
@@ -243,6 +250,7 @@ int main(int argc, char **argv)
         return usage("--chain needs --seeds, --msa and --occurrences[=M] with M > 0");
     if (strands && !seeds) return usage("--strands needs --seeds");
     if (rows && !(seeds && have_msa)) return usage("--rows needs --seeds and --msa");
+    if (cigar && !align) return usage("--cigar needs --align");
     if (align && !(chain && rows)) return usage("--align needs --chain and --rows");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
@@ -338,6 +346,8 @@ int main(int argc, char **argv)
     std::vector<uint8_t> strand(np + 1, 0);
     std::vector<uint32_t> place_rows[2], chain_rows[2];     // --rows: supporting rows and the first of them
     std::vector<uint32_t> aligned[4];                       // --align: row, edits, t_start, t_end
+    std::vector<uint64_t> cigar_off(nv + 1, 0);             // --cigar: the runs of every virtual read
+    std::vector<uint32_t> cigar_ops;
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -384,6 +394,12 @@ int main(int argc, char **argv)
             for (int k = 0; k < 4; k++) aligned[k].resize(nv + 1);
             rc = fbg_pindex_chains_align(ix, pad, 0, aligned[0].data(), aligned[1].data(), aligned[2].data(), aligned[3].data(), nullptr);
         }
+        if (rc == FBG_OK && cigar) {
+            uint64_t total = 0;
+            rc = fbg_pindex_chains_cigar(ix, nullptr, &total, nullptr);
+            cigar_ops.resize(total + 1);
+            if (rc == FBG_OK) rc = fbg_pindex_chains_cigar_fetch(ix, cigar_off.data(), cigar_ops.data());
+        }
     }
     if (rc == FBG_OK && !occurrences && !seeds)
         rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
@@ -425,8 +441,18 @@ int main(int argc, char **argv)
                     std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]
                               << '\t' << coords[3][anchor_place[i]] << '\n';
                 if (align && aligned[1][v] == FBG_ALIGN_NONE) std::cout << "G\t*\n";
-                else if (align)
-                    std::cout << "G\t" << aligned[0][v] << '\t' << aligned[1][v] << '\t' << aligned[2][v] << '\t' << aligned[3][v] << '\n';
+                else if (align) {
+                    std::cout << "G\t" << aligned[0][v] << '\t' << aligned[1][v] << '\t' << aligned[2][v] << '\t' << aligned[3][v];
+                    if (cigar) {
+                        std::cout << '\t';
+                        for (uint64_t i = cigar_off[v]; i < cigar_off[v + 1]; i++) {
+                            const uint32_t code = cigar_ops[i] & 15;
+                            std::cout << (cigar_ops[i] >> 4)
+                                      << (code == FBG_CIGAR_EQ ? '=' : code == FBG_CIGAR_X ? 'X' : code == FBG_CIGAR_I ? 'I' : 'D');
+                        }
+                    }
+                    std::cout << '\n';
+                }
             }
         };
         for (uint64_t k = 0; k < np; k++) {

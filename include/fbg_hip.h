@@ -152,6 +152,9 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *                      copy into pinned words, the sentinel of a gap-free candidate in front of the counting pass); results unchanged
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
+ *   path_batch_kib     fbg_pindex_chains_cigar: the KiB of column history in device memory that one batch of reads longer
+ *                      than 256 symbols may take (default 2^20, 1 GiB; values below 1 count as 1); a read whose own history
+ *                      is larger is a batch of its own; results unchanged
  * fbg_get_option also answers "index_kind" (read-only): -1 no index, 0 per-position records, 1 rank-order scan of a
  * gap-free MSA, 2 scan in suffix order of an MSA with gaps / ignore characters (slot by slot, or -- "span_scan_used" = 1 --
  * group by group), 3 one partition of a partitioned index.  "span_groups", "span_odd_groups", "span_irregular",
@@ -856,6 +859,58 @@ int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t max_window, u
                             uint32_t *t_start, uint32_t *t_end, double *device_ms);
 int fbg_pindex_align_stats(const fbg_pindex *ix, uint64_t *aligned, uint64_t *unsupported, uint64_t *too_long,
                            uint64_t *too_wide, uint64_t *cells, uint64_t *max_read, uint64_t *table_bytes);
+
+/* The alignment path (CIGAR) of each read that the last fbg_pindex_chains_align aligned (after a successful
+ * fbg_pindex_chains_align since the last fbg_pindex_chains, and so since the last seeds call).
+ *
+ * For a read R with edits[R] != FBG_ALIGN_NONE let P be its text as that call read it (rc(P_R) for a reverse virtual
+ * read), L = |P|, T = G_r[t_start : t_end) and N = |T|.  With unit costs let
+ *   E(i, j) = lev(P[i:], T[j:]):   E(L, j) = N - j,  E(i, N) = L - i,
+ *   E(i, j) = min(E(i+1, j+1) + [P[i] != T[j]], E(i+1, j) + 1, E(i, j+1) + 1),
+ * so that E(0, 0) == edits[R] by the definition of t_start.  The path is the walk from (0, 0) to (L, N) that takes at
+ * every cell the first of these moves that keeps the distance:
+ *   1. the diagonal, if i < L, j < N and E(i, j) == E(i+1, j+1) + [P[i] != T[j]]: op `=` for equal symbols, else `X`;
+ *   2. `I` (a read symbol with no text symbol), if i < L and E(i, j) == E(i+1, j) + 1;
+ *   3. `D` (a text symbol with no read symbol) otherwise.
+ * Among the optimal alignments it is the smallest in the order diagonal < I < D, read from the read's first symbol on.
+ * Equal consecutive ops are merged into runs; a run is one uint32, length << 4 | code, with BAM's codes FBG_CIGAR_I = 1,
+ * FBG_CIGAR_D = 2, FBG_CIGAR_EQ = 7, FBG_CIGAR_X = 8, in the order of P and of ascending positions of the row.  It
+ * follows that #X + #I + #D == edits, #= + #X + #I == L, #= + #X + #D == t_end - t_start, that a read has at most
+ * 2 * edits + 1 runs, and that its first and last run are never D (t_start is the largest start, t_end the smallest
+ * end).  A read without an alignment (empty chain, no carrying row, too long, too wide) has zero runs.
+ *
+ *   fbg_pindex_chains_cigar        n_ops: the number of runs, one entry per read of that align call; *total_ops: their
+ *       sum; *device_ms: device time of the kernels.  Any pointer may be NULL.
+ *   fbg_pindex_chains_cigar_fetch  off[n + 1], the scan of n_ops, and ops[off[n]], the runs back to back: the
+ *       count-then-fetch pattern of fbg_pindex_seeds / _seeds_fetch.  Either may be NULL.
+ *   fbg_pindex_cigar_stats         any pointer may be NULL.  Of the last successful fbg_pindex_chains_cigar (0 before the
+ *       first; a failing call leaves them): the reads traced; the total number of runs; columns, the sum of N;
+ *       history_bytes, the column history that went to device memory and not to LDS; the batches that took.
+ * On the device.  A wave per aligned read runs the second pass of fbg_pindex_chains_align again (the reversed read against
+ * T reversed with D'(0, j) = j, so D'(a, b) = E(L - a, N - b)), over exactly the N columns of T, and keeps the two
+ * vertical-difference words of every 64 read symbols after every column: 16 bytes per word and column.  It then walks
+ * from (L, N) of D' towards (0, 0), which is the walk above from the read's first symbol, so the runs come out in output
+ * order.  The three cell values a step needs come from the stored words: the cell above from the column's bit, the cell
+ * to the left carried along (one row up: less the bit of the column to the left; one column to the left: rebuilt from
+ * D'(0, j) = j and the popcounts of that column's words, one word per lane).  Reads of 1 to 4 words (L <= 256) keep the
+ * history in LDS, one launch per word count sized by the widest T of that count (N <= 2 L: at most 32 KiB); longer reads
+ * up to max_read keep it in scratch of the index, column-major, nw * N * 16 bytes each, and are worked off in batches of
+ * consecutive reads whose history fits option path_batch_kib (a read that alone exceeds it is a batch of its own).
+ * The runs are traced into 2 * edits + 1 slots per read and compacted after a scan of the counts.  Every loop is
+ * bounded (the history by N columns, the trace by L + N steps); a trace that does not arrive writes zero runs and fails
+ * the call with FBG_ERR_HIP.
+ * The calls may be repeated and leave every other state alone, the align results and stats included; like the align call
+ * they still work after a later fbg_pindex_locate or fbg_pindex_occurrences.
+ * Errors, all FBG_ERR_INVALID: a NULL index; an index without the row table; no successful fbg_pindex_chains_align since
+ * the last fbg_pindex_chains; _fetch without a successful _cigar since that align call.  No reads returns FBG_OK. */
+#define FBG_CIGAR_I 1u
+#define FBG_CIGAR_D 2u
+#define FBG_CIGAR_EQ 7u
+#define FBG_CIGAR_X 8u
+int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t *total_ops, double *device_ms);
+int fbg_pindex_chains_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint32_t *ops);
+int fbg_pindex_cigar_stats(const fbg_pindex *ix, uint64_t *paths, uint64_t *ops, uint64_t *columns, uint64_t *history_bytes,
+                           uint64_t *batches);
 
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
