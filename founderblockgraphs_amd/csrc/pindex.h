@@ -1,0 +1,294 @@
+// pindex.h -- what the files of the pattern index (fbg_pindex_*) share: constants, the index object and the state of
+// every stage, the kernel argument structs, three host helpers and the few host functions that cross files.
+//   pindex_build.hip      edge text, suffix array, occ lines, B / E; the preparation from a segmentation; create, destroy
+//   locate.hip            the batched search: locate, occurrences, seeds, and the expansion of places
+//   pindex_validate.hip   the semi-repeat-free check of an index; validation and repair of a segmentation
+//   pindex_chain.hip      co-linear chaining of a read's seeds, strands
+//   pindex_rows.hip       the MSA rows that carry a start place or a chain
+//   pindex_align.hip      edit distance of a read to a row of its chain, and the alignment path
+// Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
+// needs its launch calls a launcher declared at the end of this header.
+#pragma once
+#include "fbg_internal.h"
+#include <algorithm>
+#include <vector>
+
+#define PX_THREADS 256
+#define PX_BLK 128            // BWT positions per occ block
+#define PX_LINE 128           // bytes per occ line
+#define PX_ABSENT 0xffffu     // code of a byte that does not occur in the text
+#define PV_OUT 1u             // node flags of the validation tables: has an out-edge / an in-edge
+#define PV_IN 2u
+#define PV_CSHIFT 8           // the coarse edge table holds the edge of every 2^PV_CSHIFT-th text position
+#define PV_SHORT 16           // ranges of at most this many slots are scanned by one lane, longer ones by a wave
+#define PV_NONE 0xffffffffu   // no witness
+#define PM_W 8                // the MSA coordinate table keeps a running non-gap count every PM_W bitmap words (512 columns)
+#define PM_NONE 0xffffffffu   // a node without a bitmap (no gap in its row's stretch); the coordinate of no cell
+#define PC_SUB 16             // chaining: lanes that share a read of the small tier
+#define PC_SMALL 32           // start places of a read up to which PC_SUB lanes chain it (small_max)
+#define PC_LDS 1024           // start places of a read up to which a wave chains it with its state in LDS (lds_max)
+#define PC_NONE 0xffffffffu   // no predecessor / no chain end
+#define PR_SUB 16             // rows: lanes that share a place (or a chain) when the MSA has at most this many rows
+#define PR_NONE 0xffffffffu   // no node in a (row, block) cell (BG_NONE of block_graph.hip); no supporting row
+#define PA_MAX_READ 1024      // alignment: the longest read fbg_pindex_chains_align takes (max_read), a multiple of 64
+#define PA_REG_WORDS 4        // reads of up to this many 64-symbol words keep the bit-vector state in registers
+#define PA_NONE 0xffffffffu   // FBG_ALIGN_NONE
+#define PG_CTR 13              // counters of fbg_pindex_chains_cigar: traces that failed, reads traced, columns, reads of 1 .. 4
+                              // words and of more, the widest T of each of the five
+
+// What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
+// fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
+// and the places of the last fetch.  Grow-only, on the index's buffer list.
+struct PoState {
+    DevBuf etot, stot, esz, ssz, eoff, soff, rs, el, ss, sk, place;
+    DevBuf msa;               // the rows and columns of the last fbg_pindex_occurrences_msa / _seeds_msa, apart from place
+    bool ready = false;
+    uint64_t n = 0, etotal = 0, stotal = 0;
+};
+
+// fbg_pindex_chains: per start place of the last fbg_pindex_seeds its MSA row and column (col: rows first, a copy apart
+// from sd.msa) and its predecessor; per read the binning keys and ids (before and after the sort), the chain's end
+// place, score and length, the scan of the lengths; the chains (places, then seeds); the spill tier's slab (a uint4 per
+// start place, reserved when a read needs it); the counters of k_pc_key and k_pc_chain.  fbg_pindex_chain_strands: per
+// given read its strand and best score, and the three counters of k_pc_strand.
+struct PcState {
+    DevBuf col, pred, key, id, key2, id2, end, score, len, off, out, slab, ctr;
+    DevBuf strand, best, sctr;
+    bool ready = false;
+    uint64_t n = 0, total = 0, anchors = 0, tier[3] = {0, 0, 0};
+};
+
+// The row table of fbg_pindex_build_segmentation_rows: node_of[nb * m], block-major, and the gathered labels with their
+// offsets (a node without an edge has no copy of its label in the index text).  reads / roff: the reads of the last seeds
+// call, moved aside when a locate or occurrences call is about to overwrite pats / poff (saved).  sbase: per seed the
+// byte of the reads its substring starts at; rec: per start place (node, offset in the node, seed, block) or PR_NONE
+// first; out / cout: what the last fbg_pindex_seeds_rows / _chains_rows copied out; ctr: its count of empty sets.
+struct PrState {
+    DevBuf node_of, labels, loff, reads, roff, sbase, rec, out, cout, ctr;
+    bool saved = false;
+    uint64_t m = 0, label_bytes = 0, read_bytes = 0, places_unsupported = 0, chains_unsupported = 0;
+};
+
+// fbg_pindex_chains_align.  pref: p(r, j) as uint32[nb * m], block-major like node_of, built by the first call.  Per read
+// of the last seeds call: nrows / first (what k_pr_chain leaves: the row choice), info = (row, w0, |W| or 0 where nothing
+// is aligned, L), start = (block, node, offset in the node) at which w0 falls, wlen and its scan woff (n + 1 each), out
+// (row, edits, t_start, t_end: 4 n); win: the windows, back to back; ctr: non-empty chains without a row, reads aligned,
+// too long, too wide, and the cells.  valid: a call has succeeded since the last fbg_pindex_chains, for n reads, and
+// (on_device) left info, woff, win and out for them; not where it returned before its first kernel.
+struct PaState {
+    DevBuf pref, nrows, info, start, wlen, woff, win, out, ctr;
+    bool has_pref = false, valid = false, on_device = false;
+    uint64_t n = 0;
+    uint64_t stat[5] = {0, 0, 0, 0, 0};
+};
+
+// fbg_pindex_chains_cigar.  Per read of the last align call: sz (history units of 8 bytes, then run slots; n + 1 each)
+// and their scans hoff / soff, cnt (runs as u64, n + 1) and its scan off, nops (runs as u32); slots: 2 * edits + 1 runs
+// per aligned read; ops: the runs back to back; hist: the column history of one batch of long reads; ctr: PG_CTR
+// counters.  ready: a call has succeeded since that align call, for n reads and total runs (on_device as above).
+struct PgState {
+    DevBuf sz, hoff, soff, cnt, off, nops, slots, ops, hist, ctr;
+    bool ready = false, on_device = false;
+    uint64_t n = 0, total = 0;
+    uint64_t stat[5] = {0, 0, 0, 0, 0};      // paths, ops, columns, history_bytes, batches
+};
+
+struct fbg_pindex {
+    fbg_ctx *ctx = nullptr;
+    uint64_t N1 = 0;          // text length including the sentinel
+    int sigma = 0;            // distinct symbols of the text
+    bool compact = false;     // sigma <= 16: counts inside the line
+    uint64_t nblk = 0;        // occ blocks: N1 / 128 + 1 (the last one answers occ(c, N1))
+    uint64_t n_nodes = 0;
+    uint32_t nb = 0, ne = 0;
+    DevBuf text, sa, lines, cnt_tab, C, code, bpos, epos;
+    DevBuf pats, poff, okey, oval, okey2, oval2, cnt_out, pos_out, lines_ctr, tmp;
+    // kept for fbg_pindex_validate (not in index_bytes): per node the SA range of its label, a text position of the
+    // label, its length and in / out flags; per distinct edge its text start (E + 1), source and destination; a
+    // coarse table of the edge at every 2^PV_CSHIFT-th text position
+    DevBuf vrng, vtpos, vlen, vflag, vestart, vesrc, vedst, vctab;
+    DevBuf vblock, vstatus, vwn, vwo, vlist, vctr;      // validation scratch, kept between calls
+    // an index built from a segmentation (fbg_pindex_build_segmentation) keeps the block of every node and the first
+    // node of every block; scut / sctr: the flagged cuts and the INVALID count of fbg_segmentation_validate
+    DevBuf snode_block, sfirst, scut, sctr;
+    bool from_segmentation = false;
+    uint64_t seg_nb = 0;
+    // the MSA coordinate table of fbg_pindex_build_segmentation (not in index_bytes, not in table_bytes): mnode, one
+    // uint4 per node (representative row, first column of the block, first unit of the node's bitmap or PM_NONE, width
+    // of the block); mbits, u64 units: per gapped node, for every PM_W bitmap words, the non-gap cells before them and
+    // then those words
+    DevBuf mnode, mbits;
+    bool has_map = false;
+    uint64_t map_units = 0, map_gapped = 0;
+    // fbg_pindex_occurrences: the walk's record per pattern (3 x uint2) and the place state of its patterns;
+    // fbg_pindex_seeds: per pattern the number of reported seeds and its scan, per seed what the walk wrote (the same
+    // record, count, length as u64 for k_po_sizes, q_start, length) and the place state of the seeds.  The two place
+    // states never share a buffer: a fetch of one is not disturbed by a search of the other.
+    DevBuf orec;
+    PoState occ;
+    DevBuf snum, soff, srec, scnt, spos, sq, slen;
+    PoState sd;
+    uint64_t sd_reads = 0;        // reads of the last successful fbg_pindex_seeds (_strands: the 2n virtual reads)
+    bool sd_stranded = false;     // the last seeds call was fbg_pindex_seeds_strands, with sd_reads / 2 given reads
+    DevBuf comp;                  // its complement table (256 bytes)
+    PcState ch;
+    bool has_rows = false;        // built by fbg_pindex_build_segmentation_rows
+    PrState rw;
+    PaState al;
+    PgState cg;
+    uint64_t n_edges = 0, nctab = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, sv0 = nullptr, sv1 = nullptr;   // made with the index (px_new)
+    std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
+    double build_ms = 0, search_ms = 0, validate_ms = 0;
+    uint64_t occ_lines = 0, v_slots = 0, v_wave_nodes = 0;
+};
+
+// not in the library's dynamic symbol table: the host functions of the pattern index that cross files
+#define PX_LOCAL __attribute__((visibility("hidden")))
+
+// Grow-only, on the index's buffer list, outside the context's accounting
+static inline int px_reserve(fbg_pindex *ix, DevBuf &b, size_t bytes) { return fbg_reserve(ix->ctx, b, bytes, &ix->bufs, false); }
+
+template <class F> static int px_with_tmp(fbg_pindex *ix, F &&call)
+{
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e != hipSuccess) return fbg_fail(ix->ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
+    FBG_TRY(px_reserve(ix, ix->tmp, bytes));
+    size_t have = ix->tmp.cap;
+    e = call(ix->tmp.p, have);
+    if (e != hipSuccess)
+        return fbg_fail(ix->ctx, e == hipErrorOutOfMemory ? FBG_ERR_OOM : FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
+    return FBG_OK;
+}
+
+// The device time of a call lies between ev0 and ev1.  The stage records ev0 where its device work starts and calls
+// px_record_end after its last kernel, before it queues the copies to the host, and px_sync_elapsed after them: the
+// stream is waited for and the time between the events goes to *ms (may be NULL).
+static inline int px_record_end(fbg_pindex *ix) { FBG_HIP_TRY(ix->ctx, hipEventRecord(ix->ev1, ix->ctx->stream)); return FBG_OK; }
+static inline int px_sync_elapsed(fbg_pindex *ix, double *ms)
+{
+    FBG_HIP_TRY(ix->ctx, hipStreamSynchronize(ix->ctx->stream));
+    float f = 0;
+    FBG_HIP_TRY(ix->ctx, hipEventElapsedTime(&f, ix->ev0, ix->ev1));
+    if (ms) *ms = f;
+    return FBG_OK;
+}
+
+// ---- kernel arguments ---------------------------------------------------------------------------------------------
+// what the backward steps read (pindex_dev.h)
+struct PxDev {
+    const uint8_t *lines;
+    const uint32_t *cnt_tab;
+    const uint32_t *bpos, *epos;
+    uint32_t N, nb, ne, S;
+};
+
+// the tables of the validation and of the expansion of places
+struct PvDev {
+    const uint32_t *sa, *tpos, *len, *estart, *esrc, *edst, *ctab, *block;
+    const uint2 *rng;
+    const uint8_t *flag, *text;
+};
+
+struct PvMask {
+    uint64_t w[4];
+};
+
+struct PmDev {
+    const uint4 *node;
+    const uint64_t *bits;
+};
+
+// Read R has the seeds seed_off[R] .. seed_off[R + 1] and, as its candidate anchors, their capped start places
+// g0 = start_off[seed_off[R]] .. start_off[seed_off[R + 1]]: the places of earlier seeds first, a seed's places in slot
+// order.  A place whose column is PC_NONE is no anchor; it keeps its slot with best = 0, which no comparison picks.
+struct PcDev {
+    const uint64_t *seed_off, *start_off;
+    const uint32_t *q, *k, *col;
+    uint32_t *pred, *end, *score;
+    uint4 *slab;
+    unsigned long long *ctr;      // 0 .. 3: reads without a start place, of the small, wave and spill tier; 4: anchors
+    uint64_t band;
+};
+
+// Row r supports the start place g of seed t iff g belongs to node u at o < |label(u)|, node_of[r][block(u)] == u, and
+// the read substring S of t equals the row's gap-stripped text from o inside label(u) on.  That text is label(u)[o:]
+// followed by the labels of the row's nodes in the blocks after block(u): cells without a node (the row is all gaps
+// there) are passed over, and the text ends with block nb - 1.
+struct PrDev {
+    const uint32_t *node_of;      // [nb * m], block-major: 64 lanes read 64 consecutive rows of one block
+    const uint8_t *labels;
+    const uint64_t *loff;         // [n_nodes + 1]
+    const uint8_t *reads;
+    const uint64_t *sbase;        // [S] byte of reads at which the seed's substring starts
+    const uint32_t *slen;         // [S]
+    uint64_t m, nb;
+};
+
+// The text of row r is the labels of its nodes in block order, so a position x of G_r lies in the last block j with
+// p(r, j) <= x (a block without a node of the row has p(r, j) == p(r, j + 1) and is never that last one while x < |G_r|).
+struct PaDev {
+    const uint32_t *node_of, *pref;   // [nb * m] each, block-major
+    const uint8_t *labels;
+    const uint64_t *loff;
+    const uint8_t *reads;
+    const uint64_t *roff;             // [n + 1] byte offsets of the (virtual) reads
+    uint64_t m, nb;
+};
+
+static inline PxDev px_dev(const fbg_pindex *ix)
+{
+    PxDev d;
+    d.lines = ix->lines.as<uint8_t>();
+    d.cnt_tab = ix->cnt_tab.as<uint32_t>();
+    d.bpos = ix->bpos.as<uint32_t>();
+    d.epos = ix->epos.as<uint32_t>();
+    d.N = (uint32_t)(ix->N1 - 1);
+    d.nb = ix->nb; d.ne = ix->ne;
+    d.S = (uint32_t)ix->sigma;
+    return d;
+}
+
+// The tables of the validation and of the occurrence expansion.  block is the scratch of fbg_pindex_validate (NULL
+// before its first call): k_po_expand reads sa, estart, esrc, edst and ctab only.
+static inline PvDev pv_dev(const fbg_pindex *ix)
+{
+    PvDev d;
+    d.sa = ix->sa.as<uint32_t>();
+    d.tpos = ix->vtpos.as<uint32_t>();
+    d.len = ix->vlen.as<uint32_t>();
+    d.estart = ix->vestart.as<uint32_t>();
+    d.esrc = ix->vesrc.as<uint32_t>();
+    d.edst = ix->vedst.as<uint32_t>();
+    d.ctab = ix->vctab.as<uint32_t>();
+    d.block = ix->vblock.as<uint32_t>();
+    d.rng = ix->vrng.as<uint2>();
+    d.flag = ix->vflag.as<uint8_t>();
+    d.text = ix->text.as<uint8_t>();
+    return d;
+}
+
+// The scratch of a build; fbg_segmentation_repair keeps one from round to round.
+struct PxScratch {
+    DevBuf labels, loff, elen, eoff, keysA, keysB, valsA, valsB, cidx, cidx2, rank, headv, hscan, head, keep,
+           cntT, cntX, code_u8, count;
+    DevBuf nrow, len64, ebase, firstE, nout, nin, hist;     // px_prepare_segmentation
+    DevBuf munit, muoff, mctr;                              // ... its MSA coordinate table
+    std::vector<DevBuf *> bufs;
+    ~PxScratch() { fbg_release_all(nullptr, bufs); }
+};
+
+// ---- host functions that cross files ---------------------------------------------------------------------------------
+PX_LOCAL int px_new(fbg_ctx *ctx, fbg_pindex **out);       // pindex_build.hip: a new index object with its events
+PX_LOCAL int px_build_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, bool with_map, bool with_rows = false);
+PX_LOCAL void px_destroy(fbg_pindex *ix);
+// locate.hip: k_px_walk<false> over the labels of a build; off[0 .. n] -= base; k_po_expand_msa over one list of s
+PX_LOCAL void px_walk_labels(fbg_pindex *ix, const uint8_t *labels, const uint64_t *loff, uint64_t n_nodes, uint8_t *bflag, uint8_t *eflag);
+PX_LOCAL void px_rebase(hipStream_t st, uint64_t *off, uint64_t n, uint64_t base);
+PX_LOCAL void po_expand_msa(fbg_pindex *ix, const PoState &s, bool starts, uint32_t *orow, uint32_t *ocol);
+// pindex_rows.hip: the last seeds call's reads moved aside; k_pr_seed and k_pr_place (records ev0); k_pr_chain
+PX_LOCAL int pr_save_reads(fbg_pindex *ix);
+PX_LOCAL int pr_prepare(fbg_pindex *ix, PrDev &d);
+PX_LOCAL void pr_chain_launch(fbg_pindex *ix, const PrDev &d, uint64_t n, uint64_t words, uint32_t *n_rows, uint32_t *first_row,
+                              uint64_t *bits, unsigned long long *ctr);

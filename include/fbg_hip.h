@@ -411,7 +411,7 @@ int fbg_group_scan_f(fbg_group *g, const uint8_t *ignore_chars, uint64_t ignore_
 void *fbg_host_alloc(uint64_t bytes);
 void fbg_host_free(void *p);
 
-/* ---- pattern index of a founder graph (locate.hip) ---------------------------------------------------------------
+/* ---- pattern index of a founder graph (pindex.h lists its files) ----------------------------------------------
  *
  * The query side of the reference's founder_block_index (make_index, fbg.cpp:2809-2953; backward_search,
  * founder_block_index.hpp:86-145), built and searched on the GPU.  The graph: n_nodes labels in node id order

@@ -1,5 +1,5 @@
 """The edit distance of each read to a row that carries its chain on one MI355X: fbg_pindex_chains_align beside the
-calls it follows, csrc/locate.hip.
+calls it follows, csrc/pindex_align.hip.
 
 The star_gaps graph of scripts/gpu_rows_bench.py (and with --c3 its c3 graph); reads of 150 symbols cut from the
 gap-stripped rows, every read with two substitutions, every second one with a symbol deleted and every other second one

@@ -1,5 +1,5 @@
 """Co-linear chaining of a read's seeds on one MI355X: fbg_pindex_chains (start columns, binning, the three tiers of
-k_pc_chain, trace, scan, trace) beside the calls it saves the caller, csrc/locate.hip.
+k_pc_chain, trace, scan, trace) beside the calls it saves the caller, csrc/pindex_chain.hip.
 
 The two graphs of scripts/gpu_locate_bench.py, built through fbg_pindex_build_segmentation (chaining needs the MSA
 columns), and the two read batches of scripts/gpu_seeds_bench.py (10^6 reads of 100 symbols: "one_in_ten" with one

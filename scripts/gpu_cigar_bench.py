@@ -1,5 +1,5 @@
 """The alignment path (CIGAR) of each aligned read on one MI355X: fbg_pindex_chains_cigar beside fbg_pindex_chains_align
-for the same reads, csrc/locate.hip.
+for the same reads, csrc/pindex_align.hip.
 
 The star_gaps graph of scripts/gpu_rows_bench.py; reads cut from the gap-stripped rows as in scripts/gpu_align_bench.py
 (two substitutions per read, every second read with a symbol deleted and every other second one with a symbol inserted),

@@ -1,5 +1,5 @@
 """The MSA rows that carry a start place and a chain on one MI355X: fbg_pindex_build_segmentation_rows,
-fbg_pindex_seeds_rows and fbg_pindex_chains_rows beside the calls they follow, csrc/locate.hip.
+fbg_pindex_seeds_rows and fbg_pindex_chains_rows beside the calls they follow, csrc/pindex_rows.hip.
 
 The two graphs and the two read batches of scripts/gpu_chains_bench.py (10^6 reads of 100 symbols: "one_in_ten" with one
 substitution in 10 % of the reads, "two_each" with two in every read), minimum length 12, cap 64, unbounded band.

@@ -1,4 +1,4 @@
-"""Semi-repeat-free check of a founder graph on one MI355X (fbg_pindex_validate, csrc/locate.hip).
+"""Semi-repeat-free check of a founder graph on one MI355X (fbg_pindex_validate, csrc/pindex_validate.hip).
 
 The two graphs of scripts/gpu_locate_bench.py (c3: iid ACGT, 1000 rows x --c3-cols; star: 1000 noisy copies of one
 ancestor with 2 % gap cells in runs of 8, --star-cols), each in two segmentations:

@@ -1,5 +1,5 @@
 """The edit distance of each read to a row that carries its chain: fbg_pindex_chains_align, fbg_pindex_align_stats,
-PatternIndex.chains(align=True) / .align_stats() and fbg_locate --align (include/fbg_hip.h, csrc/locate.hip).
+PatternIndex.chains(align=True) / .align_stats() and fbg_locate --align (include/fbg_hip.h, csrc/pindex_align.hip).
 
 The checker is tests/align_model.py: the window from the row's text and the chain's diagonals, the two DPs of the
 definition cell by cell, and a brute-force minimum over all substrings of the window.  The inputs are those of

@@ -1,6 +1,6 @@
 """Alignment and alignment paths on long edited reads, many rows, many blocks and many reads in one call:
 fbg_pindex_chains_align (k_pa_prefix, k_pa_prepare, k_pa_gather, k_pa_edit) and fbg_pindex_chains_cigar (k_pg_sizes,
-k_pg_path<NW>, k_pg_compact and the host's batch loop) of csrc/locate.hip, between the toy inputs of test_align.py and
+k_pg_path<NW>, k_pg_compact and the host's batch loop) of csrc/pindex_align.hip, between the toy inputs of test_align.py and
 test_cigar.py and the workload of the benchmarks.
 
 The checkers are tests/align_model.py and tests/cigar_model.py on the CPU pipeline of test_mapping_scale.cpu(); every

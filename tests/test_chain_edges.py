@@ -1,4 +1,4 @@
-"""The chaining kernels of csrc/locate.hip (k_pc_key, pc_read in its three tiers of k_pc_chain, k_pc_trace) and the host
+"""The chaining kernels of csrc/pindex_chain.hip (k_pc_key, pc_read in its three tiers of k_pc_chain, k_pc_trace) and the host
 code of fbg_pindex_chains on the branches that tests/test_chains.py does not provably reach: both signs of the surplus on
 either side of the band, places without a column inside reads of the wave and spill tiers, workgroups of the small tier
 one read short of full, full and one read over, many workgroups of the large tiers, min_score at a read's score and
@@ -33,8 +33,8 @@ TIERS = ("small", "wave", "spill")
 
 
 def source_constants():
-    """PX_THREADS, PC_SUB, PC_SMALL and PC_LDS of csrc/locate.hip."""
-    text = open(os.path.join(ROOT, "founderblockgraphs_amd", "csrc", "locate.hip")).read()
+    """PX_THREADS, PC_SUB, PC_SMALL and PC_LDS of csrc/pindex.h."""
+    text = open(os.path.join(ROOT, "founderblockgraphs_amd", "csrc", "pindex.h")).read()
     return {k: int(re.search(r"^#define %s (\d+)\b" % k, text, re.M).group(1)) for k in ("PX_THREADS", "PC_SUB", "PC_SMALL", "PC_LDS")}
 
 

@@ -1,5 +1,5 @@
 """Co-linear chaining of a read's seeds: fbg_pindex_chains / fbg_pindex_chains_fetch / fbg_pindex_chain_stats,
-PatternIndex.chains() / .seeds(chain=True) / .chain_stats() and fbg_locate --chain (include/fbg_hip.h, csrc/locate.hip).
+PatternIndex.chains() / .seeds(chain=True) / .chain_stats() and fbg_locate --chain (include/fbg_hip.h, csrc/pindex_chain.hip).
 
 The checker is tests/chain_model.py: the dynamic programme of the header, statement by statement, applied to what
 PatternIndex.seeds(msa=True) returns (pinned by test_seeds and test_msa_coords).  Every GPU comparison is exact, on

@@ -1,5 +1,5 @@
 """The alignment path (CIGAR) of each aligned read: fbg_pindex_chains_cigar, _cigar_fetch, fbg_pindex_cigar_stats,
-PatternIndex.chains(align=True, cigar=True) / .cigar_stats() and fbg_locate --cigar (include/fbg_hip.h, csrc/locate.hip).
+PatternIndex.chains(align=True, cigar=True) / .cigar_stats() and fbg_locate --cigar (include/fbg_hip.h, csrc/pindex_align.hip).
 
 The checker is tests/cigar_model.py: the suffix DP of the definition as a full matrix, the walk, and an enumeration of
 every optimal alignment.  The inputs are those of tests/test_align.py (and through it of tests/test_rows.py), with the

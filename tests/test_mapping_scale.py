@@ -1,5 +1,5 @@
 """Seeds, MSA coordinates, chains, strands and rows on many rows, blocks and reads in one call: the read-mapping calls of
-the pattern index (include/fbg_hip.h; csrc/locate.hip: k_pr_rows / k_pr_chain, pr_walk, the wave-uniform offset searches,
+the pattern index (include/fbg_hip.h; csrc/locate.hip and csrc/pindex_*.hip: k_pr_rows / k_pr_chain, pr_walk, the wave-uniform offset searches,
 k_px_revcomp, k_pc_key / k_pc_chain, k_pc_strand) between the toy inputs of test_chains.py, test_chain_edges.py,
 test_strands.py and test_rows.py and the workload of scripts/gpu_rows_bench.py.
 

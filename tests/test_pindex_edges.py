@@ -1,4 +1,4 @@
-"""The pattern index and the semi-repeat-free check at their switch points (csrc/locate.hip).
+"""The pattern index and the semi-repeat-free check at their switch points (csrc/pindex_build.hip, locate.hip, pindex_validate.hip).
 
 px_build codes the symbols densely in byte order (the sentinel 0, then '#' unless a label byte sorts below it): at most
 16 codes take the compact occ line (4 bit planes, counts inside), more take 8 planes and a count table; the first

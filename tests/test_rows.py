@@ -1,6 +1,6 @@
 """Which MSA rows carry a start place and a chain: fbg_pindex_build_segmentation_rows, fbg_pindex_seeds_rows,
 fbg_pindex_chains_rows, fbg_pindex_rows_stats, PatternIndex.seeds(rows=True) / .chains(rows=True) / .rows_stats() and
-fbg_locate --rows (include/fbg_hip.h, csrc/locate.hip).
+fbg_locate --rows (include/fbg_hip.h, csrc/pindex_rows.hip).
 
 The checker is tests/rows_model.py: node_of and the sets from the MSA bytes and the boundaries alone, by string
 comparison on gap-stripped rows.  On the CPU every input of the GPU tests goes through seeds_model, chain_model,

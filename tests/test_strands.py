@@ -1,5 +1,5 @@
 """Seeds and chains on both strands: fbg_pindex_seeds_strands / fbg_pindex_chain_strands, PatternIndex.seeds(strands=True),
-Chains.strand / .best() and fbg_locate --strands (include/fbg_hip.h, csrc/locate.hip: k_px_revcomp, k_pc_strand).
+Chains.strand / .best() and fbg_locate --strands (include/fbg_hip.h, csrc/locate.hip: k_px_revcomp; csrc/pindex_chain.hip: k_pc_strand).
 
 The yardstick is the project's own fbg_pindex_seeds / fbg_pindex_chains: a stranded call on n reads must return, array by
 array, what the plain call returns on the 2n reads whose second half strand_model.revcomp made on the host, and that in

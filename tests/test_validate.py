@@ -1,4 +1,4 @@
-"""Semi-repeat-free check of a founder graph (fbg_pindex_validate, csrc/locate.hip, fbg_validate).
+"""Semi-repeat-free check of a founder graph (fbg_pindex_validate, csrc/pindex_validate.hip, fbg_validate).
 
 The checker is tests/validate_model.py: the four rules and the witness restated in the pattern index's terms, pinned on
 CPU against a second, naive formulation and on the example graph of xGFAspec.md.  GPU tests compare status and
