@@ -237,6 +237,8 @@ static const InfoKey g_info_keys[] = {
     {"grs_threshold", [](const fbg_ctx &c) -> int64_t { return c.grs_t; }},
     {"grs_redone", [](const fbg_ctx &c) -> int64_t { return (int64_t)c.grs_redone; }},
     {"dp_kind", [](const fbg_ctx &c) -> int64_t { return c.dp_kind; }},
+    {"dp_attempts", [](const fbg_ctx &c) -> int64_t { return c.dp_attempts; }},
+    {"ne_dp_kind", [](const fbg_ctx &c) -> int64_t { return c.ne_dp_kind; }},
     {"msd_decline", [](const fbg_ctx &c) -> int64_t { return c.diag.msd_decline; }},
     {"pass1_ahead", [](const fbg_ctx &c) -> int64_t { return c.diag.pass1_ahead; }},
     {"ext_pairs", [](const fbg_ctx &c) -> int64_t { return c.diag.ext_pairs; }},

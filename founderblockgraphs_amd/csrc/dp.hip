@@ -1426,6 +1426,7 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
                   uint64_t *d_mml, uint64_t *d_bt)
 {
     hipStream_t st = ctx->stream;
+    ctx->dp_attempts = 0;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_DP));
     const size_t w = (n + 2) * 4;
     FBG_TRY(fbg_reserve(ctx, ctx->dp_a, w));   // e
@@ -1508,6 +1509,7 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
             hipLaunchKernelGGL(k_dpw_blockY, dim3(nblocks), dim3(256), 0, st, ext16, (uint32_t)n, My, Rb);
             for (; WS <= 16384 && !done; WS *= 2) {
                 FBG_HIP_TRY(ctx, hipMemsetAsync(sc + 4, 0, sizeof(unsigned long long), st));
+                ctx->dp_attempts++;
 #define FBG_DPW2(W)                                                                                                                   \
     do {                                                                                                                              \
         const size_t lds = DPW_CHAIN2_LDS(W);                                                                                         \
@@ -1543,6 +1545,7 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
             FBG_TRY(fbg_reserve(ctx, ctx->tmp, mbytes));
             uint16_t *Mw = ctx->tmp.as<uint16_t>();
             FBG_HIP_TRY(ctx, hipMemsetAsync(sc + 4, 0, sizeof(unsigned long long), st));
+            ctx->dp_attempts++;
 #define FBG_DPW(W)                                                                                                                    \
     do {                                                                                                                              \
         hipLaunchKernelGGL((k_dpw_blockM<W>), dim3(nblocks, W / 256), dim3(256), 0, st, ext16, (uint32_t)n, Mw);                       \
@@ -1587,6 +1590,7 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
             if (ctx->opt.dp_safe_window) Rt = R;
             for (; Rt <= 4 && Rt <= R && !settled; Rt *= 2) {
                 const bool tile = Rt == 1 && ctx->opt.dp_tile && f0 == 0;
+                ctx->dp_attempts++;
                 FBG_HIP_TRY(ctx, hipMemsetAsync(sc + 4, 0, sizeof(unsigned long long), st));
                 hipLaunchKernelGGL(k_dp_prep, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, e, (uint32_t)n,
                                    tile ? 127u : 255u, ext7, clen);
@@ -1634,6 +1638,7 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
         }
         if (!settled) FBG_TRY(build_buckets());        // also zeroes what the abandoned attempts left in count / bcount / mml / bt
         if (!settled && f0 == 0 && (R > 4 || ctx->opt.dp_wave)) {
+            ctx->dp_attempts++;
             switch (R) {
             case 1: hipLaunchKernelGGL((k_dp_wave<1>), dim3(1), dim3(64), 0, st, bstart, items, (uint32_t)n, mml, bt, sc); break;
             case 2: hipLaunchKernelGGL((k_dp_wave<2>), dim3(1), dim3(64), 0, st, bstart, items, (uint32_t)n, mml, bt, sc); break;
@@ -1650,6 +1655,7 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
     }
     if (literal) {
         ctx->dp_kind = 0;
+        ctx->dp_attempts++;
         FBG_TRY(build_buckets());
         FBG_HIP_TRY(ctx, hipMemsetAsync(count, 0, w, st));
         FBG_HIP_TRY(ctx, hipMemsetAsync(bcount, 0, w, st));
@@ -1720,13 +1726,17 @@ __global__ void k_ne_prep(const uint64_t *__restrict__ v, uint32_t n, uint8_t *_
     if (jp > n) return;
     ext1[jp] = 1;
     uint32_t am = 255;
+    bool valid = false;
     if (jp >= 1) {
         const uint64_t vj = v[jp - 1];
-        if (vj <= jp - 1) am = (uint32_t)min((uint64_t)255, (uint64_t)jp - vj);
+        valid = vj <= jp - 1;
+        if (valid) am = (uint32_t)min((uint64_t)255, (uint64_t)jp - vj);
     }
     amin[jp] = (uint8_t)am;
-    // longest minimal block, to size the window
-    unsigned long long e = am == 255 ? 0 : am;
+    // longest minimal block, to size the window.  In the byte 255 also says "no valid block ends here", so a minimal block
+    // of 255 columns or more must not reach the matrix path as that byte: it counts with 255 here, which is beyond every
+    // tier (fbg_dp_repeatfree: 2 * 255 + 2 > 254), and the statement-by-statement kernel takes the input
+    unsigned long long e = valid ? am : 0;
     for (int d = 32; d >= 1; d >>= 1) e = max(e, (unsigned long long)__shfl_down(e, d, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(sc + 3, e);
 }
@@ -1774,6 +1784,7 @@ int fbg_dp_repeatfree(fbg_ctx *ctx, const uint64_t *d_v, uint64_t n, uint64_t *d
     unsigned long long *sc = ctx->scalars.as<unsigned long long>() + 16;
     FBG_HIP_TRY(ctx, hipMemsetAsync(sc, 0, 16 * sizeof(unsigned long long), st));
     bool literal = ctx->opt.dp_literal != 0;
+    ctx->ne_dp_kind = 0;
     if (!literal) {
         const size_t w = (n + 2) * 4;
         FBG_TRY(fbg_reserve(ctx, ctx->dp_a, w));
@@ -1820,8 +1831,10 @@ int fbg_dp_repeatfree(fbg_ctx *ctx, const uint64_t *d_v, uint64_t n, uint64_t *d
                                btp, sc);
             FBG_HIP_TRY(ctx, hipMemcpyAsync(hk, sc, sizeof(hk), hipMemcpyDeviceToHost, st));
             FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+            ctx->ne_dp_kind = R;
             if (hk[4] != 0) {
                 literal = true;   // window too small for this input: statement-by-statement kernel
+                ctx->ne_dp_kind = 8;
                 FBG_HIP_TRY(ctx, hipMemsetAsync(sc, 0, 8 * sizeof(unsigned long long), st));
             } else {
                 // no proper segmentation <=> the last prefix has no value (fbg.cpp:648-652)

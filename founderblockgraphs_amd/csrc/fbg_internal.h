@@ -157,6 +157,9 @@ struct fbg_ctx {
     // ---- what outlives a build ----
     int key_b = -1, key_K = -1, key_packed = -1, key_compact = -1;   // geometry of the last key setup (fbg_get_option "key_*")
     int dp_kind = -1;              // which sweep produced the last fbg_dp_minmax result (fbg_get_option "dp_kind")
+    int dp_attempts = 0;           // sweeps fbg_dp_minmax launched until one settled, the literal one included ("dp_attempts")
+    int ne_dp_kind = -1;           // what produced the last fbg_dp_repeatfree result: 0 literal kernel up front, 1 / 2 / 4 the
+                                   // matrix path with that R, 8 the matrix path flagged and the literal kernel redid it ("ne_dp_kind")
     bool grs_skip = false;         // the next build takes the record path: the gapped scan ran out of room (scan.hip)
     bool cells_built = false;      // prow / igrow hold the current MSA (built on demand: only the record path reads them)
     uint64_t held_bytes = 0;

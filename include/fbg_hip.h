@@ -168,6 +168,12 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  * "dp_kind" (read-only): the sweep that produced the last fbg_minmax_dp result: -1 none yet, 0 statement by statement,
  * 1 matrix chain with byte entries (windows up to 256 columns), 2 wave-parallel sweep, 3 .. 7 matrix chain with 16-bit
  * entries over windows of 1024 / 2048 / 4096 / 8192 / 16384 columns.
+ * "dp_attempts" (read-only): the sweeps the last fbg_minmax_dp launched until one settled: every window it tried, and the
+ * statement-by-statement sweep when that ran (1 when the first choice held; 0 before the first call or after a refusal).
+ * "ne_dp_kind" (read-only): what produced the last fbg_repeatfree_dp result: -1 none yet, 0 the statement-by-statement
+ * kernel, chosen up front (dp_literal, or a minimal block of more than 126 columns), 1 / 2 / 4 the matrix chain over
+ * windows of 64 / 128 / 256 columns, 8 the matrix chain met a value its window does not hold and the statement-by-
+ * statement kernel redid the input.
  * "msd_decline" (read-only): the three-pass MSD sort of the last index build: -1 not reached, 0 it sorted the slots, 1 the
  * geometry did not suit it (rocPRIM sorted), else the capacity that did not hold (2 / 4 a stretch of pass 1, 8 the arena
  * of pass 2, 16 a sub-bucket beyond the largest finish).  "pass1_ahead" (read-only): 1 when that sort found its pass 1 done
