@@ -105,6 +105,8 @@ SIGNATURES = {
     "fbg_pindex_seeds_rows": (C.c_int, [vp, u32p, u32p, C.POINTER(C.c_double)]),
     "fbg_pindex_chains_rows": (C.c_int, [vp, u32p, u32p, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_rows_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
+    "fbg_pindex_chains_by_row": (C.c_int, [vp, C.c_uint64, C.c_uint64, u64p, u32p, u32p, u32p, C.POINTER(C.c_double)]),
+    "fbg_pindex_chains_by_row_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "fbg_pindex_chains_align": (C.c_int, [vp, C.c_uint64, C.c_uint64, u32p, u32p, u32p, u32p, C.POINTER(C.c_double)]),
     "fbg_pindex_align_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "fbg_pindex_chains_cigar": (C.c_int, [vp, u32p, u64p, C.POINTER(C.c_double)]),

@@ -518,7 +518,7 @@ class PatternIndex:
         return dict(zip(("rows", "table_bytes", "words_per_set", "places_unsupported", "chains_unsupported"), (x.value for x in v)))
 
     def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False, chain=False, band=None, min_score=0, strands=False,
-              complement=None, rows=False):
+              complement=None, rows=False, by_row=False):
         """Every read cut greedily into the maximal pieces the search accepts (fbg_pindex_seeds, _fetch and _places):
         seeds of at least min_length symbols, each with what occurrences() reports for that substring, at most
         max_per_seed places per seed and list -> Seeds.  msa=True: as for occurrences() (fbg_pindex_seeds_msa).
@@ -527,7 +527,8 @@ class PatternIndex:
         (fbg_pindex_seeds_strands): the Seeds then cover 2k virtual reads, the k given ones and then their k reverse
         complements, and chains() also picks a strand per read.  rows=True (an index built with rows=True only): also,
         per start place, the number of MSA rows that carry it and the smallest of them (fbg_pindex_seeds_rows), as
-        Seeds.start_n_rows / Seeds.start_first_row; with chain=True the chains get their row sets too."""
+        Seeds.start_n_rows / Seeds.start_first_row; with chain=True the chains get their row sets too.  by_row=True
+        (with chain=True): the chains are those of chains(by_row=True)."""
         if min_length < 1:
             raise ValueError("min_length must be 1 or more")
         if max_per_seed < 0:
@@ -569,7 +570,7 @@ class PatternIndex:
             self._eng._chk(self._L.fbg_pindex_seeds_rows(self._h, u32(nr), u32(fr), C.byref(ms5)))
             out.start_n_rows, out.start_first_row, out.rows_ms = nr[:ns], fr[:ns], ms5.value
         if chain:
-            out.chains = self.chains(band=band, min_score=min_score, rows=rows)
+            out.chains = self.chains(band=band, min_score=min_score, rows=rows, by_row=by_row)
         return out
 
     def align_stats(self):
@@ -589,7 +590,7 @@ class PatternIndex:
         self._eng._chk(self._L.fbg_pindex_cigar_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("paths", "ops", "columns", "history_bytes", "batches"), (x.value for x in v)))
 
-    def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False):
+    def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False, by_row=False):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -602,7 +603,10 @@ class PatternIndex:
         (fbg_pindex_chains_align), as Chains.align_row, .edits, .t_start and .t_end; a read whose window is longer than
         max_window (0: no limit) is skipped.  After seeds(strands=True) also Chains.best_edits.  cigar=True (with
         align=True): also the alignment path of every aligned read (fbg_pindex_chains_cigar and _fetch), as
-        Chains.cigar_off and .cigar_ops, read with .cigar(k) and .cigar_runs(k)."""
+        Chains.cigar_off and .cigar_ops, read with .cigar(k) and .cigar_runs(k).  by_row=True (an index built with
+        rows=True only): chain along one MSA row instead (fbg_pindex_chains_by_row): per read the row whose supported
+        anchors chain best, as Chains.chain_row and .n_best_rows, and that row's chain; strands, rows=, align= and cigar=
+        then work on these chains, and every non-empty one has a row to be aligned against."""
         if cigar and not align:
             raise ValueError("cigar=True needs align=True")
         if band is not None and band < 0:
@@ -616,13 +620,21 @@ class PatternIndex:
         score = np.zeros(max(k, 1), dtype=np.uint32)
         ms1, ms2 = C.c_double(0), C.c_double(0)
         b = 0xffffffffffffffff if band is None else min(int(band), 0xffffffffffffffff)
-        self._eng._chk(self._L.fbg_pindex_chains(self._h, b, min(int(min_score), 0xffffffffffffffff), _u64(chain_off),
-                                                 score.ctypes.data_as(_lib.u32p), C.byref(ms1)))
+        if by_row:
+            crow, nbest = np.zeros(max(k, 1), dtype=np.uint32), np.zeros(max(k, 1), dtype=np.uint32)
+            self._eng._chk(self._L.fbg_pindex_chains_by_row(self._h, b, min(int(min_score), 0xffffffffffffffff), _u64(chain_off),
+                                                            score.ctypes.data_as(_lib.u32p), crow.ctypes.data_as(_lib.u32p),
+                                                            nbest.ctypes.data_as(_lib.u32p), C.byref(ms1)))
+        else:
+            self._eng._chk(self._L.fbg_pindex_chains(self._h, b, min(int(min_score), 0xffffffffffffffff), _u64(chain_off),
+                                                     score.ctypes.data_as(_lib.u32p), C.byref(ms1)))
         t = int(chain_off[k])
         place, seed = np.zeros(max(t, 1), dtype=np.uint32), np.zeros(max(t, 1), dtype=np.uint32)
         self._eng._chk(self._L.fbg_pindex_chains_fetch(self._h, place.ctypes.data_as(_lib.u32p), seed.ctypes.data_as(_lib.u32p),
                                                        C.byref(ms2)))
         out = Chains(chain_off, score[:k], place[:t], seed[:t], ms1.value, ms2.value)
+        if by_row:
+            out.chain_row, out.n_best_rows, out.by_row = crow[:k], nbest[:k], True
         given = getattr(self, "_seed_given", None)
         if given is not None:
             strand, best = np.zeros(max(given, 1), dtype=np.uint8), np.zeros(max(given, 1), dtype=np.uint32)
@@ -661,6 +673,14 @@ class PatternIndex:
             self._eng._chk(self._L.fbg_pindex_chains_cigar_fetch(self._h, _u64(coff), ops.ctypes.data_as(_lib.u32p)))
             out.cigar_off, out.cigar_ops, out.cigar_ms = coff, ops[:total.value], ms6.value
         return out
+
+    def by_row_stats(self):
+        """{reads_lds, reads_device, reads_too_many, reads_no_row, anchors_kept, lds_max, max_places} of the last
+        chains(by_row=True): see fbg_pindex_chains_by_row_stats."""
+        v = [C.c_uint64(0) for _ in range(7)]
+        self._eng._chk(self._L.fbg_pindex_chains_by_row_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("reads_lds", "reads_device", "reads_too_many", "reads_no_row", "anchors_kept", "lds_max", "max_places"),
+                        (x.value for x in v)))
 
     def chain_stats(self):
         """{anchors, reads_small, reads_wave, reads_spill, small_max, lds_max}: see fbg_pindex_chain_stats."""
@@ -843,6 +863,10 @@ class Chains:
                       the chain of that strand is empty
       best_score      uint32 per read: the larger of the two scores
       strand_counts   {forward, reverse, none}: the reads by outcome
+    and, asked for with by_row=True (by_row False and the arrays None otherwise; include/fbg_hip.h, fbg_pindex_chains_by_row):
+      chain_row       uint32 per read: the smallest MSA row whose supported anchors chain best, 0xffffffff where no row
+                      supports an anchor; the chain and the score are then those along this row
+      n_best_rows     uint32 per read: how many rows reach that score
     and, asked for with rows=True (None otherwise):
       n_rows, first_row   uint32 per read: how many MSA rows carry every anchor of its chain, and the smallest of them
                       (0 and 0xffffffff for an empty chain, and for one whose anchors no single row carries)
@@ -869,6 +893,8 @@ class Chains:
         self.device_ms, self.fetch_ms = device_ms, fetch_ms
         self.strand = self.best_score = self.strand_counts = None
         self.n_rows = self.first_row = self.row_bits = None
+        self.chain_row = self.n_best_rows = None
+        self.by_row = False
         self.align_row = self.edits = self.t_start = self.t_end = self.best_edits = self.align_ms = None
         self.cigar_off = self.cigar_ops = self.cigar_ms = None
 

@@ -229,6 +229,8 @@ static const OptKey g_opt_keys[] = {
     {"twin_hash", &FbgOptions::twin_hash},
     {"front_one_fill", &FbgOptions::front_one_fill},
     {"path_batch_kib", &FbgOptions::path_batch_kib},
+    {"byrow_max", &FbgOptions::byrow_max},
+    {"byrow_lds", &FbgOptions::byrow_lds},
 };
 
 // read-only keys of fbg_get_option: what the context and its last build report

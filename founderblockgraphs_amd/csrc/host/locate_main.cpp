@@ -3,7 +3,7 @@
 // place of its .index file:
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
-//              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--align[=PAD]] [--cigar]
+//              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--by-row] [--align[=PAD]] [--cigar]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -44,6 +44,10 @@
 // `<tab> rows <tab> first` to every B line of a seed and to every C line: how many MSA rows carry the seed from that place
 // on, or every anchor of the chain, and the smallest of them, from 0 (fbg_pindex_seeds_rows / _chains_rows; `*` for first
 // when there is none: a place or chain that only a recombinant path of the graph spells).  Without --rows no line changes.
+// --by-row (with --chain and --rows) chains every pattern along one MSA row instead (fbg_pindex_chains_by_row): the row
+// whose supported start places chain best, the smallest among equals, and that row's chain.  Every C line then ends with
+// `<tab> row <tab> n_best_rows`, the chosen row and the number of rows that reach its score (`*` and 0 where no row
+// supports a start place); the C / A / T / G lines are those of these chains.  Without --by-row no byte changes.
 // --align[=PAD] (with --chain and --rows) aligns every pattern against the smallest row that carries its chain, in a window
 // of that row's gap-stripped text PAD symbols (default 16) around the chain's diagonals (fbg_pindex_chains_align), and
 // prints after the A lines of a chain
@@ -72,7 +76,7 @@ static int usage(const char *msg)
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
-              << "                  [--align[=PAD]] [--cigar]\n"
+              << "                  [--by-row] [--align[=PAD]] [--cigar]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -95,6 +99,9 @@ static int usage(const char *msg)
               << "                     of MSA rows that carry the seed from that place on (the C line: every anchor of the\n"
               << "                     chain) and the smallest such row, from 0 (* if no row does: only a recombinant path\n"
               << "                     of the graph spells it); no other line changes\n"
+              << "  --by-row           needs --chain and --rows: chain every pattern along the one MSA row whose supported\n"
+              << "                     start places chain best (the smallest among equals); every C line ends with that row\n"
+              << "                     and the number of rows that reach its score (* and 0 if no row supports a place)\n"
               << "  --align[=PAD]      needs --chain and --rows: after the A lines of a chain a G line: the smallest row that\n"
               << "                     carries the chain, the fewest edits between the pattern and a stretch of that row's\n"
               << "                     gap-stripped text within PAD symbols (default 16) of the chain, and that stretch's start\n"
@@ -175,7 +182,7 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement;
-    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false;
+    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false;
     uint64_t pad = 16;
     bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
     uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
@@ -191,6 +198,7 @@ int main(int argc, char **argv)
             value("--msa", msa_path, have_msa) || value("--complement", complement, have_complement)) continue;
         if (a == "--strands") { strands = true; continue; }
         if (a == "--rows") { rows = true; continue; }
+        if (a == "--by-row") { by_row = true; continue; }
         if (a == "--error-on-not-found") { error_on_not_found = true; continue; }
         if (a == "--occurrences") { occurrences = true; continue; }
         if (a.compare(0, 14, "--occurrences=") == 0) {
@@ -250,6 +258,7 @@ int main(int argc, char **argv)
         return usage("--chain needs --seeds, --msa and --occurrences[=M] with M > 0");
     if (strands && !seeds) return usage("--strands needs --seeds");
     if (rows && !(seeds && have_msa)) return usage("--rows needs --seeds and --msa");
+    if (by_row && !(chain && rows)) return usage("--by-row needs --chain and --rows");
     if (cigar && !align) return usage("--cigar needs --align");
     if (align && !(chain && rows)) return usage("--align needs --chain and --rows");
     if (have_complement && !strands) return usage("--complement needs --strands");
@@ -345,6 +354,7 @@ int main(int argc, char **argv)
     std::vector<uint32_t> chain_score(nv + 1, 0), anchor_place, anchor_seed, best_score(np + 1, 0);
     std::vector<uint8_t> strand(np + 1, 0);
     std::vector<uint32_t> place_rows[2], chain_rows[2];     // --rows: supporting rows and the first of them
+    std::vector<uint32_t> chosen[2];                        // --by-row: the chosen row and the rows that reach its score
     std::vector<uint32_t> aligned[4];                       // --align: row, edits, t_start, t_end
     std::vector<uint64_t> cigar_off(nv + 1, 0);             // --cigar: the runs of every virtual read
     std::vector<uint32_t> cigar_ops;
@@ -374,7 +384,10 @@ int main(int argc, char **argv)
             for (int k = 0; k < 4; k++) coords[k].resize((k < 2 ? end_off[ns] : start_off[ns]) + 1);
             rc = fbg_pindex_seeds_msa(ix, coords[0].data(), coords[1].data(), coords[2].data(), coords[3].data(), nullptr);
         }
-        if (rc == FBG_OK && chain) rc = fbg_pindex_chains(ix, band, 0, chain_off.data(), chain_score.data(), nullptr);
+        if (rc == FBG_OK && chain && by_row) {
+            for (int k = 0; k < 2; k++) chosen[k].resize(nv + 1);
+            rc = fbg_pindex_chains_by_row(ix, band, 0, chain_off.data(), chain_score.data(), chosen[0].data(), chosen[1].data(), nullptr);
+        } else if (rc == FBG_OK && chain) rc = fbg_pindex_chains(ix, band, 0, chain_off.data(), chain_score.data(), nullptr);
         if (rc == FBG_OK && chain) {
             anchor_place.resize(chain_off[nv] + 1);
             anchor_seed.resize(chain_off[nv] + 1);
@@ -436,6 +449,11 @@ int main(int argc, char **argv)
             if (chain) {
                 std::cout << "C\t" << chain_score[v] << '\t' << chain_off[v + 1] - chain_off[v];
                 if (rows) print_row_set(chain_rows[0][v], chain_rows[1][v]);
+                if (by_row) {
+                    if (chosen[0][v] == 0xffffffffu) std::cout << "\t*";
+                    else std::cout << '\t' << chosen[0][v];
+                    std::cout << '\t' << chosen[1][v];
+                }
                 std::cout << '\n';
                 for (uint64_t i = chain_off[v]; i < chain_off[v + 1]; i++)
                     std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]

@@ -5,6 +5,7 @@
 //   pindex_validate.hip   the semi-repeat-free check of an index; validation and repair of a segmentation
 //   pindex_chain.hip      co-linear chaining of a read's seeds, strands
 //   pindex_rows.hip       the MSA rows that carry a start place or a chain
+//   pindex_byrow.hip      chaining along one row: per read the row whose supported anchors chain best
 //   pindex_align.hip      edit distance of a read to a row of its chain, and the alignment path
 // Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
 // needs its launch calls a launcher declared at the end of this header.
@@ -30,6 +31,10 @@
 #define PC_NONE 0xffffffffu   // no predecessor / no chain end
 #define PR_SUB 16             // rows: lanes that share a place (or a chain) when the MSA has at most this many rows
 #define PR_NONE 0xffffffffu   // no node in a (row, block) cell (BG_NONE of block_graph.hip); no supporting row
+#define PB_LDS 32             // chaining by row: start places of a read up to which its state stays in LDS (lds_max)
+#define PB_PLACE 280          // ... bytes of that state per start place: a record, a support word, 64 scores
+#define PB_CTR 7              // ... counters: reads without a place, of the LDS tier, of the device tier, with too many;
+                              // places of the device tier; reads with an anchor and no row; places kept by the mask
 #define PA_MAX_READ 1024      // alignment: the longest read fbg_pindex_chains_align takes (max_read), a multiple of 64
 #define PA_REG_WORDS 4        // reads of up to this many 64-symbol words keep the bit-vector state in registers
 #define PA_NONE 0xffffffffu   // FBG_ALIGN_NONE
@@ -93,6 +98,16 @@ struct PgState {
     uint64_t stat[5] = {0, 0, 0, 0, 0};      // paths, ops, columns, history_bytes, batches
 };
 
+// fbg_pindex_chains_by_row.  Per read of the last seeds call: row, score and nbest (what k_pb_score leaves), the binning
+// keys and ids before and after the sort; doff: the scan of the device tier's place counts, slab: that tier's state
+// (PB_PLACE bytes per place, reserved when a read needs it); col2: the start columns under the mask of the chosen rows,
+// which the chain DP runs on; ctr: PB_CTR counters.  ready: a call has succeeded since the last seeds or plain chains call.
+struct PbState {
+    DevBuf row, score, nbest, key, id, key2, id2, doff, slab, col2, ctr;
+    bool ready = false;
+    uint64_t stat[5] = {0, 0, 0, 0, 0};      // reads_lds, reads_device, reads_too_many, reads_no_row, anchors_kept
+};
+
 struct fbg_pindex {
     fbg_ctx *ctx = nullptr;
     uint64_t N1 = 0;          // text length including the sentinel
@@ -136,6 +151,7 @@ struct fbg_pindex {
     PrState rw;
     PaState al;
     PgState cg;
+    PbState pb;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, sv0 = nullptr, sv1 = nullptr;   // made with the index (px_new)
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -226,6 +242,18 @@ struct PrDev {
     uint64_t m, nb;
 };
 
+// Chaining by row.  Read R has the start places g0 = start_off[seed_off[R]] .. start_off[seed_off[R + 1]] as in PcDev;
+// col: their start columns (PC_NONE: no anchor), rec: what k_pr_place left per place.  lds / max: the place counts up to
+// which a read goes to the LDS tier / is chained at all.
+struct PbDev {
+    const uint64_t *seed_off, *start_off;
+    const uint32_t *q, *k, *col;
+    const uint4 *rec;
+    uint32_t *row, *score, *nbest;
+    unsigned long long *ctr;      // PB_CTR counters
+    uint64_t band, lds, max;
+};
+
 // The text of row r is the labels of its nodes in block order, so a position x of G_r lies in the last block j with
 // p(r, j) <= x (a block without a node of the row has p(r, j) == p(r, j + 1) and is never that last one while x < |G_r|).
 struct PaDev {
@@ -287,6 +315,14 @@ PX_LOCAL void px_destroy(fbg_pindex *ix);
 PX_LOCAL void px_walk_labels(fbg_pindex *ix, const uint8_t *labels, const uint64_t *loff, uint64_t n_nodes, uint8_t *bflag, uint8_t *eflag);
 PX_LOCAL void px_rebase(hipStream_t st, uint64_t *off, uint64_t n, uint64_t base);
 PX_LOCAL void po_expand_msa(fbg_pindex *ix, const PoState &s, bool starts, uint32_t *orow, uint32_t *ocol);
+// pindex_chain.hip: the checks that fbg_pindex_chains and fbg_pindex_chains_by_row share (what: the caller's name); the
+// chain state's buffers for n reads, S seeds and A start places, and d filled for the columns col; then, on those columns,
+// k_pc_key, the sort, the host's look at the bins (bin[0 .. 4)), k_pc_chain per tier, k_pc_trace, the scan, k_pc_trace;
+// and what ends either call after px_sync_elapsed: the limit on chain_off[n], the statistics (bin[4]: the anchors)
+PX_LOCAL int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *device_ms, const char *what, bool *go);
+PX_LOCAL int pc_reserve(fbg_pindex *ix, PcDev &d, const uint32_t *col, uint64_t band);
+PX_LOCAL int pc_launch(fbg_pindex *ix, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what);
+PX_LOCAL int pc_finish(fbg_pindex *ix, const uint64_t *chain_off, const uint64_t bin[5], const char *what);
 // pindex_rows.hip: the last seeds call's reads moved aside; k_pr_seed and k_pr_place (records ev0); k_pr_chain
 PX_LOCAL int pr_save_reads(fbg_pindex *ix);
 PX_LOCAL int pr_prepare(fbg_pindex *ix, PrDev &d);

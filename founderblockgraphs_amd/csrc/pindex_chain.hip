@@ -26,14 +26,6 @@ __global__ void k_pc_key(PcDev d, uint64_t n, uint32_t *key, uint32_t *id)
     }
 }
 
-// what a seed's lanes wrote becomes visible to the lanes of the same wave that scan it for the next seed
-__device__ __forceinline__ void pc_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // The DP of one read on G lanes (lane = 0 .. G - 1), state st[0 .. places of the read) = (best, column, q_start, length).
 // Seed by seed: the lanes take the seed's places G at a time, each scans the state of all earlier seeds' places in
 // ascending order -- every lane reads the same entry, a broadcast -- and keeps the first of the best predecessors; the
@@ -163,20 +155,24 @@ __global__ void k_pc_strand(const uint32_t *score, const uint64_t *len, uint64_t
 // The start columns of the seeds' places (k_po_expand_msa<true> into the chain state's own buffer), the reads sorted by
 // their number of start places, the host's look at the four bin sizes, one k_pc_chain launch per tier that has reads,
 // then count, scan and write as the seeds do.  A chain has at most one anchor per seed: S entries hold every chain.
-extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_score, uint64_t *chain_off, uint32_t *score,
-                                 double *device_ms)
+// fbg_pindex_chains_by_row (pindex_byrow.hip) runs the same steps on columns of its own, so they are four functions:
+// pc_begin, pc_reserve, pc_launch and pc_finish (pindex.h).
+
+// The checks and trivial cases of a chaining call (what: its name).  *go: there is something to launch.
+int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *device_ms, const char *what, bool *go)
 {
-    if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
     PcState &c = ix->ch;
     const PoState &s = ix->sd;
+    *go = false;
     c.ready = false;
+    ix->pb.ready = false;
     ix->al.valid = ix->cg.ready = false;      // the alignment and its paths belong to the chains
     if (device_ms) *device_ms = 0;
-    if (!chain_off) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains: missing chain_off");
+    if (!chain_off) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing chain_off", what);
     if (!ix->from_segmentation || !ix->has_map)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains: only an index built by fbg_pindex_build_segmentation knows MSA columns");
-    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains: no fbg_pindex_seeds result to chain");
+        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation knows MSA columns", what);
+    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no fbg_pindex_seeds result to chain", what);
     const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
     c.n = n;
     c.total = c.anchors = 0;
@@ -184,39 +180,50 @@ extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_sco
     std::fill(chain_off, chain_off + n + 1, (uint64_t)0);
     if (score) std::fill(score, score + n, (uint32_t)0);
     if (n == 0 || S == 0 || A == 0) { c.ready = true; return FBG_OK; }   // no start place: every score 0, every chain empty
-    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    *go = true;
+    return FBG_OK;
+}
+
+int pc_reserve(fbg_pindex *ix, PcDev &d, const uint32_t *col, uint64_t band)
+{
+    PcState &c = ix->ch;
+    const PoState &s = ix->sd;
+    const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
     FBG_TRY(px_reserve(ix, c.col, 2 * A * 4));
     FBG_TRY(px_reserve(ix, c.pred, A * 4));
     for (DevBuf *b : {&c.key, &c.id, &c.key2, &c.id2, &c.end, &c.score}) FBG_TRY(px_reserve(ix, *b, n * 4));
     for (DevBuf *b : {&c.len, &c.off}) FBG_TRY(px_reserve(ix, *b, (n + 1) * 8));
     FBG_TRY(px_reserve(ix, c.out, 2 * S * 4));
     FBG_TRY(px_reserve(ix, c.ctr, 5 * 8));
-    PcDev d;
     d.seed_off = ix->soff.as<uint64_t>();
     d.start_off = s.soff.as<uint64_t>();
     d.q = ix->sq.as<uint32_t>();
     d.k = ix->slen.as<uint32_t>();
-    d.col = c.col.as<uint32_t>() + A;
+    d.col = col ? col : c.col.as<uint32_t>() + A;
     d.pred = c.pred.as<uint32_t>();
     d.end = c.end.as<uint32_t>();
     d.score = c.score.as<uint32_t>();
     d.slab = nullptr;
     d.ctr = c.ctr.as<unsigned long long>();
     d.band = band;
-    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(c.ctr.p, 0, 5 * 8, st));
-    po_expand_msa(ix, s, true, c.col.as<uint32_t>(), c.col.as<uint32_t>() + A);
+    return FBG_OK;
+}
+
+int pc_launch(fbg_pindex *ix, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what)
+{
+    fbg_ctx *ctx = ix->ctx;
+    hipStream_t st = ctx->stream;
+    PcState &c = ix->ch;
+    const uint64_t n = ix->sd_reads, S = ix->sd.n, A = ix->sd.stotal;
     uint32_t *ka = c.key.as<uint32_t>(), *va = c.id.as<uint32_t>(), *kb = c.key2.as<uint32_t>(), *vb = c.id2.as<uint32_t>();
     hipLaunchKernelGGL(k_pc_key, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, d, n, ka, va);
     FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
         return rocprim::radix_sort_pairs(tmp, bytes, ka, kb, va, vb, (size_t)n, 0u, 32u, st);
     }));
     FBG_HIP_TRY(ctx, hipGetLastError());
-    uint64_t bin[5] = {0, 0, 0, 0, 0};
     FBG_HIP_TRY(ctx, hipMemcpyAsync(bin, c.ctr.p, 4 * 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (bin[0] + bin[1] + bin[2] + bin[3] != n) return fbg_fail(ctx, FBG_ERR_HIP, "fbg_pindex_chains: the tiers hold %llu of %llu reads",
+    if (bin[0] + bin[1] + bin[2] + bin[3] != n) return fbg_fail(ctx, FBG_ERR_HIP, "%s: the tiers hold %llu of %llu reads", what,
                                                                 (unsigned long long)(bin[0] + bin[1] + bin[2] + bin[3]), (unsigned long long)n);
     if (bin[3]) {
         FBG_TRY(px_reserve(ix, c.slab, A * 16));
@@ -235,14 +242,16 @@ extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_sco
     }));
     hipLaunchKernelGGL(k_pc_trace<true>, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, d, n, min_score, len, (const uint64_t *)off, out, out + S);
     FBG_HIP_TRY(ctx, hipGetLastError());
-    FBG_TRY(px_record_end(ix));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(chain_off, off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (score) FBG_HIP_TRY(ctx, hipMemcpyAsync(score, c.score.p, n * 4, hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(&bin[4], d.ctr + 4, 8, hipMemcpyDeviceToHost, st));
-    FBG_TRY(px_sync_elapsed(ix, device_ms));
+    return FBG_OK;
+}
+
+int pc_finish(fbg_pindex *ix, const uint64_t *chain_off, const uint64_t bin[5], const char *what)
+{
+    PcState &c = ix->ch;
+    const uint64_t n = c.n;
     // a chain takes one place per seed at most, and a call has fewer than 2^32 seeds
     if (chain_off[n] >= (1ull << 32))
-        return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_chains: %llu chain entries; a call takes fewer than 2^32", (unsigned long long)chain_off[n]);
+        return fbg_fail(ix->ctx, FBG_ERR_TOO_LARGE, "%s: %llu chain entries; a call takes fewer than 2^32", what, (unsigned long long)chain_off[n]);
     c.total = chain_off[n];
     c.anchors = bin[4];
     c.tier[0] = bin[1];
@@ -250,6 +259,34 @@ extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_sco
     c.tier[2] = bin[3];
     c.ready = true;
     return FBG_OK;
+}
+
+extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_score, uint64_t *chain_off, uint32_t *score,
+                                 double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    fbg_ctx *ctx = ix->ctx;
+    PcState &c = ix->ch;
+    const PoState &s = ix->sd;
+    bool go = false;
+    FBG_TRY(pc_begin(ix, chain_off, score, device_ms, "fbg_pindex_chains", &go));
+    if (!go) return FBG_OK;
+    const uint64_t n = ix->sd_reads, A = s.stotal;
+    FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    PcDev d;
+    FBG_TRY(pc_reserve(ix, d, nullptr, band));
+    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(c.ctr.p, 0, 5 * 8, st));
+    po_expand_msa(ix, s, true, c.col.as<uint32_t>(), c.col.as<uint32_t>() + A);
+    uint64_t bin[5] = {0, 0, 0, 0, 0};
+    FBG_TRY(pc_launch(ix, d, min_score, bin, "fbg_pindex_chains"));
+    FBG_TRY(px_record_end(ix));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(chain_off, c.off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (score) FBG_HIP_TRY(ctx, hipMemcpyAsync(score, c.score.p, n * 4, hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&bin[4], d.ctr + 4, 8, hipMemcpyDeviceToHost, st));
+    FBG_TRY(px_sync_elapsed(ix, device_ms));
+    return pc_finish(ix, chain_off, bin, "fbg_pindex_chains");
 }
 
 extern "C" int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, uint32_t *anchor_seed, double *device_ms)

@@ -39,42 +39,6 @@ __global__ __launch_bounds__(PX_THREADS) void k_pr_place(PvDev d, const uint32_t
     rec[i] = make_uint4(in ? u : PR_NONE, o, (uint32_t)q, in ? node_block[u] : 0u);
 }
 
-// Does the text of row r from offset o of its node u in block j on start with S[0 .. k)?  k >= 1, o < |label(u)|.
-// Every read is bounded: a label by its length, the row's cells by block nb, S by k.
-__device__ __forceinline__ bool pr_walk(const PrDev &d, uint64_t r, uint32_t u, uint32_t o, uint64_t j, const uint8_t *S, uint32_t k)
-{
-    uint32_t pos = 0;
-    uint64_t a = d.loff[u] + o, b = d.loff[u + 1];
-    for (;;) {
-        const uint64_t take = b - a < (uint64_t)(k - pos) ? b - a : (uint64_t)(k - pos);
-        for (uint64_t x = 0; x < take; x++)
-            if (d.labels[a + x] != S[pos + x]) return false;
-        pos += (uint32_t)take;
-        if (pos == k) return true;
-        uint32_t v;
-        do {
-            if (++j >= d.nb) return false;        // the row ends before the seed does
-            v = d.node_of[j * d.m + r];
-        } while (v == PR_NONE);
-        a = d.loff[v];
-        b = d.loff[v + 1];
-    }
-}
-
-// rec of one place and row r: is r in rows(place)?
-__device__ __forceinline__ bool pr_supports(const PrDev &d, const uint4 rc, uint64_t r)
-{
-    if (rc.x == PR_NONE || d.node_of[(uint64_t)rc.w * d.m + r] != rc.x) return false;
-    return pr_walk(d, r, rc.x, rc.y, rc.w, d.reads + d.sbase[rc.z], d.slen[rc.z]);
-}
-
-// the G bits of a wave-wide ballot that belong to the group whose first lane is sh
-template <int G> __device__ __forceinline__ uint64_t pr_group_bits(bool ok, unsigned sh)
-{
-    const uint64_t bal = __ballot(ok);
-    return G == FBG_WAVE ? bal : (bal >> sh) & ((1ull << (G % 64)) - 1);
-}
-
 // G lanes per start place, the lanes are rows, G at a time: one coalesced read of the block's stretch of node_of, the
 // lanes that hold the place's node walk, the ballot is the chunk of the set.  Every lane of the wave runs the row loop
 // (m is the same for all), so the ballots meet; places past the end and rows past m only vote no.

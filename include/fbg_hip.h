@@ -155,6 +155,11 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *   path_batch_kib     fbg_pindex_chains_cigar: the KiB of column history in device memory that one batch of reads longer
  *                      than 256 symbols may take (default 2^20, 1 GiB; values below 1 count as 1); a read whose own history
  *                      is larger is a batch of its own; results unchanged
+ *   byrow_max          fbg_pindex_chains_by_row: the most start places of a read that is still chained (default 1024;
+ *                      negative values count as 0); a read with more gets no row and no chain and is counted
+ *   byrow_lds          fbg_pindex_chains_by_row: 0 (default) keeps the state of reads of up to lds_max start places in LDS,
+ *                      a positive value below lds_max lowers that limit (larger ones clamp), -1 sends every read to the
+ *                      tier with its state in device memory; results unchanged
  * fbg_get_option also answers "index_kind" (read-only): -1 no index, 0 per-position records, 1 rank-order scan of a
  * gap-free MSA, 2 scan in suffix order of an MSA with gaps / ignore characters (slot by slot, or -- "span_scan_used" = 1 --
  * group by group), 3 one partition of a partitioned index.  "span_groups", "span_odd_groups", "span_irregular",
@@ -804,6 +809,65 @@ int fbg_pindex_rows_stats(const fbg_pindex *ix, uint64_t *rows, uint64_t *table_
                           uint64_t *places_unsupported, uint64_t *chains_unsupported);
 int fbg_pindex_seeds_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, double *device_ms);
 int fbg_pindex_chains_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row, uint64_t *row_bits, double *device_ms);
+
+/* Chaining along one MSA row: which input sequence a read lies on best, and with which anchors (an index built by
+ * fbg_pindex_build_segmentation_rows only; after a successful seeds call, plain or stranded).
+ *
+ * fbg_pindex_chains takes every start place as an anchor, whether or not an input sequence carries it, and breaks ties
+ * by the smallest place, so among similar rows its chain often mixes rows: no row then spells every anchor and
+ * fbg_pindex_chains_align has nothing to align against.  This call chains per row.  For a (virtual) read R, with the
+ * anchors, columns, `precedes`, band and ties of fbg_pindex_chains and rows(g) of the rows section:
+ *   chain(R, r)     the chain that fbg_pindex_chains defines on the anchors g of R with r in rows(g).  The columns stay
+ *                   the witness columns of fbg_pindex_seeds_msa: nothing is chained in row coordinates;
+ *   rowscore(R, r)  the score of chain(R, r), 0 without such an anchor;
+ *   score[R]        max over r of rowscore(R, r);
+ *   row[R]          the smallest r that attains score[R]; 0xffffffff where score[R] == 0;
+ *   n_best_rows[R]  the number of rows that attain score[R]; 0 where score[R] == 0;
+ *   the chain       of R is chain(R, row[R]); it is empty where score[R] < min_score or score[R] == 0.
+ * Equivalently, the result is what fbg_pindex_chains returns when the start column of every place that row[R] does not
+ * support is replaced by 0xffffffff; this is how it is computed.  It follows that
+ *   - score[R] is at most the score fbg_pindex_chains reports, and equal to it where that call's chain has a carrying row;
+ *   - after the call fbg_pindex_chains_rows gives, for every non-empty chain, first_row == row[R] and
+ *     1 <= n_rows <= n_best_rows[R] (a smaller row that carries the whole chain would reach the same score);
+ *   - fbg_pindex_chains_align gives row == row[R] for every non-empty chain, and its `unsupported` statistic is 0.
+ * A read with more start places than option byrow_max (default 1024) is not chained: score 0, no row, an empty chain;
+ * it is counted (reads_too_many).  The work per read is up to A^2 / 2 steps per 64 rows for A start places.
+ * Limits: the columns are witness columns; a chain lies on one row only, so a read that truly recombines two input
+ * sequences gets the better of its parts and no alignment of the whole; byrow_max.
+ *
+ *   fbg_pindex_chains_by_row         chain_off (n + 1) and score (n) as for fbg_pindex_chains; row and n_best_rows: n entries
+ *       each; score, row and n_best_rows may be NULL.  n = the reads of the last seeds call (2n after
+ *       fbg_pindex_seeds_strands).
+ *   fbg_pindex_chains_by_row_stats   any pointer may be NULL.  Of the last successful call since the last seeds or
+ *       fbg_pindex_chains call (0 without one): the reads whose state stayed in LDS, the reads with their state in device
+ *       memory, the reads with more than byrow_max start places, the reads within byrow_max that have an anchor and
+ *       score 0, and the start places that keep their column under the mask.  Then lds_max, the compiled capacity of the
+ *       LDS tier, and max_places, the value of option byrow_max, at any time.
+ * On the device.  The start columns and the per-place records of fbg_pindex_seeds_rows are made as those calls make them;
+ * the reads are sorted by their number of start places and binned (none, LDS tier, device tier, too many), which the
+ * host reads in one round trip.  A wave per read then takes the rows 64 at a time, a lane per row: per start place a
+ * ballot of the rows that support it, then the chain DP in place order, where for each place the lanes test 64 earlier
+ * places at a time (a supporting row in common, `precedes`) and every lane folds its own row's scores of the places
+ * that pass.  Each lane keeps its best row, and the lanes are merged by (score descending, row ascending).  The state --
+ * 280 bytes per start place -- is in LDS for reads of up to lds_max places and otherwise in a slab owned by the index,
+ * reserved only when such a read exists.  One lane per start place then masks the columns by the read's row, and the
+ * kernels of fbg_pindex_chains run on the masked columns.  The host compares the scores of the two phases; a difference
+ * fails the call with FBG_ERR_HIP and names the first read.  *device_ms (may be NULL): device time of all of it, the
+ * host's looks at the bins included, without the copies out.
+ * The call leaves the chain state as fbg_pindex_chains on the masked columns would: fbg_pindex_chains_fetch,
+ * fbg_pindex_chain_strands, fbg_pindex_chain_stats (anchors: the places kept), fbg_pindex_chains_rows, _align, _cigar and
+ * _cigar_fetch work on its chains.  Like fbg_pindex_chains it invalidates the alignment and its paths; a later
+ * fbg_pindex_chains replaces its result and a seeds call invalidates it.  It may be repeated, reads the reads of the
+ * last seeds call also after a later fbg_pindex_locate or fbg_pindex_occurrences, and leaves the seeds, their places and
+ * MSA coordinates, what the row calls returned and their statistics, the occurrences, fbg_pindex_stats, validation
+ * results and the context alone.
+ * Errors, all FBG_ERR_INVALID: a NULL index or chain_off; an index without the row table; no successful seeds call.
+ * FBG_ERR_TOO_LARGE for 2^31 reads or more (a workgroup per read).  n == 0: chain_off[0] = 0, FBG_OK.  Seeds without
+ * places: every score 0, every row 0xffffffff, every chain empty, FBG_OK, nothing launched. */
+int fbg_pindex_chains_by_row(fbg_pindex *ix, uint64_t band, uint64_t min_score, uint64_t *chain_off, uint32_t *score,
+                             uint32_t *row, uint32_t *n_best_rows, double *device_ms);
+int fbg_pindex_chains_by_row_stats(const fbg_pindex *ix, uint64_t *reads_lds, uint64_t *reads_device, uint64_t *reads_too_many,
+                                   uint64_t *reads_no_row, uint64_t *anchors_kept, uint64_t *lds_max, uint64_t *max_places);
 
 /* The edit distance of each read to a row that carries its chain (an index built by
  * fbg_pindex_build_segmentation_rows only; after a successful seeds call, plain or stranded, and a successful
