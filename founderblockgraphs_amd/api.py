@@ -590,7 +590,20 @@ class PatternIndex:
         self._eng._chk(self._L.fbg_pindex_cigar_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("paths", "ops", "columns", "history_bytes", "batches"), (x.value for x in v)))
 
-    def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False, by_row=False):
+    GRAPH_STATS = ("aligned", "not_selected", "too_long", "too_wide", "cells", "nodes", "merges", "path_nodes", "table_bytes", "batches")
+
+    def graph_align_stats(self):
+        """{aligned, not_selected, too_long, too_wide, cells, nodes, merges, path_nodes, table_bytes, batches} of the last
+        chains(graph=True) (fbg_pindex_align_graph_stats; an index built with rows=True only): cells is the sum of read
+        length times the label symbols of the window's nodes over the aligned reads, nodes the sum of those nodes, merges
+        the predecessor columns read on entering them, table_bytes the predecessor lists' and the block table's, batches
+        the batches option graph_batch_kib cut the reads into."""
+        v = [C.c_uint64(0) for _ in range(10)]
+        self._eng._chk(self._L.fbg_pindex_align_graph_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(self.GRAPH_STATS, (x.value for x in v)))
+
+    def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False, by_row=False,
+               graph=False, graph_pad=16, max_cells=0, select=None):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -606,7 +619,12 @@ class PatternIndex:
         Chains.cigar_off and .cigar_ops, read with .cigar(k) and .cigar_runs(k).  by_row=True (an index built with
         rows=True only): chain along one MSA row instead (fbg_pindex_chains_by_row): per read the row whose supported
         anchors chain best, as Chains.chain_row and .n_best_rows, and that row's chain; strands, rows=, align= and cigar=
-        then work on these chains, and every non-empty one has a row to be aligned against."""
+        then work on these chains, and every non-empty one has a row to be aligned against.  graph=True (an index built
+        with rows=True only): also the edit distance of every read to a path of the graph through the blocks around its
+        chain, graph_pad symbols beyond the anchors, and that path (fbg_pindex_chains_align_graph and _fetch), as
+        Chains.graph_edits, .graph_start, .graph_end, .graph_path_off, .graph_path_nodes and .graph_path(k); a read whose
+        window takes more than max_cells cells (0: no limit) is skipped, and so is one whose entry of select (one per
+        read of the last seeds() call, None: all) is zero.  After seeds(strands=True) also Chains.best_graph_edits."""
         if cigar and not align:
             raise ValueError("cigar=True needs align=True")
         if band is not None and band < 0:
@@ -615,6 +633,8 @@ class PatternIndex:
             raise ValueError("min_score must be 0 or more")
         if pad < 0 or max_window < 0:
             raise ValueError("pad and max_window must be 0 or more")
+        if graph_pad < 0 or max_cells < 0:
+            raise ValueError("graph_pad and max_cells must be 0 or more")
         k = getattr(self, "_seed_reads", 0)
         chain_off = np.zeros(k + 1, dtype=np.uint64)
         score = np.zeros(max(k, 1), dtype=np.uint32)
@@ -672,6 +692,28 @@ class PatternIndex:
             ops = np.zeros(max(total.value, 1), dtype=np.uint32)
             self._eng._chk(self._L.fbg_pindex_chains_cigar_fetch(self._h, _u64(coff), ops.ctypes.data_as(_lib.u32p)))
             out.cigar_off, out.cigar_ops, out.cigar_ms = coff, ops[:total.value], ms6.value
+        if graph:
+            sel = None
+            if select is not None:
+                sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+                if sel.shape != (k,):
+                    raise ValueError("select takes one entry per read of the last seeds() call")
+            arr = [np.zeros(max(k, 1), dtype=np.uint32) for _ in range(6)]
+            total, ms7 = C.c_uint64(0), C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chains_align_graph(self._h, min(int(graph_pad), 0xffffffffffffffff),
+                                                                 min(int(max_cells), 0xffffffffffffffff), None if sel is None else _u8(sel),
+                                                                 *[a.ctypes.data_as(_lib.u32p) for a in arr], C.byref(total), C.byref(ms7)))
+            poff = np.zeros(k + 1, dtype=np.uint64)
+            nodes = np.zeros(max(total.value, 1), dtype=np.uint32)
+            self._eng._chk(self._L.fbg_pindex_chains_align_graph_fetch(self._h, _u64(poff), nodes.ctypes.data_as(_lib.u32p)))
+            out.graph_edits = arr[0][:k]
+            out.graph_start = np.stack((arr[1][:k], arr[2][:k]), axis=1)
+            out.graph_end = np.stack((arr[3][:k], arr[4][:k]), axis=1)
+            out.graph_path_off, out.graph_path_nodes, out.graph_ms = poff, nodes[:total.value], ms7.value
+            if given is not None:
+                pick = np.where(out.strand[:given] == 1, given, 0) + np.arange(given)
+                out.best_graph_edits = np.where(out.strand[:given] == _lib.STRAND_NONE, np.uint32(_lib.ALIGN_NONE),
+                                                out.graph_edits[pick] if given else out.graph_edits[:0]).astype(np.uint32)
         return out
 
     def by_row_stats(self):
@@ -885,6 +927,16 @@ class Chains:
       cigar_ops       uint32 per run: length << 4 | code with BAM's codes I = 1, D = 2, = is 7, X = 8, in read order;
                       cigar(k) gives the string, cigar_runs(k) the (code, length) pairs
       cigar_ms        device time of fbg_pindex_chains_cigar
+    and, asked for with graph=True (None otherwise; include/fbg_hip.h, fbg_pindex_chains_align_graph):
+      graph_edits     uint32 per read: the fewest edits that turn the read into a stretch of a path of the graph through the
+                      blocks around its chain; 0xffffffff for an empty chain and for a read that was not selected, too
+                      long or too wide
+      graph_start, graph_end   uint32[k, 2]: (node, offset) at which that stretch starts and ends -- the first end cell in
+                      (node, offset) order, then the largest start; 0xffffffff where graph_edits is
+      graph_path_off  uint64[k + 1], CSR offsets of the reads' paths; a read without an alignment has none
+      graph_path_nodes   uint32 per path entry: the nodes from the start node to the end node; graph_path(k) gives read k's
+      best_graph_edits   after seeds(strands=True): uint32 per given read, graph_edits of the strand that strand picked
+      graph_ms        device time of fbg_pindex_chains_align_graph
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -897,6 +949,8 @@ class Chains:
         self.by_row = False
         self.align_row = self.edits = self.t_start = self.t_end = self.best_edits = self.align_ms = None
         self.cigar_off = self.cigar_ops = self.cigar_ms = None
+        self.graph_edits = self.graph_start = self.graph_end = self.graph_path_off = self.graph_path_nodes = None
+        self.best_graph_edits = self.graph_ms = None
 
     def cigar_runs(self, k):
         """int64[runs, 2]: (code, length) of the runs of read k's alignment path; no rows without an alignment."""
@@ -908,6 +962,12 @@ class Chains:
     def cigar(self, k):
         """The alignment path of read k as a CIGAR string with = and X, such as 25=1X24=; "" without an alignment."""
         return "".join(f"{n}{_lib.CIGAR_OPS[c]}" for c, n in self.cigar_runs(k).tolist())
+
+    def graph_path(self, k):
+        """int64[n_path]: the nodes of read k's path in the graph, from its start node to its end node."""
+        if self.graph_path_off is None:
+            raise ValueError("no graph alignment: ask for it with graph=True")
+        return self.graph_path_nodes[int(self.graph_path_off[k]):int(self.graph_path_off[k + 1])].astype(np.int64)
 
     def row_set(self, k):
         """int64[n_rows[k]]: the rows that carry the whole chain of read k, ascending."""

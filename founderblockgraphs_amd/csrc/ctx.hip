@@ -231,6 +231,7 @@ static const OptKey g_opt_keys[] = {
     {"path_batch_kib", &FbgOptions::path_batch_kib},
     {"byrow_max", &FbgOptions::byrow_max},
     {"byrow_lds", &FbgOptions::byrow_lds},
+    {"graph_batch_kib", &FbgOptions::graph_batch_kib},
 };
 
 // read-only keys of fbg_get_option: what the context and its last build report

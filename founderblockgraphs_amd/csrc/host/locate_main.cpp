@@ -4,6 +4,7 @@
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
 //              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--by-row] [--align[=PAD]] [--cigar]
+//              [--graph-align[=PAD]]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -58,6 +59,11 @@
 // stretch (fbg_pindex_chains_cigar): runs of = (equal symbols), X (a substitution), I (a pattern symbol with no symbol of
 // the row) and D (a symbol of the row with no pattern symbol) in pattern order, such as 25=1X24=.  `G <tab> *` stays as it
 // is, and without --cigar no line changes.
+// --graph-align[=PAD] (with --chain and --rows) aligns every pattern against the graph of the blocks around its chain, PAD
+// symbols (default 16) beyond the anchors (fbg_pindex_chains_align_graph), and prints after a chain's lines
+//   H <tab> edits <tab> start_node <tab> start_offset <tab> end_node <tab> end_offset <tab> path
+// the fewest edits, the S ids and offsets at which the stretch of the graph starts and ends, and the nodes from the start
+// to the end as >u>v>w; or `H <tab> *` when there is no alignment.  Without --graph-align no byte changes.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -76,7 +82,7 @@ static int usage(const char *msg)
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
-              << "                  [--by-row] [--align[=PAD]] [--cigar]\n"
+              << "                  [--by-row] [--align[=PAD]] [--cigar] [--graph-align[=PAD]]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -107,7 +113,11 @@ static int usage(const char *msg)
               << "                     gap-stripped text within PAD symbols (default 16) of the chain, and that stretch's start\n"
               << "                     and end in the row's text, from 0 (G and * if there is no alignment)\n"
               << "  --cigar            needs --align: a G line with numbers ends with the alignment path of the pattern against\n"
-              << "                     that stretch, runs of = X I D in pattern order (25=1X24=); no other line changes\n";
+              << "                     that stretch, runs of = X I D in pattern order (25=1X24=); no other line changes\n"
+              << "  --graph-align[=PAD]  needs --chain and --rows: after a chain's lines an H line: the fewest edits between the\n"
+              << "                     pattern and a stretch of a path of the graph through the blocks around the chain, PAD\n"
+              << "                     symbols (default 16) beyond its anchors, the node and offset at which that stretch\n"
+              << "                     starts and ends, and the path as >u>v>w (H and * if there is no alignment)\n";
     return EXIT_FAILURE;
 }
 
@@ -182,7 +192,8 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement;
-    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false;
+    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false, graph_align = false;
+    uint64_t graph_pad = 16;
     uint64_t pad = 16;
     bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
     uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
@@ -249,6 +260,18 @@ int main(int argc, char **argv)
             pad = m;
             continue;
         }
+        if (a == "--graph-align") { graph_align = true; continue; }
+        if (a.compare(0, 14, "--graph-align=") == 0) {
+            const std::string v = a.substr(14);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
+                return usage(("--graph-align takes a pad, not '" + v + "'").c_str());
+            graph_align = true;
+            graph_pad = m;
+            continue;
+        }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
         return usage(("unknown argument " + a).c_str());
     }
@@ -261,6 +284,7 @@ int main(int argc, char **argv)
     if (by_row && !(chain && rows)) return usage("--by-row needs --chain and --rows");
     if (cigar && !align) return usage("--cigar needs --align");
     if (align && !(chain && rows)) return usage("--align needs --chain and --rows");
+    if (graph_align && !(chain && rows)) return usage("--graph-align needs --chain and --rows");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
 
@@ -358,6 +382,9 @@ int main(int argc, char **argv)
     std::vector<uint32_t> aligned[4];                       // --align: row, edits, t_start, t_end
     std::vector<uint64_t> cigar_off(nv + 1, 0);             // --cigar: the runs of every virtual read
     std::vector<uint32_t> cigar_ops;
+    std::vector<uint32_t> on_graph[5];                      // --graph-align: edits, start node and offset, end node and offset
+    std::vector<uint64_t> path_off(nv + 1, 0);
+    std::vector<uint32_t> path_nodes;
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -412,6 +439,14 @@ int main(int argc, char **argv)
             rc = fbg_pindex_chains_cigar(ix, nullptr, &total, nullptr);
             cigar_ops.resize(total + 1);
             if (rc == FBG_OK) rc = fbg_pindex_chains_cigar_fetch(ix, cigar_off.data(), cigar_ops.data());
+        }
+        if (rc == FBG_OK && graph_align) {
+            uint64_t total = 0;
+            for (int k = 0; k < 5; k++) on_graph[k].resize(nv + 1);
+            rc = fbg_pindex_chains_align_graph(ix, graph_pad, 0, nullptr, on_graph[0].data(), on_graph[1].data(), on_graph[2].data(),
+                                               on_graph[3].data(), on_graph[4].data(), nullptr, &total, nullptr);
+            path_nodes.resize(total + 1);
+            if (rc == FBG_OK) rc = fbg_pindex_chains_align_graph_fetch(ix, path_off.data(), path_nodes.data());
         }
     }
     if (rc == FBG_OK && !occurrences && !seeds)
@@ -469,6 +504,13 @@ int main(int argc, char **argv)
                                       << (code == FBG_CIGAR_EQ ? '=' : code == FBG_CIGAR_X ? 'X' : code == FBG_CIGAR_I ? 'I' : 'D');
                         }
                     }
+                    std::cout << '\n';
+                }
+                if (graph_align && on_graph[0][v] == FBG_ALIGN_NONE) std::cout << "H\t*\n";
+                else if (graph_align) {
+                    std::cout << "H\t" << on_graph[0][v] << '\t' << g.ids[on_graph[1][v]] << '\t' << on_graph[2][v] << '\t'
+                              << g.ids[on_graph[3][v]] << '\t' << on_graph[4][v] << '\t';
+                    for (uint64_t i = path_off[v]; i < path_off[v + 1]; i++) std::cout << '>' << g.ids[path_nodes[i]];
                     std::cout << '\n';
                 }
             }

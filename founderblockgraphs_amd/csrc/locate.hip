@@ -547,7 +547,7 @@ static int px_seeds(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     PoState &s = ix->sd;
     s.ready = false;
     ix->ch.ready = false;         // chains belong to the seeds they were made from
-    ix->al.valid = ix->cg.ready = ix->pb.ready = false;
+    ix->al.valid = ix->cg.ready = ix->pb.ready = ix->gr.valid = false;
     if (device_ms) *device_ms = 0;
     if (!seed_off || (n_patterns && !pat_off)) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing argument", who);
     if (min_length == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: min_length is 1 or more", who);

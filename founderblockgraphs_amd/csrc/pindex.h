@@ -7,6 +7,7 @@
 //   pindex_rows.hip       the MSA rows that carry a start place or a chain
 //   pindex_byrow.hip      chaining along one row: per read the row whose supported anchors chain best
 //   pindex_align.hip      edit distance of a read to a row of its chain, and the alignment path
+//   pindex_graph.hip      edit distance of a read to a path of the graph around its chain, and that path
 // Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
 // needs its launch calls a launcher declared at the end of this header.
 #pragma once
@@ -40,6 +41,10 @@
 #define PA_NONE 0xffffffffu   // FBG_ALIGN_NONE
 #define PG_CTR 13              // counters of fbg_pindex_chains_cigar: traces that failed, reads traced, columns, reads of 1 .. 4
                               // words and of more, the widest T of each of the five
+
+#define PH_CTR 13             // counters of fbg_pindex_chains_align_graph: traces that failed, reads aligned, not selected, too long,
+                              // too wide, cells, nodes, merges, and the reads of 1 .. 4 words and of more
+#define PH_NONE 0xffffffffu   // no predecessor chosen
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
@@ -108,6 +113,21 @@ struct PbState {
     uint64_t stat[5] = {0, 0, 0, 0, 0};      // reads_lds, reads_device, reads_too_many, reads_no_row, anchors_kept
 };
 
+// fbg_pindex_chains_align_graph.  Tables, built by the first call: pin_off (u32[n_nodes + 1]) and pin (u32[E]), the
+// predecessors of every node in ascending order; C (u64[nb + 1]), the scan of the shortest label of every block; keys:
+// the edges as dst << 32 | src before and after their sort.  Per read of the last chaining call: info = (first node of
+// H, one past its last, L or 0 where nothing is aligned, jl); sz (scratch words, then path slots; n + 1 each) and their
+// scans soff / poff; out: edits, start node and offset, end node and offset, n_path (6 n); cnt (n_path as u64, n + 1) and
+// its scan off; slots: the traced nodes, end first; path: the paths back to back; scratch: the last columns of one
+// batch; sel: the caller's mask; ctr: PH_CTR counters.  valid: a call has succeeded since the last chaining call, for n
+// reads and total path nodes, and (on_device) left off and path for them.
+struct PhState {
+    DevBuf pin_off, pin, C, keys, info, sz, soff, poff, out, cnt, off, slots, path, scratch, sel, ctr;
+    bool has_tab = false, valid = false, on_device = false;
+    uint64_t n = 0, total = 0;
+    uint64_t stat[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};     // aligned, not_selected, too_long, too_wide, cells, nodes, merges, path_nodes, batches
+};
+
 struct fbg_pindex {
     fbg_ctx *ctx = nullptr;
     uint64_t N1 = 0;          // text length including the sentinel
@@ -152,6 +172,7 @@ struct fbg_pindex {
     PaState al;
     PgState cg;
     PbState pb;
+    PhState gr;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, sv0 = nullptr, sv1 = nullptr;   // made with the index (px_new)
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -263,6 +284,19 @@ struct PaDev {
     const uint8_t *reads;
     const uint64_t *roff;             // [n + 1] byte offsets of the (virtual) reads
     uint64_t m, nb;
+};
+
+// The graph of the blocks jl .. jh is the nodes first[jl] .. first[jh + 1] (ids ascend block by block, so id order is a
+// topological order) with the edges of pin: the predecessors of v are pin[pin_off[v] .. pin_off[v + 1]), ascending, all
+// of the block before v's.  C[j]: the sum of the shortest labels of the blocks before j.
+struct PhDev {
+    const uint8_t *labels;
+    const uint64_t *loff;             // [n_nodes + 1]
+    const uint8_t *reads;
+    const uint64_t *roff;             // [n + 1] byte offsets of the (virtual) reads
+    const uint64_t *first, *C;        // [nb + 1] each
+    const uint32_t *pin_off, *pin;
+    uint64_t nb;
 };
 
 static inline PxDev px_dev(const fbg_pindex *ix)

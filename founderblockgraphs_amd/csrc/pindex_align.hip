@@ -111,25 +111,6 @@ __global__ __launch_bounds__(FBG_WAVE) void k_pa_gather(PaDev d, const uint4 *in
     }
 }
 
-// One column of Myers' bit-vector recurrence for a word of 64 read symbols (Hyyro's block form).  eq: the rows of the
-// word whose read symbol equals the column's text symbol; pv / mv: the rows whose vertical difference D(i, j) -
-// D(i - 1, j) is +1 / -1; hin: the horizontal difference D(i0, j) - D(i0, j - 1) of the row below the word's first;
-// -> the horizontal difference of the row whose bit is top.  Bits above top never reach the bits below it.
-__device__ __forceinline__ int pa_step(uint64_t eq, uint64_t &pv, uint64_t &mv, int hin, uint64_t top)
-{
-    const uint64_t neg = hin < 0 ? 1 : 0;
-    const uint64_t xv = eq | mv;
-    eq |= neg;
-    const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
-    uint64_t ph = mv | ~(xh | pv), mh = pv & xh;
-    const int hout = (ph & top) ? 1 : (mh & top) ? -1 : 0;
-    ph = (ph << 1) | (hin > 0 ? 1 : 0);
-    mh = (mh << 1) | neg;
-    pv = mh | ~(xv | ph);
-    mv = ph & xv;
-    return hout;
-}
-
 // 64 text symbols of a pass per load, lane t takes column j0 + t; REV: the text backwards
 template <bool REV> __device__ __forceinline__ int pa_chunk(const uint8_t *W, uint32_t wl, uint32_t j0, unsigned lane)
 {

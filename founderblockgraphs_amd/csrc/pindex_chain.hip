@@ -168,6 +168,7 @@ int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *devic
     c.ready = false;
     ix->pb.ready = false;
     ix->al.valid = ix->cg.ready = false;      // the alignment and its paths belong to the chains
+    ix->gr.valid = false;                     // and so does the alignment to the graph
     if (device_ms) *device_ms = 0;
     if (!chain_off) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing chain_off", what);
     if (!ix->from_segmentation || !ix->has_map)

@@ -160,6 +160,10 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *   byrow_lds          fbg_pindex_chains_by_row: 0 (default) keeps the state of reads of up to lds_max start places in LDS,
  *                      a positive value below lds_max lowers that limit (larger ones clamp), -1 sends every read to the
  *                      tier with its state in device memory; results unchanged
+ *   graph_batch_kib    fbg_pindex_chains_align_graph: the KiB of node columns in device memory that one batch of reads may
+ *                      take (default 2^20, 1 GiB, as path_batch_kib: a bound on the scratch that still leaves batches of
+ *                      10^5 reads of a few hundred symbols on a dozen founders; values below 1 count as 1); a read whose own
+ *                      columns are larger is a batch of its own; results unchanged
  * fbg_get_option also answers "index_kind" (read-only): -1 no index, 0 per-position records, 1 rank-order scan of a
  * gap-free MSA, 2 scan in suffix order of an MSA with gaps / ignore characters (slot by slot, or -- "span_scan_used" = 1 --
  * group by group), 3 one partition of a partitioned index.  "span_groups", "span_odd_groups", "span_irregular",
@@ -833,7 +837,8 @@ int fbg_pindex_chains_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t *first_row
  * A read with more start places than option byrow_max (default 1024) is not chained: score 0, no row, an empty chain;
  * it is counted (reads_too_many).  The work per read is up to A^2 / 2 steps per 64 rows for A start places.
  * Limits: the columns are witness columns; a chain lies on one row only, so a read that truly recombines two input
- * sequences gets the better of its parts and no alignment of the whole; byrow_max.
+ * sequences gets the better of its parts and no alignment of the whole against a row (fbg_pindex_chains_align_graph
+ * aligns it against the graph); byrow_max.
  *
  *   fbg_pindex_chains_by_row         chain_off (n + 1) and score (n) as for fbg_pindex_chains; row and n_best_rows: n entries
  *       each; score, row and n_best_rows may be NULL.  n = the reads of the last seeds call (2n after
@@ -981,6 +986,88 @@ int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t *total_ops
 int fbg_pindex_chains_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint32_t *ops);
 int fbg_pindex_cigar_stats(const fbg_pindex *ix, uint64_t *paths, uint64_t *ops, uint64_t *columns, uint64_t *history_bytes,
                            uint64_t *batches);
+
+/* The edit distance of each read to a path of the graph around its chain, and that path (an index built by
+ * fbg_pindex_build_segmentation_rows only; after a successful seeds call, plain or stranded, and a successful
+ * fbg_pindex_chains or fbg_pindex_chains_by_row since it).
+ *
+ * fbg_pindex_chains_align aligns a read against one input sequence.  A founder graph also spells the recombinations of
+ * its rows, and a read that recombines two of them has no row to be aligned against, or pays for its other half in edits.
+ * This call aligns the whole read against the subgraph of the blocks around its chain and answers "where on the graph
+ * does this read lie, through which nodes, with how many edits".  Unit costs, both ends free in the graph, the read
+ * global; symbols are compared as bytes.  For a (virtual) read R let P be its text as fbg_pindex_chains_align reads it
+ * (rc(P_R) for a reverse virtual read) and L = |P|.
+ *   anchors    anchor i of the chain is a place in node u_i at offset o_i, of block j_i, of a seed at read offset q_i.
+ *   minlen[j]  the shortest label among the nodes of block j, 0 for a block without nodes; C[j] the sum of minlen over
+ *              the blocks before j (C[0] = 0, nb + 1 entries).
+ *   window     left need of anchor i: max(0, q_i + pad - o_i); right need: max(0, (L - q_i) + pad - (|label(u_i)| - o_i)).
+ *              jl = the minimum over the anchors of the largest j <= j_i with C[j_i] - C[j] >= the left need, or 0 if
+ *              there is none; jh = the maximum over the anchors of the smallest j >= j_i with C[j + 1] - C[j_i + 1] >= the
+ *              right need, or nb - 1 if there is none.  Every path through the blocks jl .. j_i - 1 spells at least the
+ *              left need, so no alignment within pad of the anchors' diagonals is cut off.  pad is clamped to 2^33.
+ *   H          every node of the blocks jl .. jh with its whole label, and the index's edges between them.  The graph is
+ *              layered: an edge joins a node of a block to a node of the next, and node ids ascend block by block.
+ *              cells = L * the sum of |label(v)| over H, which is the work.
+ *   D_v(i, c)  for node v of H, columns c = 1 .. |label(v)| and read rows i = 0 .. L: D_v(0, c) = 0, and
+ *              D_v(i, c) = min(D_v(i-1, c-1) + [P[i-1] != label(v)[c-1]], D_v(i-1, c) + 1, D_v(i, c-1) + 1), where column 0
+ *              of v, the column entering v, is the row-wise minimum of the last columns of v's predecessors in H; a
+ *              node of block jl, or one without a predecessor in H, enters with D(i) = i.  (The row-wise minimum of
+ *              valid columns is a valid column: neighbouring rows still differ by at most 1.)
+ *   edits[R]   the minimum of D_v(L, c) over H, or L if no cell is below L.
+ *   end        (end_node, end_offset = c): the first cell in (node id, column) order whose D_v(L, c) is strictly below
+ *              every earlier one and below L; without such a cell the empty alignment at (first node of block jl, 0).
+ *   path       walk back from the end cell: the reversed read against the reversed text of the suffix chosen so far, with
+ *              D'(0, x) = x and D'(i, 0) = i.  Inside the current node v, the first offset met walking back (so the
+ *              largest; the end offset itself and offset 0 count) at which D'(L, .) == edits is start_offset and ends
+ *              the walk with start_node = v.  Otherwise, at v's first symbol, the walk steps to the smallest
+ *              predecessor u in H with min_i (F_u(i) + B(L - i)) == edits, F_u the last column of u and B the walk's
+ *              column there.  Such a u exists whenever v holds no start.  The path is the nodes from start_node to
+ *              end_node, and lev(P, spell(path)[start_offset : up to end_offset in end_node]) == edits.
+ * The result is exact over H: no band, no cut-off.  A read without a result has FBG_ALIGN_NONE in the five arrays and
+ * n_path 0, and is no error: an empty chain; a read that select leaves out (not_selected counts those with a chain);
+ * too long, L > max_read (1024, as fbg_pindex_chains_align); too wide, max_cells != 0 and cells > max_cells, tested after
+ * too long.  An anchor whose place lies outside its node's label (none on a graph of a segmentation) is passed over.
+ * Limits: no CIGAR over the path; unit costs only, no affine gaps; every node of the window's blocks is computed, no
+ * pruning inside it, so the cost grows with the distinct nodes per block -- on an MSA of a thousand similar rows a block
+ * can hold hundreds -- which is what select is for: graph-align the reads the row alignment left out or left poor.
+ *
+ *   fbg_pindex_chains_align_graph        one entry per read of the last seeds call (2n after fbg_pindex_seeds_strands) in
+ *       each of the six arrays; select: that many bytes, non-zero = aligned, or NULL for all; *total_path: the sum of
+ *       n_path.  Any output pointer may be NULL.
+ *   fbg_pindex_chains_align_graph_fetch  path_off[n + 1], the scan of n_path, and path_nodes[path_off[n]], the paths back to
+ *       back from start_node to end_node: count then fetch, as fbg_pindex_chains_cigar / _cigar_fetch.  Either may be NULL.
+ *   fbg_pindex_align_graph_stats         any pointer may be NULL.  Of the last fbg_pindex_chains_align_graph (0 before the
+ *       first; a call that fails its checks leaves them): reads aligned, not selected, too long, too wide; cells; nodes, the
+ *       sum of |H|; merges, the predecessor columns read on entering nodes; path_nodes; then table_bytes, the device bytes of
+ *       the predecessor lists and of C (0 until the first call builds them); batches.
+ * On the device.  The first call sorts the edges by (destination, source) into a predecessor CSR and scans minlen into
+ * C; the index owns both.  One lane per read finds jl and jh by binary searches in C, the node range, the cells and the
+ * skip status.  A read's scratch is the two vertical-difference words of every 64 read symbols of every node's last
+ * column, |H| * 2 * ceil(L / 64) words; a scan places the reads and the host forms batches of consecutive reads that fit
+ * option graph_batch_kib (a batch always takes at least one read).  Per batch, a wave per read runs Myers' recurrence
+ * node by node in id order with the state in registers (1 to 4 words) or LDS (up to 16), the label loaded 64 bytes at a
+ * time, each byte made wave-uniform by a readlane and its match word one ballot per 64 read symbols.  On entering a node
+ * lane l of word w decodes row 64 w + l + 1 of every predecessor's stored column from popcounts, keeps the minimum, and the
+ * merged column is encoded again from each lane's difference to the row below by two ballots per word.  A second wave per
+ * read runs the reverse recurrence along the chosen suffix, tests every column for a start, and at a node's first symbol
+ * evaluates F_u(i) + B(L - i) per predecessor with lanes as rows and a wave minimum.  It writes the nodes into jh - jl + 1
+ * slots per read; a scan of n_path and a compaction serve the fetch.  Every loop is bounded by L, a label, a predecessor
+ * list or the node range; a walk that finds no predecessor writes no path and fails the call with FBG_ERR_HIP.
+ * *device_ms (may be NULL): device time of the kernels, the host's looks at the sizes included.
+ * A call may be repeated and leaves the seeds, their places and MSA coordinates, the chains, what the row calls
+ * returned, the row alignment and its paths, the occurrences, fbg_pindex_stats, validation results and the context
+ * alone; like the align call it still sees the reads of the last seeds call after a later fbg_pindex_locate or
+ * fbg_pindex_occurrences.  A later fbg_pindex_chains, fbg_pindex_chains_by_row or seeds call invalidates the result.
+ * Errors, all FBG_ERR_INVALID: a NULL index; an index without the row table; no successful chaining call since the last
+ * seeds call; _fetch without a successful call since the last chaining call.  FBG_ERR_TOO_LARGE for 2^31 reads or more
+ * (a workgroup per read).  No reads returns FBG_OK. */
+int fbg_pindex_chains_align_graph(fbg_pindex *ix, uint64_t pad, uint64_t max_cells, const uint8_t *select, uint32_t *edits,
+                                  uint32_t *start_node, uint32_t *start_offset, uint32_t *end_node, uint32_t *end_offset,
+                                  uint32_t *n_path, uint64_t *total_path, double *device_ms);
+int fbg_pindex_chains_align_graph_fetch(fbg_pindex *ix, uint64_t *path_off, uint32_t *path_nodes);
+int fbg_pindex_align_graph_stats(const fbg_pindex *ix, uint64_t *aligned, uint64_t *not_selected, uint64_t *too_long,
+                                 uint64_t *too_wide, uint64_t *cells, uint64_t *nodes, uint64_t *merges, uint64_t *path_nodes,
+                                 uint64_t *table_bytes, uint64_t *batches);
 
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
