@@ -228,6 +228,7 @@ static const OptKey g_opt_keys[] = {
     {"row_count_fast", &FbgOptions::row_count_fast},
     {"twin_hash", &FbgOptions::twin_hash},
     {"front_one_fill", &FbgOptions::front_one_fill},
+    {"scan_rows_ahead", &FbgOptions::scan_rows_ahead},
     {"path_batch_kib", &FbgOptions::path_batch_kib},
     {"byrow_max", &FbgOptions::byrow_max},
     {"byrow_lds", &FbgOptions::byrow_lds},

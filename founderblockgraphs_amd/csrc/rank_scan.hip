@@ -264,8 +264,8 @@ template <int L, bool PLAIN> __global__ __launch_bounds__(RS_THREADS) __attribut
 // threshold above K a slot can only matter if it ties on the key, shares its column with a neighbour, sits next to a tie
 // group or lies in the 64 columns nearest a row end -- one slot in fifteen -- and the others should cost as little as can be:
 //   * no LDS staging, no barriers: a wave streams through a stretch of the slots of its own, 64 consecutive slots at a
-//     time, a lane each, the next row's loads in flight; the neighbours' values come by DPP shifts (lanes 3 .. 60 are
-//     settled, consecutive rows overlap by six slots);
+//     time, a lane each, the next rows' loads in flight (k_rank_scan_lean's D); the neighbours' values come by DPP shifts
+//     (lanes 3 .. 60 are settled, consecutive rows overlap by six slots);
 //   * x = fract(position / row length) in single precision stands in for the column: four instructions instead of the
 //     thirteen of the exact remainder, off by less than eps / 2 (rs_lean_setup), so that |x - x'| < eps or > 1 - eps
 //     whenever two slots share a column, and x >= near_end or x < eps for a slot near a row end: filters that never say
@@ -360,6 +360,16 @@ template <class E> __device__ __forceinline__ void rl_shift(E *list, uint32_t &n
     n = rest;
 }
 
+// D: rows whose loads a wave keeps in flight (option scan_rows_ahead).  With one row ahead the waves sat parked for 56 % of
+// their cycles (profiles/scan_rows_ahead_summary.txt).  D = 2, 3: the rows go in groups of D, two register sets, a group each;
+// at the top of a group the D loads of the NEXT group go out, then the group at hand is worked through row by row, so every
+// wait of the row loop is a counted one on loads issued a whole group earlier (3: 64 registers, the most that eight waves per
+// SIMD allow).  D = 4: one set.  Every row of a group owns its registers: nothing is moved while loads are pending (a ring
+// that rotates makes the compiler wait for all of them in every row).  Same rows, same order, same lists.
+// 3.07 -> 2.72 ms at C3 with 3, 2.73 with 2, 2.79 with 4.
+#define RL_ROWS_AHEAD_DEFAULT 3
+// EXT: f.ext holds the slots' extra symbols (a template parameter: the loads of a group go out back to back, no branch between).
+template <int D, bool EXT>
 __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_rank_scan_lean(const RankArgs *__restrict__ ap, LeanArgs f)
 {
     // (the scan's arguments stay in memory: the rows below need a handful of them, and in scalar registers all of them
@@ -383,16 +393,8 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
     const uint8_t *__restrict__ ext = f.ext;
     // (a row that reaches beyond the array is a row the general code takes: what its lanes out there load does not matter)
     auto row_slot = [&](uint32_t k0) -> uint32_t { return min(max(k0 - RL_EV_LO + (uint32_t)lane, own_lo), own_hi - 1); };
-    uint64_t xnext = wlo < whi ? keys[row_slot(wlo)] : 0ull;
-    uint32_t enext = ext && wlo < whi ? ext[row_slot(wlo)] : 0u;
-    for (uint32_t k0 = wlo; k0 < whi; k0 += RL_EV) {
-        const uint64_t x = xnext;
-        const uint32_t ex = enext;
-        if (k0 + RL_EV < whi) {                                         // in flight during this row's work
-            const uint32_t kn = row_slot(k0 + RL_EV);
-            xnext = keys[kn];
-            if (ext) enext = ext[kn];
-        }
+    // one row: the slots k0 - RL_EV_LO .. k0 - RL_EV_LO + 63, a lane each, their words in x and their extra symbols in ex
+    auto row = [&](const uint32_t k0, const uint64_t x, const uint32_t ex) __attribute__((always_inline)) {
         const uint32_t slot = k0 - RL_EV_LO + (uint32_t)lane;
         // rows within reach of the ends of the array (or of this wave's last slot, where a row is not full): the general
         // code knows what a missing neighbour means
@@ -434,7 +436,7 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
             }
             if (SS) {
                 uint32_t cx = 0, cy = 0;
-                if (ext) {
+                if (EXT) {
                     // the pair's code: how many of the 4 symbols after the key the two agree on (2 bits each, first on top)
                     const uint32_t d = (ex ^ rl_from_next(ex)) & 255u;
                     const uint32_t c = d ? (uint32_t)(__builtin_clz(d) - 24) >> 1 : 4u;
@@ -450,6 +452,65 @@ __global__ __launch_bounds__(RL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
         }
         while (nq >= 64) { rl_queued(*ap, my_queue, 64, &s_cand_n, &s_tie_n); rl_shift(my_queue, nq); }
         if (nn >= 64) { rl_noted(*ap, my_note, 64, &s_pair_n, &s_code_n); rl_shift(my_note, nn); }
+    };
+    // (D > 1: a load past the wave's stretch is clamped into the array by row_slot and never looked at: issued unconditionally)
+    if constexpr (D == 1) {
+        uint64_t xnext = wlo < whi ? keys[row_slot(wlo)] : 0ull;
+        uint32_t enext = EXT && wlo < whi ? ext[row_slot(wlo)] : 0u;
+        for (uint32_t k0 = wlo; k0 < whi; k0 += RL_EV) {
+            const uint64_t x = xnext;
+            const uint32_t ex = enext;
+            if (k0 + RL_EV < whi) {                                     // in flight during this row's work
+                const uint32_t kn = row_slot(k0 + RL_EV);
+                xnext = keys[kn];
+                if (EXT) enext = ext[kn];
+            }
+            row(k0, x, ex);
+        }
+    } else if constexpr (D == 4) {
+        // (two sets of four rows do not fit the 64 registers of eight waves per SIMD: one set, unrolled in place -- a row's
+        // registers are loaded again, for the row four further on, as soon as the row has been taken out of them)
+        uint64_t xs[D];
+        uint32_t es[D];
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            const uint32_t kn = row_slot(wlo + (uint32_t)d * RL_EV);
+            xs[d] = keys[kn];
+            es[d] = EXT ? ext[kn] : 0u;
+        }
+        for (uint32_t k0 = wlo; k0 < whi; k0 += D * RL_EV) {
+#pragma unroll
+            for (int d = 0; d < D; d++) {
+                const uint64_t x = xs[d];
+                const uint32_t ex = es[d];
+                const uint32_t kn = row_slot(k0 + (uint32_t)(D + d) * RL_EV);
+                xs[d] = keys[kn];
+                es[d] = EXT ? ext[kn] : 0u;
+                if (k0 + (uint32_t)d * RL_EV < whi) row(k0 + (uint32_t)d * RL_EV, x, ex);
+            }
+        }
+    } else {
+        uint64_t xa[D], xb[D];
+        uint32_t ea[D], eb[D];
+        auto fetch = [&](const uint32_t k0, uint64_t (&xs)[D], uint32_t (&es)[D]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int d = 0; d < D; d++) {
+                const uint32_t kn = row_slot(k0 + (uint32_t)d * RL_EV);
+                xs[d] = keys[kn];
+                es[d] = EXT ? ext[kn] : 0u;
+            }
+        };
+        if (wlo < whi) fetch(wlo, xa, ea);
+        for (uint32_t k0 = wlo; k0 < whi; k0 += 2 * D * RL_EV) {
+            fetch(k0 + D * RL_EV, xb, eb);                              // in flight during group a's work
+#pragma unroll
+            for (int d = 0; d < D; d++)
+                if (k0 + (uint32_t)d * RL_EV < whi) row(k0 + (uint32_t)d * RL_EV, xa[d], ea[d]);
+            fetch(k0 + 2 * D * RL_EV, xa, ea);                          // ... during group b's
+#pragma unroll
+            for (int d = 0; d < D; d++)
+                if (k0 + (uint32_t)(D + d) * RL_EV < whi) row(k0 + (uint32_t)(D + d) * RL_EV, xb[d], eb[d]);
+        }
     }
     if (nn) rl_noted(*ap, my_note, nn, &s_pair_n, &s_code_n);
     if (nq) rl_queued(*ap, my_queue, nq, &s_cand_n, &s_tie_n);
@@ -1155,7 +1216,19 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
         FBG_TRY(fbg_reserve(ctx, ctx->kargs, sizeof(RankArgs)));
         memcpy(ctx->kargs_host, &a, sizeof(RankArgs));
         FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->kargs.p, ctx->kargs_host, sizeof(RankArgs), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_rank_scan_lean, dim3(rs_blocks), dim3(RL_THREADS), 0, st, (const RankArgs *)ctx->kargs.p, lf);
+        const RankArgs *d_args = (const RankArgs *)ctx->kargs.p;
+#define RL_LAUNCH(D) \
+    do { \
+        if (lf.ext) hipLaunchKernelGGL((k_rank_scan_lean<D, true>), dim3(rs_blocks), dim3(RL_THREADS), 0, st, d_args, lf); \
+        else hipLaunchKernelGGL((k_rank_scan_lean<D, false>), dim3(rs_blocks), dim3(RL_THREADS), 0, st, d_args, lf); \
+    } while (0)
+        switch (ctx->opt.scan_rows_ahead >= 1 && ctx->opt.scan_rows_ahead <= 4 ? (int)ctx->opt.scan_rows_ahead : RL_ROWS_AHEAD_DEFAULT) {
+        case 1: RL_LAUNCH(1); break;
+        case 2: RL_LAUNCH(2); break;
+        case 3: RL_LAUNCH(3); break;
+        default: RL_LAUNCH(4); break;
+        }
+#undef RL_LAUNCH
     }
     else
         RS_LAUNCH_SCAN(layout, a.g_min <= (uint32_t)a.K || a.values_only, dim3(rs_blocks), st, a);

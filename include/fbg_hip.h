@@ -150,6 +150,9 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *   front_one_fill     0: the counting pass's row totals, byte histogram and counts are cleared by three fills, come back by two
  *                      copies, one of them staged, and the text's sentinel is written after the wait (default 1: one fill, one
  *                      copy into pinned words, the sentinel of a gap-free candidate in front of the counting pass); results unchanged
+ *   scan_rows_ahead    the rows of 64 slots whose loads a wave of the lean rank-order scan (k_rank_scan_lean) keeps in flight
+ *                      while it works on a row: 1 = one row ahead; 2, 3, 4 = groups of that many rows, the next group's loads
+ *                      issued at the top of a group; 0 and any other value = the default, 3; results unchanged
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
  *   path_batch_kib     fbg_pindex_chains_cigar: the KiB of column history in device memory that one batch of reads longer
