@@ -116,6 +116,9 @@ SIGNATURES = {
                                                 C.POINTER(C.c_double)]),
     "fbg_pindex_chains_align_graph_fetch": (C.c_int, [vp, u64p, u32p]),
     "fbg_pindex_align_graph_stats": (C.c_int, [vp] + [u64p] * 10),
+    "fbg_pindex_chains_graph_cigar": (C.c_int, [vp, u32p, u64p, C.POINTER(C.c_double)]),
+    "fbg_pindex_chains_graph_cigar_fetch": (C.c_int, [vp, u64p, u32p]),
+    "fbg_pindex_graph_cigar_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
     "fbg_pindex_seeds_strands": (C.c_int, [vp, u8p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_chain_strands": (C.c_int, [vp, u8p, u32p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "fbg_segmentation_validate": (C.c_int, [vp, u64p, C.c_uint64, u8p, C.c_uint64, u8p, u64p, u64p, C.POINTER(C.c_double)]),

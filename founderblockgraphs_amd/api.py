@@ -602,8 +602,17 @@ class PatternIndex:
         self._eng._chk(self._L.fbg_pindex_align_graph_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(self.GRAPH_STATS, (x.value for x in v)))
 
+    def graph_cigar_stats(self):
+        """{paths, ops, columns, history_bytes, batches} of the last chains(graph=True, graph_cigar=True)
+        (fbg_pindex_graph_cigar_stats; an index built with rows=True only), with the meaning of cigar_stats(): the reads
+        traced, their runs, the sum of the lengths of the stretches of the graph they lie on, the bytes of column history
+        that went to device memory and the batches those reads were worked off in."""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._eng._chk(self._L.fbg_pindex_graph_cigar_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("paths", "ops", "columns", "history_bytes", "batches"), (x.value for x in v)))
+
     def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False, by_row=False,
-               graph=False, graph_pad=16, max_cells=0, select=None):
+               graph=False, graph_pad=16, max_cells=0, select=None, graph_cigar=False):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -624,9 +633,14 @@ class PatternIndex:
         chain, graph_pad symbols beyond the anchors, and that path (fbg_pindex_chains_align_graph and _fetch), as
         Chains.graph_edits, .graph_start, .graph_end, .graph_path_off, .graph_path_nodes and .graph_path(k); a read whose
         window takes more than max_cells cells (0: no limit) is skipped, and so is one whose entry of select (one per
-        read of the last seeds() call, None: all) is zero.  After seeds(strands=True) also Chains.best_graph_edits."""
+        read of the last seeds() call, None: all) is zero.  After seeds(strands=True) also Chains.best_graph_edits.
+        graph_cigar=True (with graph=True): also the alignment path of every such read against the stretch of the graph its
+        path spells (fbg_pindex_chains_graph_cigar and _fetch), as Chains.graph_cigar_off and .graph_cigar_ops, read with
+        .graph_cigar(k) and .graph_cigar_runs(k)."""
         if cigar and not align:
             raise ValueError("cigar=True needs align=True")
+        if graph_cigar and not graph:
+            raise ValueError("graph_cigar=True needs graph=True")
         if band is not None and band < 0:
             raise ValueError("band must be 0 or more, or None")
         if min_score < 0:
@@ -714,6 +728,13 @@ class PatternIndex:
                 pick = np.where(out.strand[:given] == 1, given, 0) + np.arange(given)
                 out.best_graph_edits = np.where(out.strand[:given] == _lib.STRAND_NONE, np.uint32(_lib.ALIGN_NONE),
                                                 out.graph_edits[pick] if given else out.graph_edits[:0]).astype(np.uint32)
+        if graph_cigar:
+            coff = np.zeros(k + 1, dtype=np.uint64)
+            total, ms8 = C.c_uint64(0), C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chains_graph_cigar(self._h, None, C.byref(total), C.byref(ms8)))
+            ops = np.zeros(max(total.value, 1), dtype=np.uint32)
+            self._eng._chk(self._L.fbg_pindex_chains_graph_cigar_fetch(self._h, _u64(coff), ops.ctypes.data_as(_lib.u32p)))
+            out.graph_cigar_off, out.graph_cigar_ops, out.graph_cigar_ms = coff, ops[:total.value], ms8.value
         return out
 
     def by_row_stats(self):
@@ -937,6 +958,11 @@ class Chains:
       graph_path_nodes   uint32 per path entry: the nodes from the start node to the end node; graph_path(k) gives read k's
       best_graph_edits   after seeds(strands=True): uint32 per given read, graph_edits of the strand that strand picked
       graph_ms        device time of fbg_pindex_chains_align_graph
+    and, asked for with graph_cigar=True beside graph=True (None otherwise; include/fbg_hip.h, fbg_pindex_chains_graph_cigar):
+      graph_cigar_off   uint64[k + 1], CSR offsets of the reads' runs; a read without a graph alignment has none
+      graph_cigar_ops   uint32 per run, as cigar_ops, in the order of the read and of its path; graph_cigar(k) gives the
+                      string, graph_cigar_runs(k) the (code, length) pairs
+      graph_cigar_ms  device time of fbg_pindex_chains_graph_cigar
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -951,6 +977,7 @@ class Chains:
         self.cigar_off = self.cigar_ops = self.cigar_ms = None
         self.graph_edits = self.graph_start = self.graph_end = self.graph_path_off = self.graph_path_nodes = None
         self.best_graph_edits = self.graph_ms = None
+        self.graph_cigar_off = self.graph_cigar_ops = self.graph_cigar_ms = None
 
     def cigar_runs(self, k):
         """int64[runs, 2]: (code, length) of the runs of read k's alignment path; no rows without an alignment."""
@@ -962,6 +989,17 @@ class Chains:
     def cigar(self, k):
         """The alignment path of read k as a CIGAR string with = and X, such as 25=1X24=; "" without an alignment."""
         return "".join(f"{n}{_lib.CIGAR_OPS[c]}" for c, n in self.cigar_runs(k).tolist())
+
+    def graph_cigar_runs(self, k):
+        """int64[runs, 2]: (code, length) of the runs of read k's alignment path in the graph; no rows without one."""
+        if self.graph_cigar_off is None:
+            raise ValueError("no paths: ask for them with graph=True, graph_cigar=True")
+        v = self.graph_cigar_ops[int(self.graph_cigar_off[k]):int(self.graph_cigar_off[k + 1])].astype(np.int64)
+        return np.stack((v & 15, v >> 4), axis=1)
+
+    def graph_cigar(self, k):
+        """The alignment path of read k against its stretch of the graph as a CIGAR string; "" without an alignment."""
+        return "".join(f"{n}{_lib.CIGAR_OPS[c]}" for c, n in self.graph_cigar_runs(k).tolist())
 
     def graph_path(self, k):
         """int64[n_path]: the nodes of read k's path in the graph, from its start node to its end node."""

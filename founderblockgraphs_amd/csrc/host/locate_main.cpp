@@ -4,7 +4,7 @@
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
 //              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--by-row] [--align[=PAD]] [--cigar]
-//              [--graph-align[=PAD]]
+//              [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -64,6 +64,15 @@
 //   H <tab> edits <tab> start_node <tab> start_offset <tab> end_node <tab> end_offset <tab> path
 // the fewest edits, the S ids and offsets at which the stretch of the graph starts and ends, and the nodes from the start
 // to the end as >u>v>w; or `H <tab> *` when there is no alignment.  Without --graph-align no byte changes.
+// --graph-cigar (with --graph-align) appends to every H line with numbers an eighth field, the alignment path of the pattern
+// against that stretch of the path's labels (fbg_pindex_chains_graph_cigar): runs of = X I D in pattern order and in path
+// order, such as 25=1X24=.  `H <tab> *` stays as it is, and without --graph-cigar no byte changes.
+// --gaf=FILE (with --graph-cigar) writes one GAF record per H line with numbers, in the order of those lines, to FILE;
+// stdout does not change.  Tab-separated: read<k> (k the pattern's index in the input, from 0), L, 0, L (the pattern is
+// aligned whole; I runs at either end stay in the CIGAR), + or - (the reverse complement), the path as >id>id, the sum of
+// the path's label lengths, start_offset, that sum - |label(end_node)| + end_offset, the number of = symbols, the number of
+// alignment columns (= X I D), 255, NM:i:edits and cg:Z:runs.  For - the CIGAR is in path order, PAF's convention.  A FILE
+// that cannot be written fails before any search.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -82,7 +91,7 @@ static int usage(const char *msg)
     std::cerr << "fbg_locate: " << msg << "\n"
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
-              << "                  [--by-row] [--align[=PAD]] [--cigar] [--graph-align[=PAD]]\n"
+              << "                  [--by-row] [--align[=PAD]] [--cigar] [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -117,7 +126,11 @@ static int usage(const char *msg)
               << "  --graph-align[=PAD]  needs --chain and --rows: after a chain's lines an H line: the fewest edits between the\n"
               << "                     pattern and a stretch of a path of the graph through the blocks around the chain, PAD\n"
               << "                     symbols (default 16) beyond its anchors, the node and offset at which that stretch\n"
-              << "                     starts and ends, and the path as >u>v>w (H and * if there is no alignment)\n";
+              << "                     starts and ends, and the path as >u>v>w (H and * if there is no alignment)\n"
+              << "  --graph-cigar      needs --graph-align: an H line with numbers ends with the alignment path of the pattern\n"
+              << "                     against that stretch, runs of = X I D in pattern and path order; no other line changes\n"
+              << "  --gaf=FILE         needs --graph-cigar: one GAF record per H line with numbers goes to FILE (read<k>, the\n"
+              << "                     path as >id>id with its coordinates, matches, alignment columns, 255, NM:i: and cg:Z:)\n";
     return EXIT_FAILURE;
 }
 
@@ -189,9 +202,19 @@ static void print_places(const XgfaGraph &g, uint64_t k, const std::vector<uint6
     }
 }
 
+// the runs ops[a .. b) as 25=1X24=
+static void print_runs(std::ostream &os, const std::vector<uint32_t> &ops, uint64_t a, uint64_t b)
+{
+    for (uint64_t i = a; i < b; i++) {
+        const uint32_t code = ops[i] & 15;
+        os << (ops[i] >> 4) << (code == FBG_CIGAR_EQ ? '=' : code == FBG_CIGAR_X ? 'X' : code == FBG_CIGAR_I ? 'I' : 'D');
+    }
+}
+
 int main(int argc, char **argv)
 {
-    std::string graph, patterns, msa_path, complement;
+    std::string graph, patterns, msa_path, complement, gaf_path;
+    bool graph_cigar = false, have_gaf = false;
     bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false, graph_align = false;
     uint64_t graph_pad = 16;
     uint64_t pad = 16;
@@ -206,7 +229,8 @@ int main(int argc, char **argv)
             return false;
         };
         if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns) ||
-            value("--msa", msa_path, have_msa) || value("--complement", complement, have_complement)) continue;
+            value("--msa", msa_path, have_msa) || value("--complement", complement, have_complement) ||
+            value("--gaf", gaf_path, have_gaf)) continue;
         if (a == "--strands") { strands = true; continue; }
         if (a == "--rows") { rows = true; continue; }
         if (a == "--by-row") { by_row = true; continue; }
@@ -260,6 +284,7 @@ int main(int argc, char **argv)
             pad = m;
             continue;
         }
+        if (a == "--graph-cigar") { graph_cigar = true; continue; }
         if (a == "--graph-align") { graph_align = true; continue; }
         if (a.compare(0, 14, "--graph-align=") == 0) {
             const std::string v = a.substr(14);
@@ -285,9 +310,17 @@ int main(int argc, char **argv)
     if (cigar && !align) return usage("--cigar needs --align");
     if (align && !(chain && rows)) return usage("--align needs --chain and --rows");
     if (graph_align && !(chain && rows)) return usage("--graph-align needs --chain and --rows");
+    if (graph_cigar && !graph_align) return usage("--graph-cigar needs --graph-align");
+    if (have_gaf && !graph_cigar) return usage("--gaf needs --graph-cigar");
+    if (have_gaf && gaf_path.empty()) return usage("--gaf takes a file");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
 
+    std::ofstream gaf;
+    if (have_gaf) {
+        gaf.open(gaf_path, std::ios::binary | std::ios::trunc);
+        if (!gaf) { std::cerr << "fbg_locate: cannot write " << gaf_path << "\n"; return EXIT_FAILURE; }
+    }
     XgfaGraph g;
     std::string error;
     if (!read_xgfa_graph(graph, g, error)) { std::cerr << "fbg_locate: " << error << "\n"; return EXIT_FAILURE; }
@@ -385,6 +418,8 @@ int main(int argc, char **argv)
     std::vector<uint32_t> on_graph[5];                      // --graph-align: edits, start node and offset, end node and offset
     std::vector<uint64_t> path_off(nv + 1, 0);
     std::vector<uint32_t> path_nodes;
+    std::vector<uint64_t> gcigar_off(nv + 1, 0);            // --graph-cigar: the runs of every virtual read
+    std::vector<uint32_t> gcigar_ops;
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -448,6 +483,12 @@ int main(int argc, char **argv)
             path_nodes.resize(total + 1);
             if (rc == FBG_OK) rc = fbg_pindex_chains_align_graph_fetch(ix, path_off.data(), path_nodes.data());
         }
+        if (rc == FBG_OK && graph_cigar) {
+            uint64_t total = 0;
+            rc = fbg_pindex_chains_graph_cigar(ix, nullptr, &total, nullptr);
+            gcigar_ops.resize(total + 1);
+            if (rc == FBG_OK) rc = fbg_pindex_chains_graph_cigar_fetch(ix, gcigar_off.data(), gcigar_ops.data());
+        }
     }
     if (rc == FBG_OK && !occurrences && !seeds)
         rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
@@ -498,11 +539,7 @@ int main(int argc, char **argv)
                     std::cout << "G\t" << aligned[0][v] << '\t' << aligned[1][v] << '\t' << aligned[2][v] << '\t' << aligned[3][v];
                     if (cigar) {
                         std::cout << '\t';
-                        for (uint64_t i = cigar_off[v]; i < cigar_off[v + 1]; i++) {
-                            const uint32_t code = cigar_ops[i] & 15;
-                            std::cout << (cigar_ops[i] >> 4)
-                                      << (code == FBG_CIGAR_EQ ? '=' : code == FBG_CIGAR_X ? 'X' : code == FBG_CIGAR_I ? 'I' : 'D');
-                        }
+                        print_runs(std::cout, cigar_ops, cigar_off[v], cigar_off[v + 1]);
                     }
                     std::cout << '\n';
                 }
@@ -511,7 +548,31 @@ int main(int argc, char **argv)
                     std::cout << "H\t" << on_graph[0][v] << '\t' << g.ids[on_graph[1][v]] << '\t' << on_graph[2][v] << '\t'
                               << g.ids[on_graph[3][v]] << '\t' << on_graph[4][v] << '\t';
                     for (uint64_t i = path_off[v]; i < path_off[v + 1]; i++) std::cout << '>' << g.ids[path_nodes[i]];
+                    if (graph_cigar) {
+                        std::cout << '\t';
+                        print_runs(std::cout, gcigar_ops, gcigar_off[v], gcigar_off[v + 1]);
+                    }
                     std::cout << '\n';
+                    if (have_gaf) {
+                        const uint64_t k = v < np ? v : v - np, L = off[k + 1] - off[k];
+                        uint64_t plen = 0, match = 0, cols = 0;
+                        gaf << "read" << k << '\t' << L << "\t0\t" << L << '\t' << (v < np ? '+' : '-') << '\t';
+                        for (uint64_t i = path_off[v]; i < path_off[v + 1]; i++) {
+                            const uint32_t u = path_nodes[i];
+                            gaf << '>' << g.ids[u];
+                            plen += g.label_off[u + 1] - g.label_off[u];
+                        }
+                        for (uint64_t i = gcigar_off[v]; i < gcigar_off[v + 1]; i++) {
+                            cols += gcigar_ops[i] >> 4;
+                            if ((gcigar_ops[i] & 15) == FBG_CIGAR_EQ) match += gcigar_ops[i] >> 4;
+                        }
+                        const uint32_t ve = on_graph[3][v];
+                        gaf << '\t' << plen << '\t' << on_graph[2][v] << '\t'
+                            << plen - (g.label_off[ve + 1] - g.label_off[ve]) + on_graph[4][v] << '\t' << match << '\t' << cols
+                            << "\t255\tNM:i:" << on_graph[0][v] << "\tcg:Z:";
+                        print_runs(gaf, gcigar_ops, gcigar_off[v], gcigar_off[v + 1]);
+                        gaf << '\n';
+                    }
                 }
             }
         };
@@ -534,6 +595,10 @@ int main(int argc, char **argv)
             }
         }
         std::cout << "Pattern? " << found << " out of " << np << " patterns seeded" << std::endl;
+        if (have_gaf) {
+            gaf.close();
+            if (!gaf) { std::cerr << "fbg_locate: cannot write " << gaf_path << "\n"; return EXIT_FAILURE; }
+        }
         return EXIT_SUCCESS;
     }
     for (uint64_t k = 0; k < np; k++) {

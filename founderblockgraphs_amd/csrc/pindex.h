@@ -8,6 +8,7 @@
 //   pindex_byrow.hip      chaining along one row: per read the row whose supported anchors chain best
 //   pindex_align.hip      edit distance of a read to a row of its chain, and the alignment path
 //   pindex_graph.hip      edit distance of a read to a path of the graph around its chain, and that path
+//   pindex_gcigar.hip     the alignment path of a read against the stretch of the graph that path spells
 // Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
 // needs its launch calls a launcher declared at the end of this header.
 #pragma once
@@ -128,6 +129,15 @@ struct PhState {
     uint64_t stat[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};     // aligned, not_selected, too_long, too_wide, cells, nodes, merges, path_nodes, batches
 };
 
+// fbg_pindex_chains_graph_cigar.  Per read of the last graph call, in the shape k_pg_sizes and k_pg_path read of the row
+// call: info = (0, 0, N, L), out (4 n: unused, edits, 0, N), wlen = N or 0 and its scan woff (n + 1 each); text: the
+// stretches T, back to back; bad: the count of paths that spell no such stretch; g: the sizes, slots, runs and history
+// of the trace, a PgState of this call's own.
+struct PjState {
+    DevBuf info, out, wlen, woff, text, bad;
+    PgState g;
+};
+
 struct fbg_pindex {
     fbg_ctx *ctx = nullptr;
     uint64_t N1 = 0;          // text length including the sentinel
@@ -173,6 +183,7 @@ struct fbg_pindex {
     PgState cg;
     PbState pb;
     PhState gr;
+    PjState gj;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, sv0 = nullptr, sv1 = nullptr;   // made with the index (px_new)
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -341,6 +352,16 @@ struct PxScratch {
     ~PxScratch() { fbg_release_all(nullptr, bufs); }
 };
 
+// What k_pg_sizes and k_pg_path read of the call whose alignments they trace, n reads: info[R] = (-, w0, -, L); out (4 n):
+// out[n + R] the edits or PA_NONE, then the start and the end of T in the positions that w0 is counted in; T itself at
+// win + woff[R] + (start - w0).
+struct PgIn {
+    const uint4 *info;
+    const uint64_t *woff;
+    const uint8_t *win;
+    const uint32_t *out;
+};
+
 // ---- host functions that cross files ---------------------------------------------------------------------------------
 PX_LOCAL int px_new(fbg_ctx *ctx, fbg_pindex **out);       // pindex_build.hip: a new index object with its events
 PX_LOCAL int px_build_segmentation(fbg_pindex *ix, PxScratch &s, const uint64_t *boundaries, uint64_t nb, bool with_map, bool with_rows = false);
@@ -362,3 +383,9 @@ PX_LOCAL int pr_save_reads(fbg_pindex *ix);
 PX_LOCAL int pr_prepare(fbg_pindex *ix, PrDev &d);
 PX_LOCAL void pr_chain_launch(fbg_pindex *ix, const PrDev &d, uint64_t n, uint64_t words, uint32_t *n_rows, uint32_t *first_row,
                               uint64_t *bits, unsigned long long *ctr);
+// pindex_align.hip: k_pg_sizes, k_pg_path per tier and batch and k_pg_compact over the alignments of in (NULL: nothing of
+// them is on the device, n reads without runs) into g, for the call `who`; started: the caller recorded ev0 with kernels of
+// its own.  Ends with px_sync_elapsed.  And the copy of g's offsets and runs to the host
+PX_LOCAL int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, uint64_t n, bool started, uint32_t *n_ops, uint64_t *total_ops,
+                      double *device_ms, const char *who);
+PX_LOCAL int pg_fetch(fbg_pindex *ix, const PgState &g, uint64_t *off, uint32_t *ops);

@@ -519,8 +519,8 @@ extern "C" int fbg_pindex_align_stats(const fbg_pindex *ix, uint64_t *aligned, u
 }
 
 // ---- alignment path (fbg_pindex_chains_cigar / _cigar_fetch / _cigar_stats) ----------------------------------------
-// Sizes and their scans, the host's look at the history offsets (which form the batches), the slot total and the tier
-// counts; one k_pg_path launch per word count that has reads, then one per batch of longer reads, all on the stream and
+// pg_trace, which fbg_pindex_chains_graph_cigar (pindex_gcigar.hip) runs too, on alignments and a state of its own: sizes
+// and their scans, the host's look at the history offsets (which form the batches), the slot total and the tier counts; one k_pg_path launch per word count that has reads, then one per batch of longer reads, all on the stream and
 // so one after the other in the one scratch; a scan of the run counts, the host's look at their sum, the compaction.
 static int pg_check(const fbg_pindex *ix, const char *who)
 {
@@ -532,28 +532,23 @@ static int pg_check(const fbg_pindex *ix, const char *who)
 }
 
 template <int NW>
-static void pg_launch(hipStream_t st, const PaDev &a, const PaState &al, PgState &g, uint64_t n, uint64_t first, uint64_t reads, uint32_t cap,
+static void pg_launch(hipStream_t st, const PaDev &a, const PgIn &in, PgState &g, uint64_t n, uint64_t first, uint64_t reads, uint32_t cap,
                       uint64_t hbase)
 {
-    hipLaunchKernelGGL(k_pg_path<NW>, dim3((unsigned)reads), dim3(FBG_WAVE), NW ? (size_t)NW * 16 * (cap ? cap : 1) : 0, st, a,
-                       (const uint4 *)al.info.as<uint4>(), (const uint64_t *)al.woff.as<uint64_t>(), (const uint8_t *)al.win.as<uint8_t>(),
-                       (const uint32_t *)al.out.as<uint32_t>(), n, first, cap, (const uint64_t *)g.hoff.as<uint64_t>(), hbase,
-                       g.hist.as<uint64_t>(), (const uint64_t *)g.soff.as<uint64_t>(), g.slots.as<uint32_t>(), g.cnt.as<uint64_t>(),
-                       g.nops.as<uint32_t>(), g.ctr.as<unsigned long long>());
+    hipLaunchKernelGGL(k_pg_path<NW>, dim3((unsigned)reads), dim3(FBG_WAVE), NW ? (size_t)NW * 16 * (cap ? cap : 1) : 0, st, a, in.info, in.woff,
+                       in.win, in.out, n, first, cap, (const uint64_t *)g.hoff.as<uint64_t>(), hbase, g.hist.as<uint64_t>(),
+                       (const uint64_t *)g.soff.as<uint64_t>(), g.slots.as<uint32_t>(), g.cnt.as<uint64_t>(), g.nops.as<uint32_t>(),
+                       g.ctr.as<unsigned long long>());
 }
 
-extern "C" int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t *total_ops, double *device_ms)
+int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, uint64_t n, bool started, uint32_t *n_ops, uint64_t *total_ops, double *device_ms,
+             const char *who)
 {
-    if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
-    const PaState &al = ix->al;
-    PgState &g = ix->cg;
-    FBG_TRY(pg_check(ix, "fbg_pindex_chains_cigar"));
     if (device_ms) *device_ms = 0;
     if (total_ops) *total_ops = 0;
-    const uint64_t n = al.n;
     g.ready = false;
-    if (n == 0 || !al.on_device) {            // no reads, or every chain empty: nothing of that align call on the device
+    if (n == 0 || !in) {
         if (n_ops) std::fill(n_ops, n_ops + n, (uint32_t)0);
         std::fill(g.stat, g.stat + 5, (uint64_t)0);
         g.n = n;
@@ -572,12 +567,11 @@ extern "C" int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t
     uint64_t *hsz = g.sz.as<uint64_t>(), *ssz = hsz + (n + 1), *hoff = g.hoff.as<uint64_t>(), *soff = g.soff.as<uint64_t>();
     uint64_t *cnt = g.cnt.as<uint64_t>(), *off = g.off.as<uint64_t>();
     auto *ctr = g.ctr.as<unsigned long long>();
-    FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
+    if (!started) FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ctr, 0, PG_CTR * 8, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(cnt, 0, (n + 1) * 8, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(g.nops.p, 0, n * 4, st));
-    hipLaunchKernelGGL(k_pg_sizes, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, (const uint4 *)al.info.as<uint4>(),
-                       (const uint32_t *)al.out.as<uint32_t>(), n, hsz, ssz, ctr);
+    hipLaunchKernelGGL(k_pg_sizes, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, in->info, in->out, n, hsz, ssz, ctr);
     for (int k = 0; k < 2; k++)
         FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
             return rocprim::exclusive_scan(tmp, bytes, k ? ssz : hsz, k ? soff : hoff, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
@@ -610,11 +604,11 @@ extern "C" int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t
     }
     FBG_TRY(px_reserve(ix, g.slots, (nslots + 1) * 4));
     if (units) FBG_TRY(px_reserve(ix, g.hist, units * 8));
-    if (c[3]) pg_launch<1>(st, a, al, g, n, 0, n, (uint32_t)c[8], 0);
-    if (c[4]) pg_launch<2>(st, a, al, g, n, 0, n, (uint32_t)c[9], 0);
-    if (c[5]) pg_launch<3>(st, a, al, g, n, 0, n, (uint32_t)c[10], 0);
-    if (c[6]) pg_launch<4>(st, a, al, g, n, 0, n, (uint32_t)c[11], 0);
-    for (const auto &b : batch) pg_launch<0>(st, a, al, g, n, b.first, b.second - b.first, 0, h[b.first]);
+    if (c[3]) pg_launch<1>(st, a, *in, g, n, 0, n, (uint32_t)c[8], 0);
+    if (c[4]) pg_launch<2>(st, a, *in, g, n, 0, n, (uint32_t)c[9], 0);
+    if (c[5]) pg_launch<3>(st, a, *in, g, n, 0, n, (uint32_t)c[10], 0);
+    if (c[6]) pg_launch<4>(st, a, *in, g, n, 0, n, (uint32_t)c[11], 0);
+    for (const auto &b : batch) pg_launch<0>(st, a, *in, g, n, b.first, b.second - b.first, 0, h[b.first]);
     FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
         return rocprim::exclusive_scan(tmp, bytes, cnt, off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st);
     }));
@@ -624,8 +618,7 @@ extern "C" int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&failed, ctr, 8, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (failed)
-        return fbg_fail(ctx, FBG_ERR_HIP, "fbg_pindex_chains_cigar: the trace of %llu reads did not arrive at the read's start", failed);
+    if (failed) return fbg_fail(ctx, FBG_ERR_HIP, "%s: the trace of %llu reads did not arrive at the read's start", who, failed);
     FBG_TRY(px_reserve(ix, g.ops, (total + 1) * 4));
     if (total) {
         hipLaunchKernelGGL(k_pg_compact, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, (const uint64_t *)soff, (const uint32_t *)g.slots.as<uint32_t>(),
@@ -645,13 +638,9 @@ extern "C" int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t
     return FBG_OK;
 }
 
-extern "C" int fbg_pindex_chains_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint32_t *ops)
+int pg_fetch(fbg_pindex *ix, const PgState &g, uint64_t *off, uint32_t *ops)
 {
-    if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
-    const PgState &g = ix->cg;
-    FBG_TRY(pg_check(ix, "fbg_pindex_chains_cigar_fetch"));
-    if (!g.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_cigar_fetch: no fbg_pindex_chains_cigar result since that align call");
     if (!g.on_device) {
         if (off) std::fill(off, off + g.n + 1, (uint64_t)0);
         return FBG_OK;
@@ -662,6 +651,25 @@ extern "C" int fbg_pindex_chains_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint
     if (ops && g.total) FBG_HIP_TRY(ctx, hipMemcpyAsync(ops, g.ops.p, g.total * 4, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return FBG_OK;
+}
+
+extern "C" int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t *total_ops, double *device_ms)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    const PaState &al = ix->al;
+    FBG_TRY(pg_check(ix, "fbg_pindex_chains_cigar"));
+    // no reads, or every chain empty: nothing of that align call on the device
+    const PgIn in = {al.info.as<uint4>(), al.woff.as<uint64_t>(), al.win.as<uint8_t>(), al.out.as<uint32_t>()};
+    return pg_trace(ix, al.on_device ? &in : nullptr, ix->cg, al.n, false, n_ops, total_ops, device_ms, "fbg_pindex_chains_cigar");
+}
+
+extern "C" int fbg_pindex_chains_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint32_t *ops)
+{
+    if (!ix) return FBG_ERR_INVALID;
+    FBG_TRY(pg_check(ix, "fbg_pindex_chains_cigar_fetch"));
+    if (!ix->cg.ready)
+        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "fbg_pindex_chains_cigar_fetch: no fbg_pindex_chains_cigar result since that align call");
+    return pg_fetch(ix, ix->cg, off, ops);
 }
 
 extern "C" int fbg_pindex_cigar_stats(const fbg_pindex *ix, uint64_t *paths, uint64_t *ops, uint64_t *columns, uint64_t *history_bytes,

@@ -531,7 +531,7 @@ extern "C" int fbg_pindex_chains_align_graph(fbg_pindex *ix, uint64_t pad, uint6
     FBG_TRY(ph_check(ix, "fbg_pindex_chains_align_graph"));
     std::fill(g.stat, g.stat + 9, (uint64_t)0);
     const uint64_t n = c.n;
-    g.valid = g.on_device = false;
+    g.valid = g.on_device = ix->gj.g.ready = false;       // the CIGARs belong to the graph call they were traced from
     g.n = n;
     g.total = 0;
     if (n == 0) { g.valid = true; return FBG_OK; }

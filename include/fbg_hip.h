@@ -155,9 +155,9 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *                      issued at the top of a group; 0 and any other value = the default, 3; results unchanged
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
- *   path_batch_kib     fbg_pindex_chains_cigar: the KiB of column history in device memory that one batch of reads longer
- *                      than 256 symbols may take (default 2^20, 1 GiB; values below 1 count as 1); a read whose own history
- *                      is larger is a batch of its own; results unchanged
+ *   path_batch_kib     fbg_pindex_chains_cigar and _chains_graph_cigar: the KiB of column history in device memory that
+ *                      one batch of reads longer than 256 symbols may take (default 2^20, 1 GiB; values below 1 count as
+ *                      1); a read whose own history is larger is a batch of its own; results unchanged
  *   byrow_max          fbg_pindex_chains_by_row: the most start places of a read that is still chained (default 1024;
  *                      negative values count as 0); a read with more gets no row and no chain and is counted
  *   byrow_lds          fbg_pindex_chains_by_row: 0 (default) keeps the state of reads of up to lds_max start places in LDS,
@@ -1030,7 +1030,8 @@ int fbg_pindex_cigar_stats(const fbg_pindex *ix, uint64_t *paths, uint64_t *ops,
  * n_path 0, and is no error: an empty chain; a read that select leaves out (not_selected counts those with a chain);
  * too long, L > max_read (1024, as fbg_pindex_chains_align); too wide, max_cells != 0 and cells > max_cells, tested after
  * too long.  An anchor whose place lies outside its node's label (none on a graph of a segmentation) is passed over.
- * Limits: no CIGAR over the path; unit costs only, no affine gaps; every node of the window's blocks is computed, no
+ * Limits: no CIGAR over the path from this call (fbg_pindex_chains_graph_cigar, below, traces it afterwards); unit costs
+ * only, no affine gaps; every node of the window's blocks is computed, no
  * pruning inside it, so the cost grows with the distinct nodes per block -- on an MSA of a thousand similar rows a block
  * can hold hundreds -- which is what select is for: graph-align the reads the row alignment left out or left poor.
  *
@@ -1071,6 +1072,52 @@ int fbg_pindex_chains_align_graph_fetch(fbg_pindex *ix, uint64_t *path_off, uint
 int fbg_pindex_align_graph_stats(const fbg_pindex *ix, uint64_t *aligned, uint64_t *not_selected, uint64_t *too_long,
                                  uint64_t *too_wide, uint64_t *cells, uint64_t *nodes, uint64_t *merges, uint64_t *path_nodes,
                                  uint64_t *table_bytes, uint64_t *batches);
+
+/* The alignment path (CIGAR) of each read that the last fbg_pindex_chains_align_graph aligned, against the stretch of the
+ * graph that its path spells (after a successful fbg_pindex_chains_align_graph since the last chaining call).
+ *
+ * For a (virtual) read R with edits[R] != FBG_ALIGN_NONE let P be its text as that call read it (rc(P_R) for a reverse
+ * virtual read) and L = |P|.  spell(path) is the labels of the path's nodes back to back, and
+ *   T = spell(path)[start_offset : |spell(path)| - |label(end_node)| + end_offset],   N = |T|:
+ * with start_node == end_node it is label[start_offset : end_offset], and for the empty alignment (edits == L, the end and
+ * the start at offset 0 of the first node of block jl) it is empty and the path is the single run L I.  By the
+ * definition of the graph call lev(P, T) == edits.  The runs are those of fbg_pindex_chains_cigar's definition with this
+ * T: E(i, j) = lev(P[i:], T[j:]), the walk from (0, 0) to (L, N) that prefers the diagonal, then I, then D, equal
+ * consecutive ops merged, a run length << 4 | code with the FBG_CIGAR_* codes, in the order of P and of the path (for a
+ * reverse virtual read: of rc(P_R), which is PAF's and GAF's convention).  It follows that #X + #I + #D == edits,
+ * #= + #X + #I == L, #= + #X + #D == N, that a read has at most 2 * edits + 1 runs, that its first and last run are never
+ * D (both ends are free in the graph and edits is the minimum), and that N <= L + edits <= 2 L, so the LDS bound of the
+ * row call carries over.  A read without a graph alignment has zero runs.  The CIGAR is one over the whole stretch: it
+ * is not split node by node.
+ *
+ *   fbg_pindex_chains_graph_cigar        n_ops: the number of runs, one entry per read of that graph call; *total_ops:
+ *       their sum; *device_ms: device time of the kernels.  Any pointer may be NULL.
+ *   fbg_pindex_chains_graph_cigar_fetch  off[n + 1], the scan of n_ops, and ops[off[n]], the runs back to back: count
+ *       then fetch, as fbg_pindex_chains_cigar / _cigar_fetch.  Either may be NULL.
+ *   fbg_pindex_graph_cigar_stats         any pointer may be NULL.  Of the last successful fbg_pindex_chains_graph_cigar (0
+ *       before the first; a failing call leaves them), with the meaning of fbg_pindex_cigar_stats: the reads traced; the
+ *       total number of runs; columns, the sum of N; history_bytes, the column history that went to device memory and not
+ *       to LDS; the batches that took.
+ * On the device, from what the graph call left there (edits, the two offsets, the path CSR, L): only the sizes that the
+ * launches need come to the host.  One lane per read sums the label lengths of its path into N and lays the read out as
+ * the row call's kernels take it; a path that spells no stretch of at most L + edits symbols fails the call with
+ * FBG_ERR_HIP.  After a scan of N a wave per read copies T label by label into one text buffer, the lanes along the
+ * bytes, the first node clipped by start_offset and the last by N.  The trace is that of fbg_pindex_chains_cigar, the
+ * same kernels on (P, T): run slots and history units per read, the history in LDS for reads of 1 to 4 words (one launch
+ * per word count, sized by the widest T of that count) and in scratch for longer reads, in batches of consecutive reads
+ * that fit option path_batch_kib (which means here what it means there), a scan of the run counts and the compaction.
+ * Every loop is bounded; a trace that does not arrive writes zero runs and fails the call with FBG_ERR_HIP.
+ * The calls may be repeated and leave every other state alone, the graph alignment and its path, the row alignment and
+ * the row CIGAR (whose buffers they do not share) included; like the align calls they still work after a later
+ * fbg_pindex_locate or fbg_pindex_occurrences.  A later seeds call, chaining call or fbg_pindex_chains_align_graph
+ * invalidates the result.
+ * Errors, all FBG_ERR_INVALID: a NULL index; an index without the row table; no successful fbg_pindex_chains_align_graph
+ * since the last chaining call; _fetch without a successful _graph_cigar since that graph call.  No reads, or a graph call
+ * that left nothing on the device (every chain empty), returns FBG_OK with zeros. */
+int fbg_pindex_chains_graph_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t *total_ops, double *device_ms);
+int fbg_pindex_chains_graph_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint32_t *ops);
+int fbg_pindex_graph_cigar_stats(const fbg_pindex *ix, uint64_t *paths, uint64_t *ops, uint64_t *columns, uint64_t *history_bytes,
+                                 uint64_t *batches);
 
 /* fbg_segmentation_validate: the semi-repeat-free check (fbg_pindex_validate's rules) of the graph of a segmentation
  * of the current MSA.  cut_bad[k] = 1 iff block k + 1 holds an INVALID node -- the reference's
