@@ -229,6 +229,7 @@ static const OptKey g_opt_keys[] = {
     {"twin_hash", &FbgOptions::twin_hash},
     {"front_one_fill", &FbgOptions::front_one_fill},
     {"scan_rows_ahead", &FbgOptions::scan_rows_ahead},
+    {"msd_cursors", &FbgOptions::msd_cursors},
     {"path_batch_kib", &FbgOptions::path_batch_kib},
     {"byrow_max", &FbgOptions::byrow_max},
     {"byrow_lds", &FbgOptions::byrow_lds},

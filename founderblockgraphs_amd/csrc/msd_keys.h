@@ -6,6 +6,15 @@
 #define MSD_SEP 0x80                           // FBG_SEP of suffix_sort.hip
 #define MSD_ITEMS 8
 
+// Pass 1 of both sorts keeps one run cursor per stretch (bucket d of nb, part xq of xs: one part per XCD).  The stretch's
+// number d * xs + xq says where it lies in the pass-1 buffer and in tile_start; its cursor lies at xq * nb + d (contig,
+// option msd_cursors, the default), so that the 64 lanes of a reserving wave -- 64 buckets, one part -- add to consecutive
+// words, one 256-byte request; at the stretch's own number (contig = false, the earlier placement) they lie xs words apart.
+__host__ __device__ __forceinline__ uint32_t msd_cursor_index(uint32_t d, uint32_t xq, uint32_t xs, uint32_t nb, bool contig)
+{
+    return contig ? xq * nb + d : d * xs + xq;
+}
+
 // The symbol codes of text positions base .. base + TILE + 64 go to LDS in two steps, so that a kernel walking several
 // tiles can have the next tile's loads in flight: msd_fetch_raw (8 text bytes per thread, threads 0..7 also the 64
 // bytes of lookahead; T is padded beyond N, base is a multiple of 8) and msd_store_tile (code table cd in LDS).

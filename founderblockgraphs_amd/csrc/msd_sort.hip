@@ -62,8 +62,9 @@ struct MsdArgs {
     uint64_t cap1;
     int xs;                                    // stretches per bucket (1, or 8: one per XCD, see k_msd_pack_split), segcap = cap1 / xs slots each
     uint64_t segcap;
-    unsigned long long *count1;                // [MSD_NB * xs]
-    const uint32_t *tile_start;                // [MSD_NB * xs + 1]: first tile of every stretch (pass 2)
+    uint32_t *count1;                          // [MSD_NB * xs] run cursors, stretch (d, xq) at msd_cursor_index (below N < 2^31: msd_plan)
+    int contig;                                // ... the cursors of an XCD's buckets side by side (option msd_cursors)
+    const uint32_t *tile_start;                // [MSD_NB * xs + 1]: first tile of every stretch d * xs + xq (pass 2)
     uint64_t tile0;                            // pass 1: the first tile of this launch
     uint32_t tiles2, tiles2_x;                 // pass 2: tiles in all; tiles per XCD when the tiles are dealt to the XCDs in ranges (0: in launch order)
     uint64_t *buf2;                            // pass 2 output: MSD_NB^2 stretches of MSD_FN_CAP slots
@@ -81,8 +82,7 @@ struct MsdArgs {
 // behind *cursor (one global atomic per non-empty digit) and leaves its start, relative to the bucket, minus the run's
 // start in the tile, in gdelta[d] (32-bit wrap-around arithmetic: the write-out adds the slot's place in the tile -- one
 // LDS lookup per slot, and these kernels are bound by their LDS operations)
-__device__ __forceinline__ void msd_scan_and_reserve(uint32_t *cnt, uint32_t *loff, uint32_t *gdelta, uint32_t *wsum,
-                                                     unsigned long long *cursor_d, bool wide_cursor, uint32_t *cursor32_d)
+__device__ __forceinline__ void msd_scan_and_reserve(uint32_t *cnt, uint32_t *loff, uint32_t *gdelta, uint32_t *wsum, uint32_t *cursor_d)
 {
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t c = threadIdx.x < MSD_NB ? cnt[threadIdx.x] : 0u;
@@ -95,9 +95,9 @@ __device__ __forceinline__ void msd_scan_and_reserve(uint32_t *cnt, uint32_t *lo
     for (uint32_t q = 0; q < wv; q++) pre += wsum[q];
     if (threadIdx.x < MSD_NB) {
         loff[threadIdx.x] = pre + inc - c;
-        unsigned long long g = 0;
-        if (c) g = wide_cursor ? atomicAdd(cursor_d, (unsigned long long)c) : (unsigned long long)atomicAdd(cursor32_d, c);
-        gdelta[threadIdx.x] = (uint32_t)g - (pre + inc - c);
+        uint32_t g = 0;
+        if (c) g = atomicAdd(cursor_d, c);
+        gdelta[threadIdx.x] = g - (pre + inc - c);
     }
     __syncthreads();
 }
@@ -132,8 +132,10 @@ __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *
     // Workgroups b and b + 8 run on the same XCD (dispatch deals them round-robin).  With one stretch per (bucket, XCD)
     // the runs that neighbour each other in memory were written through the same L2, which merges their partial
     // 128-byte lines before they leave for HBM; runs of different XCDs leave every line they share twice, in parts.
+    // (The cursors of the xs stretches of a bucket do not lie together for that: msd_cursor_index.)
     const uint32_t xq = a.xs > 1 ? (blockIdx.x & (uint32_t)(a.xs - 1)) : 0u;
-    msd_scan_and_reserve(cnt, loff, gdelta, wsum, a.count1 + (threadIdx.x < MSD_NB ? threadIdx.x * a.xs + xq : 0), true, nullptr);
+    msd_scan_and_reserve(cnt, loff, gdelta, wsum,
+                         a.count1 + (threadIdx.x < MSD_NB ? msd_cursor_index(threadIdx.x, xq, (uint32_t)a.xs, MSD_NB, a.contig != 0) : 0u));
     const int wshift = (EXT ? MSD_TILE_BITS : a.pb) + dshift;
     const uint64_t kmask = (1ull << a.kb) - 1;
     uint64_t *const obase = a.buf1 + xq * a.segcap;
@@ -181,7 +183,7 @@ static void msd_launch_pass1(const MsdArgs &a, unsigned tiles, hipStream_t st)
 }
 
 // first tile of every stretch of pass 1 (one workgroup of 1024 threads; nseg <= 4096 stretches, four per thread)
-__global__ __launch_bounds__(1024) void k_msd_tiles(const unsigned long long *__restrict__ count1, uint64_t segcap, uint32_t nseg,
+__global__ __launch_bounds__(1024) void k_msd_tiles(const uint32_t *__restrict__ count1, uint32_t xs, int contig, uint64_t segcap, uint32_t nseg,
                                                     uint32_t *__restrict__ tile_start, unsigned long long *__restrict__ flag)
 {
     __shared__ uint32_t wsum[16];
@@ -192,8 +194,9 @@ __global__ __launch_bounds__(1024) void k_msd_tiles(const unsigned long long *__
         const uint32_t s = threadIdx.x * 4 + q;
         t[q] = 0;
         if (s < nseg) {
-            const unsigned long long c = count1[s] < segcap ? count1[s] : segcap;
-            if (count1[s] > segcap) atomicOr(flag, 4ull);
+            const uint64_t have = count1[msd_cursor_index(s / xs, s % xs, xs, MSD_NB, contig != 0)];
+            const uint64_t c = have < segcap ? have : segcap;
+            if (have > segcap) atomicOr(flag, 4ull);
             t[q] = (uint32_t)((c + MSD_TILE - 1) / MSD_TILE);
         }
         tot += t[q];
@@ -233,8 +236,7 @@ __device__ __forceinline__ void msd_split_body(const MsdArgs &a, uint64_t *buf, 
         rk[r] = (FULL || j < have) ? atomicAdd(&cnt[(uint32_t)(w[r] >> wshift) & (MSD_NB - 1)], 1u) : 0u;
     }
     __syncthreads();
-    msd_scan_and_reserve(cnt, loff, gdelta, wsum, nullptr, false,
-                         a.count2 + (size_t)seg * MSD_NB + (threadIdx.x < MSD_NB ? threadIdx.x : 0));
+    msd_scan_and_reserve(cnt, loff, gdelta, wsum, a.count2 + (size_t)seg * MSD_NB + (threadIdx.x < MSD_NB ? threadIdx.x : 0));
 #pragma unroll
     for (int r = 0; r < MSD_ITEMS; r++) {
         const uint32_t j = threadIdx.x + r * MSD_THREADS;
@@ -274,7 +276,7 @@ __global__ __launch_bounds__(MSD_THREADS) void k_msd_split(MsdArgs a)
     uint32_t lo = 0, hi = MSD_NB * (uint32_t)a.xs;
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (a.tile_start[mid] <= tile) lo = mid; else hi = mid; }
     const uint32_t seg = lo / (uint32_t)a.xs;                    // the bucket
-    const uint64_t segn = min((uint64_t)a.count1[lo], a.segcap);
+    const uint64_t segn = min((uint64_t)a.count1[msd_cursor_index(seg, lo % (uint32_t)a.xs, (uint32_t)a.xs, MSD_NB, a.contig != 0)], a.segcap);
     const uint64_t first = (uint64_t)(tile - a.tile_start[lo]) * MSD_TILE;
     const uint32_t have = (uint32_t)min((uint64_t)MSD_TILE, segn - first);
     const uint64_t *in = a.buf1 + (uint64_t)seg * a.cap1 + (uint64_t)(lo % (uint32_t)a.xs) * a.segcap + first;
@@ -540,7 +542,7 @@ static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
     FBG_TRY(fbg_reserve(ctx, ctx->keysA, (size_t)MSD_NB * cap1 * 8));
     FBG_TRY(fbg_reserve(ctx, ctx->keysB, (size_t)nsub * MSD_FN_CAP * 8));
     const uint32_t nseg = MSD_NB * (uint32_t)xs;
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_a, (size_t)nseg * 8 + ((size_t)nseg + 1) * 4 + 64));
+    FBG_TRY(fbg_reserve(ctx, ctx->dp_a, (size_t)nseg * 4 + ((size_t)nseg + 1) * 4 + 64));   // the cursors, then tile_start
     FBG_TRY(fbg_reserve(ctx, ctx->dp_b, nsub * 4));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_c, (nsub + 1) * 8));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_d, (size_t)MSD_ARENA * 4 * 2));
@@ -554,8 +556,8 @@ static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
     a.xb = ext ? MSD_XBITS : 0; a.ext = ext ? ctx->msd_ext.as<uint8_t>() : nullptr;
     a.buf1 = ctx->keysA.as<uint64_t>(); a.cap1 = cap1; a.xs = xs; a.segcap = cap1 / xs;
     a.tile0 = 0; a.tiles2 = 0; a.tiles2_x = 0;
-    a.count1 = ctx->dp_a.as<unsigned long long>();
-    p->tile_start = reinterpret_cast<uint32_t *>(ctx->dp_a.as<uint8_t>() + (size_t)nseg * 8);
+    a.count1 = ctx->dp_a.as<uint32_t>(); a.contig = ctx->opt.msd_cursors != 0;
+    p->tile_start = a.count1 + nseg;
     a.tile_start = p->tile_start;
     a.buf2 = ctx->keysB.as<uint64_t>();
     a.count2 = ctx->dp_b.as<uint32_t>();
@@ -566,7 +568,7 @@ static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
     a.arena_sb = ctx->dp_d.as<uint32_t>(); a.arena_w = ctx->dp_e.as<uint64_t>(); a.arena_count = flag + 1; a.arena_cap = MSD_ARENA;
     p->g = g; p->nsub = nsub; p->nseg = nseg; p->rest = rest; p->fbits = fbits; p->xcd = xcd; p->flag = flag;
     FBG_HIP_TRY(ctx, hipMemsetAsync(flag, 0, 16, st));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(a.count1, 0, (size_t)nseg * 8, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(a.count1, 0, (size_t)nseg * 4, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.count2, 0, nsub * 4, st));
     *ok = 1;
     return FBG_OK;
@@ -618,7 +620,7 @@ static bool msd_plan_current(const fbg_ctx *ctx, const MsdPlan &p)
 {
     const MsdArgs &a = p.a;
     return a.T == ctx->text.p && a.code == ctx->small.as<uint8_t>() + 2048 && a.buf1 == ctx->keysA.p && a.out == ctx->keysA.p &&
-           a.buf2 == ctx->keysB.p && a.count1 == ctx->dp_a.p && (const void *)p.tile_start == ctx->dp_a.as<uint8_t>() + (size_t)p.nseg * 8 &&
+           a.buf2 == ctx->keysB.p && a.count1 == ctx->dp_a.p && p.tile_start == ctx->dp_a.as<uint32_t>() + p.nseg &&
            a.count2 == ctx->dp_b.p && p.off == ctx->dp_c.p && a.arena_sb == ctx->dp_d.p && a.arena_w == ctx->dp_e.p &&
            p.flag == ctx->scalars.as<unsigned long long>() + 100 && (!a.xb || a.ext == ctx->msd_ext.p);
 }
@@ -661,7 +663,7 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
         msd_launch_pass1(a, fbg_blocks(N, MSD_TILE), st);
         FBG_TRY(fbg_stage_end(ctx, FBG_STAGE_SORT_PASS1, 1));
     }
-    hipLaunchKernelGGL(k_msd_tiles, dim3(1), dim3(1024), 0, st, a.count1, a.segcap, nseg, tile_start, flag);
+    hipLaunchKernelGGL(k_msd_tiles, dim3(1), dim3(1024), 0, st, a.count1, (uint32_t)a.xs, a.contig, a.segcap, nseg, tile_start, flag);
     uint32_t tiles2 = 0;
     unsigned long long h_flag = 0;
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&tiles2, tile_start + nseg, 4, hipMemcpyDeviceToHost, st));

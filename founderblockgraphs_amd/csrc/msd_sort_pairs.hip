@@ -42,9 +42,13 @@ struct PpArgs {
     int packed;                                // 8-byte slots: key << pb | position, no second array (texts below 2^32)
     uint64_t lo, hi, mul;                      // key range (hi ignored when nohi), t = umul64hi(key - lo, mul) < 2^28
     int nohi;
-    uint64_t *w1; uint32_t *v1; uint64_t cap1; unsigned long long *count1;      // pass 1 output: PP_NB stretches
-    int xs;                                    // ... each in xs parts of segcap = cap1 / xs slots (8: one per XCD, as in msd_sort.hip; count1[PP_NB * xs])
+    uint64_t *w1; uint32_t *v1; uint64_t cap1;                                  // pass 1 output: PP_NB stretches
+    int xs;                                    // ... each in xs parts of segcap = cap1 / xs slots (8: one per XCD, as in msd_sort.hip)
     uint64_t segcap;
+    // the run cursors of the PP_NB * xs parts, part (d, xq) at msd_cursor_index: 32-bit words (count1) for a text below 2^32
+    // symbols -- a cursor counts slots the pass kept, at most N -- and 64-bit words (count1w) beyond; the other pointer is null
+    uint32_t *count1; unsigned long long *count1w;
+    int contig;                                // the cursors of an XCD's buckets side by side (option msd_cursors)
     uint32_t tiles2, tiles2_x;                 // pass 2: tiles in all; tiles per XCD when the workgroups of an XCD take a range of tiles (0: launch order)
     const uint32_t *tile_start;
     uint64_t *w2; uint32_t *v2; uint32_t *count2;                               // pass 2 output: PP_NB^2 stretches of PP_FN_CAP
@@ -165,9 +169,17 @@ __device__ __forceinline__ uint32_t pp_digit_of_slot(const uint32_t *loff, uint3
     return at;
 }
 
-// scan of PP_NB counts (one per thread) + run reservation, as msd_scan_and_reserve
+// slots that pass 1 sent to part (d, xq)
+__device__ __forceinline__ uint64_t pp_count1(const PpArgs &a, uint32_t d, uint32_t xq)
+{
+    const uint32_t i = msd_cursor_index(d, xq, (uint32_t)a.xs, PP_NB, a.contig != 0);
+    return a.count1w ? a.count1w[i] : a.count1[i];
+}
+
+// scan of PP_NB counts (one per thread) + run reservation, as msd_scan_and_reserve; the cursor of this thread's digit is
+// *cursor64_d or, where that is null, *cursor32_d
 __device__ __forceinline__ void pp_scan_and_reserve(uint32_t *cnt, uint32_t *loff, unsigned long long *gbase, uint32_t *wsum,
-                                                    unsigned long long *cursor64, uint32_t *cursor32, int stride64 = 1)
+                                                    unsigned long long *cursor64_d, uint32_t *cursor32_d)
 {
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t c = cnt[threadIdx.x];                       // PP_THREADS == PP_NB
@@ -180,7 +192,7 @@ __device__ __forceinline__ void pp_scan_and_reserve(uint32_t *cnt, uint32_t *lof
     for (uint32_t q = 0; q < wv; q++) pre += wsum[q];
     loff[threadIdx.x] = pre + inc - c;
     unsigned long long g = 0;
-    if (c) g = cursor64 ? atomicAdd(cursor64 + (size_t)threadIdx.x * stride64, (unsigned long long)c) : (unsigned long long)atomicAdd(cursor32 + threadIdx.x, c);
+    if (c) g = cursor64_d ? atomicAdd(cursor64_d, (unsigned long long)c) : (unsigned long long)atomicAdd(cursor32_d, c);
     gbase[threadIdx.x] = g - (pre + inc - c);                  // minus the run's start in the tile: the write-out adds the slot's place (wraps)
     __syncthreads();
 }
@@ -275,7 +287,8 @@ template <int MODE> __global__ __launch_bounds__(PP_THREADS) void k_pp_pack_spli
     // a stretch per (bucket, XCD): workgroups b and b + 8 share an XCD, whose L2 merges the partial lines where their runs
     // meet (msd_sort.hip, k_msd_pack_split)
     const uint32_t xq = a.xs > 1 ? (blockIdx.x & (uint32_t)(a.xs - 1)) : 0u;
-    pp_scan_and_reserve(cnt, loff, gbase, wsum, a.count1 + xq, nullptr, a.xs);
+    const uint32_t ci = msd_cursor_index(threadIdx.x, xq, (uint32_t)a.xs, PP_NB, a.contig != 0);
+    pp_scan_and_reserve(cnt, loff, gbase, wsum, a.count1w ? a.count1w + ci : nullptr, a.count1 + ci);
 #pragma unroll
     for (int r = 0; r < PP_STAGE / PP_THREADS; r++) {
         const uint32_t j = threadIdx.x + r * PP_THREADS;
@@ -297,10 +310,10 @@ template <int MODE> __global__ __launch_bounds__(PP_THREADS) void k_pp_pack_spli
 }
 
 // first tile of every stretch of pass 1 and the number of slots in all (one workgroup of 1024 threads, nseg <= 4096)
-__global__ __launch_bounds__(1024) void k_pp_tiles(const unsigned long long *__restrict__ count1, uint64_t segcap, uint32_t nseg,
-                                                   uint32_t *__restrict__ tile_start, unsigned long long *__restrict__ total,
+__global__ __launch_bounds__(1024) void k_pp_tiles(PpArgs a, uint32_t nseg, uint32_t *__restrict__ tile_start, unsigned long long *__restrict__ total,
                                                    unsigned long long *__restrict__ flag)
 {
+    const uint64_t segcap = a.segcap;
     __shared__ uint32_t wsum[16];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t t[4], tot = 0;
@@ -310,8 +323,9 @@ __global__ __launch_bounds__(1024) void k_pp_tiles(const unsigned long long *__r
         const uint32_t s = threadIdx.x * 4 + q;
         t[q] = 0;
         if (s < nseg) {
-            if (count1[s] > segcap) *flag = 1;
-            const unsigned long long c = count1[s] < segcap ? count1[s] : segcap;
+            const uint64_t have = pp_count1(a, s / (uint32_t)a.xs, s % (uint32_t)a.xs);      // stretch s = d * xs + xq
+            if (have > segcap) *flag = 1;
+            const unsigned long long c = have < segcap ? have : segcap;
             sum += c;
             t[q] = (uint32_t)((c + PP_TILE - 1) / PP_TILE);
         }
@@ -349,7 +363,7 @@ template <int MODE> __global__ __launch_bounds__(PP_THREADS) void k_pp_split(PpA
     uint32_t lo = 0, hi = PP_NB * (uint32_t)a.xs;
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (a.tile_start[mid] <= tile) lo = mid; else hi = mid; }
     const uint32_t seg = lo / (uint32_t)a.xs;
-    const uint64_t segn = min((uint64_t)a.count1[lo], a.segcap);
+    const uint64_t segn = min(pp_count1(a, seg, lo % (uint32_t)a.xs), a.segcap);
     const uint64_t first = (uint64_t)(tile - a.tile_start[lo]) * PP_TILE;
     const uint32_t have = (uint32_t)min((uint64_t)PP_TILE, segn - first);
     const uint64_t in0 = (uint64_t)seg * a.cap1 + (uint64_t)(lo % (uint32_t)a.xs) * a.segcap + first;
@@ -373,7 +387,7 @@ template <int MODE> __global__ __launch_bounds__(PP_THREADS) void k_pp_split(PpA
         rk[r] = j < have ? atomicAdd(&cnt[dg[r]], 1u) : 0u;
     }
     __syncthreads();
-    pp_scan_and_reserve(cnt, loff, gbase, wsum, nullptr, a.count2 + (size_t)seg * PP_NB);
+    pp_scan_and_reserve(cnt, loff, gbase, wsum, nullptr, a.count2 + (size_t)seg * PP_NB + threadIdx.x);
 #pragma unroll
     for (int r = 0; r < MSD_ITEMS; r++) {
         const uint32_t j = threadIdx.x + r * PP_THREADS;
@@ -830,7 +844,9 @@ static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, PpArgs &
     const bool any = MODE == 1 && a.any_order;
     a.w1 = ctx->keysA.as<uint64_t>(); a.v1 = ctx->valsA.as<uint32_t>(); a.cap1 = cap1; a.xs = xs; a.segcap = cap1 / xs;
     a.tiles2 = 0; a.tiles2_x = 0;
-    a.count1 = ctx->dp_a.as<unsigned long long>();
+    const bool c32 = N < (1ull << 32);                          // a cursor counts kept slots, at most N of them
+    a.count1 = ctx->dp_a.as<uint32_t>(); a.count1w = c32 ? nullptr : ctx->dp_a.as<unsigned long long>();
+    a.contig = ctx->opt.msd_cursors != 0;
     uint32_t *tile_start = reinterpret_cast<uint32_t *>(ctx->dp_a.as<uint8_t>() + (size_t)nseg * 8);
     a.tile_start = tile_start;
     a.w2 = ctx->msd_w.as<uint64_t>(); a.v2 = ctx->msd_v.as<uint32_t>(); a.count2 = ctx->dp_b.as<uint32_t>();
@@ -843,10 +859,10 @@ static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, PpArgs &
     a.flag = flag;
     a.wout = nullptr; a.vout = nullptr;
     FBG_HIP_TRY(ctx, hipMemsetAsync(flag, 0, 24, st));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(a.count1, 0, (size_t)nseg * 8, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(a.count1, 0, (size_t)nseg * (c32 ? 4 : 8), st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.count2, 0, nsub * 4, st));
     hipLaunchKernelGGL((k_pp_pack_split<MODE>), dim3(fbg_blocks(N, (uint64_t)PP_TILE * nparts)), dim3(PP_THREADS), 0, st, a);
-    hipLaunchKernelGGL(k_pp_tiles, dim3(1), dim3(1024), 0, st, a.count1, a.segcap, nseg, tile_start, flag + 2, flag);
+    hipLaunchKernelGGL(k_pp_tiles, dim3(1), dim3(1024), 0, st, a, nseg, tile_start, flag + 2, flag);
     uint32_t tiles2 = 0;
     unsigned long long h3[3] = {0, 0, 0};
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&tiles2, tile_start + nseg, 4, hipMemcpyDeviceToHost, st));

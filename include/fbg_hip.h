@@ -153,6 +153,10 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *   scan_rows_ahead    the rows of 64 slots whose loads a wave of the lean rank-order scan (k_rank_scan_lean) keeps in flight
  *                      while it works on a row: 1 = one row ahead; 2, 3, 4 = groups of that many rows, the next group's loads
  *                      issued at the top of a group; 0 and any other value = the default, 3; results unchanged
+ *   msd_cursors        where pass 1 of the MSD sorts keeps the run cursor of stretch (bucket d, XCD part q of xs, msd_xcd bit 1):
+ *                      1 (default) at q * 512 + d, so that the 64 lanes of a reserving wave add to consecutive words; 0 at
+ *                      d * xs + q, the stretch's own number (the earlier placement); the words are as wide either way (32 bits
+ *                      for texts below 2^32 symbols); results unchanged
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
  *   path_batch_kib     fbg_pindex_chains_cigar and _chains_graph_cigar: the KiB of column history in device memory that
