@@ -232,7 +232,7 @@ int fbg_block_graph_device(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb
     FBG_TRY(fbg_reserve(ctx, ctx->dp_e, nb * 4));          // count
     FBG_TRY(fbg_reserve(ctx, ctx->dp_f, (nb + 1) * 8 * 2)); // widened counts, first
     FBG_TRY(fbg_reserve(ctx, ctx->dp_g, nb * 8));          // edge_count
-    FBG_TRY(fbg_reserve(ctx, ctx->scalars, 256 * sizeof(unsigned long long)));
+    FBG_TRY(fbg_reserve_scalars(ctx));
     BgArgs a;
     a.msa = ctx->d_msa; a.m = m; a.n = n; a.nb = nb;
     a.bounds = ctx->io_a.as<uint64_t>();
@@ -242,7 +242,7 @@ int fbg_block_graph_device(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb
     a.first = first;
     a.edge_count = ctx->dp_g.as<unsigned long long>();
     a.edges = nullptr;
-    a.flag = ctx->scalars.as<unsigned long long>() + 110;
+    a.flag = &fbg_scalars(ctx)->graph_collision;
     FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, boundaries, nb * 8, hipMemcpyHostToDevice, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.flag, 0, 8, st));
     hipLaunchKernelGGL(k_label_hash, dim3(fbg_blocks(cells, 256)), dim3(256), 0, st, a);
@@ -265,15 +265,9 @@ int fbg_block_graph_device(fbg_ctx *ctx, const uint64_t *boundaries, uint64_t nb
     // first node of every block: exclusive scan of the counts
     hipLaunchKernelGGL(k_bg_widen, dim3(fbg_blocks(nb, 256)), dim3(256), 0, st, a.count, wide, nb);
     FBG_HIP_TRY(ctx, hipMemsetAsync(wide + nb, 0, 8, st));
-    {
-        size_t bytes = 0;
-        hipError_t e = rocprim::exclusive_scan(nullptr, bytes, wide, first, 0ull, (size_t)(nb + 1), rocprim::plus<unsigned long long>(), st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim scan size query: %s", hipGetErrorString(e));
-        FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-        size_t have = ctx->tmp.cap;
-        e = rocprim::exclusive_scan(ctx->tmp.p, have, wide, first, 0ull, (size_t)(nb + 1), rocprim::plus<unsigned long long>(), st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim exclusive_scan: %s", hipGetErrorString(e));
-    }
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, wide, first, 0ull, (size_t)(nb + 1), rocprim::plus<unsigned long long>(), st);
+    }));
     a.edges = ctx->dp_b.as<unsigned long long>();          // the hashes are not needed any more
     uint32_t cap = 64;
     while (cap < m) cap <<= 1;

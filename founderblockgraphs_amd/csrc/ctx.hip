@@ -336,8 +336,8 @@ int fbg_get_option(const fbg_ctx *ctx, const char *key, int64_t *value)
         if (strcmp(k.name, key) == 0) { *value = k.get(*ctx); return FBG_OK; }
     if (strncmp(key, "span_dbg", 8) == 0 && key[8] >= '0' && key[8] <= '7' && !key[9]) {   // debug builds (SP_PHASE_TIMERS): cycles per phase of k_sp_odd_pairs
         unsigned long long v = 0;
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess || ctx->scalars.cap < 256 * 8 ||
-            hipMemcpy(&v, (const unsigned long long *)ctx->scalars.p + 208 + 24 + (key[8] - '0'), 8, hipMemcpyDeviceToHost) != hipSuccess) return FBG_ERR_HIP;
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess || ctx->scalars.cap < FBG_SCALARS_BYTES ||
+            hipMemcpy(&v, fbg_scalars(ctx)->span + 24 + (key[8] - '0'), 8, hipMemcpyDeviceToHost) != hipSuccess) return FBG_ERR_HIP;
         *value = (int64_t)v;
         return FBG_OK;
     }

@@ -1438,11 +1438,11 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
     FBG_TRY(fbg_reserve(ctx, ctx->dp_g, w));   // mml
     FBG_TRY(fbg_reserve(ctx, ctx->dp_h, w));   // bt
     FBG_TRY(fbg_reserve(ctx, ctx->list, w));   // tnext
-    FBG_TRY(fbg_reserve(ctx, ctx->scalars, 256 * sizeof(unsigned long long)));
+    FBG_TRY(fbg_reserve_scalars(ctx));
     uint32_t *e = ctx->dp_a.as<uint32_t>(), *bstart = ctx->dp_b.as<uint32_t>(), *cur = ctx->dp_c.as<uint32_t>(),
              *items = ctx->dp_d.as<uint32_t>(), *count = ctx->dp_e.as<uint32_t>(), *bcount = ctx->dp_f.as<uint32_t>(),
              *mml = ctx->dp_g.as<uint32_t>(), *bt = ctx->dp_h.as<uint32_t>(), *tnext = ctx->list.as<uint32_t>();
-    unsigned long long *sc = ctx->scalars.as<unsigned long long>() + 16;
+    unsigned long long *sc = fbg_scalars(ctx)->dp;
     FBG_HIP_TRY(ctx, hipMemsetAsync(sc, 0, 8 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_dp_keys, dim3(fbg_blocks(n, 256, 2048)), dim3(256), 0, st, d_f, n, e, sc + 2);
     // the bucket order of fbg.cpp:1941-1953 (counting sort of x by f[x]+1): only the wave-parallel and the literal sweep
@@ -1452,14 +1452,10 @@ int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_bou
         if (buckets_ready) return FBG_OK;
         FBG_HIP_TRY(ctx, hipMemsetAsync(bstart, 0, w, st));
         hipLaunchKernelGGL(k_dp_hist, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, e, n, bstart);
-        size_t bytes = 0;
-        hipError_t er = rocprim::exclusive_scan(nullptr, bytes, bstart, bstart, 0u, (size_t)(n + 2), rocprim::plus<uint32_t>(), st);
-        if (er != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim scan size query failed");
         // ctx->tmp may hold the block matrices of an abandoned attempt: they are dead by now
-        FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-        size_t have = ctx->tmp.cap;
-        er = rocprim::exclusive_scan(ctx->tmp.p, have, bstart, bstart, 0u, (size_t)(n + 2), rocprim::plus<uint32_t>(), st);
-        if (er != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim exclusive_scan: %s", hipGetErrorString(er));
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, bstart, bstart, 0u, (size_t)(n + 2), rocprim::plus<uint32_t>(), st);
+        }));
         FBG_HIP_TRY(ctx, hipMemcpyAsync(cur, bstart, w, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_dp_scatter, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, e, n, cur, items);
         FBG_HIP_TRY(ctx, hipMemsetAsync(count, 0, w, st));
@@ -1779,9 +1775,9 @@ int fbg_dp_repeatfree(fbg_ctx *ctx, const uint64_t *d_v, uint64_t n, uint64_t *d
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_DP));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_g, (n + 2) * 4));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_h, (n + 2) * 4));
-    FBG_TRY(fbg_reserve(ctx, ctx->scalars, 256 * sizeof(unsigned long long)));
+    FBG_TRY(fbg_reserve_scalars(ctx));
     uint32_t *s = ctx->dp_g.as<uint32_t>(), *prev = ctx->dp_h.as<uint32_t>();
-    unsigned long long *sc = ctx->scalars.as<unsigned long long>() + 16;
+    unsigned long long *sc = fbg_scalars(ctx)->dp;
     FBG_HIP_TRY(ctx, hipMemsetAsync(sc, 0, 16 * sizeof(unsigned long long), st));
     bool literal = ctx->opt.dp_literal != 0;
     ctx->ne_dp_kind = 0;
@@ -1887,13 +1883,9 @@ int fbg_gapped_v_from_f(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t 
     uint32_t *best = ctx->dp_a.as<uint32_t>();
     FBG_HIP_TRY(ctx, hipMemsetAsync(best, 0, (n + 2) * 4, st));
     hipLaunchKernelGGL(k_gv_scatter, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, d_f, (uint32_t)n, best);
-    size_t bytes = 0;
-    hipError_t er = rocprim::inclusive_scan(nullptr, bytes, best, best, (size_t)n, rocprim::maximum<uint32_t>(), st);
-    if (er != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim scan size query failed");
-    FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-    size_t have = ctx->tmp.cap;
-    er = rocprim::inclusive_scan(ctx->tmp.p, have, best, best, (size_t)n, rocprim::maximum<uint32_t>(), st);
-    if (er != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim inclusive_scan: %s", hipGetErrorString(er));
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        return rocprim::inclusive_scan(tmp, bytes, best, best, (size_t)n, rocprim::maximum<uint32_t>(), st);
+    }));
     hipLaunchKernelGGL(k_gv_finish, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, best, (uint32_t)n, d_v);
     FBG_HIP_TRY(ctx, hipGetLastError());
     return FBG_OK;
@@ -2007,9 +1999,9 @@ int fbg_dp_gapped(fbg_ctx *ctx, const uint64_t *d_v, uint64_t n, uint64_t *d_s, 
     FBG_TRY(fbg_reserve(ctx, ctx->dp_g, w));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_h, w));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_b, w));
-    FBG_TRY(fbg_reserve(ctx, ctx->scalars, 256 * sizeof(unsigned long long)));
+    FBG_TRY(fbg_reserve_scalars(ctx));
     uint32_t *s = ctx->dp_g.as<uint32_t>(), *prev = ctx->dp_h.as<uint32_t>(), *btp = ctx->dp_b.as<uint32_t>();
-    unsigned long long *sc = ctx->scalars.as<unsigned long long>() + 16;
+    unsigned long long *sc = fbg_scalars(ctx)->dp;
     FBG_HIP_TRY(ctx, hipMemsetAsync(sc, 0, 16 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_dp_gapped, dim3(1), dim3(64), 0, st, d_v, (uint32_t)n, s, prev, btp);
     FBG_TRY(fbg_backtrack_lifted(ctx, btp, (uint32_t)n, d_boundaries, sc));

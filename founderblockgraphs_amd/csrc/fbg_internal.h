@@ -1,6 +1,7 @@
 // fbg_internal.h -- shared declarations of the MI355X segmentation engine (libfbg_hip.so).
 // gfx950 only: 64-wide wavefronts are assumed throughout.
 #pragma once
+#include <cstddef>
 #include <cstring>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
@@ -230,6 +231,61 @@ int fbg_fail(fbg_ctx *ctx, int code, const char *fmt, ...);
 // not those of a pattern index or of its build's scratch.
 int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes, std::vector<DevBuf *> *owner, bool accounted);
 inline int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes) { return fbg_reserve(ctx, b, bytes, &ctx->bufs, true); }
+
+// ---- the shared scratch words ---------------------------------------------------------------
+// ctx->scalars: the device-side counters and flags of every stage, one member per owner.  The members are disjoint
+// whichever stages run together; what a stage does with the words of its own member is its business.  A new counter
+// gets a new member here (DESIGN.md 4a lists them).  The blocks that kernels add to start a 64-byte line of their own.
+struct FbgScalars {
+    alignas(64) unsigned long long front[8];     // text_build.hip, front_one_fill = 0: gaps, ignore cells, N
+    unsigned long long sample_count;             // suffix_sort.hip: twins in the key sample; the slots a partition keeps
+    alignas(64) unsigned long long dp[16];       // dp.hip: results and flags of the three DPs and of the lifted backtrack
+    unsigned long long scan_exceptions;          // scan.hip: exception columns of the record scan
+    alignas(64) unsigned long long rank[8];      // rank_common.h / rank_scan.hip: RankArgs::counters ...
+    unsigned long long rank_hist[32];            // ... and right behind them the threshold histogram, 64 x u32 (rs_zero_counters: one fill)
+    alignas(64) unsigned long long pure[4];      // pure_scan.hip: PsArgs::counters
+    alignas(64) unsigned long long msd[4];       // msd_sort.hip, msd_sort_pairs.hip: decline flag, arena count, total of the pairs sort, sub-buckets left for later
+    unsigned long long sample_twins;             // msd_sort_pairs.hip: twins in the sample of the pairs sort
+    unsigned long long graph_collision;          // block_graph.hip: two labels share a hash
+    unsigned long long pair_stats[2];            // rank_scan.hip: tied pairs of the lean scan settled by the extra symbols / by the text
+    unsigned long long cand_inversions;          // rank_scan.hip: option cand_sort_check
+    unsigned long long by_position;              // suffix_sort.hip: the records by position are no permutation
+    alignas(64) unsigned long long gapped[8 + 66];   // gapped_rank.hip: GrsArgs::counters and the threshold histogram behind them
+    alignas(64) unsigned long long span[34];     // span_scan.hip: SpArgs::counters
+};
+constexpr size_t FBG_SCALARS_WORDS = 256, FBG_SCALARS_BYTES = FBG_SCALARS_WORDS * sizeof(unsigned long long);
+static_assert(sizeof(FbgScalars) <= FBG_SCALARS_BYTES, "the scalar words fit their buffer, whose size is part of fbg_device_bytes");
+static_assert(offsetof(FbgScalars, rank_hist) == offsetof(FbgScalars, rank) + sizeof(FbgScalars::rank), "one fill clears counters and histogram");
+inline int fbg_reserve_scalars(fbg_ctx *ctx) { return fbg_reserve(ctx, ctx->scalars, FBG_SCALARS_BYTES); }
+// the device address of the layout: fbg_scalars(ctx)->dp, &fbg_scalars(ctx)->sample_count (never dereferenced on the host)
+inline FbgScalars *fbg_scalars(const fbg_ctx *ctx) { return ctx->scalars.as<FbgScalars>(); }
+
+// ctx->small: the byte tables of a build, 2048 bytes apart
+struct FbgSmall {
+    alignas(2048) uint8_t ignore_tab[256];       // text_build.hip: 1 for an ignore character (ctx->have_ignore)
+    alignas(2048) uint8_t code_tab[256];         // suffix_sort.hip fbg_key_setup: the code of every byte (KeyGeom::d_code)
+    alignas(2048) unsigned long long hist[256];  // text_build.hip, front_one_fill = 0: the byte histogram of the counting pass
+};
+constexpr size_t FBG_SMALL_BYTES = 8192;
+static_assert(sizeof(FbgSmall) <= FBG_SMALL_BYTES, "the byte tables fit their buffer");
+inline FbgSmall *fbg_small(const fbg_ctx *ctx) { return ctx->small.as<FbgSmall>(); }
+
+// rocPRIM's calling pattern: ask for the temporary size, grow `tmp` (on `owner`'s list, accounted or not: fbg_reserve), call
+// again with the buffer.  call(void *tmp, size_t &bytes) holds the one argument list both calls use.
+template <class F> int fbg_with_tmp(fbg_ctx *ctx, DevBuf &tmp, std::vector<DevBuf *> *owner, bool accounted, F &&call)
+{
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
+    FBG_TRY(fbg_reserve(ctx, tmp, bytes, owner, accounted));
+    size_t have = tmp.cap;
+    e = call(tmp.p, have);
+    if (e != hipSuccess)
+        return fbg_fail(ctx, e == hipErrorOutOfMemory ? FBG_ERR_OOM : FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
+    return FBG_OK;
+}
+template <class F> int fbg_with_tmp(fbg_ctx *ctx, F &&call) { return fbg_with_tmp(ctx, ctx->tmp, &ctx->bufs, true, call); }   // the context's own tmp
+
 void fbg_release(fbg_ctx *ctx, DevBuf &b);                         // ctx = nullptr: a buffer outside the context's accounting
 void fbg_release_all(fbg_ctx *ctx, std::vector<DevBuf *> &bufs);   // ... every buffer of a list
 void fbg_index_reset(fbg_ctx *ctx);                                // ctx.hip: the top of a build, nowhere else

@@ -909,7 +909,7 @@ static void grs_args(fbg_ctx *ctx, GrsArgs &a, int disable_tricks)
     a.win = ctx->gapfree ? nullptr : ctx->gwin.as<GWin>();
     a.colT = ctx->gapfree ? nullptr : ctx->colT.as<uint32_t>();
     a.pos = ctx->pos.as<uint32_t>(); a.tot = ctx->tot.as<uint32_t>();
-    a.is_ignore = ctx->have_ignore ? ctx->small.as<uint8_t>() : nullptr;
+    a.is_ignore = ctx->have_ignore ? fbg_small(ctx)->ignore_tab : nullptr;
     a.N = ctx->N; a.n = ctx->n; a.m = ctx->m;
     if (ctx->ix.part_active) {
         a.own_lo = FBG_PART_HALO; a.own_hi = FBG_PART_HALO + ctx->ix.part_count;
@@ -923,7 +923,7 @@ static void grs_args(fbg_ctx *ctx, GrsArgs &a, int disable_tricks)
     a.ign_lo = ctx->grs_ign_lo; a.ign_hi = ctx->grs_ign_hi;
     a.t = 1;
     a.fmax = ctx->gmax.as<uint32_t>();
-    a.counters = ctx->scalars.as<unsigned long long>() + 128;
+    a.counters = fbg_scalars(ctx)->gapped;
     a.cand = nullptr; a.pm = nullptr; a.cand_cap = 0; a.longs = nullptr;
 }
 
@@ -965,13 +965,9 @@ static int grs_sort_and_runs(fbg_ctx *ctx, GrsArgs &a, uint64_t T, int *launches
     unsigned long long *sorted = ctx->ps_f.as<unsigned long long>();
     int nb = 1;
     while ((1ull << nb) < ctx->n + 1) nb++;
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, a.cand, sorted, (size_t)T, 0u, 32u + (unsigned)nb, st);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim sort size query: %s", hipGetErrorString(e));
-    FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-    size_t have = ctx->tmp.cap;
-    e = rocprim::radix_sort_keys(ctx->tmp.p, have, a.cand, sorted, (size_t)T, 0u, 32u + (unsigned)nb, st);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim radix_sort_keys: %s", hipGetErrorString(e));
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_keys(tmp, bytes, a.cand, sorted, (size_t)T, 0u, 32u + (unsigned)nb, st);
+    }));
     unsigned long long *unsorted = a.cand;
     uint32_t *lcpL = reinterpret_cast<uint32_t *>(unsorted), *lcpR = lcpL + a.cand_cap;     // the unsorted list is done with
     a.cand = sorted;

@@ -550,7 +550,7 @@ static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
     // extra symbols: 2-bit symbols (the bucket implies 9 key bits, they stand for 8), and LDS room for key and place in pass 1
     const bool ext = ctx->opt.msd_ext != 0 && g.b == 2 && g.key_bits + MSD_XBITS + MSD_TILE_BITS <= 64 && g.K + MSD_XSYM + MSD_ITEMS - 1 <= 64;
     if (ext) FBG_TRY(fbg_reserve(ctx, ctx->msd_ext, (size_t)N));
-    unsigned long long *flag = ctx->scalars.as<unsigned long long>() + 100;
+    unsigned long long *flag = fbg_scalars(ctx)->msd;
     MsdArgs &a = p->a;
     a.T = ctx->text.as<uint8_t>(); a.N = N; a.code = g.d_code; a.b = g.b; a.K = g.K; a.pb = g.pb; a.kb = g.key_bits;
     a.xb = ext ? MSD_XBITS : 0; a.ext = ext ? ctx->msd_ext.as<uint8_t>() : nullptr;
@@ -619,10 +619,10 @@ void fbg_msd_pre_free(fbg_ctx *ctx)
 static bool msd_plan_current(const fbg_ctx *ctx, const MsdPlan &p)
 {
     const MsdArgs &a = p.a;
-    return a.T == ctx->text.p && a.code == ctx->small.as<uint8_t>() + 2048 && a.buf1 == ctx->keysA.p && a.out == ctx->keysA.p &&
+    return a.T == ctx->text.p && a.code == fbg_small(ctx)->code_tab && a.buf1 == ctx->keysA.p && a.out == ctx->keysA.p &&
            a.buf2 == ctx->keysB.p && a.count1 == ctx->dp_a.p && p.tile_start == ctx->dp_a.as<uint32_t>() + p.nseg &&
            a.count2 == ctx->dp_b.p && p.off == ctx->dp_c.p && a.arena_sb == ctx->dp_d.p && a.arena_w == ctx->dp_e.p &&
-           p.flag == ctx->scalars.as<unsigned long long>() + 100 && (!a.xb || a.ext == ctx->msd_ext.p);
+           p.flag == fbg_scalars(ctx)->msd && (!a.xb || a.ext == ctx->msd_ext.p);
 }
 
 bool fbg_msd_pre_geom(fbg_ctx *ctx, KeyGeom *g)
@@ -681,15 +681,9 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
     // offsets of the sub-buckets in the sorted array: exclusive scan of their sizes
     unsigned long long *wide = reinterpret_cast<unsigned long long *>(ctx->keysA.p);   // scratch: pass 1's slots are dead
     hipLaunchKernelGGL(k_msd_widen, dim3(fbg_blocks(nsub, 256)), dim3(256), 0, st, a.count2, wide, nsub);
-    {
-        size_t bytes = 0;
-        hipError_t e = rocprim::exclusive_scan(nullptr, bytes, wide, off, 0ull, (size_t)nsub, rocprim::plus<unsigned long long>(), st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim scan size query: %s", hipGetErrorString(e));
-        FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-        size_t have = ctx->tmp.cap;
-        e = rocprim::exclusive_scan(ctx->tmp.p, have, wide, off, 0ull, (size_t)nsub, rocprim::plus<unsigned long long>(), st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim exclusive_scan: %s", hipGetErrorString(e));
-    }
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, wide, off, 0ull, (size_t)nsub, rocprim::plus<unsigned long long>(), st);
+    }));
     const int fshift = g.pb + a.xb + rest - fbits;
     const uint32_t fmask = (uint32_t)((1u << fbits) - 1);
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_SORT_PASS3));
@@ -707,13 +701,9 @@ int fbg_msd_sort(fbg_ctx *ctx, const KeyGeom &g, uint64_t **sorted, int *ok, int
         const uint32_t entries = (uint32_t)h2[1];
         uint32_t *sb_sorted = a.arena_sb + MSD_ARENA;
         uint64_t *w_sorted = a.arena_w + MSD_ARENA;
-        size_t bytes = 0;
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, a.arena_sb, sb_sorted, a.arena_w, w_sorted, (size_t)entries, 0u, 32u, st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim sort size query: %s", hipGetErrorString(e));
-        FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-        size_t have = ctx->tmp.cap;
-        e = rocprim::radix_sort_pairs(ctx->tmp.p, have, a.arena_sb, sb_sorted, a.arena_w, w_sorted, (size_t)entries, 0u, 32u, st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim radix_sort_pairs: %s", hipGetErrorString(e));
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, a.arena_sb, sb_sorted, a.arena_w, w_sorted, (size_t)entries, 0u, 32u, st);
+        }));
         hipLaunchKernelGGL(k_msd_finish_big, dim3(entries), dim3(MSD_BIG_THREADS), 0, st, a, sb_sorted, w_sorted, entries, fshift, fmask);
         FBG_HIP_TRY(ctx, hipMemcpyAsync(h2, flag, 16, hipMemcpyDeviceToHost, st));
         FBG_HIP_TRY(ctx, hipStreamSynchronize(st));

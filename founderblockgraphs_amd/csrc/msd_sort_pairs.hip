@@ -834,7 +834,7 @@ static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, PpArgs &
     FBG_TRY(fbg_reserve(ctx, ctx->dp_c, (nsub + 1) * 8 * 2));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_d, (size_t)PP_ARENA * 4 * 5));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_e, (size_t)PP_ARENA * 8 * 2));
-    unsigned long long *flag = ctx->scalars.as<unsigned long long>() + 100;      // [0] flag, [1] arena count, [2] total
+    unsigned long long *flag = fbg_scalars(ctx)->msd;      // [0] flag, [1] arena count, [2] total, [3] sub-buckets left for later
     a.T = ctx->text.as<uint8_t>(); a.N = N; a.code = g.d_code; a.b = g.b; a.K = g.K; a.pb = (g.wide || g.packed) ? g.pb : 0; a.nparts = nparts;
     a.wide = g.wide ? 1 : 0; a.packed = g.packed ? 1 : 0;
     a.ebits = (MODE == 1 && !g.wide && !g.packed && g.K <= 32) ? x.ebits : nullptr;
@@ -878,15 +878,9 @@ static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, PpArgs &
     a.tiles2_x = (xcd & 1) ? (tiles2 + 7) / 8 : 0;
     hipLaunchKernelGGL((k_pp_split<MODE>), dim3(a.tiles2_x ? 8 * a.tiles2_x : tiles2), dim3(PP_THREADS), 0, st, a);
     hipLaunchKernelGGL(k_pp_widen, dim3(fbg_blocks(nsub, 256)), dim3(256), 0, st, a.count2, wide, nsub);
-    {
-        size_t bytes = 0;
-        hipError_t e = rocprim::exclusive_scan(nullptr, bytes, wide, off, 0ull, (size_t)nsub, rocprim::plus<unsigned long long>(), st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim scan size query: %s", hipGetErrorString(e));
-        FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-        size_t have = ctx->tmp.cap;
-        e = rocprim::exclusive_scan(ctx->tmp.p, have, wide, off, 0ull, (size_t)nsub, rocprim::plus<unsigned long long>(), st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim exclusive_scan: %s", hipGetErrorString(e));
-    }
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, wide, off, 0ull, (size_t)nsub, rocprim::plus<unsigned long long>(), st);
+    }));
     if (total / nsub + total / (4 * nsub) <= PP_FN_SMALL) {
         // sparsely filled stretches: the small-capacity variant for all, the full one for the few it notes down
         FBG_TRY(fbg_reserve(ctx, ctx->ps_a, (size_t)nsub * 4));
@@ -937,13 +931,9 @@ static int pp_sort(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, PpArgs &
     if (h3[1] > 0) {
         const uint32_t entries = (uint32_t)h3[1];
         hipLaunchKernelGGL(k_pp_iota, dim3(fbg_blocks(entries, 256)), dim3(256), 0, st, a_idx, entries);
-        size_t bytes = 0;
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, a.arena_sb, sb_sorted, a_idx, idx_sorted, (size_t)entries, 0u, 32u, st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim sort size query: %s", hipGetErrorString(e));
-        FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-        size_t have = ctx->tmp.cap;
-        e = rocprim::radix_sort_pairs(ctx->tmp.p, have, a.arena_sb, sb_sorted, a_idx, idx_sorted, (size_t)entries, 0u, 32u, st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim radix_sort_pairs: %s", hipGetErrorString(e));
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, a.arena_sb, sb_sorted, a_idx, idx_sorted, (size_t)entries, 0u, 32u, st);
+        }));
         uint64_t *gw = a.arena_w + PP_ARENA;
         uint32_t *gv = a_idx;                                  // the iota is consumed by the sort
         hipLaunchKernelGGL(k_pp_gather, dim3(fbg_blocks(entries, 256)), dim3(256), 0, st, idx_sorted, a.arena_w, a.arena_v, entries, gw, gv);
@@ -1051,21 +1041,15 @@ int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, i
     FBG_TRY(fbg_reserve(ctx, ctx->ps_d, nsub * 8));
     uint64_t *smp = ctx->ps_b.as<uint64_t>(), *srt = ctx->ps_c.as<uint64_t>(), *grid = ctx->ps_d.as<uint64_t>();
     hipLaunchKernelGGL(k_ss_sample, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, ctx->text.as<uint8_t>(), N, g.d_code, g.b, g.K, N / S, S, smp);
-    {
-        size_t bytes = 0;
-        hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, smp, srt, (size_t)S, 0u, (unsigned)g.key_bits, st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim sort size query: %s", hipGetErrorString(e));
-        FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-        size_t have = ctx->tmp.cap;
-        e = rocprim::radix_sort_keys(ctx->tmp.p, have, smp, srt, (size_t)S, 0u, (unsigned)g.key_bits, st);
-        if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim radix_sort_keys: %s", hipGetErrorString(e));
-    }
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_keys(tmp, bytes, smp, srt, (size_t)S, 0u, (unsigned)g.key_bits, st);
+    }));
     {
         // rows that resemble each other tie on most keys: a suffix with a twin somewhere shows up as a twin in the sample
         // with probability S / N.  Sub-buckets full of equal keys make the finish quadratic (52 ms for 2 * 10^8 suffixes of
         // a star phylogeny with gaps), and the scan in suffix order that would follow declines such inputs anyway:
         // leave them to the library sort and say so (ctx->pairs_similar)
-        unsigned long long *d_twins = ctx->scalars.as<unsigned long long>() + 104;
+        unsigned long long *d_twins = &fbg_scalars(ctx)->sample_twins;
         FBG_HIP_TRY(ctx, hipMemsetAsync(d_twins, 0, 8, st));
         hipLaunchKernelGGL(k_ss_twins, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, srt, S, d_twins);
         unsigned long long twins = 0;

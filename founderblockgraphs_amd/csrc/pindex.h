@@ -197,18 +197,7 @@ struct fbg_pindex {
 // Grow-only, on the index's buffer list, outside the context's accounting
 static inline int px_reserve(fbg_pindex *ix, DevBuf &b, size_t bytes) { return fbg_reserve(ix->ctx, b, bytes, &ix->bufs, false); }
 
-template <class F> static int px_with_tmp(fbg_pindex *ix, F &&call)
-{
-    size_t bytes = 0;
-    hipError_t e = call(nullptr, bytes);
-    if (e != hipSuccess) return fbg_fail(ix->ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
-    FBG_TRY(px_reserve(ix, ix->tmp, bytes));
-    size_t have = ix->tmp.cap;
-    e = call(ix->tmp.p, have);
-    if (e != hipSuccess)
-        return fbg_fail(ix->ctx, e == hipErrorOutOfMemory ? FBG_ERR_OOM : FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
-    return FBG_OK;
-}
+template <class F> static int px_with_tmp(fbg_pindex *ix, F &&call) { return fbg_with_tmp(ix->ctx, ix->tmp, &ix->bufs, false, call); }
 
 // The device time of a call lies between ev0 and ev1.  The stage records ev0 where its device work starts and calls
 // px_record_end after its last kernel, before it queues the copies to the host, and px_sync_elapsed after them: the

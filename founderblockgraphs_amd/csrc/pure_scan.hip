@@ -280,18 +280,6 @@ template <int L> __global__ void k_ps_slow(PsArgs a, uint32_t count)
     rs_update(a.r, rs_col_of_rem(a.r, rem), fbg_clamp_lcp(best) + 1);
 }
 
-template <class F> static int ps_with_tmp(fbg_ctx *ctx, F &&call)
-{
-    size_t bytes = 0;
-    hipError_t e = call(nullptr, bytes);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
-    FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-    size_t have = ctx->tmp.cap;
-    e = call(ctx->tmp.p, have);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
-    return FBG_OK;
-}
-
 #define PS_LAUNCH(kernel, layout, grid, block, st, ...)                                                              \
     do {                                                                                                             \
         if ((layout) == FBG_SLOTS_PACKED) hipLaunchKernelGGL((kernel<FBG_SLOTS_PACKED>), grid, block, 0, st, __VA_ARGS__); \
@@ -320,7 +308,7 @@ int fbg_pure_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->gmax.p, 0, (n + 1) * 4, st));
     PsArgs a;
     rs_args_init(ctx, a.r, keys, vals, N, layout, geom.pb, geom.b, geom.key_bits, geom.K);
-    a.counters = ctx->scalars.as<unsigned long long>() + 40;
+    a.counters = fbg_scalars(ctx)->pure;
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.counters, 0, 4 * sizeof(unsigned long long), st));
     // groups
     const unsigned tiles = fbg_blocks(N, PS_TILE);
@@ -329,7 +317,7 @@ int fbg_pure_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     a.gstart = a.grem = a.gflags = nullptr; a.G = 0;
     PS_LAUNCH_GROUPS(layout, false, dim3(tiles), st, a);
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.tile_heads + tiles, 0, 4, st));
-    FBG_TRY(ps_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
         return rocprim::exclusive_scan(tmp, bytes, a.tile_heads, a.tile_heads, 0u, (size_t)tiles + 1, rocprim::plus<uint32_t>(), st);
     }));
     uint32_t G32 = 0;
@@ -353,7 +341,7 @@ int fbg_pure_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     a.rstart = a.rid = nullptr; a.R = 0;
     hipLaunchKernelGGL((k_ps_runs<false>), dim3(gtiles), dim3(PS_THREADS), 0, st, a);
     FBG_HIP_TRY(ctx, hipMemsetAsync(a.rtile + gtiles, 0, 4, st));
-    FBG_TRY(ps_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
         return rocprim::exclusive_scan(tmp, bytes, a.rtile, a.rtile, 0u, (size_t)gtiles + 1, rocprim::plus<uint32_t>(), st);
     }));
     uint32_t R32 = 0;

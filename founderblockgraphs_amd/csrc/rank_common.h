@@ -278,7 +278,7 @@ static inline void rs_args_init(fbg_ctx *ctx, RankArgs &a, uint64_t *keys, uint3
     a.pair_stats = nullptr;
     a.wl = nullptr; a.wl_cap = 0; a.runs_wave_min = 0; a.pairs_in_scan = 0;
     a.big = ctx->big_groups.as<uint32_t>();
-    a.counters = ctx->scalars.as<unsigned long long>() + 32;
+    a.counters = fbg_scalars(ctx)->rank;
     a.g_min = 0;
 }
 

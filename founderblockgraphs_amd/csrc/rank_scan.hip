@@ -1073,18 +1073,6 @@ __global__ void k_rank_finish(FinishArgs a)
     a.out[x] = max((unsigned long long)a.out[x], fx);                     // 1681
 }
 
-template <class F> static int rs_with_tmp(fbg_ctx *ctx, F &&call)
-{
-    size_t bytes = 0;
-    hipError_t e = call(nullptr, bytes);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
-    FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-    size_t have = ctx->tmp.cap;
-    e = call(ctx->tmp.p, have);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
-    return FBG_OK;
-}
-
 // kernels exist for both slot layouts
 #define RS_LAUNCH(kernel, layout, grid, block, st, ...)                                                     \
     do {                                                                                                    \
@@ -1148,11 +1136,11 @@ static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T
     uint32_t *sorted = ctx->dp_a.as<uint32_t>();
     uint32_t *flat = ctx->dp_e.as<uint32_t>();
     if (!sorted_already)
-        FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             return rocprim::radix_sort_keys(tmp, bytes, flat, sorted, (size_t)T, 0u, 32u, st);
         }));
     if (ctx->opt.cand_sort_check) {
-        unsigned long long *d_inv = ctx->scalars.as<unsigned long long>() + 114, inv = 0;
+        unsigned long long *d_inv = &fbg_scalars(ctx)->cand_inversions, inv = 0;
         FBG_HIP_TRY(ctx, hipMemsetAsync(d_inv, 0, sizeof(inv), st));
         hipLaunchKernelGGL(k_cand_inversions, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, sorted, T, d_inv);
         FBG_HIP_TRY(ctx, hipMemcpyAsync(&inv, d_inv, sizeof(inv), hipMemcpyDeviceToHost, st));
@@ -1206,7 +1194,7 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
             a.pair_codes = 1;
             a.pairs_in_scan = ctx->opt.pairs_in_scan != 0;
         }
-        a.pair_stats = ctx->scalars.as<unsigned long long>() + 112;
+        a.pair_stats = fbg_scalars(ctx)->pair_stats;
         FBG_HIP_TRY(ctx, hipMemsetAsync(a.pair_stats, 0, 2 * sizeof(unsigned long long), st));
         FBG_TRY(fbg_reserve(ctx, ctx->ps_g, (size_t)rs_blocks * tie_region * 8));
         FBG_TRY(fbg_reserve(ctx, ctx->ps_h, (size_t)rs_blocks * 4));
@@ -1255,10 +1243,10 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
             FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
             tot = ctx->pin_pair[0]; mx = ctx->pin_pair[1];
         } else {
-            FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
                 return rocprim::exclusive_scan(tmp, bytes, d_counts, d_offs, 0u, (size_t)(rs_blocks + 1), rocprim::plus<uint32_t>(), st);
             }));
-            FBG_TRY(rs_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
                 return rocprim::reduce(tmp, bytes, d_counts, d_max, 0u, (size_t)rs_blocks, rocprim::maximum<uint32_t>(), st);
             }));
             FBG_HIP_TRY(ctx, hipMemcpyAsync(&tot, d_offs + rs_blocks, 4, hipMemcpyDeviceToHost, st));
@@ -1350,7 +1338,7 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     const int layout = rs_layout(geom);
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_RANKSCAN));
-    unsigned long long *cnt = ctx->scalars.as<unsigned long long>() + 32;
+    unsigned long long *cnt = fbg_scalars(ctx)->rank;
     int launches = 0;
     FBG_TRY(fbg_reserve(ctx, ctx->gmax, (n + 1) * 4));             // (before rs_args_init reads the pointer)
     RankArgs a;
@@ -1453,7 +1441,7 @@ int fbg_rank_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_
     fbg_remember_slots(ctx, keys, vals, rs_layout(geom), geom);
     const int layout = rs_layout(geom);
     FBG_TRY(fbg_reserve(ctx, ctx->gmax, (n + 1) * 4));
-    unsigned long long *cnt = ctx->scalars.as<unsigned long long>() + 32;
+    unsigned long long *cnt = fbg_scalars(ctx)->rank;
     FBG_TRY(rs_zero_counters(ctx, cnt, count));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->gmax.p, 0, (n + 1) * 4, st));
     int good = pre_ok && count >= 2 * FBG_PART_HALO;
@@ -1538,7 +1526,7 @@ int fbg_rank_part_unfilled(fbg_ctx *ctx, uint64_t *unfilled)
     *unfilled = 0;
     if (ctx->ix.part_gmin <= 1) return FBG_OK;
     hipStream_t st = ctx->stream;
-    unsigned long long *cnt = ctx->scalars.as<unsigned long long>() + 32;
+    unsigned long long *cnt = fbg_scalars(ctx)->rank;
     FBG_HIP_TRY(ctx, hipMemsetAsync(cnt + 4, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_count_unfilled, dim3(fbg_blocks(ctx->n, 256)), dim3(256), 0, st, ctx->gmax.as<uint32_t>(), ctx->n, ctx->ix.part_gmin,
                        ctx->reversed, cnt);

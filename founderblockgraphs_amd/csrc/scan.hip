@@ -397,7 +397,7 @@ int fbg_scan_columns(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disab
     } else if (x1 > x0) {
         hipStream_t st = ctx->stream;
         FBG_TRY(fbg_reserve(ctx, ctx->xlist, (ctx->n + 1) * 4));
-        unsigned long long *xcount = ctx->scalars.as<unsigned long long>() + 24;
+        unsigned long long *xcount = &fbg_scalars(ctx)->scan_exceptions;
         FBG_HIP_TRY(ctx, hipMemsetAsync(xcount, 0, sizeof(unsigned long long), st));
         ScanArgs a;
         a.rec = ctx->rec.as<uint4>(); a.exc = nullptr;

@@ -1307,18 +1307,6 @@ __global__ void k_sp_count_heads(const uint32_t *__restrict__ list, uint32_t cou
     if ((threadIdx.x & 63) == 0 && mask) atomicAdd(out, (unsigned long long)__popcll(mask));
 }
 
-template <class F> static int sp_with_tmp(fbg_ctx *ctx, F &&call)
-{
-    size_t bytes = 0;
-    hipError_t e = call(nullptr, bytes);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
-    FBG_TRY(fbg_reserve(ctx, ctx->tmp, bytes));
-    size_t have = ctx->tmp.cap;
-    e = call(ctx->tmp.p, have);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
-    return FBG_OK;
-}
-
 static void sp_args(fbg_ctx *ctx, SpArgs &a, int disable_tricks)
 {
     a.keys = ctx->ix.rk_keys; a.vals = ctx->ix.sa_ptr; a.N = ctx->N;
@@ -1331,7 +1319,7 @@ static void sp_args(fbg_ctx *ctx, SpArgs &a, int disable_tricks)
     a.pos = ctx->pos.as<uint32_t>(); a.tot = ctx->tot.as<uint32_t>();
     a.cwin = ctx->gapfree ? nullptr : ctx->sp_cwin.as<CWin>();
     a.wpr = (uint32_t)((ctx->n + 127) / 128);
-    a.is_ignore = ctx->have_ignore ? ctx->small.as<uint8_t>() : nullptr;
+    a.is_ignore = ctx->have_ignore ? fbg_small(ctx)->ignore_tab : nullptr;
     a.ign_lo = ctx->grs_ign_lo; a.ign_hi = ctx->grs_ign_hi;
     a.tile_cnt = ctx->sp_tiles.as<unsigned long long>();
     a.gstart = ctx->sp_gstart.as<uint32_t>(); a.gcol = ctx->sp_gcol.as<uint32_t>(); a.gflags = ctx->sp_gflags.as<uint32_t>();
@@ -1341,8 +1329,8 @@ static void sp_args(fbg_ctx *ctx, SpArgs &a, int disable_tricks)
     a.odd = ctx->sp_odd.as<uint32_t>(); a.odd_cap = ctx->sp_odd_cap;
     a.irr = ctx->sp_irr.as<uint2>(); a.n_irr = ctx->sp_n_irr;
     a.fmax = ctx->gmax.as<uint32_t>();
-    a.counters = ctx->scalars.as<unsigned long long>() + 208;     // (gapped_rank.hip: 128 .. 202)
-    a.code = ctx->small.as<uint8_t>() + 2048;                     // (fbg_key_setup's table)
+    a.counters = fbg_scalars(ctx)->span;
+    a.code = fbg_small(ctx)->code_tab;                            // (fbg_key_setup's table)
     a.chain = ctx->sp_chain.as<SpChain>(); a.chain_cap = (uint32_t)(ctx->sp_chain.cap / sizeof(SpChain));
     a.slow = ctx->sp_slow.as<uint32_t>(); a.slow_cap = (uint32_t)(ctx->sp_slow.cap / 8);    // (the other half: the big groups' list, sorted)
     a.mins32 = ctx->gapfree ? nullptr : ctx->sp_mins.as<uint32_t>();
@@ -1507,7 +1495,7 @@ static int sp_scan(fbg_ctx *ctx, int disable_tricks, int *ok, int *launches)
             // of a thousand rows that go along for thousands of symbols: beyond a few such groups per 10^6 suffixes the
             // record path is the cheaper one (the option span_scan = 1 insists)
             uint32_t *sorted = a.slow + a.slow_cap;
-            FBG_TRY(sp_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
                 return rocprim::radix_sort_keys(tmp, bytes, (const uint32_t *)a.slow, sorted, (size_t)n_slow, 0u, 32u, st);
             }));
             FBG_HIP_TRY(ctx, hipMemsetAsync(a.counters + 15, 0, 8, st));
@@ -1588,7 +1576,7 @@ int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g,
         sp_args(ctx, a, 0);
         hipLaunchKernelGGL((k_sp_groups<false>), dim3(tiles), dim3(SP_THREADS), 0, st, a);
         FBG_HIP_TRY(ctx, hipMemsetAsync(a.tile_cnt + tiles, 0, 8, st));
-        FBG_TRY(sp_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             return rocprim::exclusive_scan(tmp, bytes, a.tile_cnt, a.tile_cnt, 0ull, (size_t)tiles + 1, rocprim::plus<unsigned long long>(), st);
         }));
         unsigned long long tot = 0;
@@ -1611,7 +1599,7 @@ int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g,
         a.rtile = ctx->ps_e.as<uint32_t>();
         hipLaunchKernelGGL((k_sp_runs<false>), dim3(gtiles), dim3(SP_THREADS), 0, st, a);
         FBG_HIP_TRY(ctx, hipMemsetAsync(a.rtile + gtiles, 0, 4, st));
-        FBG_TRY(sp_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             return rocprim::exclusive_scan(tmp, bytes, a.rtile, a.rtile, 0u, (size_t)gtiles + 1, rocprim::plus<uint32_t>(), st);
         }));
         uint32_t R32 = 0;
@@ -1650,7 +1638,7 @@ int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g,
             hipLaunchKernelGGL(k_sp_list_cols, dim3(fbg_blocks(cnt, 256)), dim3(256), 0, st, a, (const uint32_t *)lst, cnt, cols);
             int nb = 1;
             while ((1ull << nb) < n + 1) nb++;
-            FBG_TRY(sp_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
                 return rocprim::radix_sort_pairs(tmp, bytes, cols, cols_s, lst, list_s, (size_t)cnt, 0u, (unsigned)nb, st);
             }));
             FBG_HIP_TRY(ctx, hipMemcpyAsync(lst, list_s, (size_t)cnt * 4, hipMemcpyDeviceToDevice, st));

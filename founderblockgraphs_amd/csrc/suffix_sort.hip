@@ -724,28 +724,13 @@ __global__ void k_iota(uint32_t *__restrict__ a, uint64_t cnt)
     if (k < cnt) a[k] = (uint32_t)k;
 }
 
-static int ensure_tmp(fbg_ctx *ctx, size_t bytes) { return fbg_reserve(ctx, ctx->tmp, bytes); }
-
-template <class F> static int with_tmp(fbg_ctx *ctx, F &&call)
-{
-    size_t bytes = 0;
-    hipError_t e = call(nullptr, bytes);
-    if (e != hipSuccess) return fbg_fail(ctx, FBG_ERR_HIP, "rocprim size query: %s", hipGetErrorString(e));
-    FBG_TRY(ensure_tmp(ctx, bytes));
-    size_t have = ctx->tmp.cap;
-    e = call(ctx->tmp.p, have);
-    if (e != hipSuccess)
-        return fbg_fail(ctx, e == hipErrorOutOfMemory ? FBG_ERR_OOM : FBG_ERR_HIP, "rocprim call: %s", hipGetErrorString(e));
-    return FBG_OK;
-}
-
 // Alphabet compaction (order preserving) and the key geometry: b bits per symbol, K symbols per key.
 // compact = true asks for the separator-free coding of the rank-order scan; g->compact tells whether it applies.
 int fbg_key_setup(fbg_ctx *ctx, bool compact, KeyGeom *g, int *launches)
 {
     const uint64_t N = ctx->N;
     hipStream_t st = ctx->stream;
-    uint8_t *d_code = ctx->small.as<uint8_t>() + 2048;    // small: [0,256) ignore table, [2048,2304) code table, [4096,6144) histogram
+    uint8_t *d_code = fbg_small(ctx)->code_tab;
     const uint64_t *hist = ctx->byte_hist;                // made by fbg_build_text
     if (hist[0] != 1)
         return fbg_fail(ctx, FBG_ERR_INVALID, "the MSA contains a NUL byte; the text needs a unique 0 sentinel");
@@ -817,7 +802,7 @@ static int sort_slots(fbg_ctx *ctx, const KeyGeom &g, bool key_flags, uint64_t c
         unsigned lo = (unsigned)g.pb;
         const unsigned hi = (unsigned)(g.pb + g.key_bits);
         if (hi == 64 && count < (1u << 23)) lo = 0;
-        return with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        return fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             return rocprim::radix_sort_keys<fbg_sort_config>(tmp, bytes, ka, kb, (size_t)count, lo, hi, st);
         });
     }
@@ -825,7 +810,7 @@ static int sort_slots(fbg_ctx *ctx, const KeyGeom &g, bool key_flags, uint64_t c
     unsigned lo = g.wide ? (unsigned)g.pb : key_flags ? 2u : 0u;
     const unsigned hi = lo + (unsigned)g.key_bits;
     if (hi == 64 && count < (1u << 23)) lo = 0;        // same caution as above
-    return with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+    return fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
         return rocprim::radix_sort_pairs<fbg_sort_config>(tmp, bytes, ka, kb, va, vb, (size_t)count, lo, hi, st);
     });
 }
@@ -895,11 +880,11 @@ static int sample_says_similar(fbg_ctx *ctx, const KeyGeom &g, bool *similar, in
     FBG_TRY(fbg_reserve(ctx, ctx->dp_g, S * 8));
     FBG_TRY(fbg_reserve(ctx, ctx->dp_h, S * 8));
     uint64_t *smp = ctx->dp_g.as<uint64_t>(), *srt = ctx->dp_h.as<uint64_t>();
-    unsigned long long *d_count = ctx->scalars.as<unsigned long long>() + 8;
+    unsigned long long *d_count = &fbg_scalars(ctx)->sample_count;
     FBG_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 8, st));
     hipLaunchKernelGGL(k_sample_keys, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, ctx->text.as<uint8_t>(), N, g.d_code, g.b, g.K,
                        g.compact ? 1 : 0, stride, S, smp);
-    FBG_TRY(with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
         return rocprim::radix_sort_keys(tmp, bytes, smp, srt, (size_t)S, 0u, (unsigned)g.key_bits, st);
     }));
     hipLaunchKernelGGL(k_count_equal_neighbours, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, srt, S, d_count);
@@ -1057,7 +1042,7 @@ int fbg_suffix_sort(fbg_ctx *ctx)
     flags = ctx->flags.as<uint8_t>();
     // groups of equal keys -> records (rank = SA index of the group head, key-derived LCPs), unresolved flags
     hipLaunchKernelGGL(k_mark_heads, dim3(fbg_blocks(N, 256)), dim3(256), 0, st, keysB, N, (const uint32_t *)nullptr, grp);
-    FBG_TRY(with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+    FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
         return rocprim::inclusive_scan(tmp, bytes, grp, grp, (size_t)N, rocprim::maximum<uint32_t>(), st);
     }));
     // FBG_BP_MIN lowers the size from which the records travel to their positions in passes (tests); FBG_RECORD_SCATTER
@@ -1080,7 +1065,7 @@ int fbg_suffix_sort(fbg_ctx *ctx)
             hipLaunchKernelGGL(k_bp_windows, dim3(fbg_blocks(nwin, 4)), dim3(256), 0, st, ct.colT, N, ct.n, win, win_lo);
             launches++;
         }
-        unsigned long long *bflag = ctx->scalars.as<unsigned long long>() + 120;
+        unsigned long long *bflag = &fbg_scalars(ctx)->by_position;
         FBG_HIP_TRY(ctx, hipMemsetAsync(cur1, 0, (ntop + nleaf + 2) * 8, st));
         FBG_HIP_TRY(ctx, hipMemsetAsync(bflag, 0, 8, st));
         BpArgs a;
@@ -1128,7 +1113,7 @@ int fbg_suffix_sort(fbg_ctx *ctx)
             uint32_t *tile_cnt = ctx->ps_a.as<uint32_t>();
             hipLaunchKernelGGL((k_flag_compact<false>), dim3(ftiles), dim3(FC_THREADS), 0, st, flags, cnt, tile_cnt, sel);
             FBG_HIP_TRY(ctx, hipMemsetAsync(tile_cnt + ftiles, 0, 4, st));
-            FBG_TRY(with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+            FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
                 return rocprim::exclusive_scan(tmp, bytes, tile_cnt, tile_cnt, 0u, (size_t)ftiles + 1, rocprim::plus<uint32_t>(), st);
             }));
             hipLaunchKernelGGL((k_flag_compact<true>), dim3(ftiles), dim3(FC_THREADS), 0, st, flags, cnt, tile_cnt, sel);
@@ -1168,14 +1153,14 @@ int fbg_suffix_sort(fbg_ctx *ctx)
         hipLaunchKernelGGL(k_doubling_keys, dim3(fbg_blocks(ncnt, 256)), dim3(256), 0, st, vals_new, grp_new, ncnt,
                            rec, h, N, nb, dkeys_in);
         // sort by (group, rank at +h); the sorted positions go back to the same SA slots
-        FBG_TRY(with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             if (ncnt >= (1u << 23))
                 return rocprim::radix_sort_pairs<fbg_sort_config>(tmp, bytes, dkeys_in, dkeys_out, vals_new, valsA, (size_t)ncnt, 0u,
                                                                   (unsigned)(2 * nb), st);
             return rocprim::radix_sort_pairs(tmp, bytes, dkeys_in, dkeys_out, vals_new, valsA, (size_t)ncnt, 0u, (unsigned)(2 * nb), st);
         }));
         hipLaunchKernelGGL(k_mark_heads, dim3(fbg_blocks(ncnt, 256)), dim3(256), 0, st, dkeys_out, ncnt, where_new, grp_new);
-        FBG_TRY(with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             return rocprim::inclusive_scan(tmp, bytes, grp_new, grp_new, (size_t)ncnt, rocprim::maximum<uint32_t>(), st);
         }));
         hipLaunchKernelGGL(k_apply_groups, dim3(fbg_blocks(ncnt, 256)), dim3(256), 0, st, grp_new, valsA, ncnt,
@@ -1240,7 +1225,7 @@ int fbg_part_sort(fbg_ctx *ctx, int part, int nparts, uint8_t *d_blob, int *ok)
         FBG_TRY(fbg_reserve(ctx, ctx->dp_h, S * 8));
         uint64_t *smp = ctx->dp_g.as<uint64_t>(), *smp_sorted = ctx->dp_h.as<uint64_t>();
         hipLaunchKernelGGL(k_sample_keys, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, T, N, g.d_code, g.b, g.K, g.compact ? 1 : 0, stride, S, smp);
-        FBG_TRY(with_tmp(ctx, [&](void *tmp, size_t &bytes) {
+        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             return rocprim::radix_sort_keys(tmp, bytes, smp, smp_sorted, (size_t)S, 0u, (unsigned)g.key_bits, st);
         }));
         launches += 2;
@@ -1254,7 +1239,7 @@ int fbg_part_sort(fbg_ctx *ctx, int part, int nparts, uint8_t *d_blob, int *ok)
     if (pre_ok)     // three passes over 12-byte slots, packing and filtering fused into the first (msd_sort_pairs.hip)
         FBG_TRY(fbg_msd_sort_part(ctx, g, lo, hi, part + 1 >= nparts, nparts, FBG_PART_HALO, &count, &msd_ok, &launches));
     if ((pre_ok || gapped) && !msd_ok) {
-        unsigned long long *d_count = ctx->scalars.as<unsigned long long>() + 8;
+        unsigned long long *d_count = &fbg_scalars(ctx)->sample_count;
         uint64_t cap = N / nparts + N / 8 + 65536;
         if (cap > N) cap = N;
         for (int attempt = 0; attempt < 2; attempt++) {

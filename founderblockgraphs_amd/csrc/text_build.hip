@@ -588,29 +588,29 @@ int fbg_build_text(fbg_ctx *ctx, const uint8_t *ignore, uint64_t ignore_len)
     FBG_TRY(fbg_reserve(ctx, ctx->pos, m * 4));
     // Option front_one_fill (default 1): the byte histogram and the pass's counts live behind the row totals, so that one fill
     // clears what the counting pass adds to and one copy brings histogram and counts into pinned words.  0: the histogram in
-    // `small`, the counts in scalars[0..2], a fill each, and two copies -- the counts into a stack array, a staged copy.
+    // `small`, the counts in the scalars' `front`, a fill each, and two copies -- the counts into a stack array, a staged copy.
     const bool one_fill = ctx->opt.front_one_fill != 0;
-    const size_t tot_bytes = (m * 4 + 7) & ~(size_t)7, hist_bytes = 256 * sizeof(unsigned long long), cnt_bytes = 8 * sizeof(unsigned long long);
+    const size_t tot_bytes = (m * 4 + 7) & ~(size_t)7, hist_bytes = sizeof(ctx->byte_hist), cnt_bytes = 8 * sizeof(unsigned long long);
     FBG_TRY(fbg_reserve(ctx, ctx->tot, tot_bytes + hist_bytes + cnt_bytes));
-    FBG_TRY(fbg_reserve(ctx, ctx->scalars, 256 * sizeof(unsigned long long)));
-    FBG_TRY(fbg_reserve(ctx, ctx->small, 8192));   // [0,256) ignore table, [2048,2304) code table, [4096,6144) symbol histogram (front_one_fill = 0)
+    FBG_TRY(fbg_reserve_scalars(ctx));
+    FBG_TRY(fbg_reserve(ctx, ctx->small, FBG_SMALL_BYTES));
     if (one_fill) {
         if (!ctx->pin_front) FBG_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->pin_front), hist_bytes + cnt_bytes, hipHostMallocDefault));
         FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->tot.p, 0, tot_bytes + hist_bytes + cnt_bytes, st));
     } else
-        FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->scalars.p, 0, 64 * sizeof(unsigned long long), st));
+        FBG_HIP_TRY(ctx, hipMemsetAsync(fbg_scalars(ctx)->front, 0, sizeof(FbgScalars::front), st));
 
     ctx->have_ignore = ignore_len > 0;
     ctx->cells_built = false;
     memset(ctx->ignore_tab, 0, sizeof(ctx->ignore_tab));
     if (ctx->have_ignore) {
         for (uint64_t k = 0; k < ignore_len; k++) ctx->ignore_tab[ignore[k]] = 1;   // fbg.cpp:1853,1868
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->small.as<uint8_t>(), ctx->ignore_tab, 256, hipMemcpyHostToDevice, st));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(fbg_small(ctx)->ignore_tab, ctx->ignore_tab, 256, hipMemcpyHostToDevice, st));
     }
-    unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(one_fill ? ctx->tot.as<uint8_t>() + tot_bytes : ctx->small.as<uint8_t>() + 4096);
-    unsigned long long *sc = one_fill ? d_hist + 256 : ctx->scalars.as<unsigned long long>();
+    unsigned long long *d_hist = one_fill ? reinterpret_cast<unsigned long long *>(ctx->tot.as<uint8_t>() + tot_bytes) : fbg_small(ctx)->hist;
+    unsigned long long *sc = one_fill ? d_hist + 256 : fbg_scalars(ctx)->front;
     if (!one_fill) {
-        FBG_HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, 2048, st));
+        FBG_HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, sizeof(FbgSmall::hist), st));
         FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->tot.p, 0, m * 4, st));
     }
     const unsigned nseg = (unsigned)((n + RC_SEG - 1) / RC_SEG);
@@ -767,7 +767,7 @@ int fbg_build_cell_tables(fbg_ctx *ctx)
                            ctx->colT.as<uint32_t>(), (const uint32_t *)segoff, (uint16_t *)nullptr);
     }
     if (ctx->have_ignore) {
-        const uint8_t *d_is_ignore = ctx->small.as<uint8_t>();
+        const uint8_t *d_is_ignore = fbg_small(ctx)->ignore_tab;
         FBG_TRY(fbg_reserve(ctx, ctx->igrow, m * n * 4));
         hipLaunchKernelGGL(k_ignore_segmin, dim3(nseg, (unsigned)m), dim3(TB_THREADS), 0, st, ctx->d_msa, n, d_is_ignore, segmin);
         hipLaunchKernelGGL(k_ignore_sweep, dim3(nseg, (unsigned)m), dim3(TB_THREADS), 0, st, ctx->d_msa, n, d_is_ignore,

@@ -1423,6 +1423,117 @@ def test_one_engine_builds_every_index_kind_in_sequence():
             assert bad.size == 0, (name, bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())
 
 
+def test_one_engine_runs_every_owner_of_the_scalar_words_in_two_orders():
+    """Every stage that keeps counters or flags in the context's shared scalar words (FbgScalars, fbg_internal.h), on one
+    Engine, in two different orders, each result against the oracle both times: a word that two stages share, or that a
+    stage reads where another one left something, shows up as a wrong result in one of the orders.  The steps: a gap-free
+    build through the MSD sort and the slot-level scan (with the check of the candidate order), similar rows through the
+    group-level scan, a key-range partition (the count of the slots it keeps), rows with gaps and ignore characters through
+    the sample sort of pairs and the scan in suffix order (counting pass with front_one_fill = 0: its counts in the scalar
+    words, its histogram in `small`), the scan on column spans, the record path (records by position, then scan_f with its
+    exception columns), the three DPs and the block graph.  Every step asserts from get_option that the path it is
+    there for ran.  (The rank scan's histogram and the lean scan's pair statistics exist above 2^22 symbols only:
+    test_rank_scan_sampled_regime_matches_oracle, test_scan_tail.py.)"""
+    import torch
+    import founderblockgraphs_amd as F
+    rng = np.random.default_rng(9200)
+    unlike = random_msa(rng, 40, 3000)                      # (the smallest shape of test_msd_cursors.py)
+    similar = random_msa(rng, 16, 3000, similar=0.97)
+    small = random_msa(rng, 16, 2000)
+    gapped = random_msa(rng, 12, 3000, gap_p=0.02, gap_run=5, n_p=0.01)
+    star = star_msa(rng, 16, 2000, gap_cells=0.03, gap_run=7)
+    f_unlike, f_similar, f_small = O.compute_f(unlike), O.compute_f(similar), O.compute_f(small)
+    f_gapped, f_star = O.compute_f(gapped, ignore="N"), O.compute_f(star)
+    v_unlike, v_gapped = O.segment_v(unlike), O.gapped_v(gapped)
+    dp_minmax, dp_repeatfree, dp_gapped = O.minmax_dp(f_unlike), O.segment_dp(v_unlike), O.segment2_dp(v_gapped)
+    cuts = np.concatenate([np.arange(40, 2000, 50), [2000]]).astype(np.uint64)
+    graph = _block_graph_reference(star, cuts)
+
+    def build_and_scan(eng, msa, ignore, opts, want, check):
+        n = msa.shape[1]
+        with fbg_options(eng, opts):
+            eng.msa_load_host(msa)
+            eng.index_build(ignorechars=ignore)
+            check()
+            d = torch.zeros(n, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            eng.scan_f(0, n, d.data_ptr(), False)
+            eng.sync()
+        got = d.cpu().numpy().astype(np.uint64)
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, (bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())
+
+    def kind(eng, want, span=0):
+        assert eng.get_option("index_kind") == want and eng.get_option("span_scan_used") == span
+
+    def msd_rank(eng):
+        def ran():
+            kind(eng, 1)
+            assert eng.get_option("msd_decline") == 0 and eng.get_option("cand_inversions") == 0
+        build_and_scan(eng, unlike, "", {"msd_min": 1, "pure_scan": -1, "cand_sort_check": 1}, f_unlike, ran)
+
+    def pure(eng):       # (pure_scan = 1: the slot-level scan is not tried, so a ranked index is the group-level scan's)
+        build_and_scan(eng, similar, "", {"pure_scan": 1}, f_similar, lambda: kind(eng, 1))
+
+    def partition(eng):
+        n = small.shape[1]
+        eng.msa_load_host(small)
+        ok1, ok2, ok3 = _partitioned([eng], n)
+        assert all(ok1) and all(ok2) and all(ok3), (ok1, ok2, ok3)
+        assert eng.get_option("index_kind") == 3
+        d = torch.zeros(n, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        eng.scan_f(0, n, d.data_ptr())
+        eng.sync()
+        assert np.array_equal(d.cpu().numpy().astype(np.uint64), f_small)
+
+    def gapped_scan(eng):
+        def ran():
+            kind(eng, 2)
+            assert eng.get_option("pairs_rb") >= 0
+        build_and_scan(eng, gapped, "N", {"span_scan": -1, "msd_min": 1, "front_one_fill": 0}, f_gapped, ran)
+
+    def span(eng):
+        build_and_scan(eng, star, "", {"span_scan": 1}, f_star, lambda: kind(eng, 2, span=1))
+
+    def record(eng):
+        build_and_scan(eng, small, "", {"no_ranked": 1, "bp_min": 1}, f_small, lambda: kind(eng, 0))
+
+    def minmax(eng):
+        mml, bt, b = dp_minmax
+        gb, gmml, gbt = eng.minmax_dp(f_unlike, full=True)
+        assert np.array_equal(gb, b) and np.array_equal(gmml, mml) and np.array_equal(gbt, bt)
+
+    def nonelastic(eng, call, v, want):
+        s, prev, b = want
+        gs, gprev, gb = call(v)
+        assert np.array_equal(gs, s) and np.array_equal(gprev, prev)
+        assert (b is None) == (gb is None) and (b is None or np.array_equal(gb, b))
+
+    def repeatfree(eng):
+        nonelastic(eng, eng.repeatfree_dp, v_unlike, dp_repeatfree)
+
+    def gapped_dp(eng):
+        nonelastic(eng, eng.gapped_dp, v_gapped, dp_gapped)
+
+    def block_graph(eng):
+        eng.msa_load_host(star)
+        node_of, first, rep_row, ecount, edges = eng.block_graph(cuts)
+        r_node, r_first, r_reps, r_edges = graph
+        assert np.array_equal(first, r_first) and np.array_equal(node_of, r_node)
+        for j in range(len(cuts)):
+            assert list(rep_row[j, :int(first[j + 1] - first[j])]) == r_reps[j]
+            assert [(int(x) >> 32, int(x) & 0xffffffff) for x in edges[j, :int(ecount[j])]] == r_edges[j], j
+
+    steps = [msd_rank, minmax, record, pure, repeatfree, partition, gapped_scan, gapped_dp, span, block_graph]
+    other = [span, gapped_dp, pure, msd_rank, block_graph, record, minmax, gapped_scan, partition, repeatfree]
+    assert sorted(s.__name__ for s in steps) == sorted(s.__name__ for s in other)
+    with F.Engine(0) as eng:
+        for order in (steps, other):
+            for step in order:
+                step(eng)
+
+
 def test_span_scan_large_groups_by_chains(engine):
     """Groups of more than 1024 members through the chains along the later keys' groups (option span_scan = 3: the path
     the large instances of k_sp_odd_pairs replaced as the default) -- same f (fbg.cpp:1579-1695)."""
