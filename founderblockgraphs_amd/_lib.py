@@ -119,6 +119,10 @@ SIGNATURES = {
     "fbg_pindex_chains_graph_cigar": (C.c_int, [vp, u32p, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_chains_graph_cigar_fetch": (C.c_int, [vp, u64p, u32p]),
     "fbg_pindex_graph_cigar_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
+    "fbg_pindex_chains_mapq": (C.c_int, [vp, C.c_uint64, u64p, u32p, u32p, u32p, u8p, C.POINTER(C.c_double)]),
+    "fbg_pindex_chains_mapq_fetch": (C.c_int, [vp, u32p, u32p, C.POINTER(C.c_double)]),
+    "fbg_pindex_mapq_strands": (C.c_int, [vp, u8p, C.POINTER(C.c_double)]),
+    "fbg_pindex_mapq_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
     "fbg_pindex_seeds_strands": (C.c_int, [vp, u8p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_chain_strands": (C.c_int, [vp, u8p, u32p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "fbg_segmentation_validate": (C.c_int, [vp, u64p, C.c_uint64, u8p, C.c_uint64, u8p, u64p, u64p, C.POINTER(C.c_double)]),

@@ -518,7 +518,7 @@ class PatternIndex:
         return dict(zip(("rows", "table_bytes", "words_per_set", "places_unsupported", "chains_unsupported"), (x.value for x in v)))
 
     def seeds(self, patterns, min_length=1, max_per_seed=0, msa=False, chain=False, band=None, min_score=0, strands=False,
-              complement=None, rows=False, by_row=False):
+              complement=None, rows=False, by_row=False, mapq=False, mapq_margin=0):
         """Every read cut greedily into the maximal pieces the search accepts (fbg_pindex_seeds, _fetch and _places):
         seeds of at least min_length symbols, each with what occurrences() reports for that substring, at most
         max_per_seed places per seed and list -> Seeds.  msa=True: as for occurrences() (fbg_pindex_seeds_msa).
@@ -528,7 +528,10 @@ class PatternIndex:
         complements, and chains() also picks a strand per read.  rows=True (an index built with rows=True only): also,
         per start place, the number of MSA rows that carry it and the smallest of them (fbg_pindex_seeds_rows), as
         Seeds.start_n_rows / Seeds.start_first_row; with chain=True the chains get their row sets too.  by_row=True
-        (with chain=True): the chains are those of chains(by_row=True)."""
+        (with chain=True): the chains are those of chains(by_row=True).  mapq=True (with chain=True): the chains carry
+        their second-best chain and mapping quality, as chains(mapq=True, mapq_margin=mapq_margin)."""
+        if mapq and not chain:
+            raise ValueError("mapq=True needs chain=True")
         if min_length < 1:
             raise ValueError("min_length must be 1 or more")
         if max_per_seed < 0:
@@ -570,7 +573,7 @@ class PatternIndex:
             self._eng._chk(self._L.fbg_pindex_seeds_rows(self._h, u32(nr), u32(fr), C.byref(ms5)))
             out.start_n_rows, out.start_first_row, out.rows_ms = nr[:ns], fr[:ns], ms5.value
         if chain:
-            out.chains = self.chains(band=band, min_score=min_score, rows=rows, by_row=by_row)
+            out.chains = self.chains(band=band, min_score=min_score, rows=rows, by_row=by_row, mapq=mapq, mapq_margin=mapq_margin)
         return out
 
     def align_stats(self):
@@ -612,7 +615,7 @@ class PatternIndex:
         return dict(zip(("paths", "ops", "columns", "history_bytes", "batches"), (x.value for x in v)))
 
     def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False, by_row=False,
-               graph=False, graph_pad=16, max_cells=0, select=None, graph_cigar=False):
+               graph=False, graph_pad=16, max_cells=0, select=None, graph_cigar=False, mapq=False, mapq_margin=0):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -636,7 +639,15 @@ class PatternIndex:
         read of the last seeds() call, None: all) is zero.  After seeds(strands=True) also Chains.best_graph_edits.
         graph_cigar=True (with graph=True): also the alignment path of every such read against the stretch of the graph its
         path spells (fbg_pindex_chains_graph_cigar and _fetch), as Chains.graph_cigar_off and .graph_cigar_ops, read with
-        .graph_cigar(k) and .graph_cigar_runs(k)."""
+        .graph_cigar(k) and .graph_cigar_runs(k).  mapq=True: also the second-best chain of every read, chained on the
+        anchors outside the MSA columns of its chain widened by mapq_margin columns on either side (chains through other
+        alleles in the same columns are the same locus), and the mapping quality 60 * (score - min(second, score)) // read
+        length (fbg_pindex_chains_mapq and _fetch), as Chains.second_score, .second_lo, .second_hi, .mapq, .second_off,
+        .second_place, .second_seed and .second(k); after seeds(strands=True) also Chains.mapq_stranded, where the other
+        strand's score competes too (fbg_pindex_mapq_strands), and Chains.best_mapq.  A read matched in one piece has no
+        seed at a shorter copy elsewhere and gets second_score 0."""
+        if mapq_margin < 0:
+            raise ValueError("mapq_margin must be 0 or more")
         if cigar and not align:
             raise ValueError("cigar=True needs align=True")
         if graph_cigar and not graph:
@@ -679,6 +690,27 @@ class PatternIndex:
             out.strand, out.best_score = strand[:given], best[:given]
             out.strand_counts = dict(zip(("forward", "reverse", "none"), (x.value for x in cnt)))
             out.strand_ms = ms3.value
+        if mapq:
+            soff = np.zeros(k + 1, dtype=np.uint64)
+            sec, slo, shi = (np.zeros(max(k, 1), dtype=np.uint32) for _ in range(3))
+            mq = np.zeros(max(k, 1), dtype=np.uint8)
+            ms9, ms10 = C.c_double(0), C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chains_mapq(self._h, min(int(mapq_margin), 0xffffffffffffffff), _u64(soff),
+                                                          *[a.ctypes.data_as(_lib.u32p) for a in (sec, slo, shi)], _u8(mq),
+                                                          C.byref(ms9)))
+            t2 = int(soff[k])
+            splace, sseed = np.zeros(max(t2, 1), dtype=np.uint32), np.zeros(max(t2, 1), dtype=np.uint32)
+            self._eng._chk(self._L.fbg_pindex_chains_mapq_fetch(self._h, splace.ctypes.data_as(_lib.u32p),
+                                                                sseed.ctypes.data_as(_lib.u32p), C.byref(ms10)))
+            out.second_off, out.second_score, out.second_lo, out.second_hi, out.mapq = soff, sec[:k], slo[:k], shi[:k], mq[:k]
+            out.second_place, out.second_seed, out.mapq_ms = splace[:t2], sseed[:t2], ms9.value
+            if given is not None:
+                smq = np.zeros(max(k, 1), dtype=np.uint8)
+                self._eng._chk(self._L.fbg_pindex_mapq_strands(self._h, _u8(smq), None))
+                out.mapq_stranded = smq[:k]
+                pick = np.where(out.strand[:given] == 1, given, 0) + np.arange(given)
+                out.best_mapq = np.where(out.strand[:given] == _lib.STRAND_NONE, np.uint8(0),
+                                         out.mapq_stranded[pick] if given else out.mapq_stranded[:0]).astype(np.uint8)
         if rows:
             words = self.rows_stats()["words_per_set"]
             nr, fr = np.zeros(max(k, 1), dtype=np.uint32), np.zeros(max(k, 1), dtype=np.uint32)
@@ -736,6 +768,13 @@ class PatternIndex:
             self._eng._chk(self._L.fbg_pindex_chains_graph_cigar_fetch(self._h, _u64(coff), ops.ctypes.data_as(_lib.u32p)))
             out.graph_cigar_off, out.graph_cigar_ops, out.graph_cigar_ms = coff, ops[:total.value], ms8.value
         return out
+
+    def mapq_stats(self):
+        """{reads_with_second, anchors_kept, anchors_excluded, mapq0, mapq60} of the last chains(mapq=True), over the reads
+        with a non-empty chain: see fbg_pindex_mapq_stats."""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._eng._chk(self._L.fbg_pindex_mapq_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("reads_with_second", "anchors_kept", "anchors_excluded", "mapq0", "mapq60"), (x.value for x in v)))
 
     def by_row_stats(self):
         """{reads_lds, reads_device, reads_too_many, reads_no_row, anchors_kept, lds_max, max_places} of the last
@@ -963,6 +1002,17 @@ class Chains:
       graph_cigar_ops   uint32 per run, as cigar_ops, in the order of the read and of its path; graph_cigar(k) gives the
                       string, graph_cigar_runs(k) the (code, length) pairs
       graph_cigar_ms  device time of fbg_pindex_chains_graph_cigar
+    and, asked for with mapq=True (None otherwise; include/fbg_hip.h, fbg_pindex_chains_mapq):
+      second_score    uint32 per read: the score of its best chain on the anchors outside the columns of its chain, widened by
+                      the margin; 0 without one, and for an empty chain
+      second_lo, second_hi   uint32 per read: the MSA columns [second_lo, second_hi) of that second chain, 0xffffffff without one
+      mapq            uint8 per read: 60 * (score - min(second_score, score)) // read length, 0 for an empty chain
+      second_off, second_place, second_seed   the second chains, as chain_off, anchor_place and anchor_seed; second(k) gives
+                      read k's
+      mapq_stranded   after seeds(strands=True): uint8 per virtual read, mapq with the other strand's score as a competitor
+      best_mapq       after seeds(strands=True): uint8 per given read, mapq_stranded of the strand that strand picked, 0
+                      where strand is 0xff
+      mapq_ms         device time of fbg_pindex_chains_mapq
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -978,6 +1028,8 @@ class Chains:
         self.graph_edits = self.graph_start = self.graph_end = self.graph_path_off = self.graph_path_nodes = None
         self.best_graph_edits = self.graph_ms = None
         self.graph_cigar_off = self.graph_cigar_ops = self.graph_cigar_ms = None
+        self.second_score = self.second_lo = self.second_hi = self.mapq = self.second_off = None
+        self.second_place = self.second_seed = self.mapq_stranded = self.best_mapq = self.mapq_ms = None
 
     def cigar_runs(self, k):
         """int64[runs, 2]: (code, length) of the runs of read k's alignment path; no rows without an alignment."""
@@ -1018,6 +1070,13 @@ class Chains:
         """int64[rows, 2]: (anchor_place, anchor_seed) of the chain of read k."""
         a, b = int(self.chain_off[k]), int(self.chain_off[k + 1])
         return np.stack((self.anchor_place[a:b], self.anchor_seed[a:b]), axis=1).astype(np.int64)
+
+    def second(self, k):
+        """int64[rows, 2]: (anchor_place, anchor_seed) of the second-best chain of read k, as of()."""
+        if self.second_off is None:
+            raise ValueError("no second chains: ask for them with mapq=True")
+        a, b = int(self.second_off[k]), int(self.second_off[k + 1])
+        return np.stack((self.second_place[a:b], self.second_seed[a:b]), axis=1).astype(np.int64)
 
     def best(self, k):
         """int64[rows, 2]: the chain of given read k on its chosen strand, as of(); empty where strand[k] is 0xff."""

@@ -4,7 +4,7 @@
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
 //              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--by-row] [--align[=PAD]] [--cigar]
-//              [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE]
+//              [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE] [--mapq[=MARGIN]]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -73,6 +73,16 @@
 // the path's label lengths, start_offset, that sum - |label(end_node)| + end_offset, the number of = symbols, the number of
 // alignment columns (= X I D), 255, NM:i:edits and cg:Z:runs.  For - the CIGAR is in path order, PAF's convention.  A FILE
 // that cannot be written fails before any search.
+// --mapq[=MARGIN] (with --chain) finds every pattern's second-best chain outside the MSA columns of its chain, widened by
+// MARGIN columns on either side (default 0), and a mapping quality from the two scores (fbg_pindex_chains_mapq): chains
+// through other alleles in the same columns are the same locus and do not compete.  After a chain's C / A lines, before G / H,
+//   Q <tab> mapq <tab> second <tab> second_lo <tab> second_hi    60 * (score - min(second, score)) / pattern length, floored;
+//                                                     the second chain's score and its columns [second_lo, second_hi)
+// with `*` for both columns where there is no second chain, and `Q <tab> 0 <tab> 0 <tab> * <tab> *` for an empty chain.  With
+// --strands the other strand's chain competes too (fbg_pindex_mapq_strands): the Q line carries that value, and the T line
+// gets a third field, the value of the chosen strand (0 for *).  With --gaf column 12 is the value of that pattern and
+// strand instead of 255.  A pattern that matches in one piece has no seed at a shorter copy elsewhere: its second is 0.
+// Without --mapq no byte of stdout or of the GAF file changes.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -92,6 +102,7 @@ static int usage(const char *msg)
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
               << "                  [--by-row] [--align[=PAD]] [--cigar] [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE]\n"
+              << "                  [--mapq[=MARGIN]]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -130,7 +141,13 @@ static int usage(const char *msg)
               << "  --graph-cigar      needs --graph-align: an H line with numbers ends with the alignment path of the pattern\n"
               << "                     against that stretch, runs of = X I D in pattern and path order; no other line changes\n"
               << "  --gaf=FILE         needs --graph-cigar: one GAF record per H line with numbers goes to FILE (read<k>, the\n"
-              << "                     path as >id>id with its coordinates, matches, alignment columns, 255, NM:i: and cg:Z:)\n";
+              << "                     path as >id>id with its coordinates, matches, alignment columns, 255, NM:i: and cg:Z:)\n"
+              << "  --mapq[=MARGIN]    needs --chain: after a chain's C / A lines a Q line: mapping quality 0 .. 60, the score of\n"
+              << "                     the best chain outside the chain's MSA columns widened by MARGIN (default 0), and that\n"
+              << "                     chain's columns (* without one); chains in the same columns are the same locus.  With\n"
+              << "                     --strands the other strand competes too and the T line ends with the chosen strand's\n"
+              << "                     value; with --gaf column 12 is the value instead of 255.  A pattern matched in one\n"
+              << "                     piece has no seed at a shorter copy elsewhere and gets second 0\n";
     return EXIT_FAILURE;
 }
 
@@ -214,7 +231,8 @@ static void print_runs(std::ostream &os, const std::vector<uint32_t> &ops, uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement, gaf_path;
-    bool graph_cigar = false, have_gaf = false;
+    bool graph_cigar = false, have_gaf = false, want_mapq = false;
+    uint64_t margin = 0;
     bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false, graph_align = false;
     uint64_t graph_pad = 16;
     uint64_t pad = 16;
@@ -297,6 +315,18 @@ int main(int argc, char **argv)
             graph_pad = m;
             continue;
         }
+        if (a == "--mapq") { want_mapq = true; continue; }
+        if (a.compare(0, 7, "--mapq=") == 0) {
+            const std::string v = a.substr(7);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
+                return usage(("--mapq takes a margin, not '" + v + "'").c_str());
+            want_mapq = true;
+            margin = m;
+            continue;
+        }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
         return usage(("unknown argument " + a).c_str());
     }
@@ -312,6 +342,7 @@ int main(int argc, char **argv)
     if (graph_align && !(chain && rows)) return usage("--graph-align needs --chain and --rows");
     if (graph_cigar && !graph_align) return usage("--graph-cigar needs --graph-align");
     if (have_gaf && !graph_cigar) return usage("--gaf needs --graph-cigar");
+    if (want_mapq && !chain) return usage("--mapq needs --chain");
     if (have_gaf && gaf_path.empty()) return usage("--gaf takes a file");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
@@ -420,6 +451,9 @@ int main(int argc, char **argv)
     std::vector<uint32_t> path_nodes;
     std::vector<uint64_t> gcigar_off(nv + 1, 0);            // --graph-cigar: the runs of every virtual read
     std::vector<uint32_t> gcigar_ops;
+    std::vector<uint64_t> second_off(nv + 1, 0);            // --mapq: the second chains' offsets, scores and spans, the qualities
+    std::vector<uint32_t> second[3];
+    std::vector<uint8_t> quality(nv + 1, 0);
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -457,6 +491,12 @@ int main(int argc, char **argv)
         }
         if (rc == FBG_OK && chain && strands)
             rc = fbg_pindex_chain_strands(ix, strand.data(), best_score.data(), nullptr, nullptr, nullptr, nullptr);
+        if (rc == FBG_OK && want_mapq) {
+            for (int k = 0; k < 3; k++) second[k].resize(nv + 1);
+            rc = fbg_pindex_chains_mapq(ix, margin, second_off.data(), second[0].data(), second[1].data(), second[2].data(),
+                                        quality.data(), nullptr);
+            if (rc == FBG_OK && strands) rc = fbg_pindex_mapq_strands(ix, quality.data(), nullptr);
+        }
         if (rc == FBG_OK && rows && occurrences) {
             for (int k = 0; k < 2; k++) place_rows[k].resize(start_off[ns] + 1);
             rc = fbg_pindex_seeds_rows(ix, place_rows[0].data(), place_rows[1].data(), nullptr);
@@ -534,6 +574,11 @@ int main(int argc, char **argv)
                 for (uint64_t i = chain_off[v]; i < chain_off[v + 1]; i++)
                     std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]
                               << '\t' << coords[3][anchor_place[i]] << '\n';
+                if (want_mapq) {
+                    std::cout << "Q\t" << (unsigned)quality[v] << '\t' << second[0][v];
+                    if (second_off[v + 1] == second_off[v]) std::cout << "\t*\t*\n";
+                    else std::cout << '\t' << second[1][v] << '\t' << second[2][v] << '\n';
+                }
                 if (align && aligned[1][v] == FBG_ALIGN_NONE) std::cout << "G\t*\n";
                 else if (align) {
                     std::cout << "G\t" << aligned[0][v] << '\t' << aligned[1][v] << '\t' << aligned[2][v] << '\t' << aligned[3][v];
@@ -569,7 +614,7 @@ int main(int argc, char **argv)
                         const uint32_t ve = on_graph[3][v];
                         gaf << '\t' << plen << '\t' << on_graph[2][v] << '\t'
                             << plen - (g.label_off[ve + 1] - g.label_off[ve]) + on_graph[4][v] << '\t' << match << '\t' << cols
-                            << "\t255\tNM:i:" << on_graph[0][v] << "\tcg:Z:";
+                            << '\t' << (want_mapq ? (unsigned)quality[v] : 255u) << "\tNM:i:" << on_graph[0][v] << "\tcg:Z:";
                         print_runs(gaf, gcigar_ops, gcigar_off[v], gcigar_off[v + 1]);
                         gaf << '\n';
                     }
@@ -590,8 +635,11 @@ int main(int argc, char **argv)
             if (strands) {
                 std::cout << "-\t" << nr << '\n';
                 block(np + k);
-                if (chain)
-                    std::cout << "T\t" << (strand[k] == FBG_STRAND_NONE ? '*' : strand[k] ? '-' : '+') << '\t' << best_score[k] << '\n';
+                if (chain) {
+                    std::cout << "T\t" << (strand[k] == FBG_STRAND_NONE ? '*' : strand[k] ? '-' : '+') << '\t' << best_score[k];
+                    if (want_mapq) std::cout << '\t' << (strand[k] == FBG_STRAND_NONE ? 0u : (unsigned)quality[strand[k] ? np + k : k]);
+                    std::cout << '\n';
+                }
             }
         }
         std::cout << "Pattern? " << found << " out of " << np << " patterns seeded" << std::endl;

@@ -380,8 +380,14 @@ static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     const uint64_t pbytes = comp ? 2 * total : total;
     // an index with the row table: fbg_pindex_seeds_rows / _chains_rows read the reads of the last seeds call, which a
     // locate or occurrences call is about to overwrite
-    if (mode == PX_SEEDS) { ix->rw.saved = false; ix->rw.read_bytes = pbytes; }
+    if (mode == PX_SEEDS) { ix->rw.saved = ix->pq.saved = false; ix->rw.read_bytes = pbytes; }
     else if (ix->has_rows && ix->sd.ready && ix->sd_reads && !ix->rw.saved) FBG_TRY(pr_save_reads(ix));
+    else if (!ix->has_rows && ix->has_map && ix->sd.ready && ix->sd_reads && !ix->pq.saved) {
+        // without the row table: fbg_pindex_chains_mapq still reads the lengths of the last seeds call's reads
+        FBG_TRY(px_reserve(ix, ix->pq.roff, (ix->sd_reads + 1) * 8));
+        FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->pq.roff.p, ix->poff.p, (ix->sd_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
+        ix->pq.saved = true;
+    }
     FBG_TRY(px_reserve(ix, ix->pats, ((pbytes + 7) & ~7ull) + 16));
     FBG_TRY(px_reserve(ix, ix->poff, (n + 1) * 8));
     for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(px_reserve(ix, *b, n * 4));
@@ -547,7 +553,7 @@ static int px_seeds(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     PoState &s = ix->sd;
     s.ready = false;
     ix->ch.ready = false;         // chains belong to the seeds they were made from
-    ix->al.valid = ix->cg.ready = ix->pb.ready = ix->gr.valid = false;
+    ix->al.valid = ix->cg.ready = ix->pb.ready = ix->gr.valid = ix->pq.ready = false;
     if (device_ms) *device_ms = 0;
     if (!seed_off || (n_patterns && !pat_off)) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing argument", who);
     if (min_length == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: min_length is 1 or more", who);

@@ -9,6 +9,7 @@
 //   pindex_align.hip      edit distance of a read to a row of its chain, and the alignment path
 //   pindex_graph.hip      edit distance of a read to a path of the graph around its chain, and that path
 //   pindex_gcigar.hip     the alignment path of a read against the stretch of the graph that path spells
+//   pindex_mapq.hip       the second-best chain of a read outside the columns of its best one, and a mapping quality
 // Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
 // needs its launch calls a launcher declared at the end of this header.
 #pragma once
@@ -46,6 +47,9 @@
 #define PH_CTR 13             // counters of fbg_pindex_chains_align_graph: traces that failed, reads aligned, not selected, too long,
                               // too wide, cells, nodes, merges, and the reads of 1 .. 4 words and of more
 #define PH_NONE 0xffffffffu   // no predecessor chosen
+#define PQ_CTR 5              // counters of fbg_pindex_chains_mapq: anchors kept, anchors excluded, reads with a secondary chain,
+                              // reads of mapping quality 0 and of 60
+#define PQ_NOSPAN 0xffffffffffffffffull   // lo of a read without a primary chain
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
@@ -61,12 +65,12 @@ struct PoState {
 // from sd.msa) and its predecessor; per read the binning keys and ids (before and after the sort), the chain's end
 // place, score and length, the scan of the lengths; the chains (places, then seeds); the spill tier's slab (a uint4 per
 // start place, reserved when a read needs it); the counters of k_pc_key and k_pc_chain.  fbg_pindex_chain_strands: per
-// given read its strand and best score, and the three counters of k_pc_strand.
+// given read its strand and best score, and the three counters of k_pc_strand.  band: that of the last pc_reserve.
 struct PcState {
     DevBuf col, pred, key, id, key2, id2, end, score, len, off, out, slab, ctr;
     DevBuf strand, best, sctr;
     bool ready = false;
-    uint64_t n = 0, total = 0, anchors = 0, tier[3] = {0, 0, 0};
+    uint64_t n = 0, total = 0, anchors = 0, tier[3] = {0, 0, 0}, band = 0;
 };
 
 // The row table of fbg_pindex_build_segmentation_rows: node_of[nb * m], block-major, and the gathered labels with their
@@ -138,6 +142,21 @@ struct PjState {
     PgState g;
 };
 
+// fbg_pindex_chains_mapq.  ch: a chain state of this call's own, in which the chain kernels leave the secondary chains
+// (ch.col: the witness rows and columns, expanded again); span: per read lo and hi of its primary chain as u64 (2 n,
+// PQ_NOSPAN in lo for an empty chain); mcol: per start place its witness column, or PC_NONE where the anchor is excluded;
+// span2: second_lo, then second_hi (2 n); mapq / smapq: the mapping quality per read, and the stranded one; ctr: PQ_CTR
+// counters.  roff: the read offsets of the last seeds call, moved aside (saved) on an index without the row table when a
+// locate or occurrences call is about to overwrite poff.  ready: a call has succeeded since the last chaining call, for n
+// reads and total secondary anchors, and (on_device) left its arrays on the device; not where it launched nothing.
+struct PqState {
+    PcState ch;
+    DevBuf span, mcol, span2, mapq, smapq, ctr, roff;
+    bool ready = false, on_device = false, saved = false;
+    uint64_t n = 0, total = 0;
+    uint64_t stat[5] = {0, 0, 0, 0, 0};      // reads_with_second, anchors_kept, anchors_excluded, mapq0, mapq60
+};
+
 struct fbg_pindex {
     fbg_ctx *ctx = nullptr;
     uint64_t N1 = 0;          // text length including the sentinel
@@ -184,6 +203,7 @@ struct fbg_pindex {
     PbState pb;
     PhState gr;
     PjState gj;
+    PqState pq;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, sv0 = nullptr, sv1 = nullptr;   // made with the index (px_new)
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -364,9 +384,11 @@ PX_LOCAL void po_expand_msa(fbg_pindex *ix, const PoState &s, bool starts, uint3
 // k_pc_key, the sort, the host's look at the bins (bin[0 .. 4)), k_pc_chain per tier, k_pc_trace, the scan, k_pc_trace;
 // and what ends either call after px_sync_elapsed: the limit on chain_off[n], the statistics (bin[4]: the anchors)
 PX_LOCAL int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *device_ms, const char *what, bool *go);
-PX_LOCAL int pc_reserve(fbg_pindex *ix, PcDev &d, const uint32_t *col, uint64_t band);
-PX_LOCAL int pc_launch(fbg_pindex *ix, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what);
-PX_LOCAL int pc_finish(fbg_pindex *ix, const uint64_t *chain_off, const uint64_t bin[5], const char *what);
+// pc_reserve, pc_launch and pc_finish work on the chain state c: ix->ch for the two chaining calls, the mapq state's own
+// for fbg_pindex_chains_mapq (pindex_mapq.hip)
+PX_LOCAL int pc_reserve(fbg_pindex *ix, PcState &c, PcDev &d, const uint32_t *col, uint64_t band);
+PX_LOCAL int pc_launch(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what);
+PX_LOCAL int pc_finish(fbg_pindex *ix, PcState &c, const uint64_t *chain_off, const uint64_t bin[5], const char *what);
 // pindex_rows.hip: the last seeds call's reads moved aside; k_pr_seed and k_pr_place (records ev0); k_pr_chain
 PX_LOCAL int pr_save_reads(fbg_pindex *ix);
 PX_LOCAL int pr_prepare(fbg_pindex *ix, PrDev &d);

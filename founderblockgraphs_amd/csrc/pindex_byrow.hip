@@ -197,7 +197,7 @@ extern "C" int fbg_pindex_chains_by_row(fbg_pindex *ix, uint64_t band, uint64_t 
     for (DevBuf *x : {&b.row, &b.score, &b.nbest, &b.key, &b.id, &b.key2, &b.id2}) FBG_TRY(px_reserve(ix, *x, n * 4));
     FBG_TRY(px_reserve(ix, b.ctr, PB_CTR * 8));
     PcDev pd;
-    FBG_TRY(pc_reserve(ix, pd, b.col2.as<uint32_t>(), band));
+    FBG_TRY(pc_reserve(ix, c, pd, b.col2.as<uint32_t>(), band));
     PrDev w;
     FBG_TRY(pr_prepare(ix, w));                       // records ev0
     FBG_HIP_TRY(ctx, hipMemsetAsync(b.ctr.p, 0, PB_CTR * 8, st));
@@ -250,7 +250,7 @@ extern "C" int fbg_pindex_chains_by_row(fbg_pindex *ix, uint64_t band, uint64_t 
     hipLaunchKernelGGL(k_pb_mask, dim3(fbg_blocks(A, PX_THREADS)), dim3(PX_THREADS), 0, st, d, w, n, A, b.col2.as<uint32_t>());
     FBG_HIP_TRY(ctx, hipGetLastError());
     uint64_t cbin[5] = {0, 0, 0, 0, 0};
-    FBG_TRY(pc_launch(ix, pd, min_score, cbin, what));
+    FBG_TRY(pc_launch(ix, c, pd, min_score, cbin, what));
     FBG_TRY(px_record_end(ix));
     std::vector<uint32_t> first(n), second(n);
     FBG_HIP_TRY(ctx, hipMemcpyAsync(chain_off, c.off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -267,7 +267,7 @@ extern "C" int fbg_pindex_chains_by_row(fbg_pindex *ix, uint64_t band, uint64_t 
             return fbg_fail(ctx, FBG_ERR_HIP, "%s: read %llu scores %u along its row and %u on the masked columns", what,
                             (unsigned long long)R, first[R], second[R]);
     if (score) std::copy(first.begin(), first.end(), score);
-    FBG_TRY(pc_finish(ix, chain_off, cbin, what));
+    FBG_TRY(pc_finish(ix, c, chain_off, cbin, what));
     b.stat[0] = bin[1];
     b.stat[1] = bin[2];
     b.stat[2] = bin[3];

@@ -156,7 +156,8 @@ __global__ void k_pc_strand(const uint32_t *score, const uint64_t *len, uint64_t
 // their number of start places, the host's look at the four bin sizes, one k_pc_chain launch per tier that has reads,
 // then count, scan and write as the seeds do.  A chain has at most one anchor per seed: S entries hold every chain.
 // fbg_pindex_chains_by_row (pindex_byrow.hip) runs the same steps on columns of its own, so they are four functions:
-// pc_begin, pc_reserve, pc_launch and pc_finish (pindex.h).
+// pc_begin, pc_reserve, pc_launch and pc_finish (pindex.h).  The last three take the chain state they work on:
+// fbg_pindex_chains_mapq (pindex_mapq.hip) runs them on a state of its own and leaves ix->ch alone.
 
 // The checks and trivial cases of a chaining call (what: its name).  *go: there is something to launch.
 int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *device_ms, const char *what, bool *go)
@@ -169,6 +170,7 @@ int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *devic
     ix->pb.ready = false;
     ix->al.valid = ix->cg.ready = false;      // the alignment and its paths belong to the chains
     ix->gr.valid = false;                     // and so does the alignment to the graph
+    ix->pq.ready = false;                     // and the second-best chains and the mapping quality
     if (device_ms) *device_ms = 0;
     if (!chain_off) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing chain_off", what);
     if (!ix->from_segmentation || !ix->has_map)
@@ -185,9 +187,8 @@ int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *devic
     return FBG_OK;
 }
 
-int pc_reserve(fbg_pindex *ix, PcDev &d, const uint32_t *col, uint64_t band)
+int pc_reserve(fbg_pindex *ix, PcState &c, PcDev &d, const uint32_t *col, uint64_t band)
 {
-    PcState &c = ix->ch;
     const PoState &s = ix->sd;
     const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
     FBG_TRY(px_reserve(ix, c.col, 2 * A * 4));
@@ -206,15 +207,14 @@ int pc_reserve(fbg_pindex *ix, PcDev &d, const uint32_t *col, uint64_t band)
     d.score = c.score.as<uint32_t>();
     d.slab = nullptr;
     d.ctr = c.ctr.as<unsigned long long>();
-    d.band = band;
+    d.band = c.band = band;
     return FBG_OK;
 }
 
-int pc_launch(fbg_pindex *ix, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what)
+int pc_launch(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what)
 {
     fbg_ctx *ctx = ix->ctx;
     hipStream_t st = ctx->stream;
-    PcState &c = ix->ch;
     const uint64_t n = ix->sd_reads, S = ix->sd.n, A = ix->sd.stotal;
     uint32_t *ka = c.key.as<uint32_t>(), *va = c.id.as<uint32_t>(), *kb = c.key2.as<uint32_t>(), *vb = c.id2.as<uint32_t>();
     hipLaunchKernelGGL(k_pc_key, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, d, n, ka, va);
@@ -246,9 +246,8 @@ int pc_launch(fbg_pindex *ix, PcDev &d, uint64_t min_score, uint64_t bin[5], con
     return FBG_OK;
 }
 
-int pc_finish(fbg_pindex *ix, const uint64_t *chain_off, const uint64_t bin[5], const char *what)
+int pc_finish(fbg_pindex *ix, PcState &c, const uint64_t *chain_off, const uint64_t bin[5], const char *what)
 {
-    PcState &c = ix->ch;
     const uint64_t n = c.n;
     // a chain takes one place per seed at most, and a call has fewer than 2^32 seeds
     if (chain_off[n] >= (1ull << 32))
@@ -276,18 +275,18 @@ extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_sco
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     PcDev d;
-    FBG_TRY(pc_reserve(ix, d, nullptr, band));
+    FBG_TRY(pc_reserve(ix, c, d, nullptr, band));
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(c.ctr.p, 0, 5 * 8, st));
     po_expand_msa(ix, s, true, c.col.as<uint32_t>(), c.col.as<uint32_t>() + A);
     uint64_t bin[5] = {0, 0, 0, 0, 0};
-    FBG_TRY(pc_launch(ix, d, min_score, bin, "fbg_pindex_chains"));
+    FBG_TRY(pc_launch(ix, c, d, min_score, bin, "fbg_pindex_chains"));
     FBG_TRY(px_record_end(ix));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(chain_off, c.off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
     if (score) FBG_HIP_TRY(ctx, hipMemcpyAsync(score, c.score.p, n * 4, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&bin[4], d.ctr + 4, 8, hipMemcpyDeviceToHost, st));
     FBG_TRY(px_sync_elapsed(ix, device_ms));
-    return pc_finish(ix, chain_off, bin, "fbg_pindex_chains");
+    return pc_finish(ix, c, chain_off, bin, "fbg_pindex_chains");
 }
 
 extern "C" int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, uint32_t *anchor_seed, double *device_ms)

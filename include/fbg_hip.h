@@ -881,6 +881,71 @@ int fbg_pindex_chains_by_row(fbg_pindex *ix, uint64_t band, uint64_t min_score, 
 int fbg_pindex_chains_by_row_stats(const fbg_pindex *ix, uint64_t *reads_lds, uint64_t *reads_device, uint64_t *reads_too_many,
                                    uint64_t *reads_no_row, uint64_t *anchors_kept, uint64_t *lds_max, uint64_t *max_places);
 
+/* The second-best chain of every read, and a mapping quality (an index built by fbg_pindex_build_segmentation only; after
+ * a successful fbg_pindex_chains or fbg_pindex_chains_by_row since the last seeds call).
+ *
+ * A chaining call keeps the best chain of a read only, so a read that fits two loci of the MSA equally well looks as
+ * certain as a unique one.  In a pangenome the alternative alleles of one locus lie in the same MSA columns: a chain
+ * through another allele there is the same mapping and must not count against it.  Only a chain elsewhere in the
+ * columns competes.  With the vocabulary of fbg_pindex_chains (anchors g, seed t, q, k, witness column
+ * c = start_col[g] of fbg_pindex_seeds_msa, `precedes`, band, ties to the smallest g), for a (virtual) read R of the last
+ * seeds call (2n of them after fbg_pindex_seeds_strands):
+ *   the primary chain   what the last successful chaining call left, plain or by row: s1 = score[R] and the anchors
+ *                       a_1 .. a_len in read order (none where the chain is empty, also where score[R] < min_score);
+ *   span                lo = c(a_1), hi = c(a_len) + k(a_len), exclusive, in witness columns;
+ *   kept anchors        an anchor g of R is excluded iff [c, c + k) meets [lo - margin, hi + margin), that is iff
+ *                       c + k + margin > lo and c < hi + margin, evaluated so that nothing wraps (the sums saturate at
+ *                       2^64 - 1); otherwise it is kept.  margin = UINT64_MAX excludes every anchor;
+ *   the secondary chain the chain that fbg_pindex_chains defines on the kept anchors of R: the same `precedes`, the band of
+ *                       the primary call, the same ties for predecessor and end, no min_score.  It always runs on the
+ *                       unmasked witness columns, also after fbg_pindex_chains_by_row: a competing locus on any row
+ *                       counts.  second[R] is its score, second_lo[R] and second_hi[R] its span (0xffffffff where it is
+ *                       empty); its anchors are reported whenever second[R] > 0.  A read with an empty primary chain has
+ *                       no secondary: second[R] = 0;
+ *   mapq[R]             with L = |P_R| and s2 = min(second[R], s1): (60 * (s1 - s2)) / L, floored, in 64-bit; 0 where the
+ *                       primary chain is empty or L == 0.  Scores are at most L, so the value lies in 0 .. 60;
+ *   mapq_stranded[v]    after fbg_pindex_seeds_strands, with w = v +- n the twin of virtual read v: the same formula with
+ *                       s2 = min(max(second[v], score[w]), s1).  The other strand's best chain is a competing mapping
+ *                       wherever it lies, and its score is used also when it is below min_score: equal scores on both
+ *                       strands give 0 on both.
+ * It follows that after fbg_pindex_chains second[R] <= score[R]; after fbg_pindex_chains_by_row second[R] may exceed
+ * score[R] (the secondary is not bound to a row) and mapq[R] is then 0; no anchor of a secondary chain meets
+ * [lo - margin, hi + margin), though its span may reach over it, with anchors on either side.  The constants 60 and the linear shape are a convention in the range other mappers use: no
+ * truth set exists to tune them against, and the value is no calibrated probability.
+ * Limits.  Seeds are greedy maximal exact matches: a read that matches one locus in a single piece has no seed at a
+ * shorter copy elsewhere and gets second = 0; competitors become visible once an edit or a block boundary splits the
+ * read.  No gap costs, as in the chains.  Columns are witness columns, one row per place.
+ *
+ *   fbg_pindex_chains_mapq        the count step.  second_off: n + 1 CSR offsets of the secondary chains; second, second_lo,
+ *       second_hi (n uint32_t each) and mapq (n uint8_t) may be NULL.  On the device: the witness columns are expanded into
+ *       a buffer of this call's own, one lane per read takes lo and hi from the first and last entry of its primary chain,
+ *       one lane per start place finds its read by two searches of the offsets and writes its column or "none", and the
+ *       kernels of fbg_pindex_chains (sort, three tiers, trace) run on these columns in a chain state of this call's own;
+ *       one lane per read then computes the secondary span and mapq.  *device_ms (may be NULL): device time of all of it,
+ *       the host's look at the tier sizes included, without the copies out.
+ *   fbg_pindex_chains_mapq_fetch  anchor_place and anchor_seed of the secondary chains, second_off[n] entries each, as
+ *       fbg_pindex_chains_fetch; either may be NULL; may be called again.
+ *   fbg_pindex_mapq_strands       mapq_stranded: 2n entries, one per virtual read (may be NULL).  It needs a successful
+ *       fbg_pindex_seeds_strands as the last seeds call and a successful fbg_pindex_chains_mapq since the last chaining call.
+ *   fbg_pindex_mapq_stats         any pointer may be NULL.  Of the last successful fbg_pindex_chains_mapq since the last
+ *       chaining call (0 without one), over the reads with a non-empty primary chain: those with second > 0, their anchors
+ *       kept and excluded, and the reads with mapq 0 and with mapq 60.
+ * The call may be repeated with another margin; the later result replaces the earlier.  It leaves the seeds, their places
+ * and columns, the primary chains and their fetch, strands, rows, both alignments, both CIGARs, the graph paths and
+ * every statistic of those calls as they were.  A later seeds call, fbg_pindex_chains or fbg_pindex_chains_by_row
+ * invalidates the result.  The lengths of the reads stay known after a later fbg_pindex_locate or fbg_pindex_occurrences.
+ * Errors, all FBG_ERR_INVALID: a NULL index or second_off; an index not built from a segmentation; no successful
+ * chaining call since the last seeds call; a fetch or strands call without a successful fbg_pindex_chains_mapq since the
+ * last chaining call; fbg_pindex_mapq_strands after seeds that were not stranded.  n == 0, and seeds without places: every
+ * output 0 (the spans 0xffffffff), FBG_OK, nothing launched.  Scratch owned by the index: what fbg_pindex_chains takes,
+ * once more, and 4 bytes per start place and 25 per read. */
+int fbg_pindex_chains_mapq(fbg_pindex *ix, uint64_t margin, uint64_t *second_off, uint32_t *second, uint32_t *second_lo,
+                           uint32_t *second_hi, uint8_t *mapq, double *device_ms);
+int fbg_pindex_chains_mapq_fetch(fbg_pindex *ix, uint32_t *anchor_place, uint32_t *anchor_seed, double *device_ms);
+int fbg_pindex_mapq_strands(fbg_pindex *ix, uint8_t *mapq_stranded, double *device_ms);
+int fbg_pindex_mapq_stats(const fbg_pindex *ix, uint64_t *reads_with_second, uint64_t *anchors_kept, uint64_t *anchors_excluded,
+                          uint64_t *mapq0, uint64_t *mapq60);
+
 /* The edit distance of each read to a row that carries its chain (an index built by
  * fbg_pindex_build_segmentation_rows only; after a successful seeds call, plain or stranded, and a successful
  * fbg_pindex_chains since it).
