@@ -17,6 +17,10 @@
 // the longest probe sequence of an insertion.
 //     fbg_host_selftest twin-slots KEYS.bin BITS
 // prints the first slot of every key, one per line.
+//     fbg_host_selftest pindex-stages
+// prints the table of pindex_stage.h as it acts: "stages NAME ...", then per stage X "begin X" and the stages still done when
+// every stage was done and X begins, then per subset of done stages (bit i of MASK: stage i, marked by ps_finish) "need MASK"
+// and per stage "-" where ps_missing finds it and its ancestors done, else the stage it names.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -25,6 +29,7 @@
 #include "xgfa.hpp"
 #include "../tie_extent.h"
 #include "../twin_hash.h"
+#include "../pindex_stage.h"
 
 static int tie_extent_selftest()
 {
@@ -70,6 +75,34 @@ static int tie_extent_selftest()
     return 0;
 }
 
+static int pindex_stages_selftest()
+{
+    std::printf("stages");
+    for (int s = 0; s < PS_COUNT; s++) std::printf(" %s", ps_table[s].name);
+    std::printf("\n");
+    for (int x = 0; x < PS_COUNT; x++) {
+        bool done[PS_COUNT] = {};
+        for (int s = 0; s < PS_COUNT; s++) ps_finish(done, (PsStage)s);
+        ps_begin(done, (PsStage)x);
+        std::printf("begin %s", ps_table[x].name);
+        for (int s = 0; s < PS_COUNT; s++)
+            if (done[s]) std::printf(" %s", ps_table[s].name);
+        std::printf("\n");
+    }
+    for (unsigned mask = 0; mask < 1u << PS_COUNT; mask++) {
+        bool done[PS_COUNT] = {};
+        for (int s = 0; s < PS_COUNT; s++)
+            if (mask >> s & 1) ps_finish(done, (PsStage)s);
+        std::printf("need %u", mask);
+        for (int y = 0; y < PS_COUNT; y++) {
+            const int miss = ps_missing(done, (PsStage)y);
+            std::printf(" %s", miss == PS_COUNT ? "-" : ps_table[miss].name);
+        }
+        std::printf("\n");
+    }
+    return 0;
+}
+
 static int twin_hash_selftest(const char *path, int bits, bool slots_only)
 {
     FILE *fh = std::fopen(path, "rb");
@@ -106,6 +139,7 @@ int main(int argc, char **argv)
     if (argc == 4 && (std::string(argv[1]) == "twin-hash" || std::string(argv[1]) == "twin-slots"))
         return twin_hash_selftest(argv[2], std::atoi(argv[3]), std::string(argv[1]) == "twin-slots");
     if (argc == 2 && std::string(argv[1]) == "tie-extent") return tie_extent_selftest();
+    if (argc == 2 && std::string(argv[1]) == "pindex-stages") return pindex_stages_selftest();
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s FASTA GAP_LIMIT ELASTIC PATHS OUT.gfa [BOUNDARY ...]\n", argv[0]);
         return 2;

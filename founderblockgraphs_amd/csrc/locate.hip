@@ -357,13 +357,15 @@ static int po_reserve(fbg_pindex *ix, PoState &s, uint64_t n)
 
 // The front of fbg_pindex_locate, fbg_pindex_occurrences and fbg_pindex_seeds: checks, every allocation of the call
 // that depends on n only (after hipSetDevice), patterns onto the device, ev0, and the pattern ids sorted by length into
-// oval2.  n > 0.  comp (PX_SEEDS only; NULL: the reads as given): the complement table of fbg_pindex_seeds_strands.
-// Everything is then reserved for 2n reads and twice the bytes, k_px_revcomp appends the reverse virtual reads after
-// ev0, and the sort runs over the 2n.
+// oval2.  n > 0.  The patterns go to the buffers of the mode: the reads of a seeds call to the read batch, which the later
+// stages read, the patterns of the other two to pats / poff; so neither search disturbs the other's.  comp (PX_SEEDS only;
+// NULL: the reads as given): the complement table of fbg_pindex_seeds_strands.  Everything is then reserved for 2n reads
+// and twice the bytes, k_px_revcomp appends the reverse virtual reads after ev0, and the sort runs over the 2n.
 static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, const uint64_t *pat_off, uint64_t n_patterns, PxMode mode,
                     const uint8_t *comp = nullptr)
 {
     fbg_ctx *ctx = ix->ctx;
+    DevBuf &pats = mode == PX_SEEDS ? ix->batch.reads : ix->pats, &offs = mode == PX_SEEDS ? ix->batch.roff : ix->poff;
     for (uint64_t k = 0; k < n_patterns; k++)
         if (pat_off[k + 1] < pat_off[k]) return fbg_fail(ctx, FBG_ERR_INVALID, "pattern offsets decrease at pattern %llu", (unsigned long long)k);
     if (mode == PX_SEEDS)
@@ -378,18 +380,9 @@ static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     hipStream_t st = ctx->stream;
     const uint64_t n = comp ? 2 * n_patterns : n_patterns;     // reads on the device
     const uint64_t pbytes = comp ? 2 * total : total;
-    // an index with the row table: fbg_pindex_seeds_rows / _chains_rows read the reads of the last seeds call, which a
-    // locate or occurrences call is about to overwrite
-    if (mode == PX_SEEDS) { ix->rw.saved = ix->pq.saved = false; ix->rw.read_bytes = pbytes; }
-    else if (ix->has_rows && ix->sd.ready && ix->sd_reads && !ix->rw.saved) FBG_TRY(pr_save_reads(ix));
-    else if (!ix->has_rows && ix->has_map && ix->sd.ready && ix->sd_reads && !ix->pq.saved) {
-        // without the row table: fbg_pindex_chains_mapq still reads the lengths of the last seeds call's reads
-        FBG_TRY(px_reserve(ix, ix->pq.roff, (ix->sd_reads + 1) * 8));
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->pq.roff.p, ix->poff.p, (ix->sd_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
-        ix->pq.saved = true;
-    }
-    FBG_TRY(px_reserve(ix, ix->pats, ((pbytes + 7) & ~7ull) + 16));
-    FBG_TRY(px_reserve(ix, ix->poff, (n + 1) * 8));
+    if (mode == PX_SEEDS) ix->batch.bytes = pbytes;
+    FBG_TRY(px_reserve(ix, pats, ((pbytes + 7) & ~7ull) + 16));     // the kernels read whole words past the last pattern
+    FBG_TRY(px_reserve(ix, offs, (n + 1) * 8));
     for (DevBuf *b : {&ix->okey, &ix->oval, &ix->okey2, &ix->oval2}) FBG_TRY(px_reserve(ix, *b, n * 4));
     if (mode == PX_SEEDS) {
         for (DevBuf *b : {&ix->snum, &ix->soff}) FBG_TRY(px_reserve(ix, *b, (n + 1) * 8));
@@ -401,18 +394,18 @@ static int px_front(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
         FBG_TRY(px_reserve(ix, ix->orec, n * 24));
         FBG_TRY(po_reserve(ix, ix->occ, n));
     }
-    if (comp) FBG_TRY(px_reserve(ix, ix->comp, 256));
-    if (total) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->pats.p, patterns + base, total, hipMemcpyHostToDevice, st));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->poff.p, pat_off, (n_patterns + 1) * 8, hipMemcpyHostToDevice, st));
-    if (comp) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->comp.p, comp, 256, hipMemcpyHostToDevice, st));
+    if (comp) FBG_TRY(px_reserve(ix, ix->batch.comp, 256));
+    if (total) FBG_HIP_TRY(ctx, hipMemcpyAsync(pats.p, patterns + base, total, hipMemcpyHostToDevice, st));
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(offs.p, pat_off, (n_patterns + 1) * 8, hipMemcpyHostToDevice, st));
+    if (comp) FBG_HIP_TRY(ctx, hipMemcpyAsync(ix->batch.comp.p, comp, 256, hipMemcpyHostToDevice, st));
     if (mode != PX_SEEDS) FBG_HIP_TRY(ctx, hipMemsetAsync(ix->lines_ctr.p, 0, 8, st));
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
-    uint64_t *poff = ix->poff.as<uint64_t>();
+    uint64_t *poff = offs.as<uint64_t>();
     if (base) px_rebase(st, poff, n_patterns, base);
     if (comp) {
         const uint64_t words = (2 * total + 7) / 8 - total / 8;
         hipLaunchKernelGGL(k_px_revcomp, dim3(fbg_blocks(std::max(words, n_patterns), PX_THREADS)), dim3(PX_THREADS), 0, st,
-                           ix->comp.as<uint8_t>(), ix->pats.as<uint8_t>(), poff, n_patterns, total);
+                           ix->batch.comp.as<uint8_t>(), pats.as<uint8_t>(), poff, n_patterns, total);
     }
     // lanes of a wave take patterns of similar length: pattern ids sorted by length
     uint32_t *ka = ix->okey.as<uint32_t>(), *va = ix->oval.as<uint32_t>(), *kb = ix->okey2.as<uint32_t>(), *vb = ix->oval2.as<uint32_t>();
@@ -483,11 +476,11 @@ void po_expand_msa(fbg_pindex *ix, const PoState &s, bool starts, uint32_t *orow
     else po_expand_msa_launch<false>(ix, s, orow, ocol);
 }
 
-// The places of a place state into the caller's arrays: source, destination and offset of every place (end / start: three
-// arrays each; fbg_pindex_occurrences_fetch, fbg_pindex_seeds_places) or, msa, its MSA row and column (two arrays each;
-// fbg_pindex_occurrences_msa, fbg_pindex_seeds_msa) through k_po_expand_msa and a buffer of its own, so that neither
-// s.place nor a later fetch sees it.
-static int po_fetch(fbg_pindex *ix, const char *who, const char *search, PoState &s, bool msa, uint32_t *const (&end)[3],
+// The places of a place state (that of stage: PS_OCC or PS_SEEDS) into the caller's arrays: source, destination and
+// offset of every place (end / start: three arrays each; fbg_pindex_occurrences_fetch, fbg_pindex_seeds_places) or, msa,
+// its MSA row and column (two arrays each; fbg_pindex_occurrences_msa, fbg_pindex_seeds_msa) through k_po_expand_msa and
+// a buffer of its own, so that neither s.place nor a later fetch sees it.
+static int po_fetch(fbg_pindex *ix, const char *who, PsStage stage, PoState &s, bool msa, uint32_t *const (&end)[3],
                     uint32_t *const (&start)[3], double *device_ms)
 {
     fbg_ctx *ctx = ix->ctx;
@@ -495,7 +488,7 @@ static int po_fetch(fbg_pindex *ix, const char *who, const char *search, PoState
     if (device_ms) *device_ms = 0;
     if (msa && (!ix->from_segmentation || !ix->has_map))
         return fbg_fail(ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation knows MSA coordinates", who);
-    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no %s result to %s", who, search, msa ? "expand" : "fetch");
+    FBG_TRY(px_need(ix, who, stage));
     const int e_given = std::count_if(end, end + K, [](uint32_t *q) { return q != nullptr; });
     const int s_given = std::count_if(start, start + K, [](uint32_t *q) { return q != nullptr; });
     if ((e_given && e_given != K) || (s_given && s_given != K))
@@ -538,7 +531,7 @@ static int po_fetch(fbg_pindex *ix, const char *who, const char *search, PoState
 template <bool COMPACT, bool WRITE> static void px_seeds_launch(fbg_pindex *ix, const PxDev &d, uint64_t n, uint32_t min_len)
 {
     hipLaunchKernelGGL((k_px_seeds<COMPACT, WRITE>), dim3(fbg_blocks(n, PX_THREADS)), dim3(PX_THREADS), 0, ix->ctx->stream, d,
-                       ix->code.as<uint16_t>(), ix->C.as<uint32_t>(), ix->pats.as<uint8_t>(), ix->poff.as<uint64_t>(),
+                       ix->code.as<uint16_t>(), ix->C.as<uint32_t>(), ps_reads(ix), ps_roff(ix),
                        ix->oval2.as<uint32_t>(), n, min_len, (WRITE ? ix->soff : ix->snum).as<uint64_t>(),
                        ix->scnt.as<unsigned long long>(), ix->spos.as<unsigned long long>(), ix->srec.as<uint2>(),
                        ix->sq.as<uint32_t>(), ix->slen.as<uint32_t>());
@@ -551,9 +544,7 @@ static int px_seeds(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
 {
     fbg_ctx *ctx = ix->ctx;
     PoState &s = ix->sd;
-    s.ready = false;
-    ix->ch.ready = false;         // chains belong to the seeds they were made from
-    ix->al.valid = ix->cg.ready = ix->pb.ready = ix->gr.valid = ix->pq.ready = false;
+    px_begin(ix, PS_SEEDS);       // the chains, and all that is made from them, belong to the seeds they were made from
     if (device_ms) *device_ms = 0;
     if (!seed_off || (n_patterns && !pat_off)) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing argument", who);
     if (min_length == 0) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: min_length is 1 or more", who);
@@ -564,9 +555,9 @@ static int px_seeds(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     s.n = 0;
     s.etotal = s.stotal = 0;
     const uint64_t n = comp ? 2 * n_patterns : n_patterns;
-    ix->sd_reads = n;
-    ix->sd_stranded = comp != nullptr;
-    if (n == 0) { s.ready = true; return FBG_OK; }
+    ix->batch.n = n;
+    ix->batch.stranded = comp != nullptr;
+    if (n == 0) { px_finish(ix, PS_SEEDS); return FBG_OK; }
     FBG_TRY(px_front(ix, who, patterns, pat_off, n_patterns, PX_SEEDS, comp));
     hipStream_t st = ctx->stream;
     const bool none = min_length >= (1ull << 32);   // no pattern has 2^32 symbols: nothing can be reported
@@ -611,7 +602,7 @@ static int px_seeds(fbg_pindex *ix, const char *who, const uint8_t *patterns, co
     s.n = S;
     s.etotal = tot[0];
     s.stotal = tot[1];
-    s.ready = true;
+    px_finish(ix, PS_SEEDS);
     return FBG_OK;
 }
 
@@ -644,7 +635,7 @@ extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, c
     if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
     PoState &s = ix->occ;
-    s.ready = false;
+    px_begin(ix, PS_OCC);
     if (device_ms) *device_ms = 0;
     if (!end_off || !start_off || (n_patterns && (!pat_off || !count || !pos || !restarts || !end_total || !start_total)))
         return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_occurrences: missing argument");
@@ -652,7 +643,7 @@ extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, c
     end_off[0] = start_off[0] = 0;
     s.n = n_patterns;
     s.etotal = s.stotal = 0;
-    if (n_patterns == 0) { s.ready = true; return FBG_OK; }
+    if (n_patterns == 0) { px_finish(ix, PS_OCC); return FBG_OK; }
     const uint64_t n = n_patterns;
     FBG_TRY(px_search(ix, "fbg_pindex_occurrences", patterns, pat_off, n, true));
     hipStream_t st = ctx->stream;
@@ -671,7 +662,7 @@ extern "C" int fbg_pindex_occurrences(fbg_pindex *ix, const uint8_t *patterns, c
                         "entries (lower max_per_pattern or split the batch)", (unsigned long long)end_off[n], (unsigned long long)start_off[n]);
     s.etotal = end_off[n];
     s.stotal = start_off[n];
-    s.ready = true;
+    px_finish(ix, PS_OCC);
     return FBG_OK;
 }
 
@@ -679,7 +670,7 @@ extern "C" int fbg_pindex_occurrences_fetch(fbg_pindex *ix, uint32_t *end_src, u
                                             uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms)
 {
     if (!ix) return FBG_ERR_INVALID;
-    return po_fetch(ix, "fbg_pindex_occurrences_fetch", "fbg_pindex_occurrences", ix->occ, false, {end_src, end_dst, end_offset},
+    return po_fetch(ix, "fbg_pindex_occurrences_fetch", PS_OCC, ix->occ, false, {end_src, end_dst, end_offset},
                     {start_src, start_dst, start_offset}, device_ms);
 }
 
@@ -687,7 +678,7 @@ extern "C" int fbg_pindex_occurrences_msa(fbg_pindex *ix, uint32_t *end_row, uin
                                           uint32_t *start_col, double *device_ms)
 {
     if (!ix) return FBG_ERR_INVALID;
-    return po_fetch(ix, "fbg_pindex_occurrences_msa", "fbg_pindex_occurrences", ix->occ, true, {end_row, end_col, nullptr},
+    return po_fetch(ix, "fbg_pindex_occurrences_msa", PS_OCC, ix->occ, true, {end_row, end_col, nullptr},
                     {start_row, start_col, nullptr}, device_ms);
 }
 
@@ -722,7 +713,7 @@ extern "C" int fbg_pindex_seeds_fetch(fbg_pindex *ix, uint32_t *q_start, uint32_
     fbg_ctx *ctx = ix->ctx;
     PoState &s = ix->sd;
     if (device_ms) *device_ms = 0;
-    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds_fetch: no fbg_pindex_seeds result to fetch");
+    FBG_TRY(px_need(ix, "fbg_pindex_seeds_fetch", PS_SEEDS));
     const uint64_t S = s.n;
     if (S == 0) {
         if (end_off) end_off[0] = 0;
@@ -752,7 +743,7 @@ extern "C" int fbg_pindex_seeds_places(fbg_pindex *ix, uint32_t *end_src, uint32
                                        uint32_t *start_src, uint32_t *start_dst, uint32_t *start_offset, double *device_ms)
 {
     if (!ix) return FBG_ERR_INVALID;
-    return po_fetch(ix, "fbg_pindex_seeds_places", "fbg_pindex_seeds", ix->sd, false, {end_src, end_dst, end_offset},
+    return po_fetch(ix, "fbg_pindex_seeds_places", PS_SEEDS, ix->sd, false, {end_src, end_dst, end_offset},
                     {start_src, start_dst, start_offset}, device_ms);
 }
 
@@ -760,6 +751,6 @@ extern "C" int fbg_pindex_seeds_msa(fbg_pindex *ix, uint32_t *end_row, uint32_t 
                                     double *device_ms)
 {
     if (!ix) return FBG_ERR_INVALID;
-    return po_fetch(ix, "fbg_pindex_seeds_msa", "fbg_pindex_seeds", ix->sd, true, {end_row, end_col, nullptr}, {start_row, start_col, nullptr},
+    return po_fetch(ix, "fbg_pindex_seeds_msa", PS_SEEDS, ix->sd, true, {end_row, end_col, nullptr}, {start_row, start_col, nullptr},
                     device_ms);
 }

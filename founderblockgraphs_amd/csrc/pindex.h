@@ -12,8 +12,13 @@
 //   pindex_mapq.hip       the second-best chain of a read outside the columns of its best one, and a mapping quality
 // Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
 // needs its launch calls a launcher declared at the end of this header.
+// Two things tie the stages together.  The reads of the last seeds call lie in buffers of their own (PsState batch), which
+// every later stage reads through ps_reads / ps_roff and no other search writes.  Whether a stage's result is current is
+// kept in one table (pindex_stage.h, fbg_pindex::done): a producing call begins its stage (px_begin), which makes every
+// result made from it stale, and finishes it (px_finish) where it has succeeded; a call that reads a result needs it (px_need).
 #pragma once
 #include "fbg_internal.h"
+#include "pindex_stage.h"
 #include <algorithm>
 #include <vector>
 
@@ -57,7 +62,6 @@
 struct PoState {
     DevBuf etot, stot, esz, ssz, eoff, soff, rs, el, ss, sk, place;
     DevBuf msa;               // the rows and columns of the last fbg_pindex_occurrences_msa / _seeds_msa, apart from place
-    bool ready = false;
     uint64_t n = 0, etotal = 0, stotal = 0;
 };
 
@@ -69,30 +73,27 @@ struct PoState {
 struct PcState {
     DevBuf col, pred, key, id, key2, id2, end, score, len, off, out, slab, ctr;
     DevBuf strand, best, sctr;
-    bool ready = false;
     uint64_t n = 0, total = 0, anchors = 0, tier[3] = {0, 0, 0}, band = 0;
 };
 
 // The row table of fbg_pindex_build_segmentation_rows: node_of[nb * m], block-major, and the gathered labels with their
-// offsets (a node without an edge has no copy of its label in the index text).  reads / roff: the reads of the last seeds
-// call, moved aside when a locate or occurrences call is about to overwrite pats / poff (saved).  sbase: per seed the
-// byte of the reads its substring starts at; rec: per start place (node, offset in the node, seed, block) or PR_NONE
-// first; out / cout: what the last fbg_pindex_seeds_rows / _chains_rows copied out; ctr: its count of empty sets.
+// offsets (a node without an edge has no copy of its label in the index text).  sbase: per seed the byte of the reads its
+// substring starts at; rec: per start place (node, offset in the node, seed, block) or PR_NONE first; out / cout: what
+// the last fbg_pindex_seeds_rows / _chains_rows copied out; ctr: its count of empty sets.
 struct PrState {
-    DevBuf node_of, labels, loff, reads, roff, sbase, rec, out, cout, ctr;
-    bool saved = false;
-    uint64_t m = 0, label_bytes = 0, read_bytes = 0, places_unsupported = 0, chains_unsupported = 0;
+    DevBuf node_of, labels, loff, sbase, rec, out, cout, ctr;
+    uint64_t m = 0, label_bytes = 0, places_unsupported = 0, chains_unsupported = 0;
 };
 
 // fbg_pindex_chains_align.  pref: p(r, j) as uint32[nb * m], block-major like node_of, built by the first call.  Per read
 // of the last seeds call: nrows / first (what k_pr_chain leaves: the row choice), info = (row, w0, |W| or 0 where nothing
 // is aligned, L), start = (block, node, offset in the node) at which w0 falls, wlen and its scan woff (n + 1 each), out
 // (row, edits, t_start, t_end: 4 n); win: the windows, back to back; ctr: non-empty chains without a row, reads aligned,
-// too long, too wide, and the cells.  valid: a call has succeeded since the last fbg_pindex_chains, for n reads, and
-// (on_device) left info, woff, win and out for them; not where it returned before its first kernel.
+// too long, too wide, and the cells.  A current result (PS_ALIGN) is for n reads; on_device: the call left info, woff, win
+// and out for them, which it did not where it returned before its first kernel.
 struct PaState {
     DevBuf pref, nrows, info, start, wlen, woff, win, out, ctr;
-    bool has_pref = false, valid = false, on_device = false;
+    bool has_pref = false, on_device = false;
     uint64_t n = 0;
     uint64_t stat[5] = {0, 0, 0, 0, 0};
 };
@@ -100,10 +101,11 @@ struct PaState {
 // fbg_pindex_chains_cigar.  Per read of the last align call: sz (history units of 8 bytes, then run slots; n + 1 each)
 // and their scans hoff / soff, cnt (runs as u64, n + 1) and its scan off, nops (runs as u32); slots: 2 * edits + 1 runs
 // per aligned read; ops: the runs back to back; hist: the column history of one batch of long reads; ctr: PG_CTR
-// counters.  ready: a call has succeeded since that align call, for n reads and total runs (on_device as above).
+// counters.  A current result (PS_CIGAR; PS_GCIGAR for the state of the graph call) is for n reads and total runs
+// (on_device as above).
 struct PgState {
     DevBuf sz, hoff, soff, cnt, off, nops, slots, ops, hist, ctr;
-    bool ready = false, on_device = false;
+    bool on_device = false;
     uint64_t n = 0, total = 0;
     uint64_t stat[5] = {0, 0, 0, 0, 0};      // paths, ops, columns, history_bytes, batches
 };
@@ -111,10 +113,9 @@ struct PgState {
 // fbg_pindex_chains_by_row.  Per read of the last seeds call: row, score and nbest (what k_pb_score leaves), the binning
 // keys and ids before and after the sort; doff: the scan of the device tier's place counts, slab: that tier's state
 // (PB_PLACE bytes per place, reserved when a read needs it); col2: the start columns under the mask of the chosen rows,
-// which the chain DP runs on; ctr: PB_CTR counters.  ready: a call has succeeded since the last seeds or plain chains call.
+// which the chain DP runs on; ctr: PB_CTR counters.
 struct PbState {
     DevBuf row, score, nbest, key, id, key2, id2, doff, slab, col2, ctr;
-    bool ready = false;
     uint64_t stat[5] = {0, 0, 0, 0, 0};      // reads_lds, reads_device, reads_too_many, reads_no_row, anchors_kept
 };
 
@@ -124,11 +125,11 @@ struct PbState {
 // H, one past its last, L or 0 where nothing is aligned, jl); sz (scratch words, then path slots; n + 1 each) and their
 // scans soff / poff; out: edits, start node and offset, end node and offset, n_path (6 n); cnt (n_path as u64, n + 1) and
 // its scan off; slots: the traced nodes, end first; path: the paths back to back; scratch: the last columns of one
-// batch; sel: the caller's mask; ctr: PH_CTR counters.  valid: a call has succeeded since the last chaining call, for n
-// reads and total path nodes, and (on_device) left off and path for them.
+// batch; sel: the caller's mask; ctr: PH_CTR counters.  A current result (PS_GRAPH) is for n reads and total path nodes;
+// on_device: the call left off and path for them.
 struct PhState {
     DevBuf pin_off, pin, C, keys, info, sz, soff, poff, out, cnt, off, slots, path, scratch, sel, ctr;
-    bool has_tab = false, valid = false, on_device = false;
+    bool has_tab = false, on_device = false;
     uint64_t n = 0, total = 0;
     uint64_t stat[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};     // aligned, not_selected, too_long, too_wide, cells, nodes, merges, path_nodes, batches
 };
@@ -146,15 +147,23 @@ struct PjState {
 // (ch.col: the witness rows and columns, expanded again); span: per read lo and hi of its primary chain as u64 (2 n,
 // PQ_NOSPAN in lo for an empty chain); mcol: per start place its witness column, or PC_NONE where the anchor is excluded;
 // span2: second_lo, then second_hi (2 n); mapq / smapq: the mapping quality per read, and the stranded one; ctr: PQ_CTR
-// counters.  roff: the read offsets of the last seeds call, moved aside (saved) on an index without the row table when a
-// locate or occurrences call is about to overwrite poff.  ready: a call has succeeded since the last chaining call, for n
-// reads and total secondary anchors, and (on_device) left its arrays on the device; not where it launched nothing.
+// counters.  A current result (PS_MAPQ) is for n reads and total secondary anchors; on_device: the call left its arrays on
+// the device, which it did not where it launched nothing.
 struct PqState {
     PcState ch;
-    DevBuf span, mcol, span2, mapq, smapq, ctr, roff;
-    bool ready = false, on_device = false, saved = false;
+    DevBuf span, mcol, span2, mapq, smapq, ctr;
+    bool on_device = false;
     uint64_t n = 0, total = 0;
     uint64_t stat[5] = {0, 0, 0, 0, 0};      // reads_with_second, anchors_kept, anchors_excluded, mapq0, mapq60
+};
+
+// The reads of the last fbg_pindex_seeds / _seeds_strands, in buffers that only a seeds call writes: reads (bytes of them,
+// padded as px_front pads) and roff (n + 1 byte offsets).  n: the reads on the device, with _strands the 2 x given virtual
+// ones (stranded); comp: the complement table of that call (256 bytes).
+struct PsState {
+    DevBuf reads, roff, comp;
+    uint64_t n = 0, bytes = 0;
+    bool stranded = false;
 };
 
 struct fbg_pindex {
@@ -166,7 +175,7 @@ struct fbg_pindex {
     uint64_t n_nodes = 0;
     uint32_t nb = 0, ne = 0;
     DevBuf text, sa, lines, cnt_tab, C, code, bpos, epos;
-    DevBuf pats, poff, okey, oval, okey2, oval2, cnt_out, pos_out, lines_ctr, tmp;
+    DevBuf pats, poff, okey, oval, okey2, oval2, cnt_out, pos_out, lines_ctr, tmp;     // pats / poff: of locate and occurrences
     // kept for fbg_pindex_validate (not in index_bytes): per node the SA range of its label, a text position of the
     // label, its length and in / out flags; per distinct edge its text start (E + 1), source and destination; a
     // coarse table of the edge at every 2^PV_CSHIFT-th text position
@@ -192,9 +201,8 @@ struct fbg_pindex {
     PoState occ;
     DevBuf snum, soff, srec, scnt, spos, sq, slen;
     PoState sd;
-    uint64_t sd_reads = 0;        // reads of the last successful fbg_pindex_seeds (_strands: the 2n virtual reads)
-    bool sd_stranded = false;     // the last seeds call was fbg_pindex_seeds_strands, with sd_reads / 2 given reads
-    DevBuf comp;                  // its complement table (256 bytes)
+    PsState batch;
+    bool done[PS_COUNT] = {};     // the stages whose result is current: written by px_begin and px_finish only
     PcState ch;
     bool has_rows = false;        // built by fbg_pindex_build_segmentation_rows
     PrState rw;
@@ -218,6 +226,31 @@ struct fbg_pindex {
 static inline int px_reserve(fbg_pindex *ix, DevBuf &b, size_t bytes) { return fbg_reserve(ix->ctx, b, bytes, &ix->bufs, false); }
 
 template <class F> static int px_with_tmp(fbg_pindex *ix, F &&call) { return fbg_with_tmp(ix->ctx, ix->tmp, &ix->bufs, false, call); }
+
+// The table of pindex_stage.h on the index.  px_need: FBG_OK where stage y and every stage it was made from are current;
+// else the call `who` fails, naming the first call on the way to y whose result is missing or stale.
+static inline void px_begin(fbg_pindex *ix, PsStage x) { ps_begin(ix->done, x); }
+static inline void px_finish(fbg_pindex *ix, PsStage x) { ps_finish(ix->done, x); }
+static inline bool px_current(const fbg_pindex *ix, PsStage y) { return ps_missing(ix->done, y) == PS_COUNT; }
+static inline int px_need(const fbg_pindex *ix, const char *who, PsStage y)
+{
+    const int miss = ps_missing(ix->done, y);
+    if (miss == PS_COUNT) return FBG_OK;
+    return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: no current %s result (none yet, or an earlier stage has run again since)", who,
+                    ps_table[miss].call);
+}
+
+// px_need on an index that must have the row table (fbg_pindex_build_segmentation_rows)
+static inline int px_need_rows(const fbg_pindex *ix, const char *who, PsStage y)
+{
+    if (!ix->has_rows)
+        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation_rows has the row table", who);
+    return px_need(ix, who, y);
+}
+
+// The reads of the last seeds call, for every stage after it
+static inline const uint8_t *ps_reads(const fbg_pindex *ix) { return ix->batch.reads.as<uint8_t>(); }
+static inline const uint64_t *ps_roff(const fbg_pindex *ix) { return ix->batch.roff.as<uint64_t>(); }
 
 // The device time of a call lies between ev0 and ev1.  The stage records ev0 where its device work starts and calls
 // px_record_end after its last kernel, before it queues the copies to the host, and px_sync_elapsed after them: the
@@ -385,18 +418,18 @@ PX_LOCAL void po_expand_msa(fbg_pindex *ix, const PoState &s, bool starts, uint3
 // and what ends either call after px_sync_elapsed: the limit on chain_off[n], the statistics (bin[4]: the anchors)
 PX_LOCAL int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *device_ms, const char *what, bool *go);
 // pc_reserve, pc_launch and pc_finish work on the chain state c: ix->ch for the two chaining calls, the mapq state's own
-// for fbg_pindex_chains_mapq (pindex_mapq.hip)
+// for fbg_pindex_chains_mapq (pindex_mapq.hip).  None of them touches the stage table: the caller finishes its stage
 PX_LOCAL int pc_reserve(fbg_pindex *ix, PcState &c, PcDev &d, const uint32_t *col, uint64_t band);
 PX_LOCAL int pc_launch(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what);
 PX_LOCAL int pc_finish(fbg_pindex *ix, PcState &c, const uint64_t *chain_off, const uint64_t bin[5], const char *what);
-// pindex_rows.hip: the last seeds call's reads moved aside; k_pr_seed and k_pr_place (records ev0); k_pr_chain
-PX_LOCAL int pr_save_reads(fbg_pindex *ix);
+// pindex_rows.hip: k_pr_seed and k_pr_place (records ev0); k_pr_chain
 PX_LOCAL int pr_prepare(fbg_pindex *ix, PrDev &d);
 PX_LOCAL void pr_chain_launch(fbg_pindex *ix, const PrDev &d, uint64_t n, uint64_t words, uint32_t *n_rows, uint32_t *first_row,
                               uint64_t *bits, unsigned long long *ctr);
 // pindex_align.hip: k_pg_sizes, k_pg_path per tier and batch and k_pg_compact over the alignments of in (NULL: nothing of
-// them is on the device, n reads without runs) into g, for the call `who`; started: the caller recorded ev0 with kernels of
-// its own.  Ends with px_sync_elapsed.  And the copy of g's offsets and runs to the host
-PX_LOCAL int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, uint64_t n, bool started, uint32_t *n_ops, uint64_t *total_ops,
-                      double *device_ms, const char *who);
+// them is on the device, n reads without runs) into g, the state of `stage` (PS_CIGAR or PS_GCIGAR), for the call `who`;
+// started: the caller recorded ev0 with kernels of its own.  Ends with px_sync_elapsed.  And the copy of g's offsets and
+// runs to the host
+PX_LOCAL int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, PsStage stage, uint64_t n, bool started, uint32_t *n_ops,
+                      uint64_t *total_ops, double *device_ms, const char *who);
 PX_LOCAL int pg_fetch(fbg_pindex *ix, const PgState &g, uint64_t *off, uint32_t *ops);

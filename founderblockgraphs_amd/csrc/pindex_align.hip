@@ -412,8 +412,8 @@ static PaDev pa_dev(const fbg_pindex *ix)
     a.pref = ix->al.pref.as<uint32_t>();
     a.labels = w.labels.as<uint8_t>();
     a.loff = w.loff.as<uint64_t>();
-    a.reads = (w.saved ? w.reads : ix->pats).as<uint8_t>();
-    a.roff = (w.saved ? w.roff : ix->poff).as<uint64_t>();
+    a.reads = ps_reads(ix);
+    a.roff = ps_roff(ix);
     a.m = w.m;
     a.nb = ix->seg_nb;
     return a;
@@ -432,22 +432,20 @@ extern "C" int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t ma
     PaState &al = ix->al;
     const PcState &c = ix->ch;
     if (device_ms) *device_ms = 0;
-    if (!ix->has_rows)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_align: only an index built by fbg_pindex_build_segmentation_rows has the row table");
-    if (!ix->sd.ready || !c.ready)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_align: no fbg_pindex_chains result since the last seeds call");
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_chains_align", PS_CHAINS));
     std::fill(al.stat, al.stat + 5, (uint64_t)0);
     const uint64_t n = c.n;
-    al.valid = al.on_device = ix->cg.ready = false;       // the paths belong to the align call they were traced from
+    px_begin(ix, PS_ALIGN);                               // the paths belong to the align call they were traced from
+    al.on_device = false;
     al.n = n;
-    if (n == 0) { al.valid = true; return FBG_OK; }
+    if (n == 0) { px_finish(ix, PS_ALIGN); return FBG_OK; }
     if (n > 0x7fffffffull)        // a wave, and so a workgroup, per read
         return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_chains_align: %llu reads; a call takes fewer than 2^31", (unsigned long long)n);
     uint32_t *host[4] = {row, edits, t_start, t_end};
     if (c.total == 0) {          // every chain is empty, and fbg_pindex_chains may have left nothing on the device
         for (uint32_t *h : host)
             if (h) std::fill(h, h + n, (uint32_t)PA_NONE);
-        al.valid = true;
+        px_finish(ix, PS_ALIGN);
         return FBG_OK;
     }
     if (pad > (1ull << 33)) pad = 1ull << 33;         // positions and read offsets are below 2^32: beyond this nothing changes
@@ -497,7 +495,8 @@ extern "C" int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t ma
     FBG_TRY(px_sync_elapsed(ix, device_ms));
     std::copy(stat, stat + 5, al.stat);
     al.has_pref = true;
-    al.valid = al.on_device = true;
+    al.on_device = true;
+    px_finish(ix, PS_ALIGN);
     return FBG_OK;
 }
 
@@ -522,15 +521,6 @@ extern "C" int fbg_pindex_align_stats(const fbg_pindex *ix, uint64_t *aligned, u
 // pg_trace, which fbg_pindex_chains_graph_cigar (pindex_gcigar.hip) runs too, on alignments and a state of its own: sizes
 // and their scans, the host's look at the history offsets (which form the batches), the slot total and the tier counts; one k_pg_path launch per word count that has reads, then one per batch of longer reads, all on the stream and
 // so one after the other in the one scratch; a scan of the run counts, the host's look at their sum, the compaction.
-static int pg_check(const fbg_pindex *ix, const char *who)
-{
-    if (!ix->has_rows)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation_rows has the row table", who);
-    if (!ix->sd.ready || !ix->ch.ready || !ix->al.valid)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: no fbg_pindex_chains_align result since the last fbg_pindex_chains", who);
-    return FBG_OK;
-}
-
 template <int NW>
 static void pg_launch(hipStream_t st, const PaDev &a, const PgIn &in, PgState &g, uint64_t n, uint64_t first, uint64_t reads, uint32_t cap,
                       uint64_t hbase)
@@ -541,20 +531,20 @@ static void pg_launch(hipStream_t st, const PaDev &a, const PgIn &in, PgState &g
                        g.ctr.as<unsigned long long>());
 }
 
-int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, uint64_t n, bool started, uint32_t *n_ops, uint64_t *total_ops, double *device_ms,
-             const char *who)
+int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, PsStage stage, uint64_t n, bool started, uint32_t *n_ops, uint64_t *total_ops,
+             double *device_ms, const char *who)
 {
     fbg_ctx *ctx = ix->ctx;
     if (device_ms) *device_ms = 0;
     if (total_ops) *total_ops = 0;
-    g.ready = false;
+    px_begin(ix, stage);
     if (n == 0 || !in) {
         if (n_ops) std::fill(n_ops, n_ops + n, (uint32_t)0);
         std::fill(g.stat, g.stat + 5, (uint64_t)0);
         g.n = n;
         g.total = 0;
         g.on_device = false;
-        g.ready = true;
+        px_finish(ix, stage);
         return FBG_OK;
     }
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -634,7 +624,7 @@ int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, uint64_t n, bool starte
     g.n = n;
     g.total = total;
     g.on_device = true;
-    g.ready = true;
+    px_finish(ix, stage);
     return FBG_OK;
 }
 
@@ -657,18 +647,16 @@ extern "C" int fbg_pindex_chains_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t
 {
     if (!ix) return FBG_ERR_INVALID;
     const PaState &al = ix->al;
-    FBG_TRY(pg_check(ix, "fbg_pindex_chains_cigar"));
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_chains_cigar", PS_ALIGN));
     // no reads, or every chain empty: nothing of that align call on the device
     const PgIn in = {al.info.as<uint4>(), al.woff.as<uint64_t>(), al.win.as<uint8_t>(), al.out.as<uint32_t>()};
-    return pg_trace(ix, al.on_device ? &in : nullptr, ix->cg, al.n, false, n_ops, total_ops, device_ms, "fbg_pindex_chains_cigar");
+    return pg_trace(ix, al.on_device ? &in : nullptr, ix->cg, PS_CIGAR, al.n, false, n_ops, total_ops, device_ms, "fbg_pindex_chains_cigar");
 }
 
 extern "C" int fbg_pindex_chains_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint32_t *ops)
 {
     if (!ix) return FBG_ERR_INVALID;
-    FBG_TRY(pg_check(ix, "fbg_pindex_chains_cigar_fetch"));
-    if (!ix->cg.ready)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "fbg_pindex_chains_cigar_fetch: no fbg_pindex_chains_cigar result since that align call");
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_chains_cigar_fetch", PS_CIGAR));
     return pg_fetch(ix, ix->cg, off, ops);
 }
 

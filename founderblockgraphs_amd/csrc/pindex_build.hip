@@ -494,7 +494,7 @@ static int px_build_prepared(fbg_pindex *ix, PxScratch &s, const PxPrep &pp)
     ix->compact = sigma <= 16;
     ix->n_nodes = n_nodes;
     ix->nblk = N1 / PX_BLK + 1;
-    ix->occ.ready = ix->sd.ready = false;
+    for (int s = 0; s < PS_COUNT; s++) px_begin(ix, (PsStage)s);      // no result of the index as it was is current
 
     FBG_TRY(px_reserve(ix, ix->vrng, n_nodes * 8));
     ix->n_edges = E;

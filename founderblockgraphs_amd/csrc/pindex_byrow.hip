@@ -181,11 +181,11 @@ extern "C" int fbg_pindex_chains_by_row(fbg_pindex *ix, uint64_t band, uint64_t 
         return fbg_fail(ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation_rows has the row table", what);
     bool go = false;
     FBG_TRY(pc_begin(ix, chain_off, score, device_ms, what, &go));
-    const uint64_t n = ix->sd_reads, A = s.stotal;
+    const uint64_t n = ix->batch.n, A = s.stotal;
     std::fill(b.stat, b.stat + 5, (uint64_t)0);
     if (row) std::fill(row, row + n, (uint32_t)PR_NONE);
     if (n_best_rows) std::fill(n_best_rows, n_best_rows + n, (uint32_t)0);
-    if (!go) { b.ready = true; return FBG_OK; }
+    if (!go) { px_finish(ix, PS_CHAINS); px_finish(ix, PS_BYROW); return FBG_OK; }
     if (n > 0x7fffffffull)        // a wave, and so a workgroup, per read
         return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "%s: %llu reads; a call takes fewer than 2^31", what, (unsigned long long)n);
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -273,7 +273,8 @@ extern "C" int fbg_pindex_chains_by_row(fbg_pindex *ix, uint64_t band, uint64_t 
     b.stat[2] = bin[3];
     b.stat[3] = bin[5];
     b.stat[4] = bin[6];
-    b.ready = true;
+    px_finish(ix, PS_CHAINS);
+    px_finish(ix, PS_BYROW);
     return FBG_OK;
 }
 
@@ -284,7 +285,7 @@ extern "C" int fbg_pindex_chains_by_row_stats(const fbg_pindex *ix, uint64_t *re
     const PbState &b = ix->pb;
     uint64_t *out[5] = {reads_lds, reads_device, reads_too_many, reads_no_row, anchors_kept};
     for (int k = 0; k < 5; k++)
-        if (out[k]) *out[k] = b.ready ? b.stat[k] : 0;
+        if (out[k]) *out[k] = px_current(ix, PS_BYROW) ? b.stat[k] : 0;
     if (lds_max) *lds_max = PB_LDS;
     if (max_places) *max_places = ix->ctx->opt.byrow_max < 0 ? 0 : (uint64_t)ix->ctx->opt.byrow_max;
     return FBG_OK;

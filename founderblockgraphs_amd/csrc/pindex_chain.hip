@@ -159,30 +159,27 @@ __global__ void k_pc_strand(const uint32_t *score, const uint64_t *len, uint64_t
 // pc_begin, pc_reserve, pc_launch and pc_finish (pindex.h).  The last three take the chain state they work on:
 // fbg_pindex_chains_mapq (pindex_mapq.hip) runs them on a state of its own and leaves ix->ch alone.
 
-// The checks and trivial cases of a chaining call (what: its name).  *go: there is something to launch.
+// The checks and trivial cases of a chaining call (what: its name).  *go: there is something to launch; where there is
+// not, the caller finishes its stages at once.
 int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *device_ms, const char *what, bool *go)
 {
     fbg_ctx *ctx = ix->ctx;
     PcState &c = ix->ch;
     const PoState &s = ix->sd;
     *go = false;
-    c.ready = false;
-    ix->pb.ready = false;
-    ix->al.valid = ix->cg.ready = false;      // the alignment and its paths belong to the chains
-    ix->gr.valid = false;                     // and so does the alignment to the graph
-    ix->pq.ready = false;                     // and the second-best chains and the mapping quality
+    px_begin(ix, PS_CHAINS);      // with the row choice, the alignments, their paths and the mapping quality made from the chains
     if (device_ms) *device_ms = 0;
     if (!chain_off) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing chain_off", what);
     if (!ix->from_segmentation || !ix->has_map)
         return fbg_fail(ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation knows MSA columns", what);
-    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no fbg_pindex_seeds result to chain", what);
-    const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
+    FBG_TRY(px_need(ix, what, PS_SEEDS));
+    const uint64_t n = ix->batch.n, S = s.n, A = s.stotal;
     c.n = n;
     c.total = c.anchors = 0;
     c.tier[0] = c.tier[1] = c.tier[2] = 0;
     std::fill(chain_off, chain_off + n + 1, (uint64_t)0);
     if (score) std::fill(score, score + n, (uint32_t)0);
-    if (n == 0 || S == 0 || A == 0) { c.ready = true; return FBG_OK; }   // no start place: every score 0, every chain empty
+    if (n == 0 || S == 0 || A == 0) return FBG_OK;      // no start place: every score 0, every chain empty
     *go = true;
     return FBG_OK;
 }
@@ -190,7 +187,7 @@ int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, double *devic
 int pc_reserve(fbg_pindex *ix, PcState &c, PcDev &d, const uint32_t *col, uint64_t band)
 {
     const PoState &s = ix->sd;
-    const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
+    const uint64_t n = ix->batch.n, S = s.n, A = s.stotal;
     FBG_TRY(px_reserve(ix, c.col, 2 * A * 4));
     FBG_TRY(px_reserve(ix, c.pred, A * 4));
     for (DevBuf *b : {&c.key, &c.id, &c.key2, &c.id2, &c.end, &c.score}) FBG_TRY(px_reserve(ix, *b, n * 4));
@@ -215,7 +212,7 @@ int pc_launch(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score, uint64_t
 {
     fbg_ctx *ctx = ix->ctx;
     hipStream_t st = ctx->stream;
-    const uint64_t n = ix->sd_reads, S = ix->sd.n, A = ix->sd.stotal;
+    const uint64_t n = ix->batch.n, S = ix->sd.n, A = ix->sd.stotal;
     uint32_t *ka = c.key.as<uint32_t>(), *va = c.id.as<uint32_t>(), *kb = c.key2.as<uint32_t>(), *vb = c.id2.as<uint32_t>();
     hipLaunchKernelGGL(k_pc_key, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, d, n, ka, va);
     FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
@@ -257,7 +254,6 @@ int pc_finish(fbg_pindex *ix, PcState &c, const uint64_t *chain_off, const uint6
     c.tier[0] = bin[1];
     c.tier[1] = bin[2];
     c.tier[2] = bin[3];
-    c.ready = true;
     return FBG_OK;
 }
 
@@ -270,8 +266,8 @@ extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_sco
     const PoState &s = ix->sd;
     bool go = false;
     FBG_TRY(pc_begin(ix, chain_off, score, device_ms, "fbg_pindex_chains", &go));
-    if (!go) return FBG_OK;
-    const uint64_t n = ix->sd_reads, A = s.stotal;
+    if (!go) { px_finish(ix, PS_CHAINS); return FBG_OK; }
+    const uint64_t n = ix->batch.n, A = s.stotal;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     PcDev d;
@@ -286,7 +282,9 @@ extern "C" int fbg_pindex_chains(fbg_pindex *ix, uint64_t band, uint64_t min_sco
     if (score) FBG_HIP_TRY(ctx, hipMemcpyAsync(score, c.score.p, n * 4, hipMemcpyDeviceToHost, st));
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&bin[4], d.ctr + 4, 8, hipMemcpyDeviceToHost, st));
     FBG_TRY(px_sync_elapsed(ix, device_ms));
-    return pc_finish(ix, c, chain_off, bin, "fbg_pindex_chains");
+    FBG_TRY(pc_finish(ix, c, chain_off, bin, "fbg_pindex_chains"));
+    px_finish(ix, PS_CHAINS);
+    return FBG_OK;
 }
 
 extern "C" int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, uint32_t *anchor_seed, double *device_ms)
@@ -295,7 +293,7 @@ extern "C" int fbg_pindex_chains_fetch(fbg_pindex *ix, uint32_t *anchor_place, u
     fbg_ctx *ctx = ix->ctx;
     const PcState &c = ix->ch;
     if (device_ms) *device_ms = 0;
-    if (!c.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_fetch: no fbg_pindex_chains result to fetch");
+    FBG_TRY(px_need(ix, "fbg_pindex_chains_fetch", PS_CHAINS));
     if (c.total == 0 || (!anchor_place && !anchor_seed)) return FBG_OK;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -317,10 +315,11 @@ extern "C" int fbg_pindex_chain_strands(fbg_pindex *ix, uint8_t *strand, uint32_
     fbg_ctx *ctx = ix->ctx;
     PcState &c = ix->ch;
     if (device_ms) *device_ms = 0;
-    if (!ix->sd.ready || !ix->sd_stranded)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chain_strands: the last seeds call was no successful fbg_pindex_seeds_strands");
-    if (!c.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chain_strands: no fbg_pindex_chains result since that seeds call");
-    const uint64_t n = ix->sd_reads / 2;
+    FBG_TRY(px_need(ix, "fbg_pindex_chain_strands", PS_SEEDS));
+    if (!ix->batch.stranded)
+        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chain_strands: the last seeds call was no fbg_pindex_seeds_strands");
+    FBG_TRY(px_need(ix, "fbg_pindex_chain_strands", PS_CHAINS));
+    const uint64_t n = ix->batch.n / 2;
     if (n == 0) return FBG_OK;
     uint64_t cnt[3] = {0, 0, n};
     if (ix->sd.n == 0 || ix->sd.stotal == 0) {
@@ -354,10 +353,11 @@ extern "C" int fbg_pindex_chain_stats(const fbg_pindex *ix, uint64_t *anchors, u
 {
     if (!ix) return FBG_ERR_INVALID;
     const PcState &c = ix->ch;
-    if (anchors) *anchors = c.ready ? c.anchors : 0;
-    if (reads_small) *reads_small = c.ready ? c.tier[0] : 0;
-    if (reads_wave) *reads_wave = c.ready ? c.tier[1] : 0;
-    if (reads_spill) *reads_spill = c.ready ? c.tier[2] : 0;
+    const bool ok = px_current(ix, PS_CHAINS);
+    if (anchors) *anchors = ok ? c.anchors : 0;
+    if (reads_small) *reads_small = ok ? c.tier[0] : 0;
+    if (reads_wave) *reads_wave = ok ? c.tier[1] : 0;
+    if (reads_spill) *reads_spill = ok ? c.tier[2] : 0;
     if (small_max) *small_max = PC_SMALL;
     if (lds_max) *lds_max = PC_LDS;
     return FBG_OK;

@@ -70,15 +70,6 @@ __global__ __launch_bounds__(FBG_WAVE) void k_pj_gather(const uint8_t *labels, c
     }
 }
 
-static int pj_check(const fbg_pindex *ix, const char *who)
-{
-    if (!ix->has_rows)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation_rows has the row table", who);
-    if (!ix->sd.ready || !ix->ch.ready || !ix->gr.valid)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: no fbg_pindex_chains_align_graph result since the last chaining call", who);
-    return FBG_OK;
-}
-
 // k_pj_sizes, a scan of N, the host's look at its sum and at the bad paths, the gather into a text of that size, and
 // pg_trace on the result, which ends the device time that ev0 starts here.
 extern "C" int fbg_pindex_chains_graph_cigar(fbg_pindex *ix, uint32_t *n_ops, uint64_t *total_ops, double *device_ms)
@@ -88,13 +79,13 @@ extern "C" int fbg_pindex_chains_graph_cigar(fbg_pindex *ix, uint32_t *n_ops, ui
     const PhState &gr = ix->gr;
     PjState &j = ix->gj;
     const char *who = "fbg_pindex_chains_graph_cigar";
-    FBG_TRY(pj_check(ix, who));
+    FBG_TRY(px_need_rows(ix, who, PS_GRAPH));
     const uint64_t n = gr.n;
     if (n == 0 || !gr.on_device)              // no reads, or every chain empty: nothing of that graph call on the device
-        return pg_trace(ix, nullptr, j.g, n, false, n_ops, total_ops, device_ms, who);
+        return pg_trace(ix, nullptr, j.g, PS_GCIGAR, n, false, n_ops, total_ops, device_ms, who);
     if (device_ms) *device_ms = 0;
     if (total_ops) *total_ops = 0;
-    j.g.ready = false;
+    px_begin(ix, PS_GCIGAR);
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     FBG_TRY(px_reserve(ix, j.info, n * 16));
@@ -128,15 +119,13 @@ extern "C" int fbg_pindex_chains_graph_cigar(fbg_pindex *ix, uint32_t *n_ops, ui
         FBG_HIP_TRY(ctx, hipGetLastError());
     }
     const PgIn in = {j.info.as<uint4>(), woff, j.text.as<uint8_t>(), j.out.as<uint32_t>()};
-    return pg_trace(ix, &in, j.g, n, true, n_ops, total_ops, device_ms, who);
+    return pg_trace(ix, &in, j.g, PS_GCIGAR, n, true, n_ops, total_ops, device_ms, who);
 }
 
 extern "C" int fbg_pindex_chains_graph_cigar_fetch(fbg_pindex *ix, uint64_t *off, uint32_t *ops)
 {
     if (!ix) return FBG_ERR_INVALID;
-    FBG_TRY(pj_check(ix, "fbg_pindex_chains_graph_cigar_fetch"));
-    if (!ix->gj.g.ready)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "fbg_pindex_chains_graph_cigar_fetch: no fbg_pindex_chains_graph_cigar result since that graph call");
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_chains_graph_cigar_fetch", PS_GCIGAR));
     return pg_fetch(ix, ix->gj.g, off, ops);
 }
 

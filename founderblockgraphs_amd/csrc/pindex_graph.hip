@@ -470,15 +470,6 @@ __global__ void k_ph_compact(const uint64_t *poff, const uint32_t *slots, const 
 }
 
 // ---- the calls --------------------------------------------------------------------------------------------------------
-static int ph_check(const fbg_pindex *ix, const char *who)
-{
-    if (!ix->has_rows)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation_rows has the row table", who);
-    if (!ix->sd.ready || !ix->ch.ready)
-        return fbg_fail(ix->ctx, FBG_ERR_INVALID, "%s: no fbg_pindex_chains or fbg_pindex_chains_by_row result since the last seeds call", who);
-    return FBG_OK;
-}
-
 // the predecessor CSR and C, once per index
 static int ph_tables(fbg_pindex *ix)
 {
@@ -528,20 +519,21 @@ extern "C" int fbg_pindex_chains_align_graph(fbg_pindex *ix, uint64_t pad, uint6
     const PcState &c = ix->ch;
     if (device_ms) *device_ms = 0;
     if (total_path) *total_path = 0;
-    FBG_TRY(ph_check(ix, "fbg_pindex_chains_align_graph"));
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_chains_align_graph", PS_CHAINS));
     std::fill(g.stat, g.stat + 9, (uint64_t)0);
     const uint64_t n = c.n;
-    g.valid = g.on_device = ix->gj.g.ready = false;       // the CIGARs belong to the graph call they were traced from
+    px_begin(ix, PS_GRAPH);                               // the CIGARs belong to the graph call they were traced from
+    g.on_device = false;
     g.n = n;
     g.total = 0;
-    if (n == 0) { g.valid = true; return FBG_OK; }
+    if (n == 0) { px_finish(ix, PS_GRAPH); return FBG_OK; }
     if (n > 0x7fffffffull)        // a wave, and so a workgroup, per read
         return fbg_fail(ctx, FBG_ERR_TOO_LARGE, "fbg_pindex_chains_align_graph: %llu reads; a call takes fewer than 2^31", (unsigned long long)n);
     uint32_t *host[6] = {edits, start_node, start_offset, end_node, end_offset, n_path};
     if (c.total == 0) {          // every chain is empty, and the chaining call may have left nothing on the device
         for (int k = 0; k < 6; k++)
             if (host[k]) std::fill(host[k], host[k] + n, k < 5 ? (uint32_t)PA_NONE : 0u);
-        g.valid = true;
+        px_finish(ix, PS_GRAPH);
         return FBG_OK;
     }
     if (pad > (1ull << 33)) pad = 1ull << 33;         // offsets and read lengths are below 2^32: beyond this nothing changes
@@ -559,8 +551,8 @@ extern "C" int fbg_pindex_chains_align_graph(fbg_pindex *ix, uint64_t pad, uint6
     PhDev h;
     h.labels = w.labels.as<uint8_t>();
     h.loff = w.loff.as<uint64_t>();
-    h.reads = (w.saved ? w.reads : ix->pats).as<uint8_t>();
-    h.roff = (w.saved ? w.roff : ix->poff).as<uint64_t>();
+    h.reads = ps_reads(ix);
+    h.roff = ps_roff(ix);
     h.first = ix->sfirst.as<uint64_t>();
     h.C = g.C.as<uint64_t>();
     h.pin_off = g.pin_off.as<uint32_t>();
@@ -641,7 +633,8 @@ extern "C" int fbg_pindex_chains_align_graph(fbg_pindex *ix, uint64_t pad, uint6
     const uint64_t stat[9] = {cv[1], cv[2], cv[3], cv[4], cv[5], cv[6], cv[7], total, batch.size()};
     std::copy(stat, stat + 9, g.stat);
     g.total = total;
-    g.valid = g.on_device = true;
+    g.on_device = true;
+    px_finish(ix, PS_GRAPH);
     return FBG_OK;
 }
 
@@ -650,9 +643,7 @@ extern "C" int fbg_pindex_chains_align_graph_fetch(fbg_pindex *ix, uint64_t *pat
     if (!ix) return FBG_ERR_INVALID;
     fbg_ctx *ctx = ix->ctx;
     const PhState &g = ix->gr;
-    FBG_TRY(ph_check(ix, "fbg_pindex_chains_align_graph_fetch"));
-    if (!g.valid)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_align_graph_fetch: no fbg_pindex_chains_align_graph result since the last chaining call");
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_chains_align_graph_fetch", PS_GRAPH));
     if (!g.on_device) {
         if (path_off) std::fill(path_off, path_off + g.n + 1, (uint64_t)0);
         return FBG_OK;

@@ -123,7 +123,6 @@ static PqDev pq_dev(fbg_pindex *ix, uint64_t margin)
 {
     PqState &q = ix->pq;
     const PcState &c = ix->ch;
-    const PrState &w = ix->rw;
     const uint64_t S = ix->sd.n, A = ix->sd.stotal;
     PqDev d;
     d.seed_off = ix->soff.as<uint64_t>();
@@ -134,10 +133,10 @@ static PqDev pq_dev(fbg_pindex *ix, uint64_t margin)
     d.place = c.out.as<uint32_t>();
     d.seed = c.out.as<uint32_t>() + S;
     d.score = c.score.as<uint32_t>();
-    d.roff = (w.saved ? w.roff : q.saved ? q.roff : ix->poff).as<uint64_t>();
+    d.roff = ps_roff(ix);
     d.span = q.span.as<uint64_t>();
     d.ctr = q.ctr.as<unsigned long long>();
-    d.n = ix->sd_reads;
+    d.n = ix->batch.n;
     d.S = S;
     d.A = A;
     d.margin = margin;
@@ -157,14 +156,13 @@ extern "C" int fbg_pindex_chains_mapq(fbg_pindex *ix, uint64_t margin, uint64_t 
     PqState &q = ix->pq;
     const PcState &c = ix->ch;
     const PoState &s = ix->sd;
-    q.ready = false;
+    px_begin(ix, PS_MAPQ);
     if (device_ms) *device_ms = 0;
     if (!second_off) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: missing second_off", what);
     if (!ix->from_segmentation || !ix->has_map)
         return fbg_fail(ctx, FBG_ERR_INVALID, "%s: only an index built by fbg_pindex_build_segmentation knows MSA columns", what);
-    if (!s.ready || !c.ready)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no fbg_pindex_chains or fbg_pindex_chains_by_row result since the last seeds call", what);
-    const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
+    FBG_TRY(px_need(ix, what, PS_CHAINS));
+    const uint64_t n = ix->batch.n, S = s.n, A = s.stotal;
     q.n = n;
     q.total = 0;
     q.on_device = false;
@@ -174,7 +172,7 @@ extern "C" int fbg_pindex_chains_mapq(fbg_pindex *ix, uint64_t margin, uint64_t 
     if (second_lo) std::fill(second_lo, second_lo + n, (uint32_t)PC_NONE);
     if (second_hi) std::fill(second_hi, second_hi + n, (uint32_t)PC_NONE);
     if (mapq) std::fill(mapq, mapq + n, (uint8_t)0);
-    if (n == 0 || S == 0 || A == 0) { q.ready = true; return FBG_OK; }    // no start place: no primary chain, no secondary
+    if (n == 0 || S == 0 || A == 0) { px_finish(ix, PS_MAPQ); return FBG_OK; }    // no start place: no primary chain, no secondary
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     FBG_TRY(px_reserve(ix, q.span, 2 * n * 8));
@@ -210,7 +208,6 @@ extern "C" int fbg_pindex_chains_mapq(fbg_pindex *ix, uint64_t margin, uint64_t 
     FBG_HIP_TRY(ctx, hipMemcpyAsync(&bin[4], pd.ctr + 4, 8, hipMemcpyDeviceToHost, st));
     FBG_TRY(px_sync_elapsed(ix, device_ms));
     FBG_TRY(pc_finish(ix, q.ch, second_off, bin, what));
-    q.ch.ready = false;                 // the state is read through q.ready only
     q.total = second_off[n];
     q.stat[0] = ctr[2];
     q.stat[1] = ctr[0];
@@ -218,7 +215,7 @@ extern "C" int fbg_pindex_chains_mapq(fbg_pindex *ix, uint64_t margin, uint64_t 
     q.stat[3] = ctr[3];
     q.stat[4] = ctr[4];
     q.on_device = true;
-    q.ready = true;
+    px_finish(ix, PS_MAPQ);
     return FBG_OK;
 }
 
@@ -228,8 +225,7 @@ extern "C" int fbg_pindex_chains_mapq_fetch(fbg_pindex *ix, uint32_t *anchor_pla
     fbg_ctx *ctx = ix->ctx;
     const PqState &q = ix->pq;
     if (device_ms) *device_ms = 0;
-    if (!ix->ch.ready || !q.ready)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_mapq_fetch: no fbg_pindex_chains_mapq result since the last chaining call");
+    FBG_TRY(px_need(ix, "fbg_pindex_chains_mapq_fetch", PS_MAPQ));
     if (q.total == 0 || (!anchor_place && !anchor_seed)) return FBG_OK;
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -251,11 +247,10 @@ extern "C" int fbg_pindex_mapq_strands(fbg_pindex *ix, uint8_t *mapq_stranded, d
     fbg_ctx *ctx = ix->ctx;
     PqState &q = ix->pq;
     if (device_ms) *device_ms = 0;
-    if (!ix->sd.ready || !ix->sd_stranded)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: the last seeds call was no successful fbg_pindex_seeds_strands", what);
-    if (!ix->ch.ready || !q.ready)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "%s: no fbg_pindex_chains_mapq result since the last chaining call", what);
-    const uint64_t n = ix->sd_reads;
+    FBG_TRY(px_need(ix, what, PS_SEEDS));
+    if (!ix->batch.stranded) return fbg_fail(ctx, FBG_ERR_INVALID, "%s: the last seeds call was no fbg_pindex_seeds_strands", what);
+    FBG_TRY(px_need(ix, what, PS_MAPQ));
+    const uint64_t n = ix->batch.n;
     if (n == 0 || !mapq_stranded) return FBG_OK;
     if (!q.on_device) { std::fill(mapq_stranded, mapq_stranded + n, (uint8_t)0); return FBG_OK; }
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -278,7 +273,7 @@ extern "C" int fbg_pindex_mapq_stats(const fbg_pindex *ix, uint64_t *reads_with_
 {
     if (!ix) return FBG_ERR_INVALID;
     const PqState &q = ix->pq;
-    const bool ok = q.ready && ix->ch.ready;
+    const bool ok = px_current(ix, PS_MAPQ);
     uint64_t *out[5] = {reads_with_second, anchors_kept, anchors_excluded, mapq0, mapq60};
     for (int k = 0; k < 5; k++)
         if (out[k]) *out[k] = ok ? q.stat[k] : 0;

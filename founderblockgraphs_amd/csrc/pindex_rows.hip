@@ -99,19 +99,6 @@ __global__ __launch_bounds__(PX_THREADS) void k_pr_chain(PrDev d, const uint4 *r
     if (lane == 0 && none) atomicAdd(unsupported, (unsigned long long)__popcll(none));
 }
 
-// pats / poff of the last seeds call into buffers of the row state, in stream order before whatever overwrites them
-int pr_save_reads(fbg_pindex *ix)
-{
-    fbg_ctx *ctx = ix->ctx;
-    PrState &w = ix->rw;
-    FBG_TRY(px_reserve(ix, w.reads, w.read_bytes + 8));
-    FBG_TRY(px_reserve(ix, w.roff, (ix->sd_reads + 1) * 8));
-    if (w.read_bytes) FBG_HIP_TRY(ctx, hipMemcpyAsync(w.reads.p, ix->pats.p, w.read_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(w.roff.p, ix->poff.p, (ix->sd_reads + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    w.saved = true;
-    return FBG_OK;
-}
-
 // ---- rows (fbg_pindex_seeds_rows / _chains_rows / _rows_stats) -------------------------------------------------------
 // What both calls start with, for S > 0 seeds and A > 0 start places of the last seeds call: sbase per seed and rec per
 // start place (k_pr_seed, k_pr_place), into buffers of the row state; d: what the row kernels read.
@@ -121,14 +108,14 @@ int pr_prepare(fbg_pindex *ix, PrDev &d)
     hipStream_t st = ctx->stream;
     PrState &w = ix->rw;
     const PoState &s = ix->sd;
-    const uint64_t n = ix->sd_reads, S = s.n, A = s.stotal;
+    const uint64_t n = ix->batch.n, S = s.n, A = s.stotal;
     FBG_TRY(px_reserve(ix, w.sbase, S * 8));
     FBG_TRY(px_reserve(ix, w.rec, A * 16));
     FBG_TRY(px_reserve(ix, w.ctr, 8));
     FBG_HIP_TRY(ctx, hipEventRecord(ix->ev0, st));
     FBG_HIP_TRY(ctx, hipMemsetAsync(w.ctr.p, 0, 8, st));
     hipLaunchKernelGGL(k_pr_seed, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, (const uint64_t *)ix->soff.as<uint64_t>(),
-                       (const uint64_t *)(w.saved ? w.roff : ix->poff).as<uint64_t>(), (const uint32_t *)ix->sq.as<uint32_t>(), n, S,
+                       ps_roff(ix), (const uint32_t *)ix->sq.as<uint32_t>(), n, S,
                        w.sbase.as<uint64_t>());
     hipLaunchKernelGGL(k_pr_place, dim3(fbg_blocks(A, PX_THREADS)), dim3(PX_THREADS), 0, st, pv_dev(ix),
                        (const uint32_t *)ix->snode_block.as<uint32_t>(), (const uint64_t *)s.soff.as<uint64_t>(), S, A,
@@ -137,7 +124,7 @@ int pr_prepare(fbg_pindex *ix, PrDev &d)
     d.node_of = w.node_of.as<uint32_t>();
     d.labels = w.labels.as<uint8_t>();
     d.loff = w.loff.as<uint64_t>();
-    d.reads = (w.saved ? w.reads : ix->pats).as<uint8_t>();
+    d.reads = ps_reads(ix);
     d.sbase = w.sbase.as<uint64_t>();
     d.slen = ix->slen.as<uint32_t>();
     d.m = w.m;
@@ -168,9 +155,7 @@ extern "C" int fbg_pindex_seeds_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t 
     PrState &w = ix->rw;
     const PoState &s = ix->sd;
     if (device_ms) *device_ms = 0;
-    if (!ix->has_rows)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds_rows: only an index built by fbg_pindex_build_segmentation_rows has the row table");
-    if (!s.ready) return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_seeds_rows: no fbg_pindex_seeds result to expand");
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_seeds_rows", PS_SEEDS));
     w.places_unsupported = 0;
     const uint64_t A = s.stotal;
     if (A == 0) return FBG_OK;
@@ -205,10 +190,7 @@ extern "C" int fbg_pindex_chains_rows(fbg_pindex *ix, uint32_t *n_rows, uint32_t
     PrState &w = ix->rw;
     const PcState &c = ix->ch;
     if (device_ms) *device_ms = 0;
-    if (!ix->has_rows)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_rows: only an index built by fbg_pindex_build_segmentation_rows has the row table");
-    if (!ix->sd.ready || !c.ready)
-        return fbg_fail(ctx, FBG_ERR_INVALID, "fbg_pindex_chains_rows: no fbg_pindex_chains result since the last seeds call");
+    FBG_TRY(px_need_rows(ix, "fbg_pindex_chains_rows", PS_CHAINS));
     w.chains_unsupported = 0;
     const uint64_t n = c.n, words = (w.m + 63) / 64;
     if (n == 0) return FBG_OK;

@@ -809,9 +809,8 @@ int fbg_pindex_chain_strands(fbg_pindex *ix, uint8_t *strand, uint32_t *score, u
  * per-place set is kept in device memory.  Scratch owned by the index: 16 bytes per start place, 8 per seed, and what a
  * call copies out.  *device_ms (may be NULL): device time of these kernels.
  * A call may be repeated and leaves the seeds, their places and MSA coordinates, the chains, the occurrences,
- * fbg_pindex_stats, validation results and the context alone.  The reads of the last seeds call stay readable: when
- * fbg_pindex_locate or fbg_pindex_occurrences is about to overwrite them, an index with the row table first moves them
- * into a buffer of its own.
+ * fbg_pindex_stats, validation results and the context alone.  The reads of the last seeds call stay readable: they
+ * lie in buffers of their own, which fbg_pindex_locate and fbg_pindex_occurrences do not write.
  * Errors, all FBG_ERR_INVALID: a NULL index; an index without the row table (the plain builder's included); no
  * successful seeds call before fbg_pindex_seeds_rows; no successful fbg_pindex_chains since the last seeds call before
  * fbg_pindex_chains_rows.  Nothing to report returns FBG_OK. */
