@@ -229,17 +229,18 @@ def with_min_score(c, min_score):
 
 
 @functools.lru_cache(maxsize=None)
-def cpu(name):
+def cpu(name, cap=CAP, band=BAND, source=None):
     """What the engine is to return for the stranded call on an input with min_score 0, from the models alone (the shape
-    of test_rows.cpu, with the counts, restarts and totals of every seed and the strand of every read)."""
-    A, reads, truth, high = INPUTS[name]()
+    of test_rows.cpu, with the counts, restarts and totals of every seed and the strand of every read).  cap and band:
+    max_per_seed and the band of the call; source: the input of another module, a function like those of INPUTS."""
+    A, reads, truth, high = (source or INPUTS[name])()
     b = oracle_boundaries(A)
     labels, edges, blocks = HM.segmentation_graph(A, b)
     index, mm, rm = OM.Index(labels, edges), MM.Model(A, b), RM.Model(A, b)
     vreads = STM.virtual_reads(reads, TABLE)
     seed_off, q, k, start_off, places, per_seed = [0], [], [], [0], [], []
     for P in vreads:
-        for s in SDM.seeds(index, P, MIN_LENGTH, CAP):
+        for s in SDM.seeds(index, P, MIN_LENGTH, cap):
             q.append(s.q_start)
             k.append(s.length)
             per_seed.append((s.occ.count, s.occ.restarts, s.occ.end_total, s.occ.start_total))
@@ -247,7 +248,7 @@ def cpu(name):
             start_off.append(len(places))
         seed_off.append(len(q))
     pl = np.array(places, dtype=np.int64).reshape(-1, 3)
-    c = SimpleNamespace(name=name, A=A, b=b, reads=reads, truth=truth, vreads=vreads, L=MIN_LENGTH, cap=CAP, band=BAND, high=high,
+    c = SimpleNamespace(name=name, A=A, b=b, reads=reads, truth=truth, vreads=vreads, L=MIN_LENGTH, cap=cap, band=band, high=high,
                         rm=rm, mm=mm, graph=(labels, edges, blocks), text=index.N)
     c.seed_off, c.start_off = np.array(seed_off, dtype=np.uint64), np.array(start_off, dtype=np.uint64)
     c.q_start, c.length = np.array(q, dtype=np.uint32), np.array(k, dtype=np.uint32)
@@ -256,7 +257,7 @@ def cpu(name):
         ps[:, 3].astype(np.uint64)
     c.start_src, c.start_dst, c.start_offset = (pl[:, x].astype(np.uint32) for x in range(3))
     c.start_row, c.start_col = (x.astype(np.uint32) for x in mm.coords(pl[:, 0], pl[:, 1], pl[:, 2]))
-    c.solved = CM.solve(c.seed_off, c.q_start, c.length, c.start_off, c.start_col, BAND)
+    c.solved = CM.solve(c.seed_off, c.q_start, c.length, c.start_off, c.start_col, band)
     c.n_rows, c.first_row, c.sets = RM.seed_rows(rm, vreads, c.seed_off, c.q_start, c.length, c.start_off, c.start_src, c.start_dst,
                                                  c.start_offset)
     c.places_per_read = np.diff(c.start_off[c.seed_off.astype(np.int64)].astype(np.int64))
