@@ -230,6 +230,7 @@ static const OptKey g_opt_keys[] = {
     {"front_one_fill", &FbgOptions::front_one_fill},
     {"scan_rows_ahead", &FbgOptions::scan_rows_ahead},
     {"msd_cursors", &FbgOptions::msd_cursors},
+    {"msd_lds_batch", &FbgOptions::msd_lds_batch},
     {"path_batch_kib", &FbgOptions::path_batch_kib},
     {"byrow_max", &FbgOptions::byrow_max},
     {"byrow_lds", &FbgOptions::byrow_lds},

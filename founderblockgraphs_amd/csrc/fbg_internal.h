@@ -46,7 +46,7 @@ struct FbgOptions {
             cand_local_sort = 1, cand_lds_cap = 0, cand_sort_check = 0,
             tie_gallop = 1, cand_counts_fused = 1, tie_sample_loop = 1,
             row_count_fast = 1, twin_hash = 1, front_one_fill = 1,
-            scan_rows_ahead = 0, msd_cursors = 1,
+            scan_rows_ahead = 0, msd_cursors = 1, msd_lds_batch = 1,
             path_batch_kib = 1 << 20, byrow_max = 1024, byrow_lds = 0, graph_batch_kib = 1 << 20;
 };
 

@@ -54,6 +54,53 @@ __device__ __forceinline__ void msd_store_tile(uint8_t *tile, const uint8_t *cd,
         *reinterpret_cast<uint64_t *>(tile + kk) = codes2;
     }
 }
+// msd_store_tile with the table lookups of a thread issued as one batch (option msd_lds_batch): at the text's end every
+// byte is still looked up -- any byte is a valid index of cd -- and the end-of-text check is a select behind the reads,
+// so that no lookup sits in a branch of its own and is awaited alone.  FULL as above; the caller's choice must be the
+// same in all threads of the workgroup only where it wraps barriers (it does not here).
+template <int TILE, bool FULL>
+__device__ __forceinline__ void msd_store_tile_batched(uint8_t *tile, const uint8_t *cd, uint64_t N, uint64_t base, uint64_t raw, uint64_t raw2)
+{
+    const int k8 = threadIdx.x * 8;
+    const uint64_t p = base + k8;
+    uint32_t c[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) c[j] = cd[(raw >> (8 * j)) & 255u];
+    uint64_t codes = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) codes |= (uint64_t)((FULL || p + j < N) ? c[j] : (uint32_t)MSD_SEP) << (8 * j);
+    *reinterpret_cast<uint64_t *>(tile + k8) = codes;
+    // the 64 bytes of lookahead: threads 0 .. 7 hold them (msd_fetch_raw); their wave does 8 more lookups, in one batch too
+    if (threadIdx.x < 8) {
+        const int kk = TILE + threadIdx.x * 8;
+        const uint64_t q = base + kk;
+#pragma unroll
+        for (int j = 0; j < 8; j++) c[j] = cd[(raw2 >> (8 * j)) & 255u];
+        uint64_t codes2 = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) codes2 |= (uint64_t)((FULL || q + j < N) ? c[j] : (uint32_t)MSD_SEP) << (8 * j);
+        *reinterpret_cast<uint64_t *>(tile + kk) = codes2;
+    }
+}
+
+// sum of wsum[0 .. wv - 1], wv < NW <= 16 (the scan totals of the waves in front of this one; all 64 lanes call): lane q
+// reads wsum[q], one LDS read, and the lanes below wv are added up along their row of 16 lanes (three or four DPP
+// shifts, no LDS), instead of a loop of up to wv reads that are awaited one by one
+template <int NW>
+__device__ __forceinline__ uint32_t msd_waves_before(const uint32_t *wsum, uint32_t wv)
+{
+    static_assert(NW == 8 || NW == 16, "one row of 16 lanes");
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t v = wsum[lane & (NW - 1)];
+    v = lane < wv ? v : 0u;
+    // row_shr:d with zero fill: lane l adds lane l - d of its row
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
+    if (NW > 8) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, NW - 1);
+}
+
 template <int TILE, bool FULL = false>
 __device__ __forceinline__ void msd_load_tile(uint8_t *tile, const uint8_t *cd, const uint8_t *__restrict__ T, uint64_t N, uint64_t base)
 {

@@ -64,6 +64,7 @@ struct MsdArgs {
     uint64_t segcap;
     uint32_t *count1;                          // [MSD_NB * xs] run cursors, stretch (d, xq) at msd_cursor_index (below N < 2^31: msd_plan)
     int contig;                                // ... the cursors of an XCD's buckets side by side (option msd_cursors)
+    int batch;                                 // option msd_lds_batch: pass 1's batched body (LDS accesses of a thread in batches)
     const uint32_t *tile_start;                // [MSD_NB * xs + 1]: first tile of every stretch d * xs + xq (pass 2)
     uint64_t tile0;                            // pass 1: the first tile of this launch
     uint32_t tiles2, tiles2_x;                 // pass 2: tiles in all; tiles per XCD when the tiles are dealt to the XCDs in ranges (0: in launch order)
@@ -82,6 +83,8 @@ struct MsdArgs {
 // behind *cursor (one global atomic per non-empty digit) and leaves its start, relative to the bucket, minus the run's
 // start in the tile, in gdelta[d] (32-bit wrap-around arithmetic: the write-out adds the slot's place in the tile -- one
 // LDS lookup per slot, and these kernels are bound by their LDS operations)
+// BATCH: the totals of the waves in front come by msd_waves_before (only the MSD_NB / 64 waves that own a digit need them)
+template <bool BATCH>
 __device__ __forceinline__ void msd_scan_and_reserve(uint32_t *cnt, uint32_t *loff, uint32_t *gdelta, uint32_t *wsum, uint32_t *cursor_d)
 {
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -92,7 +95,9 @@ __device__ __forceinline__ void msd_scan_and_reserve(uint32_t *cnt, uint32_t *lo
     if (lane == 63) wsum[wv] = inc;
     __syncthreads();
     uint32_t pre = 0;
-    for (uint32_t q = 0; q < wv; q++) pre += wsum[q];
+    if (BATCH) pre = msd_waves_before<MSD_NB / 64>(wsum, wv < MSD_NB / 64 ? wv : 0u);
+    else
+        for (uint32_t q = 0; q < wv; q++) pre += wsum[q];
     if (threadIdx.x < MSD_NB) {
         loff[threadIdx.x] = pre + inc - c;
         uint32_t g = 0;
@@ -134,8 +139,8 @@ __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *
     // 128-byte lines before they leave for HBM; runs of different XCDs leave every line they share twice, in parts.
     // (The cursors of the xs stretches of a bucket do not lie together for that: msd_cursor_index.)
     const uint32_t xq = a.xs > 1 ? (blockIdx.x & (uint32_t)(a.xs - 1)) : 0u;
-    msd_scan_and_reserve(cnt, loff, gdelta, wsum,
-                         a.count1 + (threadIdx.x < MSD_NB ? msd_cursor_index(threadIdx.x, xq, (uint32_t)a.xs, MSD_NB, a.contig != 0) : 0u));
+    msd_scan_and_reserve<false>(cnt, loff, gdelta, wsum,
+                                a.count1 + (threadIdx.x < MSD_NB ? msd_cursor_index(threadIdx.x, xq, (uint32_t)a.xs, MSD_NB, a.contig != 0) : 0u));
     const int wshift = (EXT ? MSD_TILE_BITS : a.pb) + dshift;
     const uint64_t kmask = (1ull << a.kb) - 1;
     uint64_t *const obase = a.buf1 + xq * a.segcap;
@@ -160,7 +165,78 @@ __device__ __forceinline__ void msd_pack_split_body(const MsdArgs &a, uint64_t *
     if (over) atomicOr(a.flag, 2ull);
 }
 
-template <bool EXT>
+// The body of pass 1 with a thread's LDS accesses in batches (option msd_lds_batch): every phase first issues the reads of
+// all MSD_ITEMS items, then uses them, so that a wave waits once per phase and not once per item.  Same slots, same
+// buckets, same words as msd_pack_split_body.  The tile's raw text (msd_fetch_raw) is loaded by the kernel, in front of the
+// barrier that publishes the code table.  FULL: the tile and its lookahead lie inside the text (base + MSD_TILE + 64 <= N).
+// Otherwise an item beyond the text reads a harmless index (entry 0), its write is masked and it is not counted.
+template <bool FULL, bool EXT>
+__device__ __forceinline__ void msd_pack_split_batched(const MsdArgs &a, uint64_t base, uint64_t raw, uint64_t raw2, uint64_t *buf, const uint8_t *cd,
+                                                       uint32_t *cnt, uint32_t *loff, uint32_t *gdelta, uint32_t *wsum)
+{
+    uint8_t *tile = reinterpret_cast<uint8_t *>(buf);          // MSD_TILE + 64 bytes
+    const int b = a.b, K = a.K;
+    msd_store_tile_batched<MSD_TILE, FULL>(tile, cd, a.N, base, raw, raw2);
+    __syncthreads();
+    const int t0 = threadIdx.x * MSD_ITEMS;
+    uint64_t w[MSD_ITEMS];
+    msd_build_keys(tile, t0, b, EXT ? K + MSD_XSYM : K, w);
+    __syncthreads();                                            // the byte tile is done with: buf is free
+    // items of this thread inside the text: the first `mine` of them (positions ascend)
+    const uint32_t mine = FULL ? (uint32_t)MSD_ITEMS : (uint32_t)min((uint64_t)MSD_ITEMS, a.N - min(a.N, base + t0));
+    uint32_t rk[MSD_ITEMS];
+    const int dshift = a.kb + (EXT ? MSD_XBITS : 0) - MSD_DIG;
+#pragma unroll
+    for (int i = 0; i < MSD_ITEMS; i++) {
+        const bool ok = FULL || (uint32_t)i < mine;
+        rk[i] = 0;
+        if (ok) rk[i] = atomicAdd(&cnt[(uint32_t)(w[i] >> dshift)], 1u);     // (an item beyond the text must not count)
+        w[i] = EXT ? (w[i] << MSD_TILE_BITS) | (uint64_t)(t0 + i) : (w[i] << a.pb) | (base + t0 + i);
+        if (!ok) w[i] = 0;                                      // (never written; its digit below is 0)
+    }
+    __syncthreads();
+    const uint32_t xq = a.xs > 1 ? (blockIdx.x & (uint32_t)(a.xs - 1)) : 0u;    // (see msd_pack_split_body)
+    msd_scan_and_reserve<true>(cnt, loff, gdelta, wsum,
+                               a.count1 + (threadIdx.x < MSD_NB ? msd_cursor_index(threadIdx.x, xq, (uint32_t)a.xs, MSD_NB, a.contig != 0) : 0u));
+    const int wshift = (EXT ? MSD_TILE_BITS : a.pb) + dshift;
+    const uint64_t kmask = (1ull << a.kb) - 1;
+    uint64_t *const obase = a.buf1 + xq * a.segcap;
+    // regroup: the MSD_ITEMS offsets, then the writes
+    uint32_t lo[MSD_ITEMS];
+#pragma unroll
+    for (int i = 0; i < MSD_ITEMS; i++) lo[i] = loff[(uint32_t)(w[i] >> wshift)];
+#pragma unroll
+    for (int i = 0; i < MSD_ITEMS; i++)
+        if (FULL || (uint32_t)i < mine) buf[lo[i] + rk[i]] = w[i];
+    __syncthreads();
+    // write-out: the words, their digits' deltas, then the stores back to back; a run that does not fit only sets a bit
+    const uint32_t have = FULL ? (uint32_t)MSD_TILE : (uint32_t)min((uint64_t)MSD_TILE, a.N - base);
+    uint64_t x[MSD_ITEMS];
+    uint32_t gd[MSD_ITEMS];
+#pragma unroll
+    for (int r = 0; r < MSD_ITEMS; r++) {
+        const uint32_t j = threadIdx.x + r * MSD_THREADS;
+        x[r] = buf[(FULL || j < have) ? j : 0u];
+    }
+#pragma unroll
+    for (int r = 0; r < MSD_ITEMS; r++) gd[r] = gdelta[(uint32_t)(x[r] >> wshift)];
+    bool over = false;
+#pragma unroll
+    for (int r = 0; r < MSD_ITEMS; r++) {
+        const uint32_t j = threadIdx.x + r * MSD_THREADS;
+        const bool in = FULL || j < have;
+        const uint32_t d = (uint32_t)(x[r] >> wshift);
+        const uint32_t at = j + gd[r];                          // below 2^32: the host checks cap1 + N
+        const bool fits = in && at < a.segcap;
+        over = over || (in && !fits);
+        uint64_t y = x[r];
+        if (EXT) y = (((y >> MSD_TILE_BITS) & kmask) << a.pb) | (base + (y & (MSD_TILE - 1)));
+        if (fits) obase[(uint64_t)d * a.cap1 + at] = y;
+    }
+    if (__any(over) && (threadIdx.x & 63) == 0) atomicOr(a.flag, 2ull);    // once per wave, outside the loop
+}
+
+template <bool EXT, bool BATCH>
 __global__ __launch_bounds__(MSD_THREADS) void k_msd_pack_split(MsdArgs a)
 {
     __shared__ uint64_t buf[MSD_TILE];         // first the symbol codes of the tile (bytes), then the regrouped slots
@@ -168,6 +244,23 @@ __global__ __launch_bounds__(MSD_THREADS) void k_msd_pack_split(MsdArgs a)
     __shared__ uint32_t cnt[MSD_NB], loff[MSD_NB];
     __shared__ uint32_t gdelta[MSD_NB];
     __shared__ uint32_t wsum[MSD_THREADS / 64];
+    if (BATCH) {
+        // the tile's text loads go out in front of the barrier that publishes the code table: one memory latency, not two
+        const uint64_t base = ((uint64_t)blockIdx.x + a.tile0) * MSD_TILE;
+        uint64_t raw, raw2;
+        msd_fetch_raw<MSD_TILE>(a.T, a.N, base, raw, raw2);
+        if (threadIdx.x < 256) cd[threadIdx.x] = a.code[threadIdx.x];
+        if (threadIdx.x < MSD_NB) cnt[threadIdx.x] = 0;
+        __syncthreads();
+        // A tile whose MSD_TILE + 64 bytes lie inside the text takes the body without the end-of-text checks (a.batch == 2:
+        // none does, for measurements): 2642 against 2712 us with the checks on every tile, same box, traced -- with the
+        // batched loops the specialisation pays, see below for the serial ones.  Uniform over the workgroup, and told so
+        // (leaving that to the compiler once produced a wrong sort in k_msd_split): there are barriers inside.
+        const bool whole = a.batch != 2 && base + MSD_TILE + 64 <= a.N;
+        if (__builtin_amdgcn_readfirstlane((int)whole)) msd_pack_split_batched<true, EXT>(a, base, raw, raw2, buf, cd, cnt, loff, gdelta, wsum);
+        else msd_pack_split_batched<false, EXT>(a, base, raw, raw2, buf, cd, cnt, loff, gdelta, wsum);
+        return;
+    }
     if (threadIdx.x < 256) cd[threadIdx.x] = a.code[threadIdx.x];
     if (threadIdx.x < MSD_NB) cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -178,8 +271,13 @@ __global__ __launch_bounds__(MSD_THREADS) void k_msd_pack_split(MsdArgs a)
 
 static void msd_launch_pass1(const MsdArgs &a, unsigned tiles, hipStream_t st)
 {
-    if (a.xb) hipLaunchKernelGGL(k_msd_pack_split<true>, dim3(tiles), dim3(MSD_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(k_msd_pack_split<false>, dim3(tiles), dim3(MSD_THREADS), 0, st, a);
+    if (a.batch) {
+        if (a.xb) hipLaunchKernelGGL((k_msd_pack_split<true, true>), dim3(tiles), dim3(MSD_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((k_msd_pack_split<false, true>), dim3(tiles), dim3(MSD_THREADS), 0, st, a);
+    } else {
+        if (a.xb) hipLaunchKernelGGL((k_msd_pack_split<true, false>), dim3(tiles), dim3(MSD_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((k_msd_pack_split<false, false>), dim3(tiles), dim3(MSD_THREADS), 0, st, a);
+    }
 }
 
 // first tile of every stretch of pass 1 (one workgroup of 1024 threads; nseg <= 4096 stretches, four per thread)
@@ -236,7 +334,7 @@ __device__ __forceinline__ void msd_split_body(const MsdArgs &a, uint64_t *buf, 
         rk[r] = (FULL || j < have) ? atomicAdd(&cnt[(uint32_t)(w[r] >> wshift) & (MSD_NB - 1)], 1u) : 0u;
     }
     __syncthreads();
-    msd_scan_and_reserve(cnt, loff, gdelta, wsum, a.count2 + (size_t)seg * MSD_NB + (threadIdx.x < MSD_NB ? threadIdx.x : 0));
+    msd_scan_and_reserve<false>(cnt, loff, gdelta, wsum, a.count2 + (size_t)seg * MSD_NB + (threadIdx.x < MSD_NB ? threadIdx.x : 0));
 #pragma unroll
     for (int r = 0; r < MSD_ITEMS; r++) {
         const uint32_t j = threadIdx.x + r * MSD_THREADS;
@@ -557,6 +655,7 @@ static int msd_plan(fbg_ctx *ctx, const KeyGeom &g, MsdPlan *p, int *ok)
     a.buf1 = ctx->keysA.as<uint64_t>(); a.cap1 = cap1; a.xs = xs; a.segcap = cap1 / xs;
     a.tile0 = 0; a.tiles2 = 0; a.tiles2_x = 0;
     a.count1 = ctx->dp_a.as<uint32_t>(); a.contig = ctx->opt.msd_cursors != 0;
+    a.batch = (int)ctx->opt.msd_lds_batch;
     p->tile_start = a.count1 + nseg;
     a.tile_start = p->tile_start;
     a.buf2 = ctx->keysB.as<uint64_t>();

@@ -157,6 +157,10 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *                      1 (default) at q * 512 + d, so that the 64 lanes of a reserving wave add to consecutive words; 0 at
  *                      d * xs + q, the stretch's own number (the earlier placement); the words are as wide either way (32 bits
  *                      for texts below 2^32 symbols); results unchanged
+ *   msd_lds_batch      0: pass 1 of the three-pass MSD sort takes a thread's 8 items one after the other through LDS, every read
+ *                      awaited alone (the earlier loops; default 1: in phases -- the reads of all items, then their use -- with
+ *                      the text loads issued before the code table is published and the tiles inside the text translated
+ *                      without end-of-text checks; 2: as 1, every tile with the checks, measurements); results unchanged
  *   span_slow_split    workgroups that share the odd members of one large group whose pairs are all compared (0 = 32);
  *                      results unchanged
  *   path_batch_kib     fbg_pindex_chains_cigar and _chains_graph_cigar: the KiB of column history in device memory that
