@@ -222,6 +222,7 @@ static const OptKey g_opt_keys[] = {
     {"cand_local_sort", &FbgOptions::cand_local_sort},
     {"cand_lds_cap", &FbgOptions::cand_lds_cap},
     {"cand_sort_check", &FbgOptions::cand_sort_check},
+    {"cand_tail", &FbgOptions::cand_tail},
     {"tie_gallop", &FbgOptions::tie_gallop},
     {"cand_counts_fused", &FbgOptions::cand_counts_fused},
     {"tie_sample_loop", &FbgOptions::tie_sample_loop},
@@ -252,6 +253,7 @@ static const InfoKey g_info_keys[] = {
     {"sample_twins", [](const fbg_ctx &c) -> int64_t { return c.diag.sample_twins; }},
     {"cand_inversions", [](const fbg_ctx &c) -> int64_t { return c.diag.cand_inversions; }},
     {"cand_local_sorted", [](const fbg_ctx &c) -> int64_t { return c.diag.cand_local_sorted; }},
+    {"cand_tail_used", [](const fbg_ctx &c) -> int64_t { return c.diag.cand_tail_used; }},
     {"wave_runs", [](const fbg_ctx &c) -> int64_t { return c.diag.wave_runs; }},
     {"rank_lean_used", [](const fbg_ctx &c) -> int64_t { return c.diag.rank_lean_used; }},
     {"rank_lean_launched", [](const fbg_ctx &c) -> int64_t { return c.diag.rank_lean_launched; }},

@@ -43,7 +43,7 @@ struct FbgOptions {
             dp_safe_window = 0, dp_tile = 0, pure_scan = 0, gapped_rank = 0, part_tricks_off = 0, msd_sample_bins = 0, msd_min_force = 0, msd_probe = 0, msd_xcd = -1, rank_no_lean = 0, no_stream_upload = 0,
             span_scan = 0, span_key_flags = 0, span_slow_split = 0, poison = 0, dpw_matrix = 0, dp_chain1 = 0, msd_ext = 1, rows_wave = 0,
             pairs_in_scan = 1, runs_wave_min = 16, wave_list_cap = 0,
-            cand_local_sort = 1, cand_lds_cap = 0, cand_sort_check = 0,
+            cand_local_sort = 1, cand_lds_cap = 0, cand_sort_check = 0, cand_tail = 1,
             tie_gallop = 1, cand_counts_fused = 1, tie_sample_loop = 1,
             row_count_fast = 1, twin_hash = 1, front_one_fill = 1,
             scan_rows_ahead = 0, msd_cursors = 1, msd_lds_batch = 1,
@@ -90,6 +90,7 @@ struct BuildDiag {
     int64_t wave_runs = -1;      // the rank-order scan: runs that a wave each walked (k_runs_long)
     int64_t cand_inversions = -1;  // option cand_sort_check: places of the sorted candidate list that do not ascend
     int cand_local_sorted = -1;  // the candidates were sorted region by region in k_cand_sort_compact (1) / by the radix sort (0)
+    int cand_tail_used = -1;     // the scan's tail ran by member: k_cand_region, k_cand_lcp, k_cand_runs (1) / the kernels by head (0)
     int rank_lean_launched = 0;  // the rank-order scan launched k_rank_scan_lean ...
     int rank_lean_used = 0;      // ... and finished with it: the index holds its result
     int pairs_rb = -1;           // the sample sort of pairs: rank bits of its table, -1 it did not sort
@@ -200,6 +201,7 @@ struct fbg_ctx {
     DevBuf keysA, keysB, valsA, valsB, grp, flags, list, tie_list, big_groups, tmp, small, scalars;
     DevBuf msd_ext;            // 1 byte per SA slot: symbols K .. K+3 of its suffix (msd_sort.hip, 2-bit symbols)
     DevBuf wave_list;          // the runs that get a wave each (RankArgs::wl)
+    DevBuf cand_cf, cand_lp, cand_ln;   // parallel to the sorted candidates: column | run flags, LCP with the slot before, with the slot after (k_cand_lcp)
     DevBuf kargs;              // arguments a kernel reads from memory (k_rank_scan_lean) ...
     alignas(16) unsigned char kargs_host[512];   // ... and the host copy they are sent from
     uint8_t code_host[256];    // fbg_key_setup's code table on its way to the device (kept here: nothing to wait for)

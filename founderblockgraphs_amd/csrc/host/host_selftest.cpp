@@ -17,6 +17,12 @@
 // the longest probe sequence of an insertion.
 //     fbg_host_selftest twin-slots KEYS.bin BITS
 // prints the first slot of every key, one per line.
+//     fbg_host_selftest cand-tail
+// checks cand_tail.h (the rank-order scan's tail by member: rank_scan.hip's k_cand_region, k_cand_runs) against brute force: the
+// places of the members of tie groups of 2 .. 70 suffixes of a text of rows, with and without members that have fewer than K
+// symbols left; heads and sizes of the tie groups of a sorted slot array seen through candidate regions that cut them; the two
+// running minima of runs of 1 .. 200 members in one piece and in pieces of 64, 7 and 1.  Prints "cand_tail ok GROUPS HEADS RUNS"
+// or the first case that differs.
 //     fbg_host_selftest pindex-stages
 // prints the table of pindex_stage.h as it acts: "stages NAME ...", then per stage X "begin X" and the stages still done when
 // every stage was done and X begins, then per subset of done stages (bit i of MASK: stage i, marked by ps_finish) "need MASK"
@@ -27,7 +33,10 @@
 #include <vector>
 #include "fasta.hpp"
 #include "xgfa.hpp"
+#include <algorithm>
+#include <cstring>
 #include "../tie_extent.h"
+#include "../cand_tail.h"
 #include "../twin_hash.h"
 #include "../pindex_stage.h"
 
@@ -72,6 +81,128 @@ static int tie_extent_selftest()
             }
         }
     std::printf("tie_extent ok %llu\n", cases);
+    return 0;
+}
+
+static int cand_tail_selftest()
+{
+    uint64_t rng = 0x9e3779b97f4a7c15ull;
+    auto rnd = [&](uint32_t mod) -> uint32_t { rng = rng * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(rng >> 33) % mod; };
+    unsigned long long n_groups = 0, n_heads = 0, n_runs = 0;
+    // ---- tie groups: rows of n symbols over ACGT, '#' after each, 0 at the very end; K symbols make a key ------------------
+    const uint32_t K = 8, n = 60, rows = 80;
+    for (int shorts = 0; shorts < 2; shorts++)
+        for (uint32_t g = 2; g <= 70; g++) {
+            std::string T;
+            std::vector<uint32_t> pos;
+            const uint32_t col = rnd(n - K - 4);
+            std::string stretch;
+            for (uint32_t i = 0; i < K; i++) stretch += shorts ? 'A' : "ACGT"[rnd(4)];
+            for (uint32_t r = 0; r < rows; r++) {
+                std::string row;
+                for (uint32_t i = 0; i < n; i++) row += "ACGT"[rnd(4)];
+                if (shorts && r < K && r < g) {                                 // a member with r symbols left: the row ends in r times A
+                    for (uint32_t i = 0; i < r; i++) row[n - 1 - i] = 'A';
+                    if (r < n) row[n - 1 - r] = 'C';
+                    pos.push_back((uint32_t)T.size() + n - r);
+                } else if (pos.size() < g) {                                    // a member with the whole stretch, at its own column
+                    const uint32_t c = shorts ? col + r % 4 : col;
+                    row.replace(c, K, stretch);
+                    pos.push_back((uint32_t)T.size() + c);
+                }
+                T += row + '#';
+            }
+            T.back() = '\0';
+            T += std::string(64, '\0');
+            if (pos.size() != g) { std::printf("cand_tail: group of %u not built\n", g); return 1; }
+            const uint32_t row_len = n + 1;
+            auto rem_at = [&](uint32_t i) { return n - pos[i] % row_len; };
+            const uint32_t from = fbg_ct_from(g, K, rem_at);
+            if (from != (shorts ? 0u : K)) { std::printf("cand_tail: from %u, group of %u, shorts %d\n", from, g, shorts); return 1; }
+            auto less_from = [&](uint32_t x, uint32_t y, uint32_t f) { return x != y && std::strcmp(T.c_str() + pos[x] + f, T.c_str() + pos[y] + f) < 0; };
+            std::vector<uint32_t> order(g);
+            for (uint32_t i = 0; i < g; i++) order[i] = i;
+            std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return less_from(x, y, 0); });   // brute force: whole suffixes
+            std::vector<bool> taken(g, false);
+            for (uint32_t me = 0; me < g; me++) {
+                const uint32_t rank = fbg_ct_rank(me, g, [&](uint32_t j, uint32_t i) { return less_from(j, i, from); });
+                if (rank >= g || order[rank] != me || taken[rank]) { std::printf("cand_tail: rank %u of member %u, group of %u, shorts %d\n", rank, me, g, shorts); return 1; }
+                taken[rank] = true;
+            }
+            if (g <= 4) {
+                uint32_t rank[4];
+                fbg_ct_small_ranks<4>(g, [&](int x, int y) { return less_from((uint32_t)x, (uint32_t)y, from); }, rank);
+                for (uint32_t me = 0; me < g; me++)
+                    if (rank[me] >= g || order[rank[me]] != me) { std::printf("cand_tail: small rank %u of member %u, group of %u\n", rank[me], me, g); return 1; }
+            }
+            n_groups++;
+        }
+    // ---- heads and sizes through candidate regions ---------------------------------------------------------------------------
+    {
+        std::vector<uint64_t> keys;
+        std::vector<uint32_t> cand;
+        uint64_t key = 5;
+        for (uint32_t g = 1; g <= 70; g++)
+            for (uint32_t rep = 0; rep < 2; rep++) {
+                key += 1 + rnd(3);
+                const uint32_t s = rep ? 1 + rnd(3) : g;
+                for (uint32_t i = 0; i < s; i++) {
+                    if (s > 1 || rnd(2)) cand.push_back((uint32_t)keys.size());     // every member of a group; some of the others
+                    keys.push_back(key);
+                }
+            }
+        const uint64_t N = keys.size();
+        for (const uint32_t region : {7u, 64u, 100u, 4096u})
+            for (size_t r0 = 0; r0 < cand.size(); r0 += region) {
+                const uint32_t c = (uint32_t)std::min<size_t>(region, cand.size() - r0);
+                std::vector<uint64_t> local(c);
+                for (uint32_t i = 0; i < c; i++) local[i] = keys[cand[r0 + i]];
+                for (uint32_t i = 0; i < c; i++) {
+                    const uint64_t k0 = cand[r0 + i];
+                    const bool want_head = !(k0 > 0 && keys[k0 - 1] == keys[k0]) && k0 + 1 < N && keys[k0 + 1] == keys[k0];
+                    if (fbg_ct_heads_group(k0, 0, N, [&](uint64_t k) { return keys[k]; }) != want_head) { std::printf("cand_tail: head test at slot %llu\n", (unsigned long long)k0); return 1; }
+                    if (!want_head) continue;
+                    uint32_t want = 1;
+                    while (k0 + want < N && keys[k0 + want] == keys[k0]) want++;
+                    uint64_t local_reads = 0;
+                    auto key_at = [&](uint64_t k) {
+                        return fbg_ct_key_from(i, c, k0, k, [&](uint32_t j) { return (uint64_t)cand[r0 + j]; }, [&](uint32_t j) { local_reads++; return local[j]; },
+                                               [&](uint64_t q) { return keys[q]; });
+                    };
+                    const uint32_t got = fbg_tie_extent(k0, N, 8192, keys[k0], key_at);
+                    // (a group that lies in the region whole is measured on the region's copy: its second member at the least)
+                    if (got != want || (i + want <= c && local_reads == 0)) { std::printf("cand_tail: size %u of the group at slot %llu, want %u, region %u, %llu local reads\n", got, (unsigned long long)k0, want, region, (unsigned long long)local_reads); return 1; }
+                    n_heads++;
+                }
+            }
+    }
+    // ---- running minima of runs, in pieces --------------------------------------------------------------------------------------
+    for (uint32_t len = 1; len <= 200; len++) {
+        std::vector<uint32_t> lp(len + 1);
+        for (auto &v : lp) v = rnd(len % 3 ? 50 : 5);
+        std::vector<uint32_t> want(len);
+        for (uint32_t i = 0; i < len; i++) {
+            uint32_t a = FBG_CT_NONE, b = FBG_CT_NONE;
+            for (uint32_t j = 0; j <= i; j++) a = std::min(a, lp[j]);
+            for (uint32_t j = i + 1; j <= len; j++) b = std::min(b, lp[j]);
+            want[i] = std::max(a, b) + 1;
+        }
+        for (const uint32_t piece : {len, 64u, 7u, 1u}) {
+            std::vector<uint32_t> pm(len, 12345), got(len, 0);
+            uint32_t carry = FBG_CT_NONE;
+            for (uint32_t i0 = 0; i0 < len; i0 += piece)
+                carry = fbg_ct_min_forward(i0, std::min(len, i0 + piece), carry, [&](uint32_t i) { return lp[i]; }, [&](uint32_t i, uint32_t v) { pm[i] = v; });
+            carry = FBG_CT_NONE;
+            for (uint32_t i0 = (len - 1) / piece * piece;; i0 -= piece) {
+                carry = fbg_ct_min_backward(i0, std::min(len, i0 + piece), carry, [&](uint32_t i) { return lp[i + 1]; }, [&](uint32_t i) { return pm[i]; },
+                                            [&](uint32_t i, uint32_t g) { got[i] = g; });
+                if (i0 == 0) break;
+            }
+            if (got != want) { std::printf("cand_tail: run of %u in pieces of %u differs\n", len, piece); return 1; }
+            n_runs++;
+        }
+    }
+    std::printf("cand_tail ok %llu %llu %llu\n", n_groups, n_heads, n_runs);
     return 0;
 }
 
@@ -139,6 +270,7 @@ int main(int argc, char **argv)
     if (argc == 4 && (std::string(argv[1]) == "twin-hash" || std::string(argv[1]) == "twin-slots"))
         return twin_hash_selftest(argv[2], std::atoi(argv[3]), std::string(argv[1]) == "twin-slots");
     if (argc == 2 && std::string(argv[1]) == "tie-extent") return tie_extent_selftest();
+    if (argc == 2 && std::string(argv[1]) == "cand-tail") return cand_tail_selftest();
     if (argc == 2 && std::string(argv[1]) == "pindex-stages") return pindex_stages_selftest();
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s FASTA GAP_LIMIT ELASTIC PATHS OUT.gfa [BOUNDARY ...]\n", argv[0]);

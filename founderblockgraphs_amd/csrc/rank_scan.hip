@@ -21,6 +21,10 @@
 //                   (fbg.cpp:1644-1678) by one forward and one backward walk.
 //   k_runs_long     without partitions: runs of 16 members and more, noted by k_runs, get a wave each -- the row ends make
 //                   such runs, and a thread's walk through one is what the whole step would wait for.
+//   k_cand_region, k_cand_lcp, k_cand_runs, k_cand_runs_long
+//                   behind the lean scan (option cand_tail) the same work by member instead of by head: a workgroup per
+//                   region sorts it and orders the tie groups it heads, every LCP is computed once by candidate, and the
+//                   run heads take their minima over those arrays (cand_tail.h).
 //   k_rank_finish   f[x] / v[j] from the column maxima (fbg.cpp:1656-1672 with rank_i(x) = x, tot_i = n).
 //
 // Keys use the compact coding of suffix_sort.hip: a separator ('#', sentinel) and everything behind it inside a
@@ -41,6 +45,7 @@
 
 #include "rank_common.h"
 #include "tie_extent.h"
+#include "cand_tail.h"
 
 // k_rank_scan stages a chunk of 256 slots (+ RS_HALO either side) in LDS as (key, column): all the looking around
 // that tie groups need happens there.
@@ -868,7 +873,8 @@ template <int L> __global__ void k_tie_groups(RankArgs a, uint64_t T, int by_lis
 // symbol.  Text order is therefore: by symbols left (capped at K) first.  Members with the same number left sit in
 // one MSA column: a run whose inner order has no influence on any extension (the LCPs inside exceed those at its
 // two ends, fbg.cpp:1644-1656) -- left as it is unless `exact` (fbg_index_download wants the true suffix array).
-// The members with K real symbols are ordered by their text; more than 64 of those -> fallback flag.
+// The members with K real symbols are ordered by their text; more than 64 of those -> fallback flag, or with exact = 2 the
+// whole group as under exact = 1.
 // One workgroup per group.
 template <int L> __global__ __launch_bounds__(256) void k_tie_big(RankArgs a, int exact)
 {
@@ -900,7 +906,9 @@ template <int L> __global__ __launch_bounds__(256) void k_tie_big(RankArgs a, in
         q_start = offs[a.K];
     }
     __syncthreads();
-    if (!exact) {
+    // exact = 2 (behind the lean scan): more than 64 members with K real symbols -- a stretch that many rows share -- are no
+    // reason to give the scan up: the ranks below order such a group like any other
+    if (exact == 0 || (exact == 2 && q_count <= 64)) {
         for (uint32_t i = threadIdx.x; i < s; i += blockDim.x) {
             const uint32_t dst = atomicAdd(&offs[cls[i]], 1u);
             rs_set_pos<L>(a, k0 + dst, member(i));
@@ -940,15 +948,20 @@ template <int L> __global__ __launch_bounds__(256) void k_tie_big(RankArgs a, in
     }
 }
 
+// LCP of the suffixes of two neighbouring SA slots, x before y
+__device__ __forceinline__ uint32_t rs_pair_lcp(const RankArgs &a, const Slot &x, const Slot &y)
+{
+    if (x.key != y.key) return min(min(rs_key_lcp(x.key, y.key, a.b, a.key_bits), x.rem), y.rem);
+    const uint32_t from = (x.rem < (uint32_t)a.K || y.rem < (uint32_t)a.K) ? 0u : (uint32_t)a.K;
+    return fbg_clamp_lcp(fbg_extend_match(a.T, (uint64_t)x.pos + from, (uint64_t)y.pos + from, 0) + from);
+}
+
 // LCP of the suffixes in SA slots k-1 and k (final order, or a member of an unordered small tie group next to a
 // slot outside it: all its members have K symbols left, the result does not depend on which one it is)
 template <int L> __device__ __forceinline__ uint32_t rs_slot_lcp(const RankArgs &a, uint64_t k)
 {
     if (k == (a.first_part ? a.own_lo : 0) || k >= (a.last_part ? a.own_hi : a.N)) return 0;   // no such neighbour
-    const Slot x = rs_slot<L>(a, k - 1), y = rs_slot<L>(a, k);
-    if (x.key != y.key) return min(min(rs_key_lcp(x.key, y.key, a.b, a.key_bits), x.rem), y.rem);
-    const uint32_t from = (x.rem < (uint32_t)a.K || y.rem < (uint32_t)a.K) ? 0u : (uint32_t)a.K;
-    return fbg_clamp_lcp(fbg_extend_match(a.T, (uint64_t)x.pos + from, (uint64_t)y.pos + from, 0) + from);
+    return rs_pair_lcp(a, rs_slot<L>(a, k - 1), rs_slot<L>(a, k));
 }
 
 // test / debugging aid (fbg_index_download): suffix array, its inverse and the neighbour LCPs by text position
@@ -1047,6 +1060,305 @@ template <int L> __global__ __launch_bounds__(64) void k_runs_long(RankArgs a)
     if (lane == 0) rs_update(a, col, best);
 }
 
+// ---- the tail by member (option cand_tail; packed slots, no partitions, regions sorted in LDS; the logic is cand_tail.h's) ----
+// k_cand_sort_compact and k_tie_groups in one kernel, a workgroup per region: the region sorted in LDS and written out, the
+// word of every candidate kept beside it, a head's group measured on those (fbg_ct_key_from: the slots themselves answer past
+// the region's end -- groups span regions, the head's workgroup owns the whole group and is the only one to write its
+// positions; other workgroups read the keys of those slots only, which no write changes).  Groups of up to RC_SMALL members
+// are ordered by their head's thread in registers, those of up to 64 by a wave with a lane per member (rank = number of
+// smaller members, as k_tie_big's exact mode), larger ones go to k_tie_big as from k_tie_groups.  No private array is indexed
+// at run time: no scratch.  Every loop is bounded by the region's count, a group's cap or the text's end.
+#define RC_SMALL 4
+
+// is the suffix at po smaller than the one at pc?  wo / wc: their first 8 bytes (fbg_load8), loaded by the caller ahead of use
+__device__ __forceinline__ bool rc_text_less(const uint8_t *__restrict__ T, uint64_t po, uint64_t pc, uint64_t wo, uint64_t wc)
+{
+    const uint64_t x = wo ^ wc;
+    if (x == 0) {
+        const uint32_t h = fbg_extend_match(T, po, pc, 8);
+        return T[po + h] < T[pc + h];
+    }
+    const uint32_t sh = (uint32_t)(__ffsll((unsigned long long)x) - 1) & ~7u;      // the first byte that differs
+    return ((wo >> sh) & 0xff) < ((wc >> sh) & 0xff);
+}
+
+// a wave's own LDS writes, visible to its other lanes' reads that follow
+__device__ __forceinline__ void rc_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// one compare-exchange stage of the bitonic network over pairs [t0, t1) step `step`: pair t is (i, i + j), i = t with a zero bit
+// put in at j's place
+__device__ __forceinline__ void rc_bitonic_pairs(uint32_t *buf, uint32_t base, uint32_t t0, uint32_t t1, uint32_t step, uint32_t j, uint32_t k)
+{
+    for (uint32_t t = t0; t < t1; t += step) {
+        const uint32_t i = base + (((t & ~(j - 1)) << 1) | (t & (j - 1))), l = i + j;
+        const uint32_t x = buf[i], y = buf[l];
+        if ((x > y) == ((i & k) == 0)) { buf[i] = y; buf[l] = x; }
+    }
+}
+
+// LDS (dynamic; the host knows the largest count, cap): the words of a region's first wcap entries, its slots padded to a power
+// of two (pmax at most), the entries that head a group (at most every other one) and the groups that get a wave (lcap).  An
+// entry past wcap -- the few regions that hold the row ends -- finds its word among the slots, like a slot past the region.
+#define RC_WORDS 1024
+__global__ __launch_bounds__(256) void k_cand_region(RankArgs a, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ offsets,
+                                                     uint32_t *__restrict__ out, int gallop, uint32_t cap, uint32_t pmax, uint32_t wcap, uint32_t lcap)
+{
+    constexpr int L = FBG_SLOTS_PACKED;
+    extern __shared__ uint64_t rc_lds[];
+    uint64_t *wbuf = rc_lds;
+    uint32_t *buf = reinterpret_cast<uint32_t *>(wbuf + wcap);
+    uint32_t *glist = buf + pmax;
+    uint16_t *hlist = reinterpret_cast<uint16_t *>(glist + lcap);
+    __shared__ uint32_t gcount, hcount;
+    const uint32_t c = min(min(counts[blockIdx.x], a.region), cap), o = offsets[blockIdx.x];
+    if (c == 0) return;
+    const uint32_t wc = min(c, wcap), hcap = cap / 2 + 2;
+    uint32_t P = 2;
+    while (P < c) P <<= 1;                                              // (<= pmax: the power of two at or above cap)
+    for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) buf[i] = i < c ? a.cand[(size_t)blockIdx.x * a.region + i] : 0xffffffffu;
+    if (threadIdx.x == 0) { gcount = 0; hcount = 0; }
+    __syncthreads();
+    // k_cand_sort_compact's network, scheduled by wave: a wave owns a quarter of the slots (all of them below 256), and only the
+    // stages whose partners lie a quarter and more apart -- three of them -- go across the workgroup, between barriers
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t Q = P >= 256 ? P >> 2 : P;
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            if (j >= Q) {
+                __syncthreads();
+                rc_bitonic_pairs(buf, 0, threadIdx.x, P >> 1, blockDim.x, j, k);
+                __syncthreads();
+            } else if (wv * Q < P) {
+                rc_bitonic_pairs(buf, wv * Q, lane, Q >> 1, 64, j, k);
+                rc_wave_sync();
+            }
+        }
+    __syncthreads();
+    // the sorted slots out; a candidate's word and its two neighbours', four entries' twelve loads in flight together (an entry
+    // past the count repeats the last, a neighbour past the array the slot itself); the heads of groups onto a list
+    for (uint32_t i0 = threadIdx.x; i0 < c; i0 += 4 * blockDim.x) {
+        uint64_t k[4], w[4], wp[4], wn[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) k[q] = buf[min(i0 + (uint32_t)q * blockDim.x, c - 1)];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            w[q] = a.keys[k[q]];
+            wp[q] = a.keys[k[q] > 0 ? k[q] - 1 : k[q]];
+            wn[q] = a.keys[k[q] + 1 < a.N ? k[q] + 1 : k[q]];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t i = i0 + (uint32_t)q * blockDim.x;
+            if (i >= c) continue;
+            out[o + i] = (uint32_t)k[q];
+            if (i < wc) wbuf[i] = w[q];
+            const uint64_t key = w[q] >> a.pb;
+            if (!(k[q] > 0 && (wp[q] >> a.pb) == key) && k[q] + 1 < a.N && (wn[q] >> a.pb) == key) {
+                const uint32_t e = atomicAdd(&hcount, 1u);
+                if (e < hcap) hlist[e] = (uint16_t)i;
+                else a.counters[1] = 1;                                     // (cannot be: a head's successor is no head)
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t n_heads = min(hcount, hcap);
+    for (uint32_t h = threadIdx.x; h < n_heads; h += blockDim.x) {
+        const uint32_t i = hlist[h];
+        const uint64_t k0 = buf[i], w0 = i < wc ? wbuf[i] : a.keys[k0], key = w0 >> a.pb;
+        auto word_at = [&](uint32_t d) -> uint64_t {                    // the word of slot k0 + d
+            const uint32_t j = i + d;
+            return j < wc && buf[j] == k0 + d ? wbuf[j] : a.keys[k0 + d];
+        };
+        auto key_at = [&](uint64_t k) -> uint64_t {
+            return fbg_ct_key_from(i, wc, k0, k, [&](uint32_t j) { return (uint64_t)buf[j]; }, [&](uint32_t j) { return wbuf[j] >> a.pb; },
+                                   [&](uint64_t s) { return a.keys[s] >> a.pb; });
+        };
+        uint32_t s = 1;
+        if (gallop) s = fbg_tie_extent(k0, a.N, RS_BIG_MEMBERS, key, key_at);
+        else while (k0 + s < a.N && s <= RS_BIG_MEMBERS && key_at(k0 + s) == key) s++;
+        if (s > 64) {
+            if (s > RS_BIG_MEMBERS) { a.counters[1] = 1; continue; }
+            const unsigned long long e = atomicAdd(&a.counters[5], 1ull);
+            if (e >= RS_BIG_GROUPS) { a.counters[1] = 1; continue; }
+            a.big[2 * e] = (uint32_t)k0;
+            a.big[2 * e + 1] = s;
+            continue;
+        }
+        if (s > RC_SMALL) {
+            const uint32_t e = atomicAdd(&gcount, 1u);
+            if (e < lcap) glist[e] = i | s << 16;
+            else a.counters[1] = 1;                                         // (cannot be: such groups do not overlap)
+            continue;
+        }
+        // 2 .. RC_SMALL members, in registers: positions, where the comparison starts, the first 8 bytes of every member ahead
+        // of the comparisons, every pair compared once
+        uint32_t p[RC_SMALL];
+        uint64_t w8[RC_SMALL];
+#pragma unroll
+        for (int d = 0; d < RC_SMALL; d++) p[d] = (uint32_t)(((uint32_t)d < s ? word_at(d) : w0) & a.pmask);
+        uint32_t from = (uint32_t)a.K;
+#pragma unroll
+        for (int d = 0; d < RC_SMALL; d++)
+            if (rs_rem<L>(a, p[d]) < (uint32_t)a.K) from = 0;               // (fbg_ct_from; slots past the group repeat the head)
+#pragma unroll
+        for (int d = 0; d < RC_SMALL; d++) w8[d] = fbg_load8(a.T, (uint64_t)p[d] + from);
+        uint32_t rank[RC_SMALL];
+        fbg_ct_small_ranks<RC_SMALL>(s, [&](int x, int y) { return rc_text_less(a.T, (uint64_t)p[x] + from, (uint64_t)p[y] + from, w8[x], w8[y]); }, rank);
+#pragma unroll
+        for (int d = 0; d < RC_SMALL; d++)
+            if ((uint32_t)d < s) a.keys[k0 + rank[d]] = key << a.pb | p[d];
+    }
+    __syncthreads();
+    // the groups of RC_SMALL + 1 .. 64 members: a wave each, a lane per member
+    const uint32_t groups = min(gcount, lcap);
+    for (uint32_t e = threadIdx.x >> 6; e < groups; e += blockDim.x >> 6) {
+        const uint32_t i = glist[e] & 0xffffu, s = glist[e] >> 16;
+        const uint64_t k0 = buf[i];
+        const uint32_t d = lane < s ? lane : 0u, j = i + d;                // (lanes past the group repeat the head: every load is valid)
+        const uint64_t w = j < wc && buf[j] == k0 + d ? wbuf[j] : a.keys[k0 + d];
+        const uint32_t p = (uint32_t)(w & a.pmask);
+        const uint32_t from = __ballot(rs_rem<L>(a, p) < (uint32_t)a.K) ? 0u : (uint32_t)a.K;
+        const uint64_t w8 = fbg_load8(a.T, (uint64_t)p + from);
+        const uint32_t rank = fbg_ct_rank(lane, s, [&](uint32_t x, uint32_t) {
+            const uint32_t px = (uint32_t)__shfl((int)p, (int)x, 64);
+            const uint64_t wx = (uint64_t)(uint32_t)__shfl((int)(uint32_t)w8, (int)x, 64) | (uint64_t)(uint32_t)__shfl((int)(uint32_t)(w8 >> 32), (int)x, 64) << 32;
+            return lane < s && x != lane && rc_text_less(a.T, (uint64_t)px + from, (uint64_t)p + from, wx, w8);   // (after the exchange: all lanes take part in it)
+        });
+        if (lane < s) a.keys[k0 + rank] = (w & ~a.pmask) | p;
+    }
+}
+
+// One thread per candidate: the column of its slot, whether it begins and ends a same-column run, and its LCP with the slot
+// before it, into arrays parallel to cand[]; the LCP with the slot after it only where that slot is not the next candidate
+// (there it is that candidate's).  Every LCP of the tail is computed here, once.
+#define RC_HEAD 0x80000000u
+#define RC_TAIL 0x40000000u
+#define RC_COL 0x3fffffffu
+__global__ __launch_bounds__(256) void k_cand_lcp(RankArgs a, uint64_t T, uint32_t *__restrict__ cf, uint32_t *__restrict__ lp, uint32_t *__restrict__ ln)
+{
+    constexpr int L = FBG_SLOTS_PACKED;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    const uint64_t k = a.cand[t];
+    const uint64_t next_cand = t + 1 < T ? (uint64_t)a.cand[t + 1] : ~0ull;
+    const bool has_p = k > 0, has_n = k + 1 < a.N;
+    const uint64_t w = a.keys[k], wp = has_p ? a.keys[k - 1] : 0ull, wn = has_n ? a.keys[k + 1] : 0ull;
+    auto slot_of = [&](uint64_t word) {
+        Slot s;
+        s.key = word >> a.pb;
+        s.pos = word & a.pmask;
+        s.rem = rs_rem<L>(a, s.pos);
+        s.col = rs_col_of_rem(a, s.rem);
+        return s;
+    };
+    const Slot y = slot_of(w), x = slot_of(wp), z = slot_of(wn);
+    uint32_t f = y.col;
+    if (!(has_p && x.col == y.col)) f |= RC_HEAD;
+    if (!(has_n && z.col == y.col)) f |= RC_TAIL;
+    cf[t] = f;
+    lp[t] = has_p ? rs_pair_lcp(a, x, y) : 0u;
+    if (next_cand != k + 1) ln[t] = has_n ? rs_pair_lcp(a, y, z) : 0u;
+}
+
+// the LCP of the run's last member (candidate t + len - 1) with the slot after it
+__device__ __forceinline__ uint32_t rc_end_lcp(const RankArgs &a, uint64_t T, uint64_t t, uint64_t len, const uint32_t *__restrict__ lp,
+                                               const uint32_t *__restrict__ ln)
+{
+    const uint64_t e = t + len;
+    return e < T && a.cand[e] == a.cand[e - 1] + 1 ? lp[e] : ln[e - 1];
+}
+
+// One thread per candidate; the head of a same-column run (its members are consecutive candidates) takes the two running minima
+// over lp[] (fbg_ct_min_forward / _backward) and raises the column's maximum, as k_runs does.  A run of runs_wave_min members
+// and more is noted for k_cand_runs_long while the list has room.
+__global__ __launch_bounds__(256) void k_cand_runs(RankArgs a, uint64_t T, const uint32_t *__restrict__ cf, const uint32_t *__restrict__ lp,
+                                                   const uint32_t *__restrict__ ln, uint32_t *__restrict__ pm)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    const uint32_t f0 = cf[t], col = f0 & RC_COL;
+    if (col == (uint32_t)a.n || !(f0 & RC_HEAD)) return;             // '#' / sentinel: not a row pointer; inside a run
+    // the run's length: the tail flags, four candidates at a time
+    const uint64_t room = T - t;
+    uint64_t len = 0;
+    bool tried = false;
+    for (uint64_t i0 = 0; i0 < room && !len; i0 += 4) {
+        uint32_t g[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) g[q] = cf[min(t + i0 + q, T - 1)];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (!len && i0 + q < room && (g[q] & RC_TAIL)) len = i0 + q + 1;
+        const uint64_t known = len ? len : i0 + 5;                     // members the run is known to have by now
+        if (!tried && a.runs_wave_min >= 2 && known >= a.runs_wave_min) {
+            tried = true;                                              // a long run: a wave walks it, unless the list is full
+            const unsigned long long e = atomicAdd(&a.counters[7], 1ull);
+            if (e < a.wl_cap) { a.wl[2 * e] = (uint32_t)t; a.wl[2 * e + 1] = a.cand[t]; return; }
+        }
+    }
+    if (!len) len = room;
+    const uint32_t n_mem = (uint32_t)len;
+    fbg_ct_min_forward(0u, n_mem, FBG_CT_NONE, [&](uint32_t i) { return lp[t + i]; }, [&](uint32_t i, uint32_t v) { pm[t + i] = v; });
+    const uint32_t end = rc_end_lcp(a, T, t, len, lp, ln);
+    uint32_t best = 0;
+    fbg_ct_min_backward(0u, n_mem, FBG_CT_NONE, [&](uint32_t i) { return i + 1 < n_mem ? lp[t + i + 1] : end; },
+                        [&](uint32_t i) { return pm[t + i]; }, [&](uint32_t, uint32_t g) { best = max(best, g); });
+    rs_update(a, col, best);                                           // (the members share their column)
+}
+
+// The runs k_cand_runs noted, a wave each: k_runs_long over the LCP arrays (no LCP computed again).
+__global__ __launch_bounds__(64) void k_cand_runs_long(RankArgs a, uint64_t T, const uint32_t *__restrict__ cf, const uint32_t *__restrict__ lp,
+                                                       const uint32_t *__restrict__ ln, uint32_t *__restrict__ pm)
+{
+    if (blockIdx.x >= a.counters[7]) return;                            // (the grid is wl_cap blocks)
+    const uint64_t t = a.wl[2 * blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t col = cf[t] & RC_COL;
+    uint64_t len = 0;
+    uint32_t carry = FBG_CT_NONE;
+    for (uint64_t c0 = 0; t + c0 < T; c0 += 64) {                      // forward: minimum of LCP[head .. member]
+        const uint64_t idx = t + c0 + lane;
+        const bool valid = idx < T;
+        const uint32_t f = valid ? cf[idx] : 0u;
+        const unsigned long long stop = __ballot(valid && (f & RC_TAIL)), inval = __ballot(!valid);
+        const uint32_t first_stop = stop ? (uint32_t)__ffsll((long long)stop) - 1 : 64u, first_inv = inval ? (uint32_t)__ffsll((long long)inval) - 1 : 64u;
+        const uint32_t cnt = min(min(first_stop + 1, first_inv), 64u);  // members among these 64 candidates
+        uint32_t v = lane < cnt ? lp[idx] : FBG_CT_NONE;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(v, d, 64);
+            if (lane >= (uint32_t)d) v = min(v, o);
+        }
+        v = min(v, carry);
+        if (lane < cnt) pm[idx] = v;
+        carry = __shfl(v, 63, 64);
+        len += cnt;
+        if (first_stop < 64 || first_inv < 64) break;
+    }
+    if (len == 0) return;
+    const uint32_t end = rc_end_lcp(a, T, t, len, lp, ln);
+    uint32_t best = 0;
+    carry = FBG_CT_NONE;
+    for (uint64_t c0 = (len - 1) / 64 * 64;; c0 -= 64) {               // backward: minimum of LCP[member + 1 .. tail + 1], extension
+        const uint64_t i = c0 + lane;
+        uint32_t v = i < len ? (i + 1 < len ? lp[t + i + 1] : end) : FBG_CT_NONE;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_down(v, d, 64);
+            if (lane + (uint32_t)d < 64) v = min(v, o);
+        }
+        v = min(v, carry);
+        if (i < len) best = max(best, max(pm[t + i], v) + 1);          // (pm[t + i]: this lane's own store)
+        carry = __shfl(v, 0, 64);
+        if (c0 == 0) break;
+    }
+    for (int d = 32; d > 0; d >>= 1) best = max(best, (uint32_t)__shfl_xor(best, d, 64));
+    if (lane == 0) rs_update(a, col, best);
+}
+
 struct FinishArgs {
     const uint32_t *gmax;
     uint64_t n, x0, x1;
@@ -1126,9 +1438,22 @@ static int rs_wave_list(fbg_ctx *ctx, RankArgs &a)
     return FBG_OK;
 }
 
+// option cand_sort_check: count the places of the sorted list that do not ascend (a host round trip)
+static int rs_check_sorted(fbg_ctx *ctx, const uint32_t *sorted, uint64_t T)
+{
+    hipStream_t st = ctx->stream;
+    unsigned long long *d_inv = &fbg_scalars(ctx)->cand_inversions, inv = 0;
+    FBG_HIP_TRY(ctx, hipMemsetAsync(d_inv, 0, sizeof(inv), st));
+    hipLaunchKernelGGL(k_cand_inversions, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, sorted, T, d_inv);
+    FBG_HIP_TRY(ctx, hipMemcpyAsync(&inv, d_inv, sizeof(inv), hipMemcpyDeviceToHost, st));
+    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->diag.cand_inversions = (int64_t)inv;
+    return FBG_OK;
+}
+
 // The candidates, flat and unsorted in dp_e (or sorted in dp_a already: `sorted_already`): sorted (SA order), tie groups put in
-// final order.  On return a.cand / a.pm name the sorted list and its scratch.
-static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T, bool sorted_already, int *launches)
+// final order (big_mode: k_tie_big's `exact`, 0 or 2).  On return a.cand / a.pm name the sorted list and its scratch.
+static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T, bool sorted_already, int big_mode, int *launches)
 {
     hipStream_t st = ctx->stream;
     FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
@@ -1139,19 +1464,36 @@ static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T
         FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
             return rocprim::radix_sort_keys(tmp, bytes, flat, sorted, (size_t)T, 0u, 32u, st);
         }));
-    if (ctx->opt.cand_sort_check) {
-        unsigned long long *d_inv = &fbg_scalars(ctx)->cand_inversions, inv = 0;
-        FBG_HIP_TRY(ctx, hipMemsetAsync(d_inv, 0, sizeof(inv), st));
-        hipLaunchKernelGGL(k_cand_inversions, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, sorted, T, d_inv);
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(&inv, d_inv, sizeof(inv), hipMemcpyDeviceToHost, st));
-        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-        ctx->diag.cand_inversions = (int64_t)inv;
-    }
+    if (ctx->opt.cand_sort_check) FBG_TRY(rs_check_sorted(ctx, sorted, T));
     a.cand = sorted;
     a.pm = ctx->dp_b.as<uint32_t>();
     RS_LAUNCH(k_tie_groups, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T, 1, ctx->opt.tie_gallop != 0 ? 1 : 0);
-    RS_LAUNCH(k_tie_big, layout, dim3(RS_BIG_GROUPS), dim3(256), st, a, 0);
+    RS_LAUNCH(k_tie_big, layout, dim3(RS_BIG_GROUPS), dim3(256), st, a, big_mode);
     *launches += 3;
+    return FBG_OK;
+}
+
+// The candidates still in the regions of the lean scan's workgroups, each of which fits k_cand_region's LDS: sorted, written out
+// at their offsets and their tie groups put in final order by one kernel (option cand_tail; mx: the largest region's count, at
+// most RS_CAND_LDS).  On return a.cand / a.pm name the sorted list and its scratch, as after rs_order_candidates.
+static int rs_region_groups(fbg_ctx *ctx, RankArgs &a, unsigned rs_blocks, uint64_t T, uint32_t mx, const uint32_t *d_counts, const uint32_t *d_offs, int *launches)
+{
+    hipStream_t st = ctx->stream;
+    FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
+    FBG_TRY(fbg_reserve(ctx, ctx->dp_b, T * 4));
+    uint32_t *sorted = ctx->dp_a.as<uint32_t>();
+    // LDS by the largest region: the slots padded to a power of two, the words of the first RC_WORDS entries, the heads (every
+    // other entry at most) and a list that holds every group of more than RC_SMALL members a region can head
+    uint32_t pmax = 2;
+    while (pmax < mx) pmax <<= 1;
+    const uint32_t wcap = std::min<uint32_t>(mx, RC_WORDS), lcap = mx / (RC_SMALL + 1) + 1;
+    const size_t lds = (size_t)wcap * 8 + (size_t)pmax * 4 + (size_t)lcap * 4 + (size_t)(mx / 2 + 2) * 2;
+    hipLaunchKernelGGL(k_cand_region, dim3(rs_blocks), dim3(256), lds, st, a, d_counts, d_offs, sorted, ctx->opt.tie_gallop != 0 ? 1 : 0, mx, pmax, wcap, lcap);
+    if (ctx->opt.cand_sort_check) FBG_TRY(rs_check_sorted(ctx, sorted, T));
+    a.cand = sorted;
+    a.pm = ctx->dp_b.as<uint32_t>();
+    hipLaunchKernelGGL(k_tie_big<FBG_SLOTS_PACKED>, dim3(RS_BIG_GROUPS), dim3(256), 0, st, a, 2);
+    *launches += 2;
     return FBG_OK;
 }
 
@@ -1185,6 +1527,7 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
                       rs_lean_setup(a, a.pb, rs_blocks, &lf);
     ctx->diag.rank_lean_launched = lean ? 1 : 0;
     if (ctx->opt.cand_sort_check) ctx->diag.cand_inversions = 0;
+    ctx->diag.cand_tail_used = 0;
     if (lean)
     {
         // the symbols after the key from the MSD sort (these very slots, 2-bit symbols): the pairs carry a code in their spare
@@ -1263,6 +1606,10 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
             const uint32_t lds_cap = cap_opt > 0 && cap_opt < RS_CAND_LDS ? (uint32_t)cap_opt : RS_CAND_LDS;
             const bool local = lean && ctx->opt.cand_local_sort && mx <= lds_cap;
             ctx->diag.cand_local_sorted = local ? 1 : 0;
+            // the tail by member: packed slots (the lean scan's), columns that leave the two flag bits of k_cand_lcp free
+            const bool tail = local && ctx->opt.cand_tail != 0 && a.n <= RC_COL;
+            ctx->diag.cand_tail_used = tail ? 1 : 0;
+            if (tail) return rs_region_groups(ctx, a, rs_blocks, T, mx, d_counts, d_offs, launches);
             if (local) {
                 FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
                 hipLaunchKernelGGL(k_cand_sort_compact, dim3(rs_blocks), dim3(256), 0, st, a.cand, d_counts, d_offs, region, ctx->dp_a.as<uint32_t>());
@@ -1270,7 +1617,7 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
                 FBG_TRY(fbg_reserve(ctx, ctx->dp_e, T * 4));
                 hipLaunchKernelGGL(k_cand_compact, dim3(rs_blocks), dim3(256), 0, st, a.cand, d_counts, d_offs, region, ctx->dp_e.as<uint32_t>());
             }
-            FBG_TRY(rs_order_candidates(ctx, a, layout, T, local, launches));
+            FBG_TRY(rs_order_candidates(ctx, a, layout, T, local, lean ? 2 : 0, launches));
         }
         return FBG_OK;
     }();
@@ -1351,7 +1698,20 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     if (reject) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
     FBG_TRY(rs_classify(ctx, a, layout, &T, &launches));
     if (T == ~0ull) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);      // a region overflowed: record path
-    if (T > 0) {
+    if (T > 0 && ctx->diag.cand_tail_used == 1) {
+        // every LCP once, by candidate; then the runs' minima over those arrays
+        // (k_tie_simple may be running on the aux stream: an error return joins it first, as in rs_classify)
+        int rc = fbg_reserve(ctx, ctx->cand_cf, T * 4);
+        if (rc == FBG_OK) rc = fbg_reserve(ctx, ctx->cand_lp, T * 4);
+        if (rc == FBG_OK) rc = fbg_reserve(ctx, ctx->cand_ln, T * 4);
+        if (rc != FBG_OK) { (void)rs_join(ctx); return rc; }
+        uint32_t *cf = ctx->cand_cf.as<uint32_t>(), *lp = ctx->cand_lp.as<uint32_t>(), *ln = ctx->cand_ln.as<uint32_t>();
+        hipLaunchKernelGGL(k_cand_lcp, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, a, T, cf, lp, ln);
+        hipLaunchKernelGGL(k_cand_runs, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, a, T, cf, lp, ln, a.pm);
+        launches += 2;
+        if (a.runs_wave_min) { hipLaunchKernelGGL(k_cand_runs_long, dim3(a.wl_cap), dim3(64), 0, st, a, T, cf, lp, ln, a.pm); launches++; }
+    }
+    else if (T > 0) {
         RS_LAUNCH(k_runs, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T);
         launches++;
         if (a.runs_wave_min) { RS_LAUNCH(k_runs_long, layout, dim3(a.wl_cap), dim3(64), st, a); launches++; }

@@ -131,6 +131,12 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  *                      largest region fits); results unchanged
  *   cand_lds_cap       the largest region count that sort takes (0 = 4096, the most; tests)
  *   cand_sort_check    1: the sorted candidate list is checked to ascend ("cand_inversions"; debugging, one more wait)
+ *   cand_tail          0: behind the lean scan the sorted regions, their tie groups and the same-column runs are worked by the
+ *                      kernels that give a thread to every group's and every run's head (k_cand_sort_compact, k_tie_groups,
+ *                      k_runs, k_runs_long).  Default 1, where the regions are sorted in LDS (cand_local_sort): one kernel per
+ *                      region sorts it, keeps the candidates' words in LDS and orders the tie groups it heads (k_cand_region);
+ *                      every neighbour LCP of a candidate is computed once, by candidate (k_cand_lcp), and the runs' heads take
+ *                      their minima over those arrays (k_cand_runs, k_cand_runs_long); results unchanged ("cand_tail_used")
  *   tie_gallop         0: k_tie_groups counts the members of a tie group one by one (default 1: 8 slots one by one, then
  *                      doubling steps and bisection on the sorted keys, tie_extent.h); results unchanged
  *   cand_counts_fused  0: the candidate counts of the rank-order scan's workgroups go through rocPRIM's scan and reduce and two
@@ -206,6 +212,9 @@ const char *fbg_last_error(const fbg_ctx *ctx);
  * "cand_inversions" (read-only): with cand_sort_check, the places of the last scan's sorted candidate list whose successor
  * is not larger (0 also when the scan had no list to sort); -1 without the option.  "cand_local_sorted" (read-only): 1 when
  * that list was sorted region by region, 0 by the radix sort, -1 when no list was sorted.
+ * "cand_tail_used" (read-only): 1 when the last rank-order scan worked its candidates by member (option cand_tail), 0 when
+ * it ran the kernels by head (the option off, no lean scan, a region above the LDS capacity, partitions, no candidates);
+ * -1 when no rank-order scan ran.
  * "wave_runs" (read-only): the runs of the last rank-order scan that a wave each walked; -1 when no rank-order scan
  * finished.
  * "rank_lean_launched" (read-only): 1 when the last rank-order scan launched its lean form (k_rank_scan_lean), whether or
