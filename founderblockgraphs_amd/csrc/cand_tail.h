@@ -1,4 +1,4 @@
-// cand_tail.h -- the logic of the rank-order scan's tail that works member by member (rank_scan.hip: k_cand_region, k_cand_lcp,
+// cand_tail.h -- the logic of the rank-order scan's tail that works member by member (rank_tail.hip: k_cand_region, k_cand_lcp,
 // k_cand_runs): where a tie group begins in a sorted candidate list and where its keys are found, the order of a group's
 // members as ranks, and the two running minima of a same-column run over arrays of neighbour LCPs.
 // Plain C++ (no HIP types), templated on accessors like tie_extent.h: the kernels and the CPU check in host/host_selftest.cpp

@@ -116,7 +116,7 @@ struct fbg_ctx {
     hipStream_t aux = nullptr;
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
     bool aux_pending = false;
-    uint32_t *pin_pair = nullptr;  // two pinned words the candidates' total and largest count come back into (rank_scan.hip)
+    uint32_t *pin_pair = nullptr;  // two pinned words the candidates' total and largest count come back into (rank_tail.hip)
     // the twins among the sampled keys come back into two pinned words; twin_ev follows the copy (suffix_sort.hip sample_launch)
     unsigned long long *pin_twins = nullptr;
     hipEvent_t twin_ev = nullptr;
@@ -174,7 +174,7 @@ struct fbg_ctx {
     DevBuf igrow;              // u32[m*n]: first ignore-char column >= x, row-major (ignore chars only)
     DevBuf rec;                // uint4[N] by text position: {rank, lcp-prev | hint<<31, lcp-next | hint<<31, 0}
     DevBuf xlist;              // u32[n+1]: columns whose coloured ranks may contain consecutive integers
-    // rank-order scan (rank_scan.hip): kind ranked
+    // rank-order scan (rank_scan.hip, rank_tail.hip): kind ranked
     DevBuf gmax, excol, xslot; // u32[n+1]: column maxima of g, exception flags, exception slots
     DevBuf xbits;              // bitmap of the exception columns
     DevBuf exc_scratch;        // per-workgroup column state of k_scan_exceptions_big (MSAs of more than 4096 rows)
@@ -243,14 +243,14 @@ struct FbgScalars {
     unsigned long long sample_count;             // suffix_sort.hip: twins in the key sample; the slots a partition keeps
     alignas(64) unsigned long long dp[16];       // dp.hip: results and flags of the three DPs and of the lifted backtrack
     unsigned long long scan_exceptions;          // scan.hip: exception columns of the record scan
-    alignas(64) unsigned long long rank[8];      // rank_common.h / rank_scan.hip: RankArgs::counters ...
+    alignas(64) unsigned long long rank[8];      // rank_common.h / rank_scan.hip, rank_tail.hip: RankArgs::counters ...
     unsigned long long rank_hist[32];            // ... and right behind them the threshold histogram, 64 x u32 (rs_zero_counters: one fill)
     alignas(64) unsigned long long pure[4];      // pure_scan.hip: PsArgs::counters
     alignas(64) unsigned long long msd[4];       // msd_sort.hip, msd_sort_pairs.hip: decline flag, arena count, total of the pairs sort, sub-buckets left for later
     unsigned long long sample_twins;             // msd_sort_pairs.hip: twins in the sample of the pairs sort
     unsigned long long graph_collision;          // block_graph.hip: two labels share a hash
     unsigned long long pair_stats[2];            // rank_scan.hip: tied pairs of the lean scan settled by the extra symbols / by the text
-    unsigned long long cand_inversions;          // rank_scan.hip: option cand_sort_check
+    unsigned long long cand_inversions;          // rank_tail.hip: option cand_sort_check
     unsigned long long by_position;              // suffix_sort.hip: the records by position are no permutation
     alignas(64) unsigned long long gapped[8 + 66];   // gapped_rank.hip: GrsArgs::counters and the threshold histogram behind them
     alignas(64) unsigned long long span[34];     // span_scan.hip: SpArgs::counters

@@ -8,7 +8,7 @@
 // prints "m n" of the MSA as read, then (with boundaries given: inclusive block ends, the last one == n, fbg.cpp:2027-2039)
 // writes the xGFA and prints "nodes total_label_length founders edges".
 //     fbg_host_selftest tie-extent
-// checks fbg_tie_extent (tie_extent.h, the size of a tie group as rank_scan.hip's k_tie_groups finds it) against the plain count
+// checks fbg_tie_extent (tie_extent.h, the size of a tie group as rank_tail.hip's k_tie_groups finds it) against the plain count
 // it replaces: groups of 1 .. 70 and 8191 .. 8194 slots at the start of a sorted array, in its middle and ending exactly at
 // `hi`, each also with `hi` cutting the group short; prints "tie_extent ok CASES" or the first case that differs.
 //     fbg_host_selftest twin-hash KEYS.bin BITS
@@ -18,7 +18,7 @@
 //     fbg_host_selftest twin-slots KEYS.bin BITS
 // prints the first slot of every key, one per line.
 //     fbg_host_selftest cand-tail
-// checks cand_tail.h (the rank-order scan's tail by member: rank_scan.hip's k_cand_region, k_cand_runs) against brute force: the
+// checks cand_tail.h (the rank-order scan's tail by member: rank_tail.hip's k_cand_region, k_cand_runs) against brute force: the
 // places of the members of tie groups of 2 .. 70 suffixes of a text of rows, with and without members that have fewer than K
 // symbols left; heads and sizes of the tie groups of a sorted slot array seen through candidate regions that cut them; the two
 // running minima of runs of 1 .. 200 members in one piece and in pieces of 64, 7 and 1.  Prints "cand_tail ok GROUPS HEADS RUNS"
@@ -42,7 +42,7 @@
 
 static int tie_extent_selftest()
 {
-    const uint32_t cap = 8192;                          // rank_scan.hip: RS_BIG_MEMBERS
+    const uint32_t cap = 8192;                          // rank_tail.hip: RS_BIG_MEMBERS
     std::vector<uint32_t> sizes;
     for (uint32_t s = 1; s <= 70; s++) sizes.push_back(s);
     for (uint32_t s = 8191; s <= 8194; s++) sizes.push_back(s);

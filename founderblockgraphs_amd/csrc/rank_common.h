@@ -1,5 +1,5 @@
 // rank_common.h -- slot layouts and row arithmetic shared by the scans that work in suffix-array order
-// (rank_scan.hip: the slot-level scan; pure_scan.hip: the group-level scan for similar rows).
+// (rank_scan.hip: the slot-level scan, rank_tail.hip: its candidate tail; pure_scan.hip: the group-level scan for similar rows).
 #pragma once
 #include "fbg_internal.h"
 #include "text_cmp.h"
@@ -47,7 +47,7 @@ struct RankArgs {
     uint32_t *pm;              // scratch parallel to cand: prefix minima of the forward walk
     uint32_t *big;             // tie groups too long for one thread: (head slot, size) pairs, counters[5] of them
     unsigned long long *counters;   // [1] fallback flag, [7] runs noted in wl
-    // runs that get a wave instead of a thread (rank_scan.hip: k_runs_long; never with partitions).  wl: pairs (candidate index,
+    // runs that get a wave instead of a thread (rank_tail.hip: k_runs_long, k_cand_runs_long; never with partitions).  wl: pairs (candidate index,
     // head slot), counters[7] of them noted; a full list (wl_cap entries, RS_WAVE_LIST at most) sends the thread back to its own walk
     uint32_t *wl;
     uint32_t wl_cap;
@@ -123,6 +123,21 @@ __device__ __forceinline__ void rs_update(const RankArgs &a, uint32_t col, uint3
     if (a.gmax[col] < g) atomicMax(&a.gmax[col], g);
 }
 
+// LCP of the suffixes of two neighbouring SA slots, x before y
+__device__ __forceinline__ uint32_t rs_pair_lcp(const RankArgs &a, const Slot &x, const Slot &y)
+{
+    if (x.key != y.key) return min(min(rs_key_lcp(x.key, y.key, a.b, a.key_bits), x.rem), y.rem);
+    const uint32_t from = (x.rem < (uint32_t)a.K || y.rem < (uint32_t)a.K) ? 0u : (uint32_t)a.K;
+    return fbg_clamp_lcp(fbg_extend_match(a.T, (uint64_t)x.pos + from, (uint64_t)y.pos + from, 0) + from);
+}
+
+// LCP of the suffixes in SA slots k-1 and k (final order, or a member of an unordered small tie group next to a
+// slot outside it: all its members have K symbols left, the result does not depend on which one it is)
+template <int L> __device__ __forceinline__ uint32_t rs_slot_lcp(const RankArgs &a, uint64_t k)
+{
+    if (k == (a.first_part ? a.own_lo : 0) || k >= (a.last_part ? a.own_hi : a.N)) return 0;   // no such neighbour
+    return rs_pair_lcp(a, rs_slot<L>(a, k - 1), rs_slot<L>(a, k));
+}
 
 // one wave-aggregated append per list: a single update per wave of the workgroup's counter (LDS; it goes to
 // global memory once, when the workgroup is done)
@@ -259,6 +274,14 @@ __device__ __forceinline__ void rank_scan_slow(const RankArgs &a, const V &v, co
 
 
 // ---- host side ----------------------------------------------------------------------------------------------
+// kernels exist for both slot layouts
+#define RS_LAUNCH(kernel, layout, grid, block, st, ...)                                                     \
+    do {                                                                                                    \
+        if ((layout) == FBG_SLOTS_PACKED) hipLaunchKernelGGL((kernel<FBG_SLOTS_PACKED>), grid, block, 0, st, __VA_ARGS__);  \
+        else if ((layout) == FBG_SLOTS_WIDE) hipLaunchKernelGGL((kernel<FBG_SLOTS_WIDE>), grid, block, 0, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kernel<FBG_SLOTS_PAIRS>), grid, block, 0, st, __VA_ARGS__);                                \
+    } while (0)
+
 static inline int rs_layout(const KeyGeom &g) { return g.packed ? FBG_SLOTS_PACKED : g.wide ? FBG_SLOTS_WIDE : FBG_SLOTS_PAIRS; }
 
 static inline void rs_args_init(fbg_ctx *ctx, RankArgs &a, uint64_t *keys, uint32_t *vals, uint64_t slots, int layout, int pb, int b,

@@ -14,18 +14,14 @@
 //                   extension of a member is 1 + its longest match with any other member (k_tie_simple).
 //                   Everything else -- slots with a same-column neighbour, larger or entangled tie groups --
 //                   goes to a (short) candidate list.
+//   k_rank_scan_lean  the same scan with half the instructions per slot, where it applies (packed slots below 2^31, threshold
+//                   above K, no partitions); the simple tied pairs it sets aside go to k_tie_pairs.
 //   k_tie_simple    the small tie groups: all pairs compared beyond the key, straight into the column maxima.
-//   k_tie_groups    candidate tie groups are ordered by text comparison: final SA order.
-//   k_runs          candidates, in final order: every maximal run of same-column neighbouring slots gets
-//                   g = 1 + max(min LCP towards the run head, min LCP towards the run tail) per member
-//                   (fbg.cpp:1644-1678) by one forward and one backward walk.
-//   k_runs_long     without partitions: runs of 16 members and more, noted by k_runs, get a wave each -- the row ends make
-//                   such runs, and a thread's walk through one is what the whole step would wait for.
-//   k_cand_region, k_cand_lcp, k_cand_runs, k_cand_runs_long
-//                   behind the lean scan (option cand_tail) the same work by member instead of by head: a workgroup per
-//                   region sorts it and orders the tie groups it heads, every LCP is computed once by candidate, and the
-//                   run heads take their minima over those arrays (cand_tail.h).
+//   the candidates  rank_tail.hip: sorted, their tie groups ordered by text comparison (final SA order), and every maximal run
+//                   of same-column neighbouring slots given its extensions -- by head or by member, three tiers (its header).
 //   k_rank_finish   f[x] / v[j] from the column maxima (fbg.cpp:1656-1672 with rank_i(x) = x, tot_i = n).
+// The drivers (fbg_rank_scan_try; with partitions fbg_rank_part_classify, fbg_rank_part_runs) go in a straight line:
+// rs_scan_launch, rs_tail_order, rs_tail_runs (rank_tail.h).
 //
 // Keys use the compact coding of suffix_sort.hip: a separator ('#', sentinel) and everything behind it inside a
 // key count as code 0.  A key of a suffix with fewer than K symbols left in its row ("short") is therefore the
@@ -34,18 +30,18 @@
 // (rem = n - column, row arithmetic).  Tie groups with a short member are ordered by comparing the text from
 // the suffix start.  Slots are either (key, position) pairs or one packed word, key << pb | position.
 //
-// Falls back to the record path (suffix_sort.hip doubling + scan.hip) when a quarter of the slots tie
-// (similar rows), a workgroup's candidate region overflows, or a tie group exceeds 64 members.
+// Falls back to the record path (suffix_sort.hip doubling + scan.hip) when a quarter of the sampled slots tie (similar rows), a
+// workgroup's candidate or tie region overflows, a tie group exceeds RS_BIG_MEMBERS members or there are more than RS_BIG_GROUPS
+// groups of more than 64 (rank_tail.hip), after the general scan a group holds more than 64 members with a full key (behind the
+// lean scan k_tie_big ranks such a group whole), or, with partitions, a run outgrows a halo.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 #include "fbg_internal.h"
 #include "text_cmp.h"
-#include <rocprim/rocprim.hpp>
 
 #include "rank_common.h"
-#include "tie_extent.h"
-#include "cand_tail.h"
+#include "rank_tail.h"
 
 // k_rank_scan stages a chunk of 256 slots (+ RS_HALO either side) in LDS as (key, column): all the looking around
 // that tie groups need happens there.
@@ -739,231 +735,6 @@ __global__ void k_count_unfilled(const uint32_t *__restrict__ gmax, uint64_t n, 
     if ((threadIdx.x & 63) == 0 && mask) atomicAdd(&counters[1 + 3], (unsigned long long)__popcll(mask));   // counters[4]
 }
 
-// candidate regions of the workgroups -> one contiguous list (offsets = exclusive scan of the counts)
-__global__ void k_cand_compact(const uint32_t *__restrict__ regions, const uint32_t *__restrict__ counts,
-                               const uint32_t *__restrict__ offsets, uint32_t region, uint32_t *__restrict__ out)
-{
-    const uint32_t c = counts[blockIdx.x] < region ? counts[blockIdx.x] : region, o = offsets[blockIdx.x];
-    for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) out[o + i] = regions[(size_t)blockIdx.x * region + i];
-}
-
-// The same after k_rank_scan_lean, where a workgroup owns one contiguous stretch of the slots and the stretches ascend with the
-// workgroups: what a region holds lies in its workgroup's stretch -- but for the tail of a pair whose head is the stretch's last
-// slot, the first slot of the next stretch, which its owner never lists (a row's lane 3 that ties with lane 2 and not with lane 4
-// is neither head of a pair, nor member of a longer group, nor "not tied": none of the masks Q is made of) -- so regions sorted
-// one by one and written out at their offsets are the sorted list: no device-wide sort.  Bitonic sort in LDS, counts up to
-// RS_CAND_LDS (the host knows the largest).
-#define RS_CAND_LDS 4096
-__global__ __launch_bounds__(256) void k_cand_sort_compact(const uint32_t *__restrict__ regions, const uint32_t *__restrict__ counts,
-                                                           const uint32_t *__restrict__ offsets, uint32_t region, uint32_t *__restrict__ out)
-{
-    __shared__ uint32_t buf[RS_CAND_LDS];
-    const uint32_t c = min(min(counts[blockIdx.x], region), (uint32_t)RS_CAND_LDS), o = offsets[blockIdx.x];
-    if (c == 0) return;
-    uint32_t P = 2;
-    while (P < c) P <<= 1;
-    for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) buf[i] = i < c ? regions[(size_t)blockIdx.x * region + i] : 0xffffffffu;
-    __syncthreads();
-    for (uint32_t k = 2; k <= P; k <<= 1)
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const uint32_t x = buf[i], y = buf[l];
-                    if ((x > y) == ((i & k) == 0)) { buf[i] = y; buf[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) out[o + i] = buf[i];
-}
-
-// The candidate counts of the workgroups (nb of them, 4096 at most) -> their exclusive offsets offs[0 .. nb] (offs[nb]: the total),
-// and the total and the largest count side by side in tot_max[0 .. 1], for one copy to the host.  One workgroup: a thread
-// takes a stretch of counts, the stretches' sums are scanned across the wave and then across the 16 waves.
-#define RS_COUNTS_THREADS 1024
-__global__ __launch_bounds__(RS_COUNTS_THREADS) void k_cand_counts(const uint32_t *__restrict__ counts, uint32_t nb, uint32_t *__restrict__ offs,
-                                                                   uint32_t *__restrict__ tot_max)
-{
-    __shared__ uint32_t wsum[RS_COUNTS_THREADS / 64], wmax[RS_COUNTS_THREADS / 64];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t per = (nb + RS_COUNTS_THREADS - 1) / RS_COUNTS_THREADS;
-    const uint32_t i0 = min(threadIdx.x * per, nb), i1 = min(i0 + per, nb);
-    uint32_t sum = 0, mx = 0;
-    for (uint32_t i = i0; i < i1; i++) { const uint32_t c = counts[i]; sum += c; mx = max(mx, c); }
-    uint32_t inc = sum;                                                // inclusive scan of the stretches' sums in the wave
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= (uint32_t)d) inc += o;
-    }
-    for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, d, 64));
-    if (lane == 63) wsum[wv] = inc;
-    if (lane == 0) wmax[wv] = mx;
-    __syncthreads();
-    uint32_t before = inc - sum, total = 0, largest = 0;
-    for (uint32_t v = 0; v < RS_COUNTS_THREADS / 64; v++) {
-        if (v < wv) before += wsum[v];
-        total += wsum[v];
-        largest = max(largest, wmax[v]);
-    }
-    for (uint32_t i = i0; i < i1; i++) { offs[i] = before; before += counts[i]; }
-    if (threadIdx.x == 0) { offs[nb] = total; tot_max[0] = total; tot_max[1] = largest; }
-}
-
-// debugging aid (option cand_sort_check): places of the sorted candidate list that do not ascend
-__global__ void k_cand_inversions(const uint32_t *__restrict__ cand, uint64_t T, unsigned long long *__restrict__ count)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long mask = __ballot(t + 1 < T && cand[t] >= cand[t + 1]);
-    if ((threadIdx.x & 63) == 0 && mask) atomicAdd(count, (unsigned long long)__popcll(mask));
-}
-
-// a slot whose key equals its successor's but not its predecessor's heads a tie group: put the group in text
-// order.  by_list: t indexes the sorted candidates; otherwise every owned slot (fbg_rank_materialize).
-// Groups of more than 64 go to k_tie_big.
-#define RS_BIG_GROUPS 1024
-#define RS_BIG_MEMBERS 8192
-template <int L> __global__ void k_tie_groups(RankArgs a, uint64_t T, int by_list, int gallop)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    const uint64_t k0 = by_list ? (uint64_t)a.cand[t] : a.own_lo + t;
-    const uint64_t key = rs_key<L>(a, k0);
-    if (k0 > a.own_lo && rs_key<L>(a, k0 - 1) == key) return;                      // inside a group
-    if (k0 + 1 >= a.own_hi || rs_key<L>(a, k0 + 1) != key) return;                 // not a tie (ties never cross partitions)
-    // the group's size, RS_BIG_MEMBERS + 1 for anything larger.  Counting member by member is one dependent load each: the
-    // row ends make groups of a thousand and more, and the whole kernel is as long as that one thread (gallop: tie_extent.h)
-    uint32_t s = 1;
-    if (gallop) s = fbg_tie_extent(k0, a.own_hi, RS_BIG_MEMBERS, key, [&](uint64_t k) { return rs_key<L>(a, k); });
-    else while (k0 + s < a.own_hi && s <= RS_BIG_MEMBERS && rs_key<L>(a, k0 + s) == key) s++;
-    if (s > 64) {
-        if (s > RS_BIG_MEMBERS) { a.counters[1] = 1; return; }
-        const unsigned long long e = atomicAdd(&a.counters[5], 1ull);
-        if (e >= RS_BIG_GROUPS) { a.counters[1] = 1; return; }
-        a.big[2 * e] = (uint32_t)k0;
-        a.big[2 * e + 1] = s;
-        return;
-    }
-    // order the s suffixes by their text (insertion sort, s is tiny).  The first K symbols agree -- unless a member
-    // has fewer than K symbols left in its row: then the keys agree only up to the separator coding
-    typedef typename PosT<L>::type pos_t;
-    pos_t pos[64];
-    uint32_t from = (uint32_t)a.K;
-    for (uint32_t i = 0; i < s; i++) {
-        pos[i] = (pos_t)rs_pos<L>(a, k0 + i);
-        if (rs_rem<L>(a, pos[i]) < (uint32_t)a.K) from = 0;
-    }
-    for (uint32_t i = 1; i < s; i++) {
-        const pos_t cur = pos[i];
-        uint32_t j = i;
-        while (j > 0) {
-            const pos_t o = pos[j - 1];
-            const uint32_t h = fbg_extend_match(a.T, (uint64_t)o + from, (uint64_t)cur + from, 0);
-            if (a.T[(uint64_t)o + from + h] < a.T[(uint64_t)cur + from + h]) break;      // o < cur: in place
-            pos[j] = o;
-            j--;
-        }
-        pos[j] = cur;
-    }
-    for (uint32_t i = 0; i < s; i++) rs_set_pos<L>(a, k0 + i, pos[i]);
-}
-
-// Long tie groups exist where many rows end alike: the members of a group share their real symbols and differ in
-// how many they have left (r#, rA#, rAA#, ... and the suffixes with K real symbols), '#' being the smallest
-// symbol.  Text order is therefore: by symbols left (capped at K) first.  Members with the same number left sit in
-// one MSA column: a run whose inner order has no influence on any extension (the LCPs inside exceed those at its
-// two ends, fbg.cpp:1644-1656) -- left as it is unless `exact` (fbg_index_download wants the true suffix array).
-// The members with K real symbols are ordered by their text; more than 64 of those -> fallback flag, or with exact = 2 the
-// whole group as under exact = 1.
-// One workgroup per group.
-template <int L> __global__ __launch_bounds__(256) void k_tie_big(RankArgs a, int exact)
-{
-    __shared__ uint32_t pos_lo[RS_BIG_MEMBERS];
-    __shared__ uint8_t pos_hi[L == FBG_SLOTS_WIDE ? RS_BIG_MEMBERS : 1];     // positions beyond 32 bits: their top byte
-    __shared__ uint8_t cls[RS_BIG_MEMBERS];
-    __shared__ uint32_t offs[66];
-    __shared__ uint32_t q_start, q_count;
-    if (blockIdx.x >= a.counters[5]) return;
-    const uint64_t k0 = a.big[2 * blockIdx.x];
-    const uint32_t s = a.big[2 * blockIdx.x + 1];
-    auto member = [&](uint32_t i) -> uint64_t {
-        return L == FBG_SLOTS_WIDE ? ((uint64_t)pos_hi[L == FBG_SLOTS_WIDE ? i : 0] << 32) | pos_lo[i] : (uint64_t)pos_lo[i];
-    };
-    if (threadIdx.x < 66) offs[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < s; i += blockDim.x) {
-        const uint64_t p = rs_pos<L>(a, k0 + i);
-        const uint32_t c = min(rs_rem<L>(a, p), (uint32_t)a.K);
-        pos_lo[i] = (uint32_t)p;
-        if (L == FBG_SLOTS_WIDE) pos_hi[L == FBG_SLOTS_WIDE ? i : 0] = (uint8_t)(p >> 32);
-        cls[i] = (uint8_t)c;
-        atomicAdd(&offs[c + 1], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        q_count = offs[a.K + 1];
-        for (int c = 1; c <= a.K + 1; c++) offs[c] += offs[c - 1];      // offs[c] = first slot of class c
-        q_start = offs[a.K];
-    }
-    __syncthreads();
-    // exact = 2 (behind the lean scan): more than 64 members with K real symbols -- a stretch that many rows share -- are no
-    // reason to give the scan up: the ranks below order such a group like any other
-    if (exact == 0 || (exact == 2 && q_count <= 64)) {
-        for (uint32_t i = threadIdx.x; i < s; i += blockDim.x) {
-            const uint32_t dst = atomicAdd(&offs[cls[i]], 1u);
-            rs_set_pos<L>(a, k0 + dst, member(i));
-        }
-        __threadfence();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t q = q_count;
-            if (q > 64) { a.counters[1] = 1; return; }
-            const uint64_t kq = k0 + q_start;
-            for (uint32_t i = 1; i < q; i++) {                          // insertion sort by the text beyond the key
-                const uint64_t cur = rs_pos<L>(a, kq + i);
-                uint32_t j = i;
-                while (j > 0) {
-                    const uint64_t o = rs_pos<L>(a, kq + j - 1);
-                    const uint32_t h = fbg_extend_match(a.T, o + a.K, cur + a.K, 0);
-                    if (a.T[o + a.K + h] < a.T[cur + a.K + h]) break;
-                    rs_set_pos<L>(a, kq + j, o);
-                    j--;
-                }
-                rs_set_pos<L>(a, kq + j, cur);
-            }
-        }
-        return;
-    }
-    // exact: rank of every member among all members by text comparison (distinct suffixes: ranks are a permutation)
-    for (uint32_t i = threadIdx.x; i < s; i += blockDim.x) {
-        const uint64_t p = member(i);
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < s; j++) {
-            if (j == i) continue;
-            const uint64_t o = member(j);
-            const uint32_t h = fbg_extend_match(a.T, o, p, 0);
-            rank += a.T[o + h] < a.T[p + h] ? 1u : 0u;
-        }
-        rs_set_pos<L>(a, k0 + rank, p);
-    }
-}
-
-// LCP of the suffixes of two neighbouring SA slots, x before y
-__device__ __forceinline__ uint32_t rs_pair_lcp(const RankArgs &a, const Slot &x, const Slot &y)
-{
-    if (x.key != y.key) return min(min(rs_key_lcp(x.key, y.key, a.b, a.key_bits), x.rem), y.rem);
-    const uint32_t from = (x.rem < (uint32_t)a.K || y.rem < (uint32_t)a.K) ? 0u : (uint32_t)a.K;
-    return fbg_clamp_lcp(fbg_extend_match(a.T, (uint64_t)x.pos + from, (uint64_t)y.pos + from, 0) + from);
-}
-
-// LCP of the suffixes in SA slots k-1 and k (final order, or a member of an unordered small tie group next to a
-// slot outside it: all its members have K symbols left, the result does not depend on which one it is)
-template <int L> __device__ __forceinline__ uint32_t rs_slot_lcp(const RankArgs &a, uint64_t k)
-{
-    if (k == (a.first_part ? a.own_lo : 0) || k >= (a.last_part ? a.own_hi : a.N)) return 0;   // no such neighbour
-    return rs_pair_lcp(a, rs_slot<L>(a, k - 1), rs_slot<L>(a, k));
-}
-
 // test / debugging aid (fbg_index_download): suffix array, its inverse and the neighbour LCPs by text position
 template <int L> __global__ void k_rank_materialize(RankArgs a, uint32_t *sa, uint32_t *isa, uint32_t *pl, uint32_t *pr)
 {
@@ -974,389 +745,6 @@ template <int L> __global__ void k_rank_materialize(RankArgs a, uint32_t *sa, ui
     isa[p] = (uint32_t)k;
     pl[p] = rs_slot_lcp<L>(a, k);
     pr[p] = rs_slot_lcp<L>(a, k + 1);
-}
-
-// candidates (sorted, final SA order): one thread per run head walks its run of same-column slots.  With
-// partitions a run may begin or end in a halo (copies of the neighbouring partition's edge slots): it is walked
-// in full, but only owned members update the column maxima -- the neighbour does the same from its side.
-template <int L> __global__ void k_runs(RankArgs a, uint64_t T)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    const uint64_t k0 = a.cand[t];
-    const uint32_t col = rs_col<L>(a, k0);
-    if (col == a.n) return;                                            // '#' / sentinel: not a row pointer
-    if (k0 > a.own_lo && rs_col<L>(a, k0 - 1) == col) return;         // an owned predecessor heads this run
-    const uint64_t lo_slot = a.first_part ? a.own_lo : 0, hi_slot = a.last_part ? a.own_hi : a.N;
-    uint64_t ks = k0;                                                  // true head: possibly inside the previous halo
-    while (ks > lo_slot && rs_col<L>(a, ks - 1) == col) ks--;
-    if (ks == 0 && !a.first_part) { a.counters[1] = 1; return; }       // run longer than the halo
-    // forward: running minimum of LCP[lb..r]   (owned members of a run are contiguous in cand[])
-    uint32_t run = rs_slot_lcp<L>(a, ks);
-    uint64_t s = ks;
-    for (;;) {
-        if (s >= k0 && s < a.own_hi) a.pm[t + (s - k0)] = run;
-        if (s + 1 >= hi_slot || rs_col<L>(a, s + 1) != col) break;
-        s++;
-        if (a.runs_wave_min && s - ks + 1 == a.runs_wave_min) {        // a long run: a wave walks it (k_runs_long), unless the list is full
-            const unsigned long long e = atomicAdd(&a.counters[7], 1ull);
-            if (e < a.wl_cap) { a.wl[2 * e] = (uint32_t)t; a.wl[2 * e + 1] = (uint32_t)ks; return; }
-        }
-        run = min(run, rs_slot_lcp<L>(a, s));
-    }
-    if (s + 1 == a.N && !a.last_part) { a.counters[1] = 1; return; }   // ran through the next halo
-    // backward: running minimum of LCP[r+1..rb+1], extension, column maximum   (fbg.cpp:1656)
-    uint32_t rmin = 0xffffffffu;
-    for (;; s--) {
-        rmin = min(rmin, rs_slot_lcp<L>(a, s + 1));
-        if (s >= k0 && s < a.own_hi) rs_update(a, col, max(a.pm[t + (s - k0)], rmin) + 1);
-        if (s == ks || s <= k0) break;                                 // members before k0 belong to the neighbour
-    }
-}
-
-// The runs k_runs noted (runs_wave_min members and more; no partitions: the head is the candidate itself and every slot is
-// owned).  The last column of 1000 rows holds 250 suffixes "X#" per symbol, one run: 500 text comparisons one after the other
-// for a thread.  One wave per run, 64 members at a time, a lane each: the members' LCPs side by side, an inclusive minimum
-// scan across the wave with a carry from chunk to chunk -- forward into a.pm, then backward from the tail; the arithmetic is
-// k_runs' (fbg.cpp:1644-1678).  The members share their column: one update of its maximum.
-template <int L> __global__ __launch_bounds__(64) void k_runs_long(RankArgs a)
-{
-    if (blockIdx.x >= a.counters[7]) return;                            // (the grid is wl_cap blocks)
-    const uint64_t t = a.wl[2 * blockIdx.x], ks = a.wl[2 * blockIdx.x + 1];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t col = rs_col<L>(a, ks);
-    uint64_t len = 0;
-    uint32_t carry = 0xffffffffu;
-    for (uint64_t c0 = 0;; c0 += 64) {                                 // forward: minimum of LCP[head .. member]
-        const uint64_t s = ks + c0 + lane;
-        const unsigned long long out = ~__ballot(s < a.own_hi && rs_col<L>(a, s) == col);
-        const uint32_t cnt = out ? (uint32_t)__ffsll((long long)out) - 1 : 64u;       // members among these 64 slots
-        uint32_t v = lane < cnt ? rs_slot_lcp<L>(a, s) : 0xffffffffu;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(v, d, 64);
-            if (lane >= (uint32_t)d) v = min(v, o);
-        }
-        v = min(v, carry);
-        if (lane < cnt) a.pm[t + c0 + lane] = v;
-        carry = __shfl(v, 63, 64);
-        len += cnt;
-        if (cnt < 64) break;
-    }
-    uint32_t best = 0;
-    carry = 0xffffffffu;
-    for (uint64_t c0 = (len - 1) / 64 * 64;; c0 -= 64) {               // backward: minimum of LCP[member + 1 .. tail + 1], extension
-        const uint64_t i = c0 + lane;
-        uint32_t v = i < len ? rs_slot_lcp<L>(a, ks + i + 1) : 0xffffffffu;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_down(v, d, 64);
-            if (lane + (uint32_t)d < 64) v = min(v, o);
-        }
-        v = min(v, carry);
-        if (i < len) best = max(best, max(a.pm[t + i], v) + 1);        // (a.pm[t + i]: this lane's own store)
-        carry = __shfl(v, 0, 64);
-        if (c0 == 0) break;
-    }
-    for (int d = 32; d > 0; d >>= 1) best = max(best, (uint32_t)__shfl_xor(best, d, 64));
-    if (lane == 0) rs_update(a, col, best);
-}
-
-// ---- the tail by member (option cand_tail; packed slots, no partitions, regions sorted in LDS; the logic is cand_tail.h's) ----
-// k_cand_sort_compact and k_tie_groups in one kernel, a workgroup per region: the region sorted in LDS and written out, the
-// word of every candidate kept beside it, a head's group measured on those (fbg_ct_key_from: the slots themselves answer past
-// the region's end -- groups span regions, the head's workgroup owns the whole group and is the only one to write its
-// positions; other workgroups read the keys of those slots only, which no write changes).  Groups of up to RC_SMALL members
-// are ordered by their head's thread in registers, those of up to 64 by a wave with a lane per member (rank = number of
-// smaller members, as k_tie_big's exact mode), larger ones go to k_tie_big as from k_tie_groups.  No private array is indexed
-// at run time: no scratch.  Every loop is bounded by the region's count, a group's cap or the text's end.
-#define RC_SMALL 4
-
-// is the suffix at po smaller than the one at pc?  wo / wc: their first 8 bytes (fbg_load8), loaded by the caller ahead of use
-__device__ __forceinline__ bool rc_text_less(const uint8_t *__restrict__ T, uint64_t po, uint64_t pc, uint64_t wo, uint64_t wc)
-{
-    const uint64_t x = wo ^ wc;
-    if (x == 0) {
-        const uint32_t h = fbg_extend_match(T, po, pc, 8);
-        return T[po + h] < T[pc + h];
-    }
-    const uint32_t sh = (uint32_t)(__ffsll((unsigned long long)x) - 1) & ~7u;      // the first byte that differs
-    return ((wo >> sh) & 0xff) < ((wc >> sh) & 0xff);
-}
-
-// a wave's own LDS writes, visible to its other lanes' reads that follow
-__device__ __forceinline__ void rc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// one compare-exchange stage of the bitonic network over pairs [t0, t1) step `step`: pair t is (i, i + j), i = t with a zero bit
-// put in at j's place
-__device__ __forceinline__ void rc_bitonic_pairs(uint32_t *buf, uint32_t base, uint32_t t0, uint32_t t1, uint32_t step, uint32_t j, uint32_t k)
-{
-    for (uint32_t t = t0; t < t1; t += step) {
-        const uint32_t i = base + (((t & ~(j - 1)) << 1) | (t & (j - 1))), l = i + j;
-        const uint32_t x = buf[i], y = buf[l];
-        if ((x > y) == ((i & k) == 0)) { buf[i] = y; buf[l] = x; }
-    }
-}
-
-// LDS (dynamic; the host knows the largest count, cap): the words of a region's first wcap entries, its slots padded to a power
-// of two (pmax at most), the entries that head a group (at most every other one) and the groups that get a wave (lcap).  An
-// entry past wcap -- the few regions that hold the row ends -- finds its word among the slots, like a slot past the region.
-#define RC_WORDS 1024
-__global__ __launch_bounds__(256) void k_cand_region(RankArgs a, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ offsets,
-                                                     uint32_t *__restrict__ out, int gallop, uint32_t cap, uint32_t pmax, uint32_t wcap, uint32_t lcap)
-{
-    constexpr int L = FBG_SLOTS_PACKED;
-    extern __shared__ uint64_t rc_lds[];
-    uint64_t *wbuf = rc_lds;
-    uint32_t *buf = reinterpret_cast<uint32_t *>(wbuf + wcap);
-    uint32_t *glist = buf + pmax;
-    uint16_t *hlist = reinterpret_cast<uint16_t *>(glist + lcap);
-    __shared__ uint32_t gcount, hcount;
-    const uint32_t c = min(min(counts[blockIdx.x], a.region), cap), o = offsets[blockIdx.x];
-    if (c == 0) return;
-    const uint32_t wc = min(c, wcap), hcap = cap / 2 + 2;
-    uint32_t P = 2;
-    while (P < c) P <<= 1;                                              // (<= pmax: the power of two at or above cap)
-    for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) buf[i] = i < c ? a.cand[(size_t)blockIdx.x * a.region + i] : 0xffffffffu;
-    if (threadIdx.x == 0) { gcount = 0; hcount = 0; }
-    __syncthreads();
-    // k_cand_sort_compact's network, scheduled by wave: a wave owns a quarter of the slots (all of them below 256), and only the
-    // stages whose partners lie a quarter and more apart -- three of them -- go across the workgroup, between barriers
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t Q = P >= 256 ? P >> 2 : P;
-    for (uint32_t k = 2; k <= P; k <<= 1)
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            if (j >= Q) {
-                __syncthreads();
-                rc_bitonic_pairs(buf, 0, threadIdx.x, P >> 1, blockDim.x, j, k);
-                __syncthreads();
-            } else if (wv * Q < P) {
-                rc_bitonic_pairs(buf, wv * Q, lane, Q >> 1, 64, j, k);
-                rc_wave_sync();
-            }
-        }
-    __syncthreads();
-    // the sorted slots out; a candidate's word and its two neighbours', four entries' twelve loads in flight together (an entry
-    // past the count repeats the last, a neighbour past the array the slot itself); the heads of groups onto a list
-    for (uint32_t i0 = threadIdx.x; i0 < c; i0 += 4 * blockDim.x) {
-        uint64_t k[4], w[4], wp[4], wn[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) k[q] = buf[min(i0 + (uint32_t)q * blockDim.x, c - 1)];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            w[q] = a.keys[k[q]];
-            wp[q] = a.keys[k[q] > 0 ? k[q] - 1 : k[q]];
-            wn[q] = a.keys[k[q] + 1 < a.N ? k[q] + 1 : k[q]];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t i = i0 + (uint32_t)q * blockDim.x;
-            if (i >= c) continue;
-            out[o + i] = (uint32_t)k[q];
-            if (i < wc) wbuf[i] = w[q];
-            const uint64_t key = w[q] >> a.pb;
-            if (!(k[q] > 0 && (wp[q] >> a.pb) == key) && k[q] + 1 < a.N && (wn[q] >> a.pb) == key) {
-                const uint32_t e = atomicAdd(&hcount, 1u);
-                if (e < hcap) hlist[e] = (uint16_t)i;
-                else a.counters[1] = 1;                                     // (cannot be: a head's successor is no head)
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t n_heads = min(hcount, hcap);
-    for (uint32_t h = threadIdx.x; h < n_heads; h += blockDim.x) {
-        const uint32_t i = hlist[h];
-        const uint64_t k0 = buf[i], w0 = i < wc ? wbuf[i] : a.keys[k0], key = w0 >> a.pb;
-        auto word_at = [&](uint32_t d) -> uint64_t {                    // the word of slot k0 + d
-            const uint32_t j = i + d;
-            return j < wc && buf[j] == k0 + d ? wbuf[j] : a.keys[k0 + d];
-        };
-        auto key_at = [&](uint64_t k) -> uint64_t {
-            return fbg_ct_key_from(i, wc, k0, k, [&](uint32_t j) { return (uint64_t)buf[j]; }, [&](uint32_t j) { return wbuf[j] >> a.pb; },
-                                   [&](uint64_t s) { return a.keys[s] >> a.pb; });
-        };
-        uint32_t s = 1;
-        if (gallop) s = fbg_tie_extent(k0, a.N, RS_BIG_MEMBERS, key, key_at);
-        else while (k0 + s < a.N && s <= RS_BIG_MEMBERS && key_at(k0 + s) == key) s++;
-        if (s > 64) {
-            if (s > RS_BIG_MEMBERS) { a.counters[1] = 1; continue; }
-            const unsigned long long e = atomicAdd(&a.counters[5], 1ull);
-            if (e >= RS_BIG_GROUPS) { a.counters[1] = 1; continue; }
-            a.big[2 * e] = (uint32_t)k0;
-            a.big[2 * e + 1] = s;
-            continue;
-        }
-        if (s > RC_SMALL) {
-            const uint32_t e = atomicAdd(&gcount, 1u);
-            if (e < lcap) glist[e] = i | s << 16;
-            else a.counters[1] = 1;                                         // (cannot be: such groups do not overlap)
-            continue;
-        }
-        // 2 .. RC_SMALL members, in registers: positions, where the comparison starts, the first 8 bytes of every member ahead
-        // of the comparisons, every pair compared once
-        uint32_t p[RC_SMALL];
-        uint64_t w8[RC_SMALL];
-#pragma unroll
-        for (int d = 0; d < RC_SMALL; d++) p[d] = (uint32_t)(((uint32_t)d < s ? word_at(d) : w0) & a.pmask);
-        uint32_t from = (uint32_t)a.K;
-#pragma unroll
-        for (int d = 0; d < RC_SMALL; d++)
-            if (rs_rem<L>(a, p[d]) < (uint32_t)a.K) from = 0;               // (fbg_ct_from; slots past the group repeat the head)
-#pragma unroll
-        for (int d = 0; d < RC_SMALL; d++) w8[d] = fbg_load8(a.T, (uint64_t)p[d] + from);
-        uint32_t rank[RC_SMALL];
-        fbg_ct_small_ranks<RC_SMALL>(s, [&](int x, int y) { return rc_text_less(a.T, (uint64_t)p[x] + from, (uint64_t)p[y] + from, w8[x], w8[y]); }, rank);
-#pragma unroll
-        for (int d = 0; d < RC_SMALL; d++)
-            if ((uint32_t)d < s) a.keys[k0 + rank[d]] = key << a.pb | p[d];
-    }
-    __syncthreads();
-    // the groups of RC_SMALL + 1 .. 64 members: a wave each, a lane per member
-    const uint32_t groups = min(gcount, lcap);
-    for (uint32_t e = threadIdx.x >> 6; e < groups; e += blockDim.x >> 6) {
-        const uint32_t i = glist[e] & 0xffffu, s = glist[e] >> 16;
-        const uint64_t k0 = buf[i];
-        const uint32_t d = lane < s ? lane : 0u, j = i + d;                // (lanes past the group repeat the head: every load is valid)
-        const uint64_t w = j < wc && buf[j] == k0 + d ? wbuf[j] : a.keys[k0 + d];
-        const uint32_t p = (uint32_t)(w & a.pmask);
-        const uint32_t from = __ballot(rs_rem<L>(a, p) < (uint32_t)a.K) ? 0u : (uint32_t)a.K;
-        const uint64_t w8 = fbg_load8(a.T, (uint64_t)p + from);
-        const uint32_t rank = fbg_ct_rank(lane, s, [&](uint32_t x, uint32_t) {
-            const uint32_t px = (uint32_t)__shfl((int)p, (int)x, 64);
-            const uint64_t wx = (uint64_t)(uint32_t)__shfl((int)(uint32_t)w8, (int)x, 64) | (uint64_t)(uint32_t)__shfl((int)(uint32_t)(w8 >> 32), (int)x, 64) << 32;
-            return lane < s && x != lane && rc_text_less(a.T, (uint64_t)px + from, (uint64_t)p + from, wx, w8);   // (after the exchange: all lanes take part in it)
-        });
-        if (lane < s) a.keys[k0 + rank] = (w & ~a.pmask) | p;
-    }
-}
-
-// One thread per candidate: the column of its slot, whether it begins and ends a same-column run, and its LCP with the slot
-// before it, into arrays parallel to cand[]; the LCP with the slot after it only where that slot is not the next candidate
-// (there it is that candidate's).  Every LCP of the tail is computed here, once.
-#define RC_HEAD 0x80000000u
-#define RC_TAIL 0x40000000u
-#define RC_COL 0x3fffffffu
-__global__ __launch_bounds__(256) void k_cand_lcp(RankArgs a, uint64_t T, uint32_t *__restrict__ cf, uint32_t *__restrict__ lp, uint32_t *__restrict__ ln)
-{
-    constexpr int L = FBG_SLOTS_PACKED;
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    const uint64_t k = a.cand[t];
-    const uint64_t next_cand = t + 1 < T ? (uint64_t)a.cand[t + 1] : ~0ull;
-    const bool has_p = k > 0, has_n = k + 1 < a.N;
-    const uint64_t w = a.keys[k], wp = has_p ? a.keys[k - 1] : 0ull, wn = has_n ? a.keys[k + 1] : 0ull;
-    auto slot_of = [&](uint64_t word) {
-        Slot s;
-        s.key = word >> a.pb;
-        s.pos = word & a.pmask;
-        s.rem = rs_rem<L>(a, s.pos);
-        s.col = rs_col_of_rem(a, s.rem);
-        return s;
-    };
-    const Slot y = slot_of(w), x = slot_of(wp), z = slot_of(wn);
-    uint32_t f = y.col;
-    if (!(has_p && x.col == y.col)) f |= RC_HEAD;
-    if (!(has_n && z.col == y.col)) f |= RC_TAIL;
-    cf[t] = f;
-    lp[t] = has_p ? rs_pair_lcp(a, x, y) : 0u;
-    if (next_cand != k + 1) ln[t] = has_n ? rs_pair_lcp(a, y, z) : 0u;
-}
-
-// the LCP of the run's last member (candidate t + len - 1) with the slot after it
-__device__ __forceinline__ uint32_t rc_end_lcp(const RankArgs &a, uint64_t T, uint64_t t, uint64_t len, const uint32_t *__restrict__ lp,
-                                               const uint32_t *__restrict__ ln)
-{
-    const uint64_t e = t + len;
-    return e < T && a.cand[e] == a.cand[e - 1] + 1 ? lp[e] : ln[e - 1];
-}
-
-// One thread per candidate; the head of a same-column run (its members are consecutive candidates) takes the two running minima
-// over lp[] (fbg_ct_min_forward / _backward) and raises the column's maximum, as k_runs does.  A run of runs_wave_min members
-// and more is noted for k_cand_runs_long while the list has room.
-__global__ __launch_bounds__(256) void k_cand_runs(RankArgs a, uint64_t T, const uint32_t *__restrict__ cf, const uint32_t *__restrict__ lp,
-                                                   const uint32_t *__restrict__ ln, uint32_t *__restrict__ pm)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    const uint32_t f0 = cf[t], col = f0 & RC_COL;
-    if (col == (uint32_t)a.n || !(f0 & RC_HEAD)) return;             // '#' / sentinel: not a row pointer; inside a run
-    // the run's length: the tail flags, four candidates at a time
-    const uint64_t room = T - t;
-    uint64_t len = 0;
-    bool tried = false;
-    for (uint64_t i0 = 0; i0 < room && !len; i0 += 4) {
-        uint32_t g[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) g[q] = cf[min(t + i0 + q, T - 1)];
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            if (!len && i0 + q < room && (g[q] & RC_TAIL)) len = i0 + q + 1;
-        const uint64_t known = len ? len : i0 + 5;                     // members the run is known to have by now
-        if (!tried && a.runs_wave_min >= 2 && known >= a.runs_wave_min) {
-            tried = true;                                              // a long run: a wave walks it, unless the list is full
-            const unsigned long long e = atomicAdd(&a.counters[7], 1ull);
-            if (e < a.wl_cap) { a.wl[2 * e] = (uint32_t)t; a.wl[2 * e + 1] = a.cand[t]; return; }
-        }
-    }
-    if (!len) len = room;
-    const uint32_t n_mem = (uint32_t)len;
-    fbg_ct_min_forward(0u, n_mem, FBG_CT_NONE, [&](uint32_t i) { return lp[t + i]; }, [&](uint32_t i, uint32_t v) { pm[t + i] = v; });
-    const uint32_t end = rc_end_lcp(a, T, t, len, lp, ln);
-    uint32_t best = 0;
-    fbg_ct_min_backward(0u, n_mem, FBG_CT_NONE, [&](uint32_t i) { return i + 1 < n_mem ? lp[t + i + 1] : end; },
-                        [&](uint32_t i) { return pm[t + i]; }, [&](uint32_t, uint32_t g) { best = max(best, g); });
-    rs_update(a, col, best);                                           // (the members share their column)
-}
-
-// The runs k_cand_runs noted, a wave each: k_runs_long over the LCP arrays (no LCP computed again).
-__global__ __launch_bounds__(64) void k_cand_runs_long(RankArgs a, uint64_t T, const uint32_t *__restrict__ cf, const uint32_t *__restrict__ lp,
-                                                       const uint32_t *__restrict__ ln, uint32_t *__restrict__ pm)
-{
-    if (blockIdx.x >= a.counters[7]) return;                            // (the grid is wl_cap blocks)
-    const uint64_t t = a.wl[2 * blockIdx.x];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t col = cf[t] & RC_COL;
-    uint64_t len = 0;
-    uint32_t carry = FBG_CT_NONE;
-    for (uint64_t c0 = 0; t + c0 < T; c0 += 64) {                      // forward: minimum of LCP[head .. member]
-        const uint64_t idx = t + c0 + lane;
-        const bool valid = idx < T;
-        const uint32_t f = valid ? cf[idx] : 0u;
-        const unsigned long long stop = __ballot(valid && (f & RC_TAIL)), inval = __ballot(!valid);
-        const uint32_t first_stop = stop ? (uint32_t)__ffsll((long long)stop) - 1 : 64u, first_inv = inval ? (uint32_t)__ffsll((long long)inval) - 1 : 64u;
-        const uint32_t cnt = min(min(first_stop + 1, first_inv), 64u);  // members among these 64 candidates
-        uint32_t v = lane < cnt ? lp[idx] : FBG_CT_NONE;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(v, d, 64);
-            if (lane >= (uint32_t)d) v = min(v, o);
-        }
-        v = min(v, carry);
-        if (lane < cnt) pm[idx] = v;
-        carry = __shfl(v, 63, 64);
-        len += cnt;
-        if (first_stop < 64 || first_inv < 64) break;
-    }
-    if (len == 0) return;
-    const uint32_t end = rc_end_lcp(a, T, t, len, lp, ln);
-    uint32_t best = 0;
-    carry = FBG_CT_NONE;
-    for (uint64_t c0 = (len - 1) / 64 * 64;; c0 -= 64) {               // backward: minimum of LCP[member + 1 .. tail + 1], extension
-        const uint64_t i = c0 + lane;
-        uint32_t v = i < len ? (i + 1 < len ? lp[t + i + 1] : end) : FBG_CT_NONE;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_down(v, d, 64);
-            if (lane + (uint32_t)d < 64) v = min(v, o);
-        }
-        v = min(v, carry);
-        if (i < len) best = max(best, max(pm[t + i], v) + 1);          // (pm[t + i]: this lane's own store)
-        carry = __shfl(v, 0, 64);
-        if (c0 == 0) break;
-    }
-    for (int d = 32; d > 0; d >>= 1) best = max(best, (uint32_t)__shfl_xor(best, d, 64));
-    if (lane == 0) rs_update(a, col, best);
 }
 
 struct FinishArgs {
@@ -1384,14 +772,6 @@ __global__ void k_rank_finish(FinishArgs a)
     }
     a.out[x] = max((unsigned long long)a.out[x], fx);                     // 1681
 }
-
-// kernels exist for both slot layouts
-#define RS_LAUNCH(kernel, layout, grid, block, st, ...)                                                     \
-    do {                                                                                                    \
-        if ((layout) == FBG_SLOTS_PACKED) hipLaunchKernelGGL((kernel<FBG_SLOTS_PACKED>), grid, block, 0, st, __VA_ARGS__);  \
-        else if ((layout) == FBG_SLOTS_WIDE) hipLaunchKernelGGL((kernel<FBG_SLOTS_WIDE>), grid, block, 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kernel<FBG_SLOTS_PAIRS>), grid, block, 0, st, __VA_ARGS__);                                \
-    } while (0)
 
 #define RS_LAUNCH_SCAN(layout, plain, grid, st, args)                                                                         \
     do {                                                                                                                     \
@@ -1426,108 +806,42 @@ static int rs_join(fbg_ctx *ctx)
     FBG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_join, 0));
     return FBG_OK;
 }
+// From rs_scan_launch on k_tie_simple may be running on the aux stream: whichever way a driver is left, the aux stream is joined
+// first, so that no caller ever reuses or frees the buffers under it.  (The way out without an error joins by rs_join itself,
+// whose own error is then reported.)
+struct RsAuxJoin {
+    fbg_ctx *ctx;
+    ~RsAuxJoin() { if (ctx->aux_pending) (void)rs_join(ctx); }
+};
 
-// the list of the runs that get a wave each (its count is counters[7], zeroed with the other counters); which runs go there
-static int rs_wave_list(fbg_ctx *ctx, RankArgs &a)
-{
-    FBG_TRY(fbg_reserve(ctx, ctx->wave_list, (size_t)2 * RS_WAVE_LIST * 4));
-    a.wl = ctx->wave_list.as<uint32_t>();
-    const int64_t cap = ctx->opt.wave_list_cap;
-    a.wl_cap = cap > 0 && cap < RS_WAVE_LIST ? (uint32_t)cap : RS_WAVE_LIST;
-    a.runs_wave_min = ctx->opt.runs_wave_min > 0 ? (uint32_t)ctx->opt.runs_wave_min : 0u;
-    return FBG_OK;
-}
-
-// option cand_sort_check: count the places of the sorted list that do not ascend (a host round trip)
-static int rs_check_sorted(fbg_ctx *ctx, const uint32_t *sorted, uint64_t T)
+// The regions of the workgroups reserved, k_rank_scan_lean (*lean) or k_rank_scan launched over the owned slots with *rs_blocks
+// workgroups, and k_tie_pairs / k_tie_simple started on the aux stream (the caller holds an RsAuxJoin).  On return a.cand /
+// a.blk_count / a.region name the candidate regions: rs_tail_order takes it from there.
+static int rs_scan_launch(fbg_ctx *ctx, RankArgs &a, int layout, bool *lean_out, unsigned *blocks_out, int *launches)
 {
     hipStream_t st = ctx->stream;
-    unsigned long long *d_inv = &fbg_scalars(ctx)->cand_inversions, inv = 0;
-    FBG_HIP_TRY(ctx, hipMemsetAsync(d_inv, 0, sizeof(inv), st));
-    hipLaunchKernelGGL(k_cand_inversions, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, sorted, T, d_inv);
-    FBG_HIP_TRY(ctx, hipMemcpyAsync(&inv, d_inv, sizeof(inv), hipMemcpyDeviceToHost, st));
-    FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->diag.cand_inversions = (int64_t)inv;
-    return FBG_OK;
-}
-
-// The candidates, flat and unsorted in dp_e (or sorted in dp_a already: `sorted_already`): sorted (SA order), tie groups put in
-// final order (big_mode: k_tie_big's `exact`, 0 or 2).  On return a.cand / a.pm name the sorted list and its scratch.
-static int rs_order_candidates(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t T, bool sorted_already, int big_mode, int *launches)
-{
-    hipStream_t st = ctx->stream;
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_b, T * 4));
-    uint32_t *sorted = ctx->dp_a.as<uint32_t>();
-    uint32_t *flat = ctx->dp_e.as<uint32_t>();
-    if (!sorted_already)
-        FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
-            return rocprim::radix_sort_keys(tmp, bytes, flat, sorted, (size_t)T, 0u, 32u, st);
-        }));
-    if (ctx->opt.cand_sort_check) FBG_TRY(rs_check_sorted(ctx, sorted, T));
-    a.cand = sorted;
-    a.pm = ctx->dp_b.as<uint32_t>();
-    RS_LAUNCH(k_tie_groups, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T, 1, ctx->opt.tie_gallop != 0 ? 1 : 0);
-    RS_LAUNCH(k_tie_big, layout, dim3(RS_BIG_GROUPS), dim3(256), st, a, big_mode);
-    *launches += 3;
-    return FBG_OK;
-}
-
-// The candidates still in the regions of the lean scan's workgroups, each of which fits k_cand_region's LDS: sorted, written out
-// at their offsets and their tie groups put in final order by one kernel (option cand_tail; mx: the largest region's count, at
-// most RS_CAND_LDS).  On return a.cand / a.pm name the sorted list and its scratch, as after rs_order_candidates.
-static int rs_region_groups(fbg_ctx *ctx, RankArgs &a, unsigned rs_blocks, uint64_t T, uint32_t mx, const uint32_t *d_counts, const uint32_t *d_offs, int *launches)
-{
-    hipStream_t st = ctx->stream;
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_b, T * 4));
-    uint32_t *sorted = ctx->dp_a.as<uint32_t>();
-    // LDS by the largest region: the slots padded to a power of two, the words of the first RC_WORDS entries, the heads (every
-    // other entry at most) and a list that holds every group of more than RC_SMALL members a region can head
-    uint32_t pmax = 2;
-    while (pmax < mx) pmax <<= 1;
-    const uint32_t wcap = std::min<uint32_t>(mx, RC_WORDS), lcap = mx / (RC_SMALL + 1) + 1;
-    const size_t lds = (size_t)wcap * 8 + (size_t)pmax * 4 + (size_t)lcap * 4 + (size_t)(mx / 2 + 2) * 2;
-    hipLaunchKernelGGL(k_cand_region, dim3(rs_blocks), dim3(256), lds, st, a, d_counts, d_offs, sorted, ctx->opt.tie_gallop != 0 ? 1 : 0, mx, pmax, wcap, lcap);
-    if (ctx->opt.cand_sort_check) FBG_TRY(rs_check_sorted(ctx, sorted, T));
-    a.cand = sorted;
-    a.pm = ctx->dp_b.as<uint32_t>();
-    hipLaunchKernelGGL(k_tie_big<FBG_SLOTS_PACKED>, dim3(RS_BIG_GROUPS), dim3(256), 0, st, a, 2);
-    *launches += 2;
-    return FBG_OK;
-}
-
-// k_rank_scan over the owned slots, the small tie groups, then the candidates: compacted, sorted, tie groups put
-// in final order.  On return a.cand / a.pm name the sorted list and its scratch; *T = ~0 when a workgroup's
-// candidate region overflowed (similar rows: the caller takes another path).
-static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, int *launches)
-{
-    hipStream_t st = ctx->stream;
+    const RsScratch s = rs_scratch(ctx);
     const uint64_t own = a.own_hi - a.own_lo;
     const unsigned rs_blocks = fbg_blocks(own, RS_CHUNK, 256 * 16);
     const uint32_t region = (uint32_t)((own / rs_blocks) / 8 + 256);    // a workgroup may find 1/8 of its slots + slack
     const uint32_t tie_region = (uint32_t)((own / rs_blocks) / 6 + 256);
     FBG_TRY(fbg_reserve(ctx, ctx->list, (size_t)rs_blocks * region * 4));
     FBG_TRY(fbg_reserve(ctx, ctx->tie_list, (size_t)rs_blocks * tie_region * 4));
-    FBG_TRY(fbg_reserve(ctx, ctx->big_groups, RS_BIG_GROUPS * 8));
-    a.big = ctx->big_groups.as<uint32_t>();
-    if (!a.part_mode) FBG_TRY(rs_wave_list(ctx, a));
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_c, (size_t)(rs_blocks + 1) * 4));
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_d, (size_t)(rs_blocks + 1) * 4));
-    FBG_TRY(fbg_reserve(ctx, ctx->dp_f, (size_t)(rs_blocks + 1) * 4));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->dp_c.p, 0, (size_t)(rs_blocks + 1) * 4, st));
-    FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->dp_f.p, 0, (size_t)(rs_blocks + 1) * 4, st));
+    FBG_TRY(rs_tail_prepare(ctx, a));
+    FBG_TRY(fbg_reserve(ctx, s.counts, (size_t)(rs_blocks + 1) * 4));
+    FBG_TRY(fbg_reserve(ctx, s.offsets, (size_t)(rs_blocks + 1) * 4));
+    FBG_TRY(fbg_reserve(ctx, s.tie_count, (size_t)(rs_blocks + 1) * 4));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(s.counts.p, 0, (size_t)(rs_blocks + 1) * 4, st));
+    FBG_HIP_TRY(ctx, hipMemsetAsync(s.tie_count.p, 0, (size_t)(rs_blocks + 1) * 4, st));
     a.cand = ctx->list.as<uint32_t>();
-    a.blk_count = ctx->dp_c.as<uint32_t>(); a.region = region;
+    a.blk_count = s.counts.as<uint32_t>(); a.region = region;
     a.ties = ctx->tie_list.as<uint32_t>();
-    a.tie_count = ctx->dp_f.as<uint32_t>(); a.tie_region = tie_region;
+    a.tie_count = s.tie_count.as<uint32_t>(); a.tie_region = tie_region;
     FBG_TRY(fbg_stage_begin(ctx, FBG_STAGE_RANK_KERNEL));
     LeanArgs lf;
     const bool lean = layout == FBG_SLOTS_PACKED && a.g_min > (uint32_t)a.K && !a.values_only && !a.part_mode && !ctx->opt.rank_no_lean &&
                       rs_lean_setup(a, a.pb, rs_blocks, &lf);
     ctx->diag.rank_lean_launched = lean ? 1 : 0;
-    if (ctx->opt.cand_sort_check) ctx->diag.cand_inversions = 0;
-    ctx->diag.cand_tail_used = 0;
     if (lean)
     {
         // the symbols after the key from the MSD sort (these very slots, 2-bit symbols): the pairs carry a code in their spare
@@ -1539,9 +853,9 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
         }
         a.pair_stats = fbg_scalars(ctx)->pair_stats;
         FBG_HIP_TRY(ctx, hipMemsetAsync(a.pair_stats, 0, 2 * sizeof(unsigned long long), st));
-        FBG_TRY(fbg_reserve(ctx, ctx->ps_g, (size_t)rs_blocks * tie_region * 8));
-        FBG_TRY(fbg_reserve(ctx, ctx->ps_h, (size_t)rs_blocks * 4));
-        a.pairs = ctx->ps_g.as<uint2>(); a.pair_count = ctx->ps_h.as<uint32_t>();
+        FBG_TRY(fbg_reserve(ctx, s.pairs, (size_t)rs_blocks * tie_region * 8));
+        FBG_TRY(fbg_reserve(ctx, s.pair_count, (size_t)rs_blocks * 4));
+        a.pairs = s.pairs.as<uint2>(); a.pair_count = s.pair_count.as<uint32_t>();
         // the scan's arguments travel through memory (the host copy lives in the context: nothing to wait for)
         static_assert(sizeof(RankArgs) <= sizeof(ctx->kargs_host), "room for the scan's arguments");
         FBG_TRY(fbg_reserve(ctx, ctx->kargs, sizeof(RankArgs)));
@@ -1571,57 +885,8 @@ static int rs_classify(fbg_ctx *ctx, RankArgs &a, int layout, uint64_t *T_out, i
         RS_LAUNCH(k_tie_simple, layout, dim3(rs_blocks), dim3(256), ts, a);
     }
     *launches += 2;
-    // from here on k_tie_simple may be running on the aux stream: an error return joins it first, so that no caller
-    // ever reuses or frees the buffers under it
-    const int rc_rest = [&]() -> int {
-        // candidate counts per workgroup -> offsets; total and the largest count come back to the host
-        uint32_t *d_counts = a.blk_count, *d_offs = ctx->dp_d.as<uint32_t>();
-        uint32_t *d_max = reinterpret_cast<uint32_t *>(a.counters + 6);           // (the fused kernel: total, largest)
-        uint32_t tot = 0, mx = 0;
-        if (ctx->opt.cand_counts_fused) {
-            // one small kernel and one copy into pinned memory instead of a scan (two launches), a reduce and two copies
-            if (!ctx->pin_pair) FBG_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->pin_pair), 2 * sizeof(uint32_t), hipHostMallocDefault));
-            hipLaunchKernelGGL(k_cand_counts, dim3(1), dim3(RS_COUNTS_THREADS), 0, st, d_counts, (uint32_t)rs_blocks, d_offs, d_max);
-            FBG_HIP_TRY(ctx, hipMemcpyAsync(ctx->pin_pair, d_max, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-            tot = ctx->pin_pair[0]; mx = ctx->pin_pair[1];
-        } else {
-            FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
-                return rocprim::exclusive_scan(tmp, bytes, d_counts, d_offs, 0u, (size_t)(rs_blocks + 1), rocprim::plus<uint32_t>(), st);
-            }));
-            FBG_TRY(fbg_with_tmp(ctx, [&](void *tmp, size_t &bytes) {
-                return rocprim::reduce(tmp, bytes, d_counts, d_max, 0u, (size_t)rs_blocks, rocprim::maximum<uint32_t>(), st);
-            }));
-            FBG_HIP_TRY(ctx, hipMemcpyAsync(&tot, d_offs + rs_blocks, 4, hipMemcpyDeviceToHost, st));
-            FBG_HIP_TRY(ctx, hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, st));
-            FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
-        }
-        const uint64_t T = tot;
-        *T_out = T;
-        if (mx > region) { *T_out = ~0ull; return rs_join(ctx); }
-        if (T > 0) {
-            // k_rank_scan: workgroup b owns chunks b, b+G, ...: not contiguous -> compact, then sort.  k_rank_scan_lean: one
-            // stretch per workgroup -> every region sorted in LDS on its way out, where the largest fits
-            const int64_t cap_opt = ctx->opt.cand_lds_cap;
-            const uint32_t lds_cap = cap_opt > 0 && cap_opt < RS_CAND_LDS ? (uint32_t)cap_opt : RS_CAND_LDS;
-            const bool local = lean && ctx->opt.cand_local_sort && mx <= lds_cap;
-            ctx->diag.cand_local_sorted = local ? 1 : 0;
-            // the tail by member: packed slots (the lean scan's), columns that leave the two flag bits of k_cand_lcp free
-            const bool tail = local && ctx->opt.cand_tail != 0 && a.n <= RC_COL;
-            ctx->diag.cand_tail_used = tail ? 1 : 0;
-            if (tail) return rs_region_groups(ctx, a, rs_blocks, T, mx, d_counts, d_offs, launches);
-            if (local) {
-                FBG_TRY(fbg_reserve(ctx, ctx->dp_a, T * 4));
-                hipLaunchKernelGGL(k_cand_sort_compact, dim3(rs_blocks), dim3(256), 0, st, a.cand, d_counts, d_offs, region, ctx->dp_a.as<uint32_t>());
-            } else {
-                FBG_TRY(fbg_reserve(ctx, ctx->dp_e, T * 4));
-                hipLaunchKernelGGL(k_cand_compact, dim3(rs_blocks), dim3(256), 0, st, a.cand, d_counts, d_offs, region, ctx->dp_e.as<uint32_t>());
-            }
-            FBG_TRY(rs_order_candidates(ctx, a, layout, T, local, lean ? 2 : 0, launches));
-        }
-        return FBG_OK;
-    }();
-    if (rc_rest != FBG_OK) { (void)rs_join(ctx); return rc_rest; }
+    *lean_out = lean;
+    *blocks_out = rs_blocks;
     return FBG_OK;
 }
 
@@ -1690,34 +955,21 @@ int fbg_rank_scan_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeo
     FBG_TRY(fbg_reserve(ctx, ctx->gmax, (n + 1) * 4));             // (before rs_args_init reads the pointer)
     RankArgs a;
     rs_args_init(ctx, a, keys, vals, N, layout, geom.pb, geom.b, geom.key_bits, geom.K);
-    uint64_t T = 0;
     FBG_TRY(rs_zero_counters(ctx, cnt, N));
     FBG_HIP_TRY(ctx, hipMemsetAsync(ctx->gmax.p, 0, (n + 1) * 4, st));
     int reject = 0;
     FBG_TRY(rs_pick_threshold(ctx, a, keys, N, geom, &reject, &launches));
     if (reject) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);
-    FBG_TRY(rs_classify(ctx, a, layout, &T, &launches));
-    if (T == ~0ull) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);      // a region overflowed: record path
-    if (T > 0 && ctx->diag.cand_tail_used == 1) {
-        // every LCP once, by candidate; then the runs' minima over those arrays
-        // (k_tie_simple may be running on the aux stream: an error return joins it first, as in rs_classify)
-        int rc = fbg_reserve(ctx, ctx->cand_cf, T * 4);
-        if (rc == FBG_OK) rc = fbg_reserve(ctx, ctx->cand_lp, T * 4);
-        if (rc == FBG_OK) rc = fbg_reserve(ctx, ctx->cand_ln, T * 4);
-        if (rc != FBG_OK) { (void)rs_join(ctx); return rc; }
-        uint32_t *cf = ctx->cand_cf.as<uint32_t>(), *lp = ctx->cand_lp.as<uint32_t>(), *ln = ctx->cand_ln.as<uint32_t>();
-        hipLaunchKernelGGL(k_cand_lcp, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, a, T, cf, lp, ln);
-        hipLaunchKernelGGL(k_cand_runs, dim3(fbg_blocks(T, 256)), dim3(256), 0, st, a, T, cf, lp, ln, a.pm);
-        launches += 2;
-        if (a.runs_wave_min) { hipLaunchKernelGGL(k_cand_runs_long, dim3(a.wl_cap), dim3(64), 0, st, a, T, cf, lp, ln, a.pm); launches++; }
-    }
-    else if (T > 0) {
-        RS_LAUNCH(k_runs, layout, dim3(fbg_blocks(T, 64)), dim3(64), st, a, T);
-        launches++;
-        if (a.runs_wave_min) { RS_LAUNCH(k_runs_long, layout, dim3(a.wl_cap), dim3(64), st, a); launches++; }
-    }
+    const RsAuxJoin aux_joined{ctx};
+    bool lean = false;
+    unsigned rs_blocks = 0;
+    RsTail tail;
+    FBG_TRY(rs_scan_launch(ctx, a, layout, &lean, &rs_blocks, &launches));
+    FBG_TRY(rs_tail_order(ctx, a, layout, lean, rs_blocks, &tail, &launches));
+    FBG_TRY(rs_tail_runs(ctx, a, layout, tail, &launches));
     FBG_TRY(rs_join(ctx));
-    unsigned long long h[8], ps[2] = {0, 0};                           // h[7]: the runs k_runs noted for k_runs_long
+    if (tail.overflow) return fbg_stage_end(ctx, FBG_STAGE_RANKSCAN, launches);   // a region overflowed: record path
+    unsigned long long h[8], ps[2] = {0, 0};                           // h[7]: the runs noted for k_runs_long / k_cand_runs_long
     // a large tie group / an overflowing tie region -> record path; a column without a value lost all its rows
     // to the threshold -> redo without it
     if (a.g_min > 1)
@@ -1814,12 +1066,16 @@ int fbg_rank_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_
     }
     ctx->ix.part_gmin = a.g_min;
     if (good) {
-        uint64_t T = 0;
-        FBG_TRY(rs_classify(ctx, a, layout, &T, &launches));
+        const RsAuxJoin aux_joined{ctx};
+        bool lean = false;
+        unsigned rs_blocks = 0;
+        RsTail tail;
+        FBG_TRY(rs_scan_launch(ctx, a, layout, &lean, &rs_blocks, &launches));
+        FBG_TRY(rs_tail_order(ctx, a, layout, lean, rs_blocks, &tail, &launches));
         FBG_TRY(rs_join(ctx));
-        if (T == ~0ull) good = 0;
+        if (tail.overflow) good = 0;
         else {
-            ctx->ix.part_T = T;
+            ctx->ix.part_T = tail.T;
             unsigned long long h[2];                   // tie groups longer than 64 / tie regions too small raise [1]
             FBG_HIP_TRY(ctx, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
             FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1858,13 +1114,15 @@ int fbg_rank_part_runs(fbg_ctx *ctx, const uint8_t *d_blobs, uint32_t *d_gmax, i
     if (good) {
         RankArgs a;
         rs_part_args(ctx, a);
-        a.cand = ctx->dp_a.as<uint32_t>(); a.pm = ctx->dp_b.as<uint32_t>();
         hipLaunchKernelGGL(k_halo_import, dim3(1), dim3(FBG_PART_HALO), 0, st, d_blobs, ctx->ix.part, ctx->ix.nparts, a.own_lo,
                            a.own_hi, a.keys, a.vals);
         launches++;
         if (ctx->ix.part_T > 0) {
-            RS_LAUNCH(k_runs, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->ix.part_T, 64)), dim3(64), st, a, ctx->ix.part_T);
-            launches++;
+            // the candidates phase 1 left sorted (RsScratch's contract), walked by head: the halos hold what a run may reach into
+            RsTail tail;
+            tail.T = ctx->ix.part_T;
+            tail.tier = RsTier::by_head_radix;
+            FBG_TRY(rs_tail_runs(ctx, a, ctx->ix.rk_layout, tail, &launches));
             unsigned long long h[2];
             FBG_HIP_TRY(ctx, hipMemcpyAsync(h, a.counters, sizeof(h), hipMemcpyDeviceToHost, st));
             FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1927,11 +1185,7 @@ int fbg_rank_materialize(fbg_ctx *ctx, uint32_t *d_sa, uint32_t *d_isa, uint32_t
 {
     RankArgs a;
     rs_args_init(ctx, a, ctx->ix.rk_keys, ctx->ix.sa_ptr, ctx->N, ctx->ix.rk_layout, ctx->ix.rk_pb, ctx->ix.rk_b, ctx->ix.rk_key_bits, ctx->ix.rk_K);
-    FBG_TRY(fbg_reserve(ctx, ctx->big_groups, RS_BIG_GROUPS * 8));
-    a.big = ctx->big_groups.as<uint32_t>();
-    FBG_HIP_TRY(ctx, hipMemsetAsync(a.counters + 5, 0, sizeof(unsigned long long), ctx->stream));
-    RS_LAUNCH(k_tie_groups, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, ctx->N, 0, ctx->opt.tie_gallop != 0 ? 1 : 0);
-    RS_LAUNCH(k_tie_big, ctx->ix.rk_layout, dim3(RS_BIG_GROUPS), dim3(256), ctx->stream, a, 1);
+    FBG_TRY(rs_tail_order_all(ctx, a, ctx->ix.rk_layout));
     RS_LAUNCH(k_rank_materialize, ctx->ix.rk_layout, dim3(fbg_blocks(ctx->N, 256)), dim3(256), ctx->stream, a, d_sa, d_isa, d_pl, d_pr);
     FBG_HIP_TRY(ctx, hipGetLastError());
     return FBG_OK;

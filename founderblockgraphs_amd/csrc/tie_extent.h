@@ -1,5 +1,5 @@
 // tie_extent.h -- how many consecutive slots of a sorted array carry one key, in O(log s) reads.
-// Plain C++ (no HIP types): rank_scan.hip's k_tie_groups and the CPU check in host/host_selftest.cpp share it.
+// Plain C++ (no HIP types): rank_tail.hip's k_tie_groups and k_cand_region and the CPU check in host/host_selftest.cpp share it.
 #pragma once
 #include <stdint.h>
 

@@ -1,4 +1,4 @@
-"""The tail of the rank-order scan worked by member (option cand_tail; rank_scan.hip: k_cand_region, k_cand_lcp, k_cand_runs,
+"""The tail of the rank-order scan worked by member (option cand_tail; rank_tail.hip: k_cand_region, k_cand_lcp, k_cand_runs,
 k_cand_runs_long) against the oracle and against the kernels by head (cand_tail = 0), on inputs whose tie groups and same-column
 runs are of every size the kernels tell apart and cross the regions of the scan's workgroups.
 
@@ -85,7 +85,7 @@ def _run_lengths(v):
 
 
 def region_slots(n_slots):
-    """Slots of one workgroup of the lean scan (rank_scan.hip: rs_classify's grid, rs_lean_setup's per_wave)."""
+    """Slots of one workgroup of the lean scan (rank_scan.hip: rs_scan_launch's grid, rs_lean_setup's per_wave)."""
     blocks = min(-(-n_slots // 1024), 4096)
     per_wave = -(-(-(-n_slots // (blocks * 4))) // 58) * 58       # a wave's share, rounded up to whole rows of 58 slots
     return 4 * per_wave
@@ -153,18 +153,26 @@ SETTINGS = {
     "min0": {"FBG_RUNS_WAVE_MIN": "0"},
     "min2": {"FBG_RUNS_WAVE_MIN": "2"},
     "lds_cap8": {"FBG_CAND_LDS_CAP": "8"},
+    # the kernels by head behind the lean scan with the wave-list settings (with cand_tail = 1, the default, those above reach the
+    # kernels by member only): k_runs' "list full, walk it yourself" branch, no list at all, and k_runs_long from two members on
+    "by_head_cap1": {"FBG_CAND_TAIL": "0", "FBG_WAVE_LIST_CAP": "1"},
+    "by_head_min0": {"FBG_CAND_TAIL": "0", "FBG_RUNS_WAVE_MIN": "0"},
+    "by_head_min2": {"FBG_CAND_TAIL": "0", "FBG_RUNS_WAVE_MIN": "2"},
 }
+# the by_head_* settings on the two inputs that hold the run of three chunks and a part and the runs of 3, 15, 16 and 17 that cross regions
+CASES = [(name, setting) for name in ("planted", "plantedT256", "plantedT200", "tiled") for setting in SETTINGS
+         if not setting.startswith("by_head_") or name in ("plantedT200", "tiled")]
 
 
-@pytest.mark.parametrize("setting", list(SETTINGS))
-@pytest.mark.parametrize("name", ["planted", "plantedT256", "plantedT200", "tiled"])
+@pytest.mark.parametrize("name,setting", CASES, ids=[f"{name}-{setting}" for name, setting in CASES])
 def test_tail_by_member_equals_oracle(engine, name, setting):
     """f, v, the suffix array and both neighbour LCPs equal the oracle's and the sorted candidate list ascends, with the tail by
-    member and by head, with a wave list of one entry, with runs_wave_min 0 and 2, and with the regions' LDS capacity forced to 8
-    entries (the kernels by head after the radix sort); a second build on the same engine gives the same arrays."""
+    member and by head, with a wave list of one entry, with runs_wave_min 0 and 2 (each of the three by member and by head), and
+    with the regions' LDS capacity forced to 8 entries (the kernels by head after the radix sort); a second build on the same
+    engine gives the same arrays."""
     check_input(name)
     ref = _case(name)
-    by_member = setting not in ("by_head", "lds_cap8")
+    by_member = not setting.startswith("by_head") and setting != "lds_cap8"
     with fbg_options(engine, dict(SETTINGS[setting], FBG_MSD_MIN="1", FBG_CAND_SORT_CHECK="1")):
         for again in range(2 if setting == "tail" else 1):
             assert np.array_equal(engine.elastic_f(ref["msa"]), ref["f"]), again
@@ -175,7 +183,8 @@ def test_tail_by_member_equals_oracle(engine, name, setting):
             assert got["cand_tail_used"] == (1 if by_member else 0)
             assert got["cand_local_sorted"] == (0 if setting == "lds_cap8" else 1)
             assert got["cand_inversions"] == 0
-            assert got["wave_runs"] == 0 if setting == "min0" else got["wave_runs"] == 1 if setting == "cap1" else got["wave_runs"] >= (4 if setting == "min2" else 1)
+            waves = setting.replace("by_head_", "")
+            assert got["wave_runs"] == 0 if waves == "min0" else got["wave_runs"] == 1 if waves == "cap1" else got["wave_runs"] >= (4 if waves == "min2" else 1)
             _check_index(engine, ref)
         assert np.array_equal(engine.repeatfree_v(ref["msa"]), ref["v"])          # (its index is that of the reversed text)
         assert engine.get_option("rank_lean_used") == 1

@@ -4,7 +4,7 @@ The scan in suffix order of an MSA with gaps (csrc/gapped_rank.hip) answers "whi
 pointer of its row for" from a table of 16 bytes per 128 text positions (GWin: up to two gap runs, 16-bit run lengths, the
 run before the window's first position apart in lo0); a position that points for more than GR_LONG columns leaves the
 per-slot path; tie groups of up to GR_MAX_TIE suffixes are ordered in place, larger ones send the MSA to the record path.
-The rank-order scan of a gap-free MSA (csrc/rank_scan.hip, rank_common.h) settles tie groups of up to RS_TG inside the
+The rank-order scan of a gap-free MSA (csrc/rank_scan.hip, rank_tail.hip, rank_common.h) settles tie groups of up to RS_TG inside the
 scan, up to 64 from the candidate list, and declines beyond; it walks the slots in chunks of RS_CHUNK with RS_HALO slots
 either side, the classification of gapped_rank.hip in stretches of GR_SEG.  fbg_block_graph (csrc/block_graph.hip)
 groups a block's labels in LDS up to 4096 rows (above 2048 only with a raised dynamic LDS limit), in device memory up to
@@ -333,7 +333,7 @@ def test_tie_inputs_have_groups_of_the_size_asked_for(k, entangled, variant):
     want = 2 * k if entangled else k
     # one group per start column 100 .. 100 + PLANT - 32, none larger anywhere
     assert sizes.max() == want and int((sizes == want).sum()) >= PLANT - 32 + 1, (k, entangled, variant, np.bincount(sizes))
-    assert 4 * int(sizes.sum()) < len(T)         # far from "a quarter of the slots tie" (rank_scan.hip:31)
+    assert 4 * int(sizes.sum()) < len(T)         # far from "a quarter of the slots tie" (rank_scan.hip:33)
     assert len(T) == text_length(msa)
     assert len(T) == 80 * 401 + 1 or variant == "gaps"
     assert (ord("N") in msa) == (variant == "ignore") and (GAP in msa) == (variant == "gaps")
@@ -437,10 +437,11 @@ def _tie_kind(size, fast, limit=64):
 @pytest.mark.parametrize("k,entangled", TIE_CASES)
 def test_tie_groups_of_exact_sizes_gap_free(engine, k, entangled):
     """rank_scan.hip / rank_common.h: a tie group of up to RS_TG = 4 suffixes is settled inside the scan (rank_common.h:7,
-    :167-172, k_tie_simple rank_scan.hip:464-494), up to 64 by k_tie_groups from the candidate list (:608-648, `s > 64`
-    :618), more go to k_tie_big, which raises the fallback flag for more than 64 members with K real symbols (:655, :696).
+    :189-194, k_tie_simple rank_scan.hip:543-582), up to 64 by k_tie_groups from the candidate list (rank_tail.hip:113-156,
+    `s > 64` :126), more go to k_tie_big, which raises the fallback flag for more than 64 members with K real symbols (:166,
+    :207).
     Groups of exactly 2, 4, 5, 63, 64, 65 and 66 suffixes, and of 4, 64 and 66 whose members share columns pairwise (the
-    runs of k_runs, :753).  f (fbg.cpp:1579-1695, the walk 1633-1678), v (fbg.cpp:552-611) and the index arrays.
+    runs of k_runs, rank_tail.hip:241).  f (fbg.cpp:1579-1695, the walk 1633-1678), v (fbg.cpp:552-611) and the index arrays.
     index_kind: with pure_scan = -1 the rank-order scan is the only fast path: 1 up to 64 members, 0 (records) from 65 on;
     likewise under force_wide, a layout the group-level scan does not take (pure_scan.hip:315).  With the default options
     a decline of the rank-order scan is followed by the group-level scan (suffix_sort.hip:878-879), which holds groups of
@@ -472,8 +473,8 @@ def test_tie_groups_of_exact_sizes_with_gaps_or_ignore_characters(engine, k, ent
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", sorted(CHUNK_SHAPES))
 def test_gap_free_text_lengths_on_chunk_edges(engine, N):
-    """rank_scan.hip: k_rank_scan stages RS_CHUNK = 1024 slots and RS_HALO = 8 either side (:46, rank_common.h:137; the
-    last chunk's hi_i :73, :92, the first chunk's lo_i :72, :91).  Texts of 1024, 1025, 2047, 2048 and 2049 symbols over
+    """rank_scan.hip: k_rank_scan stages RS_CHUNK = 1024 slots and RS_HALO = 8 either side (:50, rank_common.h:159; the
+    last chunk's hi_i :77, :96, the first chunk's lo_i :76, :95).  Texts of 1024, 1025, 2047, 2048 and 2049 symbols over
     AC with shared stretches, so that tie groups and runs lie at the chunk ends.  f (fbg.cpp:1579-1695), v
     (fbg.cpp:552-611) and the index arrays."""
     msa, _, ref = reference("chunk", N)

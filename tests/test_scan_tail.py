@@ -1,4 +1,4 @@
-"""The tail of the rank-order scan (rank_scan.hip): coded tied pairs settled inside the lean scan kernel (option
+"""The tail of the rank-order scan (rank_scan.hip, rank_tail.hip): coded tied pairs settled inside the lean scan kernel (option
 pairs_in_scan), long same-column runs walked by a wave each (k_runs_long; options runs_wave_min, wave_list_cap), the
 candidate regions sorted in LDS (cand_local_sort).  Whatever the settings: f, v, the suffix array and the LCPs of the oracle."""
 import numpy as np

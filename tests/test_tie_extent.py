@@ -1,4 +1,4 @@
-"""The size of a tie group by galloping (csrc/tie_extent.h, shared with rank_scan.hip's k_tie_groups) against the plain count,
+"""The size of a tie group by galloping (csrc/tie_extent.h, shared with rank_tail.hip's k_tie_groups and k_cand_region) against the plain count,
 on the CPU: founderblockgraphs_amd/fbg_host_selftest tie-extent (g++, no GPU)."""
 import os
 import re
