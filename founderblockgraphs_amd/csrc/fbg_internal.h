@@ -169,7 +169,7 @@ struct fbg_ctx {
     uint64_t alloc_calls = 0, alloc_us = 0;   // device allocations of the context so far and the host time they took (free + malloc)
     std::vector<DevBuf *> bufs;    // every buffer reserved for this context (fbg_reserve); fbg_ctx_destroy walks it
 
-    // ---- per-stage tables: record path (suffix_sort.hip, lcp.hip, scan.hip) ----
+    // ---- per-stage tables: record path (record_sort.hip, lcp.hip, scan.hip) ----
     DevBuf prow;               // u32[m*n]: text pointer of cell (i,x), row-major (gapped MSAs only)
     DevBuf igrow;              // u32[m*n]: first ignore-char column >= x, row-major (ignore chars only)
     DevBuf rec;                // uint4[N] by text position: {rank, lcp-prev | hint<<31, lcp-next | hint<<31, 0}
@@ -251,7 +251,7 @@ struct FbgScalars {
     unsigned long long graph_collision;          // block_graph.hip: two labels share a hash
     unsigned long long pair_stats[2];            // rank_scan.hip: tied pairs of the lean scan settled by the extra symbols / by the text
     unsigned long long cand_inversions;          // rank_tail.hip: option cand_sort_check
-    unsigned long long by_position;              // suffix_sort.hip: the records by position are no permutation
+    unsigned long long by_position;              // record_sort.hip: the records by position are no permutation
     alignas(64) unsigned long long gapped[8 + 66];   // gapped_rank.hip: GrsArgs::counters and the threshold histogram behind them
     alignas(64) unsigned long long span[34];     // span_scan.hip: SpArgs::counters
 };
@@ -350,6 +350,11 @@ int fbg_span_try(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, const KeyGeom &g,
 int fbg_span_rescan(fbg_ctx *ctx, int disable_tricks, int *ok);
 int fbg_build_cell_tables(fbg_ctx *ctx);                                                                // text_build.hip
 int fbg_key_setup(fbg_ctx *ctx, bool compact, KeyGeom *g, int *launches);                                // suffix_sort.hip
+int fbg_record_sort(fbg_ctx *ctx, const KeyGeom &g, int *launches);                                      // record_sort.hip
+// equal neighbours among the S keys of a sorted sample (suffix_sort.hip), counted in the caller's scalar word and brought back;
+// a suffix with a twin somewhere is a sample twin with probability S / N: twins * N / S^2 estimates the fraction that ties
+int fbg_count_equal_neighbours(fbg_ctx *ctx, const uint64_t *sorted, uint64_t S, unsigned long long *d_word, unsigned long long *twins);
+inline bool fbg_twins_say_similar(uint64_t twins, uint64_t N, uint64_t S) { return (double)twins * (double)N / ((double)S * (double)S) > 0.5; }
 int fbg_rank_part_classify(fbg_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t count, const KeyGeom &g, int pre_ok,
                            uint8_t *d_blob, int *ok);                         // rank_scan.hip
 int fbg_rank_part_runs(fbg_ctx *ctx, const uint8_t *d_blobs, uint32_t *d_gmax, int *ok);

@@ -37,6 +37,7 @@
 // characters, and more than 65534 rows.  A position that is the pointer for more than 64 columns (long gap runs, the
 // gaps a row starts or ends with) gets a wave of its own.
 #include "fbg_internal.h"
+#include "keys.h"
 #include "text_cmp.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
@@ -85,13 +86,6 @@ struct GrsArgs {
     uint32_t *longs;                 // slots with long spans
     unsigned long long *counters;    // [0] candidates, [1] decline flag, [2] long slots, [3] columns to redo, [4] their slots, [6] long runs
 };
-
-__device__ __forceinline__ uint32_t gr_key_lcp(uint64_t a, uint64_t c, int b, int key_bits)
-{
-    const uint64_t d = a ^ c;
-    const uint32_t bits = (uint32_t)(__clzll((long long)d) - (64 - key_bits));
-    return (bits * ((65536u + (uint32_t)b - 1) / (uint32_t)b)) >> 16;
-}
 
 // row of text position p: the last row that starts at or before it
 __device__ __forceinline__ uint32_t gr_row_of(const uint32_t *__restrict__ pos, uint32_t m, uint32_t p)
@@ -277,7 +271,7 @@ __device__ __forceinline__ uint32_t gr_slot_lcp(const GrsArgs &a, uint64_t k)
 {
     if (k <= a.lim_lo || k >= a.lim_hi) return 0;
     const uint64_t x = a.keys[k - 1], y = a.keys[k];
-    if (x != y) return gr_key_lcp(x, y, a.b, a.key_bits);
+    if (x != y) return fbg_key_lcp(x, y, a.b, a.key_bits);
     return fbg_clamp_lcp(fbg_extend_match(a.T, (uint64_t)(a.vals[k - 1] & a.vmask) + a.K, (uint64_t)(a.vals[k] & a.vmask) + a.K, 0) + (uint32_t)a.K);
 }
 
@@ -292,7 +286,7 @@ __global__ __launch_bounds__(256) void k_grs_sample(GrsArgs a, uint64_t stride, 
     if (i < GR_SAMPLE && s + 1 < a.own_hi) {
         const uint64_t kp = a.keys[s - 1], k = a.keys[s], kn = a.keys[s + 1];
         uint32_t g = (uint32_t)a.K + 1;
-        if (kp != k && kn != k) g = max(gr_key_lcp(kp, k, a.b, a.key_bits), gr_key_lcp(k, kn, a.b, a.key_bits)) + 1;
+        if (kp != k && kn != k) g = max(fbg_key_lcp(kp, k, a.b, a.key_bits), fbg_key_lcp(k, kn, a.b, a.key_bits)) + 1;
         atomicAdd(&h[min(g, 65u)], 1u);
     }
     __syncthreads();
@@ -447,7 +441,7 @@ __device__ __forceinline__ void gr_slot(const GrsArgs &a, bool in, uint64_t s, u
     const uint32_t v = in ? a.vals[s] : 0u;
     const bool tie = in && ((has_prev && kp == key) || (has_next && kn == key));
     uint32_t g = 0;
-    if (in && !tie) g = max(has_prev ? gr_key_lcp(kp, key, a.b, a.key_bits) : 0u, has_next ? gr_key_lcp(key, kn, a.b, a.key_bits) : 0u) + 1;   // 1656
+    if (in && !tie) g = max(has_prev ? fbg_key_lcp(kp, key, a.b, a.key_bits) : 0u, has_next ? fbg_key_lcp(key, kn, a.b, a.key_bits) : 0u) + 1;   // 1656
     gr_slot_core(a, in, s, v, key, tie, g, in && has_prev, in && has_next, stage, stage_fill);
 }
 
@@ -586,7 +580,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_grs_classify(GrsArgs a, uint32_t
         for (int j = 1; j < 8; j++) {
             const bool both = ex[j - 1] && ex[j];
             eq[j] = both && K[j - 1] == K[j];
-            L[j] = (both && !eq[j]) ? gr_key_lcp(K[j - 1], K[j], a.b, a.key_bits) : 0u;
+            L[j] = (both && !eq[j]) ? fbg_key_lcp(K[j - 1], K[j], a.b, a.key_bits) : 0u;
         }
         // slots 1 .. 6 of K (s0 - 1 .. s0 + 4): tie, g, "the scan skips it" (regular, no tie, g < t)
         bool tie[8], skip[8];
@@ -699,8 +693,8 @@ __global__ __launch_bounds__(256) void k_grs_long(GrsArgs a, uint32_t count)
     const bool tie = (has_prev && kp == key) || (has_next && kn == key);
     uint32_t fi0 = 0;
     if (!tie) {
-        const uint32_t lp = has_prev ? gr_key_lcp(kp, key, a.b, a.key_bits) : 0u;
-        const uint32_t ln = has_next ? gr_key_lcp(key, kn, a.b, a.key_bits) : 0u;
+        const uint32_t lp = has_prev ? fbg_key_lcp(kp, key, a.b, a.key_bits) : 0u;
+        const uint32_t ln = has_next ? fbg_key_lcp(key, kn, a.b, a.key_bits) : 0u;
         fi0 = gr_extent(a, p, row, max(lp, ln) + 1, key, true, w);
     }
     // (x_lo .. x_hi, slot) -> candidates, lanes over the columns; self: direct updates where no neighbour shares the column

@@ -27,6 +27,13 @@
 // prints the table of pindex_stage.h as it acts: "stages NAME ...", then per stage X "begin X" and the stages still done when
 // every stage was done and X begins, then per subset of done stages (bit i of MASK: stage i, marked by ps_finish) "need MASK"
 // and per stage "-" where ps_missing finds it and its ancestors done, else the stage it names.
+//     fbg_host_selftest keys
+// checks keys.h against the plain definition of a key (the codes of a position up to the first separator, then zeros, most
+// significant first): msd_build_keys, k_pack's two steps (rolling, then symbol by symbol when a separator was seen), the 2-bit
+// gather and the one-symbol rule, over tiles with one separator at every offset in reach and beyond, with two and with none, in
+// the compact coding and (rolling alone, codes up to 255) in the plain one, at the geometries where a path or a mask changes;
+// fbg_key_lcp against a comparison symbol by symbol on pairs that part at every symbol.  Prints "keys ok GEOMETRIES TILES PAIRS"
+// or the first case that differs.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -39,6 +46,7 @@
 #include "../cand_tail.h"
 #include "../twin_hash.h"
 #include "../pindex_stage.h"
+#include "../keys.h"
 
 static int tie_extent_selftest()
 {
@@ -206,6 +214,106 @@ static int cand_tail_selftest()
     return 0;
 }
 
+// the definition: the codes of position p up to the first separator, then zeros
+static uint64_t naive_key(const uint8_t *codes, int p, int b, int K, bool compact)
+{
+    uint64_t key = 0;
+    int k = 0;
+    for (; k < K && !(compact && codes[p + k] >= 0x80); k++) key = (key << b) | codes[p + k];
+    for (; k < K; k++) key <<= b;
+    return key;
+}
+
+static int keys_selftest()
+{
+    struct Geom { int b, K; bool compact; };
+    std::vector<Geom> geoms;
+    const int bk[][2] = {{1, 64}, {2, 1}, {2, 16}, {2, 25}, {2, 26}, {3, 1}, {3, 21}, {5, 1}, {5, 12}, {7, 1}, {7, 9}, {8, 1}, {8, 8}};
+    for (const auto &g : bk) {
+        if (g[0] < 8) geoms.push_back({g[0], g[1], true});      // the compact coding keeps bit 7 for the separator flag
+        geoms.push_back({g[0], g[1], false});
+    }
+    const int t0 = 8, items = FBG_KEY_ITEMS;
+    uint64_t store[16];                                         // 128 codes, aligned for the gather's 8-byte reads
+    uint8_t *tile = reinterpret_cast<uint8_t *>(store);
+    uint64_t seed = 0x9e3779b97f4a7c15ull;
+    auto next = [&]() { seed = seed * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(seed >> 33); };
+    unsigned long long n_tiles = 0, n_pairs = 0;
+    for (const Geom &g : geoms) {
+        const int b = g.b, K = g.K, reach = K + items - 1;
+        const int far = reach > 40 ? reach : 40;                // (the gather reads 32 codes, more than it needs for a short key)
+        // sep = t0 + o: one separator there; o == far + 1: none; o == far + 2: one as the first symbol and one three further on
+        for (int o = 0; o <= far + 2; o++) {
+            if (!g.compact && o <= far) continue;               // no separators in the plain coding: two tiles of plain codes
+            for (int k = 0; k < 128; k++) tile[k] = (uint8_t)(next() & ((1u << b) - 1));
+            if (g.compact && o <= far) tile[t0 + o] = FBG_SEP;
+            if (g.compact && o == far + 2) tile[t0] = tile[t0 + 3] = FBG_SEP;
+            uint64_t want[FBG_KEY_ITEMS], w[FBG_KEY_ITEMS];
+            for (int i = 0; i < items; i++) want[i] = naive_key(tile, t0 + i, b, K, g.compact);
+            auto differs = [&](const char *what) {
+                for (int i = 0; i < items; i++)
+                    if (w[i] != want[i]) {
+                        std::printf("keys: %s differs: b %d K %d compact %d tile %d position %d: %llx, not %llx\n", what, b, K, (int)g.compact, o, i,
+                                    (unsigned long long)w[i], (unsigned long long)want[i]);
+                        return true;
+                    }
+                return false;
+            };
+            // k_pack: rolling, and in the compact coding symbol by symbol when a separator was seen
+            std::memset(w, 0xee, sizeof w);
+            const uint32_t seen = fbg_keys_rolling(tile, t0, b, K, w);
+            if (g.compact && (seen & FBG_SEP)) fbg_keys_by_symbol(tile, t0, b, K, w);
+            if (differs("k_pack's two steps")) return 1;
+            if (g.compact) {
+                std::memset(w, 0xee, sizeof w);
+                msd_build_keys(tile, t0, b, K, w);
+                if (differs("msd_build_keys")) return 1;
+                std::memset(w, 0xee, sizeof w);
+                fbg_keys_by_symbol(tile, t0, b, K, w);
+                if (differs("fbg_keys_by_symbol")) return 1;
+            }
+            if (g.compact && b == 2 && reach <= 32 && o >= 32 && o <= far + 1) {      // no separator among the 32 codes it reads
+                std::memset(w, 0xee, sizeof w);
+                if (fbg_keys_gather2(tile, t0, K, w)) { std::printf("keys: the gather saw a separator that is not there\n"); return 1; }
+                if (differs("fbg_keys_gather2")) return 1;
+            }
+            // the one-symbol rule, as sample_key applies it
+            for (int i = 0; i < items; i++) {
+                bool dead = false;
+                w[i] = 0;
+                for (int k = 0; k < K; k++) w[i] = (w[i] << b) | fbg_key_symbol(tile[t0 + i + k], g.compact ? 1 : 0, dead);
+            }
+            if (differs("fbg_key_symbol")) return 1;
+            n_tiles++;
+        }
+    }
+    // LCP of two keys that part at symbol j
+    for (int b = 1; b <= 8; b++)
+        for (const int K : {1, 64 / b}) {
+            const int key_bits = K * b;
+            const uint64_t sym = (1ull << b) - 1;
+            for (int j = 0; j < K; j++) {
+                uint64_t a = 0, c = 0;
+                for (int k = 0; k < K; k++) {
+                    const uint64_t x = next() & sym, y = k < j ? x : k == j ? (x + 1 + next() % sym) & sym : next() & sym;
+                    a = (a << b) | x;
+                    c = (c << b) | y;
+                }
+                uint32_t want = 0;
+                while (((a >> (b * (K - 1 - (int)want))) & sym) == ((c >> (b * (K - 1 - (int)want))) & sym)) want++;
+                const uint32_t got = fbg_key_lcp(a, c, b, key_bits), back = fbg_key_lcp(c, a, b, key_bits);
+                const uint32_t inv = fbg_key_lcp_inv(a, c, fbg_key_inv(b), key_bits);
+                if ((int)want != j || got != want || back != want || inv != want) {
+                    std::printf("keys: LCP differs: b %d K %d symbol %d: %u %u %u, not %u\n", b, K, j, got, back, inv, want);
+                    return 1;
+                }
+                n_pairs++;
+            }
+        }
+    std::printf("keys ok %llu %llu %llu\n", (unsigned long long)geoms.size(), n_tiles, n_pairs);
+    return 0;
+}
+
 static int pindex_stages_selftest()
 {
     std::printf("stages");
@@ -272,6 +380,7 @@ int main(int argc, char **argv)
     if (argc == 2 && std::string(argv[1]) == "tie-extent") return tie_extent_selftest();
     if (argc == 2 && std::string(argv[1]) == "cand-tail") return cand_tail_selftest();
     if (argc == 2 && std::string(argv[1]) == "pindex-stages") return pindex_stages_selftest();
+    if (argc == 2 && std::string(argv[1]) == "keys") return keys_selftest();
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s FASTA GAP_LIMIT ELASTIC PATHS OUT.gfa [BOUNDARY ...]\n", argv[0]);
         return 2;

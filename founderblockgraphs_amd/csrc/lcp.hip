@@ -5,10 +5,10 @@
 //     lcp_next = lcp(T[p..], T[SA[r+1]..])      (= LCP[ISA[p]+1],   0 for the last suffix)
 // These two numbers are all the reference's suffix-tree walk ever extracts for a leaf at the edge of a
 // run: depth(parent(w)) in fbg.cpp:1656 is a minimum of such values.  They are
-// written into words y/z of the position's record (suffix_sort.hip), bit 31 carrying the run hint:
+// written into words y/z of the position's record (record_sort.hip), bit 31 carrying the run hint:
 // "the SA neighbour can be a coloured row pointer in the same column as p".
 //
-// suffix_sort.hip already derives both words from the sorted keys when few suffixes tie on their first
+// record_sort.hip already derives both words from the sorted keys when few suffixes tie on their first
 // K symbols and the MSA has no gaps.  This kernel is used otherwise (similar rows: long matches; gaps:
 // the hint needs the column interval of each pointer).  Each thread walks a chunk of consecutive text
 // positions and carries the match length from p to p+1 (lcp(p+1, .) >= lcp(p, .) - 1, Kasai et al.),

@@ -1,10 +1,10 @@
-// msd_keys.h -- key building shared by the MSD sorts (msd_sort.hip, msd_sort_pairs.hip): the symbol codes of a tile
-// of text into LDS, then the keys of a thread's 8 consecutive positions.  Same keys as k_pack (suffix_sort.hip).
+// msd_keys.h -- the tiles of the MSD sorts (msd_sort.hip, msd_sort_pairs.hip): the symbol codes of a tile of text into
+// LDS, from which msd_build_keys (keys.h) makes the keys of a thread's 8 consecutive positions; cursors and wave sums.
 #pragma once
 #include <stdint.h>
+#include "keys.h"
 
-#define MSD_SEP 0x80                           // FBG_SEP of suffix_sort.hip
-#define MSD_ITEMS 8
+#define MSD_ITEMS FBG_KEY_ITEMS
 
 // Pass 1 of both sorts keeps one run cursor per stretch (bucket d of nb, part xq of xs: one part per XCD).  The stretch's
 // number d * xs + xq says where it lies in the pass-1 buffer and in tile_start; its cursor lies at xq * nb + d (contig,
@@ -38,7 +38,7 @@ __device__ __forceinline__ void msd_store_tile(uint8_t *tile, const uint8_t *cd,
     uint64_t codes = 0;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-        const uint32_t c = (FULL || p + j < N) ? cd[(raw >> (8 * j)) & 255u] : (uint32_t)MSD_SEP;
+        const uint32_t c = (FULL || p + j < N) ? cd[(raw >> (8 * j)) & 255u] : (uint32_t)FBG_SEP;
         codes |= (uint64_t)c << (8 * j);
     }
     *reinterpret_cast<uint64_t *>(tile + k8) = codes;
@@ -48,7 +48,7 @@ __device__ __forceinline__ void msd_store_tile(uint8_t *tile, const uint8_t *cd,
         uint64_t codes2 = 0;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const uint32_t c = (FULL || q + j < N) ? cd[(raw2 >> (8 * j)) & 255u] : (uint32_t)MSD_SEP;
+            const uint32_t c = (FULL || q + j < N) ? cd[(raw2 >> (8 * j)) & 255u] : (uint32_t)FBG_SEP;
             codes2 |= (uint64_t)c << (8 * j);
         }
         *reinterpret_cast<uint64_t *>(tile + kk) = codes2;
@@ -68,7 +68,7 @@ __device__ __forceinline__ void msd_store_tile_batched(uint8_t *tile, const uint
     for (int j = 0; j < 8; j++) c[j] = cd[(raw >> (8 * j)) & 255u];
     uint64_t codes = 0;
 #pragma unroll
-    for (int j = 0; j < 8; j++) codes |= (uint64_t)((FULL || p + j < N) ? c[j] : (uint32_t)MSD_SEP) << (8 * j);
+    for (int j = 0; j < 8; j++) codes |= (uint64_t)((FULL || p + j < N) ? c[j] : (uint32_t)FBG_SEP) << (8 * j);
     *reinterpret_cast<uint64_t *>(tile + k8) = codes;
     // the 64 bytes of lookahead: threads 0 .. 7 hold them (msd_fetch_raw); their wave does 8 more lookups, in one batch too
     if (threadIdx.x < 8) {
@@ -78,7 +78,7 @@ __device__ __forceinline__ void msd_store_tile_batched(uint8_t *tile, const uint
         for (int j = 0; j < 8; j++) c[j] = cd[(raw2 >> (8 * j)) & 255u];
         uint64_t codes2 = 0;
 #pragma unroll
-        for (int j = 0; j < 8; j++) codes2 |= (uint64_t)((FULL || q + j < N) ? c[j] : (uint32_t)MSD_SEP) << (8 * j);
+        for (int j = 0; j < 8; j++) codes2 |= (uint64_t)((FULL || q + j < N) ? c[j] : (uint32_t)FBG_SEP) << (8 * j);
         *reinterpret_cast<uint64_t *>(tile + kk) = codes2;
     }
 }
@@ -107,55 +107,4 @@ __device__ __forceinline__ void msd_load_tile(uint8_t *tile, const uint8_t *cd, 
     uint64_t raw, raw2;
     msd_fetch_raw<TILE>(T, N, base, raw, raw2);
     msd_store_tile<TILE, FULL>(tile, cd, N, base, raw, raw2);
-}
-
-// w[i] = key of position t0 + i of the tile, i < MSD_ITEMS (t0 = 8 * threadIdx.x)
-__device__ __forceinline__ void msd_build_keys(const uint8_t *tile, int t0, int b, int K, uint64_t *w)
-{
-    bool slow = true;
-    if (b == 2 && K + MSD_ITEMS - 1 <= 32) {
-        // 2-bit symbols: the thread's 32 symbols packed into one word (two multiplies per 8 bytes gather the low
-        // two bits of every byte), every key a shift of it
-        uint64_t P = 0, any = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint64_t x = *reinterpret_cast<const uint64_t *>(tile + t0 + 8 * q);
-            any |= x;
-            const uint32_t lo = (uint32_t)x & 0x03030303u, hi = (uint32_t)(x >> 32) & 0x03030303u;
-            const uint32_t g = (((lo * 0x40100401u) >> 24) << 8) | ((hi * 0x40100401u) >> 24);    // 8 symbols, first one on top
-            P |= (uint64_t)g << (48 - 16 * q);
-        }
-        slow = (any & 0x8080808080808080ull) != 0;              // a separator among the 32 symbols
-#pragma unroll
-        for (int i = 0; i < MSD_ITEMS; i++) w[i] = (P << (2 * i)) >> (64 - 2 * K);
-    }
-    if (b != 2 || K + MSD_ITEMS - 1 > 32) {
-        // general alphabet: rolling, one LDS byte per position (k_pack)
-        const uint64_t mask = (K * b) >= 64 ? ~0ull : ((1ull << (K * b)) - 1);
-        uint64_t key = 0;
-        uint32_t seen = 0;
-        for (int k = 0; k < K; k++) { const uint32_t c = tile[t0 + k]; seen |= c; key = (key << b) | c; }
-#pragma unroll
-        for (int i = 0; i < MSD_ITEMS; i++) {
-            w[i] = key;
-            const uint32_t c = tile[t0 + K + i];
-            seen |= c;
-            key = ((key << b) | c) & mask;
-        }
-        slow = (seen & MSD_SEP) != 0;
-    }
-    if (slow) {
-        // a row ends nearby: symbol by symbol; a separator and all behind it count as 0 (k_pack)
-#pragma unroll
-        for (int i = 0; i < MSD_ITEMS; i++) {
-            uint64_t kk = 0;
-            bool dead = false;
-            for (int k = 0; k < K; k++) {
-                const uint32_t c = tile[t0 + i + k];
-                dead = dead || (c & MSD_SEP);
-                kk = (kk << b) | (dead ? 0u : c);
-            }
-            w[i] = kk;
-        }
-    }
 }

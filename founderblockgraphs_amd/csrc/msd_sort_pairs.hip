@@ -1000,19 +1000,6 @@ __global__ void k_ss_sample(const uint8_t *__restrict__ T, uint64_t N, const uin
     out[i] = key;
 }
 
-__global__ void k_ss_twins(const uint64_t *__restrict__ sorted, uint64_t S, unsigned long long *__restrict__ out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool twin = i + 1 < S && sorted[i] == sorted[i + 1];
-    __shared__ uint32_t blk;                               // (one addition per workgroup: 65 000 on one address took 0.5 ms)
-    if (threadIdx.x == 0) blk = 0;
-    __syncthreads();
-    const unsigned long long mask = __ballot(twin);
-    if ((threadIdx.x & 63) == 0 && mask) atomicAdd(&blk, (uint32_t)__popcll(mask));
-    __syncthreads();
-    if (threadIdx.x == 0 && blk) atomicAdd(out, (unsigned long long)blk);
-}
-
 __global__ void k_ss_grid(const uint64_t *__restrict__ sorted, uint64_t S, uint64_t *__restrict__ grid)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1049,14 +1036,10 @@ int fbg_sample_sort_pairs(fbg_ctx *ctx, const KeyGeom &g, const SortExtras &x, i
         // with probability S / N.  Sub-buckets full of equal keys make the finish quadratic (52 ms for 2 * 10^8 suffixes of
         // a star phylogeny with gaps), and the scan in suffix order that would follow declines such inputs anyway:
         // leave them to the library sort and say so (ctx->pairs_similar)
-        unsigned long long *d_twins = &fbg_scalars(ctx)->sample_twins;
-        FBG_HIP_TRY(ctx, hipMemsetAsync(d_twins, 0, 8, st));
-        hipLaunchKernelGGL(k_ss_twins, dim3(fbg_blocks(S, 256)), dim3(256), 0, st, srt, S, d_twins);
         unsigned long long twins = 0;
-        FBG_HIP_TRY(ctx, hipMemcpyAsync(&twins, d_twins, 8, hipMemcpyDeviceToHost, st));
-        FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        FBG_TRY(fbg_count_equal_neighbours(ctx, srt, S, &fbg_scalars(ctx)->sample_twins, &twins));
         *launches += 1;
-        ctx->pairs_similar = (double)twins * (double)N / ((double)S * (double)S) > 0.5 && !ctx->opt.msd_min_force;
+        ctx->pairs_similar = fbg_twins_say_similar(twins, N, S) && !ctx->opt.msd_min_force;
         if (ctx->pairs_similar && !x.payload) return FBG_OK;    // (with a payload the consumer is the group-level scan: equal keys in any order)
     }
     hipLaunchKernelGGL(k_ss_grid, dim3(fbg_blocks(nsub, 256)), dim3(256), 0, st, srt, S, grid);

@@ -170,7 +170,7 @@ template <int L> __global__ void k_ps_values(PsArgs a)
         const uint64_t h = side == 0 ? lb - 1 : rb;
         const uint32_t flh = a.gflags[h];
         const uint64_t keyh = rs_key<L>(a.r, a.gstart[h]);
-        uint32_t lcp = min(rs_key_lcp(key, keyh, a.r.b, a.r.key_bits), rem);
+        uint32_t lcp = min(fbg_key_lcp(key, keyh, a.r.b, a.r.key_bits), rem);
         if (flh & PS_MIXED) {
             if (flh & PS_SHORT) {                              // which of its members reach how far: by their text
                 const unsigned long long e = atomicAdd(&a.counters[1], 1ull);
@@ -202,7 +202,7 @@ template <int L> __device__ uint32_t ps_outside_match(const PsArgs &a, uint64_t 
                 if (rq != rem) reach = max(reach, rq);
             }
         }
-        return min(min(rs_key_lcp(key, rs_key<L>(a.r, a.gstart[h]), a.r.b, a.r.key_bits), rem), reach);
+        return min(min(fbg_key_lcp(key, rs_key<L>(a.r, a.gstart[h]), a.r.b, a.r.key_bits), rem), reach);
     }
 }
 

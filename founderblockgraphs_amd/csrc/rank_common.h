@@ -2,18 +2,10 @@
 // (rank_scan.hip: the slot-level scan, rank_tail.hip: its candidate tail; pure_scan.hip: the group-level scan for similar rows).
 #pragma once
 #include "fbg_internal.h"
+#include "keys.h"
 #include "text_cmp.h"
 
 #define RS_TG 4    // tie groups up to this size are settled inside the scan
-
-// number of equal leading symbols of two different K-symbol keys (b bits per symbol)
-__device__ __forceinline__ uint32_t rs_key_lcp(uint64_t a, uint64_t c, int b, int key_bits)
-{
-    const uint64_t d = a ^ c;
-    const uint32_t bits = (uint32_t)(__clzll((long long)d) - (64 - key_bits));
-    const uint32_t inv_b = (65536u + (uint32_t)b - 1) / (uint32_t)b;   // hoisted: b is uniform
-    return (bits * inv_b) >> 16;
-}
 
 struct RankArgs {
     uint32_t magic32;          // floor(2^32 / row_len): umulhi(p, magic32) is p / row_len or one less
@@ -126,7 +118,7 @@ __device__ __forceinline__ void rs_update(const RankArgs &a, uint32_t col, uint3
 // LCP of the suffixes of two neighbouring SA slots, x before y
 __device__ __forceinline__ uint32_t rs_pair_lcp(const RankArgs &a, const Slot &x, const Slot &y)
 {
-    if (x.key != y.key) return min(min(rs_key_lcp(x.key, y.key, a.b, a.key_bits), x.rem), y.rem);
+    if (x.key != y.key) return min(min(fbg_key_lcp(x.key, y.key, a.b, a.key_bits), x.rem), y.rem);
     const uint32_t from = (x.rem < (uint32_t)a.K || y.rem < (uint32_t)a.K) ? 0u : (uint32_t)a.K;
     return fbg_clamp_lcp(fbg_extend_match(a.T, (uint64_t)x.pos + from, (uint64_t)y.pos + from, 0) + from);
 }
@@ -266,8 +258,8 @@ __device__ __forceinline__ void rank_scan_slow(const RankArgs &a, const V &v, co
         mrn = mr;
     }
     if (edge || run) { want_cand = true; return; }
-    const uint32_t lp = has_prev ? min(min(rs_key_lcp(kp, key, a.b, a.key_bits), rem), mrp) : 0u;
-    const uint32_t ln = has_next ? min(min(rs_key_lcp(key, kn, a.b, a.key_bits), rem), mrn) : 0u;
+    const uint32_t lp = has_prev ? min(min(fbg_key_lcp(kp, key, a.b, a.key_bits), rem), mrp) : 0u;
+    const uint32_t ln = has_next ? min(min(fbg_key_lcp(key, kn, a.b, a.key_bits), rem), mrn) : 0u;
     const uint32_t g = max(lp, ln) + 1;
     if (g >= a.g_min || rem <= 64) rs_update(a, rs_col_of_rem(a, rem), g);
 }

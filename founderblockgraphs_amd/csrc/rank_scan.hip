@@ -146,7 +146,7 @@ template <int L, bool PLAIN> __global__ __launch_bounds__(RS_THREADS) __attribut
         uint32_t slow4 = 0, tie4 = 0, cand4 = 0;
         uint32_t lcp[RS_ITEMS + 1];                                    // key LCP of slots my_i + r - 1 and my_i + r (K for equal keys)
 #pragma unroll
-        for (int r = 0; r <= RS_ITEMS; r++) lcp[r] = PLAIN ? rs_key_lcp(kk[r + 2], kk[r + 3], a.b, a.key_bits) : 0u;
+        for (int r = 0; r <= RS_ITEMS; r++) lcp[r] = PLAIN ? fbg_key_lcp(kk[r + 2], kk[r + 3], a.b, a.key_bits) : 0u;
 #pragma unroll
         for (int r = 0; r < RS_ITEMS; r++) {
             // slot i with keys K[-3..3] = kk[r .. r+6] and columns C[-2..2] = cc[r .. r+4]
@@ -639,8 +639,8 @@ __global__ __launch_bounds__(256) void k_tie_sample(const uint64_t *__restrict__
         if (kp == key || kn == key) {
             bin = 64;
         } else {
-            const uint32_t lp = k > 0 ? rs_key_lcp(kp, key, b, key_bits) : 0u;
-            const uint32_t ln = k + 1 < N ? rs_key_lcp(key, kn, b, key_bits) : 0u;
+            const uint32_t lp = k > 0 ? fbg_key_lcp(kp, key, b, key_bits) : 0u;
+            const uint32_t ln = k + 1 < N ? fbg_key_lcp(key, kn, b, key_bits) : 0u;
             bin = min(max(lp, ln) + 1, 63u);
         }
     }
@@ -699,8 +699,8 @@ __global__ __launch_bounds__(256) void k_tie_sample_loop(const uint64_t *__restr
             if (kp == key || kn == key) {
                 bin = 64;
             } else {
-                const uint32_t lp = k > 0 ? rs_key_lcp(kp, key, b, key_bits) : 0u;
-                const uint32_t ln = k + 1 < N ? rs_key_lcp(key, kn, b, key_bits) : 0u;
+                const uint32_t lp = k > 0 ? fbg_key_lcp(kp, key, b, key_bits) : 0u;
+                const uint32_t ln = k + 1 < N ? fbg_key_lcp(key, kn, b, key_bits) : 0u;
                 bin = min(max(lp, ln) + 1, 63u);
             }
         }

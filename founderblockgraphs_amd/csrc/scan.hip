@@ -9,7 +9,7 @@
 //         max( min(LCP[lb..r]), min(LCP[r+1..rb+1]) )
 //     and g = that + 1 is how far row i must be extended to the right of x.
 //
-// Input is the record array of suffix_sort.hip / lcp.hip: rec[p] = {rank, LCP[rank] | hint, LCP[rank+1] |
+// Input is the record array of record_sort.hip / lcp.hip: rec[p] = {rank, LCP[rank] | hint, LCP[rank+1] |
 // hint, -} per text position, the hint bit saying "my SA neighbour may be coloured in my column".
 //
 //   k_scan_stream      one THREAD per column, lanes along x: for row i the wave reads 64 consecutive

@@ -33,6 +33,7 @@
 // needed only for text comparisons and lookups, comes from a table of 20 bytes per 128 cells (symbols before the window,
 // bitmap of its symbols).  (m + 1) * (n + 1) < 2^30; '-' among the ignore characters is not for this scan.
 #include "fbg_internal.h"
+#include "keys.h"
 #include "text_cmp.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
@@ -96,13 +97,6 @@ struct SpArgs {
 #define SP_CH_OWN 0x100u
 #define SP_CH_EVENT 0x200u
 struct SpChain { uint32_t p, row, xlo, xhi, plo, phi, group, nex, evcol, ex[SP_CHAIN_EX]; };
-
-__device__ __forceinline__ uint32_t sp_key_lcp(uint64_t a, uint64_t c, int b, int key_bits)
-{
-    const uint64_t d = a ^ c;
-    const uint32_t bits = (uint32_t)(__clzll((long long)d) - (64 - key_bits));
-    return (bits * ((65536u + (uint32_t)b - 1) / (uint32_t)b)) >> 16;
-}
 
 // The flags of a slot.  (m + 1) * (n + 1) < 2^30: bits 30 and 31 of its value.  Beyond that the value is the cell alone and the
 // flags are the two lowest bits of the key word, below the K symbols (ksh = 2: fbg_span_prepare).
@@ -533,7 +527,7 @@ __device__ uint32_t sp_outside(const SpArgs &a, uint64_t g, uint64_t key, uint32
             h = dir < 0 ? a.rstart[run] : a.rstart[run + 1] - 1;
             continue;
         }
-        return sp_key_lcp(key, sp_key(a, a.gstart[h]), a.b, a.key_bits);
+        return fbg_key_lcp(key, sp_key(a, a.gstart[h]), a.b, a.key_bits);
     }
 }
 

@@ -444,7 +444,7 @@ def test_tie_groups_of_exact_sizes_gap_free(engine, k, entangled):
     runs of k_runs, rank_tail.hip:241).  f (fbg.cpp:1579-1695, the walk 1633-1678), v (fbg.cpp:552-611) and the index arrays.
     index_kind: with pure_scan = -1 the rank-order scan is the only fast path: 1 up to 64 members, 0 (records) from 65 on;
     likewise under force_wide, a layout the group-level scan does not take (pure_scan.hip:315).  With the default options
-    a decline of the rank-order scan is followed by the group-level scan (suffix_sort.hip:878-879), which holds groups of
+    a decline of the rank-order scan is followed by the group-level scan (suffix_sort.hip, ranked_path), which holds groups of
     up to 8192 members (pure_scan.hip:33) and keeps index_kind at 1 for 65 and 66 too; so do no_packed and pure_scan = 1."""
     msa, _, ref = reference("ties", k, entangled, "plain")
     size = 2 * k if entangled else k
