@@ -17,6 +17,7 @@ FBG_OK, FBG_ERR_INVALID, FBG_ERR_NO_SEGMENTATION, FBG_ERR_OOM, FBG_ERR_HIP, FBG_
 NODE_VALID, NODE_INVALID, NODE_SKIP_SOURCE_SINK, NODE_SKIP_IGNORED, NODE_SKIP_EMPTY = range(5)
 STRAND_NONE = 0xff                           # FBG_STRAND_NONE (include/fbg_hip.h)
 ALIGN_NONE = 0xffffffff                      # FBG_ALIGN_NONE
+PAIR_NONE = 0xff                             # which of fbg_pindex_chains_pairs for a pair without a valid candidate
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}     # FBG_CIGAR_*: the low four bits of a run, BAM's codes
 PART_HALO = 64                               # FBG_PART_HALO (include/fbg_hip.h)
 PART_HALO_BYTES = 2 * PART_HALO * 12 + 16    # FBG_PART_HALO_BYTES
@@ -123,6 +124,8 @@ SIGNATURES = {
     "fbg_pindex_chains_mapq_fetch": (C.c_int, [vp, u32p, u32p, C.POINTER(C.c_double)]),
     "fbg_pindex_mapq_strands": (C.c_int, [vp, u8p, C.POINTER(C.c_double)]),
     "fbg_pindex_mapq_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
+    "fbg_pindex_chains_pairs": (C.c_int, [vp, C.c_uint64, C.c_uint64, u8p, u32p, u32p, u32p, u64p, u32p, u32p, u32p, u32p, u32p,
+                                          u64p, u32p, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_seeds_strands": (C.c_int, [vp, u8p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_chain_strands": (C.c_int, [vp, u8p, u32p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "fbg_segmentation_validate": (C.c_int, [vp, u64p, C.c_uint64, u8p, C.c_uint64, u8p, u64p, u64p, C.POINTER(C.c_double)]),

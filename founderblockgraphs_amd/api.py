@@ -565,6 +565,7 @@ class PatternIndex:
         occ = Occurrences(self._label_len, count[:n], ln[:n].astype(np.uint64), rs[:n], et[:n], st[:n], eoff, soff,
                           [a[:ne] for a in ends], [a[:ns] for a in starts], ms1.value, ms2.value + ms3.value, coords, ms4)
         self._seed_reads = k
+        self._seed_total = n
         self._seed_given = given if strands else None
         out = Seeds(seed_off, q[:n], ln[:n], occ, np.diff(off.astype(np.int64)), strands)
         if rows:
@@ -615,7 +616,8 @@ class PatternIndex:
         return dict(zip(("paths", "ops", "columns", "history_bytes", "batches"), (x.value for x in v)))
 
     def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False, by_row=False,
-               graph=False, graph_pad=16, max_cells=0, select=None, graph_cigar=False, mapq=False, mapq_margin=0):
+               graph=False, graph_pad=16, max_cells=0, select=None, graph_cigar=False, mapq=False, mapq_margin=0, pairs=None,
+               adopt_pairs=False):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -645,7 +647,22 @@ class PatternIndex:
         length (fbg_pindex_chains_mapq and _fetch), as Chains.second_score, .second_lo, .second_hi, .mapq, .second_off,
         .second_place, .second_seed and .second(k); after seeds(strands=True) also Chains.mapq_stranded, where the other
         strand's score competes too (fbg_pindex_mapq_strands), and Chains.best_mapq.  A read matched in one piece has no
-        seed at a shorter copy elsewhere and gets second_score 0."""
+        seed at a shorter copy elsewhere and gets second_score 0.  pairs=(min_insert, max_insert) (after
+        seeds(strands=True) on an even number of reads, mates interleaved): also, per virtual read, a rescue chain on the
+        start places inside the insert window that its partner's chain opens, and per pair the best valid combination of a
+        chain and a rescue chain on opposite strands (fbg_pindex_chains_pairs), as Chains.pair_which, .pair_score, .pair_lo,
+        .pair_hi, .rescue_off, .rescue_score, .rescue_lo, .rescue_hi, .rescue_place, .rescue_seed, .rescue(v), .pair(p),
+        .pair_stats and .pairs_ms.  adopt_pairs=True: the chosen chains replace the chains of their reads and the twins of
+        those reads get the empty chain, right after the chaining call: chain_off, score, anchor_place, anchor_seed, the
+        strands and every field of rows=, align=, cigar=, graph=, graph_cigar= and mapq= then describe the adopted chains."""
+        if adopt_pairs and pairs is None:
+            raise ValueError("adopt_pairs=True needs pairs=(min_insert, max_insert)")
+        if pairs is not None:
+            if getattr(self, "_seed_given", None) is None:
+                raise ValueError("pairs= needs seeds(strands=True)")
+            lo_ins, hi_ins = (int(x) for x in pairs)
+            if not 0 <= lo_ins <= hi_ins:
+                raise ValueError("pairs=(min_insert, max_insert) with 0 <= min_insert <= max_insert")
         if mapq_margin < 0:
             raise ValueError("mapq_margin must be 0 or more")
         if cigar and not align:
@@ -673,11 +690,35 @@ class PatternIndex:
         else:
             self._eng._chk(self._L.fbg_pindex_chains(self._h, b, min(int(min_score), 0xffffffffffffffff), _u64(chain_off),
                                                      score.ctypes.data_as(_lib.u32p), C.byref(ms1)))
+        paired = None
+        if pairs is not None:
+            u32 = lambda a: a.ctypes.data_as(_lib.u32p)      # noqa: E731
+            npairs, nseeds = k // 4, getattr(self, "_seed_total", 0)
+            pw = np.zeros(max(npairs, 1), dtype=np.uint8)
+            psc, plo, phi = (np.zeros(max(npairs, 1), dtype=np.uint32) for _ in range(3))
+            roff = np.zeros(k + 1, dtype=np.uint64)
+            rsc, rlo, rhi = (np.zeros(max(k, 1), dtype=np.uint32) for _ in range(3))
+            rplace, rseed = (np.zeros(max(nseeds, 1), dtype=np.uint32) for _ in range(2))
+            aoff, asc = np.zeros(k + 1, dtype=np.uint64), np.zeros(max(k, 1), dtype=np.uint32)
+            pstats = np.zeros(8, dtype=np.uint64)
+            ms11 = C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_chains_pairs(self._h, lo_ins, min(hi_ins, 0xffffffffffffffff), _u8(pw), u32(psc), u32(plo),
+                                                           u32(phi), _u64(roff), u32(rsc), u32(rlo), u32(rhi), u32(rplace), u32(rseed),
+                                                           _u64(aoff) if adopt_pairs else None, u32(asc) if adopt_pairs else None,
+                                                           _u64(pstats), C.byref(ms11)))
+            if adopt_pairs:
+                chain_off, score = aoff, asc
+            t3 = int(roff[k])
+            paired = (pw[:npairs], psc[:npairs], plo[:npairs], phi[:npairs], roff, rsc[:k], rlo[:k], rhi[:k], rplace[:t3], rseed[:t3],
+                      dict(zip(Chains.PAIR_STATS, (int(x) for x in pstats))), ms11.value)
         t = int(chain_off[k])
         place, seed = np.zeros(max(t, 1), dtype=np.uint32), np.zeros(max(t, 1), dtype=np.uint32)
         self._eng._chk(self._L.fbg_pindex_chains_fetch(self._h, place.ctypes.data_as(_lib.u32p), seed.ctypes.data_as(_lib.u32p),
                                                        C.byref(ms2)))
         out = Chains(chain_off, score[:k], place[:t], seed[:t], ms1.value, ms2.value)
+        if paired is not None:
+            (out.pair_which, out.pair_score, out.pair_lo, out.pair_hi, out.rescue_off, out.rescue_score, out.rescue_lo, out.rescue_hi,
+             out.rescue_place, out.rescue_seed, out.pair_stats, out.pairs_ms) = paired
         if by_row:
             out.chain_row, out.n_best_rows, out.by_row = crow[:k], nbest[:k], True
         given = getattr(self, "_seed_given", None)
@@ -1013,6 +1054,20 @@ class Chains:
       best_mapq       after seeds(strands=True): uint8 per given read, mapq_stranded of the strand that strand picked, 0
                       where strand is 0xff
       mapq_ms         device time of fbg_pindex_chains_mapq
+    and, asked for with pairs=(min_insert, max_insert) after seeds(strands=True) on interleaved mates (None otherwise;
+    include/fbg_hip.h, fbg_pindex_chains_pairs), for the k / 4 pairs, pair p being the given reads 2p and 2p + 1:
+      pair_which      uint8 per pair: the chosen candidate 0 .. 3, 0xff (_lib.PAIR_NONE) without a valid one; pair(p) names
+                      its forward and reverse virtual read and says which of the two chains is the rescue
+      pair_score      uint32 per pair: the sum of the two chains' scores, 0 without a candidate
+      pair_lo, pair_hi   uint32 per pair: the first column of the forward chain and the end of the reverse one, 0xffffffff
+                      without a candidate
+      rescue_score, rescue_lo, rescue_hi   uint32 per virtual read: score and columns of its rescue chain, the chain on the
+                      start places inside the window its partner's chain opens (0 and 0xffffffff where it is empty)
+      rescue_off, rescue_place, rescue_seed   the rescue chains, as chain_off, anchor_place and anchor_seed; rescue(v)
+                      gives virtual read v's
+      pair_stats      {which0 .. which3, none, places_kept, places_excluded, rescue_differs}: stats[] of the call
+      pairs_ms        device time of fbg_pindex_chains_pairs
+    With adopt_pairs=True every other field describes the adopted chains.
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -1030,6 +1085,28 @@ class Chains:
         self.graph_cigar_off = self.graph_cigar_ops = self.graph_cigar_ms = None
         self.second_score = self.second_lo = self.second_hi = self.mapq = self.second_off = None
         self.second_place = self.second_seed = self.mapq_stranded = self.best_mapq = self.mapq_ms = None
+        self.pair_which = self.pair_score = self.pair_lo = self.pair_hi = self.pair_stats = self.pairs_ms = None
+        self.rescue_off = self.rescue_score = self.rescue_lo = self.rescue_hi = self.rescue_place = self.rescue_seed = None
+
+    PAIR_STATS = ("which0", "which1", "which2", "which3", "none", "places_kept", "places_excluded", "rescue_differs")
+
+    def rescue(self, v):
+        """int64[rows, 2]: (anchor_place, anchor_seed) of the rescue chain of virtual read v, as of()."""
+        if self.rescue_off is None:
+            raise ValueError("no rescue chains: ask for them with pairs=(min_insert, max_insert)")
+        a, b = int(self.rescue_off[v]), int(self.rescue_off[v + 1])
+        return np.stack((self.rescue_place[a:b], self.rescue_seed[a:b]), axis=1).astype(np.int64)
+
+    def pair(self, p):
+        """(forward virtual read, reverse virtual read, forward chain is the rescue, reverse chain is the rescue) of the
+        candidate chosen for pair p, the given reads 2p and 2p + 1; None where the pair has no valid candidate."""
+        if self.pair_which is None:
+            raise ValueError("no pairs: ask for them with pairs=(min_insert, max_insert)")
+        i, n = int(self.pair_which[p]), (len(self.chain_off) - 1) // 2
+        if i == _lib.PAIR_NONE:
+            return None
+        a, b = 2 * p, 2 * p + 1
+        return (a if i < 2 else b), (b if i < 2 else a) + n, bool(i & 1), not i & 1
 
     def cigar_runs(self, k):
         """int64[runs, 2]: (code, length) of the runs of read k's alignment path; no rows without an alignment."""

@@ -4,7 +4,7 @@
 //
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
 //              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--by-row] [--align[=PAD]] [--cigar]
-//              [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE] [--mapq[=MARGIN]]
+//              [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE] [--mapq[=MARGIN]] [--pairs=MIN,MAX]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -83,6 +83,15 @@
 // gets a third field, the value of the chosen strand (0 for *).  With --gaf column 12 is the value of that pattern and
 // strand instead of 255.  A pattern that matches in one piece has no seed at a shorter copy elsewhere: its second is 0.
 // Without --mapq no byte of stdout or of the GAF file changes.
+// --pairs=MIN,MAX (with --chain and --strands, an even number of patterns) reads the patterns as pairs of mates, patterns 2p
+// and 2p + 1, from opposite strands of one fragment whose extent in MSA columns lies in MIN .. MAX (fbg_pindex_chains_pairs):
+// every mate also gets a rescue chain on the start places inside the window that the other mate's chain opens, and the
+// pair takes the best valid combination of a chain on one strand and a chain on the other.  The chosen chains replace the
+// chains of their patterns and the other strand of either pattern gets the empty chain, before anything is printed: every
+// C / A / Q / G / H / T line and the GAF file are those of the adopted chains.  After the T line of a pair's second pattern,
+//   Z <tab> which <tab> pair_score <tab> t_lo <tab> t_hi    the candidate 0 .. 3, the sum of the two scores, the pair's columns
+// or `Z <tab> *` for a pair without a valid combination, whose chains stay as they were.  The insert is counted in MSA
+// columns, forward-reverse orientation only.  Without --pairs no byte of stdout or of the GAF file changes.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -102,7 +111,7 @@ static int usage(const char *msg)
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
               << "                  [--by-row] [--align[=PAD]] [--cigar] [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE]\n"
-              << "                  [--mapq[=MARGIN]]\n"
+              << "                  [--mapq[=MARGIN]] [--pairs=MIN,MAX]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -147,7 +156,13 @@ static int usage(const char *msg)
               << "                     chain's columns (* without one); chains in the same columns are the same locus.  With\n"
               << "                     --strands the other strand competes too and the T line ends with the chosen strand's\n"
               << "                     value; with --gaf column 12 is the value instead of 255.  A pattern matched in one\n"
-              << "                     piece has no seed at a shorter copy elsewhere and gets second 0\n";
+              << "                     piece has no seed at a shorter copy elsewhere and gets second 0\n"
+              << "  --pairs=MIN,MAX    needs --chain and --strands and an even number of patterns: patterns 2p and 2p + 1 are\n"
+              << "                     mates on opposite strands, MIN .. MAX MSA columns from the forward mate's first to the\n"
+              << "                     reverse mate's last; a mate is chained again inside the window of the other's chain, the\n"
+              << "                     best valid combination replaces the pair's chains (every line then describes those), and\n"
+              << "                     after the second pattern's T line a Z line: candidate, pair score, first and last column\n"
+              << "                     (Z and * without a valid combination)\n";
     return EXIT_FAILURE;
 }
 
@@ -231,7 +246,8 @@ static void print_runs(std::ostream &os, const std::vector<uint32_t> &ops, uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement, gaf_path;
-    bool graph_cigar = false, have_gaf = false, want_mapq = false;
+    bool graph_cigar = false, have_gaf = false, want_mapq = false, want_pairs = false;
+    uint64_t min_insert = 0, max_insert = 0;
     uint64_t margin = 0;
     bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false, graph_align = false;
     uint64_t graph_pad = 16;
@@ -327,6 +343,20 @@ int main(int argc, char **argv)
             margin = m;
             continue;
         }
+        if (a.compare(0, 8, "--pairs=") == 0) {
+            const std::string v = a.substr(8);
+            const size_t comma = v.find(',');
+            const std::string lo = v.substr(0, comma), hi = comma == std::string::npos ? "" : v.substr(comma + 1);
+            errno = 0;
+            const unsigned long long x = std::strtoull(lo.c_str(), nullptr, 10), y = std::strtoull(hi.c_str(), nullptr, 10);
+            if (lo.empty() || hi.empty() || lo.find_first_not_of("0123456789") != std::string::npos ||
+                hi.find_first_not_of("0123456789") != std::string::npos || errno || x > y)
+                return usage(("--pairs takes MIN,MAX with MIN <= MAX, not '" + v + "'").c_str());
+            want_pairs = true;
+            min_insert = x;
+            max_insert = y;
+            continue;
+        }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
         return usage(("unknown argument " + a).c_str());
     }
@@ -343,6 +373,7 @@ int main(int argc, char **argv)
     if (graph_cigar && !graph_align) return usage("--graph-cigar needs --graph-align");
     if (have_gaf && !graph_cigar) return usage("--gaf needs --graph-cigar");
     if (want_mapq && !chain) return usage("--mapq needs --chain");
+    if (want_pairs && !(chain && strands)) return usage("--pairs needs --chain and --strands");
     if (have_gaf && gaf_path.empty()) return usage("--gaf takes a file");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
@@ -394,6 +425,7 @@ int main(int argc, char **argv)
     }
     const uint64_t np = off.size() - 1;
     const uint64_t nv = strands ? 2 * np : np;      // virtual reads: the patterns, then their reverse complements
+    if (want_pairs && np % 2) return usage("--pairs takes an even number of patterns, mates interleaved");
 
     fbg_ctx *ctx = nullptr;
     int rc = fbg_ctx_create(0, &ctx);
@@ -454,6 +486,8 @@ int main(int argc, char **argv)
     std::vector<uint64_t> second_off(nv + 1, 0);            // --mapq: the second chains' offsets, scores and spans, the qualities
     std::vector<uint32_t> second[3];
     std::vector<uint8_t> quality(nv + 1, 0);
+    std::vector<uint8_t> pair_which(np / 2 + 1, 0);        // --pairs: the candidate, its score and columns per pair
+    std::vector<uint32_t> pair_out[3];
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -484,6 +518,13 @@ int main(int argc, char **argv)
             for (int k = 0; k < 2; k++) chosen[k].resize(nv + 1);
             rc = fbg_pindex_chains_by_row(ix, band, 0, chain_off.data(), chain_score.data(), chosen[0].data(), chosen[1].data(), nullptr);
         } else if (rc == FBG_OK && chain) rc = fbg_pindex_chains(ix, band, 0, chain_off.data(), chain_score.data(), nullptr);
+        if (rc == FBG_OK && want_pairs) {      // adopt: chain_off and chain_score become those of the pair-consistent chains
+            std::vector<uint64_t> rescue_off(nv + 1, 0);
+            for (int k = 0; k < 3; k++) pair_out[k].resize(np / 2 + 1);
+            rc = fbg_pindex_chains_pairs(ix, min_insert, max_insert, pair_which.data(), pair_out[0].data(), pair_out[1].data(),
+                                         pair_out[2].data(), rescue_off.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         chain_off.data(), chain_score.data(), nullptr, nullptr);
+        }
         if (rc == FBG_OK && chain) {
             anchor_place.resize(chain_off[nv] + 1);
             anchor_seed.resize(chain_off[nv] + 1);
@@ -639,6 +680,12 @@ int main(int argc, char **argv)
                     std::cout << "T\t" << (strand[k] == FBG_STRAND_NONE ? '*' : strand[k] ? '-' : '+') << '\t' << best_score[k];
                     if (want_mapq) std::cout << '\t' << (strand[k] == FBG_STRAND_NONE ? 0u : (unsigned)quality[strand[k] ? np + k : k]);
                     std::cout << '\n';
+                    if (want_pairs && k % 2) {
+                        const uint64_t p = k / 2;
+                        if (pair_which[p] == 0xffu) std::cout << "Z\t*\n";
+                        else std::cout << "Z\t" << (unsigned)pair_which[p] << '\t' << pair_out[0][p] << '\t' << pair_out[1][p] << '\t'
+                                       << pair_out[2][p] << '\n';
+                    }
                 }
             }
         }

@@ -10,6 +10,7 @@
 //   pindex_graph.hip      edit distance of a read to a path of the graph around its chain, and that path
 //   pindex_gcigar.hip     the alignment path of a read against the stretch of the graph that path spells
 //   pindex_mapq.hip       the second-best chain of a read outside the columns of its best one, and a mapping quality
+//   pindex_pairs.hip      paired reads: a mate's chain rescued in the insert window of the other's, the pick per pair, adopt
 // Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
 // needs its launch calls a launcher declared at the end of this header.
 // Two things tie the stages together.  The reads of the last seeds call lie in buffers of their own (PsState batch), which
@@ -55,6 +56,13 @@
 #define PQ_CTR 5              // counters of fbg_pindex_chains_mapq: anchors kept, anchors excluded, reads with a secondary chain,
                               // reads of mapping quality 0 and of 60
 #define PQ_NOSPAN 0xffffffffffffffffull   // lo of a read without a primary chain
+#define PP_CTR 8              // counters of fbg_pindex_chains_pairs, as its stats[]: pairs of candidate 0 .. 3, pairs without one,
+                              // places kept, places excluded, pairs whose rescue chain scores other than that read's primary
+#define PP_NOPAIR 0xffu       // which of a pair without a valid candidate
+#define PP_KEEP 0             // adopt, per virtual read: its chain stays (pair without a candidate); the chosen primary chain
+#define PP_PRIMARY 1          // stays; the chosen rescue chain replaces it; the twin of a chosen read gets the empty chain
+#define PP_RESCUE 2
+#define PP_TWIN 3
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
@@ -157,6 +165,17 @@ struct PqState {
     uint64_t stat[5] = {0, 0, 0, 0, 0};      // reads_with_second, anchors_kept, anchors_excluded, mapq0, mapq60
 };
 
+// fbg_pindex_chains_pairs.  ch: a chain state of this call's own, in which the chain kernels leave the rescue chains
+// (ch.col: the witness rows and columns, expanded again); span: lo and hi as u64, PQ_NOSPAN in lo for an empty chain, of
+// the primary chains (2 V, V the virtual reads) and then of the rescue chains (2 V); mcol: per start place its witness
+// column, or PC_NONE outside the window; rspan: rescue_lo, then rescue_hi (2 V u32); pick: per pair pair_score, t_lo,
+// t_hi (3 P u32, P = V / 4 pairs); which: per pair the candidate; src: per virtual read what adopt does with it (PP_KEEP
+// ..); ctr: PP_CTR counters in the order of stats[].  Nothing outlives the call: it returns all of it.
+struct PpState {
+    PcState ch;
+    DevBuf span, mcol, rspan, pick, which, src, ctr;
+};
+
 // The reads of the last fbg_pindex_seeds / _seeds_strands, in buffers that only a seeds call writes: reads (bytes of them,
 // padded as px_front pads) and roff (n + 1 byte offsets).  n: the reads on the device, with _strands the 2 x given virtual
 // ones (stranded); comp: the complement table of that call (256 bytes).
@@ -212,6 +231,7 @@ struct fbg_pindex {
     PhState gr;
     PjState gj;
     PqState pq;
+    PpState pp;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, sv0 = nullptr, sv1 = nullptr;   // made with the index (px_new)
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -421,6 +441,9 @@ PX_LOCAL int pc_begin(fbg_pindex *ix, uint64_t *chain_off, uint32_t *score, doub
 // for fbg_pindex_chains_mapq (pindex_mapq.hip).  None of them touches the stage table: the caller finishes its stage
 PX_LOCAL int pc_reserve(fbg_pindex *ix, PcState &c, PcDev &d, const uint32_t *col, uint64_t band);
 PX_LOCAL int pc_launch(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score, uint64_t bin[5], const char *what);
+// the tail of pc_launch on its own: k_pc_trace, the scan, k_pc_trace over end, score and pred of c (fbg_pindex_chains_pairs
+// runs it on ix->ch after it has put the adopted chains' ends, scores and predecessors there)
+PX_LOCAL int pc_trace(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score);
 PX_LOCAL int pc_finish(fbg_pindex *ix, PcState &c, const uint64_t *chain_off, const uint64_t bin[5], const char *what);
 // pindex_rows.hip: k_pr_seed and k_pr_place (records ev0); k_pr_chain
 PX_LOCAL int pr_prepare(fbg_pindex *ix, PrDev &d);

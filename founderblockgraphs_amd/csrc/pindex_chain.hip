@@ -157,7 +157,8 @@ __global__ void k_pc_strand(const uint32_t *score, const uint64_t *len, uint64_t
 // then count, scan and write as the seeds do.  A chain has at most one anchor per seed: S entries hold every chain.
 // fbg_pindex_chains_by_row (pindex_byrow.hip) runs the same steps on columns of its own, so they are four functions:
 // pc_begin, pc_reserve, pc_launch and pc_finish (pindex.h).  The last three take the chain state they work on:
-// fbg_pindex_chains_mapq (pindex_mapq.hip) runs them on a state of its own and leaves ix->ch alone.
+// fbg_pindex_chains_mapq (pindex_mapq.hip) runs them on a state of its own and leaves ix->ch alone, and so does
+// fbg_pindex_chains_pairs (pindex_pairs.hip), which with adopt runs pc_launch's tail, pc_trace, on ix->ch once more.
 
 // The checks and trivial cases of a chaining call (what: its name).  *go: there is something to launch; where there is
 // not, the caller finishes its stages at once.
@@ -212,7 +213,7 @@ int pc_launch(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score, uint64_t
 {
     fbg_ctx *ctx = ix->ctx;
     hipStream_t st = ctx->stream;
-    const uint64_t n = ix->batch.n, S = ix->sd.n, A = ix->sd.stotal;
+    const uint64_t n = ix->batch.n, A = ix->sd.stotal;
     uint32_t *ka = c.key.as<uint32_t>(), *va = c.id.as<uint32_t>(), *kb = c.key2.as<uint32_t>(), *vb = c.id2.as<uint32_t>();
     hipLaunchKernelGGL(k_pc_key, dim3(fbg_blocks(n, 256)), dim3(256), 0, st, d, n, ka, va);
     FBG_TRY(px_with_tmp(ix, [&](void *tmp, size_t &bytes) {
@@ -232,6 +233,15 @@ int pc_launch(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score, uint64_t
         hipLaunchKernelGGL(k_pc_chain<0>, dim3(fbg_blocks(bin[1], PX_THREADS / PC_SUB)), dim3(PX_THREADS), 0, st, d, ids, bin[1]);
     if (bin[2]) hipLaunchKernelGGL(k_pc_chain<1>, dim3((unsigned)bin[2]), dim3(FBG_WAVE), 0, st, d, ids + bin[1], bin[2]);
     if (bin[3]) hipLaunchKernelGGL(k_pc_chain<2>, dim3((unsigned)bin[3]), dim3(FBG_WAVE), 0, st, d, ids + bin[1] + bin[2], bin[3]);
+    return pc_trace(ix, c, d, min_score);
+}
+
+// The tail of pc_launch: from end, score and pred of c the lengths (0 below min_score), their scan, the chains.
+int pc_trace(fbg_pindex *ix, PcState &c, PcDev &d, uint64_t min_score)
+{
+    fbg_ctx *ctx = ix->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = ix->batch.n, S = ix->sd.n;
     uint64_t *len = c.len.as<uint64_t>(), *off = c.off.as<uint64_t>();
     uint32_t *out = c.out.as<uint32_t>();
     hipLaunchKernelGGL(k_pc_trace<false>, dim3(fbg_blocks(n + 1, 256)), dim3(256), 0, st, d, n, min_score, len, (const uint64_t *)off, out, out + S);

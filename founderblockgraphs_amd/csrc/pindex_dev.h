@@ -141,6 +141,9 @@ __device__ __forceinline__ uint32_t pm_col(const PmDev &m, const uint4 nd, uint3
     return PM_NONE;
 }
 
+// ---- sums of columns and margins that must not wrap (pindex_mapq.hip, pindex_pairs.hip) ---------------------------------
+__device__ __forceinline__ uint64_t pq_add_sat(uint64_t a, uint64_t b) { return b > 0xffffffffffffffffull - a ? 0xffffffffffffffffull : a + b; }
+
 // ---- one wave's own traffic through LDS or device memory (the chain DPs) ------------------------------------------------
 // what a seed's lanes wrote becomes visible to the lanes of the same wave that scan it for the next seed
 __device__ __forceinline__ void pc_sync()

@@ -22,8 +22,6 @@ struct PqDev {
     uint64_t n, S, A, margin;
 };
 
-__device__ __forceinline__ uint64_t pq_add_sat(uint64_t a, uint64_t b) { return b > 0xffffffffffffffffull - a ? 0xffffffffffffffffull : a + b; }
-
 // One lane per read: lo = c(a_1), hi = c(a_len) + k(a_len) of its primary chain; PQ_NOSPAN in lo for an empty chain.
 __global__ void k_pq_span(PqDev d)
 {

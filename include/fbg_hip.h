@@ -958,6 +958,72 @@ int fbg_pindex_mapq_strands(fbg_pindex *ix, uint8_t *mapq_stranded, double *devi
 int fbg_pindex_mapq_stats(const fbg_pindex *ix, uint64_t *reads_with_second, uint64_t *anchors_kept, uint64_t *anchors_excluded,
                           uint64_t *mapq0, uint64_t *mapq60);
 
+/* Paired reads: a mate's chain rescued in the insert window of the other mate's chain, and the best combination per pair
+ * (an index built by fbg_pindex_build_segmentation only; after a successful fbg_pindex_seeds_strands on an even number of
+ * reads and a successful fbg_pindex_chains or fbg_pindex_chains_by_row since it).
+ *
+ * Two mates come from one fragment, on opposite strands, a bounded distance apart.  A chaining call treats each as a lone
+ * read, so a mate that falls into a repeat goes to whichever copy scores a symbol more.  This call lets the other mate
+ * decide.  With the vocabulary of fbg_pindex_chains and of fbg_pindex_chains_mapq (anchors, witness column c, seed
+ * length k, span):
+ *   layout              after fbg_pindex_seeds_strands on n given reads, n even, pair p is the given reads a = 2p and
+ *                       b = 2p + 1, interleaved as in an interleaved FASTQ.  Virtual read v < n is read v as given, v >= n
+ *                       the reverse complement of read v - n.  twin(v) = v +- n.  partner(v) is the twin of v's mate:
+ *                       (v ^ 1) + n for v < n, (v - n) ^ 1 for v >= n; partner is an involution;
+ *   the primary chain   of v: what the last chaining call left, plain or by row; non-empty where chain_off[v + 1] >
+ *                       chain_off[v]; its span lo(v) = c of its first anchor, hi(v) = c + k of its last; its score score[v];
+ *   the window of w     with v = partner(w) and min_insert <= max_insert: empty where v has no primary chain;
+ *                       W = [lo(v), lo(v) + max_insert) for v < n (v is the forward mate, w the reverse one);
+ *                       W = [hi(v) - max_insert, hi(v)) for v >= n, the lower end clamped at 0.  The sum saturates at
+ *                       2^64 - 1.  A start place of w with witness column c and seed length k is kept iff c is a column,
+ *                       c >= W.lo and c + k <= W.hi.  Columns are the unmasked witness columns, also after
+ *                       fbg_pindex_chains_by_row;
+ *   the rescue chain    of w: the chain that fbg_pindex_chains defines on the kept places of w alone, with the band of the
+ *                       primary call, min_score 0 and the same ties.  All 2n virtual reads get one;
+ *   candidates          of pair p, F the forward chain and R the reverse one, in this order:
+ *                         0: F = primary(a), R = rescue(b + n)      1: F = rescue(a), R = primary(b + n)
+ *                         2: F = primary(b), R = rescue(a + n)      3: F = rescue(b), R = primary(a + n)
+ *                       A candidate is valid iff both chains are non-empty, lo(F) <= lo(R), hi(F) <= hi(R) and
+ *                       min_insert <= hi(R) - lo(F) <= max_insert.  Its score is s(F) + s(R).  The pair takes the valid
+ *                       candidate of the largest score, the smallest number among equals: which[p] in 0 .. 3, pair_score[p],
+ *                       t_lo[p] = lo(F), t_hi[p] = hi(R).  Without a valid candidate which[p] = 0xff, pair_score[p] = 0,
+ *                       t_lo[p] = t_hi[p] = 0xffffffff.
+ *   fbg_pindex_chains_pairs   one call returns everything.  which, pair_score, t_lo, t_hi: n / 2 entries each (only which
+ *       must be given).  rescue_off: 2n + 1 CSR offsets of the rescue chains (must be given); rescue_score, rescue_lo,
+ *       rescue_hi: 2n each, may be NULL (score 0 and span 0xffffffff for an empty chain); rescue_place, rescue_seed: the
+ *       anchors, as fbg_pindex_chains_fetch reports them; a chain has at most one anchor per seed, so buffers of as many
+ *       entries as the seeds call reported seeds hold them; either may be NULL.  stats[8] (may be NULL): the pairs with
+ *       which = 0, 1, 2, 3 and without a candidate; start places kept, and start places with a column that were not kept;
+ *       pairs whose chosen candidate uses a rescue chain that scores other than the same read's primary chain.  On the
+ *       device: one lane per virtual read takes the spans, one lane per start place finds its read by two searches and
+ *       writes its column or "none", the kernels of fbg_pindex_chains run on these columns in a chain state of this call's
+ *       own, one lane per virtual read takes the rescue spans and one lane per pair picks.  *device_ms (may be NULL): device
+ *       time of all of it, adopt included, without the copies out.
+ *   adopt               where adopt_chain_off (2n + 1) is given; adopt_score (2n) may be NULL.  For a pair with a
+ *       candidate its two chosen virtual reads get the chosen chains as their primary chains and their two twins the empty
+ *       chain with score 0; a pair without one keeps all four chains and scores as they were (a chain that min_score had
+ *       emptied stays empty).  adopt_chain_off and adopt_score are the new chain_off and score, fbg_pindex_chains_fetch
+ *       returns the new anchors, and every result made from the chains (fbg_pindex_chains_rows, _align, _cigar,
+ *       _align_graph, _graph_cigar, _mapq; the statistics of fbg_pindex_chains_by_row) is stale as after a chaining call:
+ *       run those calls again, and they describe the pair-consistent chains.  fbg_pindex_chain_strands then picks the pair's
+ *       strand, the twin being empty.  A second call on chains adopted after fbg_pindex_chains finds every pair that had a
+ *       candidate again, with the same two reads and chains, t_lo, t_hi and pair_score (which may name the other candidate of
+ *       the same two reads).  After fbg_pindex_chains_by_row it finds the same two reads, but a rescue chain is not bound to
+ *       the row and may then score higher than the row's chain, or tie with it on other anchors.  Without adopt nothing of
+ *       the chains is written and nothing goes stale.
+ * Limits.  The insert is counted in MSA witness columns: a stretch where most rows have gaps counts as long as its columns,
+ * not as the fragment's symbols.  Forward-reverse orientation only.  No mapping quality of the pair.  A mate without a seed
+ * inside the window is not rescued by alignment.
+ * Errors, all FBG_ERR_INVALID: a NULL index, which or rescue_off; an index not built from a segmentation; the last seeds
+ * call was not fbg_pindex_seeds_strands, or none succeeded; no successful chaining call since it; n odd;
+ * min_insert > max_insert.  A failed check leaves the index as it was.  n == 0, and seeds without places: every pair
+ * without a candidate, every rescue chain empty, FBG_OK, nothing launched.  Scratch owned by the index: what
+ * fbg_pindex_chains takes, once more, and 4 bytes per start place and 45 per virtual read. */
+int fbg_pindex_chains_pairs(fbg_pindex *ix, uint64_t min_insert, uint64_t max_insert, uint8_t *which, uint32_t *pair_score,
+                            uint32_t *t_lo, uint32_t *t_hi, uint64_t *rescue_off, uint32_t *rescue_score, uint32_t *rescue_lo,
+                            uint32_t *rescue_hi, uint32_t *rescue_place, uint32_t *rescue_seed, uint64_t *adopt_chain_off,
+                            uint32_t *adopt_score, uint64_t stats[8], double *device_ms);
+
 /* The edit distance of each read to a row that carries its chain (an index built by
  * fbg_pindex_build_segmentation_rows only; after a successful seeds call, plain or stranded, and a successful
  * fbg_pindex_chains since it).
