@@ -234,6 +234,20 @@ int fbg_fail(fbg_ctx *ctx, int code, const char *fmt, ...);
 int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes, std::vector<DevBuf *> *owner, bool accounted);
 inline int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes) { return fbg_reserve(ctx, b, bytes, &ctx->bufs, true); }
 
+// The words of FbgScalars::dp (dp.hip, dp_bytes.hip, dp_wide.hip; host and kernels).  fbg_dp_minmax and fbg_dp_gapped use the
+// first block, fbg_dp_repeatfree both: DP_NE is the base of a second block of the same shape, of which only the window
+// flag is in use -- k_dp_expand's limit test does not hold for the non-elastic values (k_ne_finish decides there), so its
+// flag goes to that block, where nobody reads it.
+enum : int {
+    DP_COUNT = 0,             // boundaries found (the backtracks)
+    DP_NO_SEGMENTATION = 1,   // the backtrack left the array / the last column has no value
+    DP_BAD_ENTRIES = 2,       // k_dp_keys: entries of f outside [x, n]
+    DP_MAX_EXT = 3,           // k_dp_keys: the longest f[x] + 1 - x; k_ne_prep: the longest minimal block
+    DP_WINDOW = 4,            // a value reached the limit of the sweep's window: the rung did not settle
+    DP_NE = 8,                // + DP_COUNT .. DP_WINDOW: the non-elastic DP's block
+    DP_WORDS = 16
+};
+
 // ---- the shared scratch words ---------------------------------------------------------------
 // ctx->scalars: the device-side counters and flags of every stage, one member per owner.  The members are disjoint
 // whichever stages run together; what a stage does with the words of its own member is its business.  A new counter
@@ -241,7 +255,7 @@ inline int fbg_reserve(fbg_ctx *ctx, DevBuf &b, size_t bytes) { return fbg_reser
 struct FbgScalars {
     alignas(64) unsigned long long front[8];     // text_build.hip, front_one_fill = 0: gaps, ignore cells, N
     unsigned long long sample_count;             // suffix_sort.hip: twins in the key sample; the slots a partition keeps
-    alignas(64) unsigned long long dp[16];       // dp.hip: results and flags of the three DPs and of the lifted backtrack
+    alignas(64) unsigned long long dp[DP_WORDS]; // dp*.hip (DP_* above): results and flags of the three DPs and of the lifted backtrack
     unsigned long long scan_exceptions;          // scan.hip: exception columns of the record scan
     alignas(64) unsigned long long rank[8];      // rank_common.h / rank_scan.hip, rank_tail.hip: RankArgs::counters ...
     unsigned long long rank_hist[32];            // ... and right behind them the threshold histogram, 64 x u32 (rs_zero_counters: one fill)
@@ -373,6 +387,9 @@ int fbg_scan_columns(fbg_ctx *ctx, uint64_t x0, uint64_t x1, int mode, int disab
                      uint64_t *d_out);                                        // scan.hip
 int fbg_dp_minmax(fbg_ctx *ctx, const uint64_t *d_f, uint64_t n, uint64_t *d_boundaries,
                   uint64_t *count_out, uint64_t *d_mml, uint64_t *d_bt);      // dp.hip
+// k_dp_blockW / k_dp_compose / k_dp_chain6 (k_dp_chain under dp_chain1) / k_dp_expand with R = 1, 2 or 4 (dp_bytes.hip)
+int fbg_dp_byte_chain(fbg_ctx *ctx, int R, const uint8_t *ext, const uint8_t *amin, uint64_t n, uint32_t Fg, uint8_t *Sg, uint32_t *out,
+                      unsigned long long *flag, uint32_t first_valid);
 // block_graph.hip: where the device stage of fbg_block_graph left the graph of a segmentation (the context's dp_* / io_a
 // workspaces).  edges: edge_count[j] sorted distinct (source << 32 | destination) at edges[j * m ..], global node numbers.
 struct BlockGraphDev {

@@ -34,6 +34,10 @@
 // the compact coding and (rolling alone, codes up to 255) in the plain one, at the geometries where a path or a mask changes;
 // fbg_key_lcp against a comparison symbol by symbol on pairs that part at every symbol.  Prints "keys ok GEOMETRIES TILES PAIRS"
 // or the first case that differs.
+//     fbg_host_selftest dp_plan
+// reads lines "max_ext f0 n dp_literal dp_wave dp_safe_window dp_tile" from stdin and prints the ladder of sweeps dp_plan.h plans
+// for each, one line of rungs per input line: B<Rt> a byte-matrix rung (T1: its k_dp_tile form), W<WS> a wide rung, V<R> the wave
+// sweep, L the literal sweep, each followed by ":" and its dp_kind_of -- e.g. "B4:1 W1024:3 W2048:4 ... V16:2 L:0".
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -47,6 +51,7 @@
 #include "../twin_hash.h"
 #include "../pindex_stage.h"
 #include "../keys.h"
+#include "../dp_plan.h"
 
 static int tie_extent_selftest()
 {
@@ -373,8 +378,26 @@ static int twin_hash_selftest(const char *path, int bits, bool slots_only)
     return 0;
 }
 
+static int dp_plan_selftest()
+{
+    unsigned long long max_ext, f0, n;
+    int lit, wave, safe, tile;
+    while (std::scanf("%llu %llu %llu %d %d %d %d", &max_ext, &f0, &n, &lit, &wave, &safe, &tile) == 7) {
+        const DpPlan p = dp_plan(max_ext, f0, n, DpPlanOptions{lit != 0, wave != 0, safe != 0, tile != 0});
+        for (int i = 0; i < p.count; i++) {
+            const DpRung &r = p.rung[i];
+            const char tag = r.family == DP_BYTES ? (r.tile ? 'T' : 'B') : r.family == DP_WIDE ? 'W' : r.family == DP_WAVE ? 'V' : 'L';
+            if (r.family == DP_LITERAL) std::printf("%sL:%d", i ? " " : "", dp_kind_of(r));
+            else std::printf("%s%c%u:%d", i ? " " : "", tag, r.size, dp_kind_of(r));
+        }
+        std::printf("\n");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && std::string(argv[1]) == "dp_plan") return dp_plan_selftest();
     if (argc == 4 && (std::string(argv[1]) == "twin-hash" || std::string(argv[1]) == "twin-slots"))
         return twin_hash_selftest(argv[2], std::atoi(argv[3]), std::string(argv[1]) == "twin-slots");
     if (argc == 2 && std::string(argv[1]) == "tie-extent") return tie_extent_selftest();

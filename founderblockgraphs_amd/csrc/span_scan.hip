@@ -31,7 +31,8 @@
 // the K symbols from here on are not K consecutive columns of the row (a gap run, the row's end, among them), i.e.
 // fi = column + g - 1 (fbg.cpp:1666) does not hold and the member looks its extent up.  The text position of a cell,
 // needed only for text comparisons and lookups, comes from a table of 20 bytes per 128 cells (symbols before the window,
-// bitmap of its symbols).  (m + 1) * (n + 1) < 2^30; '-' among the ignore characters is not for this scan.
+// bitmap of its symbols).  (m + 1) * (n + 1) < 2^32 (fbg_span_eligible; from 2^30 cells on the two flags of a slot sit in its
+// key word, fbg_span_key_flags); '-' among the ignore characters is not for this scan.
 #include "fbg_internal.h"
 #include "keys.h"
 #include "text_cmp.h"

@@ -1,4 +1,4 @@
-"""The three segmentation DPs of csrc/dp.hip at their sentinels, tiers, tiles and rings.
+"""The three segmentation DPs of csrc/dp.hip (dp_bytes.hip, dp_wide.hip) at their sentinels, tiers, tiles and rings.
 
 fbg_repeatfree_dp takes its tier from the longest minimal block (R = 1 / 2 / 4 up to 31 / 63 / 126 columns, the one-lane
 kernel above), stores a column's minimal block length in a byte whose 255 also says "no block ends here", and hands an
@@ -11,12 +11,17 @@ The inputs below sit on each of those numbers and one beside them.  Every genera
 every GPU check is exact equality with the oracle (oracle/pyoracle.py): s, prev, minmaxlength, backtrack, boundaries and
 the "no segmentation" verdict.  What ran is read from the read-only options dp_kind, ne_dp_kind and dp_attempts."""
 import functools
+import os
+import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import fbg_options
 from oracle import pyoracle as O
+
+
+SELFTEST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "founderblockgraphs_amd", "fbg_host_selftest")
 
 
 def _same(got, want, what):
@@ -247,7 +252,7 @@ def outlier_f(E, place, seed=None):
 # fbg_dp_minmax (dp.hip) for f[0] = 0, n >= 2 * DPW_B = 256, default options, by max_ext = the longest f[x] + 1 - x (k_dp_keys):
 #   bound = 2 max_ext + 2; R = bound <= 64 ? 1 : <= 128 ? 2 : <= 254 ? 4 : <= 512 ? 8 : <= 1024 ? 16 : 0
 #   R != 0 (max_ext <= 511): the byte matrices first, Rt = the smallest of 1, 2, 4 with 64 Rt >= max_ext + 2 (4 beyond) -> dp_kind 1
-#   R == 0 and max_ext + 2 <= 16384 (wide_ok): try_wide, WS = the smallest of 1024 .. 16384 that is >= max_ext + 2 -> dp_kind 3 .. 7
+#   R == 0 and max_ext + 2 <= 16384 (dp_wide_ok, dp_plan.h): the wide rungs, WS = the smallest of 1024 .. 16384 that is >= max_ext + 2 -> dp_kind 3 .. 7
 #   else the literal sweep -> dp_kind 0
 # each rung settles when no value reaches its limit (k_dp_expand: acc >= 64 R, 255 for R = 4; k_dpw_chain2: v >= WS)
 #             (max_ext from, to, dp_kind, the first rung's limit)
@@ -328,7 +333,7 @@ def test_single_outlier(engine, place, capsys):
 # (outlier, columns that cannot start a block, the first rung's limit, the next rung's, dp_kind, dp_attempts): the rungs that widen
 #   max_ext 3: R = 1, one rung of 64, then neither matrices nor wave sweep are left: the literal sweep
 #   max_ext 40: R = 2, rungs of 64 and 128;  max_ext 101: R = 4, rungs of 128 and 256 (values below 255)
-#   max_ext 601: R = 0, try_wide with WS = 1024, then 2048 (dp_kind 4)
+#   max_ext 601: R = 0, the wide rungs WS = 1024, then 2048 (dp_kind 4)
 WIDENING = ((2, 70, 64, None, 0, 2), (39, 70, 64, 128, 1, 2), (100, 130, 128, 255, 1, 2), (600, 1100, 1024, 2048, 4, 2))
 
 
@@ -362,6 +367,51 @@ def test_widening_rungs(engine):
     for E, run, _, _, kind, attempts in WIDENING:
         _check_f(engine, widening_f(E, run), (E, run))
         assert (engine.get_option("dp_kind"), engine.get_option("dp_attempts")) == (kind, attempts), (E, run)
+
+
+# Sequences the ladder (csrc/dp_plan.h) has beyond those above, n = 4000, one launch each:
+#   (E, run, options, the oracle's largest minmaxlength lies in [lo, hi), the plan for this input, (dp_kind, dp_attempts))
+#   max_ext 151, R = 8: the byte rung of 4 flags the block over the run (301 >= 255), no wide rung (151 + 2 <= 256), the wave sweep
+#   max_ext 301, R = 16: the byte rung of 4, then WIDE(1024)
+#   the first input under dp_wave: the wave sweep alone;  max_ext 151 without a run under dp_safe_window: Rt starts at R = 8,
+#   above the byte matrices, so no byte rung: the wave sweep
+# The pairs are what the commit before the ladder became a plan reported for these inputs on an MI355X (the tests were run
+# once on its library: profiles/dp_ladder_summary.txt, section 2); each is also the dp_kind of a rung of the plan and that rung's
+# position in it.
+LADDER_SEQUENCES = (
+    (150, 300, {}, (255, 512), ("B4", "V8", "L"), (2, 2)),
+    (300, 300, {}, (255, 1024), ("B4", "W1024", "W2048", "W4096", "W8192", "W16384", "V16", "L"), (3, 2)),
+    (150, 300, {"dp_wave": 1}, (255, 512), ("V8", "L"), (2, 1)),
+    (150, 0, {"dp_safe_window": 1}, (0, 512), ("V8", "L"), (2, 1)))
+RUNG_KIND = {"B": lambda size: 1, "W": lambda size: 3 + (size // 1024).bit_length() - 1, "V": lambda size: 2, "L": lambda size: 0}
+
+
+@pytest.mark.parametrize("case", range(len(LADDER_SEQUENCES)))
+def test_ladder_sequence_inputs_settle_where_the_case_needs(case):
+    E, run, options, (lo, hi), plan, (kind, attempts) = LADDER_SEQUENCES[case]
+    f = widening_f(E, run)
+    assert len(f) == 4000 and f[0] == 0
+    fx = f.astype(np.int64)
+    assert int((fx + 1 - np.arange(len(f)))[fx < len(f)].max()) == E + 1
+    mml, _, b = O.minmax_dp(f)
+    assert lo <= int(mml.max()) < hi and b[-1] == len(f)
+    rung = plan[attempts - 1]                                   # the pair names a rung of the plan: its kind, its position
+    assert RUNG_KIND[rung[0]](int(rung[1:] or 0)) == kind
+    line = f"{E + 1} 0 4000 0 {options.get('dp_wave', 0)} {options.get('dp_safe_window', 0)} 0\n"
+    r = subprocess.run([SELFTEST, "dp_plan"], input=line, capture_output=True, text=True)      # ... of dp_plan.h's plan
+    assert r.returncode == 0 and tuple(w.split(":")[0] for w in r.stdout.split()) == plan, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", range(len(LADDER_SEQUENCES)))
+def test_ladder_sequences(engine, case, capsys):
+    E, run, options, _, _, want = LADDER_SEQUENCES[case]
+    with fbg_options(engine, options):
+        _check_f(engine, widening_f(E, run), (E, run, options))
+        got = (engine.get_option("dp_kind"), engine.get_option("dp_attempts"))
+    with capsys.disabled():
+        print(f"\n  ladder sequence {case}: (dp_kind, dp_attempts) {got}")
+    assert got == want, (E, run, options)
 
 
 def random_f(rng, n, max_ext, style):
