@@ -645,6 +645,26 @@ def test_truth(engine):
             assert len(cols) and lo <= cols.min() and cols.max() < hi, k
 
 
+def z_lines(m):
+    """The Z line of every pair, as fbg_locate --pairs prints it."""
+    return [b"Z\t*" if w == PM.NO_PAIR else b"Z\t%d\t%d\t%d\t%d" % (w, s, lo, hi)
+            for w, s, lo, hi in zip(m.which.tolist(), m.pair_score.tolist(), m.t_lo.tolist(), m.t_hi.tolist())]
+
+
+def chain_lines(sd, m, k):
+    """The C / A / T lines of the chains m (chain_off, score, anchor_place, anchor_seed) over the seeds sd of k patterns:
+    pattern by pattern, forward and then reverse."""
+    want, strand, best = [], *strands_of(m, k)
+    for R in range(k):
+        for v in (R, R + k):
+            a, e = int(m.chain_off[v]), int(m.chain_off[v + 1])
+            want.append(b"C\t%d\t%d" % (m.score[v], e - a))
+            want += [b"A\t%d\t%d\t%d\t%d" % (sd.q_start[t], sd.length[t], sd.occ.start_row[g], sd.occ.start_col[g])
+                     for g, t in zip(m.anchor_place[a:e].tolist(), m.anchor_seed[a:e].tolist())]
+        want.append(b"T\t%s\t%d" % ({0: b"+", 1: b"-", 0xff: b"*"}[int(strand[R])], best[R]))
+    return want
+
+
 @pytest.mark.gpu
 def test_tool_prints_the_pairs_and_the_adopted_chains(engine, tmp_path):
     from oracle import pyoracle as O
@@ -669,29 +689,11 @@ def test_tool_prints_the_pairs_and_the_adopted_chains(engine, tmp_path):
         same(plain, m, "tool")
     assert (m.which != PM.NO_PAIR).any() and (m.which == PM.NO_PAIR).any() and not np.array_equal(m.chain_off, ch0.chain_off)
     lines = got.stdout.splitlines()
-    want_z = [b"Z\t*" if w == PM.NO_PAIR else b"Z\t%d\t%d\t%d\t%d" % (w, s, lo, hi)
-              for w, s, lo, hi in zip(m.which.tolist(), m.pair_score.tolist(), m.t_lo.tolist(), m.t_hi.tolist())]
-    assert [ln for ln in lines if ln.startswith(b"Z\t")] == want_z
+    assert [ln for ln in lines if ln.startswith(b"Z\t")] == z_lines(m)
     assert all(lines[i - 1].startswith(b"T\t") for i, ln in enumerate(lines) if ln.startswith(b"Z\t"))
     # the C / A / T lines: those of the adopted chains, pattern by pattern, forward and then reverse
-    want, strand, best = [], *strands_of(m, k)
-    for R in range(k):
-        for v in (R, R + k):
-            a, e = int(m.chain_off[v]), int(m.chain_off[v + 1])
-            want.append(b"C\t%d\t%d" % (m.score[v], e - a))
-            want += [b"A\t%d\t%d\t%d\t%d" % (sd.q_start[t], sd.length[t], sd.occ.start_row[g], sd.occ.start_col[g])
-                     for g, t in zip(m.anchor_place[a:e].tolist(), m.anchor_seed[a:e].tolist())]
-        want.append(b"T\t%s\t%d" % ({0: b"+", 1: b"-", 0xff: b"*"}[int(strand[R])], best[R]))
-    assert [ln for ln in lines if ln[:2] in (b"C\t", b"A\t", b"T\t")] == want
+    assert [ln for ln in lines if ln[:2] in (b"C\t", b"A\t", b"T\t")] == chain_lines(sd, m, k)
     # every other line is that of the run without --pairs, which is the parent's output byte for byte
     other = lambda out: [ln for ln in out.splitlines() if ln[:2] not in (b"C\t", b"A\t", b"T\t", b"Z\t")]      # noqa: E731
     assert other(got.stdout) == other(base.stdout)
-    want0, strand0, best0 = [], *strands_of(ch0, k)
-    for R in range(k):
-        for v in (R, R + k):
-            a, e = int(ch0.chain_off[v]), int(ch0.chain_off[v + 1])
-            want0.append(b"C\t%d\t%d" % (ch0.score[v], e - a))
-            want0 += [b"A\t%d\t%d\t%d\t%d" % (sd.q_start[t], sd.length[t], sd.occ.start_row[g], sd.occ.start_col[g])
-                      for g, t in zip(ch0.anchor_place[a:e].tolist(), ch0.anchor_seed[a:e].tolist())]
-        want0.append(b"T\t%s\t%d" % ({0: b"+", 1: b"-", 0xff: b"*"}[int(strand0[R])], best0[R]))
-    assert [ln for ln in base.stdout.splitlines() if ln[:2] in (b"C\t", b"A\t", b"T\t")] == want0 and b"Z\t" not in base.stdout
+    assert [ln for ln in base.stdout.splitlines() if ln[:2] in (b"C\t", b"A\t", b"T\t")] == chain_lines(sd, ch0, k) and b"Z\t" not in base.stdout
