@@ -126,6 +126,8 @@ SIGNATURES = {
     "fbg_pindex_mapq_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
     "fbg_pindex_chains_pairs": (C.c_int, [vp, C.c_uint64, C.c_uint64, u8p, u32p, u32p, u32p, u64p, u32p, u32p, u32p, u32p, u32p,
                                           u64p, u32p, u64p, C.POINTER(C.c_double)]),
+    "fbg_pindex_pairs_align": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, u8p, u32p, u32p, u32p, u32p, u32p, u8p, u32p,
+                                         u32p, u32p, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_seeds_strands": (C.c_int, [vp, u8p, u64p, C.c_uint64, u8p, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_double)]),
     "fbg_pindex_chain_strands": (C.c_int, [vp, u8p, u32p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "fbg_segmentation_validate": (C.c_int, [vp, u64p, C.c_uint64, u8p, C.c_uint64, u8p, u64p, u64p, C.POINTER(C.c_double)]),

@@ -320,6 +320,7 @@ class Engine:
         build = self._L.fbg_pindex_build_segmentation_rows if rows else self._L.fbg_pindex_build_segmentation
         self._chk(build(self._h, _u64(b), len(b), C.byref(h)))
         pix = PatternIndex._adopt(self, h, len(b))
+        pix._has_rows = bool(rows)
         if not hasattr(self, "_pindexes"):
             self._pindexes = weakref.WeakSet()
         self._pindexes.add(pix)
@@ -617,7 +618,7 @@ class PatternIndex:
 
     def chains(self, band=None, min_score=0, rows=False, align=False, pad=16, max_window=0, cigar=False, by_row=False,
                graph=False, graph_pad=16, max_cells=0, select=None, graph_cigar=False, mapq=False, mapq_margin=0, pairs=None,
-               adopt_pairs=False):
+               adopt_pairs=False, pair_align=False, pair_max_edits=0xffffffff, pair_max_window=0, pair_select=None):
         """Co-linear chaining of the seeds of the last seeds() call (fbg_pindex_chains and _fetch; an index built by
         Engine.pattern_index_of_segmentation only): per read the best-scoring selection of its seeds' start places
         that ascends in the read and in the MSA columns, the surplus of columns over read symbols between two
@@ -654,7 +655,14 @@ class PatternIndex:
         .pair_hi, .rescue_off, .rescue_score, .rescue_lo, .rescue_hi, .rescue_place, .rescue_seed, .rescue(v), .pair(p),
         .pair_stats and .pairs_ms.  adopt_pairs=True: the chosen chains replace the chains of their reads and the twins of
         those reads get the empty chain, right after the chaining call: chain_off, score, anchor_place, anchor_seed, the
-        strands and every field of rows=, align=, cigar=, graph=, graph_cigar= and mapq= then describe the adopted chains."""
+        strands and every field of rows=, align=, cigar=, graph=, graph_cigar= and mapq= then describe the adopted chains.
+        pair_align=True (with pairs=, an index built with rows=True only): after the pairing call, and after its adoption,
+        every virtual read without a chain whose partner has one is aligned in the insert window on the row of the partner's
+        chain, the insert counted in symbols of that row, and every pair is decided from these alignments
+        (fbg_pindex_pairs_align), as Chains.mate_row, .mate_edits, .mate_start, .mate_end, .mate_insert, .mate_which,
+        .mate_score, .mate_lo, .mate_hi, .mate_stats and .mate_ms.  pair_max_edits: the most edits an accepted alignment may
+        have; pair_max_window (0: no limit): a longer window is skipped; pair_select (one entry per virtual read, None: the
+        reads without a chain): the reads to align where their partner has a chain."""
         if adopt_pairs and pairs is None:
             raise ValueError("adopt_pairs=True needs pairs=(min_insert, max_insert)")
         if pairs is not None:
@@ -663,6 +671,13 @@ class PatternIndex:
             lo_ins, hi_ins = (int(x) for x in pairs)
             if not 0 <= lo_ins <= hi_ins:
                 raise ValueError("pairs=(min_insert, max_insert) with 0 <= min_insert <= max_insert")
+        if pair_align:
+            if pairs is None:
+                raise ValueError("pair_align=True needs pairs=(min_insert, max_insert)")
+            if not getattr(self, "_has_rows", False):
+                raise ValueError("pair_align=True needs an index built with rows=True")
+            if not 0 <= int(pair_max_edits) <= 0xffffffff or pair_max_window < 0:
+                raise ValueError("pair_max_edits must fit 32 bits and pair_max_window must be 0 or more")
         if mapq_margin < 0:
             raise ValueError("mapq_margin must be 0 or more")
         if cigar and not align:
@@ -711,6 +726,24 @@ class PatternIndex:
             t3 = int(roff[k])
             paired = (pw[:npairs], psc[:npairs], plo[:npairs], phi[:npairs], roff, rsc[:k], rlo[:k], rhi[:k], rplace[:t3], rseed[:t3],
                       dict(zip(Chains.PAIR_STATS, (int(x) for x in pstats))), ms11.value)
+        mated = None
+        if pair_align:
+            sel = None
+            if pair_select is not None:
+                sel = np.ascontiguousarray(np.asarray(pair_select) != 0, dtype=np.uint8)
+                if sel.shape != (k,):
+                    raise ValueError("pair_select takes one entry per virtual read of the last seeds() call")
+            per_read = [np.zeros(max(k, 1), dtype=np.uint32) for _ in range(5)]
+            mw = np.zeros(max(npairs, 1), dtype=np.uint8)
+            per_pair = [np.zeros(max(npairs, 1), dtype=np.uint32) for _ in range(3)]
+            mstats = np.zeros(10, dtype=np.uint64)
+            ms12 = C.c_double(0)
+            self._eng._chk(self._L.fbg_pindex_pairs_align(self._h, lo_ins, min(hi_ins, 0xffffffffffffffff), int(pair_max_edits),
+                                                          min(int(pair_max_window), 0xffffffffffffffff), None if sel is None else _u8(sel),
+                                                          *[u32(a) for a in per_read], _u8(mw), *[u32(a) for a in per_pair], _u64(mstats),
+                                                          C.byref(ms12)))
+            mated = tuple(a[:k] for a in per_read) + (mw[:npairs],) + tuple(a[:npairs] for a in per_pair) + \
+                (dict(zip(Chains.MATE_STATS, (int(x) for x in mstats))), ms12.value)
         t = int(chain_off[k])
         place, seed = np.zeros(max(t, 1), dtype=np.uint32), np.zeros(max(t, 1), dtype=np.uint32)
         self._eng._chk(self._L.fbg_pindex_chains_fetch(self._h, place.ctypes.data_as(_lib.u32p), seed.ctypes.data_as(_lib.u32p),
@@ -719,6 +752,9 @@ class PatternIndex:
         if paired is not None:
             (out.pair_which, out.pair_score, out.pair_lo, out.pair_hi, out.rescue_off, out.rescue_score, out.rescue_lo, out.rescue_hi,
              out.rescue_place, out.rescue_seed, out.pair_stats, out.pairs_ms) = paired
+        if mated is not None:
+            (out.mate_row, out.mate_edits, out.mate_start, out.mate_end, out.mate_insert, out.mate_which, out.mate_score, out.mate_lo,
+             out.mate_hi, out.mate_stats, out.mate_ms) = mated
         if by_row:
             out.chain_row, out.n_best_rows, out.by_row = crow[:k], nbest[:k], True
         given = getattr(self, "_seed_given", None)
@@ -1068,6 +1104,16 @@ class Chains:
       pair_stats      {which0 .. which3, none, places_kept, places_excluded, rescue_differs}: stats[] of the call
       pairs_ms        device time of fbg_pindex_chains_pairs
     With adopt_pairs=True every other field describes the adopted chains.
+    and, asked for with pair_align=True beside pairs= (None otherwise; include/fbg_hip.h, fbg_pindex_pairs_align):
+      mate_row        uint32 per virtual read: the row of its partner's chain on which its window lies, 0xffffffff for a read
+                      that is not selected or whose partner's chain no row carries
+      mate_edits, mate_start, mate_end   uint32 per virtual read: the edits of the read against its insert window and the
+                      stretch of the row's text it lies on, as edits, t_start and t_end; 0xffffffff where nothing was aligned
+      mate_insert     uint32 per virtual read: the pair's extent in symbols of the row, 0xffffffff unless accepted
+      mate_which, mate_score, mate_lo, mate_hi   per pair: the chosen candidate 0 .. 3 (0xff without one), the chain's score
+                      plus the aligned read's length less its edits, and the pair's extent on the row
+      mate_stats      {selected, aligned, no_row, empty, too_long, too_wide, rejected_edits, rejected_insert, cells, pairs}
+      mate_ms         device time of fbg_pindex_pairs_align
     device_ms: device time of the chaining; fetch_ms: of the copies of the two anchor arrays."""
 
     def __init__(self, chain_off, score, anchor_place, anchor_seed, device_ms, fetch_ms):
@@ -1087,8 +1133,11 @@ class Chains:
         self.second_place = self.second_seed = self.mapq_stranded = self.best_mapq = self.mapq_ms = None
         self.pair_which = self.pair_score = self.pair_lo = self.pair_hi = self.pair_stats = self.pairs_ms = None
         self.rescue_off = self.rescue_score = self.rescue_lo = self.rescue_hi = self.rescue_place = self.rescue_seed = None
+        self.mate_row = self.mate_edits = self.mate_start = self.mate_end = self.mate_insert = None
+        self.mate_which = self.mate_score = self.mate_lo = self.mate_hi = self.mate_stats = self.mate_ms = None
 
     PAIR_STATS = ("which0", "which1", "which2", "which3", "none", "places_kept", "places_excluded", "rescue_differs")
+    MATE_STATS = ("selected", "aligned", "no_row", "empty", "too_long", "too_wide", "rejected_edits", "rejected_insert", "cells", "pairs")
 
     def rescue(self, v):
         """int64[rows, 2]: (anchor_place, anchor_seed) of the rescue chain of virtual read v, as of()."""

@@ -5,6 +5,7 @@
 //   fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]] [--msa=msa.fasta]
 //              [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows] [--by-row] [--align[=PAD]] [--cigar]
 //              [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE] [--mapq[=MARGIN]] [--pairs=MIN,MAX]
+//              [--pair-align[=MAX_EDITS]]
 //
 // Patterns are whitespace-separated tokens from FILE or stdin, read as `std::cin >> pattern` reads them (a last
 // token without whitespace after it sets EOF and is not answered, as in locate_patterns.cpp:47-53), and answered
@@ -92,6 +93,15 @@
 //   Z <tab> which <tab> pair_score <tab> t_lo <tab> t_hi    the candidate 0 .. 3, the sum of the two scores, the pair's columns
 // or `Z <tab> *` for a pair without a valid combination, whose chains stay as they were.  The insert is counted in MSA
 // columns, forward-reverse orientation only.  Without --pairs no byte of stdout or of the GAF file changes.
+// --pair-align[=MAX_EDITS] (with --pairs and --rows) then aligns every strand of a pattern that has no chain, while the
+// other mate's opposite strand has one, inside the window of MIN .. MAX symbols that this chain opens on the smallest row
+// carrying it (fbg_pindex_pairs_align), and decides every pair again from these alignments.  After the other lines of a
+// strand,
+//   Y <tab> row <tab> edits <tab> t_start <tab> t_end <tab> insert    the row, the fewest edits of the pattern against the window,
+// the stretch of the row's text it lies on, and the pair's extent in symbols of the row (* where there are more than
+// MAX_EDITS edits or the extent is below MIN), or `Y <tab> *` where nothing was aligned; after a pair's Z line,
+//   W <tab> which <tab> score <tab> lo <tab> hi    the candidate 0 .. 3, the chain's score plus the aligned pattern's length less
+// its edits, the pair's extent on the row, or `W <tab> *`.  Without --pair-align no byte of stdout changes.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -111,7 +121,7 @@ static int usage(const char *msg)
               << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
               << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
               << "                  [--by-row] [--align[=PAD]] [--cigar] [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE]\n"
-              << "                  [--mapq[=MARGIN]] [--pairs=MIN,MAX]\n"
+              << "                  [--mapq[=MARGIN]] [--pairs=MIN,MAX] [--pair-align[=MAX_EDITS]]\n"
               << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
               << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
               << "                     at most M of each per pattern (default 64)\n"
@@ -162,7 +172,13 @@ static int usage(const char *msg)
               << "                     reverse mate's last; a mate is chained again inside the window of the other's chain, the\n"
               << "                     best valid combination replaces the pair's chains (every line then describes those), and\n"
               << "                     after the second pattern's T line a Z line: candidate, pair score, first and last column\n"
-              << "                     (Z and * without a valid combination)\n";
+              << "                     (Z and * without a valid combination)\n"
+              << "  --pair-align[=MAX_EDITS]  needs --pairs and --rows: a strand without a chain is aligned inside the window of\n"
+              << "                     MIN .. MAX symbols that the other mate's chain opens on the smallest row carrying it; after\n"
+              << "                     a strand's lines a Y line: row, edits, start and end in the row's text, the pair's extent\n"
+              << "                     in symbols (* with more than MAX_EDITS edits or below MIN; Y and * if nothing was aligned),\n"
+              << "                     and after a pair's Z line a W line: candidate, score, first and last position on the row\n"
+              << "                     (W and * without one)\n";
     return EXIT_FAILURE;
 }
 
@@ -246,7 +262,8 @@ static void print_runs(std::ostream &os, const std::vector<uint32_t> &ops, uint6
 int main(int argc, char **argv)
 {
     std::string graph, patterns, msa_path, complement, gaf_path;
-    bool graph_cigar = false, have_gaf = false, want_mapq = false, want_pairs = false;
+    bool graph_cigar = false, have_gaf = false, want_mapq = false, want_pairs = false, pair_align = false;
+    uint32_t max_edits = 0xffffffffu;
     uint64_t min_insert = 0, max_insert = 0;
     uint64_t margin = 0;
     bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false, graph_align = false;
@@ -357,6 +374,18 @@ int main(int argc, char **argv)
             max_insert = y;
             continue;
         }
+        if (a == "--pair-align") { pair_align = true; continue; }
+        if (a.compare(0, 13, "--pair-align=") == 0) {
+            const std::string v = a.substr(13);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end || m > 0xffffffffull)
+                return usage(("--pair-align takes a number of edits, not '" + v + "'").c_str());
+            pair_align = true;
+            max_edits = (uint32_t)m;
+            continue;
+        }
         if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
         return usage(("unknown argument " + a).c_str());
     }
@@ -374,6 +403,7 @@ int main(int argc, char **argv)
     if (have_gaf && !graph_cigar) return usage("--gaf needs --graph-cigar");
     if (want_mapq && !chain) return usage("--mapq needs --chain");
     if (want_pairs && !(chain && strands)) return usage("--pairs needs --chain and --strands");
+    if (pair_align && !(want_pairs && rows)) return usage("--pair-align needs --pairs and --rows");
     if (have_gaf && gaf_path.empty()) return usage("--gaf takes a file");
     if (have_complement && !strands) return usage("--complement needs --strands");
     if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
@@ -488,6 +518,8 @@ int main(int argc, char **argv)
     std::vector<uint8_t> quality(nv + 1, 0);
     std::vector<uint8_t> pair_which(np / 2 + 1, 0);        // --pairs: the candidate, its score and columns per pair
     std::vector<uint32_t> pair_out[3];
+    std::vector<uint32_t> mate[5], mate_out[3];             // --pair-align: row, edits, t_start, t_end, insert; score, lo, hi
+    std::vector<uint8_t> mate_which(np / 2 + 1, 0);
     if (rc == FBG_OK && seeds) {
         if (strands) {
             uint8_t table[256];
@@ -524,6 +556,13 @@ int main(int argc, char **argv)
             rc = fbg_pindex_chains_pairs(ix, min_insert, max_insert, pair_which.data(), pair_out[0].data(), pair_out[1].data(),
                                          pair_out[2].data(), rescue_off.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
                                          chain_off.data(), chain_score.data(), nullptr, nullptr);
+        }
+        if (rc == FBG_OK && pair_align) {      // on the adopted chains; writes nothing that a later stage reads
+            for (int k = 0; k < 5; k++) mate[k].resize(nv + 1);
+            for (int k = 0; k < 3; k++) mate_out[k].resize(np / 2 + 1);
+            rc = fbg_pindex_pairs_align(ix, min_insert, max_insert, max_edits, 0, nullptr, mate[0].data(), mate[1].data(), mate[2].data(),
+                                        mate[3].data(), mate[4].data(), mate_which.data(), mate_out[0].data(), mate_out[1].data(),
+                                        mate_out[2].data(), nullptr, nullptr);
         }
         if (rc == FBG_OK && chain) {
             anchor_place.resize(chain_off[nv] + 1);
@@ -660,6 +699,12 @@ int main(int argc, char **argv)
                         gaf << '\n';
                     }
                 }
+                if (pair_align && mate[1][v] == FBG_ALIGN_NONE) std::cout << "Y\t*\n";
+                else if (pair_align) {
+                    std::cout << "Y\t" << mate[0][v] << '\t' << mate[1][v] << '\t' << mate[2][v] << '\t' << mate[3][v] << '\t';
+                    if (mate[4][v] == FBG_ALIGN_NONE) std::cout << "*\n";
+                    else std::cout << mate[4][v] << '\n';
+                }
             }
         };
         for (uint64_t k = 0; k < np; k++) {
@@ -685,6 +730,10 @@ int main(int argc, char **argv)
                         if (pair_which[p] == 0xffu) std::cout << "Z\t*\n";
                         else std::cout << "Z\t" << (unsigned)pair_which[p] << '\t' << pair_out[0][p] << '\t' << pair_out[1][p] << '\t'
                                        << pair_out[2][p] << '\n';
+                        if (pair_align && mate_which[p] == 0xffu) std::cout << "W\t*\n";
+                        else if (pair_align)
+                            std::cout << "W\t" << (unsigned)mate_which[p] << '\t' << mate_out[0][p] << '\t' << mate_out[1][p] << '\t'
+                                      << mate_out[2][p] << '\n';
                     }
                 }
             }

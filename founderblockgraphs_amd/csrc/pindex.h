@@ -11,6 +11,7 @@
 //   pindex_gcigar.hip     the alignment path of a read against the stretch of the graph that path spells
 //   pindex_mapq.hip       the second-best chain of a read outside the columns of its best one, and a mapping quality
 //   pindex_pairs.hip      paired reads: a mate's chain rescued in the insert window of the other's, the pick per pair, adopt
+//   pindex_pairs_align.hip   paired reads: a mate without a chain aligned in the insert window on the row of the other's chain
 // Device helpers shared by kernels of several files: pindex_dev.h.  A kernel is defined in one file; another file that
 // needs its launch calls a launcher declared at the end of this header.
 // Two things tie the stages together.  The reads of the last seeds call lie in buffers of their own (PsState batch), which
@@ -63,6 +64,9 @@
 #define PP_PRIMARY 1          // stays; the chosen rescue chain replaces it; the twin of a chosen read gets the empty chain
 #define PP_RESCUE 2
 #define PP_TWIN 3
+#define PL_CTR 11             // counters of fbg_pindex_pairs_align, as its stats[]: reads selected, aligned, whose partner has no row,
+                              // empty, too long, too wide, rejected by edits, rejected by insert; cells; pairs with a candidate;
+                              // and, not reported, the non-empty chains without a row (what k_pr_chain counts)
 
 // What k_po_sizes leaves for k_po_expand, for n items (the patterns of fbg_pindex_occurrences, or the seeds of
 // fbg_pindex_seeds): totals, capped sizes and their scans, the first slot of either list, k or the length, restarts;
@@ -176,6 +180,15 @@ struct PpState {
     DevBuf span, mcol, rspan, pick, which, src, ctr;
 };
 
+// fbg_pindex_pairs_align, V virtual reads and P = V / 4 pairs.  nrows / first (2 V, what k_pr_chain leaves: the row choice);
+// frag: per virtual read (r, fs, fe, |G_r|), r = PR_NONE without a chain or a row; info, start, wlen, woff, win and out (row,
+// edits, t_start, t_end: 4 V) as in PaState, for the selected reads over their insert windows; ins: the insert per read;
+// pick: per pair pair_score, t_lo, t_hi (3 P); which: per pair the candidate; sel: the caller's mask; ctr: PL_CTR counters.
+// Nothing outlives the call: it returns all of it.
+struct PlState {
+    DevBuf nrows, frag, info, start, wlen, woff, win, out, ins, pick, which, sel, ctr;
+};
+
 // The reads of the last fbg_pindex_seeds / _seeds_strands, in buffers that only a seeds call writes: reads (bytes of them,
 // padded as px_front pads) and roff (n + 1 byte offsets).  n: the reads on the device, with _strands the 2 x given virtual
 // ones (stranded); comp: the complement table of that call (256 bytes).
@@ -232,6 +245,7 @@ struct fbg_pindex {
     PjState gj;
     PqState pq;
     PpState pp;
+    PlState pl;
     uint64_t n_edges = 0, nctab = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, sv0 = nullptr, sv1 = nullptr;   // made with the index (px_new)
     std::vector<DevBuf *> bufs;   // the index's own device buffers: outside the context's workspaces and its accounting
@@ -456,3 +470,10 @@ PX_LOCAL void pr_chain_launch(fbg_pindex *ix, const PrDev &d, uint64_t n, uint64
 PX_LOCAL int pg_trace(fbg_pindex *ix, const PgIn *in, PgState &g, PsStage stage, uint64_t n, bool started, uint32_t *n_ops,
                       uint64_t *total_ops, double *device_ms, const char *who);
 PX_LOCAL int pg_fetch(fbg_pindex *ix, const PgState &g, uint64_t *off, uint32_t *ops);
+// pindex_align.hip, for fbg_pindex_pairs_align (pindex_pairs_align.hip): the prefix table reserved and, where no call has
+// built it yet, k_pa_prefix launched (the caller sets al.has_pref once its call has succeeded); what the alignment kernels
+// read, valid after pa_prefix; k_pa_gather and k_pa_edit over n reads on the caller's own info / start / woff / win / out
+PX_LOCAL int pa_prefix(fbg_pindex *ix);
+PX_LOCAL PaDev pa_dev(const fbg_pindex *ix);
+PX_LOCAL void pa_windows(fbg_pindex *ix, const PaDev &a, uint64_t n, const uint4 *info, const uint4 *start, const uint64_t *woff, uint8_t *win,
+                         uint32_t *out);

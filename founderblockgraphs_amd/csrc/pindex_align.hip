@@ -7,6 +7,8 @@
 //                                    registers (up to PA_REG_WORDS words of 64 read symbols) or in LDS;
 //   k_pg_sizes / k_pg_path / k_pg_compact   the backward pass again with its column history kept, the walk from (L, N)
 //                                    to (0, 0) along it, and the runs of the path back to back.
+// pa_prefix and pa_windows launch k_pa_prefix, k_pa_gather and k_pa_edit for fbg_pindex_pairs_align (pindex_pairs_align.hip)
+// too, on that call's own buffers.
 #include "pindex_dev.h"
 #include <rocprim/rocprim.hpp>
 
@@ -404,7 +406,7 @@ __global__ void k_pg_compact(const uint64_t *soff, const uint32_t *slots, const 
 }
 
 // what the alignment kernels read: the row table, the prefix table and the reads of the last seeds call
-static PaDev pa_dev(const fbg_pindex *ix)
+PaDev pa_dev(const fbg_pindex *ix)
 {
     const PrState &w = ix->rw;
     PaDev a;
@@ -417,6 +419,26 @@ static PaDev pa_dev(const fbg_pindex *ix)
     a.m = w.m;
     a.nb = ix->seg_nb;
     return a;
+}
+
+// The prefix table for the call that is running: reserved, and built where no successful call has built it
+int pa_prefix(fbg_pindex *ix)
+{
+    PaState &al = ix->al;
+    const PrState &w = ix->rw;
+    FBG_TRY(px_reserve(ix, al.pref, ix->seg_nb * w.m * 4));
+    if (!al.has_pref)             // the flag is set at the end of the call, once the table is known to be written
+        hipLaunchKernelGGL(k_pa_prefix, dim3(fbg_blocks(w.m, 64)), dim3(64), 0, ix->ctx->stream, (const uint32_t *)w.node_of.as<uint32_t>(),
+                           (const uint64_t *)w.loff.as<uint64_t>(), w.m, ix->seg_nb, al.pref.as<uint32_t>());
+    return FBG_OK;
+}
+
+// A wave per read gathers its window, a wave per read runs the two passes: n reads, n below 2^31
+void pa_windows(fbg_pindex *ix, const PaDev &a, uint64_t n, const uint4 *info, const uint4 *start, const uint64_t *woff, uint8_t *win, uint32_t *out)
+{
+    hipStream_t st = ix->ctx->stream;
+    hipLaunchKernelGGL(k_pa_gather, dim3((unsigned)n), dim3(FBG_WAVE), 0, st, a, info, start, woff, win);
+    hipLaunchKernelGGL(k_pa_edit, dim3((unsigned)n), dim3(FBG_WAVE), 0, st, a, info, woff, (const uint8_t *)win, n, out);
 }
 
 // ---- alignment (fbg_pindex_chains_align / _align_stats) ------------------------------------------------------------------
@@ -451,17 +473,15 @@ extern "C" int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t ma
     if (pad > (1ull << 33)) pad = 1ull << 33;         // positions and read offsets are below 2^32: beyond this nothing changes
     FBG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const uint64_t nb = ix->seg_nb;
-    FBG_TRY(px_reserve(ix, al.pref, nb * w.m * 4));
+    FBG_TRY(px_reserve(ix, al.pref, ix->seg_nb * w.m * 4));      // before ev0; pa_prefix then finds it there
     FBG_TRY(px_reserve(ix, al.nrows, 2 * n * 4));
     for (DevBuf *b : {&al.info, &al.start, &al.out}) FBG_TRY(px_reserve(ix, *b, n * 16));
     for (DevBuf *b : {&al.wlen, &al.woff}) FBG_TRY(px_reserve(ix, *b, (n + 1) * 8));
     FBG_TRY(px_reserve(ix, al.ctr, 5 * 8));
     PrDev d;
     FBG_TRY(pr_prepare(ix, d));                       // records ev0
+    FBG_TRY(pa_prefix(ix));
     const PaDev a = pa_dev(ix);
-    if (!al.has_pref)             // the flag is set at the end of the call, once the table is known to be written
-        hipLaunchKernelGGL(k_pa_prefix, dim3(fbg_blocks(w.m, 64)), dim3(64), 0, st, a.node_of, a.loff, a.m, a.nb, al.pref.as<uint32_t>());
     auto *ctr = al.ctr.as<unsigned long long>();
     FBG_HIP_TRY(ctx, hipMemsetAsync(ctr, 0, 5 * 8, st));
     const uint4 *rec = w.rec.as<uint4>();
@@ -481,10 +501,7 @@ extern "C" int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t ma
     FBG_HIP_TRY(ctx, hipStreamSynchronize(st));
     if (total) {
         FBG_TRY(px_reserve(ix, al.win, total));
-        hipLaunchKernelGGL(k_pa_gather, dim3((unsigned)n), dim3(FBG_WAVE), 0, st, a, (const uint4 *)al.info.as<uint4>(),
-                           (const uint4 *)al.start.as<uint4>(), (const uint64_t *)woff, al.win.as<uint8_t>());
-        hipLaunchKernelGGL(k_pa_edit, dim3((unsigned)n), dim3(FBG_WAVE), 0, st, a, (const uint4 *)al.info.as<uint4>(), (const uint64_t *)woff,
-                           (const uint8_t *)al.win.as<uint8_t>(), n, out);
+        pa_windows(ix, a, n, al.info.as<uint4>(), al.start.as<uint4>(), woff, al.win.as<uint8_t>(), out);
         FBG_HIP_TRY(ctx, hipGetLastError());
     }
     FBG_TRY(px_record_end(ix));

@@ -1013,7 +1013,8 @@ int fbg_pindex_mapq_stats(const fbg_pindex *ix, uint64_t *reads_with_second, uin
  *       the chains is written and nothing goes stale.
  * Limits.  The insert is counted in MSA witness columns: a stretch where most rows have gaps counts as long as its columns,
  * not as the fragment's symbols.  Forward-reverse orientation only.  No mapping quality of the pair.  A mate without a seed
- * inside the window is not rescued by alignment.
+ * inside the window is not rescued by alignment.  (fbg_pindex_pairs_align, below, does rescue such a mate, and counts the
+ * insert in symbols of a row.)
  * Errors, all FBG_ERR_INVALID: a NULL index, which or rescue_off; an index not built from a segmentation; the last seeds
  * call was not fbg_pindex_seeds_strands, or none succeeded; no successful chaining call since it; n odd;
  * min_insert > max_insert.  A failed check leaves the index as it was.  n == 0, and seeds without places: every pair
@@ -1084,6 +1085,68 @@ int fbg_pindex_chains_align(fbg_pindex *ix, uint64_t pad, uint64_t max_window, u
                             uint32_t *t_start, uint32_t *t_end, double *device_ms);
 int fbg_pindex_align_stats(const fbg_pindex *ix, uint64_t *aligned, uint64_t *unsupported, uint64_t *too_long,
                            uint64_t *too_wide, uint64_t *cells, uint64_t *max_read, uint64_t *table_bytes);
+
+/* Paired reads: a mate without a seed is rescued by alignment in the insert window that the other mate's chain opens on a
+ * row (an index built by fbg_pindex_build_segmentation_rows only; after a successful fbg_pindex_seeds_strands on an even
+ * number of reads and a current chaining result since it: fbg_pindex_chains, fbg_pindex_chains_by_row, or the chains that
+ * fbg_pindex_chains_pairs adopted).
+ *
+ * fbg_pindex_chains_pairs rescues a mate by chaining the seeds it has inside the window.  A mate with an edit every few
+ * symbols has no seed of min_length at all: no chain, no rescue chain, and the pair is lost.  This call aligns such a mate
+ * against the text of the row that carries its partner's chain, inside the insert window, with the recurrence of
+ * fbg_pindex_chains_align.  Layout, twin and partner as in the pairs section: V = 2n virtual reads, n / 2 pairs; G_r,
+ * p(r, j), x_i, D, edits, t_start and t_end as in the align section.
+ *   anchored read v     a virtual read whose current chain is non-empty.  r(v) is the smallest row that spells every anchor
+ *                       of it: exactly the row fbg_pindex_chains_align chooses.  Where no row does, v opens no window.
+ *                       Anchor i has x_i = p(r, block(u_i)) + o_i, read offset q_i and seed length k_i; L_v is the read
+ *                       length.  The fragment ends are projected along the first and the last anchor's diagonal:
+ *                       fs(v) = max(0, x_1 - q_1) and fe(v) = min(|G_r|, x_last + L_v - q_last);
+ *   selected read w     with v = partner(w) anchored: without select, w's own chain is empty; with select (2n bytes),
+ *                       select[w] != 0.  Every other w gets "none" in every array and is not counted;
+ *   the window of w     W = G_r[fs(v) : min(|G_r|, fs(v) + max_insert)) for v < n (v is the forward mate, w the reverse one);
+ *                       W = G_r[max(0, fe(v) - max_insert) : fe(v)) for v >= n.  max_insert is clamped at 2^33, as pad is.
+ *                       The insert is counted in symbols of row r, not in MSA columns;
+ *   status              of a selected w, tested in this order and counted: partner without a carrying row; empty, L_w == 0
+ *                       or |W| == 0; too long, L_w > max_read (1024); too wide, max_window != 0 and |W| > max_window; else
+ *                       aligned.  row[w] = r(v) for every status but the first; the other arrays are "none" unless aligned;
+ *   aligned             edits[w], t_start[w], t_end[w] follow the definition of fbg_pindex_chains_align for P = the text of
+ *                       w over this W, with w0 the window's start: the read global, both ends of W free, unit costs, the
+ *                       smallest end, then the largest start;
+ *   accepted            insert[w] = t_end[w] - fs(v) for v < n and fe(v) - t_start[w] for v >= n.  w is accepted iff
+ *                       edits[w] <= max_edits and insert[w] >= min_insert; insert[w] <= max_insert holds by construction.
+ *                       A w that is not accepted keeps row, edits, t_start and t_end and gets insert[w] = 0xffffffff.
+ *                       Rejections by edits and by insert are counted apart, edits first;
+ *   candidates          of pair p = (a, b), in the order of fbg_pindex_chains_pairs:
+ *                         0: F = chain(a), R = aligned(b + n)       1: F = aligned(a), R = chain(b + n)
+ *                         2: F = chain(b), R = aligned(a + n)       3: F = aligned(b), R = chain(a + n)
+ *                       With v the chained and w the aligned read, a candidate is valid iff w is accepted; its score is
+ *                       score[v] + L_w - edits[w].  The largest score wins, the smallest number among equals: which[p] in
+ *                       0 .. 3, pair_score[p], and t_lo[p] / t_hi[p] = fs(v) / t_end[w] for the even candidates and
+ *                       t_start[w] / fe(v) for the odd ones.  Without a valid candidate which[p] = 0xff, pair_score[p] = 0,
+ *                       t_lo[p] = t_hi[p] = 0xffffffff.
+ *   fbg_pindex_pairs_align   one call returns everything and nothing outlives it.  row, edits, t_start, t_end, insert: 2n
+ *       entries each, "none" is 0xffffffff, each may be NULL.  which (must be given), pair_score, t_lo, t_hi: n / 2 each.
+ *       stats[10] (may be NULL): reads selected; aligned; whose partner has no carrying row; empty; too long; too wide;
+ *       rejected by edits; rejected by insert; cells, the sum of L_w * |W| over the aligned reads; pairs with a candidate.
+ *       *device_ms (may be NULL): device time of the kernels, without the copies out.
+ * On the device.  The rows are chosen with the kernel of fbg_pindex_chains_rows, into a buffer of this call's own; one lane
+ * per virtual read takes fs and fe from the first and last anchor of its chain; one lane per virtual read takes selection,
+ * window and status and finds the block, node and offset at which the window starts by a search of the row's column of
+ * the prefix table (built here if no call has built it yet); the window lengths are scanned and their sum sizes the
+ * scratch; the gather and bit-vector kernels of fbg_pindex_chains_align run over all 2n reads (the wave of a read that is
+ * not aligned returns at once); one lane per pair accepts and picks.  Nothing of the align, CIGAR, graph, mapq, pairs or
+ * chain state is written: every current result of those calls stays current and unchanged.
+ * Limits.  No CIGAR of the rescued mate and no adoption of the alignment as a chain; rescue against a row, not the graph;
+ * forward-reverse orientation only; no mapping quality of the pair.
+ * Errors, all FBG_ERR_INVALID and leaving the index as it was: a NULL index or which; an index without the row table; the
+ * last seeds call was not fbg_pindex_seeds_strands, or none succeeded; no current chaining result since it; n odd;
+ * min_insert > max_insert.  FBG_ERR_TOO_LARGE for 2^31 virtual reads or more (a workgroup per virtual read).  n == 0, and
+ * all chains empty: every output "none", FBG_OK, nothing launched.  Scratch owned by the index: 97 bytes per virtual
+ * read, the windows, and what fbg_pindex_chains_rows keeps per seed and start place. */
+int fbg_pindex_pairs_align(fbg_pindex *ix, uint64_t min_insert, uint64_t max_insert, uint32_t max_edits, uint64_t max_window,
+                           const uint8_t *select, uint32_t *row, uint32_t *edits, uint32_t *t_start, uint32_t *t_end,
+                           uint32_t *insert, uint8_t *which, uint32_t *pair_score, uint32_t *t_lo, uint32_t *t_hi,
+                           uint64_t stats[10], double *device_ms);
 
 /* The alignment path (CIGAR) of each read that the last fbg_pindex_chains_align aligned (after a successful
  * fbg_pindex_chains_align since the last fbg_pindex_chains, and so since the last seeds call).
