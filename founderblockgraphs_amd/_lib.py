@@ -8,6 +8,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfbg_hip.so")
 
@@ -25,6 +27,32 @@ STAGES = ("text", "suffix_sort", "lcp", "rank_scan", "scan", "dp", "rank_kernel"
 
 u8p, u32p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 vp, ip, fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)
+
+
+# a numpy array as a pointer argument
+def _u8(a):
+    return a.ctypes.data_as(u8p)
+
+
+def _u32(a):
+    return a.ctypes.data_as(u32p)
+
+
+def _u64(a):
+    return a.ctypes.data_as(u64p)
+
+
+def _sat64(x):
+    """A non-negative size, band or limit as a uint64 argument: what does not fit saturates."""
+    return min(int(x), 0xffffffffffffffff)
+
+
+def _ignore(ignorechars):
+    if isinstance(ignorechars, str):
+        ignorechars = ignorechars.encode()
+    ig = np.frombuffer(bytes(ignorechars or b"") + b"\0", dtype=np.uint8).copy()
+    return ig, len(ig) - 1
+
 
 # name -> (restype, argtypes); mirrors include/fbg_hip.h one to one
 SIGNATURES = {

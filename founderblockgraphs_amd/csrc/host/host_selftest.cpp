@@ -38,12 +38,18 @@
 // reads lines "max_ext f0 n dp_literal dp_wave dp_safe_window dp_tile" from stdin and prints the ladder of sweeps dp_plan.h plans
 // for each, one line of rungs per input line: B<Rt> a byte-matrix rung (T1: its k_dp_tile form), W<WS> a wide rung, V<R> the wave
 // sweep, L the literal sweep, each followed by ":" and its dp_kind_of -- e.g. "B4:1 W1024:3 W2048:4 ... V16:2 L:0".
+//     fbg_host_selftest locate-options
+// checks fbg_locate's command line (locate_options.cpp) against what the tool has always answered: every numeric flag absent,
+// bare, with a number and with what is no number, --pairs=MIN,MAX, both spellings of --graph, --help, an unknown argument, and
+// every prerequisite rule with its message, two of them broken at once included.  Prints "locate_options ok CASES" or the first
+// command line that is answered differently.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 #include "fasta.hpp"
 #include "xgfa.hpp"
+#include "locate_options.hpp"
 #include <algorithm>
 #include <cstring>
 #include "../tie_extent.h"
@@ -395,8 +401,146 @@ static int dp_plan_selftest()
     return 0;
 }
 
+struct LocateParse { bool ok; LocateOptions o; std::string error; };
+
+static LocateParse locate_parse(std::vector<std::string> args)
+{
+    args.insert(args.begin(), "fbg_locate");
+    std::vector<char *> argv;
+    for (std::string &a : args) argv.push_back(&a[0]);
+    LocateParse p;
+    p.ok = parse_locate_options((int)argv.size(), argv.data(), p.o, p.error);
+    return p;
+}
+
+static int locate_options_selftest()
+{
+    typedef std::vector<std::string> Args;
+    unsigned long long cases = 0;
+    auto differs = [&](const Args &args, const char *what) {
+        std::printf("locate_options: %s:", what);
+        for (const std::string &a : args) std::printf(" %s", a.c_str());
+        std::printf("\n");
+        return 1;
+    };
+    // `args` after --graph=g must be refused with exactly `message`
+    auto refused = [&](Args args, const std::string &message) {
+        args.insert(args.begin(), "--graph=g");
+        const LocateParse p = locate_parse(args);
+        cases++;
+        return !p.ok && p.error == message;
+    };
+    // ---- the numeric flags: absent, bare, =0, =7, and what is no number ---------------------------------------------------------
+    const struct { const char *name, *noun; bool LocateOptions::*on; uint64_t LocateOptions::*n; uint64_t preset; bool zero; } numeric[] = {
+        {"--occurrences", "a count", &LocateOptions::occurrences, &LocateOptions::max_places, 64, true},
+        {"--seeds", "a positive count", &LocateOptions::seeds, &LocateOptions::min_seed, 1, false},
+        {"--chain", "a band", &LocateOptions::chain, &LocateOptions::band, UINT64_MAX, true},
+        {"--align", "a pad", &LocateOptions::align, &LocateOptions::pad, 16, true},
+        {"--graph-align", "a pad", &LocateOptions::graph_align, &LocateOptions::graph_pad, 16, true},
+        {"--mapq", "a margin", &LocateOptions::mapq, &LocateOptions::margin, 0, true},
+        {"--pair-align", "a number of edits", &LocateOptions::pair_align, &LocateOptions::max_edits, 0xffffffffu, true},
+    };
+    // every prerequisite at once, so that a flag that parses is accepted
+    const Args all = {"--graph=g", "--msa=m", "--seeds", "--occurrences", "--chain", "--strands", "--rows", "--pairs=2,3"};
+    for (const auto &f : numeric) {
+        const std::string name = f.name;
+        auto with = [&](const std::string &arg) {
+            Args args = all;
+            args.erase(std::remove(args.begin(), args.end(), name), args.end());
+            if (!arg.empty()) args.push_back(arg);
+            cases++;
+            return locate_parse(args);
+        };
+        LocateParse p = with("");
+        if (p.o.*f.on || p.o.*f.n != f.preset) return differs({name}, "absent");
+        p = with(name);
+        if (!p.ok || !(p.o.*f.on) || p.o.*f.n != f.preset) return differs({name}, "bare");
+        p = with(name + "=7");
+        if (!p.ok || !(p.o.*f.on) || p.o.*f.n != 7) return differs({name + "=7"}, "a number");
+        p = with(name + "=0");
+        if (f.zero ? !(p.o.*f.on) || p.o.*f.n != 0 : p.ok) return differs({name + "=0"}, "zero");
+        if (!f.zero && p.error != name + " takes " + f.noun + ", not '0'") return differs({name + "=0"}, "the message");
+        for (const char *v : {"", "x", "-1", "123456789012345678901", "18446744073709551616", "+3", "3 ", "0x10"})
+            if (!refused({name + "=" + v}, name + " takes " + f.noun + ", not '" + v + "'")) return differs({name + "=" + v}, "no number");
+    }
+    if (!refused({"--seeds=0"}, "--seeds takes a positive count, not '0'")) return differs({"--seeds=0"}, "zero");
+    if (!refused({"--pair-align=4294967296"}, "--pair-align takes a number of edits, not '4294967296'")) return differs({"--pair-align=4294967296"}, "33 bits");
+    {
+        Args args = all;
+        args.push_back("--pair-align=4294967295");
+        const LocateParse p = locate_parse(args);
+        cases++;
+        if (!p.ok || !p.o.pair_align || p.o.max_edits != 0xffffffffu) return differs(args, "32 bits");
+    }
+    // ---- --pairs=MIN,MAX --------------------------------------------------------------------------------------------------------
+    {
+        const LocateParse p = locate_parse(all);
+        cases++;
+        if (!p.ok || !p.o.pairs || p.o.min_insert != 2 || p.o.max_insert != 3) return differs(all, "--pairs");
+    }
+    for (const char *v : {"3,2", "3", ",3", "2,", "", "x", "1,2,3", "-1,4", "1,123456789012345678901"})
+        if (!refused({std::string("--pairs=") + v}, std::string("--pairs takes MIN,MAX with MIN <= MAX, not '") + v + "'"))
+            return differs({std::string("--pairs=") + v}, "no pair");
+    if (!refused({"--pairs"}, "unknown argument --pairs")) return differs({"--pairs"}, "bare");
+    // ---- --graph in both spellings, --help, what is unknown ---------------------------------------------------------------------
+    for (const Args &args : {Args{"--graph=efg.xgfa"}, Args{"--graph", "efg.xgfa"}}) {
+        const LocateParse p = locate_parse(args);
+        cases++;
+        if (!p.ok || !p.o.have_graph || p.o.graph != "efg.xgfa" || p.o.help) return differs(args, "--graph");
+    }
+    for (const Args &args : {Args{"--help", "--bogus"}, Args{"-h"}}) {
+        const LocateParse p = locate_parse(args);
+        cases++;
+        if (!p.ok || !p.o.help) return differs(args, "--help");
+    }
+    if (!refused({"--bogus"}, "unknown argument --bogus")) return differs({"--bogus"}, "unknown");
+    if (!refused({"--graph"}, "unknown argument --graph")) return differs({"--graph"}, "no value");
+    if (!refused({"--bogus", "--help"}, "unknown argument --bogus")) return differs({"--bogus", "--help"}, "the first fault");
+    // ---- the prerequisite rules, each with its message; the last two lines break two rules and the earlier one answers ------------
+    const Args chained = {"--msa=m", "--seeds", "--occurrences", "--chain"};
+    auto plus = [](Args a, const Args &b) { a.insert(a.end(), b.begin(), b.end()); return a; };
+    const struct { Args args; const char *message; } rules[] = {
+        {{"--msa="}, "--msa takes a FASTA file"},
+        {{"--chain"}, "--chain needs --seeds, --msa and --occurrences[=M] with M > 0"},
+        {{"--msa=m", "--seeds", "--chain"}, "--chain needs --seeds, --msa and --occurrences[=M] with M > 0"},
+        {{"--msa=m", "--seeds", "--occurrences=0", "--chain"}, "--chain needs --seeds, --msa and --occurrences[=M] with M > 0"},
+        {{"--seeds", "--occurrences", "--chain"}, "--chain needs --seeds, --msa and --occurrences[=M] with M > 0"},
+        {{"--strands"}, "--strands needs --seeds"},
+        {{"--seeds", "--rows"}, "--rows needs --seeds and --msa"},
+        {{"--msa=m", "--rows"}, "--rows needs --seeds and --msa"},
+        {plus(chained, {"--by-row"}), "--by-row needs --chain and --rows"},
+        {{"--msa=m", "--seeds", "--rows", "--by-row"}, "--by-row needs --chain and --rows"},
+        {plus(chained, {"--rows", "--cigar"}), "--cigar needs --align"},
+        {plus(chained, {"--align"}), "--align needs --chain and --rows"},
+        {plus(chained, {"--graph-align=3"}), "--graph-align needs --chain and --rows"},
+        {plus(chained, {"--rows", "--graph-cigar"}), "--graph-cigar needs --graph-align"},
+        {plus(chained, {"--rows", "--graph-align", "--gaf=f"}), "--gaf needs --graph-cigar"},
+        {{"--seeds", "--mapq"}, "--mapq needs --chain"},
+        {plus(chained, {"--pairs=0,9"}), "--pairs needs --chain and --strands"},
+        {{"--seeds", "--strands", "--pairs=0,9"}, "--pairs needs --chain and --strands"},
+        {plus(chained, {"--strands", "--pairs=0,9", "--pair-align"}), "--pair-align needs --pairs and --rows"},
+        {plus(chained, {"--rows", "--pair-align=2"}), "--pair-align needs --pairs and --rows"},
+        {plus(chained, {"--rows", "--graph-align", "--graph-cigar", "--gaf="}), "--gaf takes a file"},
+        {{"--seeds", "--complement=AT"}, "--complement needs --strands"},
+        {{"--seeds", "--strands", "--complement=ATC"}, "--complement takes pairs of characters"},
+        {{"--seeds", "--strands", "--complement="}, "--complement takes pairs of characters"},
+        {{"--cigar", "--graph-cigar"}, "--cigar needs --align"},
+        {{"--mapq", "--pair-align", "--strands"}, "--strands needs --seeds"},
+    };
+    for (const auto &r : rules)
+        if (!refused(r.args, r.message)) return differs(r.args, r.message);
+    for (const Args &args : {Args{}, Args{"--graph="}, Args{"--seeds", "--strands"}}) {
+        const LocateParse p = locate_parse(args);
+        cases++;
+        if (p.ok || p.error != "--graph is required") return differs(args, "--graph is required");
+    }
+    std::printf("locate_options ok %llu\n", cases);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && std::string(argv[1]) == "locate-options") return locate_options_selftest();
     if (argc == 2 && std::string(argv[1]) == "dp_plan") return dp_plan_selftest();
     if (argc == 4 && (std::string(argv[1]) == "twin-hash" || std::string(argv[1]) == "twin-slots"))
         return twin_hash_selftest(argv[2], std::atoi(argv[3]), std::string(argv[1]) == "twin-slots");

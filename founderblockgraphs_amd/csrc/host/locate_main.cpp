@@ -103,10 +103,7 @@
 //   W <tab> which <tab> score <tab> lo <tab> hi    the candidate 0 .. 3, the chain's score plus the aligned pattern's length less
 // its edits, the pair's extent on the row, or `W <tab> *`.  Without --pair-align no byte of stdout changes.
 #include <algorithm>
-#include <cerrno>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <string>
@@ -114,71 +111,18 @@
 #include "../../../include/fbg_hip.h"
 #include "xgfa_read.hpp"
 #include "fasta.hpp"
+#include "locate_options.hpp"
 
-static int usage(const char *msg)
+static int fail(const std::string &msg)
 {
-    std::cerr << "fbg_locate: " << msg << "\n"
-              << "usage: fbg_locate --graph=efg.xgfa [--patterns=FILE] [--error-on-not-found] [--occurrences[=M]] [--seeds[=L]]\n"
-              << "                  [--msa=msa.fasta] [--chain[=BAND]] [--strands] [--complement=FROMTO] [--rows]\n"
-              << "                  [--by-row] [--align[=PAD]] [--cigar] [--graph-align[=PAD]] [--graph-cigar] [--gaf=FILE]\n"
-              << "                  [--mapq[=MARGIN]] [--pairs=MIN,MAX] [--pair-align[=MAX_EDITS]]\n"
-              << "  --occurrences[=M]  after every found pattern, the places where its matches end (E lines) and begin\n"
-              << "                     (B lines): source S id, destination S id, offset into label(src) + label(dst);\n"
-              << "                     at most M of each per pattern (default 64)\n"
-              << "  --seeds[=L]        cut every pattern greedily into the maximal pieces the search accepts and print, per\n"
-              << "                     piece of L symbols or more (default 1), an S line: q_start, length, count, restarts;\n"
-              << "                     with --occurrences the E / B lines of every piece follow its S line\n"
-              << "  --msa=msa.fasta    the MSA the graph was cut from: the index is built from it and the graph's M and X\n"
-              << "                     lines, and every E / B line ends with the MSA row and column (from 0) of that symbol\n"
-              << "                     in the representative row of its node (* for an offset outside the edge)\n"
-              << "  --chain[=BAND]     needs --seeds, --msa and --occurrences[=M] with M > 0: after a pattern's S / E / B lines a\n"
-              << "                     C line (score, anchors) and per anchor of its best co-linear chain of start places an A\n"
-              << "                     line: q_start, length, MSA row, MSA column; BAND bounds the surplus of columns over\n"
-              << "                     pattern symbols between neighbours (default: unbounded)\n"
-              << "  --strands          needs --seeds: every pattern also as its reverse complement; after a pattern's block a\n"
-              << "                     line `- K` and the K seeds of the reverse complement in the same format; with --chain a\n"
-              << "                     closing T line: + or - for the strand of the better chain (* if it is empty), its score\n"
-              << "  --complement=FROMTO  pairs of characters for --strands, e.g. ATTACGGC (the default, and the same in lower\n"
-              << "                     case); every byte not named maps to itself\n"
-              << "  --rows             needs --seeds and --msa: every B line of a seed and every C line ends with the number\n"
-              << "                     of MSA rows that carry the seed from that place on (the C line: every anchor of the\n"
-              << "                     chain) and the smallest such row, from 0 (* if no row does: only a recombinant path\n"
-              << "                     of the graph spells it); no other line changes\n"
-              << "  --by-row           needs --chain and --rows: chain every pattern along the one MSA row whose supported\n"
-              << "                     start places chain best (the smallest among equals); every C line ends with that row\n"
-              << "                     and the number of rows that reach its score (* and 0 if no row supports a place)\n"
-              << "  --align[=PAD]      needs --chain and --rows: after the A lines of a chain a G line: the smallest row that\n"
-              << "                     carries the chain, the fewest edits between the pattern and a stretch of that row's\n"
-              << "                     gap-stripped text within PAD symbols (default 16) of the chain, and that stretch's start\n"
-              << "                     and end in the row's text, from 0 (G and * if there is no alignment)\n"
-              << "  --cigar            needs --align: a G line with numbers ends with the alignment path of the pattern against\n"
-              << "                     that stretch, runs of = X I D in pattern order (25=1X24=); no other line changes\n"
-              << "  --graph-align[=PAD]  needs --chain and --rows: after a chain's lines an H line: the fewest edits between the\n"
-              << "                     pattern and a stretch of a path of the graph through the blocks around the chain, PAD\n"
-              << "                     symbols (default 16) beyond its anchors, the node and offset at which that stretch\n"
-              << "                     starts and ends, and the path as >u>v>w (H and * if there is no alignment)\n"
-              << "  --graph-cigar      needs --graph-align: an H line with numbers ends with the alignment path of the pattern\n"
-              << "                     against that stretch, runs of = X I D in pattern and path order; no other line changes\n"
-              << "  --gaf=FILE         needs --graph-cigar: one GAF record per H line with numbers goes to FILE (read<k>, the\n"
-              << "                     path as >id>id with its coordinates, matches, alignment columns, 255, NM:i: and cg:Z:)\n"
-              << "  --mapq[=MARGIN]    needs --chain: after a chain's C / A lines a Q line: mapping quality 0 .. 60, the score of\n"
-              << "                     the best chain outside the chain's MSA columns widened by MARGIN (default 0), and that\n"
-              << "                     chain's columns (* without one); chains in the same columns are the same locus.  With\n"
-              << "                     --strands the other strand competes too and the T line ends with the chosen strand's\n"
-              << "                     value; with --gaf column 12 is the value instead of 255.  A pattern matched in one\n"
-              << "                     piece has no seed at a shorter copy elsewhere and gets second 0\n"
-              << "  --pairs=MIN,MAX    needs --chain and --strands and an even number of patterns: patterns 2p and 2p + 1 are\n"
-              << "                     mates on opposite strands, MIN .. MAX MSA columns from the forward mate's first to the\n"
-              << "                     reverse mate's last; a mate is chained again inside the window of the other's chain, the\n"
-              << "                     best valid combination replaces the pair's chains (every line then describes those), and\n"
-              << "                     after the second pattern's T line a Z line: candidate, pair score, first and last column\n"
-              << "                     (Z and * without a valid combination)\n"
-              << "  --pair-align[=MAX_EDITS]  needs --pairs and --rows: a strand without a chain is aligned inside the window of\n"
-              << "                     MIN .. MAX symbols that the other mate's chain opens on the smallest row carrying it; after\n"
-              << "                     a strand's lines a Y line: row, edits, start and end in the row's text, the pair's extent\n"
-              << "                     in symbols (* with more than MAX_EDITS edits or below MIN; Y and * if nothing was aligned),\n"
-              << "                     and after a pair's Z line a W line: candidate, score, first and last position on the row\n"
-              << "                     (W and * without one)\n";
+    std::cerr << "fbg_locate: " << msg << "\n";
+    return EXIT_FAILURE;
+}
+
+static int usage(const std::string &msg)
+{
+    fail(msg);
+    std::cerr << locate_usage();
     return EXIT_FAILURE;
 }
 
@@ -259,502 +203,542 @@ static void print_runs(std::ostream &os, const std::vector<uint32_t> &ops, uint6
     }
 }
 
-int main(int argc, char **argv)
+// ---- what is searched, and what the stages give -------------------------------------------------------------------------
+
+struct Reads {
+    std::string data;                               // the patterns back to back
+    std::vector<uint64_t> off{0};                   // [np + 1]
+    uint64_t np = 0, nv = 0;                        // virtual reads: the patterns, then (--strands) their reverse complements
+    const uint8_t *bytes() const { return (const uint8_t *)data.data(); }
+};
+
+struct Located { std::vector<uint64_t> count, pos; };
+struct Places {                                     // the E / B lists, of the patterns or of the seeds
+    std::vector<uint64_t> end_off, start_off, end_total, start_total;
+    std::vector<uint32_t> restarts, at[6];          // end src / dst / offset, start src / dst / offset
+    std::vector<uint32_t> coords[4];                // --msa: end row / column, start row / column
+    std::vector<uint32_t> rows[2];                  // --rows: per start its supporting rows and the first of them
+};
+struct Seeds { std::vector<uint64_t> off, count; std::vector<uint32_t> q_start, length; };
+struct Chains {
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> score, anchor_place, anchor_seed;
+    std::vector<uint32_t> chosen[2];                // --by-row: the chosen row and the rows that reach its score
+    std::vector<uint32_t> rows[2];                  // --rows: supporting rows and the first of them
+    std::vector<uint8_t> strand;                    // --strands, per pattern
+    std::vector<uint32_t> best_score;
+};
+struct Pairs { std::vector<uint8_t> which; std::vector<uint32_t> out[3]; };    // the candidate, its score and columns per pair
+struct Mates {                                      // --pair-align
+    std::vector<uint32_t> read[5];                  // row, edits, t_start, t_end, insert
+    std::vector<uint8_t> which;
+    std::vector<uint32_t> out[3];                   // score, lo, hi
+};
+struct Mapq { std::vector<uint64_t> second_off; std::vector<uint32_t> second[3]; std::vector<uint8_t> quality; };
+struct Runs { std::vector<uint64_t> off; std::vector<uint32_t> ops; };         // the CIGAR runs of every virtual read
+struct RowAlign { std::vector<uint32_t> at[4]; Runs cigar; };                  // row, edits, t_start, t_end
+struct GraphAlign {
+    std::vector<uint32_t> at[5], path_nodes;        // edits, start node and offset, end node and offset
+    std::vector<uint64_t> path_off;
+    Runs cigar;
+};
+struct Results { Located located; Places places; Seeds seeds; Chains chains; Pairs pairs; Mates mates; Mapq mapq; RowAlign row; GraphAlign graph; };
+
+// the library's contexts; released before printing starts
+struct Engine {
+    fbg_ctx *ctx = nullptr;
+    fbg_pindex *ix = nullptr;
+    ~Engine() { fbg_pindex_destroy(ix); fbg_ctx_destroy(ctx); }
+};
+
+// v as n + 1 zeros, so that data() is never null
+template <class T> static T *sized(std::vector<T> &v, uint64_t n)
 {
-    std::string graph, patterns, msa_path, complement, gaf_path;
-    bool graph_cigar = false, have_gaf = false, want_mapq = false, want_pairs = false, pair_align = false;
-    uint32_t max_edits = 0xffffffffu;
-    uint64_t min_insert = 0, max_insert = 0;
-    uint64_t margin = 0;
-    bool have_msa = false, have_complement = false, strands = false, rows = false, align = false, cigar = false, by_row = false, graph_align = false;
-    uint64_t graph_pad = 16;
-    uint64_t pad = 16;
-    bool have_graph = false, have_patterns = false, error_on_not_found = false, occurrences = false, seeds = false, chain = false;
-    uint64_t max_places = 64, min_seed = 1, band = UINT64_MAX;
-    for (int i = 1; i < argc; i++) {
-        const std::string a = argv[i];
-        auto value = [&](const char *name, std::string &out, bool &have) {
-            const std::string pre = std::string(name) + "=";
-            if (a.compare(0, pre.size(), pre) == 0) { out = a.substr(pre.size()); have = true; return true; }
-            if (a == name && i + 1 < argc) { out = argv[++i]; have = true; return true; }
-            return false;
-        };
-        if (value("--graph", graph, have_graph) || value("--patterns", patterns, have_patterns) ||
-            value("--msa", msa_path, have_msa) || value("--complement", complement, have_complement) ||
-            value("--gaf", gaf_path, have_gaf)) continue;
-        if (a == "--strands") { strands = true; continue; }
-        if (a == "--rows") { rows = true; continue; }
-        if (a == "--by-row") { by_row = true; continue; }
-        if (a == "--error-on-not-found") { error_on_not_found = true; continue; }
-        if (a == "--occurrences") { occurrences = true; continue; }
-        if (a.compare(0, 14, "--occurrences=") == 0) {
-            const std::string v = a.substr(14);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
-                return usage(("--occurrences takes a count, not '" + v + "'").c_str());
-            occurrences = true;
-            max_places = m;
-            continue;
-        }
-        if (a == "--seeds") { seeds = true; continue; }
-        if (a.compare(0, 8, "--seeds=") == 0) {
-            const std::string v = a.substr(8);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end || m == 0)
-                return usage(("--seeds takes a positive count, not '" + v + "'").c_str());
-            seeds = true;
-            min_seed = m;
-            continue;
-        }
-        if (a == "--chain") { chain = true; continue; }
-        if (a.compare(0, 8, "--chain=") == 0) {
-            const std::string v = a.substr(8);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
-                return usage(("--chain takes a band, not '" + v + "'").c_str());
-            chain = true;
-            band = m;
-            continue;
-        }
-        if (a == "--cigar") { cigar = true; continue; }
-        if (a == "--align") { align = true; continue; }
-        if (a.compare(0, 8, "--align=") == 0) {
-            const std::string v = a.substr(8);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
-                return usage(("--align takes a pad, not '" + v + "'").c_str());
-            align = true;
-            pad = m;
-            continue;
-        }
-        if (a == "--graph-cigar") { graph_cigar = true; continue; }
-        if (a == "--graph-align") { graph_align = true; continue; }
-        if (a.compare(0, 14, "--graph-align=") == 0) {
-            const std::string v = a.substr(14);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
-                return usage(("--graph-align takes a pad, not '" + v + "'").c_str());
-            graph_align = true;
-            graph_pad = m;
-            continue;
-        }
-        if (a == "--mapq") { want_mapq = true; continue; }
-        if (a.compare(0, 7, "--mapq=") == 0) {
-            const std::string v = a.substr(7);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end)
-                return usage(("--mapq takes a margin, not '" + v + "'").c_str());
-            want_mapq = true;
-            margin = m;
-            continue;
-        }
-        if (a.compare(0, 8, "--pairs=") == 0) {
-            const std::string v = a.substr(8);
-            const size_t comma = v.find(',');
-            const std::string lo = v.substr(0, comma), hi = comma == std::string::npos ? "" : v.substr(comma + 1);
-            errno = 0;
-            const unsigned long long x = std::strtoull(lo.c_str(), nullptr, 10), y = std::strtoull(hi.c_str(), nullptr, 10);
-            if (lo.empty() || hi.empty() || lo.find_first_not_of("0123456789") != std::string::npos ||
-                hi.find_first_not_of("0123456789") != std::string::npos || errno || x > y)
-                return usage(("--pairs takes MIN,MAX with MIN <= MAX, not '" + v + "'").c_str());
-            want_pairs = true;
-            min_insert = x;
-            max_insert = y;
-            continue;
-        }
-        if (a == "--pair-align") { pair_align = true; continue; }
-        if (a.compare(0, 13, "--pair-align=") == 0) {
-            const std::string v = a.substr(13);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long m = std::strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno || *end || m > 0xffffffffull)
-                return usage(("--pair-align takes a number of edits, not '" + v + "'").c_str());
-            pair_align = true;
-            max_edits = (uint32_t)m;
-            continue;
-        }
-        if (a == "--help" || a == "-h") { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
-        return usage(("unknown argument " + a).c_str());
-    }
-    if (!have_graph || graph.empty()) return usage("--graph is required");
-    if (have_msa && msa_path.empty()) return usage("--msa takes a FASTA file");
-    if (chain && !(seeds && have_msa && occurrences && max_places > 0))
-        return usage("--chain needs --seeds, --msa and --occurrences[=M] with M > 0");
-    if (strands && !seeds) return usage("--strands needs --seeds");
-    if (rows && !(seeds && have_msa)) return usage("--rows needs --seeds and --msa");
-    if (by_row && !(chain && rows)) return usage("--by-row needs --chain and --rows");
-    if (cigar && !align) return usage("--cigar needs --align");
-    if (align && !(chain && rows)) return usage("--align needs --chain and --rows");
-    if (graph_align && !(chain && rows)) return usage("--graph-align needs --chain and --rows");
-    if (graph_cigar && !graph_align) return usage("--graph-cigar needs --graph-align");
-    if (have_gaf && !graph_cigar) return usage("--gaf needs --graph-cigar");
-    if (want_mapq && !chain) return usage("--mapq needs --chain");
-    if (want_pairs && !(chain && strands)) return usage("--pairs needs --chain and --strands");
-    if (pair_align && !(want_pairs && rows)) return usage("--pair-align needs --pairs and --rows");
-    if (have_gaf && gaf_path.empty()) return usage("--gaf takes a file");
-    if (have_complement && !strands) return usage("--complement needs --strands");
-    if (have_complement && (complement.empty() || complement.size() % 2)) return usage("--complement takes pairs of characters");
+    v.assign(n + 1, 0);
+    return v.data();
+}
 
-    std::ofstream gaf;
-    if (have_gaf) {
-        gaf.open(gaf_path, std::ios::binary | std::ios::trunc);
-        if (!gaf) { std::cerr << "fbg_locate: cannot write " << gaf_path << "\n"; return EXIT_FAILURE; }
-    }
-    XgfaGraph g;
-    std::string error;
-    if (!read_xgfa_graph(graph, g, error)) { std::cerr << "fbg_locate: " << error << "\n"; return EXIT_FAILURE; }
+// ---- the stages: each sizes its arrays and makes its calls ------------------------------------------------------------------
 
-    Msa msa;
-    std::vector<uint64_t> bounds;                   // inclusive block ends, the last one n (fbg_minmax_dp's convention)
-    if (have_msa) {
-        uint64_t gm = 0, gn = 0;
-        std::vector<uint64_t> xs;
-        if (!read_segmentation(graph, gm, gn, xs, error)) { std::cerr << "fbg_locate: " << error << "\n"; return EXIT_FAILURE; }
-        if (!read_msa(msa_path, 1, true, false, msa)) { std::cerr << "fbg_locate: cannot open " << msa_path << "\n"; return EXIT_FAILURE; }
-        if (msa.m != gm || msa.n != gn) {
-            std::cerr << "fbg_locate: " << msa_path << " does not fit " << graph << ": the MSA has " << msa.m << " rows and " << msa.n
-                      << " columns, the M line says " << gm << " and " << gn << "\n";
-            return EXIT_FAILURE;
-        }
-        for (size_t i = 1; i < xs.size(); i++) {
-            if (xs[i] < 2) { std::cerr << "fbg_locate: " << graph << ": malformed X line\n"; return EXIT_FAILURE; }
-            bounds.push_back(xs[i] - 2);
-        }
-        bounds.push_back(gn);
-    }
+typedef int Stage(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x);
 
+static int stage_locate(fbg_pindex *ix, const LocateOptions &, const Reads &r, Results &x)
+{
+    return fbg_pindex_locate(ix, r.bytes(), r.off.data(), r.np, sized(x.located.count, r.np), sized(x.located.pos, r.np));
+}
+
+static int stage_occurrences(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    Places &p = x.places;
+    return fbg_pindex_occurrences(ix, r.bytes(), r.off.data(), r.np, o.max_places, sized(x.located.count, r.np), sized(x.located.pos, r.np),
+                                  sized(p.restarts, r.np), sized(p.end_off, r.np), sized(p.start_off, r.np), sized(p.end_total, r.np),
+                                  sized(p.start_total, r.np), nullptr);
+}
+
+static int stage_seeds(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    const uint64_t max_places = o.occurrences ? o.max_places : 0;
+    uint64_t *off = sized(x.seeds.off, r.nv);
+    if (!o.strands) return fbg_pindex_seeds(ix, r.bytes(), r.off.data(), r.np, o.min_seed, max_places, off, nullptr);
+    uint8_t table[256];
+    for (int c = 0; c < 256; c++) table[c] = (uint8_t)c;
+    for (size_t i = 0; i + 1 < o.complement.size(); i += 2) table[(uint8_t)o.complement[i]] = (uint8_t)o.complement[i + 1];
+    return fbg_pindex_seeds_strands(ix, r.bytes(), r.off.data(), r.np, o.have_complement ? table : nullptr, o.min_seed, max_places, off,
+                                    nullptr);
+}
+
+static int stage_seeds_fetch(fbg_pindex *ix, const LocateOptions &, const Reads &r, Results &x)
+{
+    Seeds &s = x.seeds;
+    Places &p = x.places;
+    const uint64_t ns = s.off[r.nv];
+    return fbg_pindex_seeds_fetch(ix, sized(s.q_start, ns), sized(s.length, ns), sized(s.count, ns), sized(p.restarts, ns),
+                                  sized(p.end_total, ns), sized(p.start_total, ns), sized(p.end_off, ns), sized(p.start_off, ns), nullptr);
+}
+
+// the places behind the offsets of the search that ran
+static int stage_places(fbg_pindex *ix, const LocateOptions &o, const Reads &, Results &x)
+{
+    Places &p = x.places;
+    uint32_t *a[6];
+    for (int k = 0; k < 6; k++) a[k] = sized(p.at[k], k < 3 ? p.end_off.back() : p.start_off.back());
+    return (o.seeds ? fbg_pindex_seeds_places : fbg_pindex_occurrences_fetch)(ix, a[0], a[1], a[2], a[3], a[4], a[5], nullptr);
+}
+
+// and their MSA cells
+static int stage_coords(fbg_pindex *ix, const LocateOptions &o, const Reads &, Results &x)
+{
+    Places &p = x.places;
+    uint32_t *a[4];
+    for (int k = 0; k < 4; k++) a[k] = sized(p.coords[k], k < 2 ? p.end_off.back() : p.start_off.back());
+    return (o.seeds ? fbg_pindex_seeds_msa : fbg_pindex_occurrences_msa)(ix, a[0], a[1], a[2], a[3], nullptr);
+}
+
+static int stage_chains(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    Chains &c = x.chains;
+    uint64_t *off = sized(c.off, r.nv);
+    uint32_t *score = sized(c.score, r.nv);
+    if (!o.by_row) return fbg_pindex_chains(ix, o.band, 0, off, score, nullptr);
+    return fbg_pindex_chains_by_row(ix, o.band, 0, off, score, sized(c.chosen[0], r.nv), sized(c.chosen[1], r.nv), nullptr);
+}
+
+// adopts: the chains' offsets and scores become those of the pair-consistent chains
+static int stage_pairs(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    Pairs &p = x.pairs;
+    const uint64_t pairs = r.np / 2;
+    std::vector<uint64_t> rescue_off;
+    return fbg_pindex_chains_pairs(ix, o.min_insert, o.max_insert, sized(p.which, pairs), sized(p.out[0], pairs), sized(p.out[1], pairs),
+                                   sized(p.out[2], pairs), sized(rescue_off, r.nv), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   x.chains.off.data(), x.chains.score.data(), nullptr, nullptr);
+}
+
+// on the adopted chains; writes nothing that a later stage reads
+static int stage_pair_align(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    Mates &m = x.mates;
+    const uint64_t pairs = r.np / 2;
+    return fbg_pindex_pairs_align(ix, o.min_insert, o.max_insert, (uint32_t)o.max_edits, 0, nullptr, sized(m.read[0], r.nv),
+                                  sized(m.read[1], r.nv), sized(m.read[2], r.nv), sized(m.read[3], r.nv), sized(m.read[4], r.nv),
+                                  sized(m.which, pairs), sized(m.out[0], pairs), sized(m.out[1], pairs), sized(m.out[2], pairs), nullptr,
+                                  nullptr);
+}
+
+static int stage_chains_fetch(fbg_pindex *ix, const LocateOptions &, const Reads &r, Results &x)
+{
+    Chains &c = x.chains;
+    return fbg_pindex_chains_fetch(ix, sized(c.anchor_place, c.off[r.nv]), sized(c.anchor_seed, c.off[r.nv]), nullptr);
+}
+
+static int stage_chain_strands(fbg_pindex *ix, const LocateOptions &, const Reads &r, Results &x)
+{
+    return fbg_pindex_chain_strands(ix, sized(x.chains.strand, r.np), sized(x.chains.best_score, r.np), nullptr, nullptr, nullptr, nullptr);
+}
+
+static int stage_mapq(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    Mapq &q = x.mapq;
+    const int rc = fbg_pindex_chains_mapq(ix, o.margin, sized(q.second_off, r.nv), sized(q.second[0], r.nv), sized(q.second[1], r.nv),
+                                          sized(q.second[2], r.nv), sized(q.quality, r.nv), nullptr);
+    return rc == FBG_OK && o.strands ? fbg_pindex_mapq_strands(ix, q.quality.data(), nullptr) : rc;
+}
+
+static int stage_seeds_rows(fbg_pindex *ix, const LocateOptions &, const Reads &, Results &x)
+{
+    Places &p = x.places;
+    return fbg_pindex_seeds_rows(ix, sized(p.rows[0], p.start_off.back()), sized(p.rows[1], p.start_off.back()), nullptr);
+}
+
+static int stage_chains_rows(fbg_pindex *ix, const LocateOptions &, const Reads &r, Results &x)
+{
+    return fbg_pindex_chains_rows(ix, sized(x.chains.rows[0], r.nv), sized(x.chains.rows[1], r.nv), nullptr, nullptr);
+}
+
+static int stage_align(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    std::vector<uint32_t> *a = x.row.at;
+    return fbg_pindex_chains_align(ix, o.pad, 0, sized(a[0], r.nv), sized(a[1], r.nv), sized(a[2], r.nv), sized(a[3], r.nv), nullptr);
+}
+
+// the runs of an alignment stage (fbg_pindex_chains_cigar, fbg_pindex_chains_graph_cigar, and their _fetch)
+static int fetch_runs(fbg_pindex *ix, uint64_t nv, Runs &runs, decltype(fbg_pindex_chains_cigar) *trace,
+                      decltype(fbg_pindex_chains_cigar_fetch) *fetch)
+{
+    uint64_t total = 0;
+    const int rc = trace(ix, nullptr, &total, nullptr);
+    return rc == FBG_OK ? fetch(ix, sized(runs.off, nv), sized(runs.ops, total)) : rc;
+}
+
+static int stage_cigar(fbg_pindex *ix, const LocateOptions &, const Reads &r, Results &x)
+{
+    return fetch_runs(ix, r.nv, x.row.cigar, fbg_pindex_chains_cigar, fbg_pindex_chains_cigar_fetch);
+}
+
+static int stage_graph_align(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    GraphAlign &g = x.graph;
+    uint64_t total = 0;
+    const int rc = fbg_pindex_chains_align_graph(ix, o.graph_pad, 0, nullptr, sized(g.at[0], r.nv), sized(g.at[1], r.nv), sized(g.at[2], r.nv),
+                                                 sized(g.at[3], r.nv), sized(g.at[4], r.nv), nullptr, &total, nullptr);
+    return rc == FBG_OK ? fbg_pindex_chains_align_graph_fetch(ix, sized(g.path_off, r.nv), sized(g.path_nodes, total)) : rc;
+}
+
+static int stage_graph_cigar(fbg_pindex *ix, const LocateOptions &, const Reads &r, Results &x)
+{
+    return fetch_runs(ix, r.nv, x.graph.cigar, fbg_pindex_chains_graph_cigar, fbg_pindex_chains_graph_cigar_fetch);
+}
+
+// The stages that the options ask for, in their order: a search, its places, then what the other options add to --seeds
+// (each of them needs it).
+static int run_stages(fbg_pindex *ix, const LocateOptions &o, const Reads &r, Results &x)
+{
+    const struct { bool wanted; Stage *run; } stages[] = {
+        {!o.seeds && !o.occurrences, stage_locate},
+        {!o.seeds && o.occurrences, stage_occurrences},
+        {o.seeds, stage_seeds},
+        {o.seeds, stage_seeds_fetch},
+        {o.seeds || o.occurrences, stage_places},
+        {o.have_msa && o.occurrences, stage_coords},
+        {o.chain, stage_chains},
+        {o.pairs, stage_pairs},
+        {o.pair_align, stage_pair_align},
+        {o.chain, stage_chains_fetch},
+        {o.chain && o.strands, stage_chain_strands},
+        {o.mapq, stage_mapq},
+        {o.rows && o.occurrences, stage_seeds_rows},
+        {o.rows && o.chain, stage_chains_rows},
+        {o.align, stage_align},
+        {o.cigar, stage_cigar},
+        {o.graph_align, stage_graph_align},
+        {o.graph_cigar, stage_graph_cigar},
+    };
+    for (const auto &s : stages) {
+        const int rc = s.wanted ? s.run(ix, o, r, x) : FBG_OK;
+        if (rc != FBG_OK) return rc;
+    }
+    return FBG_OK;
+}
+
+// ---- input ------------------------------------------------------------------------------------------------------------------
+
+// the MSA of --msa and the inclusive block ends of the graph's segmentation, the last one n (fbg_minmax_dp's convention)
+static bool read_msa_of_graph(const LocateOptions &o, Msa &msa, std::vector<uint64_t> &bounds, std::string &error)
+{
+    uint64_t gm = 0, gn = 0;
+    std::vector<uint64_t> xs;
+    if (!read_segmentation(o.graph, gm, gn, xs, error)) return false;
+    if (!read_msa(o.msa_path, 1, true, false, msa)) { error = "cannot open " + o.msa_path; return false; }
+    if (msa.m != gm || msa.n != gn) {
+        error = o.msa_path + " does not fit " + o.graph + ": the MSA has " + std::to_string(msa.m) + " rows and " + std::to_string(msa.n) +
+                " columns, the M line says " + std::to_string(gm) + " and " + std::to_string(gn);
+        return false;
+    }
+    for (size_t i = 1; i < xs.size(); i++) {
+        if (xs[i] < 2) { error = o.graph + ": malformed X line"; return false; }
+        bounds.push_back(xs[i] - 2);
+    }
+    bounds.push_back(gn);
+    return true;
+}
+
+static bool read_patterns(const LocateOptions &o, Reads &r, std::string &error)
+{
     std::ifstream pf;
-    if (have_patterns) {
-        pf.open(patterns, std::ios::binary);
-        if (!pf) { std::cerr << "fbg_locate: cannot open " << patterns << "\n"; return EXIT_FAILURE; }
+    if (o.have_patterns) {
+        pf.open(o.patterns, std::ios::binary);
+        if (!pf) { error = "cannot open " + o.patterns; return false; }
     }
-    std::istream &in = have_patterns ? static_cast<std::istream &>(pf) : std::cin;
+    std::istream &in = o.have_patterns ? static_cast<std::istream &>(pf) : std::cin;
     std::ios_base::sync_with_stdio(false);
-    std::string data;
-    std::vector<uint64_t> off(1, 0);
     while (true) {
         std::string p;
         in >> p;
         if (in.eof()) break;           // also drops a last token that ends the input (locate_patterns.cpp:47-53)
-        if (!in) { std::cerr << "fbg_locate: cannot read the patterns\n"; return EXIT_FAILURE; }
-        data += p;
-        off.push_back(data.size());
+        if (!in) { error = "cannot read the patterns"; return false; }
+        r.data += p;
+        r.off.push_back(r.data.size());
     }
-    const uint64_t np = off.size() - 1;
-    const uint64_t nv = strands ? 2 * np : np;      // virtual reads: the patterns, then their reverse complements
-    if (want_pairs && np % 2) return usage("--pairs takes an even number of patterns, mates interleaved");
+    r.np = r.off.size() - 1;
+    r.nv = o.strands ? 2 * r.np : r.np;
+    return true;
+}
 
-    fbg_ctx *ctx = nullptr;
-    int rc = fbg_ctx_create(0, &ctx);
-    if (rc != FBG_OK) { std::cerr << "fbg_locate: " << fbg_last_error(nullptr) << "\n"; return EXIT_FAILURE; }
+// The index of the graph or, with --msa, of the MSA's segmentation, which must be the graph that was read: `misfit` says
+// where it is not.
+static int build_index(Engine &e, const LocateOptions &o, const XgfaGraph &g, const Msa &msa, const std::vector<uint64_t> &bounds,
+                       std::string &misfit)
+{
     const uint64_t nodes = g.label_off.size() - 1;
-    fbg_pindex *ix = nullptr;
-    if (have_msa) {
-        // the index of the MSA's segmentation, which must be the graph that was read
-        std::string why;
-        if (bounds.size() > 1 && !std::is_sorted(bounds.begin(), bounds.end() - 1)) why = "the X line does not increase";
-        rc = fbg_msa_load_host(ctx, msa.cells.data(), msa.m, msa.n);
-        if (rc == FBG_OK && why.empty())
-            rc = rows ? fbg_pindex_build_segmentation_rows(ctx, bounds.data(), bounds.size(), &ix)
-                      : fbg_pindex_build_segmentation(ctx, bounds.data(), bounds.size(), &ix);
-        if (rc == FBG_OK && why.empty()) {
-            std::vector<uint32_t> len(nodes + 1);
-            if (fbg_pindex_node_count(ix) != nodes)
-                why = "its segmentation has " + std::to_string(fbg_pindex_node_count(ix)) + " nodes, the graph " + std::to_string(nodes);
-            else if ((rc = fbg_pindex_node_info(ix, len.data(), nullptr, nullptr)) == FBG_OK)
-                for (uint64_t u = 0; u < nodes && why.empty(); u++)
-                    if (len[u] != g.label_off[u + 1] - g.label_off[u])
-                        why = "node " + std::to_string(g.ids[u]) + " has " + std::to_string(g.label_off[u + 1] - g.label_off[u]) +
-                              " symbols in the graph and " + std::to_string(len[u]) + " in the MSA";
-        }
-        if (!why.empty()) {
-            std::cerr << "fbg_locate: " << msa_path << " does not fit " << graph << ": " << why << "\n";
-            fbg_pindex_destroy(ix);
-            fbg_ctx_destroy(ctx);
-            return EXIT_FAILURE;
-        }
-    } else {
-        rc = fbg_pindex_build(ctx, (const uint8_t *)g.labels.data(), g.label_off.data(), nodes, g.edge_off.data(),
-                              g.edge_dst.data(), &ix);
+    if (!o.have_msa)
+        return fbg_pindex_build(e.ctx, (const uint8_t *)g.labels.data(), g.label_off.data(), nodes, g.edge_off.data(), g.edge_dst.data(), &e.ix);
+    std::string why;
+    if (bounds.size() > 1 && !std::is_sorted(bounds.begin(), bounds.end() - 1)) why = "the X line does not increase";
+    int rc = fbg_msa_load_host(e.ctx, msa.cells.data(), msa.m, msa.n);
+    if (rc == FBG_OK && why.empty())
+        rc = o.rows ? fbg_pindex_build_segmentation_rows(e.ctx, bounds.data(), bounds.size(), &e.ix)
+                    : fbg_pindex_build_segmentation(e.ctx, bounds.data(), bounds.size(), &e.ix);
+    if (rc == FBG_OK && why.empty()) {
+        std::vector<uint32_t> len(nodes + 1);
+        if (fbg_pindex_node_count(e.ix) != nodes)
+            why = "its segmentation has " + std::to_string(fbg_pindex_node_count(e.ix)) + " nodes, the graph " + std::to_string(nodes);
+        else if ((rc = fbg_pindex_node_info(e.ix, len.data(), nullptr, nullptr)) == FBG_OK)
+            for (uint64_t u = 0; u < nodes && why.empty(); u++)
+                if (len[u] != g.label_off[u + 1] - g.label_off[u])
+                    why = "node " + std::to_string(g.ids[u]) + " has " + std::to_string(g.label_off[u + 1] - g.label_off[u]) +
+                          " symbols in the graph and " + std::to_string(len[u]) + " in the MSA";
     }
-    std::vector<uint32_t> coords[4];                // end row / column, start row / column (--msa with --occurrences)
-    const bool want_coords = have_msa && occurrences;
-    std::vector<uint64_t> count(np + 1), pos(np + 1), end_off, start_off, end_total, start_total;
-    std::vector<uint32_t> restarts, places[6];      // end src / dst / offset, start src / dst / offset
-    if (occurrences) {
-        for (std::vector<uint64_t> *v : {&end_off, &start_off, &end_total, &start_total}) v->assign(np + 1, 0);
-        restarts.assign(np + 1, 0);
-    }
-    std::vector<uint64_t> seed_off(nv + 1, 0), seed_count;
-    std::vector<uint32_t> q_start, length;
-    std::vector<uint64_t> chain_off(nv + 1, 0);
-    std::vector<uint32_t> chain_score(nv + 1, 0), anchor_place, anchor_seed, best_score(np + 1, 0);
-    std::vector<uint8_t> strand(np + 1, 0);
-    std::vector<uint32_t> place_rows[2], chain_rows[2];     // --rows: supporting rows and the first of them
-    std::vector<uint32_t> chosen[2];                        // --by-row: the chosen row and the rows that reach its score
-    std::vector<uint32_t> aligned[4];                       // --align: row, edits, t_start, t_end
-    std::vector<uint64_t> cigar_off(nv + 1, 0);             // --cigar: the runs of every virtual read
-    std::vector<uint32_t> cigar_ops;
-    std::vector<uint32_t> on_graph[5];                      // --graph-align: edits, start node and offset, end node and offset
-    std::vector<uint64_t> path_off(nv + 1, 0);
-    std::vector<uint32_t> path_nodes;
-    std::vector<uint64_t> gcigar_off(nv + 1, 0);            // --graph-cigar: the runs of every virtual read
-    std::vector<uint32_t> gcigar_ops;
-    std::vector<uint64_t> second_off(nv + 1, 0);            // --mapq: the second chains' offsets, scores and spans, the qualities
-    std::vector<uint32_t> second[3];
-    std::vector<uint8_t> quality(nv + 1, 0);
-    std::vector<uint8_t> pair_which(np / 2 + 1, 0);        // --pairs: the candidate, its score and columns per pair
-    std::vector<uint32_t> pair_out[3];
-    std::vector<uint32_t> mate[5], mate_out[3];             // --pair-align: row, edits, t_start, t_end, insert; score, lo, hi
-    std::vector<uint8_t> mate_which(np / 2 + 1, 0);
-    if (rc == FBG_OK && seeds) {
-        if (strands) {
-            uint8_t table[256];
-            for (int c = 0; c < 256; c++) table[c] = (uint8_t)c;
-            for (size_t i = 0; i + 1 < complement.size(); i += 2) table[(uint8_t)complement[i]] = (uint8_t)complement[i + 1];
-            rc = fbg_pindex_seeds_strands(ix, (const uint8_t *)data.data(), off.data(), np, have_complement ? table : nullptr,
-                                          min_seed, occurrences ? max_places : 0, seed_off.data(), nullptr);
-        } else {
-            rc = fbg_pindex_seeds(ix, (const uint8_t *)data.data(), off.data(), np, min_seed, occurrences ? max_places : 0,
-                                  seed_off.data(), nullptr);
-        }
-        const uint64_t ns = rc == FBG_OK ? seed_off[nv] : 0;
-        for (std::vector<uint64_t> *v : {&seed_count, &end_off, &start_off, &end_total, &start_total}) v->assign(ns + 1, 0);
-        for (std::vector<uint32_t> *v : {&q_start, &length, &restarts}) v->assign(ns + 1, 0);
-        if (rc == FBG_OK)
-            rc = fbg_pindex_seeds_fetch(ix, q_start.data(), length.data(), seed_count.data(), restarts.data(), end_total.data(),
-                                        start_total.data(), end_off.data(), start_off.data(), nullptr);
-        if (rc == FBG_OK) {
-            for (int k = 0; k < 6; k++) places[k].resize((k < 3 ? end_off[ns] : start_off[ns]) + 1);
-            rc = fbg_pindex_seeds_places(ix, places[0].data(), places[1].data(), places[2].data(), places[3].data(),
-                                         places[4].data(), places[5].data(), nullptr);
-        }
-        if (rc == FBG_OK && want_coords) {
-            for (int k = 0; k < 4; k++) coords[k].resize((k < 2 ? end_off[ns] : start_off[ns]) + 1);
-            rc = fbg_pindex_seeds_msa(ix, coords[0].data(), coords[1].data(), coords[2].data(), coords[3].data(), nullptr);
-        }
-        if (rc == FBG_OK && chain && by_row) {
-            for (int k = 0; k < 2; k++) chosen[k].resize(nv + 1);
-            rc = fbg_pindex_chains_by_row(ix, band, 0, chain_off.data(), chain_score.data(), chosen[0].data(), chosen[1].data(), nullptr);
-        } else if (rc == FBG_OK && chain) rc = fbg_pindex_chains(ix, band, 0, chain_off.data(), chain_score.data(), nullptr);
-        if (rc == FBG_OK && want_pairs) {      // adopt: chain_off and chain_score become those of the pair-consistent chains
-            std::vector<uint64_t> rescue_off(nv + 1, 0);
-            for (int k = 0; k < 3; k++) pair_out[k].resize(np / 2 + 1);
-            rc = fbg_pindex_chains_pairs(ix, min_insert, max_insert, pair_which.data(), pair_out[0].data(), pair_out[1].data(),
-                                         pair_out[2].data(), rescue_off.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                                         chain_off.data(), chain_score.data(), nullptr, nullptr);
-        }
-        if (rc == FBG_OK && pair_align) {      // on the adopted chains; writes nothing that a later stage reads
-            for (int k = 0; k < 5; k++) mate[k].resize(nv + 1);
-            for (int k = 0; k < 3; k++) mate_out[k].resize(np / 2 + 1);
-            rc = fbg_pindex_pairs_align(ix, min_insert, max_insert, max_edits, 0, nullptr, mate[0].data(), mate[1].data(), mate[2].data(),
-                                        mate[3].data(), mate[4].data(), mate_which.data(), mate_out[0].data(), mate_out[1].data(),
-                                        mate_out[2].data(), nullptr, nullptr);
-        }
-        if (rc == FBG_OK && chain) {
-            anchor_place.resize(chain_off[nv] + 1);
-            anchor_seed.resize(chain_off[nv] + 1);
-            rc = fbg_pindex_chains_fetch(ix, anchor_place.data(), anchor_seed.data(), nullptr);
-        }
-        if (rc == FBG_OK && chain && strands)
-            rc = fbg_pindex_chain_strands(ix, strand.data(), best_score.data(), nullptr, nullptr, nullptr, nullptr);
-        if (rc == FBG_OK && want_mapq) {
-            for (int k = 0; k < 3; k++) second[k].resize(nv + 1);
-            rc = fbg_pindex_chains_mapq(ix, margin, second_off.data(), second[0].data(), second[1].data(), second[2].data(),
-                                        quality.data(), nullptr);
-            if (rc == FBG_OK && strands) rc = fbg_pindex_mapq_strands(ix, quality.data(), nullptr);
-        }
-        if (rc == FBG_OK && rows && occurrences) {
-            for (int k = 0; k < 2; k++) place_rows[k].resize(start_off[ns] + 1);
-            rc = fbg_pindex_seeds_rows(ix, place_rows[0].data(), place_rows[1].data(), nullptr);
-        }
-        if (rc == FBG_OK && rows && chain) {
-            for (int k = 0; k < 2; k++) chain_rows[k].resize(nv + 1);
-            rc = fbg_pindex_chains_rows(ix, chain_rows[0].data(), chain_rows[1].data(), nullptr, nullptr);
-        }
-        if (rc == FBG_OK && align) {
-            for (int k = 0; k < 4; k++) aligned[k].resize(nv + 1);
-            rc = fbg_pindex_chains_align(ix, pad, 0, aligned[0].data(), aligned[1].data(), aligned[2].data(), aligned[3].data(), nullptr);
-        }
-        if (rc == FBG_OK && cigar) {
-            uint64_t total = 0;
-            rc = fbg_pindex_chains_cigar(ix, nullptr, &total, nullptr);
-            cigar_ops.resize(total + 1);
-            if (rc == FBG_OK) rc = fbg_pindex_chains_cigar_fetch(ix, cigar_off.data(), cigar_ops.data());
-        }
-        if (rc == FBG_OK && graph_align) {
-            uint64_t total = 0;
-            for (int k = 0; k < 5; k++) on_graph[k].resize(nv + 1);
-            rc = fbg_pindex_chains_align_graph(ix, graph_pad, 0, nullptr, on_graph[0].data(), on_graph[1].data(), on_graph[2].data(),
-                                               on_graph[3].data(), on_graph[4].data(), nullptr, &total, nullptr);
-            path_nodes.resize(total + 1);
-            if (rc == FBG_OK) rc = fbg_pindex_chains_align_graph_fetch(ix, path_off.data(), path_nodes.data());
-        }
-        if (rc == FBG_OK && graph_cigar) {
-            uint64_t total = 0;
-            rc = fbg_pindex_chains_graph_cigar(ix, nullptr, &total, nullptr);
-            gcigar_ops.resize(total + 1);
-            if (rc == FBG_OK) rc = fbg_pindex_chains_graph_cigar_fetch(ix, gcigar_off.data(), gcigar_ops.data());
-        }
-    }
-    if (rc == FBG_OK && !occurrences && !seeds)
-        rc = fbg_pindex_locate(ix, (const uint8_t *)data.data(), off.data(), np, count.data(), pos.data());
-    if (rc == FBG_OK && occurrences && !seeds)
-        rc = fbg_pindex_occurrences(ix, (const uint8_t *)data.data(), off.data(), np, max_places, count.data(), pos.data(),
-                                    restarts.data(), end_off.data(), start_off.data(), end_total.data(), start_total.data(), nullptr);
-    if (rc == FBG_OK && occurrences && !seeds) {
-        for (int k = 0; k < 6; k++) places[k].resize((k < 3 ? end_off[np] : start_off[np]) + 1);
-        rc = fbg_pindex_occurrences_fetch(ix, places[0].data(), places[1].data(), places[2].data(), places[3].data(),
-                                          places[4].data(), places[5].data(), nullptr);
-    }
-    if (rc == FBG_OK && want_coords && !seeds) {
-        for (int k = 0; k < 4; k++) coords[k].resize((k < 2 ? end_off[np] : start_off[np]) + 1);
-        rc = fbg_pindex_occurrences_msa(ix, coords[0].data(), coords[1].data(), coords[2].data(), coords[3].data(), nullptr);
-    }
-    if (rc != FBG_OK) {
-        std::cerr << "fbg_locate: " << fbg_last_error(ctx) << "\n";
-        fbg_pindex_destroy(ix);
-        fbg_ctx_destroy(ctx);
-        return EXIT_FAILURE;
-    }
-    fbg_pindex_destroy(ix);
-    fbg_ctx_destroy(ctx);
+    if (!why.empty()) misfit = o.msa_path + " does not fit " + o.graph + ": " + why;
+    return rc;
+}
 
-    const std::vector<uint64_t> *const o[2] = {&end_off, &start_off}, *const t[2] = {&end_total, &start_total};
-    uint64_t found = 0;
-    if (seeds) {
-        // the S / E / B (/ C / A) lines of virtual read v
-        auto block = [&](uint64_t v) {
-            for (uint64_t j = seed_off[v]; j < seed_off[v + 1]; j++) {
-                std::cout << "S\t" << q_start[j] << '\t' << length[j] << '\t' << seed_count[j] << '\t' << restarts[j] << '\n';
-                if (occurrences) print_places(g, j, o, t, places, want_coords ? coords : nullptr, rows ? place_rows : nullptr);
-            }
-            if (chain) {
-                std::cout << "C\t" << chain_score[v] << '\t' << chain_off[v + 1] - chain_off[v];
-                if (rows) print_row_set(chain_rows[0][v], chain_rows[1][v]);
-                if (by_row) {
-                    if (chosen[0][v] == 0xffffffffu) std::cout << "\t*";
-                    else std::cout << '\t' << chosen[0][v];
-                    std::cout << '\t' << chosen[1][v];
-                }
-                std::cout << '\n';
-                for (uint64_t i = chain_off[v]; i < chain_off[v + 1]; i++)
-                    std::cout << "A\t" << q_start[anchor_seed[i]] << '\t' << length[anchor_seed[i]] << '\t' << coords[2][anchor_place[i]]
-                              << '\t' << coords[3][anchor_place[i]] << '\n';
-                if (want_mapq) {
-                    std::cout << "Q\t" << (unsigned)quality[v] << '\t' << second[0][v];
-                    if (second_off[v + 1] == second_off[v]) std::cout << "\t*\t*\n";
-                    else std::cout << '\t' << second[1][v] << '\t' << second[2][v] << '\n';
-                }
-                if (align && aligned[1][v] == FBG_ALIGN_NONE) std::cout << "G\t*\n";
-                else if (align) {
-                    std::cout << "G\t" << aligned[0][v] << '\t' << aligned[1][v] << '\t' << aligned[2][v] << '\t' << aligned[3][v];
-                    if (cigar) {
-                        std::cout << '\t';
-                        print_runs(std::cout, cigar_ops, cigar_off[v], cigar_off[v + 1]);
-                    }
-                    std::cout << '\n';
-                }
-                if (graph_align && on_graph[0][v] == FBG_ALIGN_NONE) std::cout << "H\t*\n";
-                else if (graph_align) {
-                    std::cout << "H\t" << on_graph[0][v] << '\t' << g.ids[on_graph[1][v]] << '\t' << on_graph[2][v] << '\t'
-                              << g.ids[on_graph[3][v]] << '\t' << on_graph[4][v] << '\t';
-                    for (uint64_t i = path_off[v]; i < path_off[v + 1]; i++) std::cout << '>' << g.ids[path_nodes[i]];
-                    if (graph_cigar) {
-                        std::cout << '\t';
-                        print_runs(std::cout, gcigar_ops, gcigar_off[v], gcigar_off[v + 1]);
-                    }
-                    std::cout << '\n';
-                    if (have_gaf) {
-                        const uint64_t k = v < np ? v : v - np, L = off[k + 1] - off[k];
-                        uint64_t plen = 0, match = 0, cols = 0;
-                        gaf << "read" << k << '\t' << L << "\t0\t" << L << '\t' << (v < np ? '+' : '-') << '\t';
-                        for (uint64_t i = path_off[v]; i < path_off[v + 1]; i++) {
-                            const uint32_t u = path_nodes[i];
-                            gaf << '>' << g.ids[u];
-                            plen += g.label_off[u + 1] - g.label_off[u];
-                        }
-                        for (uint64_t i = gcigar_off[v]; i < gcigar_off[v + 1]; i++) {
-                            cols += gcigar_ops[i] >> 4;
-                            if ((gcigar_ops[i] & 15) == FBG_CIGAR_EQ) match += gcigar_ops[i] >> 4;
-                        }
-                        const uint32_t ve = on_graph[3][v];
-                        gaf << '\t' << plen << '\t' << on_graph[2][v] << '\t'
-                            << plen - (g.label_off[ve + 1] - g.label_off[ve]) + on_graph[4][v] << '\t' << match << '\t' << cols
-                            << '\t' << (want_mapq ? (unsigned)quality[v] : 255u) << "\tNM:i:" << on_graph[0][v] << "\tcg:Z:";
-                        print_runs(gaf, gcigar_ops, gcigar_off[v], gcigar_off[v + 1]);
-                        gaf << '\n';
-                    }
-                }
-                if (pair_align && mate[1][v] == FBG_ALIGN_NONE) std::cout << "Y\t*\n";
-                else if (pair_align) {
-                    std::cout << "Y\t" << mate[0][v] << '\t' << mate[1][v] << '\t' << mate[2][v] << '\t' << mate[3][v] << '\t';
-                    if (mate[4][v] == FBG_ALIGN_NONE) std::cout << "*\n";
-                    else std::cout << mate[4][v] << '\n';
-                }
-            }
-        };
-        for (uint64_t k = 0; k < np; k++) {
-            const uint64_t ns = seed_off[k + 1] - seed_off[k];
-            const uint64_t nr = strands ? seed_off[np + k + 1] - seed_off[np + k] : 0;
+// ---- output -----------------------------------------------------------------------------------------------------------------
+
+struct Printer {
+    const LocateOptions &o;
+    const XgfaGraph &g;
+    const Reads &r;
+    const Results &x;
+    std::ostream &gaf;
+
+    void places(uint64_t k, bool rows) const
+    {
+        const Places &p = x.places;
+        const std::vector<uint64_t> *const off[2] = {&p.end_off, &p.start_off}, *const total[2] = {&p.end_total, &p.start_total};
+        print_places(g, k, off, total, p.at, o.have_msa && o.occurrences ? p.coords : nullptr, rows ? p.rows : nullptr);
+    }
+
+    // the S / E / B lines of virtual read v
+    void seeds(uint64_t v) const
+    {
+        const Seeds &s = x.seeds;
+        for (uint64_t j = s.off[v]; j < s.off[v + 1]; j++) {
+            std::cout << "S\t" << s.q_start[j] << '\t' << s.length[j] << '\t' << s.count[j] << '\t' << x.places.restarts[j] << '\n';
+            if (o.occurrences) places(j, o.rows);
+        }
+    }
+
+    // its C / A lines
+    void chain(uint64_t v) const
+    {
+        const Chains &c = x.chains;
+        std::cout << "C\t" << c.score[v] << '\t' << c.off[v + 1] - c.off[v];
+        if (o.rows) print_row_set(c.rows[0][v], c.rows[1][v]);
+        if (o.by_row) {
+            if (c.chosen[0][v] == 0xffffffffu) std::cout << "\t*";
+            else std::cout << '\t' << c.chosen[0][v];
+            std::cout << '\t' << c.chosen[1][v];
+        }
+        std::cout << '\n';
+        for (uint64_t i = c.off[v]; i < c.off[v + 1]; i++)
+            std::cout << "A\t" << x.seeds.q_start[c.anchor_seed[i]] << '\t' << x.seeds.length[c.anchor_seed[i]] << '\t'
+                      << x.places.coords[2][c.anchor_place[i]] << '\t' << x.places.coords[3][c.anchor_place[i]] << '\n';
+    }
+
+    // its Q line
+    void mapq(uint64_t v) const
+    {
+        const Mapq &q = x.mapq;
+        std::cout << "Q\t" << (unsigned)q.quality[v] << '\t' << q.second[0][v];
+        if (q.second_off[v + 1] == q.second_off[v]) std::cout << "\t*\t*\n";
+        else std::cout << '\t' << q.second[1][v] << '\t' << q.second[2][v] << '\n';
+    }
+
+    // its G line
+    void row_alignment(uint64_t v) const
+    {
+        const RowAlign &a = x.row;
+        if (a.at[1][v] == FBG_ALIGN_NONE) { std::cout << "G\t*\n"; return; }
+        std::cout << "G\t" << a.at[0][v] << '\t' << a.at[1][v] << '\t' << a.at[2][v] << '\t' << a.at[3][v];
+        if (o.cigar) {
+            std::cout << '\t';
+            print_runs(std::cout, a.cigar.ops, a.cigar.off[v], a.cigar.off[v + 1]);
+        }
+        std::cout << '\n';
+    }
+
+    // its H line with the path; false: H and *
+    bool graph_alignment(uint64_t v) const
+    {
+        const GraphAlign &a = x.graph;
+        if (a.at[0][v] == FBG_ALIGN_NONE) { std::cout << "H\t*\n"; return false; }
+        std::cout << "H\t" << a.at[0][v] << '\t' << g.ids[a.at[1][v]] << '\t' << a.at[2][v] << '\t' << g.ids[a.at[3][v]] << '\t' << a.at[4][v]
+                  << '\t';
+        for (uint64_t i = a.path_off[v]; i < a.path_off[v + 1]; i++) std::cout << '>' << g.ids[a.path_nodes[i]];
+        if (o.graph_cigar) {
+            std::cout << '\t';
+            print_runs(std::cout, a.cigar.ops, a.cigar.off[v], a.cigar.off[v + 1]);
+        }
+        std::cout << '\n';
+        return true;
+    }
+
+    // the GAF record of that H line
+    void gaf_record(uint64_t v) const
+    {
+        const GraphAlign &a = x.graph;
+        const uint64_t k = v < r.np ? v : v - r.np, L = r.off[k + 1] - r.off[k];
+        uint64_t plen = 0, match = 0, cols = 0;
+        gaf << "read" << k << '\t' << L << "\t0\t" << L << '\t' << (v < r.np ? '+' : '-') << '\t';
+        for (uint64_t i = a.path_off[v]; i < a.path_off[v + 1]; i++) {
+            const uint32_t u = a.path_nodes[i];
+            gaf << '>' << g.ids[u];
+            plen += g.label_off[u + 1] - g.label_off[u];
+        }
+        for (uint64_t i = a.cigar.off[v]; i < a.cigar.off[v + 1]; i++) {
+            cols += a.cigar.ops[i] >> 4;
+            if ((a.cigar.ops[i] & 15) == FBG_CIGAR_EQ) match += a.cigar.ops[i] >> 4;
+        }
+        const uint32_t ve = a.at[3][v];
+        gaf << '\t' << plen << '\t' << a.at[2][v] << '\t' << plen - (g.label_off[ve + 1] - g.label_off[ve]) + a.at[4][v] << '\t' << match
+            << '\t' << cols << '\t' << (o.mapq ? (unsigned)x.mapq.quality[v] : 255u) << "\tNM:i:" << a.at[0][v] << "\tcg:Z:";
+        print_runs(gaf, a.cigar.ops, a.cigar.off[v], a.cigar.off[v + 1]);
+        gaf << '\n';
+    }
+
+    // its Y line
+    void mate(uint64_t v) const
+    {
+        const Mates &m = x.mates;
+        if (m.read[1][v] == FBG_ALIGN_NONE) { std::cout << "Y\t*\n"; return; }
+        std::cout << "Y\t" << m.read[0][v] << '\t' << m.read[1][v] << '\t' << m.read[2][v] << '\t' << m.read[3][v] << '\t';
+        if (m.read[4][v] == FBG_ALIGN_NONE) std::cout << "*\n";
+        else std::cout << m.read[4][v] << '\n';
+    }
+
+    // every line of virtual read v
+    void block(uint64_t v) const
+    {
+        seeds(v);
+        if (!o.chain) return;
+        chain(v);
+        if (o.mapq) mapq(v);
+        if (o.align) row_alignment(v);
+        if (o.graph_align && graph_alignment(v) && o.have_gaf) gaf_record(v);
+        if (o.pair_align) mate(v);
+    }
+
+    // the T line of pattern k
+    void strand(uint64_t k) const
+    {
+        const uint8_t s = x.chains.strand[k];
+        std::cout << "T\t" << (s == FBG_STRAND_NONE ? '*' : s ? '-' : '+') << '\t' << x.chains.best_score[k];
+        if (o.mapq) std::cout << '\t' << (s == FBG_STRAND_NONE ? 0u : (unsigned)x.mapq.quality[s ? r.np + k : k]);
+        std::cout << '\n';
+    }
+
+    // the Z / W lines of pair p
+    void pair(uint64_t p) const
+    {
+        const Pairs &z = x.pairs;
+        const Mates &w = x.mates;
+        if (z.which[p] == 0xffu) std::cout << "Z\t*\n";
+        else std::cout << "Z\t" << (unsigned)z.which[p] << '\t' << z.out[0][p] << '\t' << z.out[1][p] << '\t' << z.out[2][p] << '\n';
+        if (o.pair_align && w.which[p] == 0xffu) std::cout << "W\t*\n";
+        else if (o.pair_align)
+            std::cout << "W\t" << (unsigned)w.which[p] << '\t' << w.out[0][p] << '\t' << w.out[1][p] << '\t' << w.out[2][p] << '\n';
+    }
+
+    // the answer of --seeds
+    int seeded() const
+    {
+        const std::vector<uint64_t> &off = x.seeds.off;
+        uint64_t found = 0;
+        for (uint64_t k = 0; k < r.np; k++) {
+            const uint64_t ns = off[k + 1] - off[k];
+            const uint64_t nr = o.strands ? off[r.np + k + 1] - off[r.np + k] : 0;
             std::cout << "Pattern? " << ns << " seeds found.\n";
-            if (ns + nr == 0 && error_on_not_found) {
+            if (ns + nr == 0 && o.error_on_not_found) {
                 std::cerr << "Pattern has no seed.\n";
                 std::cout.flush();
                 return EXIT_FAILURE;
             }
             found += ns + nr != 0;
             block(k);
-            if (strands) {
-                std::cout << "-\t" << nr << '\n';
-                block(np + k);
-                if (chain) {
-                    std::cout << "T\t" << (strand[k] == FBG_STRAND_NONE ? '*' : strand[k] ? '-' : '+') << '\t' << best_score[k];
-                    if (want_mapq) std::cout << '\t' << (strand[k] == FBG_STRAND_NONE ? 0u : (unsigned)quality[strand[k] ? np + k : k]);
-                    std::cout << '\n';
-                    if (want_pairs && k % 2) {
-                        const uint64_t p = k / 2;
-                        if (pair_which[p] == 0xffu) std::cout << "Z\t*\n";
-                        else std::cout << "Z\t" << (unsigned)pair_which[p] << '\t' << pair_out[0][p] << '\t' << pair_out[1][p] << '\t'
-                                       << pair_out[2][p] << '\n';
-                        if (pair_align && mate_which[p] == 0xffu) std::cout << "W\t*\n";
-                        else if (pair_align)
-                            std::cout << "W\t" << (unsigned)mate_which[p] << '\t' << mate_out[0][p] << '\t' << mate_out[1][p] << '\t'
-                                      << mate_out[2][p] << '\n';
-                    }
-                }
-            }
+            if (!o.strands) continue;
+            std::cout << "-\t" << nr << '\n';
+            block(r.np + k);
+            if (o.chain) strand(k);
+            if (o.chain && o.pairs && k % 2) pair(k / 2);
         }
-        std::cout << "Pattern? " << found << " out of " << np << " patterns seeded" << std::endl;
-        if (have_gaf) {
-            gaf.close();
-            if (!gaf) { std::cerr << "fbg_locate: cannot write " << gaf_path << "\n"; return EXIT_FAILURE; }
-        }
+        std::cout << "Pattern? " << found << " out of " << r.np << " patterns seeded" << std::endl;
         return EXIT_SUCCESS;
     }
-    for (uint64_t k = 0; k < np; k++) {
-        std::cout << "Pattern? " << count[k] << " occurrences found.\n";
-        if (count[k] == 0) {
-            std::cerr << "Pattern not found, pos = " << pos[k] << ".\n";
-            if (error_on_not_found) { std::cout.flush(); return EXIT_FAILURE; }
-        } else {
-            found++;
-            if (occurrences) print_places(g, k, o, t, places, want_coords ? coords : nullptr);
+
+    // the answer without --seeds, locate_patterns' own
+    int located() const
+    {
+        uint64_t found = 0;
+        for (uint64_t k = 0; k < r.np; k++) {
+            std::cout << "Pattern? " << x.located.count[k] << " occurrences found.\n";
+            if (x.located.count[k] == 0) {
+                std::cerr << "Pattern not found, pos = " << x.located.pos[k] << ".\n";
+                if (o.error_on_not_found) { std::cout.flush(); return EXIT_FAILURE; }
+            } else {
+                found++;
+                if (o.occurrences) places(k, false);
+            }
         }
+        std::cout << "Pattern? " << found << " out of " << r.np << " patterns found" << std::endl;
+        return EXIT_SUCCESS;
     }
-    std::cout << "Pattern? " << found << " out of " << np << " patterns found" << std::endl;
+};
+
+int main(int argc, char **argv)
+{
+    LocateOptions o;
+    std::string error;
+    if (!parse_locate_options(argc, argv, o, error)) return usage(error);
+    if (o.help) { usage("pattern search in a founder graph"); return EXIT_SUCCESS; }
+
+    std::ofstream gaf;
+    if (o.have_gaf) {
+        gaf.open(o.gaf_path, std::ios::binary | std::ios::trunc);
+        if (!gaf) return fail("cannot write " + o.gaf_path);
+    }
+    XgfaGraph g;
+    Msa msa;
+    std::vector<uint64_t> bounds;
+    Reads r;
+    if (!read_xgfa_graph(o.graph, g, error) || (o.have_msa && !read_msa_of_graph(o, msa, bounds, error)) || !read_patterns(o, r, error))
+        return fail(error);
+    if (o.pairs && r.np % 2) return usage("--pairs takes an even number of patterns, mates interleaved");
+
+    Results x;
+    {
+        Engine e;
+        if (fbg_ctx_create(0, &e.ctx) != FBG_OK) return fail(fbg_last_error(nullptr));
+        int rc = build_index(e, o, g, msa, bounds, error);
+        if (!error.empty()) return fail(error);
+        if (rc == FBG_OK) rc = run_stages(e.ix, o, r, x);
+        if (rc != FBG_OK) return fail(fbg_last_error(e.ctx));
+    }
+    const Printer out{o, g, r, x, gaf};
+    if (!o.seeds) return out.located();
+    if (out.seeded() != EXIT_SUCCESS) return EXIT_FAILURE;
+    if (o.have_gaf) {
+        gaf.close();
+        if (!gaf) return fail("cannot write " + o.gaf_path);
+    }
     return EXIT_SUCCESS;
 }
